@@ -58,7 +58,59 @@ def parse_args(argv=None):
                          "Cache: `roofline.hbm_only_frac`); <= --roofline-ring = skip")
     ap.add_argument("--roofline-rows", type=int, default=1 << 24,
                     help="rows gathered per bulk launch (16 Mi: 1.1 ms per launch; the ~9 us of ramp and tail of a launch are 3 %% of a 4 Mi one)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (f32 / f64, at most "
+                         "64 MB in all; rank 0's arrays): the envs' actions, next observations and transitions, the step's "
+                         "learn() losses and minibatch indices, and the main and target networks' state dicts. With the same "
+                         "arguments the inputs are the same from run to run, so two builds can be compared output for output "
+                         "(e.g. --dump-outputs bench_outputs/a)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def collect_outputs(L, loop, chunk) -> dict:
+    """What the timed path handed back in its last vector step, as host arrays (call after a synchronize): the environment
+    side (actions taken, next observations, the transition rows appended to the replay ring), the learner side (the U losses,
+    the U x B minibatch indices drawn) and the networks the updates left (the reference's state-dict names, BN statistics
+    included)."""
+    import numpy as np
+    out = {"actions": loop.actor.actions, "observations": loop.actor.obs, "transitions": loop.rows,
+           "losses": chunk.losses(), "minibatch_indices": chunk.idx}
+    for net, tag in ((0, "main"), (1, "target")):
+        views = dict(L.main_views() if net == 0 else L.target_views())
+        views.update(L.bn_views(net))
+        out.update({f"{tag}.{k}": v for k, v in views.items()})
+    host = {}
+    for k, v in out.items():
+        a = v.detach().cpu().numpy()
+        host[k] = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)   # (indices: exact in f64)
+    return host
+
+
+def dump_outputs(out_dir: str, arrays: dict, limit: int = DUMP_LIMIT_BYTES) -> dict:
+    """arrays -> out_dir/<name>.npy. Past `limit` bytes in all, every array larger than an equal share of the limit is
+    replaced by a fixed sample of its elements (flattened, seeded by its name, in index order), so that the files of two
+    runs still line up element for element."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    share = (limit - 256 * len(arrays)) // max(1, len(arrays))          # (256 B each for the .npy headers)
+    sampled = []
+    for name, a in arrays.items():
+        if total > limit and a.nbytes > share:
+            n = share // a.itemsize
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, size=n, replace=False))]
+            sampled.append(name)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    written = sum(os.path.getsize(os.path.join(out_dir, n + ".npy")) for n in arrays)
+    return {"dir": out_dir, "files": len(arrays), "bytes": written, "sampled": sampled}
 
 
 def launch_ranks(args) -> int:
@@ -202,6 +254,8 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    # (read before anything below launches on the same buffers: the gather bracket redraws chunk.idx)
+    dumped = dump_outputs(args.dump_outputs, collect_outputs(L, loop, chunk)) if args.dump_outputs and rank == 0 else None
     finite = bool(torch.isfinite(L.theta2).all().item())
     opt_steps = int(L.step_dev.item())
     episodes = loop.drain(final=True)            # every episode the E envs finished during warm-up + timed steps
@@ -245,6 +299,8 @@ def main():
                    "episodes_booked": len(episodes),
                    "episode_frames_booked": int(sum(e[1] for e in episodes))},
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if L.xgmi is not None:
         out["sanity"]["xgmi_allreduces"], out["sanity"]["xgmi_timed_out_waits"] = L.xgmi.status()
     if world > 1:

@@ -202,6 +202,17 @@ def main():
             g3_case(S, A, B, tag, False, out)
         np.savez_compressed(os.path.join(HERE, "g3_learn.npz"), **out)
 
+    # ---------------- G3 kuka again, with MKL in its processor-independent mode (MKL_CBWR=COMPATIBLE, set before the process
+    # starts): the same five updates give the same bits on any x86 host, whichever code path MKL would pick there by default.
+    # The torch port is held to these (tests/test_oracle_golden.py).   MKL_CBWR=COMPATIBLE python make_golden.py --only g3cnr
+    if only is not None and "g3cnr" in only:
+        if os.environ.get("MKL_CBWR") != "COMPATIBLE":
+            raise SystemExit("--only g3cnr: run with MKL_CBWR=COMPATIBLE in the environment")
+        full = {}
+        g3_case(21, 6, 256, "kuka", False, full)
+        out = {k: full[k] for k in ("kuka/dims", "kuka/losses5", "kuka/main5/hidden_layer.weight")}
+        np.savez_compressed(os.path.join(HERE, "g3_learn_cnr.npz"), **out)
+
     # ---------------- G3 at the network of the reference's own agent test: NAF(10, 5, 128), batch 64 -----------------------------
     # (tests/robotic_manipulator_rloa/naf_components/test_naf_algorithm.py:74 builds NAF(10, 5, 128, 0, 'cpu'); layer_size is a
     #  hyper-parameter of the framework, rl_framework.py:68-74)

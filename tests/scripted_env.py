@@ -59,9 +59,14 @@ class HangingEnvironment(ScriptedEnvironment):
         super().__init__(offset)
         import os
         self._n, self._hang_at = 0, hang_at
-        self._armed = bool(marker) and not os.path.exists(marker)
-        if self._armed:
-            open(marker, "w").close()
+        self._armed = False
+        if marker:
+            # O_EXCL: exactly one of the workers that start side by side creates the marker and arms itself
+            try:
+                os.close(os.open(marker, os.O_CREAT | os.O_EXCL | os.O_WRONLY))
+                self._armed = True
+            except FileExistsError:
+                pass
 
     def step(self, action):
         self._n += 1

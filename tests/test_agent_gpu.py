@@ -520,8 +520,9 @@ def test_world_8_rehearsal_in_one_process():
     above). xgmi_allreduce_kernel<8> — seven flags per rank, the rank-ordered sum of eight — bit-exact over 40 rounds with ranges
     pushed ahead; under `oneshot` and `merged` the gradient that leaves learn_rows() on every rank is the rank-ordered sum of the
     eight local gradients, and twelve updates leave eight bit-identical replicas with no timed-out wait."""
-    env = dict(os.environ, NAF_ROOT=ROOT, OMP_NUM_THREADS="2", GPU_MAX_HW_QUEUES="32")    # (a rank's launch waits for its peers' launches:
-    #                                                                                  every stream needs a hardware queue of its own)
+    # A rank's launch waits for its peers' launches, so every stream needs a hardware queue of its own. The test takes the process's
+    # queue count as the machine sets it: the worker's probe reports INPROC_SKIP where eight streams must share queues.
+    env = dict(os.environ, NAF_ROOT=ROOT, OMP_NUM_THREADS="2")
     env.pop("NAF_FUSE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "xgmi_inproc_worker.py"), "8"], env=env, capture_output=True,
                        text=True, timeout=600)
@@ -655,6 +656,34 @@ def test_bench_gpus2_launches_its_own_ranks():
         env["NAF_BENCH_REHEARSAL"] = "1"
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     _check_bench_line_n2(r, 5, rehearsal=torch.cuda.device_count() < 2)
+
+
+def test_bench_dump_outputs_same_arguments_same_arrays(tmp_path):
+    """bench.py --dump-outputs DIR: the arrays of the last timed step (f32 / f64 .npy), the same from run to run with the same
+    arguments, the step count the JSON line reports is --steps, and the learn() losses it wrote match the optimizer's step count."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "NAF_BENCH_REHEARSAL")}
+    lines, dirs = [], [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "7", "--warmup", "2", "--envs", "16",
+                            "--batch", "64", "--buffer", "20000", "--roofline-ring", "0", "--no-cpu-baseline", "--no-extras",
+                            "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
+    for out in lines:
+        assert out["steps"] == 7 and out["sanity"]["optimizer_steps"] == 16 * (7 + 2)
+        assert out["dumped_outputs"]["sampled"] == [] and out["dumped_outputs"]["bytes"] <= 64 << 20
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1])) and len(names) == lines[0]["dumped_outputs"]["files"]
+    for n in ["actions.npy", "observations.npy", "transitions.npy", "losses.npy", "minibatch_indices.npy",
+              "main.input_layer.weight.npy", "target.bn2.running_var.npy"]:
+        assert n in names, n
+    for n in names:
+        a, b = np.load(dirs[0] / n), np.load(dirs[1] / n)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
+        np.testing.assert_array_equal(a, b, err_msg=n)
+    assert np.load(dirs[0] / "actions.npy").shape == (16, 6) and np.load(dirs[0] / "losses.npy").shape == (16,)
+    idx = np.load(dirs[0] / "minibatch_indices.npy")
+    assert idx.shape == (16, 64) and (idx == np.trunc(idx)).all() and idx.min() >= 0 and idx.max() < 20000
 
 
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two MI355X (the gpurun box has one)")

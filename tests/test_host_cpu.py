@@ -276,7 +276,9 @@ def test_data_parallel_world2_gloo(tmp_path):
     with socket.socket() as sock:                      # a port nobody is using right now
         sock.bind(("127.0.0.1", 0))
         port = str(sock.getsockname()[1])
-    env = dict(os.environ, NAF_ROOT=ROOT, MASTER_ADDR="127.0.0.1", MASTER_PORT=port, OMP_NUM_THREADS="2")
+    # NAF_DP_SHARE_GPU=1: on a host with one GPU every rank may select cuda:0 (parallel.init_distributed), not cuda:LOCAL_RANK
+    env = dict(os.environ, NAF_ROOT=ROOT, MASTER_ADDR="127.0.0.1", MASTER_PORT=port, OMP_NUM_THREADS="2",
+               NAF_DP_SHARE_GPU="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                         "--master-addr", "127.0.0.1", "--master-port", port, str(script)],
                        env=env, capture_output=True, text=True, timeout=300)
@@ -318,7 +320,9 @@ def test_tick_agreement_three_ranks_gloo(tmp_path):
     with socket.socket() as sock:
         sock.bind(("127.0.0.1", 0))
         port = str(sock.getsockname()[1])
-    env = dict(os.environ, NAF_ROOT=ROOT, MASTER_ADDR="127.0.0.1", MASTER_PORT=port, OMP_NUM_THREADS="1")
+    # NAF_DP_SHARE_GPU=1: on a host with one GPU every rank may select cuda:0 (parallel.init_distributed), not cuda:LOCAL_RANK
+    env = dict(os.environ, NAF_ROOT=ROOT, MASTER_ADDR="127.0.0.1", MASTER_PORT=port, OMP_NUM_THREADS="1",
+               NAF_DP_SHARE_GPU="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=3",
                         "--master-addr", "127.0.0.1", "--master-port", port, str(script)],
                        env=env, capture_output=True, text=True, timeout=300)
@@ -346,6 +350,24 @@ def test_bench_cli_refuses_to_fake_a_multi_gpu_run():
     d = bench.parse_args([])
     assert d.gpus == 1 and d.batch == 256 and d.buffer == 1_000_000 and d.envs == 64 and d.robot == "kuka"
     assert json.dumps({"roofline": None}) and bench.pmc_traffic(-1, -1) == (None, None)
+
+
+def test_bench_dump_outputs_writes_npy_within_the_limit(tmp_path):
+    """bench.dump_outputs: one .npy per array; past the limit an oversized array becomes a fixed sample of its elements, the
+    same sample in every run, and the files stay within the limit."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(3)
+    arrays = {"small": rng.random((4, 5)).astype(np.float32), "big": rng.random(3_000_000)}
+    info = [bench.dump_outputs(str(tmp_path / d), arrays, limit=4 << 20) for d in ("a", "b")]
+    assert info[0]["sampled"] == ["big"] and info[0]["files"] == 2 and info[0]["bytes"] <= 4 << 20
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "small.npy"), arrays["small"])
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float64 and a.size == ((4 << 20) - 2 * 256) // 2 // 8 and np.isin(a, arrays["big"]).all()
+    np.testing.assert_array_equal(a, b)
+    info = bench.dump_outputs(str(tmp_path / "c"), arrays)                  # 24 MB: under the default 64 MB, written whole
+    assert info["sampled"] == [] and np.load(tmp_path / "c" / "big.npy").shape == (3_000_000,)
+    assert bench.parse_args(["--steps", "3", "--dump-outputs", "x"]).dump_outputs == "x"
 
 
 def test_pybullet_environment_adapter_with_fake_simulator(monkeypatch):

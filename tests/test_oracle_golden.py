@@ -5,7 +5,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, G3_ORACLE_TAGS, g3_case, load_group
+from conftest import GOLDEN, G3_ORACLE_TAGS, ROOT, g3_case, load_group
 from oracle import naf_oracle as O
 
 
@@ -189,27 +189,50 @@ def test_sampler_restatement_properties():
     assert [int(x) for x in v] == [0x408f276d, 0x41c83b0e, 0xa20bc7c6, 0x6d5451fd]
 
 
-def test_torch_port_matches_reference_golden():
+_PORT_LEARN5 = r"""
+import sys
+import numpy as np
+import torch
+sys.path[:0] = sys.argv[2:4]
+from oracle.torch_cpu_port import TorchCpuAgent
+from synth_data import make_transitions
+torch.set_num_threads(8)                        # (make_golden.py's)
+S, A, B = 21, 6, 256
+agent = TorchCpuAgent(S, A, 256, B, 1000, seed=0)
+st, ac, rw, ns, dn = make_transitions(5 * B, S, A, seed=7)
+for k in range(5):
+    sl = slice(k * B, (k + 1) * B)
+    agent.learn((torch.from_numpy(st[sl]), torch.from_numpy(ac[sl]).long(), torch.from_numpy(rw[sl, None]),
+                 torch.from_numpy(ns[sl]), torch.from_numpy(dn[sl, None])))
+np.savez(sys.argv[1], losses5=np.array(agent.losses), w5=agent.main.p["hidden_layer.weight"].detach().numpy())
+"""
+
+
+def test_torch_port_matches_reference_golden(tmp_path):
     """oracle/torch_cpu_port.py (the timed cpu_baseline) reproduces the unmodified reference's learn() losses and
-    its seed-0 initialisation (G3)."""
-    import torch
-    from oracle.torch_cpu_port import TorchCpuAgent, init_state_dict
-    from synth_data import make_transitions
+    its seed-0 initialisation (G3). The five updates run in a process of their own with MKL in its processor-independent
+    mode (MKL_CBWR=COMPATIBLE, 8 threads), as the reference ran for g3_learn_cnr.npz: by default MKL picks its code path by
+    processor, and the last bits of the weights after five Adam steps follow it."""
+    import subprocess
+    import sys
+    from oracle.torch_cpu_port import init_state_dict
     g = _npz("g3_learn.npz")
     S, A, B = [int(x) for x in g["kuka/dims"]]
     sd = init_state_dict(S, A, 256, 0)
     ref0 = load_group(g, "kuka/main0")
     for k in ("input_layer.weight", "hidden_layer.bias", "matrix_entries.weight", "value.bias"):
         np.testing.assert_array_equal(sd[k].numpy(), ref0[k])             # same RNG consumption order as the reference
-    agent = TorchCpuAgent(S, A, 256, B, 1000, seed=0)
-    st, ac, rw, ns, dn = make_transitions(5 * B, S, A, seed=7)
-    for k in range(5):
-        sl = slice(k * B, (k + 1) * B)
-        agent.learn((torch.from_numpy(st[sl]), torch.from_numpy(ac[sl]).long(), torch.from_numpy(rw[sl, None]),
-                     torch.from_numpy(ns[sl]), torch.from_numpy(dn[sl, None])))
-    np.testing.assert_allclose(agent.losses, g["kuka/losses5"], rtol=1e-5)
-    ref5 = load_group(g, "kuka/main5")
-    np.testing.assert_allclose(agent.main.p["hidden_layer.weight"].detach().numpy(), ref5["hidden_layer.weight"], atol=1e-6)
+    cnr = _npz("g3_learn_cnr.npz")
+    assert [int(x) for x in cnr["kuka/dims"]] == [S, A, B] == [21, 6, 256]
+    out = tmp_path / "port_learn5.npz"
+    env = dict(os.environ, MKL_CBWR="COMPATIBLE")
+    r = subprocess.run([sys.executable, "-c", _PORT_LEARN5, str(out), ROOT, GOLDEN], env=env, capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    got = np.load(out)
+    np.testing.assert_allclose(got["losses5"], g["kuka/losses5"], rtol=1e-5)
+    np.testing.assert_allclose(got["losses5"], cnr["kuka/losses5"], rtol=1e-5)
+    np.testing.assert_allclose(got["w5"], cnr["kuka/main5/hidden_layer.weight"], atol=1e-6)
 
 
 @pytest.mark.parametrize("B,n", [(100, 60), (1000, 12), (2560, 4)])

@@ -5,11 +5,10 @@ by plain pointers (naf_xgmi_connect_local) instead of hipIpc. Everything else is
 its seven flags per rank and the rank-ordered sum of eight, the finish launch's early pushes to seven peers, the exchange inside the
 finish launch (`merged`), slots double-buffered by epoch parity, the norm partials, 1 / 8 folded into the clip scale.
 
-    GPU_MAX_HW_QUEUES=32 python tests/xgmi_inproc_worker.py [world=8]
-A rank's launch waits for its peers' launches, so every stream needs a hardware queue of its own: the runtime's default is four
-queues per process, and torch hands out streams from a pool of 32 — with 32 queues every stream has its own (measured: 8 and 16
-queues leave some of the eight streams sharing one, deterministically; benchmarks/debug/inproc_probe.py). The worker first checks
-that its eight streams do run side by side (one all-reduce with a 1-s bound) and prints INPROC_SKIP if not.
+    python tests/xgmi_inproc_worker.py [world=8]
+A rank's launch waits for its peers' launches, so every stream needs a hardware queue of its own, and the process's queue count is
+set by the machine (GPU_MAX_HW_QUEUES), not by this worker. The worker first checks that its eight streams do run side by side
+(one all-reduce with a 1-s bound) and prints INPROC_SKIP if not.
 Prints INPROC_OK world=<W>; on success.
 """
 import os
@@ -53,7 +52,7 @@ def main():
         c.close(collective=False)
     if stuck:
         os.write(1, f"INPROC_SKIP the {W} streams of this process share hardware queues ({stuck} timed-out waits in the probe): "
-                    f"set GPU_MAX_HW_QUEUES=32;".encode())
+                    f"this process has fewer hardware queues than ranks;".encode())
         return
     # ---- 1. the all-reduce alone: random data, in place / out of place, ranges pushed ahead ----------------------------------
     comms = parallel.XgmiAllReduce.local_group(W, n, dev, timeout_s=20.0)
