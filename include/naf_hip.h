@@ -67,7 +67,7 @@ typedef struct {
 /* ---- library ------------------------------------------------------------------------------ */
 /* Bumped whenever a signature or a struct in this header changes; the ctypes host compares the library's answer with
  * the value in this header and refuses a mismatch (a stale .so would otherwise be called with wrong argument lists). */
-#define NAF_HIP_ABI_VERSION 34
+#define NAF_HIP_ABI_VERSION 35
 int naf_hip_abi_version(void);
 /* "gfx950" — the only architecture this library carries code objects for */
 const char* naf_hip_arch(void);
@@ -710,6 +710,19 @@ int naf_xgmi_timeouts_nowait(void* handle, uint64_t* timeouts);
  * release this rank's own slab. The host runs a barrier between the two, so no slab is released while a peer still maps it. */
 int naf_xgmi_disconnect(void* handle);
 int naf_xgmi_destroy(void* handle);
+
+/* ---- training state (ABI 35) ------------------------------------------------------------------------------------------ */
+/* One 64-bit digest per device segment {ptr, n_words} (32-bit words, ptr 4-byte aligned), in ONE read-only launch per
+ * NAF_DIGEST_MAX_SEGS segments: out[s] = sum over i < n_words of mix(i, word_i) mod 2^64 (csrc/state_digest.hip states mix).
+ * The sum is commutative, so the digest does not depend on the grid or on the order the workgroups run in; a changed word
+ * always changes it. `segs` is HOST memory, `out` DEVICE memory (n_seg words, zeroed here on the stream first).
+ * blocks_per_seg <= 0: sized from the longest segment. */
+#define NAF_DIGEST_MAX_SEGS 32
+typedef struct {
+    const void* ptr;
+    uint64_t n_words;
+} naf_digest_seg_t;
+int naf_state_digest(const naf_digest_seg_t* segs, int n_seg, uint64_t* out, int blocks_per_seg, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,13 +14,14 @@ from __future__ import annotations
 import json
 import os
 import random
+import shutil
 import time
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _lib, training_state
 from ..engine import DeviceEnvLoop, EpisodeLedger, TimestepGraph, UpdateChunk
 from ..learner import ActPath, Learner
 from ..utils.exceptions import MissingWeightsFile
@@ -58,10 +59,11 @@ class NAFAgent:
     def __init__(self, environment, state_size: int, action_size: int, layer_size: int, batch_size: int,
                  buffer_size: int, learning_rate: float, tau: float, gamma: float, update_freq: int, num_updates: int,
                  checkpoint_frequency: int, device, seed: int, *, p_mode="hadamard", action_mode="trunc_int",
-                 data_parallel: Optional[bool] = None, use_graph: bool = True) -> None:
+                 data_parallel: Optional[bool] = None, use_graph: bool = True, save_training_state: bool = False) -> None:
         """Positional arguments as the reference (naf_algorithm.py:27-41). Keyword-only extras default to the
         reference's behaviour. data_parallel=None: all-reduce gradients iff torch.distributed is initialised with
-        more than one rank."""
+        more than one rank. save_training_state: run() and run_vectorized() write checkpoints/{ep}/training_state.pt beside
+        weights.p at every checkpoint (resume with load_training_state + run(..., resume=True))."""
         _lib.require_gpu()                               # fail before touching the file system
         if torch.device(device).type != "cuda":
             raise _lib.NafHipError(f"NAFAgent needs the MI355X (got device={device}); there is no CPU fallback")
@@ -82,6 +84,9 @@ class NAFAgent:
             world = dist.get_world_size()
         self.world_size = world
         self.rank = dist.get_rank() if world > 1 else 0
+        self._save_ts = bool(save_training_state)
+        if self._save_ts:
+            training_state._require_one_gpu(self)
 
         self.learner = Learner(state_size, action_size, layer_size, batch_size, learning_rate, tau, gamma, self.device,
                                p_mode=_P_MODES[p_mode], world_size=world, process_group=pg)
@@ -118,6 +123,10 @@ class NAFAgent:
         self._row_pin = torch.zeros(1, L.lay.row_floats + 4, dtype=torch.float32).pin_memory()
         self._row_np = self._row_pin.numpy()
         self.last_run_stats: Optional[dict] = None    # counters of the most recent run_vectorized / run_host_vectorized
+        # a loaded training state: the action the saved run's last graph had drawn already, its last loss, its loop position
+        self._restored_ahead = None
+        self._restored_loss = None
+        self._resume_loop = None
 
     # ---- pretrained weights (naf_algorithm.py:91-127) ----------------------------------------------------------
     def _load_weights(self, path: str) -> None:
@@ -177,6 +186,8 @@ class NAFAgent:
                 ch.run(head_rows=1)
             self._last_loss_from = "chunk"
             return
+        # (the first step() behind load_training_state comes this way — the restore clears _fast — and draws its own next action)
+        self._restored_ahead = None
         if self._row_in_graph():
             m, row = self.memory, self._row_np[0]
             S, A = m.S, m.A
@@ -289,6 +300,14 @@ class NAFAgent:
 
     def act(self, state) -> np.ndarray:
         """Noisy clamped action for one state, main net in eval mode (naf_algorithm.py:158-178)."""
+        if self._restored_ahead is not None:
+            # the first act() behind load_training_state: the saved run's last step() had drawn this state's action already
+            obs, out = self._restored_ahead
+            self._restored_ahead = None
+            s32 = np.asarray(state, dtype=np.float32)
+            if s32.shape == obs.shape and (s32 == obs).all():
+                out = out.copy()
+                return out.squeeze() if out.size == 1 else out
         a = self._actor1 or self._actor()
         if a.host_io:
             ahead, self._ahead = self._ahead, None
@@ -344,6 +363,8 @@ class NAFAgent:
             return float(self._chunk.losses()[-1].item())
         if self._last_loss_from == "learn":
             return float(self._learn_loss.sum().item())
+        if self._last_loss_from == "restored":
+            return self._restored_loss
         raise _lib.NafHipError("last_loss(): no update has run yet")
 
     def soft_update(self, main_nn, target_nn) -> None:
@@ -360,10 +381,18 @@ class NAFAgent:
                 tp.data.copy_(self.tau * mp.data + (1. - self.tau) * tp.data)
 
     # ---- training loop with a host-side environment (naf_algorithm.py:228-292) ---------------------------------
-    def run(self, frames: int = 1000, episodes: int = 1000, verbose: bool = True) -> Dict[int, Tuple[float, int]]:
+    def run(self, frames: int = 1000, episodes: int = 1000, verbose: bool = True, *,
+            resume: bool = False) -> Dict[int, Tuple[float, int]]:
+        """resume=True: continue from the checkpoint load_training_state() read (same `frames`; `episodes` may be larger than the
+        saved run's budget) and return the whole scores dict, the restored episodes included."""
         logger.info('Training started')
         scores = {episode: (0, 0) for episode in range(1, episodes + 1)}
-        for episode in range(episodes):
+        first = 0
+        if resume:
+            first, done = training_state.resume_run(self._resume_loop, frames, episodes)
+            scores.update(done)
+            self._resume_loop = None
+        for episode in range(first, episodes):
             logger.info(f'Running Episode {episode + 1}')
             start = time.time()
             state = self.environment.reset(verbose)
@@ -397,10 +426,31 @@ class NAFAgent:
                 torch.save(self._cpu_state_dict(), f'checkpoints/{episode + 1}/weights.p')
                 with open(f'checkpoints/{episode + 1}/scores.txt', 'w') as f:
                     f.write(json.dumps(scores))
+                if self._save_ts:
+                    training_state.save(self, f'checkpoints/{episode + 1}/training_state.pt',
+                                        loop=training_state.run_position(episode + 1, frames, scores))
         if self.rank == 0:
             torch.save(self._cpu_state_dict(), self.MODEL_PATH)
             logger.info(f'Model has been successfully saved in {self.MODEL_PATH}')
         return scores
+
+    # ---- full training state (training_state.py) -----------------------------------------------------------------------
+    def save_training_state(self, path: str) -> None:
+        """Write everything the next step() of this run reads — learner, replay ring, noise counters, host RNGs, schedule
+        counters — to one file (torch.load(path, weights_only=True) reads it). Call it between step() calls."""
+        training_state.save(self, path)
+
+    def load_training_state(self, path: str) -> None:
+        """Restore a file of save_training_state() / a checkpoint's training_state.pt in place: the next step() / act() is the
+        one the saved run would have made. The whole file is checked (configuration: ValueError naming the field; every
+        section against its digest) before anything is written. A checkpoint's loop position is kept for run(resume=True) /
+        run_vectorized(resume=True)."""
+        self._resume_loop = training_state.load(self, path)
+
+    def training_state_digest(self) -> Dict[str, int]:
+        """{section: 64-bit digest} of the training state as it stands (naf_state_digest on the device): two agents with
+        equal digests continue the same way."""
+        return training_state.digest_sections(training_state.collect(self), self.device)
 
     def _cpu_state_dict(self):
         return type(self.qnetwork_main.state_dict())((k, v.cpu()) for k, v in self.qnetwork_main.state_dict().items())
@@ -424,7 +474,7 @@ class NAFAgent:
     def run_vectorized(self, vector_steps: Optional[int] = None, n_envs: int = 64, max_frames: int = 400,
                        noise_scale: float = 1.0, robot: str = "kuka", obstacle_jitter: float = 0.0, *,
                        episodes: Optional[int] = None, preset=None, variation=None, drain_every: int = 64,
-                       verbose: bool = False) -> dict:
+                       verbose: bool = False, resume: bool = False) -> dict:
         """NAFAgent.run (naf_algorithm.py:228-292) re-hosted for E synthetic arms on the GPU feeding the HBM replay ring;
         each vector step is followed by E * num_updates / update_freq learn() calls, i.e. the reference's update-to-data
         ratio. Everything stays on the device, no host sync per step.
@@ -441,7 +491,12 @@ class NAFAgent:
         Stops after `vector_steps` vector steps and/or once `episodes` episodes have finished (checked at the drains:
         training may run up to 2 x drain_every steps past the last episode; episodes finishing there are counted in
         `episodes_finished` but not recorded, as run() records exactly `episodes`).
-        Returns the counters of earlier rounds plus 'scores', 'episodes_finished', 'checkpoints'."""
+        Returns the counters of earlier rounds plus 'scores', 'episodes_finished', 'checkpoints'.
+
+        save_training_state (constructor): every checkpoint written at a drain inside the loop gets a training_state.pt holding
+        the state at that drain; resume=True continues from the one load_training_state() read — same n_envs, max_frames,
+        robot, drain_every (and noise / preset / variation); `episodes` may exceed the saved budget, `vector_steps` counts from
+        the saved run's start. Checkpoints booked by the final drain behind the loop get none (the loop has ended there)."""
         E = int(n_envs)
         if (E * self.num_updates) % self.update_freq != 0:
             raise ValueError("n_envs * num_updates must be a multiple of update_freq")
@@ -454,16 +509,39 @@ class NAFAgent:
         chunk = UpdateChunk(self.learner, self.memory, U, use_graph=self.use_graph)
         ledger = self._ledger(episodes)
         self.memory.flush()
-        logger.info(f'Training started ({E} environments on the device)')
-        t0 = time.time()
         updates = steps = 0
+        dropped = []                       # episodes the budget left unrecorded (a resume with a larger budget books them)
+        position = dict(n_envs=E, max_frames=int(max_frames), noise_scale=float(noise_scale), robot=robot,
+                        obstacle_jitter=float(obstacle_jitter), preset=None if preset is None else [float(v) for v in preset],
+                        variation=None if variation is None else [float(v) for v in variation], drain_every=loop.drain_every)
+
+        def add(score, frames):
+            if ledger.complete:
+                dropped.append((score, frames))
+            ledger.add(score, frames)
+            if verbose:
+                logger.info(f'Episode {ledger.count + ledger.extra}: Reward {score}  Number of frames {frames}')
 
         def book(final=False):
+            n_ck = len(ledger.checkpoints)
             for score, frames, *_ in loop.drain(final):
-                ledger.add(score, frames)
-                if verbose:
-                    logger.info(f'Episode {ledger.count + ledger.extra}: Reward {score}  Number of frames {frames}')
+                add(score, frames)
+            if self._save_ts and not final and len(ledger.checkpoints) > n_ck:
+                self._save_at_drain(loop, ledger, dropped, steps, updates, position, ledger.checkpoints[n_ck:])
 
+        if resume:
+            steps, updates, again = training_state.resume_vectorized(self._resume_loop, loop, ledger, position)
+            self._resume_loop = None
+            n_ck = len(ledger.checkpoints)
+            for score, frames in again:
+                add(score, frames)
+            if self._save_ts and len(ledger.checkpoints) > n_ck:
+                self._save_at_drain(loop, ledger, dropped, steps, updates, position, ledger.checkpoints[n_ck:])
+            if episodes is not None and ledger.complete:
+                vector_steps = steps       # (the restored ledger meets the budget already)
+        steps0 = steps
+        logger.info(f'Training started ({E} environments on the device)')
+        t0 = time.time()
         while vector_steps is None or steps < vector_steps:
             loop.step()
             steps += 1
@@ -481,14 +559,22 @@ class NAFAgent:
         if self.rank == 0:
             logger.info(f'Model has been successfully saved in {self.MODEL_PATH}')
         self.last_run_stats = {
-            "env_steps": steps * E, "updates": updates, "seconds": dt, "env_steps_per_s": steps * E / dt,
-            "last_loss": float(chunk.losses()[-1].item()) if updates else None, "scores": scores,
+            "env_steps": steps * E, "updates": updates, "seconds": dt, "env_steps_per_s": (steps - steps0) * E / dt,
+            "last_loss": float(chunk.losses()[-1].item()) if updates > 0 and steps > steps0 else None, "scores": scores,
             "episodes_finished": ledger.count + ledger.extra, "checkpoints": list(ledger.checkpoints)}
         return self.last_run_stats
 
+    def _save_at_drain(self, loop, ledger, dropped, steps, updates, position, new_checkpoints) -> None:
+        """training_state.pt of the checkpoints this drain wrote: one file, copied to the others"""
+        first = f'checkpoints/{new_checkpoints[0]}/training_state.pt'
+        training_state.save(self, first, loop=training_state.vectorized_position(loop, ledger, dropped, steps, updates, position))
+        for ep in new_checkpoints[1:]:
+            shutil.copyfile(first, f'checkpoints/{ep}/training_state.pt')
+
     # ---- training loop with E host environments in worker processes (PyBullet or any env with the reference protocol) --
     def run_host_vectorized(self, vec_env, vector_steps: Optional[int] = None, async_policy: bool = False,
-                            noise_scale: float = 1.0, *, episodes: Optional[int] = None, verbose: bool = False) -> dict:
+                            noise_scale: float = 1.0, *, episodes: Optional[int] = None, verbose: bool = False,
+                            resume: bool = False) -> dict:
         """vec_env: environment.vector_env.HostVectorEnv with E envs. Per vector step: batched act() on the GPU for the E
         current states -> workers step their envs -> E transitions packed into pinned memory -> one H2D copy -> HBM
         replay ring -> E * num_updates / update_freq learn() calls (the reference's update-to-data ratio).
@@ -498,6 +584,9 @@ class NAFAgent:
         Scores / checkpoints / model.p as run() writes them (see run_vectorized; here the rewards pass through the host
         every step, so an episode is booked — and a checkpoint written — in the very step it ends). The frame budget per
         episode is vec_env.max_frames. Stops after `vector_steps` steps and/or `episodes` finished episodes."""
+        if resume or self._save_ts:
+            raise _lib.NafHipError("run_host_vectorized keeps no training state: the worker processes hold the environments' "
+                                   "state (save and resume with run() or run_vectorized())")
         E = vec_env.E
         if (E * self.num_updates) % self.update_freq != 0:
             raise ValueError("n_envs * num_updates must be a multiple of update_freq")

@@ -31,7 +31,7 @@ from .environment.synthetic import SyntheticEnvironment
 from .naf_components.naf_algorithm import NAFAgent
 from .presets import ROBOT_PRESETS, pybullet_arguments, synthetic_initial_joints
 from .utils.exceptions import (ConfigurationIncomplete, EnvironmentNotInitialized, InvalidHyperParameter,
-                               InvalidManipulatorFile, InvalidNAFAgentParameter, NAFAgentNotInitialized)
+                               InvalidManipulatorFile, InvalidNAFAgentParameter, MissingWeightsFile, NAFAgentNotInitialized)
 from .utils.logger import Logger, get_global_logger
 
 logger = get_global_logger()
@@ -339,6 +339,29 @@ class ManipulatorFramework:
             return self.naf_agent.run_host_vectorized(vec, episodes=episodes, verbose=verbose)['scores']
         finally:
             vec.close()
+
+    def resume_training(self, episode: int, episodes: int, frames: Optional[int] = 500, verbose: bool = True,
+                        n_envs: Optional[int] = None):
+        """Continue the run_training() whose checkpoint `episode` holds a training_state.pt (an agent initialised with
+        save_training_state=True writes one beside weights.p) up to `episodes` episodes: the same run as if it had never
+        stopped. Returns the whole scores dict. frames / n_envs must be those of the saved run."""
+        if not self.naf_agent or not self.env:
+            raise ConfigurationIncomplete
+        if not isinstance(episode, int) or isinstance(episode, bool) or episode < 1:
+            raise InvalidNAFAgentParameter('The checkpoint episode received is not a positive integer')
+        if not isinstance(episodes, int) or isinstance(episodes, bool) or episodes < episode:
+            raise InvalidNAFAgentParameter('The episode budget received is not an integer at least as large as the checkpoint')
+        E = n_envs if n_envs is not None else self._n_envs
+        if E is not None and E > 1 and not isinstance(self.env, SyntheticEnvironment):
+            raise InvalidNAFAgentParameter('Training with environments in worker processes cannot be resumed')
+        path = f'checkpoints/{episode}/training_state.pt'
+        if not os.path.isfile(path):
+            raise MissingWeightsFile(f'{path} does not exist (initialize the agent with save_training_state=True)')
+        self.naf_agent.load_training_state(path)
+        if E is None or E <= 1:
+            return self.naf_agent.run(frames, episodes, verbose, resume=True)
+        return self.naf_agent.run_vectorized(episodes=episodes, n_envs=int(E), max_frames=frames, verbose=verbose, resume=True,
+                                             **self._device_env_arguments())['scores']
 
     def run_vectorized_training(self, vector_steps: int, n_envs: int = 64, max_frames: int = 400) -> dict:
         """Many-env training on the device-resident synthetic arms (BASELINE configs[1..4] shape) for a fixed number of
