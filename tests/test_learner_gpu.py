@@ -731,3 +731,10 @@ def test_policy_act_one_launch_matches_seven_launch_path(S, A, E, H, p_mode, mon
     np.testing.assert_allclose(a1.cpu().numpy(), a1_ref.cpu().numpy(), atol=2e-4)      # same z, sigma from nearly equal heads
     np.testing.assert_allclose(a2.cpu().numpy(), a2_ref.cpu().numpy(), atol=2e-4)
     assert not torch.equal(a1, a2)
+    # ... and both against the eval-mode forward in float64 (NAFAgent.act, naf_algorithm.py:170-173)
+    ev = O.net_forward_eval(O.cast_params(current_sd(L, 0), np.float64), obs.cpu().numpy().astype(np.float64))
+    h64 = np.concatenate([ev["mu_pre"], ev["l_pre"], ev["V"][:, None]], axis=1)
+    scale64 = max(1.0, float(np.abs(h64).max()))
+    for hh, aa in ((h, a0), (h_ref, a0_ref)):
+        np.testing.assert_allclose(hh.cpu().numpy(), h64, rtol=1e-4, atol=5e-5 * scale64)
+        np.testing.assert_allclose(aa.cpu().numpy(), ev["mu"], atol=5e-5)

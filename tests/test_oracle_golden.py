@@ -287,3 +287,59 @@ def test_g3_wide_layers_oracle(tag):
     got = [Or.learn(st[k * B:(k + 1) * B], ac[k * B:(k + 1) * B], rw[k * B:(k + 1) * B], ns[k * B:(k + 1) * B], dn[k * B:(k + 1) * B])
            for k in range(5)]
     np.testing.assert_allclose(got, g[f"{tag}/losses5"], rtol=5e-3)
+
+
+# ------------------------------------------------------------------------------------------------
+# oracle/learn_check.py: the float64 checker of tests/test_learn_f64_gpu.py, run on the float32 oracle
+# ------------------------------------------------------------------------------------------------
+def _standin_run(case, n_upd, defect_at=None, defect=None):
+    """Teacher-forced updates of the float32 oracle through check_update; yields (update, report)."""
+    from oracle import learn_check as C
+    from learn_cases import init_state, state_of_oracle, transitions
+    sd = init_state(case)
+    st, ac, rw, ns, _ = transitions(case)
+    pre = state_of_oracle(O.LearnerOracle(sd, p_mode=case.p_mode, dtype=np.float32))
+    for k in range(n_upd):
+        sl = slice(k * case.B, (k + 1) * case.B)
+        batch = (st[sl], ac[sl], rw[sl], ns[sl])
+        dev = C.f32_standin(pre, batch, p_mode=case.p_mode, defect=defect if k == defect_at else None)
+        yield k, C.check_update(pre, batch, dev, p_mode=case.p_mode)
+        pre = {key: dev[key] for key in ("main", "target", "m", "v", "t")}
+
+
+def test_f64_checker_admits_the_f32_oracle_at_every_case():
+    """Every case of tests/learn_cases.py up to B = 4096 (two or three updates each): the float32 oracle, standing in for the
+    device, passes every check of check_update — the tolerances admit honest float32 arithmetic, ReLU elements that the two
+    precisions mask differently included — with few ambiguous elements, and the table drives the clip into both regimes."""
+    from learn_cases import CASES
+    clips = []
+    for case in CASES:
+        if case.B > 4096:
+            continue
+        for k, rep in _standin_run(case, 2 if case.B >= 1024 else 3):
+            assert not rep.failures, (case.name, k, rep.failures)
+            assert rep.meta["ambiguous"] <= 32, (case.name, k, rep.meta["ambiguous"])
+            clips.append(rep.meta["clip"])
+    assert min(clips) < 1.0 and max(clips) == 1.0
+
+
+@pytest.mark.parametrize("defect,cases,checks", [
+    ("drop_row", ["rows_b17", "rows_b1040", "rows_b2047", "rows_b4096"], ("grad",)),
+    ("ktail_twice", ["rows_b320", "rows_b1040", "rows_b2100"], ("grad",)),
+    ("scale_block", ["rows_b65", "rows_b2048_m1", "cols_b9"], ("grad",)),
+    ("zero_column", ["rows_h512_b1024_m1", "rows_h512_j9_b256"], ("grad",)),
+    ("norm", ["rows_b320", "rows_b4096", "unf_a12_b64_m1"], ("theta", "m")),
+])
+def test_f64_checker_rejects_planted_defects(defect, cases, checks):
+    """Defects planted in the float32 stand-in's second update (Adam's moments are then non-zero) are each rejected by the
+    check that is meant to catch them: a minibatch row left out of a weight gradient, a K-tail chunk counted twice, one block
+    1e-3 too large, one column of a 512-wide block zeroed, a norm 1 % high (caught by the optimizer check alone: Adam's
+    moments then mix the wrongly clipped gradient into the old ones)."""
+    from learn_cases import CASES
+    by_name = {c.name: c for c in CASES}
+    for name in cases:
+        reps = dict(_standin_run(by_name[name], 2, defect_at=1, defect=defect))
+        assert not reps[0].failures, (name, reps[0].failures)
+        assert reps[1].failed(*checks), (defect, name, reps[1].ratios)
+        if defect == "norm":
+            assert reps[1].meta["clip"] < 1.0 and reps[1].failed("norm_self")
