@@ -1,0 +1,104 @@
+"""Vectorized training rate of the kinematic chain environment (csrc/chain_env.hip) beside the stand-in's at the same joint
+count, and a launch loop of the two step kernels for `rocprofv3 --kernel-trace --stats`.
+
+  python benchmarks/chain_env_bench.py rate --urdf tests/golden/urdf/iiwa_like7.urdf --steps 4000 --warmup 100
+      env-steps/s of NAFAgent.run_vectorized, E = 64, B = 256: the chain environment, then the stand-in at the same A
+      (`--standin-only`: only the latter — what a tree without the chain environment can run)
+  rocprofv3 --kernel-trace --stats -d OUT -- python benchmarks/chain_env_bench.py kernels
+      1000 launches each of chain_env_step_kernel for standin8 (A = 8, E = 64) and long32, and of synth_env_step_kernel
+"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+URDF = os.path.join(ROOT, "tests", "golden", "urdf")
+
+
+def rate(a):
+    import torch
+    from robotic_manipulator_rloa_amd.environment.synthetic import SyntheticEnvironment
+    from robotic_manipulator_rloa_amd.naf_components.naf_algorithm import NAFAgent
+    dev = torch.device("cuda:0")
+    os.chdir(tempfile.mkdtemp())
+    out = {}
+
+    def run(tag, env, A, **kw):
+        agent = NAFAgent(env, 2 * A + 9, A, 256, a.batch, 1_000_000, 1e-3, 1e-3, 0.99, 1, 1, 10 ** 9, dev, 0)
+        agent.run_vectorized(a.warmup, n_envs=a.envs, max_frames=400, **kw)
+        r = agent.run_vectorized(a.steps, n_envs=a.envs, max_frames=400, **kw)
+        out[tag] = {"env_steps_per_s": round(r["env_steps_per_s"], 1), "updates": r["updates"], "seconds": round(r["seconds"], 4)}
+
+    if not a.standin_only:
+        from robotic_manipulator_rloa_amd.environment.kinematic import build_kinematic
+        n = a.joints
+        env = build_kinematic(os.path.abspath(a.urdf) if os.path.isabs(a.urdf) else os.path.join(ROOT, a.urdf), n - 1, [n],
+                              list(range(n)), [0.45, 0.3, 0.6], [0.35, 0.2, 0.45], [0.0, 0.6, 0.0, -1.2, 0.0, 0.8, 0.0][:n],
+                              [0.1] * n, 0.03)
+        for rep in range(a.repeats):
+            run(f"chain_{rep}", env, n, chain=env.model,
+                scene={"target": [0.45, 0.3, 0.6], "obstacle": [0.35, 0.2, 0.45]})
+            run(f"standin_{rep}", SyntheticEnvironment(n), n, robot="panda")
+    else:
+        for rep in range(a.repeats):
+            run(f"standin_{rep}", SyntheticEnvironment(a.joints), a.joints, robot="panda")
+    print(json.dumps({"envs": a.envs, "batch": a.batch, "steps": a.steps, "warmup": a.warmup, "joints": a.joints, **out}))
+
+
+def kernels(a):
+    import numpy as np
+    import torch
+    from robotic_manipulator_rloa_amd import _lib
+    from robotic_manipulator_rloa_amd.environment.urdf_chain import compile_chain, load_urdf
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    E, stream = a.envs, torch.cuda.current_stream().cuda_stream
+    for name, n in (("standin8", 8), ("long32", 32)):
+        model = compile_chain(load_urdf(os.path.join(URDF, name + ".urdf")), n - 1, list(range(n)), [], None, [0.1] * n, 0.03)
+        blob = np.ascontiguousarray(model.pack())
+        h = ctypes.c_void_p()
+        _lib.check(lib.naf_chain_env_create(blob.ctypes.data, int(blob.size), ctypes.byref(h)), "create")
+        S = 2 * n + 9
+        st = torch.zeros(E, lib.naf_chain_env_state_floats(h), device=dev)
+        obs, act = torch.zeros(E, S, device=dev), torch.randn(E, n, device=dev)
+        rows = torch.zeros(E, lib.naf_replay_row_floats(S, n), device=dev)
+        scene = (ctypes.c_float * 8)(0.4, 0.85, 0.71, 0.45, 0.55, 0.55, 0.0, 0.06)
+        _lib.check(lib.naf_chain_env_reset(h, st.data_ptr(), obs.data_ptr(), E, scene, 5, 0, stream), "reset")
+        for _ in range(a.launches):
+            _lib.check(lib.naf_chain_env_step(h, st.data_ptr(), act.data_ptr(), rows.data_ptr(), obs.data_ptr(), E, 5, None, 0, None, 0,
+                                              stream), "step")
+        torch.cuda.synchronize()
+        lib.naf_chain_env_destroy(h)
+    n, S = 8, 25
+    st = torch.zeros(E, lib.naf_synth_env_state_floats(n), device=dev)
+    obs, act, rows = torch.zeros(E, S, device=dev), torch.randn(E, n, device=dev), torch.zeros(E, 64, device=dev)
+    _lib.check(lib.naf_synth_env_reset(st.data_ptr(), obs.data_ptr(), E, n, 5, 0, None, 0, stream), "reset")
+    for _ in range(a.launches):
+        _lib.check(lib.naf_synth_env_step(st.data_ptr(), act.data_ptr(), rows.data_ptr(), obs.data_ptr(), E, n, 5, None, 0, None, 0,
+                                          stream), "step")
+    torch.cuda.synchronize()
+    print(json.dumps({"launches_each": a.launches, "envs": E}))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("what", choices=["rate", "kernels"])
+    ap.add_argument("--urdf", default=os.path.join("tests", "golden", "urdf", "iiwa_like7.urdf"))
+    ap.add_argument("--joints", type=int, default=7)
+    ap.add_argument("--envs", type=int, default=64)
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--steps", type=int, default=4000)
+    ap.add_argument("--warmup", type=int, default=100)
+    ap.add_argument("--repeats", type=int, default=2)
+    ap.add_argument("--launches", type=int, default=1000)
+    ap.add_argument("--standin-only", action="store_true")
+    a = ap.parse_args()
+    (rate if a.what == "rate" else kernels)(a)
+
+
+if __name__ == "__main__":
+    main()

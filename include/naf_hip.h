@@ -67,7 +67,7 @@ typedef struct {
 /* ---- library ------------------------------------------------------------------------------ */
 /* Bumped whenever a signature or a struct in this header changes; the ctypes host compares the library's answer with
  * the value in this header and refuses a mismatch (a stale .so would otherwise be called with wrong argument lists). */
-#define NAF_HIP_ABI_VERSION 35
+#define NAF_HIP_ABI_VERSION 36
 int naf_hip_abi_version(void);
 /* "gfx950" — the only architecture this library carries code objects for */
 const char* naf_hip_arch(void);
@@ -665,6 +665,66 @@ int naf_synth_env_step(float* env_state, const float* actions, float* out_rows, 
 int naf_synth_env_reset(float* env_state, float* obs, int E, int A, uint64_t seed, uint64_t counter,
                         const float* preset_host, int preset_floats, void* stream);
 int naf_synth_env_state_floats(int A);
+
+/* ---- kinematic environment of a URDF manipulator (ABI 36) ----------------------------------------------------------------
+ * E copies of the serial chain environment/urdf_chain.py compiles from the user's URDF, stepped on the device under the
+ * reference's environment rule (environment/environment.py:431-485: state layout, reward, terminal rule, velocity control
+ * of the involved joints, held joints). Kinematic — the commanded velocity is applied exactly for one 1/240 s tick, then the
+ * position limits — and NOT a port of Bullet: no dynamics, no mesh collision, no self-collision. See csrc/chain_env.hip;
+ * environment/kinematic.py is the float64 host twin.
+ *
+ * Chain model blob (float32, every count and index stored as a float; ChainModel.pack writes it, model_check reads it):
+ *   header, NAF_CHAIN_HEADER_FLOATS: [0] NAF_CHAIN_BLOB_VERSION  [1] A (driven joints = action size, 1 .. 64)  [2] segments
+ *     [3] observation slots (= A)  [4] end-effector frame  [5..7] end-effector point in that frame  [8] floats in the blob
+ *     [9..15] 0
+ *   A driven joints in action order, NAF_CHAIN_JOINT_FLOATS each: [0..8] pre-rotation, row-major 3 x 3  [9..11] pre-translation
+ *     [12..14] unit axis  [15] type, 0 revolute / 1 prismatic  [16] 1 = has position limits  [17] lower  [18] upper
+ *     [19] initial position  [20] half-width of the reset range  [21] observation slot reporting this joint, or -1  [22..23] 0
+ *     frame 0 = world; frame k + 1 = frame k . (pre-rotation, pre-translation) . motion of joint k: every constant transform
+ *     between two driven joints (joint origins, held / fixed / parked joints) is folded into the pre-transform on the host
+ *   A + 2 begin indices: the segments of frame f are [begin[f], begin[f + 1]), f = 0 .. A; begin[A + 1] = segments
+ *   segments sorted by frame, NAF_CHAIN_SEGMENT_FLOATS each: [0] frame  [1..3] a  [4..6] b (in that frame)  [7] capsule radius;
+ *     contact = distance(segment, obstacle centre) < radius + obstacle radius
+ *   A observation slots, 2 floats each: [0] driven joint (action index) whose position / velocity the slot reports, or -1:
+ *     a constant joint, position [1], velocity 0. Slot k reports joint INDEX k of the URDF (environment.py:442-444).
+ *
+ * env_state record of one env, naf_chain_env_state_floats floats = round_up(round_up(A + 9, 2) + 2, 4):
+ *   [0 .. A) driven joint positions by action index  [A .. A+3) target  [A+3 .. A+6) obstacle centre  [A+6] obstacle radius
+ *   [A+7] frame of the episode  [A+8] episodes finished  [round_up(A + 9, 2)] running score, ONE double  rest 0
+ * Every env carries its own target and obstacle: a caller may give each env its own scene by writing them there.
+ *
+ *   model_check : NAF_OK, NAF_ERR_ARG (null / shorter than a header) or the NAF_CHAIN_ERR_* of the first wrong field; pure
+ *                 host code
+ *   create      : checks the blob, uploads it once (the one allocation) and keeps A and the counts: no launch ever trusts a
+ *                 device blob the host has not checked. model_host is HOST memory.
+ *   reset       : scene_host = NAF_CHAIN_SCENE_FLOATS HOST floats [target xyz | obstacle xyz | obstacle jitter | obstacle
+ *                 radius]; joints start at init + U(-variation, +variation); obs [E][2A+9] receives the first observation
+ *   step        : naf_synth_env_step's contract towards the rest of the engine — transition rows, the next observation,
+ *                 per-env running score (double, step order), frame budget, auto-reset, one episode record per
+ *                 (step mod record_slots, env), the same Philox keying of the reset draws and of the obstacle jitter. */
+#define NAF_CHAIN_BLOB_VERSION 1
+#define NAF_CHAIN_HEADER_FLOATS 16
+#define NAF_CHAIN_JOINT_FLOATS 24
+#define NAF_CHAIN_SEGMENT_FLOATS 8
+#define NAF_CHAIN_SCENE_FLOATS 8
+#define NAF_CHAIN_ERR_VERSION (-11)
+#define NAF_CHAIN_ERR_SIZE (-12)
+#define NAF_CHAIN_ERR_COUNTS (-13)
+#define NAF_CHAIN_ERR_VALUE (-14)   /* a NaN or an infinity anywhere */
+#define NAF_CHAIN_ERR_EE (-15)
+#define NAF_CHAIN_ERR_JOINT (-16)
+#define NAF_CHAIN_ERR_SEGMENTS (-17) /* begin table not monotone, or a segment outside its frame's range (unsorted) */
+#define NAF_CHAIN_ERR_SLOTS (-18)
+typedef struct naf_chain_env naf_chain_env_t;
+int naf_chain_env_model_check(const float* model_host, int n_floats);
+int naf_chain_env_create(const float* model_host, int n_floats, naf_chain_env_t** out);
+int naf_chain_env_destroy(naf_chain_env_t* h);
+int naf_chain_env_state_floats(const naf_chain_env_t* h);
+int naf_chain_env_reset(naf_chain_env_t* h, float* env_state, float* obs, int E, const float* scene_host, uint64_t seed,
+                        uint64_t counter, void* stream);
+int naf_chain_env_step(naf_chain_env_t* h, float* env_state, const float* actions, float* out_rows, float* obs_next, int E,
+                       uint64_t seed, const uint64_t* counter_dev, int max_frames, naf_episode_record_t* records,
+                       int record_slots, void* stream);
 
 /* ---- one-shot gradient all-reduce over peer-mapped memory (no reference counterpart) ----------
  * The data-parallel exchange that follows loss.backward() (naf_algorithm.py:207-210 on every rank): sum of the flat

@@ -17,7 +17,7 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(CSRC, "libnaf_hip.so")
 SOURCES = ["lib.hip", "replay.hip", "naf_head.hip", "bn_relu.hip", "fused_layers.hip", "big_batch.hip", "gemm_bundle.hip", "optim.hip",
            "synth_env.hip", "xgmi_reduce.hip", "policy_act.hip", "step_path.hip", "naf_head_wide.hip",
-           "state_digest.hip"]
+           "state_digest.hip", "chain_env.hip"]
 HEADERS = ["common.h", "head_body.h", "bn_tile.h", "xgmi_dev.h", "adam_body.h", "bn2bwd_fold.h", "act_body.h", "moments_body.h", "sample_body.h", "replay_dev.h", os.path.join("..", "..", "include", "naf_hip.h")]
 
 P_HADAMARD, P_MATMUL = 0, 1
@@ -249,6 +249,12 @@ _PROTOS = {
     "naf_xgmi_disconnect": [_vp],
     "naf_xgmi_destroy": [_vp],
     "naf_state_digest": [_vp, _i, _vp, _i, _vp],
+    "naf_chain_env_model_check": [_vp, _i],
+    "naf_chain_env_create": [_vp, _i, C.POINTER(_vp)],
+    "naf_chain_env_destroy": [_vp],
+    "naf_chain_env_state_floats": [_vp],
+    "naf_chain_env_reset": [_vp, _vp, _vp, _i, _vp, _u64, _u64, _vp],
+    "naf_chain_env_step": [_vp, _vp, _vp, _vp, _vp, _i, _u64, _vp, _i, _vp, _i, _vp],
 }
 _RESTYPES = {"naf_hip_arch": C.c_char_p}
 EXPORTED_SYMBOLS = tuple(_PROTOS)

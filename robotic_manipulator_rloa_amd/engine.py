@@ -790,7 +790,8 @@ class EpisodeLedger:
 
 
 class DeviceEnvLoop:
-    """E synthetic manipulator envs living on the GPU (csrc/synth_env.hip) driven by the agent's policy.
+    """E manipulator envs living on the GPU, driven by the agent's policy: the synthetic stand-in (csrc/synth_env.hip) or, with
+    `chain`, E copies of the arm a URDF describes (csrc/chain_env.hip; environment/urdf_chain.py compiles the model).
 
     Episode records (`records=True`): the step kernel keeps every env's running score and frame count and writes one
     naf_episode_record_t per (vector step, env) into a ring of `drain_every` slots; every `drain_every` steps the ring is
@@ -804,10 +805,13 @@ class DeviceEnvLoop:
     def __init__(self, learner: Learner, replay: Optional[ReplayBuffer], n_envs: int, seed: int, max_frames: int = 400,
                  noise_scale: float = 1.0, use_graph: bool = True, robot: str = "kuka", obstacle_jitter: float = 0.0,
                  preset: Optional[List[float]] = None, variation: Optional[List[float]] = None, records: bool = False,
-                 drain_every: int = 64):
+                 drain_every: int = 64, chain=None, target=None, obstacle=None, obstacle_radius: float = 0.06):
         """replay=None: no transitions are appended (evaluation). preset: 14 floats [initial joint positions(8) | target |
         obstacle] instead of a named robot's. variation: per-joint half-width of the reset range (None: 0.1 everywhere,
-        the stand-in's historical value)."""
+        the stand-in's historical value).
+        chain: an environment.urdf_chain.ChainModel — the envs are E copies of that arm (csrc/chain_env.hip: the blob is checked
+        and uploaded once, here) in the scene target / obstacle / obstacle_radius / obstacle_jitter; robot, preset and variation
+        (the stand-in's) are then unused: initial positions and reset ranges are the model's."""
         self.L, self.replay, self.E = learner, replay, int(n_envs)
         lay, dev = learner.lay, learner.dev
         self.lib = learner.lib
@@ -815,17 +819,22 @@ class DeviceEnvLoop:
         self.max_frames = int(max_frames)
         self.noise_scale = float(noise_scale)
         self.actor = ActPath(learner, self.E, seed=self.seed ^ 0xA5A5A5A5)
-        if lay.A > 8:
+        self.chain, self._chain_env = chain, None
+        import ctypes
+        if chain is not None:
+            self._open_chain(chain, target, obstacle, obstacle_radius, obstacle_jitter)
+            nst = self.lib.naf_chain_env_state_floats(self._chain_env)
+        elif lay.A > 8:
             raise _lib.NafHipError(f"the on-device stand-in environment models arms of up to 8 joints (action_size {lay.A}): drive "
                                    "such an agent through run() / run_host_vectorized with a host environment")
-        nst = self.lib.naf_synth_env_state_floats(lay.A)
+        else:
+            nst = self.lib.naf_synth_env_state_floats(lay.A)
         self.env_state = torch.zeros(self.E, nst, dtype=torch.float32, device=dev)
         self.rows = torch.zeros(self.E, lay.row_floats, dtype=torch.float32, device=dev)
         self.step_ctr = torch.zeros(1, dtype=torch.int64, device=dev)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.use_graph = use_graph
         self.env_steps = 0
-        import ctypes
         base = list(preset) if preset is not None else list(self.PRESETS[robot])
         if len(base) != 14:
             raise ValueError("DeviceEnvLoop: preset = [initial joint positions(8) | target xyz | obstacle xyz]")
@@ -843,9 +852,33 @@ class DeviceEnvLoop:
             self._pin_i = 0
         self.reset()
 
+    def _open_chain(self, chain, target, obstacle, obstacle_radius, obstacle_jitter) -> None:
+        import ctypes
+        lay = self.L.lay
+        if chain.A != lay.A or chain.state_size != lay.S:
+            raise ValueError(f"DeviceEnvLoop: the chain model drives {chain.A} joints (state size {chain.state_size}), the agent "
+                             f"was built for action_size {lay.A} / state_size {lay.S}")
+        if target is None or obstacle is None or len(target) != 3 or len(obstacle) != 3:
+            raise ValueError("DeviceEnvLoop(chain=...): give target and obstacle as xyz")
+        blob = np.ascontiguousarray(chain.pack(), np.float32)
+        handle = ctypes.c_void_p()
+        check(self.lib.naf_chain_env_create(blob.ctypes.data, int(blob.size), ctypes.byref(handle)), "chain_env_create")
+        self._chain_env = handle
+        self.scene = [float(v) for v in target] + [float(v) for v in obstacle] + [float(obstacle_jitter), float(obstacle_radius)]
+        self._scene = (ctypes.c_float * 8)(*self.scene)
+
+    def __del__(self):
+        if getattr(self, "_chain_env", None) is not None:
+            self.lib.naf_chain_env_destroy(self._chain_env)
+            self._chain_env = None
+
     def reset(self) -> None:
-        check(self.lib.naf_synth_env_reset(ptr(self.env_state), ptr(self.actor.obs), self.E, self.L.lay.A, self.seed, 0,
-                                           self._preset, 23, stream_ptr()), "synth_env_reset")
+        if self._chain_env is not None:
+            check(self.lib.naf_chain_env_reset(self._chain_env, ptr(self.env_state), ptr(self.actor.obs), self.E, self._scene,
+                                               self.seed, 0, stream_ptr()), "chain_env_reset")
+        else:
+            check(self.lib.naf_synth_env_reset(ptr(self.env_state), ptr(self.actor.obs), self.E, self.L.lay.A, self.seed, 0,
+                                               self._preset, 23, stream_ptr()), "synth_env_reset")
         self.step_ctr.zero_()
         self._steps = self._copied = 0
         self._inflight = None
@@ -854,10 +887,15 @@ class DeviceEnvLoop:
     def _body(self) -> None:
         st = stream_ptr()
         self.actor.act(self.noise_scale)                                     # NAFAgent.act for E states
-        check(self.lib.naf_synth_env_step(ptr(self.env_state), ptr(self.actor.actions), ptr(self.rows),
-                                          ptr(self.actor.obs), self.E, self.L.lay.A, self.seed, ptr(self.step_ctr),
-                                          self.max_frames, ptr(self.records), self.drain_every if self.records is not None else 0,
-                                          st), "synth_env_step")   # environment.step
+        slots = self.drain_every if self.records is not None else 0
+        if self._chain_env is not None:
+            check(self.lib.naf_chain_env_step(self._chain_env, ptr(self.env_state), ptr(self.actor.actions), ptr(self.rows),
+                                              ptr(self.actor.obs), self.E, self.seed, ptr(self.step_ctr), self.max_frames,
+                                              ptr(self.records), slots, st), "chain_env_step")   # environment.step
+        else:
+            check(self.lib.naf_synth_env_step(ptr(self.env_state), ptr(self.actor.actions), ptr(self.rows),
+                                              ptr(self.actor.obs), self.E, self.L.lay.A, self.seed, ptr(self.step_ctr),
+                                              self.max_frames, ptr(self.records), slots, st), "synth_env_step")   # environment.step
         check(self.lib.naf_counter_add(ptr(self.step_ctr), 1, st), "counter_add")
         if self.replay is not None:
             check(self.lib.naf_replay_add_batch(self.replay.handle, ptr(self.rows), self.E, st), "replay_add_batch")

@@ -1,0 +1,346 @@
+"""URDF -> chain model of the kinematic environment (environment/kinematic.py on the host, csrc/chain_env.hip on the device).
+
+Standard library + numpy only: no torch, no HIP. Line numbers cited as environment.py:N are the reference's
+robotic_manipulator_rloa/environment/environment.py.
+
+The model keeps the reference's environment RULE for the arm a URDF names — state layout, reward, terminal rule, velocity
+control of the involved joints, held joints — with the commanded velocity applied exactly for one 1/240 s tick. It is NOT a
+port of Bullet: no dynamics (gravity, motor force, solver), no mesh collision, no self-collision.
+
+  frames     frame 0 is the world (= the root link's frame: the base sits at the origin, environment.py:280-282); frame k + 1
+             is the child link frame of driven joint k. Frame k + 1 = frame k . Pre_k . Motion_k(q_k), Pre_k being every constant
+             transform between the two (joint origins, constant joints), folded here.
+  segments   collision capsules, each in the frame of the last driven joint above it.
+  slots      observation slot k of the A position / velocity slots reports joint INDEX k (environment.py:442-444).
+"""
+from __future__ import annotations
+
+import hashlib
+import math
+import os
+import xml.etree.ElementTree as ET
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+
+from ..utils.exceptions import InvalidManipulatorFile
+
+# ---- blob layout (documented once, in include/naf_hip.h: "chain model blob") --------------------------------------------
+BLOB_VERSION = 1
+HEADER_FLOATS = 16
+JOINT_FLOATS = 24
+SEGMENT_FLOATS = 8
+SLOT_FLOATS = 2
+MAX_JOINTS = 64
+DT = 1.0 / 240.0                 # environment.py:481: one stepSimulation tick
+TARGET_THRESHOLD = 0.05          # environment.py:345-371
+OBSTACLE_RADIUS = 0.06           # the stand-in's (csrc/synth_env.hip)
+REVOLUTE, PRISMATIC = 0, 1
+_MOVABLE = ("revolute", "continuous", "prismatic")
+
+
+def rpy_matrix(rpy: Sequence[float]) -> np.ndarray:
+    """URDF convention: R = Rz(yaw) . Ry(pitch) . Rx(roll)."""
+    r, p, y = (float(v) for v in rpy)
+    cr, sr, cp, sp, cy, sy = math.cos(r), math.sin(r), math.cos(p), math.sin(p), math.cos(y), math.sin(y)
+    return np.array([[cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr],
+                     [sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr],
+                     [-sp, cp * sr, cp * cr]])
+
+
+def axis_rotation(axis: np.ndarray, q) -> np.ndarray:
+    """Rodrigues: I + sin q . K + (1 - cos q) . K^2 for a unit axis; q a scalar or an array (one matrix per element)."""
+    x, y, z = axis
+    K = np.array([[0.0, -z, y], [z, 0.0, -x], [-y, x, 0.0]])
+    q = np.asarray(q, float)[..., None, None]
+    return np.eye(3) + np.sin(q) * K + (1.0 - np.cos(q)) * (K @ K)
+
+
+@dataclass
+class UrdfLink:
+    name: str
+    inertial_origin: Optional[np.ndarray] = None     # xyz of <inertial><origin>, None without <inertial>
+    collision_radius: Optional[float] = None         # of a sphere / cylinder / capsule collision primitive
+
+
+@dataclass
+class UrdfJoint:
+    name: str
+    type: str
+    parent: str
+    child: str
+    xyz: np.ndarray
+    rot: np.ndarray
+    axis: np.ndarray
+    lower: float
+    upper: float
+
+    @property
+    def limited(self) -> bool:
+        return self.type != "continuous" and self.lower < self.upper
+
+
+@dataclass
+class Urdf:
+    path: str
+    links: Dict[str, UrdfLink]
+    joints: List[UrdfJoint]      # FILE ORDER = PyBullet's joint index; joint k's child link is link index k
+    root: str
+
+
+def _floats(text: Optional[str], n: int, default: Sequence[float], what: str, path: str) -> np.ndarray:
+    if text is None:
+        return np.array(default, float)
+    try:
+        v = [float(t) for t in text.split()]
+    except ValueError:
+        v = []
+    if len(v) != n or not all(math.isfinite(x) for x in v):
+        raise InvalidManipulatorFile(f"{path}: {what} = {text!r} is not {n} finite numbers")
+    return np.array(v, float)
+
+
+def load_urdf(path: str) -> Urdf:
+    if not str(path).lower().endswith(".urdf"):
+        raise InvalidManipulatorFile(f"{path}: only .urdf files are read by the kinematic environment "
+                                     f"(extension {os.path.splitext(str(path))[1] or 'missing'!r}; SDF is out of scope)")
+    if not os.path.isfile(path):
+        raise InvalidManipulatorFile(f"{path}: file not found")
+    try:
+        robot = ET.parse(path).getroot()
+    except ET.ParseError as e:
+        raise InvalidManipulatorFile(f"{path}: malformed XML ({e})") from e
+    if robot.tag != "robot":
+        raise InvalidManipulatorFile(f"{path}: the root element is <{robot.tag}>, not <robot>")
+    links: Dict[str, UrdfLink] = {}
+    for el in robot.findall("link"):
+        link = UrdfLink(el.get("name", ""))
+        inertial = el.find("inertial")
+        if inertial is not None:
+            o = inertial.find("origin")
+            link.inertial_origin = _floats(None if o is None else o.get("xyz"), 3, (0, 0, 0),
+                                           f"link {link.name} inertial origin xyz", path)
+        for geom in el.findall("collision/geometry"):
+            for kind in ("sphere", "cylinder", "capsule"):
+                g = geom.find(kind)
+                if g is not None and g.get("radius") is not None and link.collision_radius is None:
+                    link.collision_radius = float(_floats(g.get("radius"), 1, (0,), f"link {link.name} {kind} radius", path)[0])
+        links[link.name] = link
+    joints: List[UrdfJoint] = []
+    for el in robot.findall("joint"):
+        name, jtype = el.get("name", ""), el.get("type", "")
+        if jtype in ("floating", "planar"):
+            raise InvalidManipulatorFile(f"{path}: joint {name!r} is of type {jtype}, which a kinematic chain cannot hold "
+                                         "(revolute, continuous, prismatic and fixed are read)")
+        if jtype not in _MOVABLE + ("fixed",):
+            raise InvalidManipulatorFile(f"{path}: joint {name!r} has the unknown type {jtype!r}")
+        parent, child = el.find("parent"), el.find("child")
+        if parent is None or child is None or parent.get("link") not in links or child.get("link") not in links:
+            raise InvalidManipulatorFile(f"{path}: joint {name!r} does not name a parent and a child among the links")
+        o, a, lim = el.find("origin"), el.find("axis"), el.find("limit")
+        axis = _floats(None if a is None else a.get("xyz"), 3, (1, 0, 0), f"joint {name} axis", path)
+        norm = float(np.linalg.norm(axis))
+        if jtype in _MOVABLE and norm < 1e-12:
+            raise InvalidManipulatorFile(f"{path}: joint {name!r} has a zero axis")
+        joints.append(UrdfJoint(
+            name, jtype, parent.get("link"), child.get("link"),
+            _floats(None if o is None else o.get("xyz"), 3, (0, 0, 0), f"joint {name} origin xyz", path),
+            rpy_matrix(_floats(None if o is None else o.get("rpy"), 3, (0, 0, 0), f"joint {name} origin rpy", path)),
+            axis / norm if norm >= 1e-12 else np.array([1.0, 0.0, 0.0]),
+            float(_floats(None if lim is None else lim.get("lower"), 1, (0,), f"joint {name} lower limit", path)[0]),
+            float(_floats(None if lim is None else lim.get("upper"), 1, (0,), f"joint {name} upper limit", path)[0])))
+    children = {}
+    for j in joints:
+        if j.child in children:
+            raise InvalidManipulatorFile(f"{path}: link {j.child!r} is the child of two joints")
+        children[j.child] = j
+    roots = [n for n in links if n not in children]
+    if len(roots) != 1:
+        raise InvalidManipulatorFile(f"{path}: {len(roots)} root links ({', '.join(sorted(roots)) or 'a cycle'}): "
+                                     "a manipulator has exactly one")
+    return Urdf(str(path), links, joints, roots[0])
+
+
+@dataclass
+class ChainJoint:
+    index: int                   # URDF joint index
+    pre_rot: np.ndarray          # Pre_k's rotation (3 x 3)
+    pre_xyz: np.ndarray          # ... translation
+    axis: np.ndarray
+    type: int                    # REVOLUTE | PRISMATIC
+    limited: bool
+    lower: float
+    upper: float
+    init: float
+    variation: float
+    slot: int                    # observation slot that reports this joint (its URDF index when < A), else -1
+
+
+@dataclass
+class ChainSegment:
+    frame: int
+    a: np.ndarray
+    b: np.ndarray
+    radius: float
+
+
+@dataclass
+class ChainModel:
+    joints: List[ChainJoint]
+    segments: List[ChainSegment]             # sorted by frame
+    ee_frame: int
+    ee_point: np.ndarray
+    slots: List[tuple]                       # per observation slot: (driven index or -1, constant value)
+    reach: float                             # sum of the translation norms + the end-effector offset
+    source: str = ""
+    initial_positions_variation_range: Optional[List[float]] = None
+    _blob: Optional[np.ndarray] = field(default=None, repr=False, compare=False)
+
+    @property
+    def A(self) -> int:
+        return len(self.joints)
+
+    @property
+    def state_size(self) -> int:
+        return 2 * self.A + 9
+
+    def segment_begin(self) -> List[int]:
+        """begin[f] = index of frame f's first segment, f = 0 .. A + 1 (begin[A + 1] = the number of segments)."""
+        frames = [s.frame for s in self.segments]
+        return [int(np.searchsorted(frames, f, side="left")) for f in range(self.A + 2)]
+
+    def pack(self) -> np.ndarray:
+        """The flat float32 blob csrc/chain_env.hip reads (layout: include/naf_hip.h, "chain model blob")."""
+        if self._blob is not None:
+            return self._blob.copy()
+        A, n_seg = self.A, len(self.segments)
+        head = np.zeros(HEADER_FLOATS)
+        n = HEADER_FLOATS + JOINT_FLOATS * A + (A + 2) + SEGMENT_FLOATS * n_seg + SLOT_FLOATS * A
+        head[:9] = [BLOB_VERSION, A, n_seg, A, self.ee_frame, *self.ee_point, n]
+        parts = [head]
+        for j in self.joints:
+            rec = np.zeros(JOINT_FLOATS)
+            rec[0:9], rec[9:12], rec[12:15] = j.pre_rot.reshape(9), j.pre_xyz, j.axis
+            rec[15:22] = [j.type, 1.0 if j.limited else 0.0, j.lower, j.upper, j.init, j.variation, j.slot]
+            parts.append(rec)
+        parts.append(np.array(self.segment_begin(), float))
+        for s in self.segments:
+            parts.append(np.array([s.frame, *s.a, *s.b, s.radius]))
+        for src, const in self.slots:
+            parts.append(np.array([src, const]))
+        self._blob = np.concatenate(parts).astype(np.float32)
+        assert self._blob.size == n
+        return self._blob.copy()
+
+    def digest(self) -> str:
+        return hashlib.sha256(self.pack().tobytes()).hexdigest()
+
+
+def _compose(Ra, ta, Rb, tb):
+    return Ra @ Rb, ta + Ra @ tb
+
+
+def compile_chain(urdf: Urdf, endeffector_index: int, involved_joints: Sequence[int], fixed_joints: Sequence[int] = (),
+                  initial_joint_positions: Optional[Sequence[float]] = None,
+                  initial_positions_variation_range: Optional[Sequence[float]] = None, link_radius: float = 0.0) -> ChainModel:
+    path, joints, nj = urdf.path, urdf.joints, len(urdf.joints)
+    involved = [int(k) for k in involved_joints]
+    A = len(involved)
+    if not 1 <= A <= MAX_JOINTS:
+        raise InvalidManipulatorFile(f"{path}: {A} involved joints; the chain model holds 1 to {MAX_JOINTS}")
+    if len(set(involved)) != A:
+        raise InvalidManipulatorFile(f"{path}: involved_joints names a joint twice")
+    for what, idxs in (("involved_joints", involved), ("fixed_joints", fixed_joints), ("endeffector_index", [endeffector_index])):
+        for k in idxs:
+            if not 0 <= int(k) < nj:
+                raise InvalidManipulatorFile(f"{path}: {what} names joint index {k}; the file has joints 0 .. {nj - 1}")
+    for k in involved:
+        if joints[k].type not in _MOVABLE:
+            raise InvalidManipulatorFile(f"{path}: involved joint {k} ({joints[k].name!r}) is of type {joints[k].type}: "
+                                         "it cannot be driven")
+    held = {int(k) for k in fixed_joints} - set(involved)
+    init = [float(v) for v in (initial_joint_positions or [])]
+    var = [float(v) for v in (initial_positions_variation_range or [])]
+    action_of = {k: m for m, k in enumerate(involved)}            # environment.py:466-471: action m drives involved_joints[m]
+    joint_of_child = {j.child: k for k, j in enumerate(joints)}
+
+    def constant_value(k: int) -> float:
+        """A joint that is not driven: held at 0 (environment.py:474-478), an identity when of fixed type, else parked at its
+        initial value (environment.py:284-293 writes entry k to joint index k and nothing moves it afterwards)."""
+        if k in held or joints[k].type == "fixed":
+            return 0.0
+        return init[k] if k < len(init) else 0.0
+
+    def motion(j: UrdfJoint, q: float):
+        if j.type == "prismatic":
+            return np.eye(3), j.axis * q
+        if j.type == "fixed":
+            return np.eye(3), np.zeros(3)
+        return axis_rotation(j.axis, q), np.zeros(3)
+
+    def path_from_root(link: str) -> List[int]:
+        out = []
+        while link in joint_of_child:
+            k = joint_of_child[link]
+            out.append(k)
+            link = joints[k].parent
+        return out[::-1]
+
+    # the driven joints must form ONE serial chain: each one's nearest driven ancestor is the driven joint before it
+    for m, k in enumerate(involved):
+        above = [a for a in path_from_root(joints[k].parent) if a in action_of]
+        if above != involved[:m]:
+            raise InvalidManipulatorFile(
+                f"{path}: involved joint {k} ({joints[k].name!r}) does not continue the serial chain of involved_joints "
+                f"{involved}: the driven joints above it are {above}, expected {involved[:m]}")
+
+    # pose of every link's frame relative to the frame of the last driven joint above it: (frame, R, t)
+    pose = {urdf.root: (0, np.eye(3), np.zeros(3))}
+    chain_joints: List[Optional[ChainJoint]] = [None] * A
+    reach = 0.0
+    for k in sorted(range(nj), key=lambda k: len(path_from_root(joints[k].child))):
+        j = joints[k]
+        f, R, t = pose[j.parent]
+        R, t = _compose(R, t, j.rot, j.xyz)                       # the joint's origin in frame f
+        if k in action_of:
+            m = action_of[k]
+            chain_joints[m] = ChainJoint(
+                k, R, t, j.axis, PRISMATIC if j.type == "prismatic" else REVOLUTE, j.limited, j.lower if j.limited else 0.0,
+                j.upper if j.limited else 0.0, init[k] if k < len(init) else 0.0, var[k] if k < len(var) else 0.0,
+                k if k < A else -1)
+            reach += float(np.linalg.norm(t))
+            if j.type == "prismatic" and j.limited:
+                reach += max(abs(j.lower), abs(j.upper))
+            pose[j.child] = (m + 1, np.eye(3), np.zeros(3))
+        else:
+            Rm, tm = motion(j, constant_value(k))
+            R, t = _compose(R, t, Rm, tm)
+            pose[j.child] = (f, R, t)
+
+    ee_link = joints[int(endeffector_index)].child
+    if not any(a in action_of for a in path_from_root(ee_link)):
+        raise InvalidManipulatorFile(f"{path}: the end-effector link (joint index {endeffector_index}) does not descend from the "
+                                     f"chain of involved_joints {involved}")
+    f_ee, R, t = pose[ee_link]
+    inertial = urdf.links[ee_link].inertial_origin                  # getLinkState(...)[0] (environment.py:446): the centre of mass
+    ee_point = t + R @ inertial if inertial is not None else t.copy()
+    reach += float(np.linalg.norm(ee_point))
+
+    # one capsule per (link, child joint): link frame origin -> the child joint's origin; + the end-effector link's own
+    def radius_of(link_name: str) -> float:
+        r = urdf.links[link_name].collision_radius
+        return float(link_radius) if r is None else float(r)
+
+    segments: List[ChainSegment] = []
+    for j in joints:
+        f, R, t = pose[j.parent]
+        segments.append(ChainSegment(f, t.copy(), t + R @ j.xyz, radius_of(j.parent)))
+    segments.append(ChainSegment(f_ee, pose[ee_link][2].copy(), ee_point.copy(), radius_of(ee_link)))
+    segments.sort(key=lambda s: s.frame)                            # (stable: file order within a frame)
+
+    slots = []
+    for k in range(A):                                              # environment.py:442-444: slot k <- joint index k
+        slots.append((action_of[k], 0.0) if k in action_of else (-1, constant_value(k)))
+    return ChainModel(list(chain_joints), segments, f_ee, ee_point, slots, max(reach, 1e-6), source=os.path.basename(path),
+                      initial_positions_variation_range=None if initial_positions_variation_range is None else var)

@@ -474,7 +474,7 @@ class NAFAgent:
     def run_vectorized(self, vector_steps: Optional[int] = None, n_envs: int = 64, max_frames: int = 400,
                        noise_scale: float = 1.0, robot: str = "kuka", obstacle_jitter: float = 0.0, *,
                        episodes: Optional[int] = None, preset=None, variation=None, drain_every: int = 64,
-                       verbose: bool = False, resume: bool = False) -> dict:
+                       verbose: bool = False, resume: bool = False, chain=None, scene: Optional[dict] = None) -> dict:
         """NAFAgent.run (naf_algorithm.py:228-292) re-hosted for E synthetic arms on the GPU feeding the HBM replay ring;
         each vector step is followed by E * num_updates / update_freq learn() calls, i.e. the reference's update-to-data
         ratio. Everything stays on the device, no host sync per step.
@@ -496,7 +496,12 @@ class NAFAgent:
         save_training_state (constructor): every checkpoint written at a drain inside the loop gets a training_state.pt holding
         the state at that drain; resume=True continues from the one load_training_state() read — same n_envs, max_frames,
         robot, drain_every (and noise / preset / variation); `episodes` may exceed the saved budget, `vector_steps` counts from
-        the saved run's start. Checkpoints booked by the final drain behind the loop get none (the loop has ended there)."""
+        the saved run's start. Checkpoints booked by the final drain behind the loop get none (the loop has ended there).
+
+        chain (environment.urdf_chain.ChainModel) + scene (dict: target, obstacle, optionally obstacle_radius, obstacle_jitter):
+        the E envs are copies of that arm, stepped by csrc/chain_env.hip, instead of the stand-in's (robot / preset / variation /
+        obstacle_jitter are then unused). The saved loop position then carries the model's digest and the scene, and a resume
+        with another model is refused."""
         E = int(n_envs)
         if (E * self.num_updates) % self.update_freq != 0:
             raise ValueError("n_envs * num_updates must be a multiple of update_freq")
@@ -504,8 +509,9 @@ class NAFAgent:
             raise ValueError("run_vectorized: give vector_steps and/or episodes")
         U = E * self.num_updates // self.update_freq
         loop = DeviceEnvLoop(self.learner, self.memory, E, seed=self.seed + 104729 * self.rank, max_frames=max_frames,
-                             noise_scale=noise_scale, use_graph=self.use_graph, robot=robot, obstacle_jitter=obstacle_jitter,
-                             preset=preset, variation=variation, records=True, drain_every=drain_every)
+                             noise_scale=noise_scale, use_graph=self.use_graph, robot=robot, preset=preset, variation=variation,
+                             records=True, drain_every=drain_every,
+                             **{"obstacle_jitter": obstacle_jitter, **self._chain_arguments(chain, scene)})
         chunk = UpdateChunk(self.learner, self.memory, U, use_graph=self.use_graph)
         ledger = self._ledger(episodes)
         self.memory.flush()
@@ -514,6 +520,8 @@ class NAFAgent:
         position = dict(n_envs=E, max_frames=int(max_frames), noise_scale=float(noise_scale), robot=robot,
                         obstacle_jitter=float(obstacle_jitter), preset=None if preset is None else [float(v) for v in preset],
                         variation=None if variation is None else [float(v) for v in variation], drain_every=loop.drain_every)
+        if chain is not None:              # (files of stand-in runs keep exactly the keys they have)
+            position.update(chain=chain.digest(), scene=list(loop.scene))
 
         def add(score, frames):
             if ledger.complete:
@@ -563,6 +571,22 @@ class NAFAgent:
             "last_loss": float(chunk.losses()[-1].item()) if updates > 0 and steps > steps0 else None, "scores": scores,
             "episodes_finished": ledger.count + ledger.extra, "checkpoints": list(ledger.checkpoints)}
         return self.last_run_stats
+
+    @staticmethod
+    def _chain_arguments(chain, scene: Optional[dict]) -> dict:
+        """DeviceEnvLoop's keyword arguments for a chain model in a scene."""
+        if chain is None:
+            if scene is not None:
+                raise ValueError("scene describes the surroundings of a chain model: give chain too")
+            return {}
+        if not scene or "target" not in scene or "obstacle" not in scene:
+            raise ValueError("chain needs scene = {'target': xyz, 'obstacle': xyz[, 'obstacle_radius': r, 'obstacle_jitter': j]}")
+        unknown = set(scene) - {"target", "obstacle", "obstacle_radius", "obstacle_jitter"}
+        if unknown:
+            raise ValueError(f"scene: unknown keys {sorted(unknown)}")
+        return dict(chain=chain, target=scene["target"], obstacle=scene["obstacle"],
+                    obstacle_radius=float(scene.get("obstacle_radius", 0.06)),
+                    obstacle_jitter=float(scene.get("obstacle_jitter", 0.0)))
 
     def _save_at_drain(self, loop, ledger, dropped, steps, updates, position, new_checkpoints) -> None:
         """training_state.pt of the checkpoints this drain wrote: one file, copied to the others"""
@@ -688,7 +712,7 @@ class NAFAgent:
 
     def evaluate_vectorized(self, n_episodes: int, frames: int, n_envs: int = 64, noise_scale: float = 1.0,
                             robot: str = "kuka", obstacle_jitter: float = 0.0, preset=None, variation=None,
-                            drain_every: int = 32) -> List[Tuple[bool, int, bool]]:
+                            drain_every: int = 32, chain=None, scene: Optional[dict] = None) -> List[Tuple[bool, int, bool]]:
         """test_trained_model's episode loop for E device envs: one batched act() (eval-mode BatchNorm, noisy as every
         act() of the reference is) and one env step per vector step, nothing appended to the replay ring, no learning.
         Returns [(completed, last frame index, done)] — completed iff the episode ended `done` with reward == 250; an
@@ -697,8 +721,9 @@ class NAFAgent:
         E = int(n_envs)
         quota = self._episode_quota(int(n_episodes), E)
         loop = DeviceEnvLoop(self.learner, None, E, seed=self.seed + 15485863 + 104729 * self.rank, max_frames=frames,
-                             noise_scale=noise_scale, use_graph=self.use_graph, robot=robot, obstacle_jitter=obstacle_jitter,
-                             preset=preset, variation=variation, records=True, drain_every=drain_every)
+                             noise_scale=noise_scale, use_graph=self.use_graph, robot=robot, preset=preset, variation=variation,
+                             records=True, drain_every=drain_every,
+                             **{"obstacle_jitter": obstacle_jitter, **self._chain_arguments(chain, scene)})
         seen = np.zeros(E, np.int64)
         results = []
         while (seen < quota).any():

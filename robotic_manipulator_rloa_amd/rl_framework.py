@@ -14,6 +14,9 @@ Differences, all opt-in or forced by the image:
     synthetic stand-in, in E worker processes for anything else (PyBullet) — and produce what the one-env calls
     produce: the {episode: (score, last_frame)} dict, checkpoints/{episode}/weights.p + scores.txt, model.p, the logged
     test summary. Without n_envs every call is the reference's one-env loop, signature and behaviour untouched.
+  * initialize_kinematic_environment() takes initialize_environment()'s arguments and builds the user's URDF arm as a
+    kinematic chain under the reference's environment rule (environment/urdf_chain.py, environment/kinematic.py): one env
+    on the host, n_envs=E on the device (csrc/chain_env.hip). Not a Bullet port: no dynamics, no mesh collision.
 """
 from __future__ import annotations
 
@@ -27,6 +30,7 @@ from typing import List, Optional, Union
 import numpy as np
 import torch
 
+from .environment.kinematic import KinematicEnvironment, build_kinematic
 from .environment.synthetic import SyntheticEnvironment
 from .naf_components.naf_algorithm import NAFAgent
 from .presets import ROBOT_PRESETS, pybullet_arguments, synthetic_initial_joints
@@ -88,6 +92,10 @@ def _build_environment(manipulator_file: str, config_kwargs: dict):
 
 def _build_synthetic(n_joints, target, obstacle, init, variation):
     return SyntheticEnvironment(n_joints, target, obstacle, init, variation)
+
+
+# environments whose E copies are stepped on the device (everything else: E worker processes)
+_DEVICE_ENVS = (SyntheticEnvironment, KinematicEnvironment)
 
 
 class ManipulatorFramework:
@@ -277,6 +285,30 @@ class ManipulatorFramework:
                                               initial_joint_positions, initial_positions_variation_range)
         logger.info('Synthetic (kinematic stand-in) Environment successfully initialized')
 
+    def initialize_kinematic_environment(self, manipulator_file: str, endeffector_index: int, fixed_joints: List[int],
+                                         involved_joints: List[int], target_position: List[float],
+                                         obstacle_position: List[float], initial_joint_positions: List[float] = None,
+                                         initial_positions_variation_range: List[float] = None, link_radius: float = 0.0,
+                                         obstacle_radius: float = 0.06, obstacle_jitter: float = 0.0, max_force: float = 200.,
+                                         visualize: bool = False) -> None:
+        """initialize_environment()'s arguments (rl_framework.py:369-417) for the built-in kinematic environment: the arm of
+        `manipulator_file` (a URDF) as a serial chain under the reference's environment rule, velocity control applied exactly.
+        Not a Bullet port — no dynamics (max_force is accepted and ignored), no mesh collision (links are capsules of their
+        primitive collision radius, else link_radius), no GUI (visualize=True is refused). obstacle_jitter: as
+        initialize_synthetic_environment's. One env runs on the host, n_envs=E copies run on the device."""
+        if visualize:
+            raise InvalidManipulatorFile('the kinematic environment has no visualisation: pass visualize=False '
+                                         '(initialize_environment() opens the PyBullet GUI)')
+        args = (manipulator_file, endeffector_index, list(fixed_joints), list(involved_joints), list(target_position),
+                list(obstacle_position), None if initial_joint_positions is None else list(initial_joint_positions),
+                None if initial_positions_variation_range is None else list(initial_positions_variation_range),
+                float(link_radius), float(obstacle_radius))
+        self.env = build_kinematic(*args)
+        self._obstacle_jitter = float(obstacle_jitter)
+        self._env_factory = functools.partial(build_kinematic, *args)
+        logger.info(f'Kinematic Environment successfully initialized from {manipulator_file} '
+                    f'({self.env.model.A} driven joints, {len(self.env.model.segments)} collision capsules)')
+
     def delete_environment(self) -> None:
         if not self.env:
             logger.error('No existing instance of Environment found')
@@ -331,7 +363,7 @@ class ManipulatorFramework:
         E = n_envs if n_envs is not None else self._n_envs
         if E is None or E <= 1:
             return self.naf_agent.run(frames, episodes, verbose)
-        if isinstance(self.env, SyntheticEnvironment):
+        if isinstance(self.env, _DEVICE_ENVS):
             return self.naf_agent.run_vectorized(episodes=episodes, n_envs=int(E), max_frames=frames, verbose=verbose,
                                                  **self._device_env_arguments())['scores']
         vec = self._host_vector_env(int(E), frames)
@@ -352,7 +384,7 @@ class ManipulatorFramework:
         if not isinstance(episodes, int) or isinstance(episodes, bool) or episodes < episode:
             raise InvalidNAFAgentParameter('The episode budget received is not an integer at least as large as the checkpoint')
         E = n_envs if n_envs is not None else self._n_envs
-        if E is not None and E > 1 and not isinstance(self.env, SyntheticEnvironment):
+        if E is not None and E > 1 and not isinstance(self.env, _DEVICE_ENVS):
             raise InvalidNAFAgentParameter('Training with environments in worker processes cannot be resumed')
         path = f'checkpoints/{episode}/training_state.pt'
         if not os.path.isfile(path):
@@ -368,13 +400,18 @@ class ManipulatorFramework:
         vector steps; see NAFAgent.run_vectorized (counters + 'scores')."""
         if not self.naf_agent or not self.env:
             raise ConfigurationIncomplete
-        kw = self._device_env_arguments() if isinstance(self.env, SyntheticEnvironment) else {}
+        kw = self._device_env_arguments() if isinstance(self.env, _DEVICE_ENVS) else {}
         return self.naf_agent.run_vectorized(vector_steps, n_envs=n_envs, max_frames=max_frames, **kw)
 
     # ---- E copies of the configured environment -------------------------------------------------------------------
     def _device_env_arguments(self) -> dict:
-        """The synthetic environment's configuration as csrc/synth_env.hip takes it."""
+        """The synthetic environment's configuration as csrc/synth_env.hip takes it; the kinematic environment's chain model
+        and scene (csrc/chain_env.hip)."""
         env = self.env
+        if isinstance(env, KinematicEnvironment):
+            return {'chain': env.model, 'scene': {
+                'target': [float(x) for x in env.target_pos], 'obstacle': [float(x) for x in env.obstacle_pos],
+                'obstacle_radius': env.obstacle_radius, 'obstacle_jitter': getattr(self, '_obstacle_jitter', 0.0)}}
         pad8 = lambda v: ([float(x) for x in v] + [0.0] * 8)[:8]          # noqa: E731
         var = env.initial_positions_variation_range
         return {'preset': pad8(env.initial_joint_positions) + [float(x) for x in env.target_pos] +
@@ -390,7 +427,7 @@ class ManipulatorFramework:
                              max_frames=frames, seed=self.naf_agent.seed)
 
     def _many_env_results(self, n_episodes: int, frames: int, n_envs: int):
-        if isinstance(self.env, SyntheticEnvironment):
+        if isinstance(self.env, _DEVICE_ENVS):
             return self.naf_agent.evaluate_vectorized(n_episodes, frames, n_envs=n_envs, **self._device_env_arguments())
         vec = self._host_vector_env(n_envs, frames)
         try:

@@ -355,6 +355,9 @@ def resume_vectorized(loop: Optional[dict], loop_env, ledger, args: dict) -> Tup
     if loop is None or loop["meta"].get("kind") != "vectorized":
         raise ValueError("run_vectorized(resume=True): load a training state written at a checkpoint of run_vectorized() first")
     lm = loop["meta"]
+    for k in lm["args"]:
+        if k not in args:                  # (a chain model's run loaded into a stand-in's: 'chain', 'scene')
+            raise ValueError(f"run_vectorized(resume=True): the saved run used {k} = {lm['args'][k]!r}, this one has none")
     for k, v in args.items():
         if lm["args"].get(k) != v:
             raise ValueError(f"run_vectorized(resume=True): {k} is {v!r}, the saved run used {lm['args'].get(k)!r}")
