@@ -3,9 +3,11 @@ count, and a launch loop of the two step kernels for `rocprofv3 --kernel-trace -
 
   python benchmarks/chain_env_bench.py rate --urdf tests/golden/urdf/iiwa_like7.urdf --steps 4000 --warmup 100
       env-steps/s of NAFAgent.run_vectorized, E = 64, B = 256: the chain environment, then the stand-in at the same A
-      (`--standin-only`: only the latter — what a tree without the chain environment can run)
+      (`--standin-only`: only the latter — what a tree without the chain environment can run; `--autocollision`: the chain
+      environment compiled with consider_autocollision=True, `--arm standin8`: a fixture arm with its full joint count)
   rocprofv3 --kernel-trace --stats -d OUT -- python benchmarks/chain_env_bench.py kernels
       1000 launches each of chain_env_step_kernel for standin8 (A = 8, E = 64) and long32, and of synth_env_step_kernel
+      (`--autocollision`: the two arms compiled with their self-collision pairs, 18 and 465: the SC = true instantiation)
 """
 import argparse
 import ctypes
@@ -36,9 +38,14 @@ def rate(a):
     if not a.standin_only:
         from robotic_manipulator_rloa_amd.environment.kinematic import build_kinematic
         n = a.joints
-        env = build_kinematic(os.path.abspath(a.urdf) if os.path.isabs(a.urdf) else os.path.join(ROOT, a.urdf), n - 1, [n],
-                              list(range(n)), [0.45, 0.3, 0.6], [0.35, 0.2, 0.45], [0.0, 0.6, 0.0, -1.2, 0.0, 0.8, 0.0][:n],
-                              [0.1] * n, 0.03)
+        if a.arm:        # a fixture arm: every joint driven, none held (standin8, long12: serial chains without fixed joints)
+            env = build_kinematic(os.path.join(URDF, a.arm + ".urdf"), n - 1, [], list(range(n)), [0.4, 0.85, 0.71], [0.45, 0.55, 0.55],
+                                  ([0.9, 0.45] + [0.0] * n)[:n], [0.1] * n, 0.03, consider_autocollision=a.autocollision)
+        else:
+            env = build_kinematic(os.path.abspath(a.urdf) if os.path.isabs(a.urdf) else os.path.join(ROOT, a.urdf), n - 1, [n],
+                                  list(range(n)), [0.45, 0.3, 0.6], [0.35, 0.2, 0.45], [0.0, 0.6, 0.0, -1.2, 0.0, 0.8, 0.0][:n],
+                                  [0.1] * n, 0.03, consider_autocollision=a.autocollision)
+        out["self_pairs"] = len(env.model.self_pairs)
         for rep in range(a.repeats):
             run(f"chain_{rep}", env, n, chain=env.model,
                 scene={"target": [0.45, 0.3, 0.6], "obstacle": [0.35, 0.2, 0.45]})
@@ -58,7 +65,8 @@ def kernels(a):
     dev = torch.device("cuda:0")
     E, stream = a.envs, torch.cuda.current_stream().cuda_stream
     for name, n in (("standin8", 8), ("long32", 32)):
-        model = compile_chain(load_urdf(os.path.join(URDF, name + ".urdf")), n - 1, list(range(n)), [], None, [0.1] * n, 0.03)
+        model = compile_chain(load_urdf(os.path.join(URDF, name + ".urdf")), n - 1, list(range(n)), [], None, [0.1] * n, 0.03,
+                              consider_autocollision=a.autocollision)
         blob = np.ascontiguousarray(model.pack())
         h = ctypes.c_void_p()
         _lib.check(lib.naf_chain_env_create(blob.ctypes.data, int(blob.size), ctypes.byref(h)), "create")
@@ -81,7 +89,7 @@ def kernels(a):
         _lib.check(lib.naf_synth_env_step(st.data_ptr(), act.data_ptr(), rows.data_ptr(), obs.data_ptr(), E, n, 5, None, 0, None, 0,
                                           stream), "step")
     torch.cuda.synchronize()
-    print(json.dumps({"launches_each": a.launches, "envs": E}))
+    print(json.dumps({"launches_each": a.launches, "envs": E, "autocollision": a.autocollision}))
 
 
 def main():
@@ -96,6 +104,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=2)
     ap.add_argument("--launches", type=int, default=1000)
     ap.add_argument("--standin-only", action="store_true")
+    ap.add_argument("--autocollision", action="store_true")
+    ap.add_argument("--arm", default="", help="rate: a fixture arm of tests/golden/urdf by name, --joints its joint count")
     a = ap.parse_args()
     (rate if a.what == "rate" else kernels)(a)
 

@@ -67,7 +67,7 @@ typedef struct {
 /* ---- library ------------------------------------------------------------------------------ */
 /* Bumped whenever a signature or a struct in this header changes; the ctypes host compares the library's answer with
  * the value in this header and refuses a mismatch (a stale .so would otherwise be called with wrong argument lists). */
-#define NAF_HIP_ABI_VERSION 36
+#define NAF_HIP_ABI_VERSION 37
 int naf_hip_abi_version(void);
 /* "gfx950" — the only architecture this library carries code objects for */
 const char* naf_hip_arch(void);
@@ -666,17 +666,18 @@ int naf_synth_env_reset(float* env_state, float* obs, int E, int A, uint64_t see
                         const float* preset_host, int preset_floats, void* stream);
 int naf_synth_env_state_floats(int A);
 
-/* ---- kinematic environment of a URDF manipulator (ABI 36) ----------------------------------------------------------------
+/* ---- kinematic environment of a URDF manipulator (ABI 36; self-collision and probe: ABI 37) ----------------------------------------------------------------
  * E copies of the serial chain environment/urdf_chain.py compiles from the user's URDF, stepped on the device under the
  * reference's environment rule (environment/environment.py:431-485: state layout, reward, terminal rule, velocity control
  * of the involved joints, held joints). Kinematic — the commanded velocity is applied exactly for one 1/240 s tick, then the
- * position limits — and NOT a port of Bullet: no dynamics, no mesh collision, no self-collision. See csrc/chain_env.hip;
- * environment/kinematic.py is the float64 host twin.
+ * position limits — and NOT a port of Bullet: no dynamics, no mesh collision. Self-collision is the reference's rule
+ * (environment.py:311-343, :394-412) between capsules, for the segment pairs the blob lists; a blob without pairs is the
+ * environment without it. See csrc/chain_env.hip; environment/kinematic.py is the float64 host twin.
  *
  * Chain model blob (float32, every count and index stored as a float; ChainModel.pack writes it, model_check reads it):
  *   header, NAF_CHAIN_HEADER_FLOATS: [0] NAF_CHAIN_BLOB_VERSION  [1] A (driven joints = action size, 1 .. 64)  [2] segments
  *     [3] observation slots (= A)  [4] end-effector frame  [5..7] end-effector point in that frame  [8] floats in the blob
- *     [9..15] 0
+ *     [9] self-collision pairs P (0: none, the blob then ends after the slots)  [10..15] 0
  *   A driven joints in action order, NAF_CHAIN_JOINT_FLOATS each: [0..8] pre-rotation, row-major 3 x 3  [9..11] pre-translation
  *     [12..14] unit axis  [15] type, 0 revolute / 1 prismatic  [16] 1 = has position limits  [17] lower  [18] upper
  *     [19] initial position  [20] half-width of the reset range  [21] observation slot reporting this joint, or -1  [22..23] 0
@@ -687,6 +688,9 @@ int naf_synth_env_state_floats(int A);
  *     contact = distance(segment, obstacle centre) < radius + obstacle radius
  *   A observation slots, 2 floats each: [0] driven joint (action index) whose position / velocity the slot reports, or -1:
  *     a constant joint, position [1], velocity 0. Slot k reports joint INDEX k of the URDF (environment.py:442-444).
+ *   P self-collision pairs, 2 floats each: segment indices [0] s < [1] t, no pair twice;
+ *     self-contact = distance(segment s, segment t) - radius s - radius t < 0 for any pair: reward -1000 and done, as obstacle
+ *     contact (reaching the target still wins). NAF_CHAIN_BLOB_VERSION stays 1: without pairs the bytes are ABI 36's.
  *
  * env_state record of one env, naf_chain_env_state_floats floats = round_up(round_up(A + 9, 2) + 2, 4):
  *   [0 .. A) driven joint positions by action index  [A .. A+3) target  [A+3 .. A+6) obstacle centre  [A+6] obstacle radius
@@ -696,12 +700,19 @@ int naf_synth_env_state_floats(int A);
  *   model_check : NAF_OK, NAF_ERR_ARG (null / shorter than a header) or the NAF_CHAIN_ERR_* of the first wrong field; pure
  *                 host code
  *   create      : checks the blob, uploads it once (the one allocation) and keeps A and the counts: no launch ever trusts a
- *                 device blob the host has not checked. model_host is HOST memory.
+ *                 device blob the host has not checked. model_host is HOST memory. With P > 0 the step stages every capsule's
+ *                 world end points in LDS, 24 bytes per segment and env: an arm with many segments gets fewer envs per
+ *                 workgroup (64, 32, .. 1), and NAF_CHAIN_ERR_LDS when one env's do not fit a workgroup's LDS.
  *   reset       : scene_host = NAF_CHAIN_SCENE_FLOATS HOST floats [target xyz | obstacle xyz | obstacle jitter | obstacle
  *                 radius]; joints start at init + U(-variation, +variation); obs [E][2A+9] receives the first observation
  *   step        : naf_synth_env_step's contract towards the rest of the engine — transition rows, the next observation,
  *                 per-env running score (double, step order), frame budget, auto-reset, one episode record per
- *                 (step mod record_slots, env), the same Philox keying of the reset draws and of the obstacle jitter. */
+ *                 (step mod record_slots, env), the same Philox keying of the reset draws and of the obstacle jitter.
+ *                 With P = 0 the launch is ABI 36's kernel. The auto-reset inside step does not test the reset pose against
+ *                 itself: a reset pose in self-contact ends its episode at the next step.
+ *   probe       : out [E][NAF_CHAIN_PROBE_FLOATS] = [end-effector xyz | min over segments of (distance to the obstacle centre -
+ *                 capsule radius) - obstacle radius (obstacle contact iff < 0) | min over the pairs of the pair clearance
+ *                 (self-contact iff < 0; +inf when P = 0)] at the joint values and scene in env_state; changes no state. */
 #define NAF_CHAIN_BLOB_VERSION 1
 #define NAF_CHAIN_HEADER_FLOATS 16
 #define NAF_CHAIN_JOINT_FLOATS 24
@@ -715,6 +726,9 @@ int naf_synth_env_state_floats(int A);
 #define NAF_CHAIN_ERR_JOINT (-16)
 #define NAF_CHAIN_ERR_SEGMENTS (-17) /* begin table not monotone, or a segment outside its frame's range (unsorted) */
 #define NAF_CHAIN_ERR_SLOTS (-18)
+#define NAF_CHAIN_ERR_PAIRS (-19)    /* pair count or table size, an index out of range or not an integer, s >= t, a pair twice */
+#define NAF_CHAIN_ERR_LDS (-20)      /* create: P > 0 and one env's capsule end points exceed a workgroup's LDS */
+#define NAF_CHAIN_PROBE_FLOATS 5
 typedef struct naf_chain_env naf_chain_env_t;
 int naf_chain_env_model_check(const float* model_host, int n_floats);
 int naf_chain_env_create(const float* model_host, int n_floats, naf_chain_env_t** out);
@@ -725,6 +739,7 @@ int naf_chain_env_reset(naf_chain_env_t* h, float* env_state, float* obs, int E,
 int naf_chain_env_step(naf_chain_env_t* h, float* env_state, const float* actions, float* out_rows, float* obs_next, int E,
                        uint64_t seed, const uint64_t* counter_dev, int max_frames, naf_episode_record_t* records,
                        int record_slots, void* stream);
+int naf_chain_env_probe(naf_chain_env_t* h, const float* env_state, float* out, int E, void* stream);
 
 /* ---- one-shot gradient all-reduce over peer-mapped memory (no reference counterpart) ----------
  * The data-parallel exchange that follows loss.backward() (naf_algorithm.py:207-210 on every rank): sum of the flat

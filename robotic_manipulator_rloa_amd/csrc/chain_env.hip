@@ -6,17 +6,27 @@
 //   reward = +250 on reaching the target (dist < 0.05), -1000 on obstacle contact, else -(dist - 0.05)
 //            (environment.py:345-371, :419-429);  done = 1 on either (environment.py:311-333)
 //   step   = velocity control for one 1/240 s tick, applied exactly, then the position limits (environment.py:453-485)
-// NOT a port of Bullet: no dynamics, no mesh collision, no self-collision. environment/kinematic.py is its float64 twin.
+// NOT a port of Bullet: no dynamics, no mesh collision. Self-collision is the reference's rule (environment.py:311-343, :394-412;
+// collision_detector.py:63-98) between capsules, for the segment pairs the blob lists. environment/kinematic.py is its float64 twin.
 //
 // One lane per env, 64-lane workgroups. The model is the same for every lane and is read through a uniform pointer with
 // uniform indices (scalar loads / one broadcast line); nothing of it is copied into per-lane arrays. The walk keeps only the
 // current frame (R, p) in registers; joint values and actions are read from and written to env_state / the row as the walk
 // reaches them, so there is no runtime-indexed per-lane array and nothing goes to scratch, at any A <= 64.
+//
+// Self-collision (P > 0 pairs in the blob) is a second instantiation of the same kernels, SC = true; with P = 0 the launch is
+// the SC = false one: no LDS, one wave per workgroup, the rows it always wrote. With SC the walking wave also stores each
+// capsule's two world end points in LDS as [segment][6][lane] floats — lane-contiguous, so every access is one conflict-free
+// row and no per-lane array is indexed at run time — and the workgroup has W waves: wave 0 walks, a barrier, then pair p is
+// tested by wave p mod W (lane = env, pair indices and radii through uniform loads), each wave leaves the minimum of its pairs'
+// clearances in LDS, a barrier, and wave 0 takes the minimum of the W before it writes reward and done.
 #include "common.h"
 #include "../../include/naf_hip.h"
 
+#include <algorithm>
 #include <cmath>
 #include <new>
+#include <vector>
 
 #define CH_DT (1.0f / 240.0f)
 #define CH_MAX_A NAF_MAX_A_WIDE
@@ -28,7 +38,13 @@
 struct naf_chain_env {
     float* model_dev;
     int n_floats, A, n_seg;
+    int n_pairs, lanes, waves;      // P; with P > 0: envs per workgroup (64, 32, .. 1) and waves per workgroup
 };
+#ifndef CH_MAX_WAVES
+#define CH_MAX_WAVES 16                      // (-DCH_MAX_WAVES=1 through NAF_BUILD_DEFINES: the one-wave pair loop, NOTEBOOK §15)
+#endif
+#define CH_PAIRS_PER_WAVE 16                 // waves = ceil(P / this), at most CH_MAX_WAVES
+#define CH_MAX_DYN_LDS (144 * 1024)          // of the CU's 160 KiB; the SC kernels have no static LDS beside it
 
 struct ChainScene {
     float v[NAF_CHAIN_SCENE_FLOATS];    // target | obstacle | jitter | obstacle radius
@@ -37,6 +53,11 @@ struct ChainScene {
 __host__ __device__ static inline int ch_off_begin(int A) { return CH_HDR + CH_JNT * A; }
 __host__ __device__ static inline int ch_off_seg(int A) { return ch_off_begin(A) + A + 2; }
 __host__ __device__ static inline int ch_off_slot(int A, int n_seg) { return ch_off_seg(A) + CH_SEG * n_seg; }
+__host__ __device__ static inline int ch_off_pair(int A, int n_seg) { return ch_off_slot(A, n_seg) + 2 * A; }
+// dynamic LDS of an SC launch: end points [n_seg][6][lanes], then one minimum per (wave, lane)
+__host__ __device__ static inline size_t ch_lds_bytes(int n_seg, int lanes, int waves) {
+    return ((size_t)n_seg * 6 + waves) * lanes * sizeof(float);
+}
 // env_state record of one env (include/naf_hip.h): q[A] | target[3] | obstacle[3] | obstacle radius | frame | episode | score (double)
 __host__ __device__ static inline int ch_off_score(int A) { return naf_round_up(A + 9, 2); }
 __host__ __device__ static inline int ch_state_floats(int A) { return naf_round_up(ch_off_score(A) + 2, 4); }
@@ -57,9 +78,46 @@ struct Frame {
     float r00, r01, r02, r10, r11, r12, r20, r21, r22, px, py, pz;
 };
 
+// squared distance between the segments a-b and c-d. The minimum over five candidates, each between two points that lie on the
+// two segments (so none is below the answer): the carrying lines' closest points — closed form with a guarded denominator,
+// clamped, then each parameter projected once more given the other — and the four end-point-to-segment distances. The minimum
+// over the parameter square is interior (the lines' pair) or has a parameter at 0 or 1 (an end point against the other
+// segment); parallel and zero-length segments, where the denominator vanishes, attain theirs at an end point.
+__device__ static inline float seg_seg_dist2(float ax, float ay, float az, float bx, float by, float bz, float cx, float cy, float cz,
+                                             float dx, float dy, float dz) {
+    const float ux = bx - ax, uy = by - ay, uz = bz - az;
+    const float vx = dx - cx, vy = dy - cy, vz = dz - cz;
+    const float wx = ax - cx, wy = ay - cy, wz = az - cz;
+    const float a = ux * ux + uy * uy + uz * uz, b = ux * vx + uy * vy + uz * vz, c = vx * vx + vy * vy + vz * vz;
+    const float d = ux * wx + uy * wy + uz * wz, e = vx * wx + vy * wy + vz * wz;
+    const float den = a * c - b * b;
+    float s = den > 1e-7f * a * c ? (b * e - c * d) / den : 0.f;
+    s = fminf(1.f, fmaxf(0.f, s));
+    float t = c > 0.f ? (b * s + e) / c : 0.f;
+    t = fminf(1.f, fmaxf(0.f, t));
+    s = a > 0.f ? (b * t - d) / a : 0.f;
+    s = fminf(1.f, fmaxf(0.f, s));
+    const float xx = wx + s * ux - t * vx, xy = wy + s * uy - t * vy, xz = wz + s * uz - t * vz;
+    float best = xx * xx + xy * xy + xz * xz;
+    best = fminf(best, seg_point_dist2(cx, cy, cz, dx, dy, dz, ax, ay, az));
+    best = fminf(best, seg_point_dist2(cx, cy, cz, dx, dy, dz, bx, by, bz));
+    best = fminf(best, seg_point_dist2(ax, ay, az, bx, by, bz, cx, cy, cz));
+    best = fminf(best, seg_point_dist2(ax, ay, az, bx, by, bz, dx, dy, dz));
+    return best;
+}
+
+// Where the SC instantiations keep the capsules' world end points: `ends` is the LDS array already offset by the lane, `lanes`
+// its innermost extent. PROBE: `clear` collects min over the capsules of (distance to the obstacle centre - capsule radius).
+struct WalkAux {
+    float* ends;
+    int lanes;
+    float clear;
+};
+
 // contact of the capsules of frame f with the obstacle sphere, and the end-effector point when it lives in f
+template <bool SC, bool PROBE>
 __device__ static inline bool frame_geometry(const float* __restrict__ model, int A, int f, const Frame& F, float ox, float oy,
-                                             float oz, float orad, int ee_frame, float* ee) {
+                                             float oz, float orad, int ee_frame, float* ee, WalkAux& aux) {
     const float* begin = model + ch_off_begin(A);
     const float* segs = model + ch_off_seg(A);
     const int s0 = (int)begin[f], s1 = (int)begin[f + 1];
@@ -73,7 +131,14 @@ __device__ static inline bool frame_geometry(const float* __restrict__ model, in
         const float by = F.py + F.r10 * g[4] + F.r11 * g[5] + F.r12 * g[6];
         const float bz = F.pz + F.r20 * g[4] + F.r21 * g[5] + F.r22 * g[6];
         const float rr = g[7] + orad;
-        hit |= seg_point_dist2(ax, ay, az, bx, by, bz, ox, oy, oz) < rr * rr;
+        const float d2 = seg_point_dist2(ax, ay, az, bx, by, bz, ox, oy, oz);
+        hit |= d2 < rr * rr;
+        if constexpr (SC) {
+            float* w = aux.ends + (size_t)s * 6 * aux.lanes;
+            w[0] = ax; w[aux.lanes] = ay; w[2 * aux.lanes] = az;
+            w[3 * aux.lanes] = bx; w[4 * aux.lanes] = by; w[5 * aux.lanes] = bz;
+        }
+        if constexpr (PROBE) aux.clear = fminf(aux.clear, sqrtf(d2) - g[7]);
     }
     if (f == ee_frame) {
         ee[0] = F.px + F.r00 * model[5] + F.r01 * model[6] + F.r02 * model[7];
@@ -84,18 +149,23 @@ __device__ static inline bool frame_geometry(const float* __restrict__ model, in
 }
 
 // Walks the chain at the joint values in st[0 .. A): writes the position slots, the constants' slots (velocity 0), the end
-// effector, target and obstacle into the observation `o`; the DRIVEN joints' velocity slots are the caller's. Returns contact.
-__device__ static inline bool chain_walk(const float* __restrict__ model, int A, int n_seg, const float* st, float* o, float* ee) {
+// effector, target and obstacle into the observation `o` (not with PROBE: o is unused); the DRIVEN joints' velocity slots are the
+// caller's. Returns contact with the obstacle.
+template <bool SC, bool PROBE>
+__device__ static inline bool chain_walk(const float* __restrict__ model, int A, int n_seg, const float* st, float* o, float* ee,
+                                         WalkAux& aux) {
     const int ee_frame = (int)model[4];
     const float ox = st[A + 3], oy = st[A + 4], oz = st[A + 5], orad = st[A + 6];
     Frame F = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
     ee[0] = ee[1] = ee[2] = 0.f;
-    bool hit = frame_geometry(model, A, 0, F, ox, oy, oz, orad, ee_frame, ee);
+    bool hit = frame_geometry<SC, PROBE>(model, A, 0, F, ox, oy, oz, orad, ee_frame, ee, aux);
     for (int m = 0; m < A; ++m) {
         const float* j = model + CH_HDR + m * CH_JNT;
         const float q = st[m];
-        const int slot = (int)j[21];
-        if (slot >= 0) o[slot] = q;
+        if constexpr (!PROBE) {
+            const int slot = (int)j[21];
+            if (slot >= 0) o[slot] = q;
+        }
         // p += R . t_pre ;  R = R . R_pre
         F.px += F.r00 * j[9] + F.r01 * j[10] + F.r02 * j[11];
         F.py += F.r10 * j[9] + F.r11 * j[10] + F.r12 * j[11];
@@ -135,13 +205,44 @@ __device__ static inline bool chain_walk(const float* __restrict__ model, int A,
             F.r21 = G.r20 * m01 + G.r21 * m11 + G.r22 * m21;
             F.r22 = G.r20 * m02 + G.r21 * m12 + G.r22 * m22;
         }
-        hit |= frame_geometry(model, A, m + 1, F, ox, oy, oz, orad, ee_frame, ee);
+        hit |= frame_geometry<SC, PROBE>(model, A, m + 1, F, ox, oy, oz, orad, ee_frame, ee, aux);
     }
-    const float* slots = model + ch_off_slot(A, n_seg);
-    for (int k = 0; k < A; ++k)
-        if (slots[2 * k] < 0.f) { o[k] = slots[2 * k + 1]; o[A + k] = 0.f; }
-    for (int k = 0; k < 3; ++k) { o[2 * A + k] = ee[k]; o[2 * A + 3 + k] = st[A + k]; o[2 * A + 6 + k] = st[A + 3 + k]; }
+    if constexpr (!PROBE) {
+        const float* slots = model + ch_off_slot(A, n_seg);
+        for (int k = 0; k < A; ++k)
+            if (slots[2 * k] < 0.f) { o[k] = slots[2 * k + 1]; o[A + k] = 0.f; }
+        for (int k = 0; k < 3; ++k) { o[2 * A + k] = ee[k]; o[2 * A + 3 + k] = st[A + k]; o[2 * A + 6 + k] = st[A + 3 + k]; }
+    }
     return hit;
+}
+
+// The pair phase of an SC workgroup, entered by EVERY thread after the walking wave has stored the end points: returns, to
+// every thread, min over the blob's pairs of distance(segment s, segment t) - radius s - radius t for the env of its lane.
+__device__ static inline float self_clearance_phase(const float* __restrict__ model, int A, int n_seg, int n_pairs, float* lds,
+                                                    int lanes, int lane, bool active) {
+    const int waves = blockDim.x >> 6;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const float* segs = model + ch_off_seg(A);
+    const float* pairs = model + ch_off_pair(A, n_seg);
+    float* red = lds + (size_t)n_seg * 6 * lanes;
+    __syncthreads();
+    float best = INFINITY;
+    if (active) {
+        const float* ends = lds + lane;
+        for (int p = wave; p < n_pairs; p += waves) {
+            const int s = (int)pairs[2 * p], t = (int)pairs[2 * p + 1];
+            const float* u = ends + (size_t)s * 6 * lanes;
+            const float* v = ends + (size_t)t * 6 * lanes;
+            const float d2 = seg_seg_dist2(u[0], u[lanes], u[2 * lanes], u[3 * lanes], u[4 * lanes], u[5 * lanes], v[0], v[lanes],
+                                           v[2 * lanes], v[3 * lanes], v[4 * lanes], v[5 * lanes]);
+            best = fminf(best, sqrtf(d2) - (segs[s * CH_SEG + 7] + segs[t * CH_SEG + 7]));
+        }
+        red[wave * lanes + lane] = best;
+    }
+    __syncthreads();
+    if (active)
+        for (int w = 0; w < waves; ++w) best = fminf(best, red[w * lanes + lane]);
+    return best;
 }
 
 // initial joint positions + uniform(-variation, +variation): env_reset_one's draw (csrc/synth_env.hip), keyed the same way,
@@ -180,15 +281,31 @@ __global__ void chain_env_reset_kernel(const float* __restrict__ model, float* e
     st[A + 6] = scene.v[7];
     chain_reset_one(model, st, o, e, A, seed, ctr);
     float ee[3];
-    chain_walk(model, A, n_seg, st, o, ee);
+    WalkAux aux = {nullptr, 0, 0.f};
+    chain_walk<false, false>(model, A, n_seg, st, o, ee, aux);
 }
 
-__global__ void chain_env_step_kernel(const float* __restrict__ model, float* env_state, const float* __restrict__ actions,
-                                      float* __restrict__ out_rows, float* __restrict__ obs_next, int E, int A, int n_seg,
-                                      int row_floats, uint64_t seed, const uint64_t* counter_dev, int max_frames,
-                                      naf_episode_record_t* __restrict__ records, int record_slots) {
-    int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
+// SC = false: one wave per workgroup, lane = env. SC = true: `lanes` envs per workgroup (lane < lanes of every wave), wave 0 is
+// the env's walker and the only one that touches global memory; the others join it for the pair phase.
+template <bool SC>
+__global__ void __launch_bounds__(64 * CH_MAX_WAVES)
+chain_env_step_kernel(const float* __restrict__ model, float* env_state, const float* __restrict__ actions,
+                      float* __restrict__ out_rows, float* __restrict__ obs_next, int E, int A, int n_seg, int row_floats,
+                      uint64_t seed, const uint64_t* counter_dev, int max_frames, naf_episode_record_t* __restrict__ records,
+                      int record_slots, int n_pairs, int lanes) {
+    extern __shared__ __attribute__((aligned(16))) float ch_lds[];
+    int e, lane = 0;
+    bool active = true, walker = true;
+    if constexpr (SC) {
+        lane = threadIdx.x & 63;
+        e = blockIdx.x * lanes + lane;
+        active = lane < lanes && e < E;
+        walker = active && threadIdx.x < 64;
+        if (!active) e = 0;      // (addresses below stay inside the arrays; nothing is read or written through them)
+    } else {
+        e = blockIdx.x * blockDim.x + threadIdx.x;
+        if (e >= E) return;
+    }
     const int S = 2 * A + 9;
     float* st = env_state + (int64_t)e * ch_state_floats(A);
     float* row = out_rows + (int64_t)e * row_floats;
@@ -196,25 +313,35 @@ __global__ void chain_env_step_kernel(const float* __restrict__ model, float* en
     const uint64_t ctr = counter_dev ? *counter_dev : 0ull;
     const int off_s2 = naf_row_off_s2(S, A), off_d = naf_row_off_done(S, A);
     float* o2 = row + off_s2;
-
-    // the observation the action was chosen from is the row's `state`
-    for (int k = 0; k < S; ++k) row[k] = ob[k];
-    for (int m = 0; m < A; ++m) {
-        const float* j = model + CH_HDR + m * CH_JNT;
-        const float a = actions[(int64_t)e * A + m];
-        row[S + m] = a;
-        float q = st[m] + CH_DT * a;      // velocity control: the commanded velocity is reached within the tick
-        float vel = a;
-        if (j[16] != 0.f) {               // position limits: a joint its limit stopped reports velocity 0
-            if (q > j[18]) { q = j[18]; vel = 0.f; }
-            if (q < j[17]) { q = j[17]; vel = 0.f; }
-        }
-        st[m] = q;
-        const int slot = (int)j[21];
-        if (slot >= 0) o2[A + slot] = vel;
-    }
     float ee[3];
-    const bool hit = chain_walk(model, A, n_seg, st, o2, ee);
+    bool hit = false;
+    WalkAux aux = {SC ? ch_lds + lane : nullptr, lanes, 0.f};
+
+    if (walker) {
+        // the observation the action was chosen from is the row's `state`
+        for (int k = 0; k < S; ++k) row[k] = ob[k];
+        for (int m = 0; m < A; ++m) {
+            const float* j = model + CH_HDR + m * CH_JNT;
+            const float a = actions[(int64_t)e * A + m];
+            row[S + m] = a;
+            float q = st[m] + CH_DT * a;      // velocity control: the commanded velocity is reached within the tick
+            float vel = a;
+            if (j[16] != 0.f) {               // position limits: a joint its limit stopped reports velocity 0
+                if (q > j[18]) { q = j[18]; vel = 0.f; }
+                if (q < j[17]) { q = j[17]; vel = 0.f; }
+            }
+            st[m] = q;
+            const int slot = (int)j[21];
+            if (slot >= 0) o2[A + slot] = vel;
+        }
+        hit = chain_walk<SC, false>(model, A, n_seg, st, o2, ee, aux);
+    }
+    if constexpr (SC) {
+        // self-contact counts as contact (environment.py:311-343); the walker's lanes hold the minimum over all pairs
+        const float self_clear = self_clearance_phase(model, A, n_seg, n_pairs, ch_lds, lanes, lane, active);
+        if (!walker) return;
+        hit |= self_clear < 0.f;
+    }
     float dx = ee[0] - st[A], dy = ee[1] - st[A + 1], dz = ee[2] - st[A + 2];
     float dist = sqrtf(dx * dx + dy * dy + dz * dz);
     const bool reached = dist < 0.05f;
@@ -246,10 +373,43 @@ __global__ void chain_env_step_kernel(const float* __restrict__ model, float* en
         // episode over (terminal state, or the frame budget of NAFAgent.run, naf_algorithm.py:249): auto-reset
         st[A + 8] += 1.f;
         chain_reset_one(model, st, ob, e, A, seed, ctr * 0x9E3779B97F4A7C15ull + (uint64_t)st[A + 8]);
-        chain_walk(model, A, n_seg, st, ob, ee);
+        chain_walk<false, false>(model, A, n_seg, st, ob, ee, aux);
     } else {
         for (int k = 0; k < S; ++k) ob[k] = o2[k];
     }
+}
+
+// naf_chain_env_probe: the walk and the pair phase of the step at the joint values in env_state, nothing written but `out`
+template <bool SC>
+__global__ void __launch_bounds__(64 * CH_MAX_WAVES)
+chain_env_probe_kernel(const float* __restrict__ model, const float* __restrict__ env_state, float* __restrict__ out, int E, int A,
+                       int n_seg, int n_pairs, int lanes) {
+    extern __shared__ __attribute__((aligned(16))) float ch_lds[];
+    int e, lane = 0;
+    bool active = true, walker = true;
+    if constexpr (SC) {
+        lane = threadIdx.x & 63;
+        e = blockIdx.x * lanes + lane;
+        active = lane < lanes && e < E;
+        walker = active && threadIdx.x < 64;
+        if (!active) e = 0;
+    } else {
+        e = blockIdx.x * blockDim.x + threadIdx.x;
+        if (e >= E) return;
+    }
+    const float* st = env_state + (int64_t)e * ch_state_floats(A);
+    float ee[3];
+    WalkAux aux = {SC ? ch_lds + lane : nullptr, lanes, INFINITY};
+    if (walker) chain_walk<SC, true>(model, A, n_seg, st, nullptr, ee, aux);
+    float self_clear = INFINITY;
+    if constexpr (SC) {
+        self_clear = self_clearance_phase(model, A, n_seg, n_pairs, ch_lds, lanes, lane, active);
+        if (!walker) return;
+    }
+    float* o = out + (int64_t)e * NAF_CHAIN_PROBE_FLOATS;
+    o[0] = ee[0]; o[1] = ee[1]; o[2] = ee[2];
+    o[3] = aux.clear - st[A + 6];
+    o[4] = self_clear;
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
@@ -265,10 +425,13 @@ extern "C" int naf_chain_env_model_check(const float* m, int n_floats) {
     int A, n_seg, n_slot, ee_frame, total;
     if (!ch_int(m[1], 1, CH_MAX_A, &A) || !ch_int(m[2], 0, 1 << 20, &n_seg) || !ch_int(m[3], A, A, &n_slot))
         return NAF_CHAIN_ERR_COUNTS;
-    if (!ch_int(m[8], CH_HDR, 1 << 24, &total) || total != n_floats || total != ch_off_slot(A, n_seg) + 2 * A)
-        return NAF_CHAIN_ERR_SIZE;
+    if (!ch_int(m[8], CH_HDR, 1 << 24, &total) || total != n_floats) return NAF_CHAIN_ERR_SIZE;
+    int P = 0;
+    const bool pairs_counted = ch_int(m[9], 0, 1 << 22, &P);
+    if (pairs_counted && P == 0 && total != ch_off_pair(A, n_seg)) return NAF_CHAIN_ERR_SIZE;
     for (int k = 0; k < n_floats; ++k)
         if (!std::isfinite(m[k])) return NAF_CHAIN_ERR_VALUE;
+    if (!pairs_counted || total != ch_off_pair(A, n_seg) + 2 * P) return NAF_CHAIN_ERR_PAIRS;
     if (!ch_int(m[4], 0, A, &ee_frame)) return NAF_CHAIN_ERR_EE;
     for (int k = 0; k < A; ++k) {
         const float* j = m + CH_HDR + k * CH_JNT;
@@ -299,6 +462,33 @@ extern "C" int naf_chain_env_model_check(const float* m, int n_floats) {
         const int slot = (int)m[CH_HDR + k * CH_JNT + 21];
         if (slot >= 0 && (int)slots[2 * slot] != k) return NAF_CHAIN_ERR_SLOTS;
     }
+    const float* pairs = m + ch_off_pair(A, n_seg);
+    std::vector<int64_t> seen;
+    seen.reserve(P);
+    for (int p = 0; p < P; ++p) {
+        int s, t;
+        if (!ch_int(pairs[2 * p], 0, n_seg - 1, &s) || !ch_int(pairs[2 * p + 1], s + 1, n_seg - 1, &t)) return NAF_CHAIN_ERR_PAIRS;
+        seen.push_back((int64_t)s * n_seg + t);
+    }
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return NAF_CHAIN_ERR_PAIRS;
+    return NAF_OK;
+}
+
+// the SC kernels' dynamic LDS may exceed the 64 KB a kernel gets unasked: raised once per device
+static int ch_raise_lds_limit() {
+    static bool raised_dev[64];
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return (int)e;
+    if (dev < 0 || dev >= 64) return NAF_ERR_ARG;
+    if (raised_dev[dev]) return NAF_OK;
+    const void* ks[2] = {(const void*)chain_env_step_kernel<true>, (const void*)chain_env_probe_kernel<true>};
+    for (const void* k : ks) {
+        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, CH_MAX_DYN_LDS);
+        if (e != hipSuccess) return (int)e;
+    }
+    raised_dev[dev] = true;
     return NAF_OK;
 }
 
@@ -312,6 +502,19 @@ extern "C" int naf_chain_env_create(const float* model_host, int n_floats, naf_c
     h->n_floats = n_floats;
     h->A = (int)model_host[1];
     h->n_seg = (int)model_host[2];
+    h->n_pairs = (int)model_host[9];
+    h->lanes = 64;
+    h->waves = 1;
+    if (h->n_pairs > 0) {
+        // fewer envs per workgroup for an arm whose end points do not fit with 64; a refusal when one env's do not fit
+        h->waves = std::min(CH_MAX_WAVES, (h->n_pairs + CH_PAIRS_PER_WAVE - 1) / CH_PAIRS_PER_WAVE);
+        while (h->lanes > 1 && ch_lds_bytes(h->n_seg, h->lanes, h->waves) > CH_MAX_DYN_LDS) h->lanes >>= 1;
+        rc = ch_lds_bytes(h->n_seg, h->lanes, h->waves) > CH_MAX_DYN_LDS ? NAF_CHAIN_ERR_LDS : ch_raise_lds_limit();
+        if (rc != NAF_OK) {
+            delete h;
+            return rc;
+        }
+    }
     hipError_t e = hipMalloc((void**)&h->model_dev, (size_t)n_floats * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(h->model_dev, model_host, (size_t)n_floats * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
@@ -352,9 +555,27 @@ extern "C" int naf_chain_env_step(naf_chain_env_t* h, float* env_state, const fl
     const int A = h->A;
     const int rf = naf_replay_row_floats(2 * A + 9, A);
     if (rf <= 0) return NAF_ERR_ARG;
-    chain_env_step_kernel<<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(h->model_dev, env_state, actions, out_rows, obs_next, E,
-                                                                         A, h->n_seg, rf, seed, counter_dev, max_frames, records,
-                                                                         record_slots);
+    if (h->n_pairs > 0)
+        chain_env_step_kernel<true><<<(E + h->lanes - 1) / h->lanes, 64 * h->waves, ch_lds_bytes(h->n_seg, h->lanes, h->waves),
+                                      (hipStream_t)stream>>>(h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf,
+                                                             seed, counter_dev, max_frames, records, record_slots, h->n_pairs,
+                                                             h->lanes);
+    else
+        chain_env_step_kernel<false><<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(h->model_dev, env_state, actions, out_rows,
+                                                                                    obs_next, E, A, h->n_seg, rf, seed, counter_dev,
+                                                                                    max_frames, records, record_slots, 0, 64);
+    NAF_CHECK_LAUNCH();
+    return NAF_OK;
+}
+
+extern "C" int naf_chain_env_probe(naf_chain_env_t* h, const float* env_state, float* out, int E, void* stream) {
+    if (!h || !env_state || !out || E <= 0) return NAF_ERR_ARG;
+    if (h->n_pairs > 0)
+        chain_env_probe_kernel<true><<<(E + h->lanes - 1) / h->lanes, 64 * h->waves, ch_lds_bytes(h->n_seg, h->lanes, h->waves),
+                                       (hipStream_t)stream>>>(h->model_dev, env_state, out, E, h->A, h->n_seg, h->n_pairs, h->lanes);
+    else
+        chain_env_probe_kernel<false><<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(h->model_dev, env_state, out, E, h->A, h->n_seg,
+                                                                                     0, 64);
     NAF_CHECK_LAUNCH();
     return NAF_OK;
 }

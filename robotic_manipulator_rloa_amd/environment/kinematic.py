@@ -4,10 +4,12 @@ action_space as zero arrays), exactly as SyntheticEnvironment offers it.
 
 Built from a ChainModel (environment/urdf_chain.py) and evaluated from the MODEL, not from the packed blob, so that a packing
 error shows as a disagreement with the kernel. Kinematic: the commanded velocity is applied exactly for one 1/240 s tick
-(environment.py:453-485 with an ideal motor). NOT a port of Bullet: no dynamics, no mesh collision, no self-collision.
+(environment.py:453-485 with an ideal motor). NOT a port of Bullet: no dynamics, no mesh collision. Self-collision is the
+reference's rule (environment.py:311-343, :394-412) between the capsules of model.self_pairs, when the model was compiled with it.
   state  = [pos(A), vel(A), end-effector xyz, target xyz, obstacle xyz], slot k of pos / vel reporting joint INDEX k
            (environment.py:442-451)
-  reward = +250 reached (dist < 0.05) | -1000 contact | -(dist - 0.05), done on either (environment.py:311-371, :416-429)
+  reward = +250 reached (dist < 0.05) | -1000 obstacle contact or self-contact | -(dist - 0.05), done on any of the three
+           (environment.py:311-371, :416-429)
 """
 from __future__ import annotations
 
@@ -28,6 +30,31 @@ def segment_point_distance2(a: np.ndarray, b: np.ndarray, c: np.ndarray):
     return np.sum(d * d, axis=-1)
 
 
+def segment_segment_distance2(a1: np.ndarray, b1: np.ndarray, a2: np.ndarray, b2: np.ndarray):
+    """Squared distance between the segments a1-b1 and a2-b2; arrays of points [..., 3] broadcast.
+    The minimum over five candidates, each the squared distance between two points that DO lie on the two segments, so none is
+    below the answer: the four end-point-to-segment distances, and the closest points of the two carrying lines (closed form,
+    clamped into the segments, then each parameter projected once more given the other). One of them attains it: the minimum
+    over the square [0, 1]^2 of the two parameters is either interior — then it is the lines' closest pair — or has a parameter
+    at 0 or 1, an end point against the other segment. The closed form's denominator |u|^2 |v|^2 - (u.v)^2 vanishes for parallel
+    or zero-length segments; it is guarded and the candidate then starts from parameter 0, which loses nothing: between parallel
+    segments the minimum is also attained at an end point, and a zero-length segment is an end point."""
+    u, v, w = b1 - a1, b2 - a2, a1 - a2
+    a, b, c = np.sum(u * u, axis=-1), np.sum(u * v, axis=-1), np.sum(v * v, axis=-1)
+    d, e = np.sum(u * w, axis=-1), np.sum(v * w, axis=-1)
+    den = a * c - b * b
+    ok = den > 1e-14 * a * c
+    s = np.clip(np.where(ok, (b * e - c * d) / np.where(ok, den, 1.0), 0.0), 0.0, 1.0)
+    t = np.clip((b * s + e) / np.where(c > 0.0, c, 1.0), 0.0, 1.0) * (c > 0.0)
+    s = np.clip((b * t - d) / np.where(a > 0.0, a, 1.0), 0.0, 1.0) * (a > 0.0)
+    x = w + s[..., None] * u - t[..., None] * v
+    best = np.sum(x * x, axis=-1)
+    for cand in (segment_point_distance2(a2, b2, a1), segment_point_distance2(a2, b2, b1),
+                 segment_point_distance2(a1, b1, a2), segment_point_distance2(a1, b1, b2)):
+        best = np.minimum(best, cand)
+    return best
+
+
 class KinematicEnvironment:
 
     def __init__(self, model: ChainModel, target_position: Sequence[float], obstacle_position: Sequence[float],
@@ -46,6 +73,7 @@ class KinematicEnvironment:
         self.qd = np.zeros(self.n)
         self.last_distance = float("nan")                     # |ee - target| of the last step
         self.last_clearance = float("nan")                    # min over segments of (distance to the obstacle centre - radius)
+        self.last_self_clearance = float("nan")               # min over model.self_pairs of the pair clearance (+inf without pairs)
 
     @property
     def observation_space(self) -> np.ndarray:
@@ -88,6 +116,22 @@ class KinematicEnvironment:
         c = self.obstacle_pos if obstacle is None else np.asarray(obstacle, float)
         return np.min([np.sqrt(segment_point_distance2(a, b, c)) - r for a, b, r in self.world_segments(q)], axis=0)
 
+    def pair_clearances(self, q: Optional[np.ndarray] = None) -> np.ndarray:
+        """[pairs, ...]: distance(segment s, segment t) - radius_s - radius_t of every pair of model.self_pairs; contact iff < 0."""
+        segs = self.world_segments(q)
+        lead = np.shape(segs[0][0])[:-1]
+        out = np.empty((len(self.model.self_pairs),) + lead)
+        for k, (s, t) in enumerate(self.model.self_pairs):
+            out[k] = np.sqrt(segment_segment_distance2(segs[s][0], segs[s][1], segs[t][0], segs[t][1])) - segs[s][2] - segs[t][2]
+        return out
+
+    def self_clearance(self, q: Optional[np.ndarray] = None):
+        """min over model.self_pairs of the pair clearance, +inf without pairs; self-contact iff < 0."""
+        lead = np.shape(self.q if q is None else q)[:-1]
+        if not self.model.self_pairs:
+            return np.full(lead, np.inf) if lead else float("inf")
+        return np.min(self.pair_clearances(q), axis=0)
+
     def get_state(self) -> np.ndarray:
         A = self.n
         out = np.empty(2 * A + 9)
@@ -121,17 +165,19 @@ class KinematicEnvironment:
         A = self.n
         dist = float(np.linalg.norm(state[2 * A:2 * A + 3] - self.target_pos))
         clear = float(self.clearance())
-        self.last_distance, self.last_clearance = dist, clear
+        self_clear = float(self.self_clearance())
+        self.last_distance, self.last_clearance, self.last_self_clearance = dist, clear, self_clear
         reached = dist < TARGET_THRESHOLD
-        hit = clear < self.obstacle_radius
+        hit = clear < self.obstacle_radius or self_clear < 0.0        # environment.py:311-343: either collision ends the episode
         reward = 250 if reached else (-1000 if hit else -1 * (dist - TARGET_THRESHOLD))
         return state, reward, 1 if (reached or hit) else 0
 
 
 def build_kinematic(manipulator_file, endeffector_index, fixed_joints, involved_joints, target_position, obstacle_position,
                     initial_joint_positions=None, initial_positions_variation_range=None, link_radius=0.0,
-                    obstacle_radius=OBSTACLE_RADIUS) -> KinematicEnvironment:
+                    obstacle_radius=OBSTACLE_RADIUS, consider_autocollision=False, autocollision_ignore=None) -> KinematicEnvironment:
     """Picklable factory (HostVectorEnv's worker processes call it through functools.partial)."""
     model = compile_chain(load_urdf(manipulator_file), endeffector_index, involved_joints, fixed_joints,
-                          initial_joint_positions, initial_positions_variation_range, link_radius)
+                          initial_joint_positions, initial_positions_variation_range, link_radius, consider_autocollision,
+                          autocollision_ignore or ())
     return KinematicEnvironment(model, target_position, obstacle_position, obstacle_radius)

@@ -5,13 +5,18 @@ robotic_manipulator_rloa/environment/environment.py.
 
 The model keeps the reference's environment RULE for the arm a URDF names — state layout, reward, terminal rule, velocity
 control of the involved joints, held joints — with the commanded velocity applied exactly for one 1/240 s tick. It is NOT a
-port of Bullet: no dynamics (gravity, motor force, solver), no mesh collision, no self-collision.
+port of Bullet: no dynamics (gravity, motor force, solver), no mesh collision. Self-collision is the reference's rule between
+the links' capsules, off by default (compile_chain(consider_autocollision=True), "self pairs" below).
 
   frames     frame 0 is the world (= the root link's frame: the base sits at the origin, environment.py:280-282); frame k + 1
              is the child link frame of driven joint k. Frame k + 1 = frame k . Pre_k . Motion_k(q_k), Pre_k being every constant
              transform between the two (joint origins, constant joints), folded here.
   segments   collision capsules, each in the frame of the last driven joint above it.
   slots      observation slot k of the A position / velocity slots reports joint INDEX k (environment.py:442-444).
+  self pairs segment pairs (s, t), s < t, tested against each other when consider_autocollision is on: the reference tests
+             link i against link j for i, j in 0 .. num_joints - 1 with |i - j| <= 1 left out, contact when the closest distance
+             is below 0 (environment.py:311-343, :394-412; collision_detector.py:63-98). The root link (index -1) takes no part.
+             Contact of a pair here: distance(segment s, segment t) - radius_s - radius_t < 0.
 """
 from __future__ import annotations
 
@@ -32,10 +37,16 @@ HEADER_FLOATS = 16
 JOINT_FLOATS = 24
 SEGMENT_FLOATS = 8
 SLOT_FLOATS = 2
+PAIR_FLOATS = 2
 MAX_JOINTS = 64
 DT = 1.0 / 240.0                 # environment.py:481: one stepSimulation tick
 TARGET_THRESHOLD = 0.05          # environment.py:345-371
 OBSTACLE_RADIUS = 0.06           # the stand-in's (csrc/synth_env.hip)
+# Capsules are fatter than meshes: a pair that is in contact at EVERY pose of this fixed sample (uniform inside the limits,
+# +-pi where there are none) can never be out of contact and is dropped at compile time. Constants, so that one URDF always
+# compiles to one model.
+SELF_PRUNE_SEED = 20240607
+SELF_PRUNE_POSES = 256
 REVOLUTE, PRISMATIC = 0, 1
 _MOVABLE = ("revolute", "continuous", "prismatic")
 
@@ -183,6 +194,8 @@ class ChainSegment:
     a: np.ndarray
     b: np.ndarray
     radius: float
+    link: int = -1               # PyBullet index of the link the capsule belongs to: the joint whose child it is; the root is -1
+    link_name: str = ""
 
 
 @dataclass
@@ -195,6 +208,9 @@ class ChainModel:
     reach: float                             # sum of the translation norms + the end-effector offset
     source: str = ""
     initial_positions_variation_range: Optional[List[float]] = None
+    consider_autocollision: bool = False
+    self_pairs: List[tuple] = field(default_factory=list)            # (s, t), s < t: segment indices tested against each other
+    self_pairs_dropped: List[tuple] = field(default_factory=list)    # (link name, link name) of the pairs the pose sample pruned
     _blob: Optional[np.ndarray] = field(default=None, repr=False, compare=False)
 
     @property
@@ -214,10 +230,10 @@ class ChainModel:
         """The flat float32 blob csrc/chain_env.hip reads (layout: include/naf_hip.h, "chain model blob")."""
         if self._blob is not None:
             return self._blob.copy()
-        A, n_seg = self.A, len(self.segments)
+        A, n_seg, n_pairs = self.A, len(self.segments), len(self.self_pairs)
         head = np.zeros(HEADER_FLOATS)
-        n = HEADER_FLOATS + JOINT_FLOATS * A + (A + 2) + SEGMENT_FLOATS * n_seg + SLOT_FLOATS * A
-        head[:9] = [BLOB_VERSION, A, n_seg, A, self.ee_frame, *self.ee_point, n]
+        n = HEADER_FLOATS + JOINT_FLOATS * A + (A + 2) + SEGMENT_FLOATS * n_seg + SLOT_FLOATS * A + PAIR_FLOATS * n_pairs
+        head[:10] = [BLOB_VERSION, A, n_seg, A, self.ee_frame, *self.ee_point, n, n_pairs]
         parts = [head]
         for j in self.joints:
             rec = np.zeros(JOINT_FLOATS)
@@ -229,6 +245,8 @@ class ChainModel:
             parts.append(np.array([s.frame, *s.a, *s.b, s.radius]))
         for src, const in self.slots:
             parts.append(np.array([src, const]))
+        for pair in self.self_pairs:                                  # (none: the blob is byte for byte the one without the table)
+            parts.append(np.array(pair, float))
         self._blob = np.concatenate(parts).astype(np.float32)
         assert self._blob.size == n
         return self._blob.copy()
@@ -243,7 +261,11 @@ def _compose(Ra, ta, Rb, tb):
 
 def compile_chain(urdf: Urdf, endeffector_index: int, involved_joints: Sequence[int], fixed_joints: Sequence[int] = (),
                   initial_joint_positions: Optional[Sequence[float]] = None,
-                  initial_positions_variation_range: Optional[Sequence[float]] = None, link_radius: float = 0.0) -> ChainModel:
+                  initial_positions_variation_range: Optional[Sequence[float]] = None, link_radius: float = 0.0,
+                  consider_autocollision: bool = False, autocollision_ignore: Sequence = ()) -> ChainModel:
+    """consider_autocollision: the model carries self_pairs (module text) minus the pairs that the fixed pose sample finds in
+    contact at every pose (listed in self_pairs_dropped) and minus autocollision_ignore: pairs of links, each given by name or
+    by PyBullet link index, dropped by hand."""
     path, joints, nj = urdf.path, urdf.joints, len(urdf.joints)
     involved = [int(k) for k in involved_joints]
     A = len(involved)
@@ -335,12 +357,52 @@ def compile_chain(urdf: Urdf, endeffector_index: int, involved_joints: Sequence[
     segments: List[ChainSegment] = []
     for j in joints:
         f, R, t = pose[j.parent]
-        segments.append(ChainSegment(f, t.copy(), t + R @ j.xyz, radius_of(j.parent)))
-    segments.append(ChainSegment(f_ee, pose[ee_link][2].copy(), ee_point.copy(), radius_of(ee_link)))
+        segments.append(ChainSegment(f, t.copy(), t + R @ j.xyz, radius_of(j.parent), joint_of_child.get(j.parent, -1), j.parent))
+    segments.append(ChainSegment(f_ee, pose[ee_link][2].copy(), ee_point.copy(), radius_of(ee_link), int(endeffector_index), ee_link))
     segments.sort(key=lambda s: s.frame)                            # (stable: file order within a frame)
 
     slots = []
     for k in range(A):                                              # environment.py:442-444: slot k <- joint index k
         slots.append((action_of[k], 0.0) if k in action_of else (-1, constant_value(k)))
-    return ChainModel(list(chain_joints), segments, f_ee, ee_point, slots, max(reach, 1e-6), source=os.path.basename(path),
-                      initial_positions_variation_range=None if initial_positions_variation_range is None else var)
+    model = ChainModel(list(chain_joints), segments, f_ee, ee_point, slots, max(reach, 1e-6), source=os.path.basename(path),
+                       initial_positions_variation_range=None if initial_positions_variation_range is None else var)
+    if consider_autocollision:
+        model.consider_autocollision = True
+        _self_pairs(model, urdf, autocollision_ignore)
+    return model
+
+
+def _self_pairs(model: ChainModel, urdf: Urdf, ignore: Sequence) -> None:
+    """Fills model.self_pairs / self_pairs_dropped: the reference's pair rule, the hand-made exceptions, then the pruning."""
+    path, segs = urdf.path, model.segments
+    link_index = {j.child: k for k, j in enumerate(urdf.joints)}
+
+    def index_of(link) -> int:
+        if isinstance(link, str):
+            if link not in link_index:
+                raise InvalidManipulatorFile(f"{path}: autocollision_ignore names the link {link!r}, which is not the child of a "
+                                             "joint of the file (the root link takes no part in self-collision)")
+            return link_index[link]
+        if not 0 <= int(link) < len(urdf.joints):
+            raise InvalidManipulatorFile(f"{path}: autocollision_ignore names link index {link}; the file has links 0 .. "
+                                         f"{len(urdf.joints) - 1}")
+        return int(link)
+
+    ignored = set()
+    for pair in ignore or ():
+        if isinstance(pair, str) or len(pair) != 2:
+            raise InvalidManipulatorFile(f"{path}: autocollision_ignore holds {pair!r}; each entry is a pair of links")
+        ignored.add(frozenset(index_of(l) for l in pair))
+    # environment.py:394-412 / collision_detector.py:63-98: link i against link j, both in 0 .. num_joints - 1, |i - j| <= 1 left out
+    pairs = [(s, t) for s in range(len(segs)) for t in range(s + 1, len(segs))
+             if segs[s].link >= 0 and segs[t].link >= 0 and abs(segs[s].link - segs[t].link) > 1
+             and frozenset((segs[s].link, segs[t].link)) not in ignored]
+    if pairs:
+        from .kinematic import KinematicEnvironment                 # (the twin imports this module: resolved at call time)
+        rng = np.random.default_rng(SELF_PRUNE_SEED)
+        q = np.stack([[rng.uniform(j.lower, j.upper) if j.limited else rng.uniform(-math.pi, math.pi) for j in model.joints]
+                      for _ in range(SELF_PRUNE_POSES)])
+        model.self_pairs = pairs
+        always = np.all(KinematicEnvironment(model, (0, 0, 0), (0, 0, 0)).pair_clearances(q) < 0.0, axis=1)
+        model.self_pairs = [p for p, drop in zip(pairs, always) if not drop]
+        model.self_pairs_dropped = [(segs[s].link_name, segs[t].link_name) for (s, t), drop in zip(pairs, always) if drop]

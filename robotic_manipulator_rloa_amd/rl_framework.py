@@ -290,20 +290,36 @@ class ManipulatorFramework:
                                          obstacle_position: List[float], initial_joint_positions: List[float] = None,
                                          initial_positions_variation_range: List[float] = None, link_radius: float = 0.0,
                                          obstacle_radius: float = 0.06, obstacle_jitter: float = 0.0, max_force: float = 200.,
-                                         visualize: bool = False) -> None:
+                                         visualize: bool = False, consider_autocollision: bool = False,
+                                         autocollision_ignore: Optional[list] = None) -> None:
         """initialize_environment()'s arguments (rl_framework.py:369-417) for the built-in kinematic environment: the arm of
         `manipulator_file` (a URDF) as a serial chain under the reference's environment rule, velocity control applied exactly.
         Not a Bullet port — no dynamics (max_force is accepted and ignored), no mesh collision (links are capsules of their
         primitive collision radius, else link_radius), no GUI (visualize=True is refused). obstacle_jitter: as
-        initialize_synthetic_environment's. One env runs on the host, n_envs=E copies run on the device."""
+        initialize_synthetic_environment's. One env runs on the host, n_envs=E copies run on the device.
+        consider_autocollision: initialize_environment()'s switch — contact between the capsules of two links that are not
+        neighbours ends the episode with -1000 (environment.py:311-371, :394-412); pairs that the capsules keep in contact at
+        every pose are dropped when the model is compiled (env.model.self_pairs_dropped), autocollision_ignore (pairs of link
+        names or link indices) drops more. A start pose in self-contact is refused here."""
         if visualize:
             raise InvalidManipulatorFile('the kinematic environment has no visualisation: pass visualize=False '
                                          '(initialize_environment() opens the PyBullet GUI)')
         args = (manipulator_file, endeffector_index, list(fixed_joints), list(involved_joints), list(target_position),
                 list(obstacle_position), None if initial_joint_positions is None else list(initial_joint_positions),
                 None if initial_positions_variation_range is None else list(initial_positions_variation_range),
-                float(link_radius), float(obstacle_radius))
-        self.env = build_kinematic(*args)
+                float(link_radius), float(obstacle_radius), bool(consider_autocollision),
+                None if autocollision_ignore is None else [tuple(p) for p in autocollision_ignore])
+        env = build_kinematic(*args)
+        if env.model.self_pairs:
+            clear = env.pair_clearances(env.initial_joint_positions)
+            worst = int(np.argmin(clear))
+            if clear[worst] < 0.0:
+                a, b = (env.model.segments[s].link_name for s in env.model.self_pairs[worst])
+                raise ValueError(f'{manipulator_file}: at the initial joint positions the links {a!r} and {b!r} are in '
+                                 f'self-contact (clearance {clear[worst]:.4f} m between their capsules): every episode would end at '
+                                 f'its first step. Choose another start pose or a smaller link_radius, or pass '
+                                 f'autocollision_ignore=[({a!r}, {b!r})]')
+        self.env = env
         self._obstacle_jitter = float(obstacle_jitter)
         self._env_factory = functools.partial(build_kinematic, *args)
         logger.info(f'Kinematic Environment successfully initialized from {manipulator_file} '
