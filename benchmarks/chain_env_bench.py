@@ -8,6 +8,15 @@ count, and a launch loop of the two step kernels for `rocprofv3 --kernel-trace -
   rocprofv3 --kernel-trace --stats -d OUT -- python benchmarks/chain_env_bench.py kernels
       1000 launches each of chain_env_step_kernel for standin8 (A = 8, E = 64) and long32, and of synth_env_step_kernel
       (`--autocollision`: the two arms compiled with their self-collision pairs, 18 and 465: the SC = true instantiation)
+  python benchmarks/chain_env_bench.py step --envs 4096 --launches 4000 [--autocollision]
+      microseconds per naf_chain_env_step launch of --urdf (device events around `--launches` launches with the step counter
+      running, max_frames = 400, N(0, 1) actions; `--repeats` windows after one warm-up window). Two launches per step are
+      enqueued by the host, so at small E the figure is bounded below by launch submission: the kernel's own time comes from
+      `rocprofv3 --kernel-trace --stats -d OUT -- python benchmarks/chain_env_bench.py step ...`, a run of its own, whose
+      maximum per kernel is the launch in which the envs reset (every 400th).
+
+`--target-range X Y Z` / `--obstacle-range X Y Z` (rate, step): half-widths of the boxes every episode draws its target / obstacle
+from (include/naf_hip.h, "Scene ranges"); step then also prints how the episode starts of the run chose their scenes.
 """
 import argparse
 import ctypes
@@ -48,12 +57,70 @@ def rate(a):
         out["self_pairs"] = len(env.model.self_pairs)
         for rep in range(a.repeats):
             run(f"chain_{rep}", env, n, chain=env.model,
-                scene={"target": [0.45, 0.3, 0.6], "obstacle": [0.35, 0.2, 0.45]})
+                scene={"target": [0.45, 0.3, 0.6], "obstacle": [0.35, 0.2, 0.45], **_ranges(a)})
             run(f"standin_{rep}", SyntheticEnvironment(n), n, robot="panda")
     else:
         for rep in range(a.repeats):
             run(f"standin_{rep}", SyntheticEnvironment(a.joints), a.joints, robot="panda")
     print(json.dumps({"envs": a.envs, "batch": a.batch, "steps": a.steps, "warmup": a.warmup, "joints": a.joints, **out}))
+
+
+def _ranges(a) -> dict:
+    if a.target_range is None and a.obstacle_range is None:
+        return {}
+    return {"target_range": a.target_range or [0.0] * 3, "obstacle_range": a.obstacle_range or [0.0] * 3}
+
+
+def step(a):
+    import numpy as np
+    import torch
+    from robotic_manipulator_rloa_amd import _lib
+    from robotic_manipulator_rloa_amd.environment.urdf_chain import compile_chain, load_urdf
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    E, n, stream = a.envs, a.joints, torch.cuda.current_stream().cuda_stream
+    urdf = os.path.abspath(a.urdf) if os.path.isabs(a.urdf) else os.path.join(ROOT, a.urdf)
+    # the start pose and reset ranges of the README's example on the first seven joints, 0 +- 0.1 on any further one
+    init = ([0.0, 0.6, 0.0, -1.2, 0.0, 0.8, 0.0] + [0.0] * n)[:n]
+    var = ([0.1, 0.1, 0.1, 0.1, 0.2, 0.2, 0.2] + [0.1] * n)[:n]
+    model = compile_chain(load_urdf(urdf), n - 1, list(range(n)), [n], init, var, 0.03, consider_autocollision=a.autocollision)
+    blob = np.ascontiguousarray(model.pack())
+    h = ctypes.c_void_p()
+    _lib.check(lib.naf_chain_env_create(blob.ctypes.data, int(blob.size), ctypes.byref(h)), "create")
+    S = 2 * n + 9
+    st = torch.zeros(E, lib.naf_chain_env_state_floats(h), device=dev)
+    torch.manual_seed(5)                                  # the same actions in every run: runs of two builds do the same work
+    obs, act = torch.zeros(E, S, device=dev), torch.randn(E, n, device=dev)
+    rows = torch.zeros(E, lib.naf_replay_row_floats(S, n), device=dev)
+    ctr = torch.zeros(1, dtype=torch.int64, device=dev)
+    centre = [0.45, 0.3, 0.6, 0.35, 0.2, 0.45]
+    scene = (ctypes.c_float * 8)(*centre, 0.0, 0.06)
+    ranges = _ranges(a)
+    if ranges:
+        r7 = (ctypes.c_float * 7)(*ranges["target_range"], *ranges["obstacle_range"], 0.02)
+        _lib.check(lib.naf_chain_env_set_scene_ranges(h, r7), "set_scene_ranges")
+    _lib.check(lib.naf_chain_env_reset(h, st.data_ptr(), obs.data_ptr(), E, scene, 5, 0, stream), "reset")
+    times, starts = [], 0
+    for w in range(a.repeats + 1):                        # window 0 warms up
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        before = st[:, n + 8].sum().item()
+        t0.record()
+        for _ in range(a.launches):
+            _lib.check(lib.naf_chain_env_step(h, st.data_ptr(), act.data_ptr(), rows.data_ptr(), obs.data_ptr(), E, 5, ctr.data_ptr(),
+                                              400, None, 0, stream), "step")
+            _lib.check(lib.naf_counter_add(ctr.data_ptr(), 1, stream), "counter_add")
+        t1.record()
+        torch.cuda.synchronize()
+        if w:
+            times.append(round(1e3 * t0.elapsed_time(t1) / a.launches, 3))
+        starts += int(st[:, n + 8].sum().item() - before)
+    out = {"arm": os.path.basename(urdf), "envs": E, "autocollision": a.autocollision, "self_pairs": len(model.self_pairs),
+           "launches": a.launches, "ranges": ranges or None, "us_per_step_and_counter_launch": times, "episode_starts": starts}
+    if ranges:      # the scenes the envs hold now: the centres, exactly, are fallbacks
+        s = st[:, n:n + 6].cpu().numpy()
+        out["fallback_share_now"] = round(float(np.mean(np.all(s == np.float32(centre), axis=1))), 4)
+    lib.naf_chain_env_destroy(h)
+    print(json.dumps(out))
 
 
 def kernels(a):
@@ -94,7 +161,7 @@ def kernels(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["rate", "kernels"])
+    ap.add_argument("what", choices=["rate", "kernels", "step"])
     ap.add_argument("--urdf", default=os.path.join("tests", "golden", "urdf", "iiwa_like7.urdf"))
     ap.add_argument("--joints", type=int, default=7)
     ap.add_argument("--envs", type=int, default=64)
@@ -106,8 +173,10 @@ def main():
     ap.add_argument("--standin-only", action="store_true")
     ap.add_argument("--autocollision", action="store_true")
     ap.add_argument("--arm", default="", help="rate: a fixture arm of tests/golden/urdf by name, --joints its joint count")
+    ap.add_argument("--target-range", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))
+    ap.add_argument("--obstacle-range", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))
     a = ap.parse_args()
-    (rate if a.what == "rate" else kernels)(a)
+    {"rate": rate, "kernels": kernels, "step": step}[a.what](a)
 
 
 if __name__ == "__main__":

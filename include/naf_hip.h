@@ -67,7 +67,7 @@ typedef struct {
 /* ---- library ------------------------------------------------------------------------------ */
 /* Bumped whenever a signature or a struct in this header changes; the ctypes host compares the library's answer with
  * the value in this header and refuses a mismatch (a stale .so would otherwise be called with wrong argument lists). */
-#define NAF_HIP_ABI_VERSION 37
+#define NAF_HIP_ABI_VERSION 38
 int naf_hip_abi_version(void);
 /* "gfx950" — the only architecture this library carries code objects for */
 const char* naf_hip_arch(void);
@@ -666,7 +666,7 @@ int naf_synth_env_reset(float* env_state, float* obs, int E, int A, uint64_t see
                         const float* preset_host, int preset_floats, void* stream);
 int naf_synth_env_state_floats(int A);
 
-/* ---- kinematic environment of a URDF manipulator (ABI 36; self-collision and probe: ABI 37) ----------------------------------------------------------------
+/* ---- kinematic environment of a URDF manipulator (ABI 36; self-collision and probe: ABI 37; scene ranges: ABI 38) ----------------------------------------------------------------
  * E copies of the serial chain environment/urdf_chain.py compiles from the user's URDF, stepped on the device under the
  * reference's environment rule (environment/environment.py:431-485: state layout, reward, terminal rule, velocity control
  * of the involved joints, held joints). Kinematic — the commanded velocity is applied exactly for one 1/240 s tick, then the
@@ -712,7 +712,28 @@ int naf_synth_env_state_floats(int A);
  *                 itself: a reset pose in self-contact ends its episode at the next step.
  *   probe       : out [E][NAF_CHAIN_PROBE_FLOATS] = [end-effector xyz | min over segments of (distance to the obstacle centre -
  *                 capsule radius) - obstacle radius (obstacle contact iff < 0) | min over the pairs of the pair clearance
- *                 (self-contact iff < 0; +inf when P = 0)] at the joint values and scene in env_state; changes no state. */
+ *                 (self-contact iff < 0; +inf when P = 0)] at the joint values and scene in env_state; changes no state.
+ *
+ * Scene ranges (ABI 38): a new target and obstacle at the start of every episode — the reset and every auto-reset inside step.
+ *   set_scene_ranges : ranges_host = NAF_CHAIN_RANGE_FLOATS HOST floats [target half-widths xyz | obstacle half-widths xyz |
+ *                 margin m], kept in the handle; NULL clears them. A negative or non-finite value: NAF_ERR_ARG, the handle
+ *                 unchanged. With all six half-widths 0 (or never set, or cleared) reset and step launch exactly the kernels
+ *                 described above. Otherwise the handle also keeps a copy of the last reset's scene_host: its target and obstacle
+ *                 are the centres of the two boxes and the fallback scene. reset with a non-zero obstacle jitter then returns
+ *                 NAF_ERR_ARG, and step without a reset since the ranges were set returns NAF_ERR_STATE.
+ *   the rule    : the joints are drawn first, as without ranges: the start pose q0. Then NAF_CHAIN_SCENE_TRIES candidates c = 0 ..:
+ *                   target_c = target + (2u - 1) * target half-widths,  obstacle_c = obstacle + (2u - 1) * obstacle half-widths,
+ *                 each component ONE fmaf; the uniforms are Philox4x32-10 keyed as the joint draw — counter (ctr lo, ctr hi, env,
+ *                 domain), key = seed, ctr = reset's `counter` argument or, in an auto-reset, step counter * 0x9E3779B97F4A7C15 +
+ *                 episodes finished — with domain 'SCEN' (0x5343454E) + 2c for the target and 'SCEN' + 2c + 1 for the obstacle,
+ *                 words 0..2 = x, y, z as naf_u01 maps them; a half-width of 0 leaves the centre. Candidate c is admissible when
+ *                   (1) |ee(q0) - target_c| >= 0.05 + m                       (the episode does not end with +250 at once)
+ *                   (2) min over capsules (dist(segment, obstacle_c) - radius) - obstacle radius >= m     (no contact at the start)
+ *                   (3) |target_c - obstacle_c| >= obstacle radius + 0.05 + m                (the target is not inside the obstacle)
+ *                 The first admissible candidate is the episode's scene; if none is, the scene is scene_host's target / obstacle.
+ *                 Always NAF_CHAIN_SCENE_TRIES tries, all tested during the ONE walk of the reset pose. The row that ends an
+ *                 episode carries the old scene in next_state; obs_next and env_state [A .. A+6) carry the new one; envs whose
+ *                 episode goes on keep theirs. The env_state record does not change. */
 #define NAF_CHAIN_BLOB_VERSION 1
 #define NAF_CHAIN_HEADER_FLOATS 16
 #define NAF_CHAIN_JOINT_FLOATS 24
@@ -729,6 +750,8 @@ int naf_synth_env_state_floats(int A);
 #define NAF_CHAIN_ERR_PAIRS (-19)    /* pair count or table size, an index out of range or not an integer, s >= t, a pair twice */
 #define NAF_CHAIN_ERR_LDS (-20)      /* create: P > 0 and one env's capsule end points exceed a workgroup's LDS */
 #define NAF_CHAIN_PROBE_FLOATS 5
+#define NAF_CHAIN_SCENE_TRIES 8
+#define NAF_CHAIN_RANGE_FLOATS 7
 typedef struct naf_chain_env naf_chain_env_t;
 int naf_chain_env_model_check(const float* model_host, int n_floats);
 int naf_chain_env_create(const float* model_host, int n_floats, naf_chain_env_t** out);
@@ -740,6 +763,7 @@ int naf_chain_env_step(naf_chain_env_t* h, float* env_state, const float* action
                        uint64_t seed, const uint64_t* counter_dev, int max_frames, naf_episode_record_t* records,
                        int record_slots, void* stream);
 int naf_chain_env_probe(naf_chain_env_t* h, const float* env_state, float* out, int E, void* stream);
+int naf_chain_env_set_scene_ranges(naf_chain_env_t* h, const float* ranges_host);
 
 /* ---- one-shot gradient all-reduce over peer-mapped memory (no reference counterpart) ----------
  * The data-parallel exchange that follows loss.backward() (naf_algorithm.py:207-210 on every rank): sum of the flat

@@ -256,6 +256,7 @@ _PROTOS = {
     "naf_chain_env_reset": [_vp, _vp, _vp, _i, _vp, _u64, _u64, _vp],
     "naf_chain_env_step": [_vp, _vp, _vp, _vp, _vp, _i, _u64, _vp, _i, _vp, _i, _vp],
     "naf_chain_env_probe": [_vp, _vp, _vp, _i, _vp],
+    "naf_chain_env_set_scene_ranges": [_vp, _vp],
 }
 _RESTYPES = {"naf_hip_arch": C.c_char_p}
 EXPORTED_SYMBOLS = tuple(_PROTOS)

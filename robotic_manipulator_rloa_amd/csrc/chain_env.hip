@@ -20,6 +20,13 @@
 // row and no per-lane array is indexed at run time — and the workgroup has W waves: wave 0 walks, a barrier, then pair p is
 // tested by wave p mod W (lane = env, pair indices and radii through uniform loads), each wave leaves the minimum of its pairs'
 // clearances in LDS, a barrier, and wave 0 takes the minimum of the W before it writes reward and done.
+//
+// Scene ranges (naf_chain_env_set_scene_ranges, a non-zero half-width) are a further instantiation of the reset and step kernels,
+// SCENE = true; with all half-widths zero the launch is the SCENE = false one. Every episode then starts with a scene of its
+// own: after the joint draw the CH_TRIES obstacle candidates are drawn, the ONE walk of the reset pose collects each
+// candidate's clearance beside the end effector (CH_TRIES clearances in registers, every loop over them unrolled), and the first
+// candidate that meets the three conditions of include/naf_hip.h becomes the scene, the nominal scene if none does. No trip count
+// depends on a draw. In an SC workgroup this is the walking wave's business alone, as the auto-reset already is.
 #include "common.h"
 #include "../../include/naf_hip.h"
 
@@ -34,21 +41,43 @@
 #define CH_HDR NAF_CHAIN_HEADER_FLOATS
 #define CH_JNT NAF_CHAIN_JOINT_FLOATS
 #define CH_SEG NAF_CHAIN_SEGMENT_FLOATS
+#define CH_TRIES NAF_CHAIN_SCENE_TRIES
+#define CH_REACHED 0.05f                     // the target threshold of the reward rule
 
 struct naf_chain_env {
     float* model_dev;
     int n_floats, A, n_seg;
     int n_pairs, lanes, waves;      // P; with P > 0: envs per workgroup (64, 32, .. 1) and waves per workgroup
+    float ranges[NAF_CHAIN_RANGE_FLOATS];      // set_scene_ranges: target half-widths | obstacle half-widths | margin
+    float centre[6];                // target | obstacle of the last reset's scene_host: the boxes' centres and the fallback
+    bool scene_on, scene_ready;     // a half-width is non-zero; a reset has run since the ranges were set
 };
 #ifndef CH_MAX_WAVES
 #define CH_MAX_WAVES 16                      // (-DCH_MAX_WAVES=1 through NAF_BUILD_DEFINES: the one-wave pair loop, NOTEBOOK §15)
 #endif
+// A SCENE launch holds CH_TRIES candidates and clearances through the walk of a reset pose: its workgroups are at most 8 waves
+// (SC; the pair phase takes any wave count and its minimum does not depend on it) or one (no SC), so that the register
+// budget, which the launch bound sets, holds them without scratch.
+#define CH_SCENE_WAVES (CH_MAX_WAVES < 8 ? CH_MAX_WAVES : 8)
 #define CH_PAIRS_PER_WAVE 16                 // waves = ceil(P / this), at most CH_MAX_WAVES
 #define CH_MAX_DYN_LDS (144 * 1024)          // of the CU's 160 KiB; the SC kernels have no static LDS beside it
 
 struct ChainScene {
     float v[NAF_CHAIN_SCENE_FLOATS];    // target | obstacle | jitter | obstacle radius
 };
+
+// what a SCENE launch draws from: target | obstacle centres, target | obstacle half-widths, margin
+struct ChainRanges {
+    float centre[6], half[6], margin;
+};
+// the obstacle candidates of one reset and, after the walk, each one's min over the capsules of (distance - capsule radius)
+struct SceneCand {
+    float o[CH_TRIES][3], clear[CH_TRIES];
+};
+// The kernels take the ranges as a trailing parameter PACK: one ChainRanges in a SCENE launch, nothing in a SCENE = false one,
+// whose kernel arguments are then exactly those of the kernels before the ranges existed.
+template <class... Rest>
+__device__ static inline const ChainRanges& scene_ranges(const ChainRanges& rg, const Rest&...) { return rg; }
 
 __host__ __device__ static inline int ch_off_begin(int A) { return CH_HDR + CH_JNT * A; }
 __host__ __device__ static inline int ch_off_seg(int A) { return ch_off_begin(A) + A + 2; }
@@ -115,9 +144,9 @@ struct WalkAux {
 };
 
 // contact of the capsules of frame f with the obstacle sphere, and the end-effector point when it lives in f
-template <bool SC, bool PROBE>
+template <bool SC, bool PROBE, bool SCENE = false>
 __device__ static inline bool frame_geometry(const float* __restrict__ model, int A, int f, const Frame& F, float ox, float oy,
-                                             float oz, float orad, int ee_frame, float* ee, WalkAux& aux) {
+                                             float oz, float orad, int ee_frame, float* ee, WalkAux& aux, SceneCand* cand = nullptr) {
     const float* begin = model + ch_off_begin(A);
     const float* segs = model + ch_off_seg(A);
     const int s0 = (int)begin[f], s1 = (int)begin[f + 1];
@@ -139,6 +168,20 @@ __device__ static inline bool frame_geometry(const float* __restrict__ model, in
             w[3 * aux.lanes] = bx; w[4 * aux.lanes] = by; w[5 * aux.lanes] = bz;
         }
         if constexpr (PROBE) aux.clear = fminf(aux.clear, sqrtf(d2) - g[7]);
+        if constexpr (SCENE) {
+            // seg_point_dist2 for CH_TRIES centres against ONE segment: its direction and 1 / |u|^2 are computed once, and the
+            // root is the hardware's (1 ulp): both far inside the band in which the choice is compared with the twin's
+            const float ux = bx - ax, uy = by - ay, uz = bz - az;
+            const float den = ux * ux + uy * uy + uz * uz;
+            const float inv = den > 0.f ? 1.f / den : 0.f;
+#pragma unroll
+            for (int c = 0; c < CH_TRIES; ++c) {
+                const float wx = cand->o[c][0] - ax, wy = cand->o[c][1] - ay, wz = cand->o[c][2] - az;
+                const float t = fminf(1.f, fmaxf(0.f, (wx * ux + wy * uy + wz * uz) * inv));
+                const float dx = wx - t * ux, dy = wy - t * uy, dz = wz - t * uz;
+                cand->clear[c] = fminf(cand->clear[c], __builtin_amdgcn_sqrtf(dx * dx + dy * dy + dz * dz) - g[7]);
+            }
+        }
     }
     if (f == ee_frame) {
         ee[0] = F.px + F.r00 * model[5] + F.r01 * model[6] + F.r02 * model[7];
@@ -151,14 +194,14 @@ __device__ static inline bool frame_geometry(const float* __restrict__ model, in
 // Walks the chain at the joint values in st[0 .. A): writes the position slots, the constants' slots (velocity 0), the end
 // effector, target and obstacle into the observation `o` (not with PROBE: o is unused); the DRIVEN joints' velocity slots are the
 // caller's. Returns contact with the obstacle.
-template <bool SC, bool PROBE>
+template <bool SC, bool PROBE, bool SCENE = false>
 __device__ static inline bool chain_walk(const float* __restrict__ model, int A, int n_seg, const float* st, float* o, float* ee,
-                                         WalkAux& aux) {
+                                         WalkAux& aux, SceneCand* cand = nullptr) {
     const int ee_frame = (int)model[4];
     const float ox = st[A + 3], oy = st[A + 4], oz = st[A + 5], orad = st[A + 6];
     Frame F = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
     ee[0] = ee[1] = ee[2] = 0.f;
-    bool hit = frame_geometry<SC, PROBE>(model, A, 0, F, ox, oy, oz, orad, ee_frame, ee, aux);
+    bool hit = frame_geometry<SC, PROBE, SCENE>(model, A, 0, F, ox, oy, oz, orad, ee_frame, ee, aux, cand);
     for (int m = 0; m < A; ++m) {
         const float* j = model + CH_HDR + m * CH_JNT;
         const float q = st[m];
@@ -205,7 +248,7 @@ __device__ static inline bool chain_walk(const float* __restrict__ model, int A,
             F.r21 = G.r20 * m01 + G.r21 * m11 + G.r22 * m21;
             F.r22 = G.r20 * m02 + G.r21 * m12 + G.r22 * m22;
         }
-        hit |= frame_geometry<SC, PROBE>(model, A, m + 1, F, ox, oy, oz, orad, ee_frame, ee, aux);
+        hit |= frame_geometry<SC, PROBE, SCENE>(model, A, m + 1, F, ox, oy, oz, orad, ee_frame, ee, aux, cand);
     }
     if constexpr (!PROBE) {
         const float* slots = model + ch_off_slot(A, n_seg);
@@ -265,8 +308,58 @@ __device__ static inline void chain_reset_one(const float* __restrict__ model, f
     *(double*)(st + ch_off_score(A)) = 0.0;
 }
 
-__global__ void chain_env_reset_kernel(const float* __restrict__ model, float* env_state, float* obs, int E, int A, int n_seg,
-                                       uint64_t seed, uint64_t ctr, const ChainScene scene) {
+// centre + (2u - 1) half-width of the three components: ONE rounding each, a half-width of 0 leaves the centre
+__device__ static inline void scene_point(const Philox4& p, const float* centre, const float* half, float* out) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[k] = fmaf(naf_u01(p.v[k]) * 2.f - 1.f, half[k], centre[k]);
+}
+
+// The walk of a reset pose (st[0 .. A) drawn by chain_reset_one with the same e, seed, ctr) that also chooses the episode's scene:
+// the first of CH_TRIES candidates with (1) |ee - target| >= 0.05 + m, (2) clearance - obstacle radius >= m, (3) |target -
+// obstacle| >= obstacle radius + 0.05 + m, else the centres. Writes the scene into st[A .. A+6) and the observation's slots.
+__device__ static inline void chain_scene_walk(const float* __restrict__ model, int A, int n_seg, float* st, float* o, float* ee,
+                                               WalkAux& aux, const ChainRanges& rg, int e, uint64_t seed, uint64_t ctr) {
+    SceneCand cand;
+#pragma unroll
+    for (int c = 0; c < CH_TRIES; ++c) {
+        const Philox4 p = philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)e, 0x5343454Eu + 2 * c + 1, (uint32_t)seed,
+                                        (uint32_t)(seed >> 32));
+        scene_point(p, rg.centre + 3, rg.half + 3, cand.o[c]);
+        cand.clear[c] = INFINITY;
+    }
+    chain_walk<false, false, true>(model, A, n_seg, st, o, ee, aux, &cand);
+    const float orad = st[A + 6];
+    const float far1 = CH_REACHED + rg.margin, far3 = orad + CH_REACHED + rg.margin;
+    float sc[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) sc[k] = rg.centre[k];
+    bool found = false;
+#pragma unroll
+    for (int c = 0; c < CH_TRIES; ++c) {
+        const Philox4 p = philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)e, 0x5343454Eu + 2 * c, (uint32_t)seed,
+                                        (uint32_t)(seed >> 32));
+        float t[3];
+        scene_point(p, rg.centre, rg.half, t);
+        const float ax = ee[0] - t[0], ay = ee[1] - t[1], az = ee[2] - t[2];
+        const float bx = t[0] - cand.o[c][0], by = t[1] - cand.o[c][1], bz = t[2] - cand.o[c][2];
+        const bool ok = sqrtf(ax * ax + ay * ay + az * az) >= far1 && cand.clear[c] - orad >= rg.margin &&
+                        sqrtf(bx * bx + by * by + bz * bz) >= far3;
+        const bool take = ok && !found;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            sc[k] = take ? t[k] : sc[k];
+            sc[3 + k] = take ? cand.o[c][k] : sc[3 + k];
+        }
+        found |= ok;
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) { st[A + k] = sc[k]; o[2 * A + 3 + k] = sc[k]; }
+}
+
+template <bool SCENE, class... Rg>
+__global__ void __launch_bounds__(SCENE ? 64 : 1024)
+chain_env_reset_kernel(const float* __restrict__ model, float* env_state, float* obs, int E, int A, int n_seg,
+                                       uint64_t seed, uint64_t ctr, const ChainScene scene, const Rg... rg) {
     int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= E) return;
     const int nst = ch_state_floats(A);
@@ -282,17 +375,20 @@ __global__ void chain_env_reset_kernel(const float* __restrict__ model, float* e
     chain_reset_one(model, st, o, e, A, seed, ctr);
     float ee[3];
     WalkAux aux = {nullptr, 0, 0.f};
-    chain_walk<false, false>(model, A, n_seg, st, o, ee, aux);
+    if constexpr (SCENE)
+        chain_scene_walk(model, A, n_seg, st, o, ee, aux, scene_ranges(rg...), e, seed, ctr);
+    else
+        chain_walk<false, false>(model, A, n_seg, st, o, ee, aux);
 }
 
 // SC = false: one wave per workgroup, lane = env. SC = true: `lanes` envs per workgroup (lane < lanes of every wave), wave 0 is
 // the env's walker and the only one that touches global memory; the others join it for the pair phase.
-template <bool SC>
-__global__ void __launch_bounds__(64 * CH_MAX_WAVES)
+template <bool SC, bool SCENE, class... Rg>
+__global__ void __launch_bounds__(SCENE ? (SC ? 64 * CH_SCENE_WAVES : 64) : 64 * CH_MAX_WAVES)
 chain_env_step_kernel(const float* __restrict__ model, float* env_state, const float* __restrict__ actions,
                       float* __restrict__ out_rows, float* __restrict__ obs_next, int E, int A, int n_seg, int row_floats,
                       uint64_t seed, const uint64_t* counter_dev, int max_frames, naf_episode_record_t* __restrict__ records,
-                      int record_slots, int n_pairs, int lanes) {
+                      int record_slots, int n_pairs, int lanes, const Rg... rg) {
     extern __shared__ __attribute__((aligned(16))) float ch_lds[];
     int e, lane = 0;
     bool active = true, walker = true;
@@ -373,7 +469,11 @@ chain_env_step_kernel(const float* __restrict__ model, float* env_state, const f
         // episode over (terminal state, or the frame budget of NAFAgent.run, naf_algorithm.py:249): auto-reset
         st[A + 8] += 1.f;
         chain_reset_one(model, st, ob, e, A, seed, ctr * 0x9E3779B97F4A7C15ull + (uint64_t)st[A + 8]);
-        chain_walk<false, false>(model, A, n_seg, st, ob, ee, aux);
+        if constexpr (SCENE)
+            chain_scene_walk(model, A, n_seg, st, ob, ee, aux, scene_ranges(rg...), e, seed,
+                             ctr * 0x9E3779B97F4A7C15ull + (uint64_t)st[A + 8]);
+        else
+            chain_walk<false, false>(model, A, n_seg, st, ob, ee, aux);
     } else {
         for (int k = 0; k < S; ++k) ob[k] = o2[k];
     }
@@ -483,7 +583,8 @@ static int ch_raise_lds_limit() {
     if (e != hipSuccess) return (int)e;
     if (dev < 0 || dev >= 64) return NAF_ERR_ARG;
     if (raised_dev[dev]) return NAF_OK;
-    const void* ks[2] = {(const void*)chain_env_step_kernel<true>, (const void*)chain_env_probe_kernel<true>};
+    const void* ks[3] = {(const void*)chain_env_step_kernel<true, false>, (const void*)chain_env_step_kernel<true, true, ChainRanges>,
+                         (const void*)chain_env_probe_kernel<true>};
     for (const void* k : ks) {
         e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, CH_MAX_DYN_LDS);
         if (e != hipSuccess) return (int)e;
@@ -535,14 +636,43 @@ extern "C" int naf_chain_env_destroy(naf_chain_env_t* h) {
 
 extern "C" int naf_chain_env_state_floats(const naf_chain_env_t* h) { return h ? ch_state_floats(h->A) : NAF_ERR_ARG; }
 
+extern "C" int naf_chain_env_set_scene_ranges(naf_chain_env_t* h, const float* ranges_host) {
+    if (!h) return NAF_ERR_ARG;
+    bool on = false;
+    for (int k = 0; ranges_host && k < NAF_CHAIN_RANGE_FLOATS; ++k) {
+        if (!std::isfinite(ranges_host[k]) || ranges_host[k] < 0.f) return NAF_ERR_ARG;
+        on |= k < 6 && ranges_host[k] > 0.f;
+    }
+    for (int k = 0; k < NAF_CHAIN_RANGE_FLOATS; ++k) h->ranges[k] = ranges_host ? ranges_host[k] : 0.f;
+    h->scene_on = on;
+    h->scene_ready = false;
+    return NAF_OK;
+}
+
+static ChainRanges ch_ranges(const naf_chain_env* h) {
+    ChainRanges rg;
+    for (int k = 0; k < 6; ++k) { rg.centre[k] = h->centre[k]; rg.half[k] = h->ranges[k]; }
+    rg.margin = h->ranges[6];
+    return rg;
+}
+
 extern "C" int naf_chain_env_reset(naf_chain_env_t* h, float* env_state, float* obs, int E, const float* scene_host, uint64_t seed,
                                    uint64_t counter, void* stream) {
     if (!h || !env_state || !obs || !scene_host || E <= 0) return NAF_ERR_ARG;
     ChainScene sc;
     for (int k = 0; k < NAF_CHAIN_SCENE_FLOATS; ++k) sc.v[k] = scene_host[k];
     if (!(sc.v[7] >= 0.f) || !(sc.v[6] >= 0.f)) return NAF_ERR_ARG;
-    chain_env_reset_kernel<<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(h->model_dev, env_state, obs, E, h->A, h->n_seg, seed,
-                                                                          counter, sc);
+    if (h->scene_on) {
+        if (sc.v[6] != 0.f) return NAF_ERR_ARG;      // the jitter is drawn once per env, the scene every episode: one or the other
+        for (int k = 0; k < 6; ++k)
+            if (!std::isfinite(sc.v[k])) return NAF_ERR_ARG;
+        for (int k = 0; k < 6; ++k) h->centre[k] = sc.v[k];
+        h->scene_ready = true;
+        chain_env_reset_kernel<true, ChainRanges><<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(h->model_dev, env_state, obs, E, h->A, h->n_seg,
+                                                                                    seed, counter, sc, ch_ranges(h));
+    } else
+        chain_env_reset_kernel<false><<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(h->model_dev, env_state, obs, E, h->A, h->n_seg,
+                                                                                     seed, counter, sc);
     NAF_CHECK_LAUNCH();
     return NAF_OK;
 }
@@ -555,15 +685,27 @@ extern "C" int naf_chain_env_step(naf_chain_env_t* h, float* env_state, const fl
     const int A = h->A;
     const int rf = naf_replay_row_floats(2 * A + 9, A);
     if (rf <= 0) return NAF_ERR_ARG;
-    if (h->n_pairs > 0)
-        chain_env_step_kernel<true><<<(E + h->lanes - 1) / h->lanes, 64 * h->waves, ch_lds_bytes(h->n_seg, h->lanes, h->waves),
+    if (h->scene_on) {
+        if (!h->scene_ready) return NAF_ERR_STATE;
+        const int waves = std::min(h->waves, CH_SCENE_WAVES);
+        if (h->n_pairs > 0)
+            chain_env_step_kernel<true, true, ChainRanges><<<(E + h->lanes - 1) / h->lanes, 64 * waves, ch_lds_bytes(h->n_seg, h->lanes, waves),
+                                                (hipStream_t)stream>>>(
+                h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
+                record_slots, h->n_pairs, h->lanes, ch_ranges(h));
+        else
+            chain_env_step_kernel<false, true, ChainRanges><<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(
+                h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
+                record_slots, 0, 64, ch_ranges(h));
+    } else if (h->n_pairs > 0)
+        chain_env_step_kernel<true, false><<<(E + h->lanes - 1) / h->lanes, 64 * h->waves, ch_lds_bytes(h->n_seg, h->lanes, h->waves),
                                       (hipStream_t)stream>>>(h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf,
                                                              seed, counter_dev, max_frames, records, record_slots, h->n_pairs,
                                                              h->lanes);
     else
-        chain_env_step_kernel<false><<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(h->model_dev, env_state, actions, out_rows,
-                                                                                    obs_next, E, A, h->n_seg, rf, seed, counter_dev,
-                                                                                    max_frames, records, record_slots, 0, 64);
+        chain_env_step_kernel<false, false><<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(
+            h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
+            record_slots, 0, 64);
     NAF_CHECK_LAUNCH();
     return NAF_OK;
 }

@@ -805,13 +805,17 @@ class DeviceEnvLoop:
     def __init__(self, learner: Learner, replay: Optional[ReplayBuffer], n_envs: int, seed: int, max_frames: int = 400,
                  noise_scale: float = 1.0, use_graph: bool = True, robot: str = "kuka", obstacle_jitter: float = 0.0,
                  preset: Optional[List[float]] = None, variation: Optional[List[float]] = None, records: bool = False,
-                 drain_every: int = 64, chain=None, target=None, obstacle=None, obstacle_radius: float = 0.06):
+                 drain_every: int = 64, chain=None, target=None, obstacle=None, obstacle_radius: float = 0.06,
+                 target_range=None, obstacle_range=None, scene_margin: float = 0.02):
         """replay=None: no transitions are appended (evaluation). preset: 14 floats [initial joint positions(8) | target |
         obstacle] instead of a named robot's. variation: per-joint half-width of the reset range (None: 0.1 everywhere,
         the stand-in's historical value).
         chain: an environment.urdf_chain.ChainModel — the envs are E copies of that arm (csrc/chain_env.hip: the blob is checked
         and uploaded once, here) in the scene target / obstacle / obstacle_radius / obstacle_jitter; robot, preset and variation
-        (the stand-in's) are then unused: initial positions and reset ranges are the model's."""
+        (the stand-in's) are then unused: initial positions and reset ranges are the model's.
+        target_range / obstacle_range (chain only): half-widths xyz of the boxes around target / obstacle from which every
+        episode of every env draws its scene, kept scene_margin clear of the start pose (include/naf_hip.h, "Scene ranges");
+        None or zeros: the scene is fixed and the launches are those of a loop without them."""
         self.L, self.replay, self.E = learner, replay, int(n_envs)
         lay, dev = learner.lay, learner.dev
         self.lib = learner.lib
@@ -822,8 +826,10 @@ class DeviceEnvLoop:
         self.chain, self._chain_env = chain, None
         import ctypes
         if chain is not None:
-            self._open_chain(chain, target, obstacle, obstacle_radius, obstacle_jitter)
+            self._open_chain(chain, target, obstacle, obstacle_radius, obstacle_jitter, target_range, obstacle_range, scene_margin)
             nst = self.lib.naf_chain_env_state_floats(self._chain_env)
+        elif target_range is not None or obstacle_range is not None:
+            raise ValueError("DeviceEnvLoop: target_range / obstacle_range belong to a chain model's scene")
         elif lay.A > 8:
             raise _lib.NafHipError(f"the on-device stand-in environment models arms of up to 8 joints (action_size {lay.A}): drive "
                                    "such an agent through run() / run_host_vectorized with a host environment")
@@ -852,7 +858,8 @@ class DeviceEnvLoop:
             self._pin_i = 0
         self.reset()
 
-    def _open_chain(self, chain, target, obstacle, obstacle_radius, obstacle_jitter) -> None:
+    def _open_chain(self, chain, target, obstacle, obstacle_radius, obstacle_jitter, target_range=None, obstacle_range=None,
+                    scene_margin=0.02) -> None:
         import ctypes
         lay = self.L.lay
         if chain.A != lay.A or chain.state_size != lay.S:
@@ -866,6 +873,17 @@ class DeviceEnvLoop:
         self._chain_env = handle
         self.scene = [float(v) for v in target] + [float(v) for v in obstacle] + [float(obstacle_jitter), float(obstacle_radius)]
         self._scene = (ctypes.c_float * 8)(*self.scene)
+        ranges = [float(v) for r in (target_range, obstacle_range) for v in ((0.0, 0.0, 0.0) if r is None else r)]
+        if len(ranges) != 6:
+            raise ValueError("DeviceEnvLoop(chain=...): target_range and obstacle_range are half-widths xyz")
+        if any(ranges):
+            # before the first reset(), hence before capture: the handle keeps them, and the saved position's scene carries
+            # them (a loop without ranges keeps exactly the scene it had)
+            ranges.append(float(scene_margin))
+            if obstacle_jitter:
+                raise ValueError("DeviceEnvLoop(chain=...): obstacle_jitter and scene ranges exclude each other")
+            check(self.lib.naf_chain_env_set_scene_ranges(handle, (ctypes.c_float * 7)(*ranges)), "chain_env_set_scene_ranges")
+            self.scene = self.scene + ranges
 
     def __del__(self):
         if getattr(self, "_chain_env", None) is not None:

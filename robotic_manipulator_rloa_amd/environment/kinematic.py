@@ -10,6 +10,8 @@ reference's rule (environment.py:311-343, :394-412) between the capsules of mode
            (environment.py:442-451)
   reward = +250 reached (dist < 0.05) | -1000 obstacle contact or self-contact | -(dist - 0.05), done on any of the three
            (environment.py:311-371, :416-429)
+With target_range / obstacle_range every episode gets a scene of its own: choose_scene below is the rule's float64 statement
+(include/naf_hip.h, "Scene ranges", is the kernel's).
 """
 from __future__ import annotations
 
@@ -18,7 +20,8 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .urdf_chain import DT, OBSTACLE_RADIUS, PRISMATIC, TARGET_THRESHOLD, ChainModel, axis_rotation, compile_chain, load_urdf
+from .urdf_chain import (DT, OBSTACLE_RADIUS, PRISMATIC, SCENE_TRIES, TARGET_THRESHOLD, ChainModel, axis_rotation, compile_chain,
+                         load_urdf)
 
 
 def segment_point_distance2(a: np.ndarray, b: np.ndarray, c: np.ndarray):
@@ -55,15 +58,67 @@ def segment_segment_distance2(a1: np.ndarray, b1: np.ndarray, a2: np.ndarray, b2
     return best
 
 
+SCENE_CONDITIONS = ("the target is within reach of the start pose's end effector", "the obstacle touches the arm at the start pose",
+                    "the target lies inside the obstacle")
+
+
+def choose_scene(twin: "KinematicEnvironment", q0, uniforms):
+    """The scene of an episode that starts at the joint values q0, from uniforms[K, 6] in [0, 1) — row c: target xyz | obstacle
+    xyz of candidate c, K <= SCENE_TRIES rows:
+      target_c = target_centre + (2u - 1) * target_range,  obstacle_c = obstacle_centre + (2u - 1) * obstacle_range
+    (a half-width of 0 leaves the centre). margins[c] = how far candidate c is on the admissible side of
+      (1) |ee(q0) - target_c| >= 0.05 + m     (2) clearance(q0, obstacle_c) - obstacle radius >= m
+      (3) |target_c - obstacle_c| >= obstacle radius + 0.05 + m,      m = scene_margin;
+    admissible = all three >= 0. Returns (target, obstacle, index, margins[K, 3]): the first admissible candidate, or the
+    centres and index -1 when there is none. Batches: q0[..., A] with uniforms[..., K, 6] give arrays with the same lead.
+    clearance(q0, obstacle_c) is KinematicEnvironment.clearance's expression, for K centres per pose."""
+    u = np.asarray(uniforms, float)
+    u = u.reshape((-1, 6)) if u.ndim < 2 else u
+    if u.shape[-1] != 6 or u.shape[-2] > SCENE_TRIES:
+        raise ValueError(f"choose_scene: uniforms are [K, 6] with at most {SCENE_TRIES} candidates")
+    q0 = np.asarray(q0, float)
+    targets = twin.target_centre + (2.0 * u[..., :3] - 1.0) * twin.target_range
+    obstacles = twin.obstacle_centre + (2.0 * u[..., 3:] - 1.0) * twin.obstacle_range
+    m, orad = twin.scene_margin, twin.obstacle_radius
+    ee = twin.end_effector(q0)[..., None, :]
+    clear = np.min([np.sqrt(segment_point_distance2(a[..., None, :], b[..., None, :], obstacles)) - r
+                    for a, b, r in twin.world_segments(q0)], axis=0)
+    margins = np.stack([np.linalg.norm(ee - targets, axis=-1) - (TARGET_THRESHOLD + m), clear - orad - m,
+                        np.linalg.norm(targets - obstacles, axis=-1) - (orad + TARGET_THRESHOLD + m)], axis=-1)
+    ok = np.all(margins >= 0.0, axis=-1)
+    index = np.where(np.any(ok, axis=-1), np.argmax(ok, axis=-1), -1)
+    pick = np.maximum(index, 0)[..., None, None]
+    target = np.where((index < 0)[..., None], twin.target_centre, np.take_along_axis(targets, pick, axis=-2)[..., 0, :])
+    obstacle = np.where((index < 0)[..., None], twin.obstacle_centre, np.take_along_axis(obstacles, pick, axis=-2)[..., 0, :])
+    return target, obstacle, (int(index) if index.ndim == 0 else index), margins
+
+
+def _half_widths(v) -> np.ndarray:
+    out = np.zeros(3) if v is None else np.array(v, float).reshape(3)
+    if not np.all(np.isfinite(out)) or np.any(out < 0.0):
+        raise ValueError(f"a scene range is three non-negative half-widths, got {v!r}")
+    return out
+
+
 class KinematicEnvironment:
 
     def __init__(self, model: ChainModel, target_position: Sequence[float], obstacle_position: Sequence[float],
-                 obstacle_radius: float = OBSTACLE_RADIUS):
+                 obstacle_radius: float = OBSTACLE_RADIUS, target_range: Optional[Sequence[float]] = None,
+                 obstacle_range: Optional[Sequence[float]] = None, scene_margin: float = 0.02):
+        """target_range / obstacle_range: half-widths xyz of the boxes around target_position / obstacle_position from which
+        reset() draws every episode's scene (choose_scene); None or zeros: the scene is fixed."""
         self.model = model
         self.n = model.A
         self.involved_joints = [j.index for j in model.joints]
-        self.target_pos = np.array(target_position, float)
-        self.obstacle_pos = np.array(obstacle_position, float)
+        self.target_centre = np.array(target_position, float)
+        self.obstacle_centre = np.array(obstacle_position, float)
+        self.target_range, self.obstacle_range = _half_widths(target_range), _half_widths(obstacle_range)
+        self.scene_margin = float(scene_margin)
+        if not np.isfinite(self.scene_margin) or self.scene_margin < 0.0:
+            raise ValueError(f"scene_margin is a non-negative length, got {scene_margin!r}")
+        self.scene_index = -1                                 # the candidate the last reset() took, -1: the centres
+        self.target_pos = self.target_centre.copy()           # the episode's scene
+        self.obstacle_pos = self.obstacle_centre.copy()
         self.obstacle_radius = float(obstacle_radius)
         self.initial_joint_positions = np.array([j.init for j in model.joints])
         self.initial_positions_variation_range = model.initial_positions_variation_range
@@ -146,11 +201,26 @@ class KinematicEnvironment:
     # ---- protocol ---------------------------------------------------------------------------------------------------------
     def reset(self, verbose: bool = True) -> np.ndarray:
         """Joint index k starts at initial_joint_positions[k] + U(-variation[k], +variation[k]) from Python's global RNG
-        (environment.py:284-293); only driven joints vary."""
+        (environment.py:284-293); only driven joints vary. With scene ranges the episode's target and obstacle follow from the
+        same RNG: candidates are drawn one at a time (components of half-width 0 are not drawn) until choose_scene admits one, at
+        most SCENE_TRIES."""
         self.q = np.array([random.uniform(j.init - j.variation, j.init + j.variation) if j.variation > 0.0 else j.init
                            for j in self.model.joints])
         self.qd = np.zeros(self.n)
+        if self.scene_ranges_on:
+            half = np.concatenate([self.target_range, self.obstacle_range])
+            self.target_pos, self.obstacle_pos, self.scene_index = self.target_centre.copy(), self.obstacle_centre.copy(), -1
+            for c in range(SCENE_TRIES):
+                u = [random.random() if h > 0.0 else 0.5 for h in half]
+                target, obstacle, index, _ = choose_scene(self, self.q, [u])
+                if index == 0:
+                    self.target_pos, self.obstacle_pos, self.scene_index = target, obstacle, c
+                    break
         return self.get_state()
+
+    @property
+    def scene_ranges_on(self) -> bool:
+        return bool(np.any(self.target_range > 0.0) or np.any(self.obstacle_range > 0.0))
 
     def step(self, action) -> Tuple[np.ndarray, float, int]:
         a = np.asarray(action, float).reshape(self.n)
@@ -175,9 +245,11 @@ class KinematicEnvironment:
 
 def build_kinematic(manipulator_file, endeffector_index, fixed_joints, involved_joints, target_position, obstacle_position,
                     initial_joint_positions=None, initial_positions_variation_range=None, link_radius=0.0,
-                    obstacle_radius=OBSTACLE_RADIUS, consider_autocollision=False, autocollision_ignore=None) -> KinematicEnvironment:
+                    obstacle_radius=OBSTACLE_RADIUS, consider_autocollision=False, autocollision_ignore=None, *, target_range=None,
+                    obstacle_range=None, scene_margin=0.02) -> KinematicEnvironment:
     """Picklable factory (HostVectorEnv's worker processes call it through functools.partial)."""
     model = compile_chain(load_urdf(manipulator_file), endeffector_index, involved_joints, fixed_joints,
                           initial_joint_positions, initial_positions_variation_range, link_radius, consider_autocollision,
                           autocollision_ignore or ())
-    return KinematicEnvironment(model, target_position, obstacle_position, obstacle_radius)
+    return KinematicEnvironment(model, target_position, obstacle_position, obstacle_radius, target_range, obstacle_range,
+                                scene_margin)

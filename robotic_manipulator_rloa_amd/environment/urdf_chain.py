@@ -42,6 +42,8 @@ MAX_JOINTS = 64
 DT = 1.0 / 240.0                 # environment.py:481: one stepSimulation tick
 TARGET_THRESHOLD = 0.05          # environment.py:345-371
 OBSTACLE_RADIUS = 0.06           # the stand-in's (csrc/synth_env.hip)
+SCENE_TRIES = 8                  # include/naf_hip.h NAF_CHAIN_SCENE_TRIES: candidate scenes per episode start
+RANGE_FLOATS = 7                 # NAF_CHAIN_RANGE_FLOATS: target half-widths xyz | obstacle half-widths xyz | margin
 # Capsules are fatter than meshes: a pair that is in contact at EVERY pose of this fixed sample (uniform inside the limits,
 # +-pi where there are none) can never be out of contact and is dropped at compile time. Constants, so that one URDF always
 # compiles to one model.

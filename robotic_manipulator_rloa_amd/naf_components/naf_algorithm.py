@@ -498,7 +498,8 @@ class NAFAgent:
         robot, drain_every (and noise / preset / variation); `episodes` may exceed the saved budget, `vector_steps` counts from
         the saved run's start. Checkpoints booked by the final drain behind the loop get none (the loop has ended there).
 
-        chain (environment.urdf_chain.ChainModel) + scene (dict: target, obstacle, optionally obstacle_radius, obstacle_jitter):
+        chain (environment.urdf_chain.ChainModel) + scene (dict: target, obstacle, optionally obstacle_radius, obstacle_jitter,
+        target_range, obstacle_range, scene_margin — a new target / obstacle every episode, see DeviceEnvLoop):
         the E envs are copies of that arm, stepped by csrc/chain_env.hip, instead of the stand-in's (robot / preset / variation /
         obstacle_jitter are then unused). The saved loop position then carries the model's digest and the scene, and a resume
         with another model is refused."""
@@ -580,13 +581,16 @@ class NAFAgent:
                 raise ValueError("scene describes the surroundings of a chain model: give chain too")
             return {}
         if not scene or "target" not in scene or "obstacle" not in scene:
-            raise ValueError("chain needs scene = {'target': xyz, 'obstacle': xyz[, 'obstacle_radius': r, 'obstacle_jitter': j]}")
-        unknown = set(scene) - {"target", "obstacle", "obstacle_radius", "obstacle_jitter"}
+            raise ValueError("chain needs scene = {'target': xyz, 'obstacle': xyz[, 'obstacle_radius': r, 'obstacle_jitter': j, "
+                             "'target_range': xyz, 'obstacle_range': xyz, 'scene_margin': m]}")
+        unknown = set(scene) - {"target", "obstacle", "obstacle_radius", "obstacle_jitter", "target_range", "obstacle_range",
+                                "scene_margin"}
         if unknown:
             raise ValueError(f"scene: unknown keys {sorted(unknown)}")
         return dict(chain=chain, target=scene["target"], obstacle=scene["obstacle"],
                     obstacle_radius=float(scene.get("obstacle_radius", 0.06)),
-                    obstacle_jitter=float(scene.get("obstacle_jitter", 0.0)))
+                    obstacle_jitter=float(scene.get("obstacle_jitter", 0.0)), target_range=scene.get("target_range"),
+                    obstacle_range=scene.get("obstacle_range"), scene_margin=float(scene.get("scene_margin", 0.02)))
 
     def _save_at_drain(self, loop, ledger, dropped, steps, updates, position, new_checkpoints) -> None:
         """training_state.pt of the checkpoints this drain wrote: one file, copied to the others"""

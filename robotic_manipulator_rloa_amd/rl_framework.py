@@ -30,11 +30,12 @@ from typing import List, Optional, Union
 import numpy as np
 import torch
 
-from .environment.kinematic import KinematicEnvironment, build_kinematic
+from .environment.kinematic import SCENE_CONDITIONS, KinematicEnvironment, build_kinematic, choose_scene
 from .environment.synthetic import SyntheticEnvironment
+from .environment.urdf_chain import SCENE_TRIES
 from .naf_components.naf_algorithm import NAFAgent
 from .presets import ROBOT_PRESETS, pybullet_arguments, synthetic_initial_joints
-from .utils.exceptions import (ConfigurationIncomplete, EnvironmentNotInitialized, InvalidHyperParameter,
+from .utils.exceptions import (ConfigurationIncomplete, EnvironmentNotInitialized, InvalidEnvironmentParameter, InvalidHyperParameter,
                                InvalidManipulatorFile, InvalidNAFAgentParameter, MissingWeightsFile, NAFAgentNotInitialized)
 from .utils.logger import Logger, get_global_logger
 
@@ -93,6 +94,10 @@ def _build_environment(manipulator_file: str, config_kwargs: dict):
 def _build_synthetic(n_joints, target, obstacle, init, variation):
     return SyntheticEnvironment(n_joints, target, obstacle, init, variation)
 
+
+# initialize_kinematic_environment's check of the scene ranges: (start pose, scene) draws of the twin, from a fixed seed
+SCENE_CHECK_CASES = 1024
+SCENE_CHECK_SEED = 20241017
 
 # environments whose E copies are stepped on the device (everything else: E worker processes)
 _DEVICE_ENVS = (SyntheticEnvironment, KinematicEnvironment)
@@ -190,6 +195,11 @@ class ManipulatorFramework:
                             ('Initial variation range of joints', 'initial_positions_variation_range'),
                             ('Max Force to be applied on joints', 'max_force'), ('Visualize mode', 'visualize')):
             logger.info('* {:<38} {}'.format(label + ':', getattr(self.env, attr, 'n/a')))
+        if isinstance(self.env, KinematicEnvironment) and self.env.scene_ranges_on:
+            for label, attr in (('Centre of the Target box', 'target_centre'), ('Half-widths of the Target box', 'target_range'),
+                                ('Centre of the Obstacle box', 'obstacle_centre'),
+                                ('Half-widths of the Obstacle box', 'obstacle_range'), ('Scene margin', 'scene_margin')):
+                logger.info('* {:<38} {}'.format(label + ':', getattr(self.env, attr)))
         logger.info(f'* Instance of the Environment:         {self.env}')
 
     def get_nafagent_configuration(self) -> None:
@@ -291,7 +301,8 @@ class ManipulatorFramework:
                                          initial_positions_variation_range: List[float] = None, link_radius: float = 0.0,
                                          obstacle_radius: float = 0.06, obstacle_jitter: float = 0.0, max_force: float = 200.,
                                          visualize: bool = False, consider_autocollision: bool = False,
-                                         autocollision_ignore: Optional[list] = None) -> None:
+                                         autocollision_ignore: Optional[list] = None, target_range: Optional[List[float]] = None,
+                                         obstacle_range: Optional[List[float]] = None, scene_margin: float = 0.02) -> None:
         """initialize_environment()'s arguments (rl_framework.py:369-417) for the built-in kinematic environment: the arm of
         `manipulator_file` (a URDF) as a serial chain under the reference's environment rule, velocity control applied exactly.
         Not a Bullet port — no dynamics (max_force is accepted and ignored), no mesh collision (links are capsules of their
@@ -300,16 +311,40 @@ class ManipulatorFramework:
         consider_autocollision: initialize_environment()'s switch — contact between the capsules of two links that are not
         neighbours ends the episode with -1000 (environment.py:311-371, :394-412); pairs that the capsules keep in contact at
         every pose are dropped when the model is compiled (env.model.self_pairs_dropped), autocollision_ignore (pairs of link
-        names or link indices) drops more. A start pose in self-contact is refused here."""
+        names or link indices) drops more. A start pose in self-contact is refused here.
+        target_range / obstacle_range: half-widths [x, y, z] of the boxes around target_position / obstacle_position. Every
+        episode, of the host env and of each device env, then gets a target and an obstacle of its own from them: up to 8
+        candidates are drawn and the first one is taken whose target is farther than 0.05 + scene_margin from the start pose's
+        end effector, whose obstacle is scene_margin clear of the arm at the start pose and whose target is not inside the
+        obstacle; if none is, the episode runs in the nominal scene. Ranges that put the scene on the arm — more than half of
+        1024 sampled episode starts falling back — are refused here. Not together with obstacle_jitter."""
         if visualize:
             raise InvalidManipulatorFile('the kinematic environment has no visualisation: pass visualize=False '
                                          '(initialize_environment() opens the PyBullet GUI)')
+        for label, r in (('Target range', target_range), ('Obstacle range', obstacle_range)):
+            if r is None:
+                continue
+            if not isinstance(r, list) or len(r) != 3:
+                raise InvalidEnvironmentParameter(f'{label} received is not a list of three half-widths')
+            if not all(isinstance(v, (int, float)) and not isinstance(v, bool) and np.isfinite(v) and v >= 0 for v in r):
+                raise InvalidEnvironmentParameter(f'An item inside the {label} list is not a non-negative number')
+        if isinstance(scene_margin, bool) or not isinstance(scene_margin, (int, float)) or not scene_margin >= 0:
+            raise InvalidEnvironmentParameter('Scene margin received is not a non-negative number')
+        ranged = any(v > 0 for r in (target_range, obstacle_range) if r is not None for v in r)
+        if ranged and obstacle_jitter > 0:
+            raise ValueError('obstacle_jitter moves each env\'s obstacle once, target_range / obstacle_range draw a scene every '
+                             'episode: give one or the other')
         args = (manipulator_file, endeffector_index, list(fixed_joints), list(involved_joints), list(target_position),
                 list(obstacle_position), None if initial_joint_positions is None else list(initial_joint_positions),
                 None if initial_positions_variation_range is None else list(initial_positions_variation_range),
                 float(link_radius), float(obstacle_radius), bool(consider_autocollision),
                 None if autocollision_ignore is None else [tuple(p) for p in autocollision_ignore])
-        env = build_kinematic(*args)
+        scene_kw = dict(target_range=None if target_range is None else [float(v) for v in target_range],
+                        obstacle_range=None if obstacle_range is None else [float(v) for v in obstacle_range],
+                        scene_margin=float(scene_margin))
+        env = build_kinematic(*args, **scene_kw)
+        if ranged:
+            self._check_scene_ranges(env, manipulator_file)
         if env.model.self_pairs:
             clear = env.pair_clearances(env.initial_joint_positions)
             worst = int(np.argmin(clear))
@@ -321,9 +356,32 @@ class ManipulatorFramework:
                                  f'autocollision_ignore=[({a!r}, {b!r})]')
         self.env = env
         self._obstacle_jitter = float(obstacle_jitter)
-        self._env_factory = functools.partial(build_kinematic, *args)
+        self._env_factory = functools.partial(build_kinematic, *args, **scene_kw)
         logger.info(f'Kinematic Environment successfully initialized from {manipulator_file} '
                     f'({self.env.model.A} driven joints, {len(self.env.model.segments)} collision capsules)')
+
+    @staticmethod
+    def _check_scene_ranges(env: KinematicEnvironment, manipulator_file: str) -> None:
+        """SCENE_CHECK_CASES (start pose, scene) draws of the twin from a fixed seed: logs how many take a candidate, and refuses
+        ranges under which more than half fall back to the nominal scene."""
+        rng = np.random.default_rng(SCENE_CHECK_SEED)
+        joints = env.model.joints
+        init, var = np.array([j.init for j in joints]), np.array([j.variation for j in joints])
+        q0 = init + rng.uniform(-1.0, 1.0, (SCENE_CHECK_CASES, len(joints))) * var
+        _, _, index, margins = choose_scene(env, q0, rng.random((SCENE_CHECK_CASES, SCENE_TRIES, 6)))
+        fallback, first = int(np.sum(index < 0)), int(np.sum(index == 0))
+        tried = np.arange(SCENE_TRIES) < np.where(index < 0, SCENE_TRIES, index)[:, None]      # the candidates before the choice
+        rejects = np.sum((margins < 0.0) & tried[..., None], axis=(0, 1))
+        rate = 1.0 - fallback / SCENE_CHECK_CASES
+        logger.info(f'Scene ranges: {100.0 * rate:.1f}% of {SCENE_CHECK_CASES} sampled episode starts take a drawn scene '
+                    f'({100.0 * first / SCENE_CHECK_CASES:.1f}% the first candidate), {100.0 * (1.0 - rate):.1f}% fall back to the '
+                    f'nominal scene')
+        if fallback > SCENE_CHECK_CASES // 2:
+            raise ValueError(f'{manipulator_file}: with these target_range / obstacle_range {fallback} of {SCENE_CHECK_CASES} sampled '
+                             f'episode starts find no admissible scene among {SCENE_TRIES} candidates and fall back to the nominal '
+                             f'one; most rejections: {SCENE_CONDITIONS[int(np.argmax(rejects))]} (condition '
+                             f'{int(np.argmax(rejects)) + 1}, {int(rejects.max())} candidates). The ranges put the scene on the arm: '
+                             f'move the boxes away from it or make them larger')
 
     def delete_environment(self) -> None:
         if not self.env:
@@ -425,9 +483,13 @@ class ManipulatorFramework:
         and scene (csrc/chain_env.hip)."""
         env = self.env
         if isinstance(env, KinematicEnvironment):
-            return {'chain': env.model, 'scene': {
-                'target': [float(x) for x in env.target_pos], 'obstacle': [float(x) for x in env.obstacle_pos],
-                'obstacle_radius': env.obstacle_radius, 'obstacle_jitter': getattr(self, '_obstacle_jitter', 0.0)}}
+            scene = {'target': [float(x) for x in env.target_pos], 'obstacle': [float(x) for x in env.obstacle_pos],
+                     'obstacle_radius': env.obstacle_radius, 'obstacle_jitter': getattr(self, '_obstacle_jitter', 0.0)}
+            if env.scene_ranges_on:      # target_pos / obstacle_pos are then some episode's scene: the device draws around the centres
+                scene.update(target=[float(x) for x in env.target_centre], obstacle=[float(x) for x in env.obstacle_centre],
+                             target_range=[float(x) for x in env.target_range],
+                             obstacle_range=[float(x) for x in env.obstacle_range], scene_margin=env.scene_margin)
+            return {'chain': env.model, 'scene': scene}
         pad8 = lambda v: ([float(x) for x in v] + [0.0] * 8)[:8]          # noqa: E731
         var = env.initial_positions_variation_range
         return {'preset': pad8(env.initial_joint_positions) + [float(x) for x in env.target_pos] +
