@@ -1,5 +1,5 @@
 """Vectorized training rate of the kinematic chain environment (csrc/chain_env.hip) beside the stand-in's at the same joint
-count, and a launch loop of the two step kernels for `rocprofv3 --kernel-trace --stats`.
+count, a launch loop of the two step kernels for `rocprofv3 --kernel-trace --stats`, and the step and rollout-step launches timed.
 
   python benchmarks/chain_env_bench.py rate --urdf tests/golden/urdf/iiwa_like7.urdf --steps 4000 --warmup 100
       env-steps/s of NAFAgent.run_vectorized, E = 64, B = 256: the chain environment, then the stand-in at the same A
@@ -14,6 +14,12 @@ count, and a launch loop of the two step kernels for `rocprofv3 --kernel-trace -
       enqueued by the host, so at small E the figure is bounded below by launch submission: the kernel's own time comes from
       `rocprofv3 --kernel-trace --stats -d OUT -- python benchmarks/chain_env_bench.py step ...`, a run of its own, whose
       maximum per kernel is the launch in which the envs reset (every 400th).
+
+  python benchmarks/chain_env_bench.py rollout --envs 4096 --launches 4000 [--autocollision]
+      microseconds per naf_chain_env_rollout_step launch of --urdf, measured as `step` measures (the same arm, start pose and seeded
+      N(0, 1) actions; ONE launch per step: there is no counter), after naf_chain_env_reset_given at the start pose with target and
+      obstacle 3 m away and a frame budget beyond the run, so that every env stays live: a held lane returns at once and would
+      flatter the figure. `--trajectory`: the joint values of a window of frames are recorded too (the budget is then the window).
 
 `--target-range X Y Z` / `--obstacle-range X Y Z` (rate, step): half-widths of the boxes every episode draws its target / obstacle
 from (include/naf_hip.h, "Scene ranges"); step then also prints how the episode starts of the run chose their scenes.
@@ -123,6 +129,52 @@ def step(a):
     print(json.dumps(out))
 
 
+def rollout(a):
+    import numpy as np
+    import torch
+    from robotic_manipulator_rloa_amd import _lib
+    from robotic_manipulator_rloa_amd.environment.urdf_chain import compile_chain, load_urdf
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    E, n, stream = a.envs, a.joints, torch.cuda.current_stream().cuda_stream
+    urdf = os.path.abspath(a.urdf) if os.path.isabs(a.urdf) else os.path.join(ROOT, a.urdf)
+    init = ([0.0, 0.6, 0.0, -1.2, 0.0, 0.8, 0.0] + [0.0] * n)[:n]             # step's arm and start pose
+    var = ([0.1, 0.1, 0.1, 0.1, 0.2, 0.2, 0.2] + [0.1] * n)[:n]
+    model = compile_chain(load_urdf(urdf), n - 1, list(range(n)), [n], init, var, 0.03, consider_autocollision=a.autocollision)
+    blob = np.ascontiguousarray(model.pack())
+    h = ctypes.c_void_p()
+    _lib.check(lib.naf_chain_env_create(blob.ctypes.data, int(blob.size), ctypes.byref(h)), "create")
+    S = 2 * n + 9
+    st = torch.zeros(E, lib.naf_chain_env_state_floats(h), device=dev)
+    torch.manual_seed(5)
+    obs, act = torch.zeros(E, S, device=dev), torch.randn(E, n, device=dev)
+    outcome = torch.zeros(E, 8, device=dev)
+    q0 = torch.tensor(init, device=dev).repeat(E, 1).contiguous()
+    scene = torch.tensor([0.0, 0.0, 3.0, 0.0, 0.0, -3.0], device=dev).repeat(E, 1).contiguous()
+    budget = a.launches if a.trajectory else a.launches * (a.repeats + 1) + 1
+    traj = torch.zeros(budget + 1, E, n, device=dev) if a.trajectory else None
+    times, held = [], []
+    for w in range(a.repeats + 1):                        # window 0 warms up
+        if w == 0 or a.trajectory:
+            _lib.check(lib.naf_chain_env_reset_given(h, st.data_ptr(), obs.data_ptr(), E, q0.data_ptr(), scene.data_ptr(), 0.06,
+                                                     stream), "reset_given")
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(a.launches):
+            _lib.check(lib.naf_chain_env_rollout_step(h, st.data_ptr(), act.data_ptr(), obs.data_ptr(), outcome.data_ptr(),
+                                                      traj.data_ptr() if traj is not None else None, E, budget, stream), "rollout_step")
+        t1.record()
+        torch.cuda.synchronize()
+        if w:
+            times.append(round(1e3 * t0.elapsed_time(t1) / a.launches, 3))
+            # envs that ended before the window's last launch idled in it
+            held.append(int(((outcome[:, 0] != 0) | (outcome[:, 1] < (a.launches if a.trajectory else a.launches * (w + 1)))).sum().item()))
+    lib.naf_chain_env_destroy(h)
+    print(json.dumps({"arm": os.path.basename(urdf), "envs": E, "autocollision": a.autocollision, "self_pairs": len(model.self_pairs),
+                      "launches": a.launches, "trajectory": bool(a.trajectory), "us_per_rollout_step_launch": times,
+                      "envs_held_before_the_window_ended": held}))
+
+
 def kernels(a):
     import numpy as np
     import torch
@@ -161,7 +213,7 @@ def kernels(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["rate", "kernels", "step"])
+    ap.add_argument("what", choices=["rate", "kernels", "step", "rollout"])
     ap.add_argument("--urdf", default=os.path.join("tests", "golden", "urdf", "iiwa_like7.urdf"))
     ap.add_argument("--joints", type=int, default=7)
     ap.add_argument("--envs", type=int, default=64)
@@ -172,11 +224,12 @@ def main():
     ap.add_argument("--launches", type=int, default=1000)
     ap.add_argument("--standin-only", action="store_true")
     ap.add_argument("--autocollision", action="store_true")
+    ap.add_argument("--trajectory", action="store_true", help="rollout: record the joint values of every frame")
     ap.add_argument("--arm", default="", help="rate: a fixture arm of tests/golden/urdf by name, --joints its joint count")
     ap.add_argument("--target-range", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))
     ap.add_argument("--obstacle-range", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))
     a = ap.parse_args()
-    {"rate": rate, "kernels": kernels, "step": step}[a.what](a)
+    {"rate": rate, "kernels": kernels, "step": step, "rollout": rollout}[a.what](a)
 
 
 if __name__ == "__main__":

@@ -67,7 +67,7 @@ typedef struct {
 /* ---- library ------------------------------------------------------------------------------ */
 /* Bumped whenever a signature or a struct in this header changes; the ctypes host compares the library's answer with
  * the value in this header and refuses a mismatch (a stale .so would otherwise be called with wrong argument lists). */
-#define NAF_HIP_ABI_VERSION 38
+#define NAF_HIP_ABI_VERSION 39
 int naf_hip_abi_version(void);
 /* "gfx950" — the only architecture this library carries code objects for */
 const char* naf_hip_arch(void);
@@ -666,7 +666,7 @@ int naf_synth_env_reset(float* env_state, float* obs, int E, int A, uint64_t see
                         const float* preset_host, int preset_floats, void* stream);
 int naf_synth_env_state_floats(int A);
 
-/* ---- kinematic environment of a URDF manipulator (ABI 36; self-collision and probe: ABI 37; scene ranges: ABI 38) ----------------------------------------------------------------
+/* ---- kinematic environment of a URDF manipulator (ABI 36; self-collision and probe: ABI 37; scene ranges: ABI 38; rollout: ABI 39) ----------------------------------------------------------------
  * E copies of the serial chain environment/urdf_chain.py compiles from the user's URDF, stepped on the device under the
  * reference's environment rule (environment/environment.py:431-485: state layout, reward, terminal rule, velocity control
  * of the involved joints, held joints). Kinematic — the commanded velocity is applied exactly for one 1/240 s tick, then the
@@ -733,7 +733,24 @@ int naf_synth_env_state_floats(int A);
  *                 The first admissible candidate is the episode's scene; if none is, the scene is scene_host's target / obstacle.
  *                 Always NAF_CHAIN_SCENE_TRIES tries, all tested during the ONE walk of the reset pose. The row that ends an
  *                 episode carries the old scene in next_state; obs_next and env_state [A .. A+6) carry the new one; envs whose
- *                 episode goes on keep theirs. The env_state record does not change. */
+ *                 episode goes on keep theirs. The env_state record does not change.
+ *
+ * Rollout to given targets (ABI 39): the policy run as a query — from these poses, in these scenes — instead of a training stream.
+ *   reset_given : env e starts at q0_dev[e] (DEVICE, [E][A], action order; a limited joint is clamped into its limits exactly as a
+ *                 step clamps it) in the scene scene_dev[e] (DEVICE, [E][6] target | obstacle centre), obstacle_radius for all.
+ *                 Frame, episodes finished and score are 0; one walk writes the first observation (velocities 0). Nothing is
+ *                 drawn: no seed. Scene ranges set on the handle are ignored.
+ *   rollout_step: one tick under step's rule — the same velocity control, limits and walk, the pair phase when the blob has pairs,
+ *                 the same reached / contact / reward expressions — with three differences. (1) HOLD instead of auto-reset: an
+ *                 env whose episode is over has env_state[A+8] >= 1; its lane walks nothing and writes nothing, so pose,
+ *                 observation and outcome stay as they were. An episode is over by reaching the target, by obstacle contact, by
+ *                 self-contact, or at frame == max_frames (>= 1). (2) outcome [E][NAF_CHAIN_OUTCOME_FLOATS], updated by the env's
+ *                 own lane every live step: [0] code, 0 = running or frame budget used up, 1 = reached, 2 = obstacle contact,
+ *                 3 = self-contact (precedence 1 > 2 > 3)  [1] frames stepped  [2] |ee - target| after the last step  [3] min over
+ *                 the steps so far of probe's [3]  [4] min over the steps so far of probe's [4], +inf when P = 0  [5] score as
+ *                 float  [6..7] 0. (3) traj (NULL, or DEVICE [max_frames + 1][E][A]): a live env writes its post-step joint values
+ *                 to traj[frame][e]; frame 0 is the caller's (q0), as are a held env's later frames.
+ *                 No transition rows, no episode records, no counter. The record and every prototype above are unchanged. */
 #define NAF_CHAIN_BLOB_VERSION 1
 #define NAF_CHAIN_HEADER_FLOATS 16
 #define NAF_CHAIN_JOINT_FLOATS 24
@@ -764,6 +781,11 @@ int naf_chain_env_step(naf_chain_env_t* h, float* env_state, const float* action
                        int record_slots, void* stream);
 int naf_chain_env_probe(naf_chain_env_t* h, const float* env_state, float* out, int E, void* stream);
 int naf_chain_env_set_scene_ranges(naf_chain_env_t* h, const float* ranges_host);
+#define NAF_CHAIN_OUTCOME_FLOATS 8
+int naf_chain_env_reset_given(naf_chain_env_t* h, float* env_state, float* obs, int E, const float* q0_dev, const float* scene_dev,
+                              float obstacle_radius, void* stream);
+int naf_chain_env_rollout_step(naf_chain_env_t* h, float* env_state, const float* actions, float* obs_next, float* outcome,
+                               float* traj, int E, int max_frames, void* stream);
 
 /* ---- one-shot gradient all-reduce over peer-mapped memory (no reference counterpart) ----------
  * The data-parallel exchange that follows loss.backward() (naf_algorithm.py:207-210 on every rank): sum of the flat

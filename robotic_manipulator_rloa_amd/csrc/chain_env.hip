@@ -136,7 +136,7 @@ __device__ static inline float seg_seg_dist2(float ax, float ay, float az, float
 }
 
 // Where the SC instantiations keep the capsules' world end points: `ends` is the LDS array already offset by the lane, `lanes`
-// its innermost extent. PROBE: `clear` collects min over the capsules of (distance to the obstacle centre - capsule radius).
+// its innermost extent. CLEAR: `clear` collects min over the capsules of (distance to the obstacle centre - capsule radius).
 struct WalkAux {
     float* ends;
     int lanes;
@@ -144,7 +144,7 @@ struct WalkAux {
 };
 
 // contact of the capsules of frame f with the obstacle sphere, and the end-effector point when it lives in f
-template <bool SC, bool PROBE, bool SCENE = false>
+template <bool SC, bool PROBE, bool SCENE = false, bool CLEAR = PROBE>
 __device__ static inline bool frame_geometry(const float* __restrict__ model, int A, int f, const Frame& F, float ox, float oy,
                                              float oz, float orad, int ee_frame, float* ee, WalkAux& aux, SceneCand* cand = nullptr) {
     const float* begin = model + ch_off_begin(A);
@@ -167,7 +167,7 @@ __device__ static inline bool frame_geometry(const float* __restrict__ model, in
             w[0] = ax; w[aux.lanes] = ay; w[2 * aux.lanes] = az;
             w[3 * aux.lanes] = bx; w[4 * aux.lanes] = by; w[5 * aux.lanes] = bz;
         }
-        if constexpr (PROBE) aux.clear = fminf(aux.clear, sqrtf(d2) - g[7]);
+        if constexpr (CLEAR) aux.clear = fminf(aux.clear, sqrtf(d2) - g[7]);
         if constexpr (SCENE) {
             // seg_point_dist2 for CH_TRIES centres against ONE segment: its direction and 1 / |u|^2 are computed once, and the
             // root is the hardware's (1 ulp): both far inside the band in which the choice is compared with the twin's
@@ -193,15 +193,16 @@ __device__ static inline bool frame_geometry(const float* __restrict__ model, in
 
 // Walks the chain at the joint values in st[0 .. A): writes the position slots, the constants' slots (velocity 0), the end
 // effector, target and obstacle into the observation `o` (not with PROBE: o is unused); the DRIVEN joints' velocity slots are the
-// caller's. Returns contact with the obstacle.
-template <bool SC, bool PROBE, bool SCENE = false>
+// caller's. Returns contact with the obstacle. CLEAR (the probe's walk, and the rollout step's beside its observation) also collects
+// the obstacle clearance in aux.clear.
+template <bool SC, bool PROBE, bool SCENE = false, bool CLEAR = PROBE>
 __device__ static inline bool chain_walk(const float* __restrict__ model, int A, int n_seg, const float* st, float* o, float* ee,
                                          WalkAux& aux, SceneCand* cand = nullptr) {
     const int ee_frame = (int)model[4];
     const float ox = st[A + 3], oy = st[A + 4], oz = st[A + 5], orad = st[A + 6];
     Frame F = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
     ee[0] = ee[1] = ee[2] = 0.f;
-    bool hit = frame_geometry<SC, PROBE, SCENE>(model, A, 0, F, ox, oy, oz, orad, ee_frame, ee, aux, cand);
+    bool hit = frame_geometry<SC, PROBE, SCENE, CLEAR>(model, A, 0, F, ox, oy, oz, orad, ee_frame, ee, aux, cand);
     for (int m = 0; m < A; ++m) {
         const float* j = model + CH_HDR + m * CH_JNT;
         const float q = st[m];
@@ -248,7 +249,7 @@ __device__ static inline bool chain_walk(const float* __restrict__ model, int A,
             F.r21 = G.r20 * m01 + G.r21 * m11 + G.r22 * m21;
             F.r22 = G.r20 * m02 + G.r21 * m12 + G.r22 * m22;
         }
-        hit |= frame_geometry<SC, PROBE, SCENE>(model, A, m + 1, F, ox, oy, oz, orad, ee_frame, ee, aux, cand);
+        hit |= frame_geometry<SC, PROBE, SCENE, CLEAR>(model, A, m + 1, F, ox, oy, oz, orad, ee_frame, ee, aux, cand);
     }
     if constexpr (!PROBE) {
         const float* slots = model + ch_off_slot(A, n_seg);
@@ -512,6 +513,115 @@ chain_env_probe_kernel(const float* __restrict__ model, const float* __restrict_
     o[4] = self_clear;
 }
 
+// naf_chain_env_reset_given: env e starts at q0[e] (clamped into the limits as a step clamps) in the scene scene[e]; nothing is drawn
+__global__ void __launch_bounds__(64)
+chain_env_reset_given_kernel(const float* __restrict__ model, float* env_state, float* obs, int E, int A, int n_seg,
+                             const float* __restrict__ q0, const float* __restrict__ scene, float orad) {
+    int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    const int nst = ch_state_floats(A);
+    float* st = env_state + (int64_t)e * nst;
+    float* o = obs + (int64_t)e * (2 * A + 9);
+    for (int k = A; k < nst; ++k) st[k] = 0.f;
+    for (int k = 0; k < 6; ++k) st[A + k] = scene[(int64_t)e * 6 + k];
+    st[A + 6] = orad;
+    for (int m = 0; m < A; ++m) {
+        const float* j = model + CH_HDR + m * CH_JNT;
+        float q = q0[(int64_t)e * A + m];
+        if (j[16] != 0.f) {
+            if (q > j[18]) q = j[18];
+            if (q < j[17]) q = j[17];
+        }
+        st[m] = q;
+        const int slot = (int)j[21];
+        if (slot >= 0) o[A + slot] = 0.f;
+    }
+    float ee[3];
+    WalkAux aux = {nullptr, 0, 0.f};
+    chain_walk<false, false>(model, A, n_seg, st, o, ee, aux);
+}
+
+// naf_chain_env_rollout_step: the step kernel's tick for a query instead of a training stream. An env whose episode is over
+// (env_state[A+8] >= 1) is HELD: its lane walks nothing and writes nothing, and in an SC workgroup only joins the barriers. A live
+// lane writes the observation straight into obs_next, keeps its outcome record and, with traj, its joint values of the frame.
+template <bool SC>
+__global__ void __launch_bounds__(SC ? 64 * CH_MAX_WAVES : 64)      // (without SC a workgroup is one wave)
+chain_env_rollout_kernel(const float* __restrict__ model, float* env_state, const float* __restrict__ actions,
+                         float* __restrict__ obs_next, float* __restrict__ outcome, float* __restrict__ traj, int E, int A, int n_seg,
+                         int max_frames, int n_pairs, int lanes) {
+    extern __shared__ __attribute__((aligned(16))) float ch_lds[];
+    int e, lane = 0;
+    bool active = true, walker = true;
+    if constexpr (SC) {
+        lane = threadIdx.x & 63;
+        e = blockIdx.x * lanes + lane;
+        active = lane < lanes && e < E;
+        walker = active && threadIdx.x < 64;
+        if (!active) e = 0;      // (addresses below stay inside the arrays; nothing is written through them)
+    } else {
+        e = blockIdx.x * blockDim.x + threadIdx.x;
+        if (e >= E) return;
+    }
+    const int S = 2 * A + 9;
+    float* st = env_state + (int64_t)e * ch_state_floats(A);
+    float* ob = obs_next + (int64_t)e * S;
+    // every wave of an SC workgroup reads the hold flag here, before the first barrier; the walker raises it behind the second
+    const bool live = active && st[A + 8] < 1.f;
+    walker = walker && live;
+    if constexpr (!SC)
+        if (!live) return;
+    float ee[3];
+    bool hit = false;
+    WalkAux aux = {SC ? ch_lds + lane : nullptr, lanes, INFINITY};
+    if (walker) {
+        for (int m = 0; m < A; ++m) {
+            const float* j = model + CH_HDR + m * CH_JNT;
+            const float a = actions[(int64_t)e * A + m];
+            float q = st[m] + CH_DT * a;      // the step kernel's rule: velocity control, then the position limits
+            float vel = a;
+            if (j[16] != 0.f) {
+                if (q > j[18]) { q = j[18]; vel = 0.f; }
+                if (q < j[17]) { q = j[17]; vel = 0.f; }
+            }
+            st[m] = q;
+            const int slot = (int)j[21];
+            if (slot >= 0) ob[A + slot] = vel;
+        }
+        hit = chain_walk<SC, false, false, true>(model, A, n_seg, st, ob, ee, aux);
+    }
+    float self_clear = INFINITY;
+    if constexpr (SC) {
+        self_clear = self_clearance_phase(model, A, n_seg, n_pairs, ch_lds, lanes, lane, live);
+        if (!walker) return;
+    }
+    const bool self_hit = self_clear < 0.f;
+    float dx = ee[0] - st[A], dy = ee[1] - st[A + 1], dz = ee[2] - st[A + 2];
+    float dist = sqrtf(dx * dx + dy * dy + dz * dz);
+    const bool reached = dist < 0.05f;
+    const float reward = reached ? 250.f : ((hit || self_hit) ? -1000.f : -(dist - 0.05f));
+    const bool done = reached || hit || self_hit;
+    const bool first = st[A + 7] == 0.f;
+    const float frame = st[A + 7] + 1.f;
+    st[A + 7] = frame;
+    double* score_p = (double*)(st + ch_off_score(A));
+    const double score = *score_p + (double)reward;
+    *score_p = score;
+    float* oc = outcome + (int64_t)e * NAF_CHAIN_OUTCOME_FLOATS;
+    oc[0] = reached ? 1.f : (hit ? 2.f : (self_hit ? 3.f : 0.f));
+    oc[1] = frame;
+    oc[2] = dist;
+    oc[3] = fminf(first ? INFINITY : oc[3], aux.clear - st[A + 6]);
+    oc[4] = fminf(first ? INFINITY : oc[4], self_clear);
+    oc[5] = (float)score;
+    oc[6] = 0.f;
+    oc[7] = 0.f;
+    if (traj && frame <= (float)max_frames) {      // (a record that did not come from reset_given cannot write past the buffer)
+        float* tr = traj + ((int64_t)frame * E + e) * A;
+        for (int m = 0; m < A; ++m) tr[m] = st[m];
+    }
+    if (done || frame >= (float)max_frames) st[A + 8] += 1.f;
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------------
 static inline bool ch_int(float v, int lo, int hi, int* out) {
     if (!std::isfinite(v) || v != std::floor(v) || v < (float)lo || v > (float)hi) return false;
@@ -583,8 +693,8 @@ static int ch_raise_lds_limit() {
     if (e != hipSuccess) return (int)e;
     if (dev < 0 || dev >= 64) return NAF_ERR_ARG;
     if (raised_dev[dev]) return NAF_OK;
-    const void* ks[3] = {(const void*)chain_env_step_kernel<true, false>, (const void*)chain_env_step_kernel<true, true, ChainRanges>,
-                         (const void*)chain_env_probe_kernel<true>};
+    const void* ks[4] = {(const void*)chain_env_step_kernel<true, false>, (const void*)chain_env_step_kernel<true, true, ChainRanges>,
+                         (const void*)chain_env_probe_kernel<true>, (const void*)chain_env_rollout_kernel<true>};
     for (const void* k : ks) {
         e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, CH_MAX_DYN_LDS);
         if (e != hipSuccess) return (int)e;
@@ -718,6 +828,29 @@ extern "C" int naf_chain_env_probe(naf_chain_env_t* h, const float* env_state, f
     else
         chain_env_probe_kernel<false><<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(h->model_dev, env_state, out, E, h->A, h->n_seg,
                                                                                      0, 64);
+    NAF_CHECK_LAUNCH();
+    return NAF_OK;
+}
+
+extern "C" int naf_chain_env_reset_given(naf_chain_env_t* h, float* env_state, float* obs, int E, const float* q0_dev,
+                                         const float* scene_dev, float obstacle_radius, void* stream) {
+    if (!h || !env_state || !obs || !q0_dev || !scene_dev || E <= 0 || !(obstacle_radius >= 0.f)) return NAF_ERR_ARG;
+    chain_env_reset_given_kernel<<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(h->model_dev, env_state, obs, E, h->A, h->n_seg, q0_dev,
+                                                                                scene_dev, obstacle_radius);
+    NAF_CHECK_LAUNCH();
+    return NAF_OK;
+}
+
+extern "C" int naf_chain_env_rollout_step(naf_chain_env_t* h, float* env_state, const float* actions, float* obs_next, float* outcome,
+                                          float* traj, int E, int max_frames, void* stream) {
+    if (!h || !env_state || !actions || !obs_next || !outcome || E <= 0 || max_frames < 1) return NAF_ERR_ARG;
+    if (h->n_pairs > 0)
+        chain_env_rollout_kernel<true><<<(E + h->lanes - 1) / h->lanes, 64 * h->waves, ch_lds_bytes(h->n_seg, h->lanes, h->waves),
+                                         (hipStream_t)stream>>>(h->model_dev, env_state, actions, obs_next, outcome, traj, E, h->A,
+                                                                h->n_seg, max_frames, h->n_pairs, h->lanes);
+    else
+        chain_env_rollout_kernel<false><<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(h->model_dev, env_state, actions, obs_next, outcome,
+                                                                                       traj, E, h->A, h->n_seg, max_frames, 0, 64);
     NAF_CHECK_LAUNCH();
     return NAF_OK;
 }

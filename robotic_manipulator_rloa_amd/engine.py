@@ -8,6 +8,8 @@
   DeviceEnvLoop  : E synthetic arms stepped on the device: act (eval-mode policy + noise) -> env step ->
                    append E transitions to the HBM ring, as ONE graph; followed by an UpdateChunk with
                    U = E * num_updates / update_freq so the reference's update-to-data ratio is kept.
+  DeviceRollout  : the policy run as a QUERY on a chain model: given start poses and scenes, act -> rollout step as ONE graph per
+                   frame, an env held at the end of its episode; outcome, clearances and joint paths come back (ReachResult).
 
 Graph capture goes through torch.cuda.CUDAGraph (= hipGraph on ROCm): the ctypes kernel launches use the
 stream torch reports as current, which inside the capture context is the capturing stream.
@@ -16,6 +18,7 @@ from __future__ import annotations
 
 import json
 import os
+from dataclasses import dataclass
 from typing import Callable, Dict, List, Optional, Tuple
 
 import numpy as np
@@ -991,3 +994,124 @@ class DeviceEnvLoop:
             self._parse_inflight()
         out, self._finished = self._finished, []
         return out
+
+
+OUTCOME_NAMES = np.array(["frames", "reached", "obstacle", "self"])      # by naf_chain_env_rollout_step's outcome code
+
+
+@dataclass
+class ReachResult:
+    """What N rollouts to given targets came to, arrays over the queries (ManipulatorFramework.reach_targets)."""
+    outcome: np.ndarray                        # [N] str: 'reached' | 'obstacle' | 'self' | 'frames' (the frame budget was used up)
+    frames: np.ndarray                         # [N] int64: steps taken
+    final_distance: np.ndarray                 # [N] float32: |end effector - target| after the last step
+    min_clearance: np.ndarray                  # [N] float32: least distance between arm and obstacle surface over the steps
+    min_self_clearance: np.ndarray             # [N] float32: least self-clearance over the steps, +inf without self-collision pairs
+    score: np.ndarray                          # [N] float32: sum of the rewards
+    joint_positions: Optional[np.ndarray]      # [N][frames + 1][A] float32, entry m = involved_joints[m]; None: not recorded
+    start_distance: np.ndarray                 # [N] float32: the same three measures at the start pose, before any step
+    start_clearance: np.ndarray
+    start_self_clearance: np.ndarray
+
+
+class DeviceRollout:
+    """E copies of a chain model (csrc/chain_env.hip) that run the learner's policy from GIVEN start poses in GIVEN scenes:
+    naf_chain_env_reset_given, then per frame one batched act() and one naf_chain_env_rollout_step — a captured one-step graph, as
+    DeviceEnvLoop's (use_graph=False: direct launches). Nothing is appended anywhere and the learner is only read."""
+
+    def __init__(self, learner: Learner, chain, n_envs: int, obstacle_radius: float = 0.06, seed: int = 0, use_graph: bool = True):
+        import ctypes
+        self.L, self.E, self.lib, self.chain = learner, int(n_envs), learner.lib, chain
+        lay, dev = learner.lay, learner.dev
+        if chain.A != lay.A or chain.state_size != lay.S:
+            raise ValueError(f"DeviceRollout: the chain model drives {chain.A} joints (state size {chain.state_size}), the agent "
+                             f"was built for action_size {lay.A} / state_size {lay.S}")
+        if self.E < 1:
+            raise ValueError("DeviceRollout: n_envs is a positive number of envs")
+        self.obstacle_radius = float(obstacle_radius)
+        self.use_graph = use_graph
+        self.actor = ActPath(learner, self.E, seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
+        blob = np.ascontiguousarray(chain.pack(), np.float32)
+        self._chain_env = ctypes.c_void_p()
+        check(self.lib.naf_chain_env_create(blob.ctypes.data, int(blob.size), ctypes.byref(self._chain_env)), "chain_env_create")
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.env_state = torch.zeros(self.E, self.lib.naf_chain_env_state_floats(self._chain_env), **f32)
+        self.outcome = torch.zeros(self.E, 8, **f32)
+        self.start = torch.zeros(self.E, 5, **f32)           # naf_chain_env_probe behind the reset
+        self.q0 = torch.zeros(self.E, lay.A, **f32)
+        self.scene = torch.zeros(self.E, 6, **f32)
+        self.traj: Optional[torch.Tensor] = None             # [frames + 1][E][A], kept once a run has recorded trajectories
+        self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}  # one-step graphs by (frames, noise scale, trajectory pointer)
+        self._key = None
+
+    def __del__(self):
+        if getattr(self, "_chain_env", None) is not None:
+            self.lib.naf_chain_env_destroy(self._chain_env)
+            self._chain_env = None
+
+    @staticmethod
+    def chunks(n: int, e: int) -> List[Tuple[int, int, int]]:
+        """[(first query, queries, padding)] of n queries over e envs; only the last chunk can be padded (with copies of its last
+        query, which are dropped from the result)."""
+        return [(first, min(e, n - first), e - min(e, n - first)) for first in range(0, n, e)]
+
+    def _body(self) -> None:
+        frames, noise_scale, traj = self._key
+        self.actor.act(noise_scale)
+        check(self.lib.naf_chain_env_rollout_step(self._chain_env, ptr(self.env_state), ptr(self.actor.actions), ptr(self.actor.obs),
+                                                  ptr(self.outcome), traj, self.E, frames, stream_ptr()), "chain_env_rollout_step")
+
+    def _prepare(self, frames: int, noise_scale: float, trajectories: bool) -> None:
+        """The trajectory buffer and the one-step graph for this frame budget and noise scale (both are arguments of its launches).
+        The buffer stays when a run does without trajectories (its launches get NULL), and every graph captured is kept, so
+        alternating between settings neither re-allocates nor recaptures; another frame budget drops the buffer and its graphs."""
+        if trajectories and (self.traj is None or self.traj.shape[0] != frames + 1):
+            self.traj = None
+            self._graphs = {k: g for k, g in self._graphs.items() if k[2] is None}
+            self.traj = torch.zeros(frames + 1, self.E, self.L.lay.A, dtype=torch.float32, device=self.L.dev)
+        self._key = (frames, noise_scale, self.traj.data_ptr() if trajectories else None)
+        if self.use_graph and self._key not in self._graphs:
+            # the warm-up steps whatever the envs hold: every run starts with a reset, only the noise position is put back
+            self._graphs[self._key] = _capture(self._body, _StateSnapshot(self.L, None, (self.actor.counter,)))
+
+    def run(self, q0, targets, obstacles, frames: int, noise_scale: float = 0.0, trajectories: bool = True) -> ReachResult:
+        """q0[N][A] (action order), targets[N][3], obstacles[N][3] -> ReachResult. Queries beyond n_envs run in chunks of n_envs.
+        With noise_scale = 0 a query's result depends on nothing but the query and the policy: alone on one env or in any chunk, the
+        same bits. With noise the draw is keyed by (seed, act() ordinal since the start of the run, env index): a run is repeatable,
+        but a query's noise depends on the chunk and the env it lands in, hence on n_envs and on its position among the queries."""
+        A, E, frames = self.L.lay.A, self.E, int(frames)
+        q0 = np.ascontiguousarray(q0, np.float32).reshape(-1, A)
+        N = len(q0)
+        scenes = np.concatenate([np.asarray(targets, np.float32).reshape(N, 3), np.asarray(obstacles, np.float32).reshape(N, 3)], axis=1)
+        if frames < 1 or N < 1:
+            raise ValueError("DeviceRollout.run: at least one query and one frame")
+        self._prepare(frames, float(noise_scale), trajectories)
+        self.actor.counter.zero_()                 # a run is a function of its arguments and the policy
+        outcome, start = np.empty((N, 8), np.float32), np.empty((N, 5), np.float32)
+        paths = np.empty((N, frames + 1, A), np.float32) if trajectories else None
+        for first, n, pad in self.chunks(N, E):
+            idx = np.concatenate([np.arange(first, first + n), np.full(pad, first + n - 1, np.int64)])
+            self.q0.copy_(torch.from_numpy(q0[idx]))
+            self.scene.copy_(torch.from_numpy(scenes[idx]))
+            st = stream_ptr()
+            check(self.lib.naf_chain_env_reset_given(self._chain_env, ptr(self.env_state), ptr(self.actor.obs), E, ptr(self.q0),
+                                                     ptr(self.scene), self.obstacle_radius, st), "chain_env_reset_given")
+            check(self.lib.naf_chain_env_probe(self._chain_env, ptr(self.env_state), ptr(self.start), E, st), "chain_env_probe")
+            if trajectories:
+                self.traj[0].copy_(self.env_state[:, :A])          # frame 0: the start pose as the reset clamped it
+            for _ in range(frames):
+                if self.use_graph:
+                    self._graphs[self._key].replay()
+                else:
+                    self._body()
+            outcome[first:first + n] = self.outcome.cpu().numpy()[:n]
+            start[first:first + n] = self.start.cpu().numpy()[:n]
+            if paths is not None:
+                # a held env wrote nothing beyond its last frame: those repeat its final pose
+                tr = self.traj.cpu().numpy()[:, :n]
+                t = np.minimum(np.arange(frames + 1)[:, None], outcome[first:first + n, 1].astype(np.int64)[None, :])
+                paths[first:first + n] = np.take_along_axis(tr, t[:, :, None], axis=0).transpose(1, 0, 2)
+        target_start = np.linalg.norm(start[:, :3].astype(np.float64) - scenes[:, :3], axis=1).astype(np.float32)
+        return ReachResult(OUTCOME_NAMES[outcome[:, 0].astype(np.int64)], outcome[:, 1].astype(np.int64), outcome[:, 2].copy(),
+                           outcome[:, 3].copy(), outcome[:, 4].copy(), outcome[:, 5].copy(), paths, target_start, start[:, 3].copy(),
+                           start[:, 4].copy())

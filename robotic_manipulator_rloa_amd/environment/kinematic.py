@@ -16,7 +16,7 @@ With target_range / obstacle_range every episode gets a scene of its own: choose
 from __future__ import annotations
 
 import random
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -98,6 +98,21 @@ def _half_widths(v) -> np.ndarray:
     if not np.all(np.isfinite(out)) or np.any(out < 0.0):
         raise ValueError(f"a scene range is three non-negative half-widths, got {v!r}")
     return out
+
+
+OUTCOMES = ("frames", "reached", "obstacle", "self")      # by outcome code: naf_chain_env_rollout_step's outcome[0]
+
+
+class Trace(NamedTuple):
+    """KinematicEnvironment.trace's result; every field has the queries' leading shape [...]."""
+    code: np.ndarray                  # int: index into OUTCOMES (0: the frame budget was used up)
+    frames: np.ndarray                # int: steps taken
+    final_distance: np.ndarray        # |ee - target| after the last step
+    min_clearance: np.ndarray         # min over the steps of clearance - obstacle radius
+    min_self_clearance: np.ndarray    # min over the steps of the self-clearance, +inf without pairs
+    score: np.ndarray                 # sum of the rewards, in step order
+    joint_positions: np.ndarray       # [..., frames + 1, A]: the path; a finished query repeats its final pose
+    margins: np.ndarray               # [..., frames, 3]: distance - 0.05 | clearance - obstacle radius | self-clearance; NaN: no step
 
 
 class KinematicEnvironment:
@@ -241,6 +256,94 @@ class KinematicEnvironment:
         hit = clear < self.obstacle_radius or self_clear < 0.0        # environment.py:311-343: either collision ends the episode
         reward = 250 if reached else (-1000 if hit else -1 * (dist - TARGET_THRESHOLD))
         return state, reward, 1 if (reached or hit) else 0
+
+
+    def trace(self, q0, actions, target, obstacle, frames: int) -> Trace:
+        """The rollout rule of naf_chain_env_rollout_step in float64: from the joint values q0[..., A] (clamped into the limits),
+        step t applies actions[..., t, A] under step()'s rule in the scene target[..., 3] / obstacle[..., 3], until the query
+        reaches the target, touches the obstacle or itself, or has taken `frames` steps; from then on it is held. Pure: neither
+        self.q, the episode's scene nor any RNG is touched."""
+        q = np.array(q0, float)
+        lead = q.shape[:-1]
+        A, frames = self.n, int(frames)
+        actions = np.broadcast_to(np.asarray(actions, float), lead + (frames, A))
+        target = np.broadcast_to(np.asarray(target, float), lead + (3,))
+        obstacle = np.broadcast_to(np.asarray(obstacle, float), lead + (3,))
+        lo = np.array([j.lower if j.limited else -np.inf for j in self.model.joints])
+        hi = np.array([j.upper if j.limited else np.inf for j in self.model.joints])
+        q = np.minimum(np.maximum(q, lo), hi)
+        code, steps = np.zeros(lead, np.int64), np.zeros(lead, np.int64)
+        live = np.ones(lead, bool)
+        dist, score = np.full(lead, np.nan), np.zeros(lead)
+        min_clear, min_self = np.full(lead, np.inf), np.full(lead, np.inf)
+        path = np.empty(lead + (frames + 1, A))
+        margins = np.full(lead + (frames, 3), np.nan)
+        path[..., 0, :] = q
+        for t in range(frames):
+            q = np.where(live[..., None], np.minimum(np.maximum(q + DT * actions[..., t, :], lo), hi), q)
+            path[..., t + 1, :] = q
+            # step()'s own expression, vector by vector (a norm taken along an axis rounds differently from the norm of one vector)
+            d = (self.end_effector(q) - target).reshape(-1, 3)
+            d = np.array([np.linalg.norm(v) for v in d]).reshape(lead)
+            clear = self.clearance(q, obstacle) - self.obstacle_radius
+            self_clear = self.self_clearance(q) + np.zeros(lead)
+            reached, hit, self_hit = d < TARGET_THRESHOLD, clear < 0.0, self_clear < 0.0
+            reward = np.where(reached, 250.0, np.where(hit | self_hit, -1000.0, -1 * (d - TARGET_THRESHOLD)))
+            margins[..., t, :] = np.where(live[..., None], np.stack([d - TARGET_THRESHOLD, clear, self_clear], axis=-1), np.nan)
+            dist = np.where(live, d, dist)
+            score = np.where(live, score + reward, score)
+            min_clear = np.where(live, np.minimum(min_clear, clear), min_clear)
+            min_self = np.where(live, np.minimum(min_self, self_clear), min_self)
+            steps = steps + live
+            code = np.where(live, np.where(reached, 1, np.where(hit, 2, np.where(self_hit, 3, 0))), code)
+            live = live & ~(reached | hit | self_hit)
+        return Trace(code, steps, dist, min_clear, min_self, score, path, margins)
+
+
+def reach_queries(model: ChainModel, targets, obstacles, initial_joint_positions, frames, nominal_obstacle=None, nominal_start=None):
+    """The arguments of a rollout to given targets, checked and broadcast: (q0[N, A], targets[N, 3], obstacles[N, 3], frames) as
+    float64 arrays. targets: [N][3], or [3] for one query. obstacles: [N][3], [3] (every query's) or None (nominal_obstacle).
+    initial_joint_positions: [N][A], [A] (every query's) or None (nominal_start, else the model's initial positions); entry m is
+    the value of driven joint m, i.e. of involved_joints[m]. ValueError for a wrong shape, a number that is not finite, a joint
+    value outside its limits (the message names the joint and the query) or frames < 1."""
+    A = model.A
+    if isinstance(frames, bool) or not isinstance(frames, (int, np.integer)) or frames < 1:
+        raise ValueError(f"frames is a number of steps, at least 1: got {frames!r}")
+
+    def numbers(v, what):
+        try:
+            out = np.array(v, float)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what} is not an array of numbers") from None
+        if not np.all(np.isfinite(out)):
+            raise ValueError(f"{what} holds a number that is not finite")
+        return out
+    t = numbers(targets, "targets")
+    if t.shape == (3,):
+        t = t[None]
+    if t.ndim != 2 or t.shape[1] != 3 or len(t) == 0:
+        raise ValueError(f"targets is [N][3], or [3] for one query: got shape {t.shape}")
+    N = len(t)
+    if obstacles is None:
+        if nominal_obstacle is None:
+            raise ValueError("obstacles=None needs the scene's nominal obstacle")
+        obstacles = nominal_obstacle
+    o = numbers(obstacles, "obstacles")
+    if o.shape != (3,) and o.shape != (N, 3):
+        raise ValueError(f"obstacles is [N][3] with N = {N}, or [3] for all queries: got shape {o.shape}")
+    if initial_joint_positions is None:
+        initial_joint_positions = [j.init for j in model.joints] if nominal_start is None else nominal_start
+    q = numbers(initial_joint_positions, "initial_joint_positions")
+    if q.shape != (A,) and q.shape != (N, A):
+        raise ValueError(f"initial_joint_positions is [N][{A}] with N = {N}, or [{A}] for all queries (one value per involved "
+                         f"joint): got shape {q.shape}")
+    q = np.broadcast_to(q, (N, A))
+    for m, j in enumerate(model.joints):
+        bad = np.nonzero((q[:, m] < j.lower) | (q[:, m] > j.upper))[0] if j.limited else ()
+        if len(bad):
+            raise ValueError(f"initial_joint_positions of query {int(bad[0])}: joint {j.index} (involved_joints[{m}]) at "
+                             f"{q[bad[0], m]:.6g} is outside its limits [{j.lower:.6g}, {j.upper:.6g}]")
+    return q.copy(), t, np.broadcast_to(o, (N, 3)).copy(), int(frames)
 
 
 def build_kinematic(manipulator_file, endeffector_index, fixed_joints, involved_joints, target_position, obstacle_position,

@@ -22,7 +22,8 @@ import numpy as np
 import torch
 
 from .. import _lib, training_state
-from ..engine import DeviceEnvLoop, EpisodeLedger, TimestepGraph, UpdateChunk
+from ..engine import DeviceEnvLoop, DeviceRollout, EpisodeLedger, ReachResult, TimestepGraph, UpdateChunk
+from ..environment.kinematic import reach_queries
 from ..learner import ActPath, Learner
 from ..utils.exceptions import MissingWeightsFile
 from ..utils.logger import get_global_logger
@@ -739,6 +740,42 @@ class NAFAgent:
                     results.append((ordinal, env, bool(done) and last_reward == 250, nfr - 1, bool(done)))
         results.sort()
         return [tuple(r[2:]) for r in results]
+
+    def rollout_vectorized(self, chain, targets, obstacles=None, initial_joint_positions=None, frames: int = 400,
+                           noise_scale: float = 0.0, n_envs: Optional[int] = None, trajectories: bool = True,
+                           scene: Optional[dict] = None) -> ReachResult:
+        """The policy rolled out to GIVEN targets on the device (engine.DeviceRollout): query i starts at
+        initial_joint_positions[i] (None: the chain's initial positions, no variation) with target targets[i] and obstacle
+        obstacles[i] (None: scene['obstacle']) and runs until it reaches the target, touches the obstacle or itself, or has taken
+        `frames` steps. Shapes and checks: environment.kinematic.reach_queries. noise_scale defaults to 0: a plan is deterministic
+        unless noise is asked for, and a query's result then does not depend on the other queries or on n_envs. With noise the
+        stream derives from the agent's seed, as evaluate_vectorized's; two equal calls agree, but a query's noise depends on the
+        chunk and env it lands in (DeviceRollout.run). n_envs: envs per chunk (None: the number of queries, at most 4096).
+        scene: {'obstacle': xyz, 'obstacle_radius': r}, both optional; no other key is taken.
+        The DeviceRollout of the last (chain, n_envs, obstacle radius) is kept on the agent with its captured graphs: a second call
+        of the same shape captures nothing. Nothing is learned or appended; the agent's training state is untouched."""
+        if self.world_size > 1:
+            raise ValueError("rollout_vectorized answers a query on one GPU: not with a data-parallel agent")
+        scene = scene or {}
+        unknown = set(scene) - {"obstacle", "obstacle_radius"}
+        if unknown:
+            raise ValueError(f"scene: unknown keys {sorted(unknown)} (a rollout takes 'obstacle' and 'obstacle_radius')")
+        radius, noise_scale = float(scene.get("obstacle_radius", 0.06)), float(noise_scale)
+        if not (np.isfinite(radius) and radius >= 0.0):
+            raise ValueError(f"scene['obstacle_radius'] is a non-negative length: got {radius!r}")
+        if not (np.isfinite(noise_scale) and noise_scale >= 0.0):
+            raise ValueError(f"noise_scale is a non-negative factor: got {noise_scale!r}")
+        q0, targets, obstacles, frames = reach_queries(chain, targets, obstacles, initial_joint_positions, frames,
+                                                       nominal_obstacle=scene.get("obstacle"))
+        E = min(len(q0), 4096) if n_envs is None else int(n_envs)
+        if E < 1:
+            raise ValueError(f"n_envs is a positive number of envs: got {n_envs!r}")
+        key = (chain.digest(), E, radius, self.use_graph)
+        if getattr(self, "_rollout", None) is None or self._rollout[0] != key:
+            self._rollout = None                   # (the old one's buffers go before the new one's are allocated)
+            self._rollout = (key, DeviceRollout(self.learner, chain, E, obstacle_radius=radius,
+                                                seed=self.seed + 15485863 + 104729 * self.rank, use_graph=self.use_graph))
+        return self._rollout[1].run(q0, targets, obstacles, frames, noise_scale=noise_scale, trajectories=trajectories)
 
     def evaluate_host_vectorized(self, vec_env, n_episodes: int, noise_scale: float = 1.0) -> List[Tuple[bool, int, bool]]:
         """The same for E host environments in worker processes (frame budget = vec_env.max_frames)."""

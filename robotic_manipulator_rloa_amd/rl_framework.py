@@ -30,7 +30,7 @@ from typing import List, Optional, Union
 import numpy as np
 import torch
 
-from .environment.kinematic import SCENE_CONDITIONS, KinematicEnvironment, build_kinematic, choose_scene
+from .environment.kinematic import SCENE_CONDITIONS, KinematicEnvironment, build_kinematic, choose_scene, reach_queries
 from .environment.synthetic import SyntheticEnvironment
 from .environment.urdf_chain import SCENE_TRIES
 from .naf_components.naf_algorithm import NAFAgent
@@ -255,6 +255,44 @@ class ManipulatorFramework:
         logger.info(f'Average number of frames required to complete an episode: {summary["mean_frames_to_success"]}')
         logger.info(f'Number of episodes terminated because of collisions: {num_collisions}')
         return summary
+
+    def reach_targets(self, targets, obstacles=None, initial_joint_positions=None, frames: int = 400, noise_scale: float = 0.0,
+                      n_envs: Optional[int] = None, trajectories: bool = True):
+        """Roll the trained policy out to GIVEN targets (kinematic environment only; on the device, thousands at once): query i
+        starts at initial_joint_positions[i], with target targets[i] and obstacle obstacles[i], and runs until it reaches the
+        target, touches the obstacle or itself, or has taken `frames` steps. A query whose start pose is already in contact or at
+        the target is not refused: its first step ends it (see start_* below).
+          targets                 : [N][3], or [3] for a single query
+          obstacles               : [N][3], [3] for all queries, or None: the environment's nominal obstacle
+          initial_joint_positions : [N][A], [A] for all queries, or None: the environment's initial positions, no variation; one
+                                    value per involved joint, in the order of involved_joints
+          noise_scale             : 0 (default): the deterministic plan; 1: the exploration noise every act() of training has
+          n_envs                  : envs per chunk of queries on the device (None: all queries at once, at most 4096)
+        Returns an engine.ReachResult of numpy arrays over the queries: outcome ('reached' | 'obstacle' | 'self' | 'frames'),
+        frames, final_distance, min_clearance, min_self_clearance, score, joint_positions [N][frames + 1][A] (None with
+        trajectories=False; a finished query repeats its final pose) and start_distance / start_clearance / start_self_clearance,
+        the three measures at the start pose. The agent is only read: training can go on afterwards."""
+        if not self.env:
+            raise EnvironmentNotInitialized
+        if not self.naf_agent:
+            raise NAFAgentNotInitialized
+        if not isinstance(self.env, KinematicEnvironment):
+            raise ConfigurationIncomplete('reach_targets() needs the kinematic environment (initialize_kinematic_environment()): '
+                                          'PyBullet and the synthetic stand-in have no given-scene reset')
+        if getattr(self.naf_agent, 'world_size', 1) > 1:
+            raise InvalidNAFAgentParameter('reach_targets() answers a query on one GPU: not with a data-parallel agent')
+        if n_envs is not None and not _positive_int(n_envs):
+            raise InvalidNAFAgentParameter('Number of environments received is not a positive integer')
+        env = self.env
+        nominal = env.obstacle_centre if env.scene_ranges_on else env.obstacle_pos
+        try:
+            q0, targets, obstacles, frames = reach_queries(env.model, targets, obstacles, initial_joint_positions, frames,
+                                                           nominal_obstacle=nominal, nominal_start=env.initial_joint_positions)
+        except ValueError as err:
+            raise InvalidEnvironmentParameter(str(err)) from None
+        return self.naf_agent.rollout_vectorized(env.model, targets, obstacles, q0, frames=frames, noise_scale=float(noise_scale),
+                                                 n_envs=n_envs, trajectories=bool(trajectories),
+                                                 scene={'obstacle_radius': env.obstacle_radius})
 
     # ---- environment ------------------------------------------------------------------------------------------------
     def initialize_environment(self, manipulator_file: str, endeffector_index: int, fixed_joints: List[int],
