@@ -8,18 +8,22 @@ count, a launch loop of the two step kernels for `rocprofv3 --kernel-trace --sta
   rocprofv3 --kernel-trace --stats -d OUT -- python benchmarks/chain_env_bench.py kernels
       1000 launches each of chain_env_step_kernel for standin8 (A = 8, E = 64) and long32, and of synth_env_step_kernel
       (`--autocollision`: the two arms compiled with their self-collision pairs, 18 and 465: the SC = true instantiation)
-  python benchmarks/chain_env_bench.py step --envs 4096 --launches 4000 [--autocollision]
+  python benchmarks/chain_env_bench.py step --envs 4096 --launches 4000 [--autocollision] [--workcell]
       microseconds per naf_chain_env_step launch of --urdf (device events around `--launches` launches with the step counter
       running, max_frames = 400, N(0, 1) actions; `--repeats` windows after one warm-up window). Two launches per step are
       enqueued by the host, so at small E the figure is bounded below by launch submission: the kernel's own time comes from
       `rocprofv3 --kernel-trace --stats -d OUT -- python benchmarks/chain_env_bench.py step ...`, a run of its own, whose
       maximum per kernel is the launch in which the envs reset (every 400th).
 
-  python benchmarks/chain_env_bench.py rollout --envs 4096 --launches 4000 [--autocollision]
+  python benchmarks/chain_env_bench.py rollout --envs 4096 --launches 4000 [--autocollision] [--workcell]
       microseconds per naf_chain_env_rollout_step launch of --urdf, measured as `step` measures (the same arm, start pose and seeded
       N(0, 1) actions; ONE launch per step: there is no counter), after naf_chain_env_reset_given at the start pose with target and
       obstacle 3 m away and a frame budget beyond the run, so that every env stays live: a held lane returns at once and would
       flatter the figure. `--trajectory`: the joint values of a window of frames are recorded too (the budget is then the window).
+
+`--workcell` (step, rollout): the chain model gets a floor under the base and two spheres beside the arm, so the launches are the
+workcell instantiations. In a rollout an env that touches one of them is held from then on: `envs_held_before_the_window_ended`
+says how many did.
 
 `--target-range X Y Z` / `--obstacle-range X Y Z` (rate, step): half-widths of the boxes every episode draws its target / obstacle
 from (include/naf_hip.h, "Scene ranges"); step then also prints how the episode starts of the run chose their scenes.
@@ -71,6 +75,13 @@ def rate(a):
     print(json.dumps({"envs": a.envs, "batch": a.batch, "steps": a.steps, "warmup": a.warmup, "joints": a.joints, **out}))
 
 
+def _workcell(a) -> dict:
+    """--workcell: a floor under the base and two spheres beside the arm (compile_chain's arguments), clear of the start pose"""
+    if not a.workcell:
+        return {}
+    return {"floor_height": 0.0, "workcell_spheres": [(0.51, 0.38, 0.64, 0.128), (-0.4, -0.4, 0.5, 0.1)]}
+
+
 def _ranges(a) -> dict:
     if a.target_range is None and a.obstacle_range is None:
         return {}
@@ -89,7 +100,8 @@ def step(a):
     # the start pose and reset ranges of the README's example on the first seven joints, 0 +- 0.1 on any further one
     init = ([0.0, 0.6, 0.0, -1.2, 0.0, 0.8, 0.0] + [0.0] * n)[:n]
     var = ([0.1, 0.1, 0.1, 0.1, 0.2, 0.2, 0.2] + [0.1] * n)[:n]
-    model = compile_chain(load_urdf(urdf), n - 1, list(range(n)), [n], init, var, 0.03, consider_autocollision=a.autocollision)
+    model = compile_chain(load_urdf(urdf), n - 1, list(range(n)), [n], init, var, 0.03, consider_autocollision=a.autocollision,
+                          **_workcell(a))
     blob = np.ascontiguousarray(model.pack())
     h = ctypes.c_void_p()
     _lib.check(lib.naf_chain_env_create(blob.ctypes.data, int(blob.size), ctypes.byref(h)), "create")
@@ -121,7 +133,7 @@ def step(a):
             times.append(round(1e3 * t0.elapsed_time(t1) / a.launches, 3))
         starts += int(st[:, n + 8].sum().item() - before)
     out = {"arm": os.path.basename(urdf), "envs": E, "autocollision": a.autocollision, "self_pairs": len(model.self_pairs),
-           "launches": a.launches, "ranges": ranges or None, "us_per_step_and_counter_launch": times, "episode_starts": starts}
+           "workcell_pairs": len(model.cell_pairs), "launches": a.launches, "ranges": ranges or None, "us_per_step_and_counter_launch": times, "episode_starts": starts}
     if ranges:      # the scenes the envs hold now: the centres, exactly, are fallbacks
         s = st[:, n:n + 6].cpu().numpy()
         out["fallback_share_now"] = round(float(np.mean(np.all(s == np.float32(centre), axis=1))), 4)
@@ -140,7 +152,8 @@ def rollout(a):
     urdf = os.path.abspath(a.urdf) if os.path.isabs(a.urdf) else os.path.join(ROOT, a.urdf)
     init = ([0.0, 0.6, 0.0, -1.2, 0.0, 0.8, 0.0] + [0.0] * n)[:n]             # step's arm and start pose
     var = ([0.1, 0.1, 0.1, 0.1, 0.2, 0.2, 0.2] + [0.1] * n)[:n]
-    model = compile_chain(load_urdf(urdf), n - 1, list(range(n)), [n], init, var, 0.03, consider_autocollision=a.autocollision)
+    model = compile_chain(load_urdf(urdf), n - 1, list(range(n)), [n], init, var, 0.03, consider_autocollision=a.autocollision,
+                          **_workcell(a))
     blob = np.ascontiguousarray(model.pack())
     h = ctypes.c_void_p()
     _lib.check(lib.naf_chain_env_create(blob.ctypes.data, int(blob.size), ctypes.byref(h)), "create")
@@ -171,7 +184,7 @@ def rollout(a):
             held.append(int(((outcome[:, 0] != 0) | (outcome[:, 1] < (a.launches if a.trajectory else a.launches * (w + 1)))).sum().item()))
     lib.naf_chain_env_destroy(h)
     print(json.dumps({"arm": os.path.basename(urdf), "envs": E, "autocollision": a.autocollision, "self_pairs": len(model.self_pairs),
-                      "launches": a.launches, "trajectory": bool(a.trajectory), "us_per_rollout_step_launch": times,
+                      "workcell_pairs": len(model.cell_pairs), "launches": a.launches, "trajectory": bool(a.trajectory), "us_per_rollout_step_launch": times,
                       "envs_held_before_the_window_ended": held}))
 
 
@@ -224,6 +237,7 @@ def main():
     ap.add_argument("--launches", type=int, default=1000)
     ap.add_argument("--standin-only", action="store_true")
     ap.add_argument("--autocollision", action="store_true")
+    ap.add_argument("--workcell", action="store_true", help="step / rollout: a floor and two spheres in the chain model")
     ap.add_argument("--trajectory", action="store_true", help="rollout: record the joint values of every frame")
     ap.add_argument("--arm", default="", help="rate: a fixture arm of tests/golden/urdf by name, --joints its joint count")
     ap.add_argument("--target-range", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))

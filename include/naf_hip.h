@@ -67,7 +67,7 @@ typedef struct {
 /* ---- library ------------------------------------------------------------------------------ */
 /* Bumped whenever a signature or a struct in this header changes; the ctypes host compares the library's answer with
  * the value in this header and refuses a mismatch (a stale .so would otherwise be called with wrong argument lists). */
-#define NAF_HIP_ABI_VERSION 39
+#define NAF_HIP_ABI_VERSION 40
 int naf_hip_abi_version(void);
 /* "gfx950" — the only architecture this library carries code objects for */
 const char* naf_hip_arch(void);
@@ -666,7 +666,7 @@ int naf_synth_env_reset(float* env_state, float* obs, int E, int A, uint64_t see
                         const float* preset_host, int preset_floats, void* stream);
 int naf_synth_env_state_floats(int A);
 
-/* ---- kinematic environment of a URDF manipulator (ABI 36; self-collision and probe: ABI 37; scene ranges: ABI 38; rollout: ABI 39) ----------------------------------------------------------------
+/* ---- kinematic environment of a URDF manipulator (ABI 36; self-collision and probe: ABI 37; scene ranges: ABI 38; rollout: ABI 39; workcell: ABI 40) ----------------------------------------------------------------
  * E copies of the serial chain environment/urdf_chain.py compiles from the user's URDF, stepped on the device under the
  * reference's environment rule (environment/environment.py:431-485: state layout, reward, terminal rule, velocity control
  * of the involved joints, held joints). Kinematic — the commanded velocity is applied exactly for one 1/240 s tick, then the
@@ -677,7 +677,8 @@ int naf_synth_env_state_floats(int A);
  * Chain model blob (float32, every count and index stored as a float; ChainModel.pack writes it, model_check reads it):
  *   header, NAF_CHAIN_HEADER_FLOATS: [0] NAF_CHAIN_BLOB_VERSION  [1] A (driven joints = action size, 1 .. 64)  [2] segments
  *     [3] observation slots (= A)  [4] end-effector frame  [5..7] end-effector point in that frame  [8] floats in the blob
- *     [9] self-collision pairs P (0: none, the blob then ends after the slots)  [10..15] 0
+ *     [9] self-collision pairs P (0: none, the blob then ends after the slots)  [10] workcell spheres G  [11] workcell
+ *     half-spaces H (G + H <= NAF_CHAIN_MAX_CELL; both 0: no workcell, the blob then ends after the pairs)  [12..15] 0
  *   A driven joints in action order, NAF_CHAIN_JOINT_FLOATS each: [0..8] pre-rotation, row-major 3 x 3  [9..11] pre-translation
  *     [12..14] unit axis  [15] type, 0 revolute / 1 prismatic  [16] 1 = has position limits  [17] lower  [18] upper
  *     [19] initial position  [20] half-width of the reset range  [21] observation slot reporting this joint, or -1  [22..23] 0
@@ -691,6 +692,14 @@ int naf_synth_env_state_floats(int A);
  *   P self-collision pairs, 2 floats each: segment indices [0] s < [1] t, no pair twice;
  *     self-contact = distance(segment s, segment t) - radius s - radius t < 0 for any pair: reward -1000 and done, as obstacle
  *     contact (reaching the target still wins). NAF_CHAIN_BLOB_VERSION stays 1: without pairs the bytes are ABI 36's.
+ *   Workcell (ABI 40; only when G + H > 0), fixed geometry that is the same in every episode and has no slot in the observation:
+ *     G spheres, 4 floats each: centre xyz, radius >= 0;  H half-spaces, 4 floats each: unit normal n, offset d, the free side
+ *     is n.x - d >= 0;  then one mask float per segment: bit g set = test this segment against geometry g, spheres first (an
+ *     integer below 2^(G+H) <= 65536, exact in a float). Clearance of a capsule (world end points a, b, radius rho):
+ *     distance(segment ab, centre) - rho - r against a sphere, min(n.a, n.b) - d - rho against a half-space. Workcell contact =
+ *     a tested (segment, geometry) pair with clearance < 0: reward -1000 and done, as obstacle contact (reaching the target
+ *     still wins). The workcell clearance of a pose is the minimum over the tested pairs, +inf when there are none.
+ *     NAF_CHAIN_BLOB_VERSION stays 1: with G = H = 0 the bytes are ABI 39's, and so is every launch.
  *
  * env_state record of one env, naf_chain_env_state_floats floats = round_up(round_up(A + 9, 2) + 2, 4):
  *   [0 .. A) driven joint positions by action index  [A .. A+3) target  [A+3 .. A+6) obstacle centre  [A+6] obstacle radius
@@ -709,10 +718,13 @@ int naf_synth_env_state_floats(int A);
  *                 per-env running score (double, step order), frame budget, auto-reset, one episode record per
  *                 (step mod record_slots, env), the same Philox keying of the reset draws and of the obstacle jitter.
  *                 With P = 0 the launch is ABI 36's kernel. The auto-reset inside step does not test the reset pose against
- *                 itself: a reset pose in self-contact ends its episode at the next step.
+ *                 itself: a reset pose in self-contact ends its episode at the next step. Neither against the workcell: the
+ *                 same rule. With G + H > 0 the launch is a further instantiation of the kernel (csrc/chain_env.hip).
  *   probe       : out [E][NAF_CHAIN_PROBE_FLOATS] = [end-effector xyz | min over segments of (distance to the obstacle centre -
  *                 capsule radius) - obstacle radius (obstacle contact iff < 0) | min over the pairs of the pair clearance
  *                 (self-contact iff < 0; +inf when P = 0)] at the joint values and scene in env_state; changes no state.
+ *   probe_cell  : out [E] = the workcell clearance of each env's pose (workcell contact iff < 0; +inf when no pair is tested);
+ *                 changes no state. NAF_ERR_STATE when the handle's blob has no workcell.
  *
  * Scene ranges (ABI 38): a new target and obstacle at the start of every episode — the reset and every auto-reset inside step.
  *   set_scene_ranges : ranges_host = NAF_CHAIN_RANGE_FLOATS HOST floats [target half-widths xyz | obstacle half-widths xyz |
@@ -748,7 +760,8 @@ int naf_synth_env_state_floats(int A);
  *                 own lane every live step: [0] code, 0 = running or frame budget used up, 1 = reached, 2 = obstacle contact,
  *                 3 = self-contact (precedence 1 > 2 > 3)  [1] frames stepped  [2] |ee - target| after the last step  [3] min over
  *                 the steps so far of probe's [3]  [4] min over the steps so far of probe's [4], +inf when P = 0  [5] score as
- *                 float  [6..7] 0. (3) traj (NULL, or DEVICE [max_frames + 1][E][A]): a live env writes its post-step joint values
+ *                 float  [6] with a workcell: min over the steps so far of probe_cell's value, and code 4 = workcell contact
+ *                 (precedence 1 > 2 > 3 > 4); 0 without  [7] 0. (3) traj (NULL, or DEVICE [max_frames + 1][E][A]): a live env writes its post-step joint values
  *                 to traj[frame][e]; frame 0 is the caller's (q0), as are a held env's later frames.
  *                 No transition rows, no episode records, no counter. The record and every prototype above are unchanged. */
 #define NAF_CHAIN_BLOB_VERSION 1
@@ -765,6 +778,9 @@ int naf_synth_env_state_floats(int A);
 #define NAF_CHAIN_ERR_SEGMENTS (-17) /* begin table not monotone, or a segment outside its frame's range (unsorted) */
 #define NAF_CHAIN_ERR_SLOTS (-18)
 #define NAF_CHAIN_ERR_PAIRS (-19)    /* pair count or table size, an index out of range or not an integer, s >= t, a pair twice */
+#define NAF_CHAIN_ERR_CELL (-21)     /* workcell: a count out of range, a non-unit normal, a negative radius, a mask that is not an
+                                        integer below 2^(G+H), a wrong blob size */
+#define NAF_CHAIN_MAX_CELL 16
 #define NAF_CHAIN_ERR_LDS (-20)      /* create: P > 0 and one env's capsule end points exceed a workgroup's LDS */
 #define NAF_CHAIN_PROBE_FLOATS 5
 #define NAF_CHAIN_SCENE_TRIES 8
@@ -781,6 +797,7 @@ int naf_chain_env_step(naf_chain_env_t* h, float* env_state, const float* action
                        int record_slots, void* stream);
 int naf_chain_env_probe(naf_chain_env_t* h, const float* env_state, float* out, int E, void* stream);
 int naf_chain_env_set_scene_ranges(naf_chain_env_t* h, const float* ranges_host);
+int naf_chain_env_probe_cell(naf_chain_env_t* h, const float* env_state, float* out, int E, void* stream);
 #define NAF_CHAIN_OUTCOME_FLOATS 8
 int naf_chain_env_reset_given(naf_chain_env_t* h, float* env_state, float* obs, int E, const float* q0_dev, const float* scene_dev,
                               float obstacle_radius, void* stream);

@@ -257,6 +257,7 @@ _PROTOS = {
     "naf_chain_env_step": [_vp, _vp, _vp, _vp, _vp, _i, _u64, _vp, _i, _vp, _i, _vp],
     "naf_chain_env_probe": [_vp, _vp, _vp, _i, _vp],
     "naf_chain_env_set_scene_ranges": [_vp, _vp],
+    "naf_chain_env_probe_cell": [_vp, _vp, _vp, _i, _vp],
     "naf_chain_env_reset_given": [_vp, _vp, _vp, _i, _vp, _vp, _f, _vp],
     "naf_chain_env_rollout_step": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
 }

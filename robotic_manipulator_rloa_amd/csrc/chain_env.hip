@@ -27,12 +27,18 @@
 // candidate's clearance beside the end effector (CH_TRIES clearances in registers, every loop over them unrolled), and the first
 // candidate that meets the three conditions of include/naf_hip.h becomes the scene, the nominal scene if none does. No trip count
 // depends on a draw. In an SC workgroup this is the walking wave's business alone, as the auto-reset already is.
+//
+// Workcell (G + H > 0 fixed spheres and half-spaces in the blob) is one more instantiation of the step and rollout kernels,
+// CELL = true, and a probe of its own; without one the launches are the CELL-less kernels, unchanged. The walk tests each capsule,
+// behind its obstacle test, against the geometries its mask names: counts, mask and geometry come through uniform loads, the
+// trip counts are uniform, and nothing is kept per lane but the running minimum. The walk of an auto-reset pose does not test.
 #include "common.h"
 #include "../../include/naf_hip.h"
 
 #include <algorithm>
 #include <cmath>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #define CH_DT (1.0f / 240.0f)
@@ -47,6 +53,7 @@
 struct naf_chain_env {
     float* model_dev;
     int n_floats, A, n_seg;
+    int n_cell;                     // G + H: workcell geometries in the blob (0: the CELL-less kernels are launched)
     int n_pairs, lanes, waves;      // P; with P > 0: envs per workgroup (64, 32, .. 1) and waves per workgroup
     float ranges[NAF_CHAIN_RANGE_FLOATS];      // set_scene_ranges: target half-widths | obstacle half-widths | margin
     float centre[6];                // target | obstacle of the last reset's scene_host: the boxes' centres and the fallback
@@ -76,6 +83,8 @@ struct SceneCand {
 };
 // The kernels take the ranges as a trailing parameter PACK: one ChainRanges in a SCENE launch, nothing in a SCENE = false one,
 // whose kernel arguments are then exactly those of the kernels before the ranges existed.
+// a further, empty member of the pack: the launch tests the workcell (chain_env_step_kernel)
+struct ChainCell {};
 template <class... Rest>
 __device__ static inline const ChainRanges& scene_ranges(const ChainRanges& rg, const Rest&...) { return rg; }
 
@@ -83,6 +92,8 @@ __host__ __device__ static inline int ch_off_begin(int A) { return CH_HDR + CH_J
 __host__ __device__ static inline int ch_off_seg(int A) { return ch_off_begin(A) + A + 2; }
 __host__ __device__ static inline int ch_off_slot(int A, int n_seg) { return ch_off_seg(A) + CH_SEG * n_seg; }
 __host__ __device__ static inline int ch_off_pair(int A, int n_seg) { return ch_off_slot(A, n_seg) + 2 * A; }
+// the workcell section: G spheres, H half-spaces (4 floats each), then n_seg masks
+__host__ __device__ static inline int ch_off_cell(int A, int n_seg, int n_pairs) { return ch_off_pair(A, n_seg) + 2 * n_pairs; }
 // dynamic LDS of an SC launch: end points [n_seg][6][lanes], then one minimum per (wave, lane)
 __host__ __device__ static inline size_t ch_lds_bytes(int n_seg, int lanes, int waves) {
     return ((size_t)n_seg * 6 + waves) * lanes * sizeof(float);
@@ -136,15 +147,19 @@ __device__ static inline float seg_seg_dist2(float ax, float ay, float az, float
 }
 
 // Where the SC instantiations keep the capsules' world end points: `ends` is the LDS array already offset by the lane, `lanes`
-// its innermost extent. CLEAR: `clear` collects min over the capsules of (distance to the obstacle centre - capsule radius).
+// its innermost extent. CLEAR: `clear` collects min over the capsules of (distance to the obstacle centre - capsule radius),
+// and with CELL `cell` the workcell clearance: min over the tested (capsule, geometry) pairs.
 struct WalkAux {
     float* ends;
     int lanes;
     float clear;
+    float cell;
 };
 
-// contact of the capsules of frame f with the obstacle sphere, and the end-effector point when it lives in f
-template <bool SC, bool PROBE, bool SCENE = false, bool CLEAR = PROBE>
+// contact of the capsules of frame f with the obstacle sphere, and the end-effector point when it lives in f. CELL: also their
+// contact with the workcell — ORed into the result, except with CLEAR, where aux.cell < 0 says it and the result stays the
+// obstacle's own (the rollout tells the two apart).
+template <bool SC, bool PROBE, bool SCENE = false, bool CLEAR = PROBE, bool CELL = false>
 __device__ static inline bool frame_geometry(const float* __restrict__ model, int A, int f, const Frame& F, float ox, float oy,
                                              float oz, float orad, int ee_frame, float* ee, WalkAux& aux, SceneCand* cand = nullptr) {
     const float* begin = model + ch_off_begin(A);
@@ -168,6 +183,26 @@ __device__ static inline bool frame_geometry(const float* __restrict__ model, in
             w[3 * aux.lanes] = bx; w[4 * aux.lanes] = by; w[5 * aux.lanes] = bz;
         }
         if constexpr (CLEAR) aux.clear = fminf(aux.clear, sqrtf(d2) - g[7]);
+        if constexpr (CELL) {
+            const int n_sph = (int)model[10], n_geo = n_sph + (int)model[11];
+            const float* geo = model + ch_off_cell(A, (int)model[2], (int)model[9]);
+            const int mask = (int)geo[4 * n_geo + s];
+            float least = INFINITY;
+            for (int k = 0; k < n_geo; ++k) {      // (uniform: the counts, the mask and the geometry are the blob's)
+                if (!(mask >> k & 1)) continue;
+                const float* c = geo + 4 * k;
+                float d;
+                if (k < n_sph) {
+                    d = sqrtf(seg_point_dist2(ax, ay, az, bx, by, bz, c[0], c[1], c[2])) - c[3];
+                } else {
+                    const float na = c[0] * ax + c[1] * ay + c[2] * az, nb = c[0] * bx + c[1] * by + c[2] * bz;
+                    d = fminf(na, nb) - c[3];
+                }
+                least = fminf(least, d - g[7]);
+            }
+            if constexpr (CLEAR) aux.cell = fminf(aux.cell, least);
+            else hit |= least < 0.f;
+        }
         if constexpr (SCENE) {
             // seg_point_dist2 for CH_TRIES centres against ONE segment: its direction and 1 / |u|^2 are computed once, and the
             // root is the hardware's (1 ulp): both far inside the band in which the choice is compared with the twin's
@@ -194,15 +229,15 @@ __device__ static inline bool frame_geometry(const float* __restrict__ model, in
 // Walks the chain at the joint values in st[0 .. A): writes the position slots, the constants' slots (velocity 0), the end
 // effector, target and obstacle into the observation `o` (not with PROBE: o is unused); the DRIVEN joints' velocity slots are the
 // caller's. Returns contact with the obstacle. CLEAR (the probe's walk, and the rollout step's beside its observation) also collects
-// the obstacle clearance in aux.clear.
-template <bool SC, bool PROBE, bool SCENE = false, bool CLEAR = PROBE>
+// the obstacle clearance in aux.clear. CELL: the workcell is tested too (frame_geometry).
+template <bool SC, bool PROBE, bool SCENE = false, bool CLEAR = PROBE, bool CELL = false>
 __device__ static inline bool chain_walk(const float* __restrict__ model, int A, int n_seg, const float* st, float* o, float* ee,
                                          WalkAux& aux, SceneCand* cand = nullptr) {
     const int ee_frame = (int)model[4];
     const float ox = st[A + 3], oy = st[A + 4], oz = st[A + 5], orad = st[A + 6];
     Frame F = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
     ee[0] = ee[1] = ee[2] = 0.f;
-    bool hit = frame_geometry<SC, PROBE, SCENE, CLEAR>(model, A, 0, F, ox, oy, oz, orad, ee_frame, ee, aux, cand);
+    bool hit = frame_geometry<SC, PROBE, SCENE, CLEAR, CELL>(model, A, 0, F, ox, oy, oz, orad, ee_frame, ee, aux, cand);
     for (int m = 0; m < A; ++m) {
         const float* j = model + CH_HDR + m * CH_JNT;
         const float q = st[m];
@@ -249,7 +284,7 @@ __device__ static inline bool chain_walk(const float* __restrict__ model, int A,
             F.r21 = G.r20 * m01 + G.r21 * m11 + G.r22 * m21;
             F.r22 = G.r20 * m02 + G.r21 * m12 + G.r22 * m22;
         }
-        hit |= frame_geometry<SC, PROBE, SCENE, CLEAR>(model, A, m + 1, F, ox, oy, oz, orad, ee_frame, ee, aux, cand);
+        hit |= frame_geometry<SC, PROBE, SCENE, CLEAR, CELL>(model, A, m + 1, F, ox, oy, oz, orad, ee_frame, ee, aux, cand);
     }
     if constexpr (!PROBE) {
         const float* slots = model + ch_off_slot(A, n_seg);
@@ -384,12 +419,15 @@ chain_env_reset_kernel(const float* __restrict__ model, float* env_state, float*
 
 // SC = false: one wave per workgroup, lane = env. SC = true: `lanes` envs per workgroup (lane < lanes of every wave), wave 0 is
 // the env's walker and the only one that touches global memory; the others join it for the pair phase.
+// A trailing ChainCell in the pack (CELL below): the walk of the stepped pose also tests the workcell; the walk of an auto-reset
+// pose does not. The instantiations without it keep their arguments, their names and their code.
 template <bool SC, bool SCENE, class... Rg>
 __global__ void __launch_bounds__(SCENE ? (SC ? 64 * CH_SCENE_WAVES : 64) : 64 * CH_MAX_WAVES)
 chain_env_step_kernel(const float* __restrict__ model, float* env_state, const float* __restrict__ actions,
                       float* __restrict__ out_rows, float* __restrict__ obs_next, int E, int A, int n_seg, int row_floats,
                       uint64_t seed, const uint64_t* counter_dev, int max_frames, naf_episode_record_t* __restrict__ records,
                       int record_slots, int n_pairs, int lanes, const Rg... rg) {
+    constexpr bool CELL = (std::is_same_v<Rg, ChainCell> || ... || false);
     extern __shared__ __attribute__((aligned(16))) float ch_lds[];
     int e, lane = 0;
     bool active = true, walker = true;
@@ -431,7 +469,7 @@ chain_env_step_kernel(const float* __restrict__ model, float* env_state, const f
             const int slot = (int)j[21];
             if (slot >= 0) o2[A + slot] = vel;
         }
-        hit = chain_walk<SC, false>(model, A, n_seg, st, o2, ee, aux);
+        hit = chain_walk<SC, false, false, false, CELL>(model, A, n_seg, st, o2, ee, aux);
     }
     if constexpr (SC) {
         // self-contact counts as contact (environment.py:311-343); the walker's lanes hold the minimum over all pairs
@@ -478,6 +516,19 @@ chain_env_step_kernel(const float* __restrict__ model, float* env_state, const f
     } else {
         for (int k = 0; k < S; ++k) ob[k] = o2[k];
     }
+}
+
+// naf_chain_env_probe_cell: the workcell clearance of the pose in env_state. One wave per workgroup, lane = env: the workcell needs
+// no pair phase.
+__global__ void __launch_bounds__(64)
+chain_env_probe_cell_kernel(const float* __restrict__ model, const float* __restrict__ env_state, float* __restrict__ out, int E, int A,
+                            int n_seg) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    float ee[3];
+    WalkAux aux = {nullptr, 0, INFINITY, INFINITY};
+    chain_walk<false, true, false, true, true>(model, A, n_seg, env_state + (int64_t)e * ch_state_floats(A), nullptr, ee, aux);
+    out[e] = aux.cell;
 }
 
 // naf_chain_env_probe: the walk and the pair phase of the step at the joint values in env_state, nothing written but `out`
@@ -544,11 +595,13 @@ chain_env_reset_given_kernel(const float* __restrict__ model, float* env_state, 
 // naf_chain_env_rollout_step: the step kernel's tick for a query instead of a training stream. An env whose episode is over
 // (env_state[A+8] >= 1) is HELD: its lane walks nothing and writes nothing, and in an SC workgroup only joins the barriers. A live
 // lane writes the observation straight into obs_next, keeps its outcome record and, with traj, its joint values of the frame.
-template <bool SC>
+// A trailing ChainCell (CELL below, as in chain_env_step_kernel): code 4 and outcome[6], the workcell's.
+template <bool SC, class... Cell>
 __global__ void __launch_bounds__(SC ? 64 * CH_MAX_WAVES : 64)      // (without SC a workgroup is one wave)
 chain_env_rollout_kernel(const float* __restrict__ model, float* env_state, const float* __restrict__ actions,
                          float* __restrict__ obs_next, float* __restrict__ outcome, float* __restrict__ traj, int E, int A, int n_seg,
-                         int max_frames, int n_pairs, int lanes) {
+                         int max_frames, int n_pairs, int lanes, const Cell... cell) {
+    constexpr bool CELL = (std::is_same_v<Cell, ChainCell> || ... || false);
     extern __shared__ __attribute__((aligned(16))) float ch_lds[];
     int e, lane = 0;
     bool active = true, walker = true;
@@ -572,7 +625,7 @@ chain_env_rollout_kernel(const float* __restrict__ model, float* env_state, cons
         if (!live) return;
     float ee[3];
     bool hit = false;
-    WalkAux aux = {SC ? ch_lds + lane : nullptr, lanes, INFINITY};
+    WalkAux aux = {SC ? ch_lds + lane : nullptr, lanes, INFINITY, INFINITY};
     if (walker) {
         for (int m = 0; m < A; ++m) {
             const float* j = model + CH_HDR + m * CH_JNT;
@@ -587,7 +640,7 @@ chain_env_rollout_kernel(const float* __restrict__ model, float* env_state, cons
             const int slot = (int)j[21];
             if (slot >= 0) ob[A + slot] = vel;
         }
-        hit = chain_walk<SC, false, false, true>(model, A, n_seg, st, ob, ee, aux);
+        hit = chain_walk<SC, false, false, true, CELL>(model, A, n_seg, st, ob, ee, aux);
     }
     float self_clear = INFINITY;
     if constexpr (SC) {
@@ -595,11 +648,12 @@ chain_env_rollout_kernel(const float* __restrict__ model, float* env_state, cons
         if (!walker) return;
     }
     const bool self_hit = self_clear < 0.f;
+    const bool cell_hit = CELL && aux.cell < 0.f;
     float dx = ee[0] - st[A], dy = ee[1] - st[A + 1], dz = ee[2] - st[A + 2];
     float dist = sqrtf(dx * dx + dy * dy + dz * dz);
     const bool reached = dist < 0.05f;
-    const float reward = reached ? 250.f : ((hit || self_hit) ? -1000.f : -(dist - 0.05f));
-    const bool done = reached || hit || self_hit;
+    const float reward = reached ? 250.f : ((hit || self_hit || cell_hit) ? -1000.f : -(dist - 0.05f));
+    const bool done = reached || hit || self_hit || cell_hit;
     const bool first = st[A + 7] == 0.f;
     const float frame = st[A + 7] + 1.f;
     st[A + 7] = frame;
@@ -607,13 +661,14 @@ chain_env_rollout_kernel(const float* __restrict__ model, float* env_state, cons
     const double score = *score_p + (double)reward;
     *score_p = score;
     float* oc = outcome + (int64_t)e * NAF_CHAIN_OUTCOME_FLOATS;
-    oc[0] = reached ? 1.f : (hit ? 2.f : (self_hit ? 3.f : 0.f));
+    oc[0] = reached ? 1.f : (hit ? 2.f : (self_hit ? 3.f : (cell_hit ? 4.f : 0.f)));
     oc[1] = frame;
     oc[2] = dist;
     oc[3] = fminf(first ? INFINITY : oc[3], aux.clear - st[A + 6]);
     oc[4] = fminf(first ? INFINITY : oc[4], self_clear);
     oc[5] = (float)score;
-    oc[6] = 0.f;
+    if constexpr (CELL) oc[6] = fminf(first ? INFINITY : oc[6], aux.cell);
+    else oc[6] = 0.f;
     oc[7] = 0.f;
     if (traj && frame <= (float)max_frames) {      // (a record that did not come from reset_given cannot write past the buffer)
         float* tr = traj + ((int64_t)frame * E + e) * A;
@@ -636,12 +691,16 @@ extern "C" int naf_chain_env_model_check(const float* m, int n_floats) {
     if (!ch_int(m[1], 1, CH_MAX_A, &A) || !ch_int(m[2], 0, 1 << 20, &n_seg) || !ch_int(m[3], A, A, &n_slot))
         return NAF_CHAIN_ERR_COUNTS;
     if (!ch_int(m[8], CH_HDR, 1 << 24, &total) || total != n_floats) return NAF_CHAIN_ERR_SIZE;
-    int P = 0;
+    int P = 0, G = 0, H = 0;
     const bool pairs_counted = ch_int(m[9], 0, 1 << 22, &P);
-    if (pairs_counted && P == 0 && total != ch_off_pair(A, n_seg)) return NAF_CHAIN_ERR_SIZE;
+    // (a blob without a workcell has zeros here and takes every check below as it always did)
+    if (!ch_int(m[10], 0, NAF_CHAIN_MAX_CELL, &G) || !ch_int(m[11], 0, NAF_CHAIN_MAX_CELL - G, &H)) return NAF_CHAIN_ERR_CELL;
+    const int cell = G + H > 0 ? 4 * (G + H) + n_seg : 0;
+    if (pairs_counted && P == 0 && cell == 0 && total != ch_off_pair(A, n_seg)) return NAF_CHAIN_ERR_SIZE;
     for (int k = 0; k < n_floats; ++k)
         if (!std::isfinite(m[k])) return NAF_CHAIN_ERR_VALUE;
-    if (!pairs_counted || total != ch_off_pair(A, n_seg) + 2 * P) return NAF_CHAIN_ERR_PAIRS;
+    if (!pairs_counted || (cell == 0 && total != ch_off_pair(A, n_seg) + 2 * P)) return NAF_CHAIN_ERR_PAIRS;
+    if (cell > 0 && (int64_t)total != (int64_t)ch_off_cell(A, n_seg, P) + cell) return NAF_CHAIN_ERR_CELL;
     if (!ch_int(m[4], 0, A, &ee_frame)) return NAF_CHAIN_ERR_EE;
     for (int k = 0; k < A; ++k) {
         const float* j = m + CH_HDR + k * CH_JNT;
@@ -682,6 +741,17 @@ extern "C" int naf_chain_env_model_check(const float* m, int n_floats) {
     }
     std::sort(seen.begin(), seen.end());
     if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return NAF_CHAIN_ERR_PAIRS;
+    const float* geo = m + ch_off_cell(A, n_seg, P);
+    for (int g = 0; g < G; ++g)
+        if (geo[4 * g + 3] < 0.f) return NAF_CHAIN_ERR_CELL;
+    for (int g = G; g < G + H; ++g) {
+        const float* n = geo + 4 * g;
+        if (std::fabs(n[0] * n[0] + n[1] * n[1] + n[2] * n[2] - 1.f) > 1e-4f) return NAF_CHAIN_ERR_CELL;
+    }
+    for (int s = 0; cell > 0 && s < n_seg; ++s) {
+        int mask;
+        if (!ch_int(geo[4 * (G + H) + s], 0, (1 << (G + H)) - 1, &mask)) return NAF_CHAIN_ERR_CELL;
+    }
     return NAF_OK;
 }
 
@@ -693,8 +763,11 @@ static int ch_raise_lds_limit() {
     if (e != hipSuccess) return (int)e;
     if (dev < 0 || dev >= 64) return NAF_ERR_ARG;
     if (raised_dev[dev]) return NAF_OK;
-    const void* ks[4] = {(const void*)chain_env_step_kernel<true, false>, (const void*)chain_env_step_kernel<true, true, ChainRanges>,
-                         (const void*)chain_env_probe_kernel<true>, (const void*)chain_env_rollout_kernel<true>};
+    const void* ks[7] = {(const void*)chain_env_step_kernel<true, false>, (const void*)chain_env_step_kernel<true, true, ChainRanges>,
+                         (const void*)chain_env_probe_kernel<true>, (const void*)chain_env_rollout_kernel<true>,
+                         (const void*)chain_env_step_kernel<true, false, ChainCell>,
+                         (const void*)chain_env_step_kernel<true, true, ChainRanges, ChainCell>,
+                         (const void*)chain_env_rollout_kernel<true, ChainCell>};
     for (const void* k : ks) {
         e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, CH_MAX_DYN_LDS);
         if (e != hipSuccess) return (int)e;
@@ -714,6 +787,7 @@ extern "C" int naf_chain_env_create(const float* model_host, int n_floats, naf_c
     h->A = (int)model_host[1];
     h->n_seg = (int)model_host[2];
     h->n_pairs = (int)model_host[9];
+    h->n_cell = (int)model_host[10] + (int)model_host[11];
     h->lanes = 64;
     h->waves = 1;
     if (h->n_pairs > 0) {
@@ -795,7 +869,29 @@ extern "C" int naf_chain_env_step(naf_chain_env_t* h, float* env_state, const fl
     const int A = h->A;
     const int rf = naf_replay_row_floats(2 * A + 9, A);
     if (rf <= 0) return NAF_ERR_ARG;
-    if (h->scene_on) {
+    if (h->n_cell > 0) {      // the workcell's instantiations, launched as their CELL-less counterparts below are
+        if (h->scene_on && !h->scene_ready) return NAF_ERR_STATE;
+        const int waves = h->scene_on ? std::min(h->waves, CH_SCENE_WAVES) : h->waves;
+        const dim3 grid_sc((E + h->lanes - 1) / h->lanes), grid((E + 63) / 64);
+        const size_t lds = ch_lds_bytes(h->n_seg, h->lanes, waves);
+        hipStream_t s = (hipStream_t)stream;
+        if (h->scene_on && h->n_pairs > 0)
+            chain_env_step_kernel<true, true, ChainRanges, ChainCell><<<grid_sc, 64 * waves, lds, s>>>(
+                h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
+                record_slots, h->n_pairs, h->lanes, ch_ranges(h), ChainCell{});
+        else if (h->scene_on)
+            chain_env_step_kernel<false, true, ChainRanges, ChainCell><<<grid, 64, 0, s>>>(
+                h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
+                record_slots, 0, 64, ch_ranges(h), ChainCell{});
+        else if (h->n_pairs > 0)
+            chain_env_step_kernel<true, false, ChainCell><<<grid_sc, 64 * waves, lds, s>>>(
+                h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
+                record_slots, h->n_pairs, h->lanes, ChainCell{});
+        else
+            chain_env_step_kernel<false, false, ChainCell><<<grid, 64, 0, s>>>(
+                h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
+                record_slots, 0, 64, ChainCell{});
+    } else if (h->scene_on) {
         if (!h->scene_ready) return NAF_ERR_STATE;
         const int waves = std::min(h->waves, CH_SCENE_WAVES);
         if (h->n_pairs > 0)
@@ -832,6 +928,14 @@ extern "C" int naf_chain_env_probe(naf_chain_env_t* h, const float* env_state, f
     return NAF_OK;
 }
 
+extern "C" int naf_chain_env_probe_cell(naf_chain_env_t* h, const float* env_state, float* out, int E, void* stream) {
+    if (!h || !env_state || !out || E <= 0) return NAF_ERR_ARG;
+    if (h->n_cell == 0) return NAF_ERR_STATE;
+    chain_env_probe_cell_kernel<<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(h->model_dev, env_state, out, E, h->A, h->n_seg);
+    NAF_CHECK_LAUNCH();
+    return NAF_OK;
+}
+
 extern "C" int naf_chain_env_reset_given(naf_chain_env_t* h, float* env_state, float* obs, int E, const float* q0_dev,
                                          const float* scene_dev, float obstacle_radius, void* stream) {
     if (!h || !env_state || !obs || !q0_dev || !scene_dev || E <= 0 || !(obstacle_radius >= 0.f)) return NAF_ERR_ARG;
@@ -844,7 +948,16 @@ extern "C" int naf_chain_env_reset_given(naf_chain_env_t* h, float* env_state, f
 extern "C" int naf_chain_env_rollout_step(naf_chain_env_t* h, float* env_state, const float* actions, float* obs_next, float* outcome,
                                           float* traj, int E, int max_frames, void* stream) {
     if (!h || !env_state || !actions || !obs_next || !outcome || E <= 0 || max_frames < 1) return NAF_ERR_ARG;
-    if (h->n_pairs > 0)
+    if (h->n_cell > 0 && h->n_pairs > 0)
+        chain_env_rollout_kernel<true, ChainCell><<<(E + h->lanes - 1) / h->lanes, 64 * h->waves, ch_lds_bytes(h->n_seg, h->lanes, h->waves),
+                                               (hipStream_t)stream>>>(h->model_dev, env_state, actions, obs_next, outcome, traj, E,
+                                                                      h->A, h->n_seg, max_frames, h->n_pairs, h->lanes,
+                                                                      ChainCell{});
+    else if (h->n_cell > 0)
+        chain_env_rollout_kernel<false, ChainCell><<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(h->model_dev, env_state, actions, obs_next,
+                                                                                             outcome, traj, E, h->A, h->n_seg, max_frames,
+                                                                                             0, 64, ChainCell{});
+    else if (h->n_pairs > 0)
         chain_env_rollout_kernel<true><<<(E + h->lanes - 1) / h->lanes, 64 * h->waves, ch_lds_bytes(h->n_seg, h->lanes, h->waves),
                                          (hipStream_t)stream>>>(h->model_dev, env_state, actions, obs_next, outcome, traj, E, h->A,
                                                                 h->n_seg, max_frames, h->n_pairs, h->lanes);

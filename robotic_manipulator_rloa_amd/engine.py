@@ -996,13 +996,13 @@ class DeviceEnvLoop:
         return out
 
 
-OUTCOME_NAMES = np.array(["frames", "reached", "obstacle", "self"])      # by naf_chain_env_rollout_step's outcome code
+OUTCOME_NAMES = np.array(["frames", "reached", "obstacle", "self", "workcell"])      # by naf_chain_env_rollout_step's outcome code
 
 
 @dataclass
 class ReachResult:
     """What N rollouts to given targets came to, arrays over the queries (ManipulatorFramework.reach_targets)."""
-    outcome: np.ndarray                        # [N] str: 'reached' | 'obstacle' | 'self' | 'frames' (the frame budget was used up)
+    outcome: np.ndarray                        # [N] str: 'reached' | 'obstacle' | 'self' | 'workcell' | 'frames' (the budget was used up)
     frames: np.ndarray                         # [N] int64: steps taken
     final_distance: np.ndarray                 # [N] float32: |end effector - target| after the last step
     min_clearance: np.ndarray                  # [N] float32: least distance between arm and obstacle surface over the steps
@@ -1012,6 +1012,8 @@ class ReachResult:
     start_distance: np.ndarray                 # [N] float32: the same three measures at the start pose, before any step
     start_clearance: np.ndarray
     start_self_clearance: np.ndarray
+    min_cell_clearance: np.ndarray             # [N] float32: least workcell clearance over the steps, +inf without a workcell
+    start_cell_clearance: np.ndarray           # [N] float32: the workcell clearance at the start pose, +inf without a workcell
 
 
 class DeviceRollout:
@@ -1038,6 +1040,8 @@ class DeviceRollout:
         self.env_state = torch.zeros(self.E, self.lib.naf_chain_env_state_floats(self._chain_env), **f32)
         self.outcome = torch.zeros(self.E, 8, **f32)
         self.start = torch.zeros(self.E, 5, **f32)           # naf_chain_env_probe behind the reset
+        self.has_cell = bool(chain.cell_spheres or chain.cell_planes)
+        self.start_cell = torch.full((self.E,), float("inf"), **f32)      # naf_chain_env_probe_cell, when the model has a workcell
         self.q0 = torch.zeros(self.E, lay.A, **f32)
         self.scene = torch.zeros(self.E, 6, **f32)
         self.traj: Optional[torch.Tensor] = None             # [frames + 1][E][A], kept once a run has recorded trajectories
@@ -1088,6 +1092,7 @@ class DeviceRollout:
         self._prepare(frames, float(noise_scale), trajectories)
         self.actor.counter.zero_()                 # a run is a function of its arguments and the policy
         outcome, start = np.empty((N, 8), np.float32), np.empty((N, 5), np.float32)
+        start_cell = np.full(N, np.inf, np.float32)
         paths = np.empty((N, frames + 1, A), np.float32) if trajectories else None
         for first, n, pad in self.chunks(N, E):
             idx = np.concatenate([np.arange(first, first + n), np.full(pad, first + n - 1, np.int64)])
@@ -1097,6 +1102,9 @@ class DeviceRollout:
             check(self.lib.naf_chain_env_reset_given(self._chain_env, ptr(self.env_state), ptr(self.actor.obs), E, ptr(self.q0),
                                                      ptr(self.scene), self.obstacle_radius, st), "chain_env_reset_given")
             check(self.lib.naf_chain_env_probe(self._chain_env, ptr(self.env_state), ptr(self.start), E, st), "chain_env_probe")
+            if self.has_cell:
+                check(self.lib.naf_chain_env_probe_cell(self._chain_env, ptr(self.env_state), ptr(self.start_cell), E, st),
+                      "chain_env_probe_cell")
             if trajectories:
                 self.traj[0].copy_(self.env_state[:, :A])          # frame 0: the start pose as the reset clamped it
             for _ in range(frames):
@@ -1106,6 +1114,7 @@ class DeviceRollout:
                     self._body()
             outcome[first:first + n] = self.outcome.cpu().numpy()[:n]
             start[first:first + n] = self.start.cpu().numpy()[:n]
+            start_cell[first:first + n] = self.start_cell.cpu().numpy()[:n]
             if paths is not None:
                 # a held env wrote nothing beyond its last frame: those repeat its final pose
                 tr = self.traj.cpu().numpy()[:, :n]
@@ -1114,4 +1123,4 @@ class DeviceRollout:
         target_start = np.linalg.norm(start[:, :3].astype(np.float64) - scenes[:, :3], axis=1).astype(np.float32)
         return ReachResult(OUTCOME_NAMES[outcome[:, 0].astype(np.int64)], outcome[:, 1].astype(np.int64), outcome[:, 2].copy(),
                            outcome[:, 3].copy(), outcome[:, 4].copy(), outcome[:, 5].copy(), paths, target_start, start[:, 3].copy(),
-                           start[:, 4].copy())
+                           start[:, 4].copy(), outcome[:, 6].copy() if self.has_cell else np.full(N, np.inf, np.float32), start_cell)

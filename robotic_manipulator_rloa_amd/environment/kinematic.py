@@ -8,8 +8,9 @@ error shows as a disagreement with the kernel. Kinematic: the commanded velocity
 reference's rule (environment.py:311-343, :394-412) between the capsules of model.self_pairs, when the model was compiled with it.
   state  = [pos(A), vel(A), end-effector xyz, target xyz, obstacle xyz], slot k of pos / vel reporting joint INDEX k
            (environment.py:442-451)
-  reward = +250 reached (dist < 0.05) | -1000 obstacle contact or self-contact | -(dist - 0.05), done on any of the three
-           (environment.py:311-371, :416-429)
+  reward = +250 reached (dist < 0.05) | -1000 obstacle contact, self-contact or workcell contact | -(dist - 0.05), done on any
+           of them (environment.py:311-371, :416-429). The workcell — fixed spheres and half-spaces, environment/urdf_chain.py —
+           is the model's, and has no slot in the state.
 With target_range / obstacle_range every episode gets a scene of its own: choose_scene below is the rule's float64 statement
 (include/naf_hip.h, "Scene ranges", is the kernel's).
 """
@@ -100,7 +101,7 @@ def _half_widths(v) -> np.ndarray:
     return out
 
 
-OUTCOMES = ("frames", "reached", "obstacle", "self")      # by outcome code: naf_chain_env_rollout_step's outcome[0]
+OUTCOMES = ("frames", "reached", "obstacle", "self", "workcell")      # by outcome code: naf_chain_env_rollout_step's outcome[0]
 
 
 class Trace(NamedTuple):
@@ -113,6 +114,8 @@ class Trace(NamedTuple):
     score: np.ndarray                 # sum of the rewards, in step order
     joint_positions: np.ndarray       # [..., frames + 1, A]: the path; a finished query repeats its final pose
     margins: np.ndarray               # [..., frames, 3]: distance - 0.05 | clearance - obstacle radius | self-clearance; NaN: no step
+    min_cell_clearance: np.ndarray    # min over the steps of the workcell clearance, +inf without a workcell
+    cell_margins: np.ndarray          # [..., frames]: the workcell clearance; NaN: no step
 
 
 class KinematicEnvironment:
@@ -144,6 +147,7 @@ class KinematicEnvironment:
         self.last_distance = float("nan")                     # |ee - target| of the last step
         self.last_clearance = float("nan")                    # min over segments of (distance to the obstacle centre - radius)
         self.last_self_clearance = float("nan")               # min over model.self_pairs of the pair clearance (+inf without pairs)
+        self.last_cell_clearance = float("nan")               # min over model.cell_pairs of the workcell clearance (+inf without)
 
     @property
     def observation_space(self) -> np.ndarray:
@@ -202,6 +206,30 @@ class KinematicEnvironment:
             return np.full(lead, np.inf) if lead else float("inf")
         return np.min(self.pair_clearances(q), axis=0)
 
+    def cell_clearances(self, q: Optional[np.ndarray] = None) -> np.ndarray:
+        """[pairs, ...]: clearance of every (segment, geometry) pair of model.cell_pairs — distance(segment, centre) - radius -
+        sphere radius, or min(n.a, n.b) - d - radius against a half-space; contact iff < 0."""
+        segs = self.world_segments(q)
+        lead = np.shape(segs[0][0])[:-1]
+        pairs, G = self.model.cell_pairs, len(self.model.cell_spheres)
+        out = np.empty((len(pairs),) + lead)
+        for k, (s, g) in enumerate(pairs):
+            a, b, r = segs[s]
+            if g < G:
+                c = np.array(self.model.cell_spheres[g])
+                out[k] = np.sqrt(segment_point_distance2(a, b, c[:3])) - r - c[3]
+            else:
+                n = np.array(self.model.cell_planes[g - G])
+                out[k] = np.minimum(a @ n[:3], b @ n[:3]) - n[3] - r
+        return out
+
+    def cell_clearance(self, q: Optional[np.ndarray] = None):
+        """min over model.cell_pairs of the pair's clearance, +inf without a workcell; workcell contact iff < 0."""
+        lead = np.shape(self.q if q is None else q)[:-1]
+        if not self.model.cell_pairs:
+            return np.full(lead, np.inf) if lead else float("inf")
+        return np.min(self.cell_clearances(q), axis=0)
+
     def get_state(self) -> np.ndarray:
         A = self.n
         out = np.empty(2 * A + 9)
@@ -251,9 +279,12 @@ class KinematicEnvironment:
         dist = float(np.linalg.norm(state[2 * A:2 * A + 3] - self.target_pos))
         clear = float(self.clearance())
         self_clear = float(self.self_clearance())
+        cell_clear = float(self.cell_clearance())
         self.last_distance, self.last_clearance, self.last_self_clearance = dist, clear, self_clear
+        self.last_cell_clearance = cell_clear
         reached = dist < TARGET_THRESHOLD
-        hit = clear < self.obstacle_radius or self_clear < 0.0        # environment.py:311-343: either collision ends the episode
+        # environment.py:311-343: either collision ends the episode; so does contact with the workcell
+        hit = clear < self.obstacle_radius or self_clear < 0.0 or cell_clear < 0.0
         reward = 250 if reached else (-1000 if hit else -1 * (dist - TARGET_THRESHOLD))
         return state, reward, 1 if (reached or hit) else 0
 
@@ -261,7 +292,7 @@ class KinematicEnvironment:
     def trace(self, q0, actions, target, obstacle, frames: int) -> Trace:
         """The rollout rule of naf_chain_env_rollout_step in float64: from the joint values q0[..., A] (clamped into the limits),
         step t applies actions[..., t, A] under step()'s rule in the scene target[..., 3] / obstacle[..., 3], until the query
-        reaches the target, touches the obstacle or itself, or has taken `frames` steps; from then on it is held. Pure: neither
+        reaches the target, touches the obstacle, itself or the workcell, or has taken `frames` steps; from then on it is held. Pure: neither
         self.q, the episode's scene nor any RNG is touched."""
         q = np.array(q0, float)
         lead = q.shape[:-1]
@@ -275,7 +306,8 @@ class KinematicEnvironment:
         code, steps = np.zeros(lead, np.int64), np.zeros(lead, np.int64)
         live = np.ones(lead, bool)
         dist, score = np.full(lead, np.nan), np.zeros(lead)
-        min_clear, min_self = np.full(lead, np.inf), np.full(lead, np.inf)
+        min_clear, min_self, min_cell = np.full(lead, np.inf), np.full(lead, np.inf), np.full(lead, np.inf)
+        cell_margins = np.full(lead + (frames,), np.nan)
         path = np.empty(lead + (frames + 1, A))
         margins = np.full(lead + (frames, 3), np.nan)
         path[..., 0, :] = q
@@ -287,17 +319,30 @@ class KinematicEnvironment:
             d = np.array([np.linalg.norm(v) for v in d]).reshape(lead)
             clear = self.clearance(q, obstacle) - self.obstacle_radius
             self_clear = self.self_clearance(q) + np.zeros(lead)
-            reached, hit, self_hit = d < TARGET_THRESHOLD, clear < 0.0, self_clear < 0.0
-            reward = np.where(reached, 250.0, np.where(hit | self_hit, -1000.0, -1 * (d - TARGET_THRESHOLD)))
+            cell_clear = self.cell_clearance(q) + np.zeros(lead)
+            reached, hit, self_hit, cell_hit = d < TARGET_THRESHOLD, clear < 0.0, self_clear < 0.0, cell_clear < 0.0
+            reward = np.where(reached, 250.0, np.where(hit | self_hit | cell_hit, -1000.0, -1 * (d - TARGET_THRESHOLD)))
+            cell_margins[..., t] = np.where(live, cell_clear, np.nan)
             margins[..., t, :] = np.where(live[..., None], np.stack([d - TARGET_THRESHOLD, clear, self_clear], axis=-1), np.nan)
             dist = np.where(live, d, dist)
             score = np.where(live, score + reward, score)
             min_clear = np.where(live, np.minimum(min_clear, clear), min_clear)
             min_self = np.where(live, np.minimum(min_self, self_clear), min_self)
+            min_cell = np.where(live, np.minimum(min_cell, cell_clear), min_cell)
             steps = steps + live
-            code = np.where(live, np.where(reached, 1, np.where(hit, 2, np.where(self_hit, 3, 0))), code)
-            live = live & ~(reached | hit | self_hit)
-        return Trace(code, steps, dist, min_clear, min_self, score, path, margins)
+            code = np.where(live, np.where(reached, 1, np.where(hit, 2, np.where(self_hit, 3, np.where(cell_hit, 4, 0)))), code)
+            live = live & ~(reached | hit | self_hit | cell_hit)
+        return Trace(code, steps, dist, min_clear, min_self, score, path, margins, min_cell, cell_margins)
+
+
+def cell_box_gaps(model: ChainModel, centre, half) -> np.ndarray:
+    """[G + H]: how near the box centre +- half (a point when half is 0) comes to each workcell geometry. Against a half-space
+    the box corner with the smallest n.x decides: min over the box of n.x - d = n.centre - |n|.half - d. Against a sphere: the
+    distance from its centre to the box (0 inside) minus its radius."""
+    centre, half = np.asarray(centre, float), np.asarray(half, float)
+    out = [np.linalg.norm(np.maximum(np.abs(np.array(c[:3]) - centre) - half, 0.0)) - c[3] for c in model.cell_spheres]
+    out += [float(np.dot(n[:3], centre) - np.dot(np.abs(n[:3]), half) - n[3]) for n in model.cell_planes]
+    return np.array(out, float)
 
 
 def reach_queries(model: ChainModel, targets, obstacles, initial_joint_positions, frames, nominal_obstacle=None, nominal_start=None):
@@ -349,10 +394,11 @@ def reach_queries(model: ChainModel, targets, obstacles, initial_joint_positions
 def build_kinematic(manipulator_file, endeffector_index, fixed_joints, involved_joints, target_position, obstacle_position,
                     initial_joint_positions=None, initial_positions_variation_range=None, link_radius=0.0,
                     obstacle_radius=OBSTACLE_RADIUS, consider_autocollision=False, autocollision_ignore=None, *, target_range=None,
-                    obstacle_range=None, scene_margin=0.02) -> KinematicEnvironment:
+                    obstacle_range=None, scene_margin=0.02, floor_height=None, workcell_planes=None, workcell_spheres=None,
+                    cell_ignore=None) -> KinematicEnvironment:
     """Picklable factory (HostVectorEnv's worker processes call it through functools.partial)."""
     model = compile_chain(load_urdf(manipulator_file), endeffector_index, involved_joints, fixed_joints,
                           initial_joint_positions, initial_positions_variation_range, link_radius, consider_autocollision,
-                          autocollision_ignore or ())
+                          autocollision_ignore or (), floor_height, workcell_planes, workcell_spheres, cell_ignore or ())
     return KinematicEnvironment(model, target_position, obstacle_position, obstacle_radius, target_range, obstacle_range,
                                 scene_margin)

@@ -13,6 +13,11 @@ the links' capsules, off by default (compile_chain(consider_autocollision=True),
              transform between the two (joint origins, constant joints), folded here.
   segments   collision capsules, each in the frame of the last driven joint above it.
   slots      observation slot k of the A position / velocity slots reports joint INDEX k (environment.py:442-444).
+  workcell   fixed geometry of the cell the arm stands in, the same in every episode: up to MAX_CELL spheres (cx, cy, cz, r) and
+             half-spaces (nx, ny, nz, d), n a unit vector, the free side n.x - d >= 0. Clearance of a capsule (world end points
+             a, b, radius rho): distance(segment ab, c) - rho - r against a sphere, min(n.a, n.b) - d - rho against a half-space;
+             contact when < 0, for the (capsule, geometry) pairs the model tests: reward -1000 and done, as obstacle contact.
+             Geometry index g counts the spheres first, then the half-spaces. Off unless compile_chain is given some.
   self pairs segment pairs (s, t), s < t, tested against each other when consider_autocollision is on: the reference tests
              link i against link j for i, j in 0 .. num_joints - 1 with |i - j| <= 1 left out, contact when the closest distance
              is below 0 (environment.py:311-343, :394-412; collision_detector.py:63-98). The root link (index -1) takes no part.
@@ -38,6 +43,8 @@ JOINT_FLOATS = 24
 SEGMENT_FLOATS = 8
 SLOT_FLOATS = 2
 PAIR_FLOATS = 2
+CELL_FLOATS = 4                  # per workcell geometry; behind them one mask float per segment
+MAX_CELL = 16                    # include/naf_hip.h NAF_CHAIN_MAX_CELL: spheres + half-spaces
 MAX_JOINTS = 64
 DT = 1.0 / 240.0                 # environment.py:481: one stepSimulation tick
 TARGET_THRESHOLD = 0.05          # environment.py:345-371
@@ -213,6 +220,10 @@ class ChainModel:
     consider_autocollision: bool = False
     self_pairs: List[tuple] = field(default_factory=list)            # (s, t), s < t: segment indices tested against each other
     self_pairs_dropped: List[tuple] = field(default_factory=list)    # (link name, link name) of the pairs the pose sample pruned
+    cell_spheres: List[tuple] = field(default_factory=list)          # (cx, cy, cz, r): geometry 0 .. G - 1
+    cell_planes: List[tuple] = field(default_factory=list)           # (nx, ny, nz, d), |n| = 1, free side n.x - d >= 0: geometry G ..
+    cell_masks: List[int] = field(default_factory=list)              # per segment: bit g set = tested against geometry g
+    cell_pairs_dropped: List[tuple] = field(default_factory=list)    # (link name, geometry index) of the pairs the pose sample pruned
     _blob: Optional[np.ndarray] = field(default=None, repr=False, compare=False)
 
     @property
@@ -228,14 +239,22 @@ class ChainModel:
         frames = [s.frame for s in self.segments]
         return [int(np.searchsorted(frames, f, side="left")) for f in range(self.A + 2)]
 
+    @property
+    def cell_pairs(self) -> List[tuple]:
+        """(segment, geometry) pairs the workcell rule tests, segment-major."""
+        return [(s, g) for s, mask in enumerate(self.cell_masks) for g in range(len(self.cell_spheres) + len(self.cell_planes))
+                if mask >> g & 1]
+
     def pack(self) -> np.ndarray:
         """The flat float32 blob csrc/chain_env.hip reads (layout: include/naf_hip.h, "chain model blob")."""
         if self._blob is not None:
             return self._blob.copy()
         A, n_seg, n_pairs = self.A, len(self.segments), len(self.self_pairs)
         head = np.zeros(HEADER_FLOATS)
+        G, H = len(self.cell_spheres), len(self.cell_planes)
         n = HEADER_FLOATS + JOINT_FLOATS * A + (A + 2) + SEGMENT_FLOATS * n_seg + SLOT_FLOATS * A + PAIR_FLOATS * n_pairs
-        head[:10] = [BLOB_VERSION, A, n_seg, A, self.ee_frame, *self.ee_point, n, n_pairs]
+        n += CELL_FLOATS * (G + H) + (n_seg if G + H else 0)          # (no workcell: the blob ends where it always did)
+        head[:12] = [BLOB_VERSION, A, n_seg, A, self.ee_frame, *self.ee_point, n, n_pairs, G, H]
         parts = [head]
         for j in self.joints:
             rec = np.zeros(JOINT_FLOATS)
@@ -249,6 +268,10 @@ class ChainModel:
             parts.append(np.array([src, const]))
         for pair in self.self_pairs:                                  # (none: the blob is byte for byte the one without the table)
             parts.append(np.array(pair, float))
+        for geom in list(self.cell_spheres) + list(self.cell_planes):
+            parts.append(np.array(geom, float))
+        if G + H:
+            parts.append(np.array(self.cell_masks, float))
         self._blob = np.concatenate(parts).astype(np.float32)
         assert self._blob.size == n
         return self._blob.copy()
@@ -264,8 +287,14 @@ def _compose(Ra, ta, Rb, tb):
 def compile_chain(urdf: Urdf, endeffector_index: int, involved_joints: Sequence[int], fixed_joints: Sequence[int] = (),
                   initial_joint_positions: Optional[Sequence[float]] = None,
                   initial_positions_variation_range: Optional[Sequence[float]] = None, link_radius: float = 0.0,
-                  consider_autocollision: bool = False, autocollision_ignore: Sequence = ()) -> ChainModel:
-    """consider_autocollision: the model carries self_pairs (module text) minus the pairs that the fixed pose sample finds in
+                  consider_autocollision: bool = False, autocollision_ignore: Sequence = (), floor_height: Optional[float] = None,
+                  workcell_planes: Optional[Sequence] = None, workcell_spheres: Optional[Sequence] = None,
+                  cell_ignore: Sequence = ()) -> ChainModel:
+    """floor_height z0 (sugar for the half-space (0, 0, 1, z0), the first one), workcell_planes [(nx, ny, nz, d)],
+    workcell_spheres [(cx, cy, cz, r)]: the workcell (module text). The model tests every (capsule, geometry) pair except those
+    the fixed pose sample finds in contact at every pose (listed in cell_pairs_dropped: the base standing on the floor) and
+    those of cell_ignore: (link, geometry index) entries, the link by name or by PyBullet link index.
+    consider_autocollision: the model carries self_pairs (module text) minus the pairs that the fixed pose sample finds in
     contact at every pose (listed in self_pairs_dropped) and minus autocollision_ignore: pairs of links, each given by name or
     by PyBullet link index, dropped by hand."""
     path, joints, nj = urdf.path, urdf.joints, len(urdf.joints)
@@ -371,7 +400,86 @@ def compile_chain(urdf: Urdf, endeffector_index: int, involved_joints: Sequence[
     if consider_autocollision:
         model.consider_autocollision = True
         _self_pairs(model, urdf, autocollision_ignore)
+    planes = ([] if floor_height is None else [(0.0, 0.0, 1.0, floor_height)]) + list(workcell_planes or ())
+    if planes or workcell_spheres or cell_ignore:
+        _workcell(model, urdf, list(workcell_spheres or ()), planes, cell_ignore)
     return model
+
+
+def _prune_poses(model: ChainModel) -> np.ndarray:
+    """The fixed pose sample [SELF_PRUNE_POSES, A]: uniform inside the limits, +-pi where there are none."""
+    rng = np.random.default_rng(SELF_PRUNE_SEED)
+    return np.stack([[rng.uniform(j.lower, j.upper) if j.limited else rng.uniform(-math.pi, math.pi) for j in model.joints]
+                     for _ in range(SELF_PRUNE_POSES)])
+
+
+def cell_geometry_name(model: ChainModel, g: int) -> str:
+    """'workcell sphere 1 (centre ..., radius ...)' / 'workcell plane 0 (normal ..., offset ...)' of geometry index g."""
+    G = len(model.cell_spheres)
+    if g < G:
+        c = model.cell_spheres[g]
+        return f"workcell sphere {g} (centre {c[0]:.4g} {c[1]:.4g} {c[2]:.4g}, radius {c[3]:.4g})"
+    n = model.cell_planes[g - G]
+    return f"workcell plane {g - G} (normal {n[0]:.4g} {n[1]:.4g} {n[2]:.4g}, offset {n[3]:.4g})"
+
+
+def _workcell(model: ChainModel, urdf: Urdf, spheres: list, planes: list, ignore: Sequence) -> None:
+    """Fills model.cell_spheres / cell_planes / cell_masks / cell_pairs_dropped: the geometry checked, every pair, the hand-made
+    exceptions, then the pruning. A geometry that is left with no tested pair is refused."""
+    path, segs = urdf.path, model.segments
+
+    def numbers(v, what):
+        try:
+            out = tuple(float(x) for x in v)
+        except (TypeError, ValueError):
+            out = ()
+        if len(out) != 4 or not all(math.isfinite(x) for x in out):
+            raise InvalidManipulatorFile(f"{path}: {what} {v!r} is not four finite numbers")
+        return out
+
+    model.cell_spheres = [numbers(c, "workcell sphere (cx, cy, cz, r)") for c in spheres]
+    model.cell_planes = [numbers(n, "workcell plane (nx, ny, nz, d)") for n in planes]
+    G, n_geom = len(spheres), len(spheres) + len(planes)
+    if n_geom > MAX_CELL:
+        raise InvalidManipulatorFile(f"{path}: {n_geom} workcell geometries; a chain model holds at most {MAX_CELL}")
+    for g, c in enumerate(model.cell_spheres):
+        if c[3] < 0.0:
+            raise InvalidManipulatorFile(f"{path}: {cell_geometry_name(model, g)} has a negative radius")
+    for h, n in enumerate(model.cell_planes):
+        if abs(math.sqrt(n[0] ** 2 + n[1] ** 2 + n[2] ** 2) - 1.0) > 1e-6:
+            raise InvalidManipulatorFile(f"{path}: {cell_geometry_name(model, G + h)}: the normal is not a unit vector")
+    link_names = {s.link_name for s in segs}
+    link_of_index = {s.link: s.link_name for s in segs}
+    ignored = set()
+    for entry in ignore or ():
+        if isinstance(entry, str) or len(entry) != 2:
+            raise InvalidManipulatorFile(f"{path}: cell_ignore holds {entry!r}; each entry is (link, geometry index)")
+        link, g = entry
+        if not isinstance(link, str):
+            if isinstance(link, bool) or not isinstance(link, (int, np.integer)) or int(link) not in link_of_index:
+                raise InvalidManipulatorFile(f"{path}: cell_ignore names link index {link!r}, which carries no capsule")
+            link = link_of_index[int(link)]
+        if link not in link_names:
+            raise InvalidManipulatorFile(f"{path}: cell_ignore names the link {link!r}, which carries no capsule")
+        if isinstance(g, bool) or not isinstance(g, (int, np.integer)) or not 0 <= int(g) < n_geom:
+            raise InvalidManipulatorFile(f"{path}: cell_ignore names workcell geometry {g!r}; the workcell has geometries 0 .. "
+                                         f"{n_geom - 1} (spheres first)")
+        ignored.add((link, int(g)))
+    model.cell_masks = [sum(1 << g for g in range(n_geom) if (s.link_name, g) not in ignored) for s in segs]
+    pairs = model.cell_pairs
+    if pairs:
+        from .kinematic import KinematicEnvironment                 # (the twin imports this module: resolved at call time)
+        always = np.all(KinematicEnvironment(model, (0, 0, 0), (0, 0, 0)).cell_clearances(_prune_poses(model)) < 0.0, axis=1)
+        for (s, g), drop in zip(pairs, always):
+            if drop:
+                model.cell_masks[s] &= ~(1 << g)
+                if (segs[s].link_name, g) not in model.cell_pairs_dropped:
+                    model.cell_pairs_dropped.append((segs[s].link_name, g))
+    for g in range(n_geom):
+        if not any(mask >> g & 1 for mask in model.cell_masks):
+            raise InvalidManipulatorFile(
+                f"{path}: {cell_geometry_name(model, g)} is left with no capsule to test: every capsule is in contact with it at "
+                f"every one of {SELF_PRUNE_POSES} sampled poses, or dropped by cell_ignore. The geometry cuts through the arm: move it")
 
 
 def _self_pairs(model: ChainModel, urdf: Urdf, ignore: Sequence) -> None:
@@ -401,9 +509,7 @@ def _self_pairs(model: ChainModel, urdf: Urdf, ignore: Sequence) -> None:
              and frozenset((segs[s].link, segs[t].link)) not in ignored]
     if pairs:
         from .kinematic import KinematicEnvironment                 # (the twin imports this module: resolved at call time)
-        rng = np.random.default_rng(SELF_PRUNE_SEED)
-        q = np.stack([[rng.uniform(j.lower, j.upper) if j.limited else rng.uniform(-math.pi, math.pi) for j in model.joints]
-                      for _ in range(SELF_PRUNE_POSES)])
+        q = _prune_poses(model)
         model.self_pairs = pairs
         always = np.all(KinematicEnvironment(model, (0, 0, 0), (0, 0, 0)).pair_clearances(q) < 0.0, axis=1)
         model.self_pairs = [p for p, drop in zip(pairs, always) if not drop]

@@ -30,9 +30,10 @@ from typing import List, Optional, Union
 import numpy as np
 import torch
 
-from .environment.kinematic import SCENE_CONDITIONS, KinematicEnvironment, build_kinematic, choose_scene, reach_queries
+from .environment.kinematic import (SCENE_CONDITIONS, KinematicEnvironment, build_kinematic, cell_box_gaps, choose_scene,
+                                    reach_queries)
 from .environment.synthetic import SyntheticEnvironment
-from .environment.urdf_chain import SCENE_TRIES
+from .environment.urdf_chain import SCENE_TRIES, TARGET_THRESHOLD, cell_geometry_name
 from .naf_components.naf_algorithm import NAFAgent
 from .presets import ROBOT_PRESETS, pybullet_arguments, synthetic_initial_joints
 from .utils.exceptions import (ConfigurationIncomplete, EnvironmentNotInitialized, InvalidEnvironmentParameter, InvalidHyperParameter,
@@ -260,7 +261,7 @@ class ManipulatorFramework:
                       n_envs: Optional[int] = None, trajectories: bool = True):
         """Roll the trained policy out to GIVEN targets (kinematic environment only; on the device, thousands at once): query i
         starts at initial_joint_positions[i], with target targets[i] and obstacle obstacles[i], and runs until it reaches the
-        target, touches the obstacle or itself, or has taken `frames` steps. A query whose start pose is already in contact or at
+        target, touches the obstacle, itself or the workcell, or has taken `frames` steps. A query whose start pose is already in contact or at
         the target is not refused: its first step ends it (see start_* below).
           targets                 : [N][3], or [3] for a single query
           obstacles               : [N][3], [3] for all queries, or None: the environment's nominal obstacle
@@ -268,10 +269,11 @@ class ManipulatorFramework:
                                     value per involved joint, in the order of involved_joints
           noise_scale             : 0 (default): the deterministic plan; 1: the exploration noise every act() of training has
           n_envs                  : envs per chunk of queries on the device (None: all queries at once, at most 4096)
-        Returns an engine.ReachResult of numpy arrays over the queries: outcome ('reached' | 'obstacle' | 'self' | 'frames'),
-        frames, final_distance, min_clearance, min_self_clearance, score, joint_positions [N][frames + 1][A] (None with
-        trajectories=False; a finished query repeats its final pose) and start_distance / start_clearance / start_self_clearance,
-        the three measures at the start pose. The agent is only read: training can go on afterwards."""
+        Returns an engine.ReachResult of numpy arrays over the queries: outcome ('reached' | 'obstacle' | 'self' | 'workcell' |
+        'frames'), frames, final_distance, min_clearance, min_self_clearance, min_cell_clearance, score, joint_positions
+        [N][frames + 1][A] (None with trajectories=False; a finished query repeats its final pose) and start_distance /
+        start_clearance / start_self_clearance / start_cell_clearance, the measures at the start pose (the workcell's are +inf
+        without a workcell). The agent is only read: training can go on afterwards."""
         if not self.env:
             raise EnvironmentNotInitialized
         if not self.naf_agent:
@@ -340,7 +342,9 @@ class ManipulatorFramework:
                                          obstacle_radius: float = 0.06, obstacle_jitter: float = 0.0, max_force: float = 200.,
                                          visualize: bool = False, consider_autocollision: bool = False,
                                          autocollision_ignore: Optional[list] = None, target_range: Optional[List[float]] = None,
-                                         obstacle_range: Optional[List[float]] = None, scene_margin: float = 0.02) -> None:
+                                         obstacle_range: Optional[List[float]] = None, scene_margin: float = 0.02,
+                                         floor_height: Optional[float] = None, workcell_planes: Optional[list] = None,
+                                         workcell_spheres: Optional[list] = None, cell_ignore: Optional[list] = None) -> None:
         """initialize_environment()'s arguments (rl_framework.py:369-417) for the built-in kinematic environment: the arm of
         `manipulator_file` (a URDF) as a serial chain under the reference's environment rule, velocity control applied exactly.
         Not a Bullet port — no dynamics (max_force is accepted and ignored), no mesh collision (links are capsules of their
@@ -355,7 +359,16 @@ class ManipulatorFramework:
         candidates are drawn and the first one is taken whose target is farther than 0.05 + scene_margin from the start pose's
         end effector, whose obstacle is scene_margin clear of the arm at the start pose and whose target is not inside the
         obstacle; if none is, the episode runs in the nominal scene. Ranges that put the scene on the arm — more than half of
-        1024 sampled episode starts falling back — are refused here. Not together with obstacle_jitter."""
+        1024 sampled episode starts falling back — are refused here. Not together with obstacle_jitter.
+        floor_height / workcell_planes / workcell_spheres: the fixed geometry of the cell the arm stands in — a floor z >= z0,
+        half-spaces (nx, ny, nz, d) with a unit normal and the free side n.x - d >= 0, spheres (cx, cy, cz, r), 16 in all. A
+        capsule that touches one ends the episode with -1000, as obstacle contact does; the geometry is the same in every
+        episode and is not part of the state. (Capsule, geometry) pairs in contact at every pose — the base on the floor — are
+        dropped when the model is compiled (env.model.cell_pairs_dropped), cell_ignore [(link, geometry index)] drops more;
+        geometry indices count the spheres first, then the floor, then workcell_planes. Refused here: a start pose in
+        workcell contact, a target (or, with target_range, a point of its box) within 0.05 (+ scene_margin) of a geometry,
+        and initial_positions_variation_range under which more than half of 1024 sampled episode starts are in workcell
+        contact. PyBullet and the stand-in environment have no workcell."""
         if visualize:
             raise InvalidManipulatorFile('the kinematic environment has no visualisation: pass visualize=False '
                                          '(initialize_environment() opens the PyBullet GUI)')
@@ -377,10 +390,25 @@ class ManipulatorFramework:
                 None if initial_positions_variation_range is None else list(initial_positions_variation_range),
                 float(link_radius), float(obstacle_radius), bool(consider_autocollision),
                 None if autocollision_ignore is None else [tuple(p) for p in autocollision_ignore])
+        if floor_height is not None and (isinstance(floor_height, bool) or not isinstance(floor_height, (int, float))
+                                         or not np.isfinite(floor_height)):
+            raise InvalidEnvironmentParameter('Floor height received is not a finite number')
+        for label, geoms in (('Workcell planes', workcell_planes), ('Workcell spheres', workcell_spheres)):
+            if geoms is None:
+                continue
+            if not isinstance(geoms, (list, tuple)) or not all(isinstance(g, (list, tuple)) and len(g) == 4 for g in geoms):
+                raise InvalidEnvironmentParameter(f'{label} received is not a list of four-number entries')
+            if not all(isinstance(v, (int, float)) and not isinstance(v, bool) and np.isfinite(v) for g in geoms for v in g):
+                raise InvalidEnvironmentParameter(f'An item inside the {label} list is not a finite number')
         scene_kw = dict(target_range=None if target_range is None else [float(v) for v in target_range],
                         obstacle_range=None if obstacle_range is None else [float(v) for v in obstacle_range],
-                        scene_margin=float(scene_margin))
+                        scene_margin=float(scene_margin), floor_height=None if floor_height is None else float(floor_height),
+                        workcell_planes=None if workcell_planes is None else [tuple(float(v) for v in g) for g in workcell_planes],
+                        workcell_spheres=None if workcell_spheres is None else [tuple(float(v) for v in g) for g in workcell_spheres],
+                        cell_ignore=None if cell_ignore is None else [tuple(p) for p in cell_ignore])
         env = build_kinematic(*args, **scene_kw)
+        if env.model.cell_pairs:
+            self._check_workcell(env, manipulator_file)
         if ranged:
             self._check_scene_ranges(env, manipulator_file)
         if env.model.self_pairs:
@@ -397,6 +425,40 @@ class ManipulatorFramework:
         self._env_factory = functools.partial(build_kinematic, *args, **scene_kw)
         logger.info(f'Kinematic Environment successfully initialized from {manipulator_file} '
                     f'({self.env.model.A} driven joints, {len(self.env.model.segments)} collision capsules)')
+
+    @staticmethod
+    def _check_workcell(env: KinematicEnvironment, manipulator_file: str) -> None:
+        """Refuses a nominal start pose in workcell contact, a target (box) too near a geometry and start ranges under which more
+        than half of SCENE_CHECK_CASES sampled episode starts are in workcell contact; logs that share otherwise."""
+        model = env.model
+        pairs = model.cell_pairs
+        clear = env.cell_clearances(env.initial_joint_positions)
+        worst = int(np.argmin(clear))
+        if clear[worst] < 0.0:
+            s, g = pairs[worst]
+            raise ValueError(f'{manipulator_file}: at the initial joint positions the link {model.segments[s].link_name!r} is in '
+                             f'contact with {cell_geometry_name(model, g)} (clearance {clear[worst]:.4f} m): every episode would '
+                             f'end at its first step. Choose another start pose, move the geometry, or pass '
+                             f'cell_ignore=[({model.segments[s].link_name!r}, {g})]')
+        need = TARGET_THRESHOLD + (env.scene_margin if env.scene_ranges_on else 0.0)
+        gaps = cell_box_gaps(model, env.target_centre, env.target_range)
+        g = int(np.argmin(gaps))
+        if gaps[g] < need:
+            what = (f'the target box (target_position +- target_range) comes within {gaps[g]:.4f} m' if env.scene_ranges_on
+                    else f'the target lies within {gaps[g]:.4f} m')
+            raise ValueError(f'{manipulator_file}: {what} of {cell_geometry_name(model, g)}; a target needs {need:.4f} m (the 0.05 of '
+                             f'the reward rule' + (' + scene_margin' if env.scene_ranges_on else '') + ') so that the arm can '
+                             f'reach it without touching the workcell')
+        rng = np.random.default_rng(SCENE_CHECK_SEED)
+        init, var = np.array([j.init for j in model.joints]), np.array([j.variation for j in model.joints])
+        touching = int(np.sum(env.cell_clearance(init + rng.uniform(-1.0, 1.0, (SCENE_CHECK_CASES, len(init))) * var) < 0.0))
+        if touching > SCENE_CHECK_CASES // 2:
+            raise ValueError(f'{manipulator_file}: {touching} of {SCENE_CHECK_CASES} sampled episode starts (initial joint positions '
+                             f'+- initial_positions_variation_range) are in workcell contact and would end at their first step: '
+                             f'narrow the variation range, choose another start pose or move the geometry')
+        logger.info(f'Workcell: {len(model.cell_spheres)} spheres, {len(model.cell_planes)} half-spaces, {len(pairs)} tested pairs; '
+                    f'{100.0 * touching / SCENE_CHECK_CASES:.1f}% of {SCENE_CHECK_CASES} sampled episode starts are in workcell '
+                    f'contact')
 
     @staticmethod
     def _check_scene_ranges(env: KinematicEnvironment, manipulator_file: str) -> None:
