@@ -25,6 +25,17 @@ count, a launch loop of the two step kernels for `rocprofv3 --kernel-trace --sta
 workcell instantiations. In a rollout an env that touches one of them is held from then on: `envs_held_before_the_window_ended`
 says how many did.
 
+  python benchmarks/chain_env_bench.py gather [--hindsight 0.8] [--horizon 400] [--launches 200]
+      microseconds per launch of the replay gather at n = 64 x 256 rows of the S = 23 / A = 7 arm (--urdf), between device events
+      around every single launch (median and minimum of `--launches` launches after 20 unmeasured ones), on a ring that
+      DeviceEnvLoop(tag_rows=True) filled with `--steps` vector steps of E = `--envs` envs under the untrained policy: the plain
+      gather (naf_replay_gather_rows) and the hindsight gather at the given ratio and horizon, interleaved, on the same indices;
+      and the hindsight kernel's registers and scratch as the compiler reported them.
+
+`--hindsight R` (rate): the chain runs relabel a share R of every minibatch (NAFAgent.run_vectorized(hindsight=R)). Such a run
+wants an empty ring, so with the flag — also `--hindsight 0`, the figure to compare with — the warm-up steps run on an agent of
+their own and the timed run starts on a fresh one (its graph captures are inside the timed window, in both).
+
 `--target-range X Y Z` / `--obstacle-range X Y Z` (rate, step): half-widths of the boxes every episode draws its target / obstacle
 from (include/naf_hip.h, "Scene ranges"); step then also prints how the episode starts of the run chose their scenes.
 """
@@ -50,9 +61,15 @@ def rate(a):
 
     def run(tag, env, A, **kw):
         agent = NAFAgent(env, 2 * A + 9, A, 256, a.batch, 1_000_000, 1e-3, 1e-3, 0.99, 1, 1, 10 ** 9, dev, 0)
-        agent.run_vectorized(a.warmup, n_envs=a.envs, max_frames=400, **kw)
+        if a.hindsight is not None and "chain" in kw:
+            kw = dict(kw, hindsight=a.hindsight, hindsight_horizon=a.horizon)
+            agent.run_vectorized(a.warmup, n_envs=a.envs, max_frames=400, **kw)
+            agent = NAFAgent(env, 2 * A + 9, A, 256, a.batch, 1_000_000, 1e-3, 1e-3, 0.99, 1, 1, 10 ** 9, dev, 0)
+        else:
+            agent.run_vectorized(a.warmup, n_envs=a.envs, max_frames=400, **kw)
         r = agent.run_vectorized(a.steps, n_envs=a.envs, max_frames=400, **kw)
         out[tag] = {"env_steps_per_s": round(r["env_steps_per_s"], 1), "updates": r["updates"], "seconds": round(r["seconds"], 4)}
+        out[tag].update({k: round(v, 4) for k, v in r.items() if k.startswith("hindsight")})
 
     if not a.standin_only:
         from robotic_manipulator_rloa_amd.environment.kinematic import build_kinematic
@@ -72,7 +89,8 @@ def rate(a):
     else:
         for rep in range(a.repeats):
             run(f"standin_{rep}", SyntheticEnvironment(a.joints), a.joints, robot="panda")
-    print(json.dumps({"envs": a.envs, "batch": a.batch, "steps": a.steps, "warmup": a.warmup, "joints": a.joints, **out}))
+    print(json.dumps({"envs": a.envs, "batch": a.batch, "steps": a.steps, "warmup": a.warmup, "joints": a.joints,
+                      "hindsight": a.hindsight, **out}))
 
 
 def _workcell(a) -> dict:
@@ -188,6 +206,53 @@ def rollout(a):
                       "envs_held_before_the_window_ended": held}))
 
 
+def gather(a):
+    import numpy as np
+    import torch
+    from robotic_manipulator_rloa_amd import _lib
+    from robotic_manipulator_rloa_amd.engine import DeviceEnvLoop
+    from robotic_manipulator_rloa_amd.environment.kinematic import build_kinematic
+    from robotic_manipulator_rloa_amd.naf_components.naf_algorithm import NAFAgent
+    dev = torch.device("cuda:0")
+    os.chdir(tempfile.mkdtemp())
+    n = a.joints
+    env = build_kinematic(os.path.abspath(a.urdf) if os.path.isabs(a.urdf) else os.path.join(ROOT, a.urdf), n - 1, [n], list(range(n)),
+                          [0.45, 0.3, 0.6], [0.35, 0.2, 0.45], [0.0, 0.6, 0.0, -1.2, 0.0, 0.8, 0.0][:n], [0.1] * n, 0.03)
+    U, B, E = 64, 256, a.envs
+    agent = NAFAgent(env, 2 * n + 9, n, 256, B, 1_000_000, 1e-3, 1e-3, 0.99, 1, 1, 10 ** 9, dev, 0)
+    mem = agent.memory
+    loop = DeviceEnvLoop(agent.learner, mem, E, seed=1, max_frames=400, chain=env.model, target=[0.45, 0.3, 0.6],
+                         obstacle=[0.35, 0.2, 0.45], target_range=a.target_range or [0.15, 0.15, 0.1], tag_rows=True)
+    for _ in range(a.steps):
+        loop.step()
+    idx = torch.zeros(U, B, dtype=torch.int32, device=dev)
+    mem.sample_indices(idx, U)
+    rows = torch.zeros(U * B, mem.batch_row_floats, device=dev)
+    k_out = torch.zeros(U * B, dtype=torch.int32, device=dev)
+    ratio = 0.8 if a.hindsight is None else a.hindsight
+    horizon = 400 if a.horizon is None else a.horizon
+    forms = {"plain": lambda: mem.gather_rows(idx, rows, U * B),
+             "hindsight": lambda: mem.gather_rows_hindsight(idx, rows, U * B, E, horizon, ratio, B, -U, k_out)}
+    times = {k: [] for k in forms}
+    for i in range(a.launches + 20):
+        for k, f in forms.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            f()
+            t1.record()
+            t1.synchronize()
+            if i >= 20:
+                times[k].append(1e3 * t0.elapsed_time(t1))
+    k = k_out.cpu().numpy()
+    usage = json.load(open(_lib.USAGE_PATH)) if os.path.exists(_lib.USAGE_PATH) else {}
+    regs = {name.split("kernelILi")[1].split("E")[0]: {q: v[q] for q in ("vgprs", "sgprs", "scratch_bytes_per_lane")}
+            for name, v in usage.items() if "replay_gather_rows_hindsight_kernel" in name}
+    print(json.dumps({"rows": U * B, "ring_rows": len(mem), "envs": E, "ratio": ratio, "horizon": horizon, "launches": a.launches,
+                      "us_per_launch": {k: {"median": round(float(np.median(v)), 2), "min": round(float(np.min(v)), 2)} for k, v in times.items()},
+                      "relabelled_share": round(float(np.mean(k >= 0)), 4), "no_valid_candidate_share": round(float(np.mean(k == -2)), 4),
+                      "hindsight_kernel_registers_by_width": regs}))
+
+
 def kernels(a):
     import numpy as np
     import torch
@@ -226,7 +291,7 @@ def kernels(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["rate", "kernels", "step", "rollout"])
+    ap.add_argument("what", choices=["rate", "kernels", "step", "rollout", "gather"])
     ap.add_argument("--urdf", default=os.path.join("tests", "golden", "urdf", "iiwa_like7.urdf"))
     ap.add_argument("--joints", type=int, default=7)
     ap.add_argument("--envs", type=int, default=64)
@@ -242,8 +307,10 @@ def main():
     ap.add_argument("--arm", default="", help="rate: a fixture arm of tests/golden/urdf by name, --joints its joint count")
     ap.add_argument("--target-range", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))
     ap.add_argument("--obstacle-range", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))
+    ap.add_argument("--hindsight", type=float, default=None, help="rate, gather: the share of rows replayed under a hindsight goal")
+    ap.add_argument("--horizon", type=int, default=None, help="rate, gather: hindsight_horizon (rate: max_frames; gather: 400)")
     a = ap.parse_args()
-    {"rate": rate, "kernels": kernels, "step": step, "rollout": rollout}[a.what](a)
+    {"rate": rate, "kernels": kernels, "step": step, "rollout": rollout, "gather": gather}[a.what](a)
 
 
 if __name__ == "__main__":

@@ -140,6 +140,38 @@ int naf_replay_sample_indices_big(naf_replay_t* h, uint64_t seed, const uint64_t
 int naf_replay_batch_row_floats(int S, int A);
 int naf_replay_gather_rows(naf_replay_t* h, const int32_t* idx, float* out_rows, int n, int out_ld, int action_mode,
                            void* stream);
+/* Hindsight goals (an addition within ABI 40: nothing above changes). naf_replay_gather_rows with a relabelling on the way out, for
+ * rings of the chain environment's rows (S = 2 A + 9: state = [q | qdot | end effector | target | obstacle]) that
+ * naf_chain_env_step_tagged filled E rows at a time. Output row r (minibatch u = r / rows_per_batch, row b = r % rows_per_batch,
+ * ring row at deque position i = idx[r]):
+ *   draw       Philox4x32-10, key = seed, counter = (lo, hi of *counter_dev + counter_off + u, b, 0x48494E44). The row is drawn iff
+ *              the uniform of word 0 (as every draw of this library forms it: ((x >> 8) + 0.5) / 2^24 in f32) < ratio; k0 = (uint64(word 1) * horizon) >> 32. (counter_dev may be NULL: 0.)
+ *   candidates k_j = k0 >> j, j = 0 .. ceil(log2 horizon) (the last is 0). k is valid iff tag(i) >= 1, i + k * stride < size,
+ *              tag(i + k * stride) == tag(i) and reward(i + k * stride) != -1000, tag(x) being float `tag_col` of deque row x.
+ *              The first valid candidate is taken; none valid, a row not drawn, or a bad index: the row is naf_replay_gather_rows'.
+ *   rewrite    g = end effector of next_state of row i + k * stride. The target columns of state (2A+3 .. 2A+5) and of next_state
+ *              become g bit for bit; d = |end effector of next_state of row i - g| in f32 as the step kernel forms it; reward, done
+ *              = 250, 1 if d < 0.05, else -(d - 0.05), 0. Everything else, action truncation included, is the plain gather's.
+ *   k_out      (NULL, or n int32 on the device) -1 not drawn (or bad index), -2 drawn and no candidate valid, else the k taken.
+ *   k0_out     (NULL, or n int32 on the device) the k0 drawn, -1 for a row not drawn: what a statistic of shortened looks needs.
+ * stride >= 1 (rows i and i + k * stride are the same env, k ticks apart), 1 <= horizon <= NAF_HINDSIGHT_MAX_HORIZON,
+ * 0 <= ratio <= 1, rows_per_batch >= 1, tag_col behind `done` and inside the ring's row (naf_replay_row_floats - 1 is where the
+ * tagged step writes); anything else, or a ring of another row layout: NAF_ERR_ARG. Bad indices are counted as the plain gather
+ * counts them. One launch, capturable; the descriptor is read on the host at the call. */
+#define NAF_HINDSIGHT_MAX_HORIZON 1024
+typedef struct {
+    int32_t stride, horizon;
+    float ratio;
+    int32_t rows_per_batch;
+    uint64_t seed;
+    const uint64_t* counter_dev;
+    uint64_t counter_off;
+    int32_t tag_col;
+    int32_t* k_out;
+    int32_t* k0_out;
+} naf_hindsight_t;
+int naf_replay_gather_rows_hindsight(naf_replay_t* h, const int32_t* idx, float* out_rows, int n, int out_ld, int action_mode,
+                                     const naf_hindsight_t* hd, void* stream);
 /* same, to the reference's five separate tensors (states[n,S], actions[n,A], rewards[n], next_states[n,S],
  * dones[n]) — the ReplayBuffer.sample() return contract (replay_buffer.py:67). */
 int naf_replay_gather_soa(naf_replay_t* h, const int32_t* idx, float* s, float* u, float* r, float* s2,
@@ -795,6 +827,14 @@ int naf_chain_env_reset(naf_chain_env_t* h, float* env_state, float* obs, int E,
 int naf_chain_env_step(naf_chain_env_t* h, float* env_state, const float* actions, float* out_rows, float* obs_next, int E,
                        uint64_t seed, const uint64_t* counter_dev, int max_frames, naf_episode_record_t* records,
                        int record_slots, void* stream);
+/* naf_chain_env_step with an episode tag in the row (an addition within ABI 40): float naf_replay_row_floats(2A+9, A) - 1 of every
+ * out_rows row holds the 1-based ordinal of the env's current episode (the record's `episode`), exact in a float; every other
+ * float, env_state, obs_next and the records are naf_chain_env_step's. 0, which naf_chain_env_step and every other writer of rows
+ * leave there, means "untagged". NAF_ERR_ARG for an arm whose used row fills the padded one
+ * (naf_replay_row_floats - 1 < naf_replay_batch_row_floats: A = 21 and A = 47). */
+int naf_chain_env_step_tagged(naf_chain_env_t* h, float* env_state, const float* actions, float* out_rows, float* obs_next, int E,
+                              uint64_t seed, const uint64_t* counter_dev, int max_frames, naf_episode_record_t* records,
+                              int record_slots, void* stream);
 int naf_chain_env_probe(naf_chain_env_t* h, const float* env_state, float* out, int E, void* stream);
 int naf_chain_env_set_scene_ranges(naf_chain_env_t* h, const float* ranges_host);
 int naf_chain_env_probe_cell(naf_chain_env_t* h, const float* env_state, float* out, int E, void* stream);

@@ -260,6 +260,8 @@ _PROTOS = {
     "naf_chain_env_probe_cell": [_vp, _vp, _vp, _i, _vp],
     "naf_chain_env_reset_given": [_vp, _vp, _vp, _i, _vp, _vp, _f, _vp],
     "naf_chain_env_rollout_step": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
+    "naf_replay_gather_rows_hindsight": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp],
+    "naf_chain_env_step_tagged": [_vp, _vp, _vp, _vp, _vp, _i, _u64, _vp, _i, _vp, _i, _vp],
 }
 _RESTYPES = {"naf_hip_arch": C.c_char_p}
 EXPORTED_SYMBOLS = tuple(_PROTOS)
@@ -269,6 +271,13 @@ class XgmiPushDesc(C.Structure):
     """naf_xgmi_push_t (include/naf_hip.h)"""
     _fields_ = [("peer_base", C.c_void_p * 8), ("ctrl", C.c_void_p), ("data_off", C.c_uint64), ("n_pad", C.c_uint64),
                 ("rank", C.c_int), ("world", C.c_int), ("timeout_ticks", C.c_longlong), ("host_timeouts", C.c_void_p)]
+
+
+class Hindsight(C.Structure):
+    """naf_hindsight_t (include/naf_hip.h)"""
+    _fields_ = [("stride", C.c_int32), ("horizon", C.c_int32), ("ratio", C.c_float), ("rows_per_batch", C.c_int32),
+                ("seed", C.c_uint64), ("counter_dev", C.c_void_p), ("counter_off", C.c_uint64), ("tag_col", C.c_int32),
+                ("k_out", C.c_void_p), ("k0_out", C.c_void_p)]
 
 
 class SlabSeg(C.Structure):

@@ -85,6 +85,9 @@ struct SceneCand {
 // whose kernel arguments are then exactly those of the kernels before the ranges existed.
 // a further, empty member of the pack: the launch tests the workcell (chain_env_step_kernel)
 struct ChainCell {};
+// and one more, last in the pack: the row's last float carries the 1-based ordinal of the env's current episode (hindsight
+// relabelling in the replay gather asks for it; 0, what every launch without it leaves there, means "untagged")
+struct ChainTag {};
 template <class... Rest>
 __device__ static inline const ChainRanges& scene_ranges(const ChainRanges& rg, const Rest&...) { return rg; }
 
@@ -428,6 +431,7 @@ chain_env_step_kernel(const float* __restrict__ model, float* env_state, const f
                       uint64_t seed, const uint64_t* counter_dev, int max_frames, naf_episode_record_t* __restrict__ records,
                       int record_slots, int n_pairs, int lanes, const Rg... rg) {
     constexpr bool CELL = (std::is_same_v<Rg, ChainCell> || ... || false);
+    constexpr bool TAG = (std::is_same_v<Rg, ChainTag> || ... || false);
     extern __shared__ __attribute__((aligned(16))) float ch_lds[];
     int e, lane = 0;
     bool active = true, walker = true;
@@ -486,6 +490,7 @@ chain_env_step_kernel(const float* __restrict__ model, float* env_state, const f
     for (int k = S + A + 1; k < off_s2; ++k) row[k] = 0.f;
     row[off_d] = done;
     for (int k = off_d + 1; k < row_floats; ++k) row[k] = 0.f;
+    if constexpr (TAG) row[row_floats - 1] = st[A + 8] + 1.f;      // rec.episode below; the host checked row_floats - 1 > off_d
 
     st[A + 7] += 1.f;
     double* score_p = (double*)(st + ch_off_score(A));
@@ -763,11 +768,15 @@ static int ch_raise_lds_limit() {
     if (e != hipSuccess) return (int)e;
     if (dev < 0 || dev >= 64) return NAF_ERR_ARG;
     if (raised_dev[dev]) return NAF_OK;
-    const void* ks[7] = {(const void*)chain_env_step_kernel<true, false>, (const void*)chain_env_step_kernel<true, true, ChainRanges>,
+    const void* ks[11] = {(const void*)chain_env_step_kernel<true, false>, (const void*)chain_env_step_kernel<true, true, ChainRanges>,
                          (const void*)chain_env_probe_kernel<true>, (const void*)chain_env_rollout_kernel<true>,
                          (const void*)chain_env_step_kernel<true, false, ChainCell>,
                          (const void*)chain_env_step_kernel<true, true, ChainRanges, ChainCell>,
-                         (const void*)chain_env_rollout_kernel<true, ChainCell>};
+                         (const void*)chain_env_rollout_kernel<true, ChainCell>,
+                         (const void*)chain_env_step_kernel<true, false, ChainTag>,
+                         (const void*)chain_env_step_kernel<true, true, ChainRanges, ChainTag>,
+                         (const void*)chain_env_step_kernel<true, false, ChainCell, ChainTag>,
+                         (const void*)chain_env_step_kernel<true, true, ChainRanges, ChainCell, ChainTag>};
     for (const void* k : ks) {
         e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, CH_MAX_DYN_LDS);
         if (e != hipSuccess) return (int)e;
@@ -861,9 +870,11 @@ extern "C" int naf_chain_env_reset(naf_chain_env_t* h, float* env_state, float* 
     return NAF_OK;
 }
 
-extern "C" int naf_chain_env_step(naf_chain_env_t* h, float* env_state, const float* actions, float* out_rows, float* obs_next,
-                                  int E, uint64_t seed, const uint64_t* counter_dev, int max_frames, naf_episode_record_t* records,
-                                  int record_slots, void* stream) {
+// Tag: nothing (naf_chain_env_step: the launches are the ones they always were) or one ChainTag (naf_chain_env_step_tagged)
+template <class... Tag>
+static int ch_step_launch(naf_chain_env_t* h, float* env_state, const float* actions, float* out_rows, float* obs_next,
+                          int E, uint64_t seed, const uint64_t* counter_dev, int max_frames, naf_episode_record_t* records,
+                          int record_slots, void* stream, const Tag... tag) {
     if (!h || !env_state || !actions || !out_rows || !obs_next || E <= 0) return NAF_ERR_ARG;
     if (records && (record_slots <= 0 || !counter_dev)) return NAF_ERR_ARG;
     const int A = h->A;
@@ -876,44 +887,62 @@ extern "C" int naf_chain_env_step(naf_chain_env_t* h, float* env_state, const fl
         const size_t lds = ch_lds_bytes(h->n_seg, h->lanes, waves);
         hipStream_t s = (hipStream_t)stream;
         if (h->scene_on && h->n_pairs > 0)
-            chain_env_step_kernel<true, true, ChainRanges, ChainCell><<<grid_sc, 64 * waves, lds, s>>>(
+            chain_env_step_kernel<true, true, ChainRanges, ChainCell, Tag...><<<grid_sc, 64 * waves, lds, s>>>(
                 h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
-                record_slots, h->n_pairs, h->lanes, ch_ranges(h), ChainCell{});
+                record_slots, h->n_pairs, h->lanes, ch_ranges(h), ChainCell{}, tag...);
         else if (h->scene_on)
-            chain_env_step_kernel<false, true, ChainRanges, ChainCell><<<grid, 64, 0, s>>>(
+            chain_env_step_kernel<false, true, ChainRanges, ChainCell, Tag...><<<grid, 64, 0, s>>>(
                 h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
-                record_slots, 0, 64, ch_ranges(h), ChainCell{});
+                record_slots, 0, 64, ch_ranges(h), ChainCell{}, tag...);
         else if (h->n_pairs > 0)
-            chain_env_step_kernel<true, false, ChainCell><<<grid_sc, 64 * waves, lds, s>>>(
+            chain_env_step_kernel<true, false, ChainCell, Tag...><<<grid_sc, 64 * waves, lds, s>>>(
                 h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
-                record_slots, h->n_pairs, h->lanes, ChainCell{});
+                record_slots, h->n_pairs, h->lanes, ChainCell{}, tag...);
         else
-            chain_env_step_kernel<false, false, ChainCell><<<grid, 64, 0, s>>>(
+            chain_env_step_kernel<false, false, ChainCell, Tag...><<<grid, 64, 0, s>>>(
                 h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
-                record_slots, 0, 64, ChainCell{});
+                record_slots, 0, 64, ChainCell{}, tag...);
     } else if (h->scene_on) {
         if (!h->scene_ready) return NAF_ERR_STATE;
         const int waves = std::min(h->waves, CH_SCENE_WAVES);
         if (h->n_pairs > 0)
-            chain_env_step_kernel<true, true, ChainRanges><<<(E + h->lanes - 1) / h->lanes, 64 * waves, ch_lds_bytes(h->n_seg, h->lanes, waves),
+            chain_env_step_kernel<true, true, ChainRanges, Tag...><<<(E + h->lanes - 1) / h->lanes, 64 * waves, ch_lds_bytes(h->n_seg, h->lanes, waves),
                                                 (hipStream_t)stream>>>(
                 h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
-                record_slots, h->n_pairs, h->lanes, ch_ranges(h));
+                record_slots, h->n_pairs, h->lanes, ch_ranges(h), tag...);
         else
-            chain_env_step_kernel<false, true, ChainRanges><<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(
+            chain_env_step_kernel<false, true, ChainRanges, Tag...><<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(
                 h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
-                record_slots, 0, 64, ch_ranges(h));
+                record_slots, 0, 64, ch_ranges(h), tag...);
     } else if (h->n_pairs > 0)
-        chain_env_step_kernel<true, false><<<(E + h->lanes - 1) / h->lanes, 64 * h->waves, ch_lds_bytes(h->n_seg, h->lanes, h->waves),
+        chain_env_step_kernel<true, false, Tag...><<<(E + h->lanes - 1) / h->lanes, 64 * h->waves, ch_lds_bytes(h->n_seg, h->lanes, h->waves),
                                       (hipStream_t)stream>>>(h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf,
                                                              seed, counter_dev, max_frames, records, record_slots, h->n_pairs,
-                                                             h->lanes);
+                                                             h->lanes, tag...);
     else
-        chain_env_step_kernel<false, false><<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(
+        chain_env_step_kernel<false, false, Tag...><<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(
             h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
-            record_slots, 0, 64);
+            record_slots, 0, 64, tag...);
     NAF_CHECK_LAUNCH();
     return NAF_OK;
+}
+
+extern "C" int naf_chain_env_step(naf_chain_env_t* h, float* env_state, const float* actions, float* out_rows, float* obs_next,
+                                  int E, uint64_t seed, const uint64_t* counter_dev, int max_frames, naf_episode_record_t* records,
+                                  int record_slots, void* stream) {
+    return ch_step_launch(h, env_state, actions, out_rows, obs_next, E, seed, counter_dev, max_frames, records, record_slots, stream);
+}
+
+// the same step; every row's last float (naf_replay_row_floats - 1) holds the episode ordinal its record reports
+extern "C" int naf_chain_env_step_tagged(naf_chain_env_t* h, float* env_state, const float* actions, float* out_rows,
+                                         float* obs_next, int E, uint64_t seed, const uint64_t* counter_dev, int max_frames,
+                                         naf_episode_record_t* records, int record_slots, void* stream) {
+    if (!h) return NAF_ERR_ARG;
+    const int S = 2 * h->A + 9;
+    // the tag needs a float of the padded row that the learner's minibatch row does not reach (none at A = 21 and A = 47)
+    if (naf_replay_row_floats(S, h->A) - 1 < naf_replay_batch_row_floats(S, h->A)) return NAF_ERR_ARG;
+    return ch_step_launch(h, env_state, actions, out_rows, obs_next, E, seed, counter_dev, max_frames, records, record_slots, stream,
+                          ChainTag{});
 }
 
 extern "C" int naf_chain_env_probe(naf_chain_env_t* h, const float* env_state, float* out, int E, void* stream) {

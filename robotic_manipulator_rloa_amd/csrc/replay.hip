@@ -471,6 +471,173 @@ extern "C" int naf_replay_gather_rows(naf_replay_t* h, const int32_t* idx, float
 }
 
 // ------------------------------------------------------------------------------------------------
+// gather with hindsight goals (include/naf_hip.h, "Hindsight goals"): the row gather above, one lane per output float4, with a
+// relabelling decided per ROW on the way out. Every lane of a row repeats the row's draw (one Philox block: the 13 - 16 lanes of a
+// row mostly share a wave, and a hand-over through LDS would cost a barrier) and reads the same tag / reward words, which the
+// hardware serves as one transaction per line. The candidates k0 >> j are known before any load, so the 2 x HS_CAND probe loads
+// are issued together with the row's own float4; the one load that depends on them is the goal of the candidate taken. A row that
+// is not drawn probes itself (k = 0 everywhere: lines the row's own float4 brought in), a candidate past the ring's end likewise.
+// H <= 1024 makes k0 < 2^10, so candidate HS_CAND - 1 is always 0 and candidates beyond ceil(log2 H) repeat it: a fixed trip
+// count gives the first valid candidate of the rule's list.
+// ------------------------------------------------------------------------------------------------
+#define HS_CAND 11
+#define HS_DOMAIN 0x48494E44u      // 'HIND'
+
+struct HindsightArgs {
+    uint64_t seed, counter_off;
+    const uint64_t* counter_dev;
+    int32_t *k_out, *k0_out;
+    float ratio;
+    int stride, horizon, rows_per_batch, tag_col;
+    int S, A;
+};
+
+template <int W4C /* 0 = run-time width */>
+__global__ __launch_bounds__(256) void replay_gather_rows_hindsight_kernel(const float4* __restrict__ ring,
+                                                                           uint64_t* __restrict__ meta,
+                                                                           const int32_t* __restrict__ idx,
+                                                                           float4* __restrict__ out, int n, uint64_t cap,
+                                                                           int rf4_shift, int w4_rt, int trunc_lo, int trunc_hi,
+                                                                           const HindsightArgs hs) {
+    const uint64_t head = meta[META_HEAD];
+    const uint64_t size = meta[META_SIZE];
+    const uint64_t base = head + cap - size;
+    const unsigned w4 = W4C ? (unsigned)W4C : (unsigned)w4_rt;
+    const int64_t total = (int64_t)n * w4;
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool ok = j < total;
+    const unsigned jj = ok ? (unsigned)j : 0u;
+    const unsigned r = jj / w4;
+    const int col = (int)(jj - r * w4);
+    int64_t i = (int64_t)idx[r];
+    bool bad = false;
+    if (i < 0 || (uint64_t)i >= size) {
+        if (ok && col == 0) atomicAdd((unsigned long long*)&meta[META_BAD_IDX], 1ull);
+        i = 0;
+        bad = true;          // row 0 as the plain gather writes it, never relabelled
+    }
+    const float* ringf = (const float*)ring;
+    const int rf_shift = rf4_shift + 2;
+    uint64_t pos = base + (uint64_t)i;
+    pos = pos >= cap ? pos - cap : pos;
+    pos = pos >= cap ? pos - cap : pos;
+    const uint64_t row0 = pos << rf_shift;                       // first float of ring row i
+
+    // the row's draw: the stream position of its minibatch's index draw
+    const unsigned u = r / (unsigned)hs.rows_per_batch, b = r - u * (unsigned)hs.rows_per_batch;
+    const uint64_t ctr = (hs.counter_dev ? *hs.counter_dev : 0ull) + hs.counter_off + (uint64_t)u;
+    const Philox4 p = philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), b, HS_DOMAIN, (uint32_t)hs.seed, (uint32_t)(hs.seed >> 32));
+    const bool drawn = !bad && naf_u01(p.v[0]) < hs.ratio;
+    const unsigned k0 = drawn ? __umulhi(p.v[1], (unsigned)hs.horizon) : 0u;
+
+    const int S = hs.S, A = hs.A;
+    const int off_r = S + A, off_s2 = naf_row_off_s2(S, A), off_d = off_s2 + S;
+    const int ee2 = off_s2 + 2 * A;                              // end effector of next_state
+
+    uint64_t crow[HS_CAND];
+    bool inside[HS_CAND];
+#pragma unroll
+    for (int c = 0; c < HS_CAND; ++c) {
+        const uint64_t ic = (uint64_t)i + (uint64_t)(k0 >> c) * (uint64_t)hs.stride;      // < 2^31 + 2^10 * 2^31
+        inside[c] = ic < size;
+        uint64_t pc = base + (inside[c] ? ic : (uint64_t)i);
+        pc = pc >= cap ? pc - cap : pc;
+        pc = pc >= cap ? pc - cap : pc;
+        crow[c] = pc << rf_shift;
+    }
+    // every load below is unconditional and inside the ring
+    const float4 v_in = ring[(pos << rf4_shift) + (uint64_t)col];
+    const float tag_i = ringf[row0 + hs.tag_col];
+    float ctag[HS_CAND], crew[HS_CAND];
+#pragma unroll
+    for (int c = 0; c < HS_CAND; ++c) {
+        ctag[c] = ringf[crow[c] + hs.tag_col];
+        crew[c] = ringf[crow[c] + off_r];
+    }
+    const float ex = ringf[row0 + ee2], ey = ringf[row0 + ee2 + 1], ez = ringf[row0 + ee2 + 2];
+
+    int taken = -1;
+    uint64_t grow = row0;
+#pragma unroll
+    for (int c = HS_CAND - 1; c >= 0; --c) {                     // (descending: the first valid one wins)
+        const bool valid = drawn && tag_i >= 1.f && inside[c] && ctag[c] == tag_i && crew[c] != -1000.f;
+        taken = valid ? (int)(k0 >> c) : taken;
+        grow = valid ? crow[c] : grow;
+    }
+    const float gx = ringf[grow + ee2], gy = ringf[grow + ee2 + 1], gz = ringf[grow + ee2 + 2];
+    const float dx = ex - gx, dy = ey - gy, dz = ez - gz;
+    const float dist = sqrtf(dx * dx + dy * dy + dz * dz);
+    const bool reached = dist < 0.05f;
+    const float reward = reached ? 250.f : -(dist - 0.05f);
+    const float done = reached ? 1.f : 0.f;
+
+    if (!ok) return;
+    if (col == 0 && hs.k_out) hs.k_out[r] = !drawn ? -1 : (taken < 0 ? -2 : taken);
+    if (col == 0 && hs.k0_out) hs.k0_out[r] = drawn ? (int)k0 : -1;
+    float v[4] = {v_in.x, v_in.y, v_in.z, v_in.w};
+    const int f0 = col * 4;
+    const int t1 = 2 * A + 3, t2 = off_s2 + 2 * A + 3;           // the target columns of state and of next_state
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int f = f0 + c;
+        if (f >= trunc_lo && f < trunc_hi) v[c] = truncf(v[c]);
+        if (taken >= 0) {
+            const int g = f >= t2 ? f - t2 : f - t1;
+            if (g >= 0 && g < 3) v[c] = g == 0 ? gx : (g == 1 ? gy : gz);
+            if (f == off_r) v[c] = reward;
+            if (f == off_d) v[c] = done;
+        }
+    }
+    out[j] = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+extern "C" int naf_replay_gather_rows_hindsight(naf_replay_t* h, const int32_t* idx, float* out_rows, int n, int out_ld,
+                                                int action_mode, const naf_hindsight_t* hd, void* stream) {
+    if (!h || h->magic != NAF_REPLAY_MAGIC) return NAF_ERR_STATE;
+    if (!idx || !out_rows || !hd || n < 0 || ((uintptr_t)out_rows & 15) != 0) return NAF_ERR_ARG;
+    if (action_mode != NAF_ACTION_TRUNC_INT && action_mode != NAF_ACTION_FLOAT) return NAF_ERR_ARG;
+    if ((out_ld & 3) != 0 || out_ld < naf_round_up(naf_row_off_done(h->S, h->A) + 1, 4) || out_ld > h->row_floats)
+        return NAF_ERR_ARG;
+    // the chain environment's row: state = [q | qdot | end effector | target | obstacle]
+    if (h->S != 2 * h->A + 9) return NAF_ERR_ARG;
+    if (hd->stride < 1 || hd->horizon < 1 || hd->horizon > NAF_HINDSIGHT_MAX_HORIZON || hd->rows_per_batch < 1) return NAF_ERR_ARG;
+    if (!(hd->ratio >= 0.f && hd->ratio <= 1.f)) return NAF_ERR_ARG;
+    if (hd->tag_col <= naf_row_off_done(h->S, h->A) || hd->tag_col >= h->row_floats) return NAF_ERR_ARG;
+    if (((uintptr_t)hd->counter_dev & 7) != 0 || ((uintptr_t)hd->k_out & 3) != 0 || ((uintptr_t)hd->k0_out & 3) != 0) return NAF_ERR_ARG;
+    if (n == 0) return NAF_OK;
+    const int w4 = out_ld / 4;
+    if ((int64_t)n * w4 >= 0x7fffffffll) return NAF_ERR_ARG;
+    const int sh = ilog2_exact(h->row_floats / 4);
+    int lo = h->S, hi = h->S + h->A;
+    if (action_mode == NAF_ACTION_FLOAT) lo = hi = 0x7fffffff;
+    HindsightArgs hs;
+    hs.seed = hd->seed;
+    hs.counter_off = hd->counter_off;
+    hs.counter_dev = hd->counter_dev;
+    hs.k_out = hd->k_out;
+    hs.k0_out = hd->k0_out;
+    hs.ratio = hd->ratio;
+    hs.stride = hd->stride;
+    hs.horizon = hd->horizon;
+    hs.rows_per_batch = hd->rows_per_batch;
+    hs.tag_col = hd->tag_col;
+    hs.S = h->S;
+    hs.A = h->A;
+    const int blocks = (int)(((int64_t)n * w4 + 255) / 256);
+    hipStream_t st = (hipStream_t)stream;
+#define HS_LAUNCH(W4V)                                                                                                 \
+    replay_gather_rows_hindsight_kernel<W4V><<<blocks, 256, 0, st>>>((const float4*)h->rows, h->meta, idx, (float4*)out_rows, n,  \
+                                                                     h->capacity, sh, w4, lo, hi, hs)
+    if (w4 == 13) HS_LAUNCH(13);
+    else if (w4 == 14) HS_LAUNCH(14);
+    else if (w4 == 16) HS_LAUNCH(16);
+    else HS_LAUNCH(0);
+#undef HS_LAUNCH
+    NAF_CHECK_LAUNCH();
+    return NAF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // gather to the reference's five tensors (API path of ReplayBuffer.sample()): one thread per element
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void replay_gather_soa_kernel(const float* __restrict__ ring,

@@ -72,10 +72,26 @@ class UpdateChunk:
     long parity runs use it; the reference's own per-timestep loop is TimestepGraph below."""
 
     def __init__(self, learner: Learner, replay: ReplayBuffer, n_updates: int, teacher_forced: bool = False,
-                 use_graph: bool = True, gather_outside_graph: bool = False):
+                 use_graph: bool = True, gather_outside_graph: bool = False, hindsight=None):
         """gather_outside_graph: launch sample+gather eagerly in front of the graph of U updates, so the caller can
-        bracket the gather launch with events (bench.py's live roofline measurement)."""
+        bracket the gather launch with events (bench.py's live roofline measurement).
+        hindsight: (ratio, horizon, stride) — the gather relabels goals (ReplayBuffer.gather_rows_hindsight); k_out / k0_out [U, B]
+        then hold what it did to the last chunk's rows. A minibatch's hindsight draw sits at the stream position of its index draw:
+        the sampler's counter has advanced by U when the gather runs, a teacher-forced chunk states its first position in
+        `hindsight_position`."""
         self.L, self.replay, self.U = learner, replay, int(n_updates)
+        self.hindsight = None
+        self.hindsight_position = 0        # teacher-forced: stream position of minibatch 0, relative to the sampler's counter
+        if hindsight is not None and float(hindsight[0]) > 0.0:
+            from .utils import hindsight as hs
+            ratio, horizon, stride = float(hindsight[0]), int(hindsight[1]), int(hindsight[2])
+            hs.check_arguments(ratio, hindsight[1])
+            hs.require_tag_column(learner.lay.S, learner.lay.A)
+            if stride < 1:
+                raise ValueError("UpdateChunk(hindsight=(ratio, horizon, stride)): stride is the number of envs, at least 1")
+            self.hindsight = (ratio, horizon, stride)
+            self.k_out = torch.full((self.U, learner.B), -1, dtype=torch.int32, device=learner.dev)
+            self.k0_out = torch.full((self.U, learner.B), -1, dtype=torch.int32, device=learner.dev)
         self.teacher_forced = teacher_forced
         self.gather_outside_graph = gather_outside_graph
         self.gather_events = None          # optional (start, end) torch.cuda.Event pair recorded around the gather
@@ -102,7 +118,13 @@ class UpdateChunk:
         ev = self.gather_events
         if ev is not None:
             ev[0].record()
-        self.replay.gather_rows(self.idx, self.batch, self.U * self.L.B)
+        if self.hindsight is None:
+            self.replay.gather_rows(self.idx, self.batch, self.U * self.L.B)
+        else:
+            ratio, horizon, stride = self.hindsight
+            off = self.hindsight_position if self.teacher_forced else -self.U
+            self.replay.gather_rows_hindsight(self.idx, self.batch, self.U * self.L.B, stride, horizon, ratio, self.L.B, off,
+                                              self.k_out, self.k0_out)
         if ev is not None:
             ev[1].record()
             if self.empty_events is not None:
@@ -125,7 +147,8 @@ class UpdateChunk:
         self._updates()
 
     def _snapshot(self, extra=()) -> _StateSnapshot:
-        return _StateSnapshot(self.L, self.replay, (self.idx, self.batch, self.loss_parts) + tuple(extra))
+        k = (self.k_out, self.k0_out) if self.hindsight is not None else ()
+        return _StateSnapshot(self.L, self.replay, (self.idx, self.batch, self.loss_parts) + k + tuple(extra))
 
     def capture(self) -> None:
         self.replay.flush()
@@ -809,7 +832,7 @@ class DeviceEnvLoop:
                  noise_scale: float = 1.0, use_graph: bool = True, robot: str = "kuka", obstacle_jitter: float = 0.0,
                  preset: Optional[List[float]] = None, variation: Optional[List[float]] = None, records: bool = False,
                  drain_every: int = 64, chain=None, target=None, obstacle=None, obstacle_radius: float = 0.06,
-                 target_range=None, obstacle_range=None, scene_margin: float = 0.02):
+                 target_range=None, obstacle_range=None, scene_margin: float = 0.02, tag_rows: bool = False):
         """replay=None: no transitions are appended (evaluation). preset: 14 floats [initial joint positions(8) | target |
         obstacle] instead of a named robot's. variation: per-joint half-width of the reset range (None: 0.1 everywhere,
         the stand-in's historical value).
@@ -818,8 +841,16 @@ class DeviceEnvLoop:
         (the stand-in's) are then unused: initial positions and reset ranges are the model's.
         target_range / obstacle_range (chain only): half-widths xyz of the boxes around target / obstacle from which every
         episode of every env draws its scene, kept scene_margin clear of the start pose (include/naf_hip.h, "Scene ranges");
-        None or zeros: the scene is fixed and the launches are those of a loop without them."""
+        None or zeros: the scene is fixed and the launches are those of a loop without them.
+        tag_rows (chain only): every row's last float carries its env's episode ordinal (naf_chain_env_step_tagged), which the
+        hindsight gather needs; False: the launches and the rows are those of a loop without it."""
         self.L, self.replay, self.E = learner, replay, int(n_envs)
+        self.tag_rows = bool(tag_rows)
+        if self.tag_rows:
+            if chain is None:
+                raise ValueError("DeviceEnvLoop(tag_rows=True): episode tags belong to a chain model's rows, the stand-in has none")
+            from .utils.hindsight import require_tag_column
+            require_tag_column(learner.lay.S, learner.lay.A)
         lay, dev = learner.lay, learner.dev
         self.lib = learner.lib
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -910,9 +941,9 @@ class DeviceEnvLoop:
         self.actor.act(self.noise_scale)                                     # NAFAgent.act for E states
         slots = self.drain_every if self.records is not None else 0
         if self._chain_env is not None:
-            check(self.lib.naf_chain_env_step(self._chain_env, ptr(self.env_state), ptr(self.actor.actions), ptr(self.rows),
-                                              ptr(self.actor.obs), self.E, self.seed, ptr(self.step_ctr), self.max_frames,
-                                              ptr(self.records), slots, st), "chain_env_step")   # environment.step
+            step = self.lib.naf_chain_env_step_tagged if self.tag_rows else self.lib.naf_chain_env_step
+            check(step(self._chain_env, ptr(self.env_state), ptr(self.actor.actions), ptr(self.rows), ptr(self.actor.obs), self.E,
+                       self.seed, ptr(self.step_ctr), self.max_frames, ptr(self.records), slots, st), "chain_env_step")   # environment.step
         else:
             check(self.lib.naf_synth_env_step(ptr(self.env_state), ptr(self.actor.actions), ptr(self.rows),
                                               ptr(self.actor.obs), self.E, self.L.lay.A, self.seed, ptr(self.step_ctr),

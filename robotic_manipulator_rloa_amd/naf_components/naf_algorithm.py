@@ -475,7 +475,8 @@ class NAFAgent:
     def run_vectorized(self, vector_steps: Optional[int] = None, n_envs: int = 64, max_frames: int = 400,
                        noise_scale: float = 1.0, robot: str = "kuka", obstacle_jitter: float = 0.0, *,
                        episodes: Optional[int] = None, preset=None, variation=None, drain_every: int = 64,
-                       verbose: bool = False, resume: bool = False, chain=None, scene: Optional[dict] = None) -> dict:
+                       verbose: bool = False, resume: bool = False, chain=None, scene: Optional[dict] = None,
+                       hindsight: float = 0.0, hindsight_horizon: Optional[int] = None) -> dict:
         """NAFAgent.run (naf_algorithm.py:228-292) re-hosted for E synthetic arms on the GPU feeding the HBM replay ring;
         each vector step is followed by E * num_updates / update_freq learn() calls, i.e. the reference's update-to-data
         ratio. Everything stays on the device, no host sync per step.
@@ -503,8 +504,16 @@ class NAFAgent:
         target_range, obstacle_range, scene_margin — a new target / obstacle every episode, see DeviceEnvLoop):
         the E envs are copies of that arm, stepped by csrc/chain_env.hip, instead of the stand-in's (robot / preset / variation /
         obstacle_jitter are then unused). The saved loop position then carries the model's digest and the scene, and a resume
-        with another model is refused."""
+        with another model is refused.
+
+        hindsight (chain only): the share of every minibatch's rows that is replayed under a goal the end effector reached up to
+        hindsight_horizon ticks later in the same episode (default max_frames, at most 1024; utils/hindsight.py states the rule).
+        The step kernel then tags every row with its episode and the gather relabels goal, reward and done; nothing else changes.
+        The ring must be empty when such a run starts (a resume continues its own ring), and last_run_stats gains
+        hindsight_relabelled_share / hindsight_shortened_share / hindsight_reached_share, a sample of the LAST chunk's rows.
+        0 (the default): the launches, the rows and the training state of a run without the argument."""
         E = int(n_envs)
+        hs = self._hindsight_arguments(hindsight, hindsight_horizon, max_frames, chain, resume)
         if (E * self.num_updates) % self.update_freq != 0:
             raise ValueError("n_envs * num_updates must be a multiple of update_freq")
         if vector_steps is None and episodes is None:
@@ -513,8 +522,9 @@ class NAFAgent:
         loop = DeviceEnvLoop(self.learner, self.memory, E, seed=self.seed + 104729 * self.rank, max_frames=max_frames,
                              noise_scale=noise_scale, use_graph=self.use_graph, robot=robot, preset=preset, variation=variation,
                              records=True, drain_every=drain_every,
-                             **{"obstacle_jitter": obstacle_jitter, **self._chain_arguments(chain, scene)})
-        chunk = UpdateChunk(self.learner, self.memory, U, use_graph=self.use_graph)
+                             **{"obstacle_jitter": obstacle_jitter, **self._chain_arguments(chain, scene)},
+                             **({"tag_rows": True} if hs else {}))
+        chunk = UpdateChunk(self.learner, self.memory, U, use_graph=self.use_graph, hindsight=hs and (hs[0], hs[1], E))
         ledger = self._ledger(episodes)
         self.memory.flush()
         updates = steps = 0
@@ -524,6 +534,8 @@ class NAFAgent:
                         variation=None if variation is None else [float(v) for v in variation], drain_every=loop.drain_every)
         if chain is not None:              # (files of stand-in runs keep exactly the keys they have)
             position.update(chain=chain.digest(), scene=list(loop.scene))
+        if hs:                             # (files of runs without hindsight keep exactly the keys they have)
+            position.update(hindsight=hs[0], hindsight_horizon=hs[1])
 
         def add(score, frames):
             if ledger.complete:
@@ -572,7 +584,33 @@ class NAFAgent:
             "env_steps": steps * E, "updates": updates, "seconds": dt, "env_steps_per_s": (steps - steps0) * E / dt,
             "last_loss": float(chunk.losses()[-1].item()) if updates > 0 and steps > steps0 else None, "scores": scores,
             "episodes_finished": ledger.count + ledger.extra, "checkpoints": list(ledger.checkpoints)}
+        if hs and updates > 0 and steps > steps0:
+            from ..utils.hindsight import shares      # a sample: the rows of the last chunk only
+            off_d = self.learner.lay.S + self.memory.off_s2
+            self.last_run_stats.update(shares(chunk.k_out.cpu().numpy(), chunk.k0_out.cpu().numpy(),
+                                              chunk.batch[..., off_d].cpu().numpy()))
         return self.last_run_stats
+
+    def _hindsight_arguments(self, hindsight, horizon, max_frames, chain, resume):
+        """(ratio, horizon) of a run with hindsight goals, None without; every refusal names its reason."""
+        from ..utils import hindsight as hs
+        if not hindsight and horizon is None:
+            return None
+        if horizon is None:
+            horizon = max(1, min(int(max_frames), hs.MAX_HORIZON))
+        hs.check_arguments(hindsight, horizon)
+        if float(hindsight) == 0.0:
+            return None
+        if chain is None:
+            raise ValueError("hindsight goals need the kinematic arm environment's rows (a chain model): the stand-in, PyBullet "
+                             "and host environments store no end effector the gather could take a goal from")
+        if self.world_size > 1:
+            raise ValueError("hindsight goals are not available in a data-parallel run")
+        hs.require_tag_column(self.state_size, self.action_size)
+        if not resume and len(self.memory) > 0:
+            raise ValueError(f"hindsight goals need a ring filled by this run alone: the replay buffer already holds "
+                             f"{len(self.memory)} rows (rows i and i + n_envs must be the same env one tick apart)")
+        return float(hindsight), int(horizon)
 
     @staticmethod
     def _chain_arguments(chain, scene: Optional[dict]) -> dict:

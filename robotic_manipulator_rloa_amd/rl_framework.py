@@ -528,17 +528,20 @@ class ManipulatorFramework:
         logger.info('NAFAgent instance has been successfully removed')
 
     # ---- training ---------------------------------------------------------------------------------------------------
-    def run_training(self, episodes: int, frames: Optional[int] = 500, verbose: bool = True, n_envs: Optional[int] = None):
+    def run_training(self, episodes: int, frames: Optional[int] = 500, verbose: bool = True, n_envs: Optional[int] = None,
+                     hindsight: float = 0.0, hindsight_horizon: Optional[int] = None):
         """rl_framework.py:478-501 -> NAFAgent.run(frames, episodes, verbose): {episode: (score, last_frame)}, checkpoints,
         model.p. n_envs=E (or the n_envs given to initialize_naf_agent): the same outputs from E environments at once —
-        episodes numbered in completion order, `frames` the budget of each; counters in naf_agent.last_run_stats."""
+        episodes numbered in completion order, `frames` the budget of each; counters in naf_agent.last_run_stats.
+        hindsight / hindsight_horizon (kinematic environment with n_envs=E only): NAFAgent.run_vectorized's hindsight goals."""
         if not self.naf_agent or not self.env:
             raise ConfigurationIncomplete
         E = n_envs if n_envs is not None else self._n_envs
+        hs = self._hindsight_arguments(hindsight, hindsight_horizon, E)
         if E is None or E <= 1:
             return self.naf_agent.run(frames, episodes, verbose)
         if isinstance(self.env, _DEVICE_ENVS):
-            return self.naf_agent.run_vectorized(episodes=episodes, n_envs=int(E), max_frames=frames, verbose=verbose,
+            return self.naf_agent.run_vectorized(episodes=episodes, n_envs=int(E), max_frames=frames, verbose=verbose, **hs,
                                                  **self._device_env_arguments())['scores']
         vec = self._host_vector_env(int(E), frames)
         try:
@@ -546,8 +549,19 @@ class ManipulatorFramework:
         finally:
             vec.close()
 
+    def _hindsight_arguments(self, hindsight, hindsight_horizon, E) -> dict:
+        """run_vectorized's two arguments, or nothing for a call without them; a refusal where no kinematic many-env loop runs"""
+        if not hindsight and hindsight_horizon is None:
+            return {}
+        from .utils.hindsight import check_arguments
+        check_arguments(hindsight, 1 if hindsight_horizon is None else hindsight_horizon)
+        if hindsight and (E is None or E <= 1 or not isinstance(self.env, KinematicEnvironment)):
+            raise ValueError('hindsight goals need the kinematic arm environment with n_envs > 1 (a chain model on the device): '
+                             'the one-env loop, the synthetic stand-in and PyBullet store no goal the gather could rewrite')
+        return {'hindsight': float(hindsight), 'hindsight_horizon': hindsight_horizon}
+
     def resume_training(self, episode: int, episodes: int, frames: Optional[int] = 500, verbose: bool = True,
-                        n_envs: Optional[int] = None):
+                        n_envs: Optional[int] = None, hindsight: float = 0.0, hindsight_horizon: Optional[int] = None):
         """Continue the run_training() whose checkpoint `episode` holds a training_state.pt (an agent initialised with
         save_training_state=True writes one beside weights.p) up to `episodes` episodes: the same run as if it had never
         stopped. Returns the whole scores dict. frames / n_envs must be those of the saved run."""
@@ -560,6 +574,7 @@ class ManipulatorFramework:
         E = n_envs if n_envs is not None else self._n_envs
         if E is not None and E > 1 and not isinstance(self.env, _DEVICE_ENVS):
             raise InvalidNAFAgentParameter('Training with environments in worker processes cannot be resumed')
+        hs = self._hindsight_arguments(hindsight, hindsight_horizon, E)
         path = f'checkpoints/{episode}/training_state.pt'
         if not os.path.isfile(path):
             raise MissingWeightsFile(f'{path} does not exist (initialize the agent with save_training_state=True)')
@@ -567,7 +582,7 @@ class ManipulatorFramework:
         if E is None or E <= 1:
             return self.naf_agent.run(frames, episodes, verbose, resume=True)
         return self.naf_agent.run_vectorized(episodes=episodes, n_envs=int(E), max_frames=frames, verbose=verbose, resume=True,
-                                             **self._device_env_arguments())['scores']
+                                             **hs, **self._device_env_arguments())['scores']
 
     def run_vectorized_training(self, vector_steps: int, n_envs: int = 64, max_frames: int = 400) -> dict:
         """Many-env training on the device-resident synthetic arms (BASELINE configs[1..4] shape) for a fixed number of

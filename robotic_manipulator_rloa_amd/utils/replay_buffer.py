@@ -172,6 +172,37 @@ class ReplayBuffer:
         check(self.lib.naf_replay_gather_rows(self.handle, ptr(idx), ptr(out_rows), int(n), int(out_rows.shape[-1]),
                                               self.action_mode, stream_ptr()), "naf_replay_gather_rows")
 
+    def gather_rows_hindsight(self, idx: torch.Tensor, out_rows: torch.Tensor, n: int, stride: int, horizon: int, ratio: float,
+                              rows_per_batch: int, counter_off: int, k_out: Optional[torch.Tensor] = None,
+                              k0_out: Optional[torch.Tensor] = None) -> None:
+        """gather_rows with hindsight goals (utils/hindsight.py states the rule; include/naf_hip.h, "Hindsight goals"): a share
+        `ratio` of the rows is written as if its goal had been where the end effector stood up to `horizon` ticks later in the
+        same episode. stride: rows i and i + k * stride in deque order are the same env, k ticks apart. The draw of output row r
+        sits at stream position sampler counter + counter_off + r // rows_per_batch (mod 2^64). k_out / k0_out: optional int32 [n],
+        the k taken (-1 not drawn, -2 no valid candidate) and the k0 drawn. ratio == 0 is the plain gather."""
+        from . import hindsight
+        hindsight.check_arguments(ratio, horizon)
+        if int(stride) < 1 or int(rows_per_batch) < 1:
+            raise ValueError("gather_rows_hindsight: stride and rows_per_batch are positive")
+        tag_col = hindsight.require_tag_column(self.S, self.A)
+        if float(ratio) == 0.0:
+            if k_out is not None:
+                k_out.fill_(-1)
+            if k0_out is not None:
+                k0_out.fill_(-1)
+            return self.gather_rows(idx, out_rows, n)
+        self._join_side()
+        if not out_rows.is_contiguous() or out_rows.numel() < int(n) * out_rows.shape[-1]:
+            raise ValueError("gather_rows_hindsight: out_rows must be contiguous and hold n rows")
+        for t in (k_out, k0_out):
+            if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < int(n)):
+                raise ValueError("gather_rows_hindsight: k_out / k0_out are contiguous int32 tensors of n elements")
+        d = _lib.Hindsight(int(stride), int(horizon), float(ratio), int(rows_per_batch), self.seed & 0xFFFFFFFFFFFFFFFF,
+                           ptr(self._sample_ctr), int(counter_off) & 0xFFFFFFFFFFFFFFFF, tag_col, ptr(k_out), ptr(k0_out))
+        check(self.lib.naf_replay_gather_rows_hindsight(self.handle, ptr(idx), ptr(out_rows), int(n), int(out_rows.shape[-1]),
+                                                        self.action_mode, _lib.C.byref(d), stream_ptr()),
+              "naf_replay_gather_rows_hindsight")
+
     def sample(self, idx: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, ...]:
         """(states, actions, rewards, next_states, dones) with the reference's shapes and dtypes
         (replay_buffer.py:47-67): f32 (B,S), int64 (B,A) truncated, f32 (B,1), f32 (B,S), f32 (B,1).
