@@ -8,14 +8,14 @@ count, a launch loop of the two step kernels for `rocprofv3 --kernel-trace --sta
   rocprofv3 --kernel-trace --stats -d OUT -- python benchmarks/chain_env_bench.py kernels
       1000 launches each of chain_env_step_kernel for standin8 (A = 8, E = 64) and long32, and of synth_env_step_kernel
       (`--autocollision`: the two arms compiled with their self-collision pairs, 18 and 465: the SC = true instantiation)
-  python benchmarks/chain_env_bench.py step --envs 4096 --launches 4000 [--autocollision] [--workcell]
+  python benchmarks/chain_env_bench.py step --envs 4096 --launches 4000 [--autocollision] [--workcell [--boxes]]
       microseconds per naf_chain_env_step launch of --urdf (device events around `--launches` launches with the step counter
       running, max_frames = 400, N(0, 1) actions; `--repeats` windows after one warm-up window). Two launches per step are
       enqueued by the host, so at small E the figure is bounded below by launch submission: the kernel's own time comes from
       `rocprofv3 --kernel-trace --stats -d OUT -- python benchmarks/chain_env_bench.py step ...`, a run of its own, whose
       maximum per kernel is the launch in which the envs reset (every 400th).
 
-  python benchmarks/chain_env_bench.py rollout --envs 4096 --launches 4000 [--autocollision] [--workcell]
+  python benchmarks/chain_env_bench.py rollout --envs 4096 --launches 4000 [--autocollision] [--workcell [--boxes]]
       microseconds per naf_chain_env_rollout_step launch of --urdf, measured as `step` measures (the same arm, start pose and seeded
       N(0, 1) actions; ONE launch per step: there is no counter), after naf_chain_env_reset_given at the start pose with target and
       obstacle 3 m away and a frame budget beyond the run, so that every env stays live: a held lane returns at once and would
@@ -23,7 +23,8 @@ count, a launch loop of the two step kernels for `rocprofv3 --kernel-trace --sta
 
 `--workcell` (step, rollout): the chain model gets a floor under the base and two spheres beside the arm, so the launches are the
 workcell instantiations. In a rollout an env that touches one of them is held from then on: `envs_held_before_the_window_ended`
-says how many did.
+says how many did. `--workcell --boxes` adds three boxes to them — a table top beside the base, a shelf, a rounded post — so the
+launches are the box instantiations, which test the floor and the spheres too.
 
   python benchmarks/chain_env_bench.py gather [--hindsight 0.8] [--horizon 400] [--launches 200]
       microseconds per launch of the replay gather at n = 64 x 256 rows of the S = 23 / A = 7 arm (--urdf), between device events
@@ -95,9 +96,15 @@ def rate(a):
 
 def _workcell(a) -> dict:
     """--workcell: a floor under the base and two spheres beside the arm (compile_chain's arguments), clear of the start pose"""
+    if a.boxes and not a.workcell:
+        raise SystemExit("--boxes adds to --workcell: give both")
     if not a.workcell:
         return {}
-    return {"floor_height": 0.0, "workcell_spheres": [(0.51, 0.38, 0.64, 0.128), (-0.4, -0.4, 0.5, 0.1)]}
+    cell = {"floor_height": 0.0, "workcell_spheres": [(0.51, 0.38, 0.64, 0.128), (-0.4, -0.4, 0.5, 0.1)]}
+    if a.boxes:      # a table top, a shelf, a post (a capsule: zero half extents across, a rounding radius)
+        cell["workcell_boxes"] = [(0.58, -0.45, 0.19, 0.32, 0.2, 0.026, 0.0, 0.0, 0.3), (-0.13, 0.64, 0.77, 0.26, 0.064, 0.19, 0.4, -0.3, 0.8),
+                                  (0.0, -0.58, 0.9, 0.0, 0.0, 0.38, 1.2, 0.2, 0.0, 0.05)]
+    return cell
 
 
 def _ranges(a) -> dict:
@@ -151,7 +158,7 @@ def step(a):
             times.append(round(1e3 * t0.elapsed_time(t1) / a.launches, 3))
         starts += int(st[:, n + 8].sum().item() - before)
     out = {"arm": os.path.basename(urdf), "envs": E, "autocollision": a.autocollision, "self_pairs": len(model.self_pairs),
-           "workcell_pairs": len(model.cell_pairs), "launches": a.launches, "ranges": ranges or None, "us_per_step_and_counter_launch": times, "episode_starts": starts}
+           "workcell_pairs": len(model.cell_pairs), "boxes": len(model.cell_boxes), "launches": a.launches, "ranges": ranges or None, "us_per_step_and_counter_launch": times, "episode_starts": starts}
     if ranges:      # the scenes the envs hold now: the centres, exactly, are fallbacks
         s = st[:, n:n + 6].cpu().numpy()
         out["fallback_share_now"] = round(float(np.mean(np.all(s == np.float32(centre), axis=1))), 4)
@@ -202,7 +209,7 @@ def rollout(a):
             held.append(int(((outcome[:, 0] != 0) | (outcome[:, 1] < (a.launches if a.trajectory else a.launches * (w + 1)))).sum().item()))
     lib.naf_chain_env_destroy(h)
     print(json.dumps({"arm": os.path.basename(urdf), "envs": E, "autocollision": a.autocollision, "self_pairs": len(model.self_pairs),
-                      "workcell_pairs": len(model.cell_pairs), "launches": a.launches, "trajectory": bool(a.trajectory), "us_per_rollout_step_launch": times,
+                      "workcell_pairs": len(model.cell_pairs), "boxes": len(model.cell_boxes), "launches": a.launches, "trajectory": bool(a.trajectory), "us_per_rollout_step_launch": times,
                       "envs_held_before_the_window_ended": held}))
 
 
@@ -303,6 +310,7 @@ def main():
     ap.add_argument("--standin-only", action="store_true")
     ap.add_argument("--autocollision", action="store_true")
     ap.add_argument("--workcell", action="store_true", help="step / rollout: a floor and two spheres in the chain model")
+    ap.add_argument("--boxes", action="store_true", help="step / rollout, with --workcell: three boxes beside the floor and the spheres")
     ap.add_argument("--trajectory", action="store_true", help="rollout: record the joint values of every frame")
     ap.add_argument("--arm", default="", help="rate: a fixture arm of tests/golden/urdf by name, --joints its joint count")
     ap.add_argument("--target-range", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))

@@ -710,7 +710,8 @@ int naf_synth_env_state_floats(int A);
  *   header, NAF_CHAIN_HEADER_FLOATS: [0] NAF_CHAIN_BLOB_VERSION  [1] A (driven joints = action size, 1 .. 64)  [2] segments
  *     [3] observation slots (= A)  [4] end-effector frame  [5..7] end-effector point in that frame  [8] floats in the blob
  *     [9] self-collision pairs P (0: none, the blob then ends after the slots)  [10] workcell spheres G  [11] workcell
- *     half-spaces H (G + H <= NAF_CHAIN_MAX_CELL; both 0: no workcell, the blob then ends after the pairs)  [12..15] 0
+ *     half-spaces H  [12] workcell boxes B (G + H + B <= NAF_CHAIN_MAX_CELL; all 0: no workcell, the blob then ends after the
+ *     pairs)  [13..15] 0
  *   A driven joints in action order, NAF_CHAIN_JOINT_FLOATS each: [0..8] pre-rotation, row-major 3 x 3  [9..11] pre-translation
  *     [12..14] unit axis  [15] type, 0 revolute / 1 prismatic  [16] 1 = has position limits  [17] lower  [18] upper
  *     [19] initial position  [20] half-width of the reset range  [21] observation slot reporting this joint, or -1  [22..23] 0
@@ -724,14 +725,21 @@ int naf_synth_env_state_floats(int A);
  *   P self-collision pairs, 2 floats each: segment indices [0] s < [1] t, no pair twice;
  *     self-contact = distance(segment s, segment t) - radius s - radius t < 0 for any pair: reward -1000 and done, as obstacle
  *     contact (reaching the target still wins). NAF_CHAIN_BLOB_VERSION stays 1: without pairs the bytes are ABI 36's.
- *   Workcell (ABI 40; only when G + H > 0), fixed geometry that is the same in every episode and has no slot in the observation:
+ *   Workcell (ABI 40; only when G + H + B > 0), fixed geometry that is the same in every episode and has no slot in the observation:
  *     G spheres, 4 floats each: centre xyz, radius >= 0;  H half-spaces, 4 floats each: unit normal n, offset d, the free side
- *     is n.x - d >= 0;  then one mask float per segment: bit g set = test this segment against geometry g, spheres first (an
- *     integer below 2^(G+H) <= 65536, exact in a float). Clearance of a capsule (world end points a, b, radius rho):
- *     distance(segment ab, centre) - rho - r against a sphere, min(n.a, n.b) - d - rho against a half-space. Workcell contact =
+ *     is n.x - d >= 0;  B rounded oriented boxes, NAF_CHAIN_BOX_FLOATS each: [0..2] centre c  [3..11] orientation R, row-major
+ *     3 x 3, orthonormal (its columns are the box's axes in the world)  [12..14] half extents h >= 0  [15] rounding radius r >= 0;
+ *     then one mask float per segment: bit g set = test this segment against geometry g, spheres first, then half-spaces, then
+ *     boxes (an integer below 2^(G+H+B) <= 65536, exact in a float). Clearance of a capsule (world end points a, b, radius rho):
+ *     distance(segment ab, centre) - rho - r against a sphere, min(n.a, n.b) - d - rho against a half-space, distance(segment ab,
+ *     box) - rho - r against a box: with p(t) = R^T (a - c) + t R^T (b - a), sqrt(min over t in [0, 1] of sum_i max(|p_i(t)| -
+ *     h_i, 0)^2), which is 0 for a segment that enters the box — no penetration depth is reported. Zero half extents with r > 0
+ *     make the record a fixed capsule or a rounded plate. Workcell contact =
  *     a tested (segment, geometry) pair with clearance < 0: reward -1000 and done, as obstacle contact (reaching the target
  *     still wins). The workcell clearance of a pose is the minimum over the tested pairs, +inf when there are none.
- *     NAF_CHAIN_BLOB_VERSION stays 1: with G = H = 0 the bytes are ABI 39's, and so is every launch.
+ *     NAF_CHAIN_BLOB_VERSION stays 1: with G = H = B = 0 the bytes are ABI 39's, and so is every launch; with B = 0 the bytes
+ *     and the launches are those of the workcell without boxes (boxes are a further instantiation of its kernels and of the
+ *     probe's: no entry point was added for them, the ABI stays 40).
  *
  * env_state record of one env, naf_chain_env_state_floats floats = round_up(round_up(A + 9, 2) + 2, 4):
  *   [0 .. A) driven joint positions by action index  [A .. A+3) target  [A+3 .. A+6) obstacle centre  [A+6] obstacle radius
@@ -751,7 +759,7 @@ int naf_synth_env_state_floats(int A);
  *                 (step mod record_slots, env), the same Philox keying of the reset draws and of the obstacle jitter.
  *                 With P = 0 the launch is ABI 36's kernel. The auto-reset inside step does not test the reset pose against
  *                 itself: a reset pose in self-contact ends its episode at the next step. Neither against the workcell: the
- *                 same rule. With G + H > 0 the launch is a further instantiation of the kernel (csrc/chain_env.hip).
+ *                 same rule. With G + H + B > 0 the launch is a further instantiation of the kernel (csrc/chain_env.hip).
  *   probe       : out [E][NAF_CHAIN_PROBE_FLOATS] = [end-effector xyz | min over segments of (distance to the obstacle centre -
  *                 capsule radius) - obstacle radius (obstacle contact iff < 0) | min over the pairs of the pair clearance
  *                 (self-contact iff < 0; +inf when P = 0)] at the joint values and scene in env_state; changes no state.
@@ -810,9 +818,11 @@ int naf_synth_env_state_floats(int A);
 #define NAF_CHAIN_ERR_SEGMENTS (-17) /* begin table not monotone, or a segment outside its frame's range (unsorted) */
 #define NAF_CHAIN_ERR_SLOTS (-18)
 #define NAF_CHAIN_ERR_PAIRS (-19)    /* pair count or table size, an index out of range or not an integer, s >= t, a pair twice */
-#define NAF_CHAIN_ERR_CELL (-21)     /* workcell: a count out of range, a non-unit normal, a negative radius, a mask that is not an
-                                        integer below 2^(G+H), a wrong blob size */
-#define NAF_CHAIN_MAX_CELL 16
+#define NAF_CHAIN_ERR_CELL (-21)     /* workcell: a count out of range, a non-unit normal, a negative radius or half extent, a box
+                                        orientation with |R R^T - I| > 1e-4, a mask that is not an integer below 2^(G+H+B), a wrong
+                                        blob size */
+#define NAF_CHAIN_MAX_CELL 16        /* spheres + half-spaces + boxes */
+#define NAF_CHAIN_BOX_FLOATS 16
 #define NAF_CHAIN_ERR_LDS (-20)      /* create: P > 0 and one env's capsule end points exceed a workgroup's LDS */
 #define NAF_CHAIN_PROBE_FLOATS 5
 #define NAF_CHAIN_SCENE_TRIES 8

@@ -32,6 +32,11 @@
 // CELL = true, and a probe of its own; without one the launches are the CELL-less kernels, unchanged. The walk tests each capsule,
 // behind its obstacle test, against the geometries its mask names: counts, mask and geometry come through uniform loads, the
 // trip counts are uniform, and nothing is kept per lane but the running minimum. The walk of an auto-reset pose does not test.
+//
+// Boxes (B > 0 rounded oriented boxes in the blob) are one more instantiation again, BOX = true, of the CELL kernels and of the
+// probe: behind the sphere and half-space loop the capsule's segment is taken into each box's frame and its distance to the box is
+// found in closed form (seg_box_dist2: eight knots, a fixed trip count, the running bracket of the derivative the only state).
+// The BOX kernels test the model's spheres and half-spaces too; a model without a box launches the kernels it always did.
 #include "common.h"
 #include "../../include/naf_hip.h"
 
@@ -48,12 +53,14 @@
 #define CH_JNT NAF_CHAIN_JOINT_FLOATS
 #define CH_SEG NAF_CHAIN_SEGMENT_FLOATS
 #define CH_TRIES NAF_CHAIN_SCENE_TRIES
+#define CH_BOX NAF_CHAIN_BOX_FLOATS
 #define CH_REACHED 0.05f                     // the target threshold of the reward rule
 
 struct naf_chain_env {
     float* model_dev;
     int n_floats, A, n_seg;
-    int n_cell;                     // G + H: workcell geometries in the blob (0: the CELL-less kernels are launched)
+    int n_cell;                     // G + H + B: workcell geometries in the blob (0: the CELL-less kernels are launched)
+    int n_box;                      // B of them boxes (0: the launches are the ones of a model without boxes)
     int n_pairs, lanes, waves;      // P; with P > 0: envs per workgroup (64, 32, .. 1) and waves per workgroup
     float ranges[NAF_CHAIN_RANGE_FLOATS];      // set_scene_ranges: target half-widths | obstacle half-widths | margin
     float centre[6];                // target | obstacle of the last reset's scene_host: the boxes' centres and the fallback
@@ -88,6 +95,8 @@ struct ChainCell {};
 // and one more, last in the pack: the row's last float carries the 1-based ordinal of the env's current episode (hindsight
 // relabelling in the replay gather asks for it; 0, what every launch without it leaves there, means "untagged")
 struct ChainTag {};
+// a third empty member, behind ChainCell: the model holds boxes, which the walk tests behind the spheres and half-spaces
+struct ChainBox {};
 template <class... Rest>
 __device__ static inline const ChainRanges& scene_ranges(const ChainRanges& rg, const Rest&...) { return rg; }
 
@@ -95,7 +104,7 @@ __host__ __device__ static inline int ch_off_begin(int A) { return CH_HDR + CH_J
 __host__ __device__ static inline int ch_off_seg(int A) { return ch_off_begin(A) + A + 2; }
 __host__ __device__ static inline int ch_off_slot(int A, int n_seg) { return ch_off_seg(A) + CH_SEG * n_seg; }
 __host__ __device__ static inline int ch_off_pair(int A, int n_seg) { return ch_off_slot(A, n_seg) + 2 * A; }
-// the workcell section: G spheres, H half-spaces (4 floats each), then n_seg masks
+// the workcell section: G spheres, H half-spaces (4 floats each), B boxes (CH_BOX floats each), then n_seg masks
 __host__ __device__ static inline int ch_off_cell(int A, int n_seg, int n_pairs) { return ch_off_pair(A, n_seg) + 2 * n_pairs; }
 // dynamic LDS of an SC launch: end points [n_seg][6][lanes], then one minimum per (wave, lane)
 __host__ __device__ static inline size_t ch_lds_bytes(int n_seg, int lanes, int waves) {
@@ -149,6 +158,45 @@ __device__ static inline float seg_seg_dist2(float ax, float ay, float az, float
     return best;
 }
 
+// half of f'(t) for f(t) = sum_i max(|p_i + t u_i| - h_i, 0)^2: sum_i (x_i - clamp(x_i, -h_i, h_i)) u_i at x = p + t u
+__device__ static inline float box_slope(float t, float px, float py, float pz, float ux, float uy, float uz, float hx, float hy,
+                                         float hz) {
+    const float x = fmaf(t, ux, px), y = fmaf(t, uy, py), z = fmaf(t, uz, pz);
+    return (x - fminf(hx, fmaxf(-hx, x))) * ux + (y - fminf(hy, fmaxf(-hy, y))) * uy + (z - fminf(hz, fmaxf(-hz, z))) * uz;
+}
+
+// squared distance from the segment p + t u, t in [0, 1], to the box |x_i| <= h_i, all in the box's frame. f is convex and
+// piecewise quadratic, so f' is non-decreasing and linear between its knots: 0, 1 and the six (+-h_i - p_i) / u_i clipped into
+// [0, 1] (an axis with u_i = 0 has none: its two fall on the knot 0). The largest knot with f' <= 0 and the smallest with f' >= 0
+// bracket the minimum, which is where the line through them crosses 0; f' > 0 at 0 puts it at 0, f' < 0 at 1 at 1. No sort, no
+// iteration, and only the bracket is live across the knots.
+__device__ static inline float seg_box_dist2(float px, float py, float pz, float ux, float uy, float uz, float hx, float hy,
+                                             float hz) {
+    float t_lo = 0.f, t_hi = 1.f;
+    float g_lo = box_slope(0.f, px, py, pz, ux, uy, uz, hx, hy, hz), g_hi = box_slope(1.f, px, py, pz, ux, uy, uz, hx, hy, hz);
+    const float g0 = g_lo, g1 = g_hi;
+    const float p[3] = {px, py, pz}, u[3] = {ux, uy, uz}, h[3] = {hx, hy, hz};
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const int i = k >> 1;
+        const float inv = u[i] != 0.f ? 1.f / u[i] : 0.f;
+        const float t = fminf(1.f, fmaxf(0.f, ((k & 1 ? h[i] : -h[i]) - p[i]) * inv));
+        const float g = box_slope(t, px, py, pz, ux, uy, uz, hx, hy, hz);
+        const bool lo = g <= 0.f && t >= t_lo, hi = g >= 0.f && t <= t_hi;
+        t_lo = lo ? t : t_lo;
+        g_lo = lo ? g : g_lo;
+        t_hi = hi ? t : t_hi;
+        g_hi = hi ? g : g_hi;
+    }
+    const float den = g_hi - g_lo;
+    float t = den > 0.f ? t_lo - g_lo * (t_hi - t_lo) / den : t_lo;
+    t = fminf(t_hi, fmaxf(t_lo, t));
+    t = g0 > 0.f ? 0.f : (g1 < 0.f ? 1.f : t);
+    const float x = fmaf(t, ux, px), y = fmaf(t, uy, py), z = fmaf(t, uz, pz);
+    const float ex = fmaxf(fabsf(x) - hx, 0.f), ey = fmaxf(fabsf(y) - hy, 0.f), ez = fmaxf(fabsf(z) - hz, 0.f);
+    return ex * ex + ey * ey + ez * ez;
+}
+
 // Where the SC instantiations keep the capsules' world end points: `ends` is the LDS array already offset by the lane, `lanes`
 // its innermost extent. CLEAR: `clear` collects min over the capsules of (distance to the obstacle centre - capsule radius),
 // and with CELL `cell` the workcell clearance: min over the tested (capsule, geometry) pairs.
@@ -162,7 +210,7 @@ struct WalkAux {
 // contact of the capsules of frame f with the obstacle sphere, and the end-effector point when it lives in f. CELL: also their
 // contact with the workcell — ORed into the result, except with CLEAR, where aux.cell < 0 says it and the result stays the
 // obstacle's own (the rollout tells the two apart).
-template <bool SC, bool PROBE, bool SCENE = false, bool CLEAR = PROBE, bool CELL = false>
+template <bool SC, bool PROBE, bool SCENE = false, bool CLEAR = PROBE, bool CELL = false, bool BOX = false>
 __device__ static inline bool frame_geometry(const float* __restrict__ model, int A, int f, const Frame& F, float ox, float oy,
                                              float oz, float orad, int ee_frame, float* ee, WalkAux& aux, SceneCand* cand = nullptr) {
     const float* begin = model + ch_off_begin(A);
@@ -189,7 +237,9 @@ __device__ static inline bool frame_geometry(const float* __restrict__ model, in
         if constexpr (CELL) {
             const int n_sph = (int)model[10], n_geo = n_sph + (int)model[11];
             const float* geo = model + ch_off_cell(A, (int)model[2], (int)model[9]);
-            const int mask = (int)geo[4 * n_geo + s];
+            int mask;
+            if constexpr (BOX) mask = (int)geo[4 * n_geo + CH_BOX * (int)model[12] + s];
+            else mask = (int)geo[4 * n_geo + s];
             float least = INFINITY;
             for (int k = 0; k < n_geo; ++k) {      // (uniform: the counts, the mask and the geometry are the blob's)
                 if (!(mask >> k & 1)) continue;
@@ -202,6 +252,21 @@ __device__ static inline bool frame_geometry(const float* __restrict__ model, in
                     d = fminf(na, nb) - c[3];
                 }
                 least = fminf(least, d - g[7]);
+            }
+            if constexpr (BOX) {
+                // the boxes' records lie between the G + H records and the masks; geometry index n_geo + k
+                const int n_box = (int)model[12], bmask = mask >> n_geo;
+                const float wx = bx - ax, wy = by - ay, wz = bz - az;
+                for (int k = 0; k < n_box; ++k) {      // (uniform, as above)
+                    if (!(bmask >> k & 1)) continue;
+                    const float* x = geo + 4 * n_geo + CH_BOX * k;      // c | R row-major | h | r
+                    const float ex = ax - x[0], ey = ay - x[1], ez = az - x[2];
+                    const float d2 = seg_box_dist2(x[3] * ex + x[6] * ey + x[9] * ez, x[4] * ex + x[7] * ey + x[10] * ez,
+                                                   x[5] * ex + x[8] * ey + x[11] * ez, x[3] * wx + x[6] * wy + x[9] * wz,
+                                                   x[4] * wx + x[7] * wy + x[10] * wz, x[5] * wx + x[8] * wy + x[11] * wz, x[12],
+                                                   x[13], x[14]);
+                    least = fminf(least, sqrtf(d2) - x[15] - g[7]);
+                }
             }
             if constexpr (CLEAR) aux.cell = fminf(aux.cell, least);
             else hit |= least < 0.f;
@@ -233,14 +298,14 @@ __device__ static inline bool frame_geometry(const float* __restrict__ model, in
 // effector, target and obstacle into the observation `o` (not with PROBE: o is unused); the DRIVEN joints' velocity slots are the
 // caller's. Returns contact with the obstacle. CLEAR (the probe's walk, and the rollout step's beside its observation) also collects
 // the obstacle clearance in aux.clear. CELL: the workcell is tested too (frame_geometry).
-template <bool SC, bool PROBE, bool SCENE = false, bool CLEAR = PROBE, bool CELL = false>
+template <bool SC, bool PROBE, bool SCENE = false, bool CLEAR = PROBE, bool CELL = false, bool BOX = false>
 __device__ static inline bool chain_walk(const float* __restrict__ model, int A, int n_seg, const float* st, float* o, float* ee,
                                          WalkAux& aux, SceneCand* cand = nullptr) {
     const int ee_frame = (int)model[4];
     const float ox = st[A + 3], oy = st[A + 4], oz = st[A + 5], orad = st[A + 6];
     Frame F = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
     ee[0] = ee[1] = ee[2] = 0.f;
-    bool hit = frame_geometry<SC, PROBE, SCENE, CLEAR, CELL>(model, A, 0, F, ox, oy, oz, orad, ee_frame, ee, aux, cand);
+    bool hit = frame_geometry<SC, PROBE, SCENE, CLEAR, CELL, BOX>(model, A, 0, F, ox, oy, oz, orad, ee_frame, ee, aux, cand);
     for (int m = 0; m < A; ++m) {
         const float* j = model + CH_HDR + m * CH_JNT;
         const float q = st[m];
@@ -287,7 +352,7 @@ __device__ static inline bool chain_walk(const float* __restrict__ model, int A,
             F.r21 = G.r20 * m01 + G.r21 * m11 + G.r22 * m21;
             F.r22 = G.r20 * m02 + G.r21 * m12 + G.r22 * m22;
         }
-        hit |= frame_geometry<SC, PROBE, SCENE, CLEAR, CELL>(model, A, m + 1, F, ox, oy, oz, orad, ee_frame, ee, aux, cand);
+        hit |= frame_geometry<SC, PROBE, SCENE, CLEAR, CELL, BOX>(model, A, m + 1, F, ox, oy, oz, orad, ee_frame, ee, aux, cand);
     }
     if constexpr (!PROBE) {
         const float* slots = model + ch_off_slot(A, n_seg);
@@ -432,6 +497,7 @@ chain_env_step_kernel(const float* __restrict__ model, float* env_state, const f
                       int record_slots, int n_pairs, int lanes, const Rg... rg) {
     constexpr bool CELL = (std::is_same_v<Rg, ChainCell> || ... || false);
     constexpr bool TAG = (std::is_same_v<Rg, ChainTag> || ... || false);
+    constexpr bool BOX = (std::is_same_v<Rg, ChainBox> || ... || false);
     extern __shared__ __attribute__((aligned(16))) float ch_lds[];
     int e, lane = 0;
     bool active = true, walker = true;
@@ -473,7 +539,7 @@ chain_env_step_kernel(const float* __restrict__ model, float* env_state, const f
             const int slot = (int)j[21];
             if (slot >= 0) o2[A + slot] = vel;
         }
-        hit = chain_walk<SC, false, false, false, CELL>(model, A, n_seg, st, o2, ee, aux);
+        hit = chain_walk<SC, false, false, false, CELL, BOX>(model, A, n_seg, st, o2, ee, aux);
     }
     if constexpr (SC) {
         // self-contact counts as contact (environment.py:311-343); the walker's lanes hold the minimum over all pairs
@@ -533,6 +599,18 @@ chain_env_probe_cell_kernel(const float* __restrict__ model, const float* __rest
     float ee[3];
     WalkAux aux = {nullptr, 0, INFINITY, INFINITY};
     chain_walk<false, true, false, true, true>(model, A, n_seg, env_state + (int64_t)e * ch_state_floats(A), nullptr, ee, aux);
+    out[e] = aux.cell;
+}
+
+// the same for a model with boxes
+__global__ void __launch_bounds__(64)
+chain_env_probe_cell_box_kernel(const float* __restrict__ model, const float* __restrict__ env_state, float* __restrict__ out, int E,
+                                int A, int n_seg) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    float ee[3];
+    WalkAux aux = {nullptr, 0, INFINITY, INFINITY};
+    chain_walk<false, true, false, true, true, true>(model, A, n_seg, env_state + (int64_t)e * ch_state_floats(A), nullptr, ee, aux);
     out[e] = aux.cell;
 }
 
@@ -607,6 +685,7 @@ chain_env_rollout_kernel(const float* __restrict__ model, float* env_state, cons
                          float* __restrict__ obs_next, float* __restrict__ outcome, float* __restrict__ traj, int E, int A, int n_seg,
                          int max_frames, int n_pairs, int lanes, const Cell... cell) {
     constexpr bool CELL = (std::is_same_v<Cell, ChainCell> || ... || false);
+    constexpr bool BOX = (std::is_same_v<Cell, ChainBox> || ... || false);
     extern __shared__ __attribute__((aligned(16))) float ch_lds[];
     int e, lane = 0;
     bool active = true, walker = true;
@@ -645,7 +724,7 @@ chain_env_rollout_kernel(const float* __restrict__ model, float* env_state, cons
             const int slot = (int)j[21];
             if (slot >= 0) ob[A + slot] = vel;
         }
-        hit = chain_walk<SC, false, false, true, CELL>(model, A, n_seg, st, ob, ee, aux);
+        hit = chain_walk<SC, false, false, true, CELL, BOX>(model, A, n_seg, st, ob, ee, aux);
     }
     float self_clear = INFINITY;
     if constexpr (SC) {
@@ -696,11 +775,13 @@ extern "C" int naf_chain_env_model_check(const float* m, int n_floats) {
     if (!ch_int(m[1], 1, CH_MAX_A, &A) || !ch_int(m[2], 0, 1 << 20, &n_seg) || !ch_int(m[3], A, A, &n_slot))
         return NAF_CHAIN_ERR_COUNTS;
     if (!ch_int(m[8], CH_HDR, 1 << 24, &total) || total != n_floats) return NAF_CHAIN_ERR_SIZE;
-    int P = 0, G = 0, H = 0;
+    int P = 0, G = 0, H = 0, B = 0;
     const bool pairs_counted = ch_int(m[9], 0, 1 << 22, &P);
     // (a blob without a workcell has zeros here and takes every check below as it always did)
-    if (!ch_int(m[10], 0, NAF_CHAIN_MAX_CELL, &G) || !ch_int(m[11], 0, NAF_CHAIN_MAX_CELL - G, &H)) return NAF_CHAIN_ERR_CELL;
-    const int cell = G + H > 0 ? 4 * (G + H) + n_seg : 0;
+    if (!ch_int(m[10], 0, NAF_CHAIN_MAX_CELL, &G) || !ch_int(m[11], 0, NAF_CHAIN_MAX_CELL - G, &H) ||
+        !ch_int(m[12], 0, NAF_CHAIN_MAX_CELL - G - H, &B))
+        return NAF_CHAIN_ERR_CELL;
+    const int cell = G + H + B > 0 ? 4 * (G + H) + CH_BOX * B + n_seg : 0;
     if (pairs_counted && P == 0 && cell == 0 && total != ch_off_pair(A, n_seg)) return NAF_CHAIN_ERR_SIZE;
     for (int k = 0; k < n_floats; ++k)
         if (!std::isfinite(m[k])) return NAF_CHAIN_ERR_VALUE;
@@ -753,9 +834,19 @@ extern "C" int naf_chain_env_model_check(const float* m, int n_floats) {
         const float* n = geo + 4 * g;
         if (std::fabs(n[0] * n[0] + n[1] * n[1] + n[2] * n[2] - 1.f) > 1e-4f) return NAF_CHAIN_ERR_CELL;
     }
+    for (int b = 0; b < B; ++b) {
+        const float* x = geo + 4 * (G + H) + CH_BOX * b;      // c | R row-major | h | r
+        const float* R = x + 3;
+        if (x[12] < 0.f || x[13] < 0.f || x[14] < 0.f || x[15] < 0.f) return NAF_CHAIN_ERR_CELL;
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) {
+                const float dot = R[3 * i] * R[3 * j] + R[3 * i + 1] * R[3 * j + 1] + R[3 * i + 2] * R[3 * j + 2];
+                if (std::fabs(dot - (i == j ? 1.f : 0.f)) > 1e-4f) return NAF_CHAIN_ERR_CELL;
+            }
+    }
     for (int s = 0; cell > 0 && s < n_seg; ++s) {
         int mask;
-        if (!ch_int(geo[4 * (G + H) + s], 0, (1 << (G + H)) - 1, &mask)) return NAF_CHAIN_ERR_CELL;
+        if (!ch_int(geo[4 * (G + H) + CH_BOX * B + s], 0, (1 << (G + H + B)) - 1, &mask)) return NAF_CHAIN_ERR_CELL;
     }
     return NAF_OK;
 }
@@ -768,7 +859,7 @@ static int ch_raise_lds_limit() {
     if (e != hipSuccess) return (int)e;
     if (dev < 0 || dev >= 64) return NAF_ERR_ARG;
     if (raised_dev[dev]) return NAF_OK;
-    const void* ks[11] = {(const void*)chain_env_step_kernel<true, false>, (const void*)chain_env_step_kernel<true, true, ChainRanges>,
+    const void* ks[16] = {(const void*)chain_env_step_kernel<true, false>, (const void*)chain_env_step_kernel<true, true, ChainRanges>,
                          (const void*)chain_env_probe_kernel<true>, (const void*)chain_env_rollout_kernel<true>,
                          (const void*)chain_env_step_kernel<true, false, ChainCell>,
                          (const void*)chain_env_step_kernel<true, true, ChainRanges, ChainCell>,
@@ -776,7 +867,12 @@ static int ch_raise_lds_limit() {
                          (const void*)chain_env_step_kernel<true, false, ChainTag>,
                          (const void*)chain_env_step_kernel<true, true, ChainRanges, ChainTag>,
                          (const void*)chain_env_step_kernel<true, false, ChainCell, ChainTag>,
-                         (const void*)chain_env_step_kernel<true, true, ChainRanges, ChainCell, ChainTag>};
+                         (const void*)chain_env_step_kernel<true, true, ChainRanges, ChainCell, ChainTag>,
+                         (const void*)chain_env_step_kernel<true, false, ChainCell, ChainBox>,
+                         (const void*)chain_env_step_kernel<true, true, ChainRanges, ChainCell, ChainBox>,
+                         (const void*)chain_env_rollout_kernel<true, ChainCell, ChainBox>,
+                         (const void*)chain_env_step_kernel<true, false, ChainCell, ChainBox, ChainTag>,
+                         (const void*)chain_env_step_kernel<true, true, ChainRanges, ChainCell, ChainBox, ChainTag>};
     for (const void* k : ks) {
         e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, CH_MAX_DYN_LDS);
         if (e != hipSuccess) return (int)e;
@@ -796,7 +892,8 @@ extern "C" int naf_chain_env_create(const float* model_host, int n_floats, naf_c
     h->A = (int)model_host[1];
     h->n_seg = (int)model_host[2];
     h->n_pairs = (int)model_host[9];
-    h->n_cell = (int)model_host[10] + (int)model_host[11];
+    h->n_box = (int)model_host[12];
+    h->n_cell = (int)model_host[10] + (int)model_host[11] + h->n_box;
     h->lanes = 64;
     h->waves = 1;
     if (h->n_pairs > 0) {
@@ -870,6 +967,34 @@ extern "C" int naf_chain_env_reset(naf_chain_env_t* h, float* env_state, float* 
     return NAF_OK;
 }
 
+// The four workcell launches of a step. Cell: ChainCell, or ChainCell, ChainBox for a model with boxes; then the tag, if any
+template <class... Cell>
+static void ch_step_launch_cell(naf_chain_env_t* h, float* env_state, const float* actions, float* out_rows, float* obs_next, int E,
+                                int rf, uint64_t seed, const uint64_t* counter_dev, int max_frames, naf_episode_record_t* records,
+                                int record_slots, void* stream, const Cell... cell) {
+    const int A = h->A;
+    const int waves = h->scene_on ? std::min(h->waves, CH_SCENE_WAVES) : h->waves;
+    const dim3 grid_sc((E + h->lanes - 1) / h->lanes), grid((E + 63) / 64);
+    const size_t lds = ch_lds_bytes(h->n_seg, h->lanes, waves);
+    hipStream_t s = (hipStream_t)stream;
+    if (h->scene_on && h->n_pairs > 0)
+        chain_env_step_kernel<true, true, ChainRanges, Cell...><<<grid_sc, 64 * waves, lds, s>>>(
+            h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
+            record_slots, h->n_pairs, h->lanes, ch_ranges(h), cell...);
+    else if (h->scene_on)
+        chain_env_step_kernel<false, true, ChainRanges, Cell...><<<grid, 64, 0, s>>>(
+            h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
+            record_slots, 0, 64, ch_ranges(h), cell...);
+    else if (h->n_pairs > 0)
+        chain_env_step_kernel<true, false, Cell...><<<grid_sc, 64 * waves, lds, s>>>(
+            h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
+            record_slots, h->n_pairs, h->lanes, cell...);
+    else
+        chain_env_step_kernel<false, false, Cell...><<<grid, 64, 0, s>>>(
+            h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
+            record_slots, 0, 64, cell...);
+}
+
 // Tag: nothing (naf_chain_env_step: the launches are the ones they always were) or one ChainTag (naf_chain_env_step_tagged)
 template <class... Tag>
 static int ch_step_launch(naf_chain_env_t* h, float* env_state, const float* actions, float* out_rows, float* obs_next,
@@ -882,26 +1007,12 @@ static int ch_step_launch(naf_chain_env_t* h, float* env_state, const float* act
     if (rf <= 0) return NAF_ERR_ARG;
     if (h->n_cell > 0) {      // the workcell's instantiations, launched as their CELL-less counterparts below are
         if (h->scene_on && !h->scene_ready) return NAF_ERR_STATE;
-        const int waves = h->scene_on ? std::min(h->waves, CH_SCENE_WAVES) : h->waves;
-        const dim3 grid_sc((E + h->lanes - 1) / h->lanes), grid((E + 63) / 64);
-        const size_t lds = ch_lds_bytes(h->n_seg, h->lanes, waves);
-        hipStream_t s = (hipStream_t)stream;
-        if (h->scene_on && h->n_pairs > 0)
-            chain_env_step_kernel<true, true, ChainRanges, ChainCell, Tag...><<<grid_sc, 64 * waves, lds, s>>>(
-                h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
-                record_slots, h->n_pairs, h->lanes, ch_ranges(h), ChainCell{}, tag...);
-        else if (h->scene_on)
-            chain_env_step_kernel<false, true, ChainRanges, ChainCell, Tag...><<<grid, 64, 0, s>>>(
-                h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
-                record_slots, 0, 64, ch_ranges(h), ChainCell{}, tag...);
-        else if (h->n_pairs > 0)
-            chain_env_step_kernel<true, false, ChainCell, Tag...><<<grid_sc, 64 * waves, lds, s>>>(
-                h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
-                record_slots, h->n_pairs, h->lanes, ChainCell{}, tag...);
+        if (h->n_box > 0)
+            ch_step_launch_cell(h, env_state, actions, out_rows, obs_next, E, rf, seed, counter_dev, max_frames, records, record_slots,
+                                stream, ChainCell{}, ChainBox{}, tag...);
         else
-            chain_env_step_kernel<false, false, ChainCell, Tag...><<<grid, 64, 0, s>>>(
-                h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
-                record_slots, 0, 64, ChainCell{}, tag...);
+            ch_step_launch_cell(h, env_state, actions, out_rows, obs_next, E, rf, seed, counter_dev, max_frames, records, record_slots,
+                                stream, ChainCell{}, tag...);
     } else if (h->scene_on) {
         if (!h->scene_ready) return NAF_ERR_STATE;
         const int waves = std::min(h->waves, CH_SCENE_WAVES);
@@ -960,7 +1071,10 @@ extern "C" int naf_chain_env_probe(naf_chain_env_t* h, const float* env_state, f
 extern "C" int naf_chain_env_probe_cell(naf_chain_env_t* h, const float* env_state, float* out, int E, void* stream) {
     if (!h || !env_state || !out || E <= 0) return NAF_ERR_ARG;
     if (h->n_cell == 0) return NAF_ERR_STATE;
-    chain_env_probe_cell_kernel<<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(h->model_dev, env_state, out, E, h->A, h->n_seg);
+    if (h->n_box > 0)
+        chain_env_probe_cell_box_kernel<<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(h->model_dev, env_state, out, E, h->A, h->n_seg);
+    else
+        chain_env_probe_cell_kernel<<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(h->model_dev, env_state, out, E, h->A, h->n_seg);
     NAF_CHECK_LAUNCH();
     return NAF_OK;
 }
@@ -977,7 +1091,15 @@ extern "C" int naf_chain_env_reset_given(naf_chain_env_t* h, float* env_state, f
 extern "C" int naf_chain_env_rollout_step(naf_chain_env_t* h, float* env_state, const float* actions, float* obs_next, float* outcome,
                                           float* traj, int E, int max_frames, void* stream) {
     if (!h || !env_state || !actions || !obs_next || !outcome || E <= 0 || max_frames < 1) return NAF_ERR_ARG;
-    if (h->n_cell > 0 && h->n_pairs > 0)
+    if (h->n_box > 0 && h->n_pairs > 0)
+        chain_env_rollout_kernel<true, ChainCell, ChainBox><<<(E + h->lanes - 1) / h->lanes, 64 * h->waves, ch_lds_bytes(h->n_seg, h->lanes, h->waves),
+                                                         (hipStream_t)stream>>>(h->model_dev, env_state, actions, obs_next, outcome, traj, E,
+                                                                                h->A, h->n_seg, max_frames, h->n_pairs, h->lanes,
+                                                                                ChainCell{}, ChainBox{});
+    else if (h->n_box > 0)
+        chain_env_rollout_kernel<false, ChainCell, ChainBox><<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(
+            h->model_dev, env_state, actions, obs_next, outcome, traj, E, h->A, h->n_seg, max_frames, 0, 64, ChainCell{}, ChainBox{});
+    else if (h->n_cell > 0 && h->n_pairs > 0)
         chain_env_rollout_kernel<true, ChainCell><<<(E + h->lanes - 1) / h->lanes, 64 * h->waves, ch_lds_bytes(h->n_seg, h->lanes, h->waves),
                                                (hipStream_t)stream>>>(h->model_dev, env_state, actions, obs_next, outcome, traj, E,
                                                                       h->A, h->n_seg, max_frames, h->n_pairs, h->lanes,

@@ -1071,7 +1071,7 @@ class DeviceRollout:
         self.env_state = torch.zeros(self.E, self.lib.naf_chain_env_state_floats(self._chain_env), **f32)
         self.outcome = torch.zeros(self.E, 8, **f32)
         self.start = torch.zeros(self.E, 5, **f32)           # naf_chain_env_probe behind the reset
-        self.has_cell = bool(chain.cell_spheres or chain.cell_planes)
+        self.has_cell = bool(chain.cell_spheres or chain.cell_planes or chain.cell_boxes)
         self.start_cell = torch.full((self.E,), float("inf"), **f32)      # naf_chain_env_probe_cell, when the model has a workcell
         self.q0 = torch.zeros(self.E, lay.A, **f32)
         self.scene = torch.zeros(self.E, 6, **f32)

@@ -9,8 +9,8 @@ reference's rule (environment.py:311-343, :394-412) between the capsules of mode
   state  = [pos(A), vel(A), end-effector xyz, target xyz, obstacle xyz], slot k of pos / vel reporting joint INDEX k
            (environment.py:442-451)
   reward = +250 reached (dist < 0.05) | -1000 obstacle contact, self-contact or workcell contact | -(dist - 0.05), done on any
-           of them (environment.py:311-371, :416-429). The workcell — fixed spheres and half-spaces, environment/urdf_chain.py —
-           is the model's, and has no slot in the state.
+           of them (environment.py:311-371, :416-429). The workcell — fixed spheres, half-spaces and rounded oriented boxes,
+           environment/urdf_chain.py — is the model's, and has no slot in the state.
 With target_range / obstacle_range every episode gets a scene of its own: choose_scene below is the rule's float64 statement
 (include/naf_hip.h, "Scene ranges", is the kernel's).
 """
@@ -57,6 +57,39 @@ def segment_segment_distance2(a1: np.ndarray, b1: np.ndarray, a2: np.ndarray, b2
                  segment_point_distance2(a1, b1, a2), segment_point_distance2(a1, b1, b2)):
         best = np.minimum(best, cand)
     return best
+
+
+def segment_box_distance(a: np.ndarray, b: np.ndarray, half: np.ndarray):
+    """Distance between the segment a-b and the box |x_i| <= half_i, the points given in the box's frame; arrays [..., 3]
+    broadcast. 0 for a segment that touches or enters the box: the rule reports no penetration depth.
+    With p(t) = a + t (b - a), f(t) = sum_i max(|p_i(t)| - half_i, 0)^2 is convex, C1 and piecewise quadratic: f' is non-decreasing
+    and linear between its knots — 0, 1 and the up to six t in (0, 1) at which a coordinate crosses a face plane, p_i(t) = +-half_i.
+    Sorted, the knots bracket the root of f': the last one with f' <= 0 and the first with f' >= 0, between which f' is linear. f' > 0
+    at 0 puts the minimum at t = 0, f' < 0 at 1 at t = 1; a zero-length segment has f' = 0 throughout and takes t = 0."""
+    a, b, half = np.broadcast_arrays(np.asarray(a, float), np.asarray(b, float), np.asarray(half, float))
+    u = b - a
+
+    def slope(t):                                         # f'(t) / 2
+        x = a + t[..., None] * u
+        return np.sum((x - np.clip(x, -half, half)) * u, axis=-1)
+
+    with np.errstate(divide="ignore", invalid="ignore"):
+        knots = np.concatenate([(half - a) / u, (-half - a) / u], axis=-1)
+    knots = np.where(np.isfinite(knots), np.clip(knots, 0.0, 1.0), 0.0)       # (an axis the segment does not move along: no knot)
+    lead = knots.shape[:-1]
+    knots = np.sort(np.concatenate([np.zeros(lead + (1,)), knots, np.ones(lead + (1,))], axis=-1), axis=-1)
+    g = np.stack([slope(knots[..., k]) for k in range(8)], axis=-1)
+    # f' is non-decreasing along the sorted knots up to rounding: the bracket is taken by position, not by value
+    n_neg = np.sum(np.cumsum(g > 0.0, axis=-1) == 0, axis=-1)                 # knots before the first with f' > 0
+    lo, hi = np.clip(n_neg - 1, 0, 7)[..., None], np.clip(n_neg, 0, 7)[..., None]
+    t_lo, t_hi = np.take_along_axis(knots, lo, -1)[..., 0], np.take_along_axis(knots, hi, -1)[..., 0]
+    g_lo, g_hi = np.take_along_axis(g, lo, -1)[..., 0], np.take_along_axis(g, hi, -1)[..., 0]
+    den = g_hi - g_lo
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = np.where(den > 0.0, t_lo - g_lo * (t_hi - t_lo) / np.where(den > 0.0, den, 1.0), t_lo)
+    t = np.where(n_neg == 0, 0.0, np.where(n_neg == 8, 1.0, np.clip(t, t_lo, t_hi)))
+    x = a + t[..., None] * u
+    return np.sqrt(np.sum(np.maximum(np.abs(x) - half, 0.0) ** 2, axis=-1))
 
 
 SCENE_CONDITIONS = ("the target is within reach of the start pose's end effector", "the obstacle touches the arm at the start pose",
@@ -114,7 +147,8 @@ class Trace(NamedTuple):
     score: np.ndarray                 # sum of the rewards, in step order
     joint_positions: np.ndarray       # [..., frames + 1, A]: the path; a finished query repeats its final pose
     margins: np.ndarray               # [..., frames, 3]: distance - 0.05 | clearance - obstacle radius | self-clearance; NaN: no step
-    min_cell_clearance: np.ndarray    # min over the steps of the workcell clearance, +inf without a workcell
+    min_cell_clearance: np.ndarray    # min over the steps of the workcell clearance, +inf without a workcell (a capsule whose axis
+                                      # is inside a box reads -radius - r there: the box rule reports no penetration depth)
     cell_margins: np.ndarray          # [..., frames]: the workcell clearance; NaN: no step
 
 
@@ -208,16 +242,21 @@ class KinematicEnvironment:
 
     def cell_clearances(self, q: Optional[np.ndarray] = None) -> np.ndarray:
         """[pairs, ...]: clearance of every (segment, geometry) pair of model.cell_pairs — distance(segment, centre) - radius -
-        sphere radius, or min(n.a, n.b) - d - radius against a half-space; contact iff < 0."""
+        sphere radius, min(n.a, n.b) - d - radius against a half-space, or segment_box_distance in the box's frame - radius -
+        rounding radius against a box; contact iff < 0."""
         segs = self.world_segments(q)
         lead = np.shape(segs[0][0])[:-1]
-        pairs, G = self.model.cell_pairs, len(self.model.cell_spheres)
+        pairs, G, GH = self.model.cell_pairs, len(self.model.cell_spheres), len(self.model.cell_spheres) + len(self.model.cell_planes)
         out = np.empty((len(pairs),) + lead)
         for k, (s, g) in enumerate(pairs):
             a, b, r = segs[s]
             if g < G:
                 c = np.array(self.model.cell_spheres[g])
                 out[k] = np.sqrt(segment_point_distance2(a, b, c[:3])) - r - c[3]
+            elif g >= GH:
+                x = np.array(self.model.cell_boxes[g - GH])
+                R = x[3:12].reshape(3, 3)                     # its columns are the box's axes: v in the box's frame is R^T v = v @ R
+                out[k] = segment_box_distance((a - x[:3]) @ R, (b - x[:3]) @ R, x[12:15]) - r - x[15]
             else:
                 n = np.array(self.model.cell_planes[g - G])
                 out[k] = np.minimum(a @ n[:3], b @ n[:3]) - n[3] - r
@@ -336,13 +375,38 @@ class KinematicEnvironment:
 
 
 def cell_box_gaps(model: ChainModel, centre, half) -> np.ndarray:
-    """[G + H]: how near the box centre +- half (a point when half is 0) comes to each workcell geometry. Against a half-space
+    """[G + H + B]: how near the box centre +- half (a point when half is 0) comes to each workcell geometry. Against a half-space
     the box corner with the smallest n.x decides: min over the box of n.x - d = n.centre - |n|.half - d. Against a sphere: the
-    distance from its centre to the box (0 inside) minus its radius."""
+    distance from its centre to the box (0 inside) minus its radius. Against an oriented box: the closest pair of two disjoint
+    boxes has a point on an edge of one of them, so the minimum of segment_box_distance over the 12 edges of each box against the
+    other, minus the rounding radius; intersecting boxes give 0 - r."""
     centre, half = np.asarray(centre, float), np.asarray(half, float)
     out = [np.linalg.norm(np.maximum(np.abs(np.array(c[:3]) - centre) - half, 0.0)) - c[3] for c in model.cell_spheres]
     out += [float(np.dot(n[:3], centre) - np.dot(np.abs(n[:3]), half) - n[3]) for n in model.cell_planes]
+    for x in model.cell_boxes:
+        x = np.array(x)
+        c, R, h = x[:3], x[3:12].reshape(3, 3), x[12:15]
+        ea, eb = _box_edges(half)                             # the target box's edges, in its own (world-aligned) frame
+        d1 = segment_box_distance((ea + centre - c) @ R, (eb + centre - c) @ R, h)
+        ea, eb = _box_edges(h)                                # the oriented box's edges, taken to the world, about the target's centre
+        d2 = segment_box_distance(ea @ R.T + c - centre, eb @ R.T + c - centre, half)
+        out.append(float(min(d1.min(), d2.min())) - x[15])
     return np.array(out, float)
+
+
+def _box_edges(half: np.ndarray):
+    """(a[12, 3], b[12, 3]): the 12 edges of the box |x_i| <= half_i"""
+    a, b = [], []
+    for axis in range(3):
+        for s1 in (-1.0, 1.0):
+            for s2 in (-1.0, 1.0):
+                p = np.zeros(3)
+                p[(axis + 1) % 3], p[(axis + 2) % 3] = s1 * half[(axis + 1) % 3], s2 * half[(axis + 2) % 3]
+                lo, hi = p.copy(), p.copy()
+                lo[axis], hi[axis] = -half[axis], half[axis]
+                a.append(lo)
+                b.append(hi)
+    return np.array(a), np.array(b)
 
 
 def reach_queries(model: ChainModel, targets, obstacles, initial_joint_positions, frames, nominal_obstacle=None, nominal_start=None):
@@ -395,10 +459,11 @@ def build_kinematic(manipulator_file, endeffector_index, fixed_joints, involved_
                     initial_joint_positions=None, initial_positions_variation_range=None, link_radius=0.0,
                     obstacle_radius=OBSTACLE_RADIUS, consider_autocollision=False, autocollision_ignore=None, *, target_range=None,
                     obstacle_range=None, scene_margin=0.02, floor_height=None, workcell_planes=None, workcell_spheres=None,
-                    cell_ignore=None) -> KinematicEnvironment:
+                    cell_ignore=None, workcell_boxes=None) -> KinematicEnvironment:
     """Picklable factory (HostVectorEnv's worker processes call it through functools.partial)."""
     model = compile_chain(load_urdf(manipulator_file), endeffector_index, involved_joints, fixed_joints,
                           initial_joint_positions, initial_positions_variation_range, link_radius, consider_autocollision,
-                          autocollision_ignore or (), floor_height, workcell_planes, workcell_spheres, cell_ignore or ())
+                          autocollision_ignore or (), floor_height, workcell_planes, workcell_spheres, cell_ignore or (),
+                          workcell_boxes)
     return KinematicEnvironment(model, target_position, obstacle_position, obstacle_radius, target_range, obstacle_range,
                                 scene_margin)

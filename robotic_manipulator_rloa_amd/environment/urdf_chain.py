@@ -13,11 +13,14 @@ the links' capsules, off by default (compile_chain(consider_autocollision=True),
              transform between the two (joint origins, constant joints), folded here.
   segments   collision capsules, each in the frame of the last driven joint above it.
   slots      observation slot k of the A position / velocity slots reports joint INDEX k (environment.py:442-444).
-  workcell   fixed geometry of the cell the arm stands in, the same in every episode: up to MAX_CELL spheres (cx, cy, cz, r) and
-             half-spaces (nx, ny, nz, d), n a unit vector, the free side n.x - d >= 0. Clearance of a capsule (world end points
-             a, b, radius rho): distance(segment ab, c) - rho - r against a sphere, min(n.a, n.b) - d - rho against a half-space;
-             contact when < 0, for the (capsule, geometry) pairs the model tests: reward -1000 and done, as obstacle contact.
-             Geometry index g counts the spheres first, then the half-spaces. Off unless compile_chain is given some.
+  workcell   fixed geometry of the cell the arm stands in, the same in every episode: up to MAX_CELL spheres (cx, cy, cz, r),
+             half-spaces (nx, ny, nz, d), n a unit vector, the free side n.x - d >= 0, and rounded oriented boxes (centre c, half
+             extents h >= 0, orientation R, rounding radius r >= 0). Clearance of a capsule (world end points a, b, radius rho):
+             distance(segment ab, c) - rho - r against a sphere, min(n.a, n.b) - d - rho against a half-space, distance(segment
+             ab, box) - rho - r against a box (kinematic.segment_box_distance in the box's frame; 0 for a segment that enters
+             the box: no penetration depth); contact when < 0, for the (capsule, geometry) pairs the model tests: reward -1000
+             and done, as obstacle contact. Geometry index g counts the spheres first, then the half-spaces, then the boxes.
+             Off unless compile_chain is given some.
   self pairs segment pairs (s, t), s < t, tested against each other when consider_autocollision is on: the reference tests
              link i against link j for i, j in 0 .. num_joints - 1 with |i - j| <= 1 left out, contact when the closest distance
              is below 0 (environment.py:311-343, :394-412; collision_detector.py:63-98). The root link (index -1) takes no part.
@@ -43,8 +46,9 @@ JOINT_FLOATS = 24
 SEGMENT_FLOATS = 8
 SLOT_FLOATS = 2
 PAIR_FLOATS = 2
-CELL_FLOATS = 4                  # per workcell geometry; behind them one mask float per segment
-MAX_CELL = 16                    # include/naf_hip.h NAF_CHAIN_MAX_CELL: spheres + half-spaces
+CELL_FLOATS = 4                  # per workcell sphere / half-space
+BOX_FLOATS = 16                  # per workcell box, behind them: c (3) | R row-major (9) | h (3) | r; then one mask float per segment
+MAX_CELL = 16                    # include/naf_hip.h NAF_CHAIN_MAX_CELL: spheres + half-spaces + boxes
 MAX_JOINTS = 64
 DT = 1.0 / 240.0                 # environment.py:481: one stepSimulation tick
 TARGET_THRESHOLD = 0.05          # environment.py:345-371
@@ -222,6 +226,7 @@ class ChainModel:
     self_pairs_dropped: List[tuple] = field(default_factory=list)    # (link name, link name) of the pairs the pose sample pruned
     cell_spheres: List[tuple] = field(default_factory=list)          # (cx, cy, cz, r): geometry 0 .. G - 1
     cell_planes: List[tuple] = field(default_factory=list)           # (nx, ny, nz, d), |n| = 1, free side n.x - d >= 0: geometry G ..
+    cell_boxes: List[tuple] = field(default_factory=list)            # 16 floats: c | R row-major | h | r: geometry G + H ..
     cell_masks: List[int] = field(default_factory=list)              # per segment: bit g set = tested against geometry g
     cell_pairs_dropped: List[tuple] = field(default_factory=list)    # (link name, geometry index) of the pairs the pose sample pruned
     _blob: Optional[np.ndarray] = field(default=None, repr=False, compare=False)
@@ -240,10 +245,13 @@ class ChainModel:
         return [int(np.searchsorted(frames, f, side="left")) for f in range(self.A + 2)]
 
     @property
+    def n_cell(self) -> int:
+        return len(self.cell_spheres) + len(self.cell_planes) + len(self.cell_boxes)
+
+    @property
     def cell_pairs(self) -> List[tuple]:
         """(segment, geometry) pairs the workcell rule tests, segment-major."""
-        return [(s, g) for s, mask in enumerate(self.cell_masks) for g in range(len(self.cell_spheres) + len(self.cell_planes))
-                if mask >> g & 1]
+        return [(s, g) for s, mask in enumerate(self.cell_masks) for g in range(self.n_cell) if mask >> g & 1]
 
     def pack(self) -> np.ndarray:
         """The flat float32 blob csrc/chain_env.hip reads (layout: include/naf_hip.h, "chain model blob")."""
@@ -251,10 +259,10 @@ class ChainModel:
             return self._blob.copy()
         A, n_seg, n_pairs = self.A, len(self.segments), len(self.self_pairs)
         head = np.zeros(HEADER_FLOATS)
-        G, H = len(self.cell_spheres), len(self.cell_planes)
+        G, H, B = len(self.cell_spheres), len(self.cell_planes), len(self.cell_boxes)
         n = HEADER_FLOATS + JOINT_FLOATS * A + (A + 2) + SEGMENT_FLOATS * n_seg + SLOT_FLOATS * A + PAIR_FLOATS * n_pairs
-        n += CELL_FLOATS * (G + H) + (n_seg if G + H else 0)          # (no workcell: the blob ends where it always did)
-        head[:12] = [BLOB_VERSION, A, n_seg, A, self.ee_frame, *self.ee_point, n, n_pairs, G, H]
+        n += CELL_FLOATS * (G + H) + BOX_FLOATS * B + (n_seg if G + H + B else 0)      # (no workcell: the blob ends where it always did)
+        head[:13] = [BLOB_VERSION, A, n_seg, A, self.ee_frame, *self.ee_point, n, n_pairs, G, H, B]
         parts = [head]
         for j in self.joints:
             rec = np.zeros(JOINT_FLOATS)
@@ -268,9 +276,9 @@ class ChainModel:
             parts.append(np.array([src, const]))
         for pair in self.self_pairs:                                  # (none: the blob is byte for byte the one without the table)
             parts.append(np.array(pair, float))
-        for geom in list(self.cell_spheres) + list(self.cell_planes):
+        for geom in list(self.cell_spheres) + list(self.cell_planes) + list(self.cell_boxes):
             parts.append(np.array(geom, float))
-        if G + H:
+        if G + H + B:
             parts.append(np.array(self.cell_masks, float))
         self._blob = np.concatenate(parts).astype(np.float32)
         assert self._blob.size == n
@@ -289,9 +297,11 @@ def compile_chain(urdf: Urdf, endeffector_index: int, involved_joints: Sequence[
                   initial_positions_variation_range: Optional[Sequence[float]] = None, link_radius: float = 0.0,
                   consider_autocollision: bool = False, autocollision_ignore: Sequence = (), floor_height: Optional[float] = None,
                   workcell_planes: Optional[Sequence] = None, workcell_spheres: Optional[Sequence] = None,
-                  cell_ignore: Sequence = ()) -> ChainModel:
+                  cell_ignore: Sequence = (), workcell_boxes: Optional[Sequence] = None) -> ChainModel:
     """floor_height z0 (sugar for the half-space (0, 0, 1, z0), the first one), workcell_planes [(nx, ny, nz, d)],
-    workcell_spheres [(cx, cy, cz, r)]: the workcell (module text). The model tests every (capsule, geometry) pair except those
+    workcell_spheres [(cx, cy, cz, r)], workcell_boxes [(cx, cy, cz, hx, hy, hz)], [(.., roll, pitch, yaw)] or [(.., roll, pitch,
+    yaw, r)] (half extents; the angles in rpy_matrix's convention; r the rounding radius — zero half extents with r > 0 give a
+    fixed capsule or a rounded plate): the workcell (module text). The model tests every (capsule, geometry) pair except those
     the fixed pose sample finds in contact at every pose (listed in cell_pairs_dropped: the base standing on the floor) and
     those of cell_ignore: (link, geometry index) entries, the link by name or by PyBullet link index.
     consider_autocollision: the model carries self_pairs (module text) minus the pairs that the fixed pose sample finds in
@@ -401,8 +411,8 @@ def compile_chain(urdf: Urdf, endeffector_index: int, involved_joints: Sequence[
         model.consider_autocollision = True
         _self_pairs(model, urdf, autocollision_ignore)
     planes = ([] if floor_height is None else [(0.0, 0.0, 1.0, floor_height)]) + list(workcell_planes or ())
-    if planes or workcell_spheres or cell_ignore:
-        _workcell(model, urdf, list(workcell_spheres or ()), planes, cell_ignore)
+    if planes or workcell_spheres or workcell_boxes or cell_ignore:
+        _workcell(model, urdf, list(workcell_spheres or ()), planes, cell_ignore, list(workcell_boxes or ()))
     return model
 
 
@@ -414,8 +424,13 @@ def _prune_poses(model: ChainModel) -> np.ndarray:
 
 
 def cell_geometry_name(model: ChainModel, g: int) -> str:
-    """'workcell sphere 1 (centre ..., radius ...)' / 'workcell plane 0 (normal ..., offset ...)' of geometry index g."""
-    G = len(model.cell_spheres)
+    """'workcell sphere 1 (centre ..., radius ...)' / 'workcell plane 0 (normal ..., offset ...)' / 'workcell box 0 (centre ...,
+    half extents ..., radius ...)' of geometry index g."""
+    G, H = len(model.cell_spheres), len(model.cell_planes)
+    if g >= G + H:
+        b = model.cell_boxes[g - G - H]
+        return (f"workcell box {g - G - H} (centre {b[0]:.4g} {b[1]:.4g} {b[2]:.4g}, half extents {b[12]:.4g} {b[13]:.4g} {b[14]:.4g}, "
+                f"radius {b[15]:.4g})")
     if g < G:
         c = model.cell_spheres[g]
         return f"workcell sphere {g} (centre {c[0]:.4g} {c[1]:.4g} {c[2]:.4g}, radius {c[3]:.4g})"
@@ -423,25 +438,37 @@ def cell_geometry_name(model: ChainModel, g: int) -> str:
     return f"workcell plane {g - G} (normal {n[0]:.4g} {n[1]:.4g} {n[2]:.4g}, offset {n[3]:.4g})"
 
 
-def _workcell(model: ChainModel, urdf: Urdf, spheres: list, planes: list, ignore: Sequence) -> None:
-    """Fills model.cell_spheres / cell_planes / cell_masks / cell_pairs_dropped: the geometry checked, every pair, the hand-made
-    exceptions, then the pruning. A geometry that is left with no tested pair is refused."""
+def _workcell(model: ChainModel, urdf: Urdf, spheres: list, planes: list, ignore: Sequence, boxes: Sequence = ()) -> None:
+    """Fills model.cell_spheres / cell_planes / cell_boxes / cell_masks / cell_pairs_dropped: the geometry checked, every pair, the
+    hand-made exceptions, then the pruning. A geometry that is left with no tested pair is refused."""
     path, segs = urdf.path, model.segments
 
-    def numbers(v, what):
+    def numbers(v, what, lengths=(4,), said="four finite numbers"):
         try:
             out = tuple(float(x) for x in v)
         except (TypeError, ValueError):
             out = ()
-        if len(out) != 4 or not all(math.isfinite(x) for x in out):
-            raise InvalidManipulatorFile(f"{path}: {what} {v!r} is not four finite numbers")
+        if len(out) not in lengths or not all(math.isfinite(x) for x in out):
+            raise InvalidManipulatorFile(f"{path}: {what} {v!r} is not {said}")
         return out
+
+    def box_record(v):
+        """c (3) | R row-major (9) | h (3) | r of an entry of 6, 9 or 10 numbers"""
+        b = numbers(v, "workcell box (cx, cy, cz, hx, hy, hz[, roll, pitch, yaw[, r]])", (6, 9, 10), "6, 9 or 10 finite numbers")
+        R = rpy_matrix(b[6:9]) if len(b) >= 9 else np.eye(3)
+        return b[:3] + tuple(float(x) for x in R.reshape(9)) + b[3:6] + (b[9] if len(b) == 10 else 0.0,)
 
     model.cell_spheres = [numbers(c, "workcell sphere (cx, cy, cz, r)") for c in spheres]
     model.cell_planes = [numbers(n, "workcell plane (nx, ny, nz, d)") for n in planes]
-    G, n_geom = len(spheres), len(spheres) + len(planes)
+    model.cell_boxes = [box_record(b) for b in boxes]
+    G, n_geom = len(spheres), len(spheres) + len(planes) + len(boxes)
     if n_geom > MAX_CELL:
         raise InvalidManipulatorFile(f"{path}: {n_geom} workcell geometries; a chain model holds at most {MAX_CELL}")
+    for k, b in enumerate(model.cell_boxes):
+        if min(b[12:15]) < 0.0:
+            raise InvalidManipulatorFile(f"{path}: {cell_geometry_name(model, n_geom - len(boxes) + k)} has a negative half extent")
+        if b[15] < 0.0:
+            raise InvalidManipulatorFile(f"{path}: {cell_geometry_name(model, n_geom - len(boxes) + k)} has a negative radius")
     for g, c in enumerate(model.cell_spheres):
         if c[3] < 0.0:
             raise InvalidManipulatorFile(f"{path}: {cell_geometry_name(model, g)} has a negative radius")
@@ -463,7 +490,7 @@ def _workcell(model: ChainModel, urdf: Urdf, spheres: list, planes: list, ignore
             raise InvalidManipulatorFile(f"{path}: cell_ignore names the link {link!r}, which carries no capsule")
         if isinstance(g, bool) or not isinstance(g, (int, np.integer)) or not 0 <= int(g) < n_geom:
             raise InvalidManipulatorFile(f"{path}: cell_ignore names workcell geometry {g!r}; the workcell has geometries 0 .. "
-                                         f"{n_geom - 1} (spheres first)")
+                                         f"{n_geom - 1} (spheres first" + (", boxes last" if boxes else "") + ")")
         ignored.add((link, int(g)))
     model.cell_masks = [sum(1 << g for g in range(n_geom) if (s.link_name, g) not in ignored) for s in segs]
     pairs = model.cell_pairs

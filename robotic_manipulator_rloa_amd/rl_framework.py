@@ -344,7 +344,8 @@ class ManipulatorFramework:
                                          autocollision_ignore: Optional[list] = None, target_range: Optional[List[float]] = None,
                                          obstacle_range: Optional[List[float]] = None, scene_margin: float = 0.02,
                                          floor_height: Optional[float] = None, workcell_planes: Optional[list] = None,
-                                         workcell_spheres: Optional[list] = None, cell_ignore: Optional[list] = None) -> None:
+                                         workcell_spheres: Optional[list] = None, cell_ignore: Optional[list] = None,
+                                         workcell_boxes: Optional[list] = None) -> None:
         """initialize_environment()'s arguments (rl_framework.py:369-417) for the built-in kinematic environment: the arm of
         `manipulator_file` (a URDF) as a serial chain under the reference's environment rule, velocity control applied exactly.
         Not a Bullet port — no dynamics (max_force is accepted and ignored), no mesh collision (links are capsules of their
@@ -368,7 +369,13 @@ class ManipulatorFramework:
         geometry indices count the spheres first, then the floor, then workcell_planes. Refused here: a start pose in
         workcell contact, a target (or, with target_range, a point of its box) within 0.05 (+ scene_margin) of a geometry,
         and initial_positions_variation_range under which more than half of 1024 sampled episode starts are in workcell
-        contact. PyBullet and the stand-in environment have no workcell."""
+        contact. PyBullet and the stand-in environment have no workcell.
+        workcell_boxes: rounded oriented boxes among those 16 — the table top with its edge, a shelf, a post — each
+        [cx, cy, cz, hx, hy, hz] (centre and half extents), [.., roll, pitch, yaw] (the URDF convention of a joint origin's rpy)
+        or [.., roll, pitch, yaw, r] with a rounding radius r: zero half extents and r > 0 give a fixed capsule or a rounded
+        plate. Clearance of a capsule: distance(its axis, box) - its radius - r; an axis that enters the box is at distance 0,
+        so min_cell_clearance of reach_targets reads -(radius + r) there: no penetration depth is reported. Geometry indices
+        count the boxes last. The same refusals hold for boxes."""
         if visualize:
             raise InvalidManipulatorFile('the kinematic environment has no visualisation: pass visualize=False '
                                          '(initialize_environment() opens the PyBullet GUI)')
@@ -400,12 +407,20 @@ class ManipulatorFramework:
                 raise InvalidEnvironmentParameter(f'{label} received is not a list of four-number entries')
             if not all(isinstance(v, (int, float)) and not isinstance(v, bool) and np.isfinite(v) for g in geoms for v in g):
                 raise InvalidEnvironmentParameter(f'An item inside the {label} list is not a finite number')
+        if workcell_boxes is not None:
+            if not isinstance(workcell_boxes, (list, tuple)) or not all(isinstance(g, (list, tuple)) and len(g) in (6, 9, 10)
+                                                                        for g in workcell_boxes):
+                raise InvalidEnvironmentParameter('Workcell boxes received is not a list of entries of 6, 9 or 10 numbers')
+            if not all(isinstance(v, (int, float)) and not isinstance(v, bool) and np.isfinite(v) for g in workcell_boxes for v in g):
+                raise InvalidEnvironmentParameter('An item inside the Workcell boxes list is not a finite number')
         scene_kw = dict(target_range=None if target_range is None else [float(v) for v in target_range],
                         obstacle_range=None if obstacle_range is None else [float(v) for v in obstacle_range],
                         scene_margin=float(scene_margin), floor_height=None if floor_height is None else float(floor_height),
                         workcell_planes=None if workcell_planes is None else [tuple(float(v) for v in g) for g in workcell_planes],
                         workcell_spheres=None if workcell_spheres is None else [tuple(float(v) for v in g) for g in workcell_spheres],
                         cell_ignore=None if cell_ignore is None else [tuple(p) for p in cell_ignore])
+        if workcell_boxes:      # (a box-free call keeps the factory's arguments it always had)
+            scene_kw['workcell_boxes'] = [tuple(float(v) for v in g) for g in workcell_boxes]
         env = build_kinematic(*args, **scene_kw)
         if env.model.cell_pairs:
             self._check_workcell(env, manipulator_file)
@@ -456,7 +471,8 @@ class ManipulatorFramework:
             raise ValueError(f'{manipulator_file}: {touching} of {SCENE_CHECK_CASES} sampled episode starts (initial joint positions '
                              f'+- initial_positions_variation_range) are in workcell contact and would end at their first step: '
                              f'narrow the variation range, choose another start pose or move the geometry')
-        logger.info(f'Workcell: {len(model.cell_spheres)} spheres, {len(model.cell_planes)} half-spaces, {len(pairs)} tested pairs; '
+        boxes = f', {len(model.cell_boxes)} boxes' if model.cell_boxes else ''
+        logger.info(f'Workcell: {len(model.cell_spheres)} spheres, {len(model.cell_planes)} half-spaces{boxes}, {len(pairs)} tested pairs; '
                     f'{100.0 * touching / SCENE_CHECK_CASES:.1f}% of {SCENE_CHECK_CASES} sampled episode starts are in workcell '
                     f'contact')
 

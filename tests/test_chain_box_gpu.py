@@ -1,0 +1,385 @@
+"""GPU (`-m gpu`): the box instantiations of csrc/chain_env.hip — naf_chain_env_probe_cell, the rollout step and the training step in
+workcells of rounded oriented boxes — against the float64 twin (environment/kinematic.py) through the C ABI, the masks, a cell of
+all three kinds, that nothing changes without a box, graph capture, and the kinematic environment with boxes end to end."""
+import dataclasses
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import chain_box_common as X
+import chain_cell_common as K
+import chain_rollout_common as C
+from test_chain_cell_gpu import RANGES, CellRig, _graph_of, bits
+from test_chain_env_cpu import ARMS as ARM_TABLE
+from test_chain_env_cpu import model_of, path
+
+from robotic_manipulator_rloa_amd.environment.kinematic import KinematicEnvironment
+from robotic_manipulator_rloa_amd.environment.urdf_chain import DT
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+F = X.FRAMES
+
+
+@pytest.fixture()
+def scratch_cwd(tmp_path):
+    old = os.getcwd()
+    os.chdir(tmp_path)
+    yield tmp_path
+    os.chdir(old)
+
+
+class BoxRig(CellRig):
+    """CellRig whose training step may go through naf_chain_env_step_tagged"""
+
+    def __init__(self, *args, tagged=False, **kw):
+        super().__init__(*args, **kw)
+        self.tagged = tagged
+
+    def launch_step(self, max_frames=0):
+        fn = self.lib.naf_chain_env_step_tagged if self.tagged else self.lib.naf_chain_env_step
+        assert fn(self.h, self.st.data_ptr(), self.act.data_ptr(), self.rows.data_ptr(), self.obs.data_ptr(), self.E, self.seed,
+                  self.ctr.data_ptr(), max_frames, self.recs.data_ptr() if self.recs is not None else None, self.K, self.stream) == 0
+        assert self.lib.naf_counter_add(self.ctr.data_ptr(), 1, self.stream) == 0
+
+
+def _probe_and_one_rollout_step(model, q, frames=3):
+    """(rc, probe_cell[n], outcome[n, 8]) of the poses q with target and obstacle out of the way and zero actions"""
+    n = len(q)
+    far_t, far_o = C.away(model)
+    rig = CellRig(model, n, frames=frames)
+    rig.reset_given(q, np.tile(far_t, (n, 1)), np.tile(far_o, (n, 1)))
+    rc, probe = rig.probe_cell()
+    rig.load_actions(np.zeros((n, model.A)))
+    rig.launch_rollout()
+    out = rig.out.cpu().numpy()
+    rig.close()
+    return rc, probe, out
+
+
+# ---- (1) probe_cell ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", X.ARMS)
+def test_probe_cell_against_twin(name):
+    """256 uniform poses per arm among its boxes: within 2 tol of cell_clearance — the band of the workcell tests, one walk's error
+    in each end point; the box arithmetic (nine products into the box's frame, the knot form) added 1.8e-7 m at unit scale in a
+    float32 trial of the rule — and the sign equal outside |clearance| <= 2 tol (at most 1 % of the poses inside)."""
+    model, twin = X.arm(name)
+    q = X.uniform_poses(name)
+    n, tol = len(q), X.tol_of(model)
+    far_t, far_o = C.away(model)
+    rig = CellRig(model, n)
+    rig.reset_given(q, np.tile(far_t, (n, 1)), np.tile(far_o, (n, 1)))
+    rc, got = rig.probe_cell()
+    assert rig.lib.naf_chain_env_probe_cell(rig.h, rig.st.data_ptr(), None, n, rig.stream) == -1
+    rig.close()
+    assert rc == 0
+    want = twin.cell_clearance(q)
+    err = np.abs(got - want)
+    inside = np.abs(want) <= 2 * tol
+    print(f"{name}: worst error {err.max():.2e} (2 tol = {2 * tol:.2e}), {int(inside.sum())} of {n} inside the band, "
+          f"{int(np.sum(want < 0))} in contact")
+    assert err.max() <= 2 * tol, (err.max(), tol)
+    assert inside.sum() <= 0.01 * n and np.array_equal((got < 0)[~inside], (want < 0)[~inside])
+    assert np.sum(want < 0) >= 8
+
+
+# ---- (2) rollout -------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("E", X.SIZES)
+@pytest.mark.parametrize("name", X.ARMS)
+def test_rollout_kernel_against_twin(name, E):
+    """reset_given + 40 rollout steps with the case's scripted actions; the twin is evaluated at the RECORDED joint values
+    (teacher-forced). Code and frames equal, except that an env is skipped from its first step inside the band
+    (chain_cell_common.band4; at most CAP of the (env, step) pairs, at least FLOOR envs per outcome compared to their end when
+    E >= 64); outcome[6] within 2 tol of the minimum of the twin's workcell clearance over the same poses."""
+    case = X.build_case(name, E)
+    model, A, tol = case.model, case.model.A, X.tol_of(case.model)
+    rig = CellRig(model, E)
+    rig.reset_given(case.q0, case.target, case.obstacle)
+    st0 = rig.st.cpu().numpy()
+    for t in range(F):
+        rig.load_actions(case.act[:, t])
+        rig.launch_rollout()
+    out, traj, st = rig.out.cpu().numpy(), rig.traj.cpu().numpy(), rig.st.cpu().numpy()
+    rig.close()
+    traj[0] = st0[:, :A]
+    code, fd = out[:, 0].astype(np.int64), out[:, 1].astype(np.int64)
+    assert np.all((fd >= 1) & (fd <= F)) and np.all(np.isin(code, (0, 1, 2, 3, 4))) and np.all(out[:, 7] == 0.0)
+    assert np.all(st[:, A + 8] == 1.0) and np.all((code > 0) | (fd == F))
+    filled = np.take_along_axis(traj, np.minimum(np.arange(F + 1)[:, None], fd[None, :])[:, :, None], axis=0)
+    margins = X.teacher_forced(case, filled)                              # [E, F, 4]
+    stepped = np.arange(F)[None, :] < fd[:, None]
+    band = X.band4(margins, tol) & stepped
+    first = np.where(band.any(axis=1), band.argmax(axis=1), F)
+    worst = 0.0
+    for e in range(E):
+        n = int(fd[e])
+        m = margins[e, :n]
+        upto = min(n, int(first[e]))
+        assert np.all(m[:min(upto, n - 1)] >= 0.0), (e, "the device went on where the twin ends", m[:upto].min(axis=0))
+        if first[e] < n:
+            continue
+        tw_code, tw_frames = X.outcome_from_margins(m[None])
+        assert (int(tw_code[0]), int(tw_frames[0])) == (int(code[e]), n) or (tw_code[0] == 0 and code[e] == 0 and n == F), \
+            (e, int(tw_code[0]), int(tw_frames[0]), int(code[e]), n, m[-1])
+        err = abs(out[e, 6] - m[:, 3].min())
+        worst = max(worst, err)
+        assert err <= 2 * tol and abs(out[e, 3] - m[:, 1].min()) <= 2 * tol, (e, out[e, 6], m[:, 3].min(), tol)
+        if code[e] == 4:
+            assert out[e, 6] < 0.0 and out[e, 5] <= -1000.0 + n
+    print(f"{name} E={E}: worst outcome[6] error {worst:.2e} (2 tol = {2 * tol:.2e})")
+    X.census(case, code, fd, band)
+
+
+def test_precedence_on_the_device():
+    """One step at which several endings hold together (iiwa_like7 with self-collision above a slab): poses in self-contact — all of
+    which reach into the slab — give 3; with the obstacle on a capsule, 2; with the target on the end effector, 1; a pose in the slab
+    that touches neither itself nor the obstacle, 4."""
+    model, twin = X.slab()
+    rng = np.random.default_rng(5)
+    both = C.contact_poses(model, twin, rng, 400)
+    both = C.f32(both[(twin.self_clearance(both) < -0.005) & (twin.cell_clearance(both) < -0.005)][:12])
+    slab = X.uniform_poses("iiwa_like7", 2048, seed=78)
+    slab = slab[(twin.cell_clearance(slab) < -0.005) & (twin.self_clearance(slab) > 0.005)][:4]
+    assert len(both) == 12 and len(slab) == 4
+    q = np.concatenate([both, slab])
+    n = len(q)
+    want = np.array([1, 2, 3] * 4 + [4] * 4)
+    far_t, far_o = C.away(model)
+    target = np.where((want == 1)[:, None], twin.end_effector(q), far_t)
+    obstacle = np.where(((want == 2) | ((want == 1) & (np.arange(n) % 6 == 0)))[:, None], twin.world_segments(q)[3][0] + np.zeros((n, 3)), far_o)
+    rig = CellRig(model, n, frames=5)
+    rig.reset_given(q, target, obstacle)
+    rig.load_actions(np.zeros((n, model.A)))
+    rig.launch_rollout()
+    out = rig.out.cpu().numpy()
+    rig.close()
+    assert np.array_equal(out[:, 0], want) and np.all(out[:, 1] == 1.0)
+    assert np.array_equal(out[:, 5], np.where(want == 1, 250.0, -1000.0)) and np.all(out[:, 6] < -0.004)
+
+
+# ---- (3) training step -------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,ranged,tagged", [("planar3", False, False), ("planar3", True, False), ("iiwa_like7", False, False),
+                                                ("iiwa_like7", True, False), ("iiwa_like7", True, True)])
+def test_step_kernel_against_twin(name, ranged, tagged):
+    """The four SC x SCENE instantiations (self-collision pairs: iiwa_like7; scene ranges: `ranged`) and one tagged one. E = 100 envs
+    are put on the case's start poses and scenes by writing env_state, then stepped 40 times with the case's actions, records on.
+    Every row's reward and done are held to the twin's rule at the pose the row was stepped to (float64 from the device's own
+    previous joint values), outside the band; a row that ends in box contact alone carries -1000 / 1, its env starts a new episode
+    (frame 0, one more episode finished, joints back inside the reset range) and its episode record says so; a tagged row's last
+    float is its record's episode."""
+    E = 100
+    case = X.build_case(name, E)
+    model, twin, A, tol = case.model, case.twin, case.model.A, X.tol_of(case.model)
+    lo = np.array([j.lower if j.limited else -np.inf for j in model.joints])
+    hi = np.array([j.upper if j.limited else np.inf for j in model.joints])
+    init, var = np.array([j.init for j in model.joints]), np.array([j.variation for j in model.joints])
+    rig = BoxRig(model, E, ranges=RANGES if ranged else None, record_slots=4, tagged=tagged)
+    rig.reset(np.array([0.3, 0.2, 0.4]), np.array([3.0, 3.0, 3.0]))
+    st = rig.st.cpu().numpy()
+    st[:, :A] = case.q0
+    st[:, A:A + 3], st[:, A + 3:A + 6] = case.target, case.obstacle
+    rig.st.copy_(torch.from_numpy(st))
+    steps = skipped = cell_ends = 0
+    for t in range(F):
+        prev = rig.st.cpu().numpy()
+        rig.load_actions(case.act[:, t])
+        rig.launch_step()
+        row, now, recs = rig.rows.cpu().numpy(), rig.st.cpu().numpy(), rig.recs.cpu().numpy()
+        q = np.clip(prev[:, :A].astype(np.float64) + DT * case.act[:, t], lo, hi)
+        m = X.margins4(twin, q, prev[:, A:A + 3].astype(np.float64), prev[:, A + 3:A + 6].astype(np.float64))
+        band = X.band4(m, tol)
+        reward, done = row[:, rig.off_r], row[:, rig.off_d]
+        rec = recs[t % 4]
+        assert np.array_equal(row[:, -1], rec[:, 5].astype(np.float32) if tagged else np.zeros(E, np.float32))
+        for e in range(E):
+            steps += 1
+            if band[e]:
+                skipped += 1
+                continue
+            ends = m[e] < 0.0
+            want = 250.0 if ends[0] else (-1000.0 if ends[1:].any() else None)
+            assert done[e] == float(want is not None), (t, e, m[e], reward[e], done[e])
+            if want is None:
+                assert abs(reward[e] + m[e, 0]) <= tol and now[e, A + 7] == prev[e, A + 7] + 1 and now[e, A + 8] == prev[e, A + 8]
+                continue
+            assert reward[e] == want, (t, e, m[e], reward[e])
+            assert now[e, A + 7] == 0.0 and now[e, A + 8] == prev[e, A + 8] + 1
+            assert np.all(np.abs(now[e, :A] - init) <= var + 1e-6)
+            assert rec[e, 3] == 1 and rec[e, 2] == int(prev[e, A + 7]) + 1 and rec[e, 5] == int(now[e, A + 8])
+            assert rec[e, 4:5].view(np.float32)[0] == want
+            cell_ends += int(ends[3] and not ends[:3].any())
+    rig.close()
+    print(f"{name} ranged={ranged} tagged={tagged}: {steps} rows, {skipped} inside the band, {cell_ends} ended by box contact alone")
+    assert skipped <= X.CAP * steps and cell_ends >= X.FLOOR
+
+
+# ---- (4) masks, sixteen geometries, all three kinds -----------------------------------------------------------------------------------
+def test_a_cleared_bit_takes_the_box_out():
+    """iiwa_like7 with a capsule 2 cm and more inside its table top; in the blob the table's bit is cleared on every capsule that
+    comes within 1 cm of it at any of the poses. No episode ends on it, and the clearance is that of the pairs left."""
+    model, twin = X.arm("iiwa_like7")
+    q = X.uniform_poses("iiwa_like7", 4096, seed=79)
+    pairs_all = twin.cell_clearances(q)                                     # [pairs, n]
+    table = np.array([g == 0 for _, g in model.cell_pairs])
+    q = q[(pairs_all[table].min(axis=0) < -0.02) & (twin.self_clearance(q) > 0.01)][:64]
+    n = len(q)
+    assert n == 64
+    pairs = twin.cell_clearances(q)
+    near = {s for k, (s, g) in enumerate(model.cell_pairs) if g == 0 and pairs[k].min() < 0.01}
+    cut = dataclasses.replace(model, cell_masks=[m & ~1 if s in near else m for s, m in enumerate(model.cell_masks)], _blob=None)
+    assert 0 < len(near) and cut.cell_masks != model.cell_masks
+    want = KinematicEnvironment(cut, (0, 0, 0), (0, 0, 0)).cell_clearance(q)
+    keep = want > 0.01                                                      # (poses that touch the shelf or the post besides are left out)
+    assert keep.sum() >= 32
+    (rc_a, probe_a, out_a), (rc_b, probe_b, out_b) = _probe_and_one_rollout_step(model, q), _probe_and_one_rollout_step(cut, q)
+    assert rc_a == 0 and rc_b == 0
+    assert np.all(out_a[:, 0] == 4) and np.all(probe_a < -0.019)
+    assert np.all(out_b[keep, 0] == 0) and np.all(out_b[keep, 1] == 1)
+    tol = X.tol_of(model)
+    assert np.abs(probe_b - want)[keep].max() <= 2 * tol and np.abs(out_b[:, 6] - want)[keep].max() <= 2 * tol
+
+
+def test_sixteen_geometries_and_a_box_at_bit_15():
+    """14 spheres and a wall out of reach and the table top as geometry 15: every mask is 65535, and the table still ends the
+    episode of a pose that reaches into it — and of no other."""
+    model, twin = X.sixteen()
+    assert (len(model.cell_spheres), len(model.cell_planes), len(model.cell_boxes)) == (14, 1, 1)
+    assert model.cell_masks == [65535] * len(model.segments)
+    q = X.uniform_poses("iiwa_like7", 2048, seed=80)
+    c = twin.cell_clearance(q)
+    inside, outside = q[c < -0.01][:32], q[c > 0.01][:32]
+    q = np.concatenate([inside, outside])
+    assert len(inside) == 32 and len(outside) == 32
+    rc, probe, out = _probe_and_one_rollout_step(model, q)
+    assert rc == 0 and np.abs(probe - twin.cell_clearance(q)).max() <= 2 * X.tol_of(model)
+    assert np.array_equal(out[:, 0], [4.0] * 32 + [0.0] * 32)
+
+
+def test_a_cell_of_all_three_kinds():
+    """iiwa_like7 among a sphere, a floor and three boxes: poses whose nearest geometry is each of the five in turn, in contact by
+    1 cm and more, and free poses; the probe and outcome[6] are the twin's minimum over all five, and only the poses in contact end."""
+    model, twin = X.mixed()
+    q = X.uniform_poses("iiwa_like7", 2048, seed=80)
+    q = q[twin.self_clearance(q) > 0.01]
+    each = twin.cell_clearances(q)
+    nearest = np.array([g for _, g in model.cell_pairs])[each.argmin(axis=0)]
+    c = each.min(axis=0)
+    picks = [q[(nearest == g) & (c < -0.01)][:8] for g in range(5)] + [q[c > 0.01][:24]]
+    assert [len(p) for p in picks] == [8] * 5 + [24]
+    q = np.concatenate(picks)
+    rc, probe, out = _probe_and_one_rollout_step(model, q)
+    want = twin.cell_clearance(q)
+    tol = X.tol_of(model)
+    assert rc == 0 and np.abs(probe - want).max() <= 2 * tol and np.abs(out[:, 6] - want).max() <= 2 * tol
+    assert np.array_equal(out[:, 0], [4.0] * 40 + [0.0] * 24)
+
+
+# ---- (5) off means off -------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["planar3", "iiwa_like7"])
+def test_without_a_box_nothing_changes(name):
+    """A model compiled with an empty workcell_boxes against one compiled without the argument, in a workcell of spheres and
+    half-spaces and without any: rows, observations, env_state, outcomes and the probe of a fixed-seed training stream and of a
+    rollout are bit-equal, and the handle of the arm without a workcell still has no workcell to probe."""
+    case = K.build_case(name, 64)
+    sc = {k: v for k, v in K.workcell_of(name).items() if k == "consider_autocollision"}
+    for models in ((K.arm(name)[0], model_of(name, workcell_boxes=[], **K.workcell_of(name))),
+                   (K.plain(name), model_of(name, workcell_boxes=[], **sc))):
+        results = []
+        for model in models:
+            assert model.pack()[12] == 0
+            rig = CellRig(model, 64, record_slots=4)
+            rig.reset((0.3, 0.2, 0.4), (0.2, 0.1, 0.3))
+            stream = []
+            for t in range(12):
+                rig.load_actions(case.act[:, t])
+                rig.launch_step(max_frames=7)
+                stream += [rig.rows.cpu().numpy().copy(), rig.obs.cpu().numpy().copy(), rig.st.cpu().numpy().copy()]
+            stream.append(rig.recs.cpu().numpy().view(np.float32).copy())
+            rig.reset_given(case.q0, case.target, case.obstacle)
+            rc, probe = rig.probe_cell()
+            assert rc == (0 if model.cell_pairs else -2)
+            for t in range(12):
+                rig.load_actions(case.act[:, t])
+                rig.launch_rollout()
+            stream += [rig.out.cpu().numpy(), rig.obs.cpu().numpy(), rig.traj.cpu().numpy()] + ([probe] if rc == 0 else [])
+            rig.close()
+            results.append(b"".join(bits(a).tobytes() for a in stream))
+        assert results[0] == results[1]
+
+
+# ---- (6) graph capture -------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("ranged", [False, True])
+def test_captured_launches_equal_direct_ones(ranged):
+    """A captured training step and a captured rollout step, replayed, give the bits of direct launches (iiwa_like7 among its boxes,
+    E = 100)."""
+    E = 100
+    case = X.build_case("iiwa_like7", E)
+    runs = []
+    for captured in (False, True):
+        rig = CellRig(case.model, E, ranges=RANGES if ranged else None, record_slots=4)
+        rig.reset((0.3, 0.2, 0.4), (3.0, 3.0, 3.0))
+        step = _graph_of(lambda: rig.launch_step(max_frames=9)) if captured else None
+        roll = _graph_of(rig.launch_rollout) if captured else None
+        for buf in (rig.rows, rig.out, rig.traj, rig.recs):                 # (what the warm-up launches wrote)
+            buf.zero_()
+        rig.reset((0.3, 0.2, 0.4), (3.0, 3.0, 3.0))
+        stream = []
+        for t in range(12):
+            rig.load_actions(case.act[:, t])
+            step.replay() if captured else rig.launch_step(max_frames=9)
+            stream += [rig.rows.cpu().numpy().copy(), rig.obs.cpu().numpy().copy(), rig.st.cpu().numpy().copy()]
+        stream.append(rig.recs.cpu().numpy().view(np.float32).copy())
+        rig.reset_given(case.q0, case.target, case.obstacle)
+        for t in range(12):
+            rig.load_actions(case.act[:, t])
+            roll.replay() if captured else rig.launch_rollout()
+        stream += [rig.out.cpu().numpy(), rig.obs.cpu().numpy(), rig.traj.cpu().numpy(), rig.st.cpu().numpy()]
+        rig.close()
+        runs.append(b"".join(bits(a).tobytes() for a in stream))
+    assert runs[0] == runs[1]
+
+
+# ---- (7) end to end ----------------------------------------------------------------------------------------------------------------
+def test_framework_with_boxes_end_to_end(scratch_cwd):
+    """run_training on iiwa_like7 among a table top, a shelf and a post at n_envs = 64, scene ranges on, a training state saved; then
+    reach_targets from start poses with a capsule 2 to 10 mm clear of a box, with exploration noise: queries end in 'workcell',
+    each one's min_cell_clearance is the twin's over its own joint path, and start_cell_clearance the twin's at its start pose;
+    a framework with the shelf moved is refused the resume."""
+    from chain_resume_worker import make_framework
+    ee, involved, fixed, init, var = ARM_TABLE["iiwa_like7"]
+    boxes = [list(b) for b in X.boxes_of("iiwa_like7")]
+    arm = dict(manipulator_file=path("iiwa_like7"), endeffector_index=ee, fixed_joints=fixed, involved_joints=involved,
+               target_position=[0.45, -0.3, 0.6], obstacle_position=[0.35, -0.2, 0.45], initial_joint_positions=init,
+               initial_positions_variation_range=var, link_radius=0.03, consider_autocollision=True, target_range=[0.15, 0.15, 0.15],
+               workcell_boxes=boxes)
+    f = make_framework(arm, checkpoint_frequency=64, save=True)
+    scores = f.run_training(64, 50, verbose=False, n_envs=64)
+    assert list(scores.keys()) == list(range(1, 65)) and os.path.isfile("checkpoints/64/training_state.pt")
+    model = f.env.model
+    assert len(model.cell_boxes) == 3 and list(model.pack()[10:13]) == [0, 0, 3]
+    twin = KinematicEnvironment(model, (0, 0, 0), (0, 0, 0))
+    q = X.uniform_poses("iiwa_like7", 16384, seed=81)
+    c = twin.cell_clearance(q)
+    q = q[(c > 0.002) & (c < 0.010) & (twin.self_clearance(q) > 0.01)][:64]
+    N, Fr = len(q), 60
+    assert N >= 32
+    targets = twin.end_effector(q) - np.array([0.0, 0.0, 0.3])
+    out = f.reach_targets(targets, obstacles=[3.0, 3.0, 3.0], initial_joint_positions=q, frames=Fr, noise_scale=1.0)
+    tol = X.tol_of(model)
+    assert set(out.outcome) <= {"reached", "obstacle", "self", "workcell", "frames"} and np.sum(out.outcome == "workcell") >= 1
+    assert out.min_cell_clearance.dtype == np.float32 and out.start_cell_clearance.shape == (N,)
+    assert np.abs(out.start_cell_clearance - twin.cell_clearance(q.astype(np.float32).astype(np.float64))).max() <= 2 * tol
+    for i in range(N):
+        own = twin.cell_clearance(out.joint_positions[i, 1:out.frames[i] + 1].astype(np.float64))
+        assert abs(out.min_cell_clearance[i] - own.min()) <= 2 * tol, (i, out.min_cell_clearance[i], own.min())
+        if out.outcome[i] == "workcell":
+            assert out.min_cell_clearance[i] < 0.0 and own[-1] < 2 * tol and np.all(own[:-1] > -2 * tol)
+    # another box is another model: the training state is refused by the model digest
+    moved = [list(b) for b in boxes]
+    moved[1][0] -= 0.05
+    other = make_framework(dict(arm, workcell_boxes=moved), checkpoint_frequency=64, save=False)
+    assert other.env.model.digest() != model.digest()
+    with pytest.raises(ValueError, match="chain"):
+        other.resume_training(64, 128, 50, verbose=False, n_envs=64)
