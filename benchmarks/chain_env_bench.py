@@ -33,6 +33,14 @@ launches are the box instantiations, which test the floor and the spheres too.
       gather (naf_replay_gather_rows) and the hindsight gather at the given ratio and horizon, interleaved, on the same indices;
       and the hindsight kernel's registers and scratch as the compiler reported them.
 
+  python benchmarks/chain_env_bench.py ik [--envs 4096] [--launches 20]
+      goal poses for N = --envs targets (default 4096 here), R = 8 restarts, K = 32 updates, on --urdf with self-collision inside
+      the --workcell --boxes cell (always on for this subcommand), targets uniform in a box around the nominal one:
+      microseconds per naf_chain_ik_solve launch and milliseconds per whole GoalPoseSolver.solve call (host seeds, uploads,
+      solve -> reset_given -> probes -> select, downloads), each between device events, median and minimum of `--launches` after
+      two unmeasured ones; the reachable and free shares; and the float64 host twin's seconds on the first 64 of the queries,
+      with its time for all N EXTRAPOLATED from those 64 (it is linear in N) — that figure is not a measurement.
+
 `--hindsight R` (rate): the chain runs relabel a share R of every minibatch (NAFAgent.run_vectorized(hindsight=R)). Such a run
 wants an empty ring, so with the flag — also `--hindsight 0`, the figure to compare with — the warm-up steps run on an agent of
 their own and the timed run starts on a fresh one (its graph captures are inside the timed window, in both).
@@ -260,6 +268,60 @@ def gather(a):
                       "hindsight_kernel_registers_by_width": regs}))
 
 
+def ik(a):
+    import time
+    import numpy as np
+    import torch
+    from robotic_manipulator_rloa_amd import _lib
+    from robotic_manipulator_rloa_amd.engine import GoalPoseSolver
+    from robotic_manipulator_rloa_amd.environment.kinematic import KinematicEnvironment, goal_poses_host
+    from robotic_manipulator_rloa_amd.environment.urdf_chain import compile_chain, load_urdf
+    N, R, K, n = (4096 if a.envs == 64 else a.envs), 8, 32, a.joints
+    a.workcell = a.boxes = True
+    urdf = os.path.abspath(a.urdf) if os.path.isabs(a.urdf) else os.path.join(ROOT, a.urdf)
+    init = ([0.0, 0.6, 0.0, -1.2, 0.0, 0.8, 0.0] + [0.0] * n)[:n]
+    model = compile_chain(load_urdf(urdf), n - 1, list(range(n)), [n], init, [0.1] * n, 0.03, consider_autocollision=True, **_workcell(a))
+    rng = np.random.default_rng(5)
+    targets = np.array([0.45, 0.3, 0.6]) + rng.uniform(-0.25, 0.25, (N, 3))
+    obstacles, q0 = np.tile([0.35, 0.2, 0.45], (N, 1)), np.tile(init, (N, 1))
+    solver = GoalPoseSolver(model, 0.06)
+    whole, kernel = [], []
+    for i in range(a.launches + 2):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        out = solver.solve(q0, targets, obstacles, restarts=R, iterations=K)
+        t1.record()
+        t1.synchronize()
+        if i >= 2:
+            whole.append(t0.elapsed_time(t1))
+    prm = solver.params(K)                                   # the last chunk's queries are still in the buffers
+    per = min(N, solver.chunk // R)
+    for i in range(a.launches + 2):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        solver.launch(per, R, prm, 1e-3, 0.0, solve_only=True)
+        t1.record()
+        t1.synchronize()
+        if i >= 2:
+            kernel.append(1e3 * t0.elapsed_time(t1))
+    twin = KinematicEnvironment(model, (0.45, 0.3, 0.6), (0.35, 0.2, 0.45), 0.06)
+    t = time.perf_counter()
+    host = goal_poses_host(twin, q0[:64], targets[:64], obstacles[:64], restarts=R, iterations=K)
+    twin_s = time.perf_counter() - t
+    usage = json.load(open(_lib.USAGE_PATH)) if os.path.exists(_lib.USAGE_PATH) else {}
+    regs = {name: {q: v.get(q) for q in ("vgprs", "sgprs", "scratch_bytes_per_lane", "occupancy")} for name, v in usage.items()
+            if "chain_ik_" in name}
+    print(json.dumps({"arm": os.path.basename(urdf), "queries": N, "restarts": R, "iterations": K, "self_pairs": len(model.self_pairs),
+                      "workcell_pairs": len(model.cell_pairs), "candidates_per_solve_launch": per * R,
+                      "us_per_ik_solve_launch": {"median": round(float(np.median(kernel)), 1), "min": round(float(np.min(kernel)), 1)},
+                      "ms_per_solve_goal_poses_call": {"median": round(float(np.median(whole)), 2), "min": round(float(np.min(whole)), 2)},
+                      "reachable_share": round(float(out.reachable.mean()), 4), "free_share": round(float(out.free.mean()), 4),
+                      "twin_seconds_for_64_queries": round(twin_s, 3),
+                      "twin_seconds_for_all_queries_EXTRAPOLATED_from_64": round(twin_s * N / 64, 1),
+                      "twin_and_device_agree_on_reachable_of_64": int(np.sum(host.reachable == out.reachable[:64])),
+                      "kernel_registers": regs}))
+
+
 def kernels(a):
     import numpy as np
     import torch
@@ -298,7 +360,7 @@ def kernels(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["rate", "kernels", "step", "rollout", "gather"])
+    ap.add_argument("what", choices=["rate", "kernels", "step", "rollout", "gather", "ik"])
     ap.add_argument("--urdf", default=os.path.join("tests", "golden", "urdf", "iiwa_like7.urdf"))
     ap.add_argument("--joints", type=int, default=7)
     ap.add_argument("--envs", type=int, default=64)
@@ -318,7 +380,7 @@ def main():
     ap.add_argument("--hindsight", type=float, default=None, help="rate, gather: the share of rows replayed under a hindsight goal")
     ap.add_argument("--horizon", type=int, default=None, help="rate, gather: hindsight_horizon (rate: max_frames; gather: 400)")
     a = ap.parse_args()
-    {"rate": rate, "kernels": kernels, "step": step, "rollout": rollout, "gather": gather}[a.what](a)
+    {"rate": rate, "kernels": kernels, "step": step, "rollout": rollout, "gather": gather, "ik": ik}[a.what](a)
 
 
 if __name__ == "__main__":

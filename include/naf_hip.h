@@ -854,6 +854,46 @@ int naf_chain_env_reset_given(naf_chain_env_t* h, float* env_state, float* obs, 
 int naf_chain_env_rollout_step(naf_chain_env_t* h, float* env_state, const float* actions, float* obs_next, float* outcome,
                                float* traj, int E, int max_frames, void* stream);
 
+/* Goal poses (additions within ABI 40): joint values that put the end effector on given targets, by a damped least-squares iteration on
+ * its positional Jacobian, batched over queries and restarts; and the choice among a query's restarts. environment/kinematic.py
+ * (jacobian, ik_step, solve_ik, select_goal_pose) is the float64 statement. Orientation is no goal; contact is not part of the
+ * iteration — it is met by restarts and selection only.
+ *   A candidate is (query n, restart r), index n R + r: target g = targets_dev[n], start pose q_start_dev[n], seed = q_start_dev[n]
+ *   for r = 0 and seeds_dev[n][r] otherwise (seeds_dev[n][0] is not read). R is a power of two, 1 .. 64.
+ *   the rule    : q = seed, then `iterations` updates, a fixed trip count:
+ *                   walk the chain at q: ee, and for every driven joint m before the end-effector frame its axis in the world
+ *                   a_m = (F.R R_pre) axis and the point p_m = F.p + F.R t_pre on it (the frame before the joint's motion);
+ *                   c_m = a_m x (ee - p_m) revolute | a_m prismatic | 0 for m >= end-effector frame;
+ *                   e = g - ee, scaled to length e_max when longer;  M = sum_m c_m c_m^T + lam2 I;  M y = e in closed form;
+ *                   dq_m = c_m . y, all of dq scaled so that max |dq_m| <= dq_max;  q_m += dq_m, then the position limits as a
+ *                   step applies them.
+ *                 After the last update one more walk gives residual = |g - ee(q)|.
+ *   ik_solve    : q_out [N R][A] and residual_out [N R] (DEVICE) receive every candidate's pose and residual; iters_out, NULL or
+ *                 DEVICE [iterations + 1][N R][A], the pose before the first and after every update (for tests). q_out is also the
+ *                 kernel's working pose and may alias none of the inputs. One lane per candidate; (a_m, p_m) are staged in LDS,
+ *                 1536 bytes per walked joint and wave. NAF_ERR_ARG, and no launch, for a null pointer, N < 1, R not a power of
+ *                 two in 1 .. 64, iterations < 1, or lam2 / e_max / dq_max not finite and positive.
+ *   clearances  : of the poses in q_out, by naf_chain_env_reset_given (q0 = q_out, each candidate's scene), naf_chain_env_probe and,
+ *                 with a workcell, naf_chain_env_probe_cell, E = N R: no collision code of its own.
+ *   ik_select   : per candidate joint_distance_out [N R] = max_m |q_out_m - q_start_m| (float32). A candidate is converged iff
+ *                 residual <= tolerance, and free iff probe_dev [N R][NAF_CHAIN_PROBE_FLOATS] has [3] >= margin (the obstacle
+ *                 clearance, the obstacle radius already subtracted as probe reports it) and [4] >= margin, and cell_dev [N R]
+ *                 (NULL: no workcell) >= margin. Class 0: converged and free, 1: converged, not free, 2: not converged. Per query
+ *                 the lowest class wins; inside classes 0 and 1 the smallest joint distance, inside class 2 the smallest residual;
+ *                 ties go to the lowest r. choice_out [N] (int32) = the winner's r, class_out [N] (int32) its class: reachable
+ *                 iff <= 1, free iff 0. A reduction over the R adjacent lanes by shuffles. NAF_ERR_ARG, and no launch, for a
+ *                 null pointer other than cell_dev, the counts as above, tolerance not finite or negative, margin not finite. */
+typedef struct {
+    int32_t iterations;     /* K >= 1 */
+    float lam2;             /* the damping, squared */
+    float e_max, dq_max;    /* the longest error vector and the largest joint update of one iteration */
+} naf_chain_ik_params_t;
+int naf_chain_ik_solve(naf_chain_env_t* h, const float* targets_dev, const float* q_start_dev, const float* seeds_dev, int N, int R,
+                       naf_chain_ik_params_t params, float* q_out, float* residual_out, float* iters_out, void* stream);
+int naf_chain_ik_select(naf_chain_env_t* h, const float* q_out, const float* q_start_dev, const float* residual_out,
+                        const float* probe_dev, const float* cell_dev, int N, int R, float tolerance, float margin, int* choice_out,
+                        int* class_out, float* joint_distance_out, void* stream);
+
 /* ---- one-shot gradient all-reduce over peer-mapped memory (no reference counterpart) ----------
  * The data-parallel exchange that follows loss.backward() (naf_algorithm.py:207-210 on every rank): sum of the flat
  * gradient over the W <= 8 GPUs of one node, each rank pushing its gradient into a receive slot on every peer over

@@ -160,6 +160,11 @@ _lib: Optional[C.CDLL] = None
 
 _vp, _i, _f, _u64, _sz, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_size_t, C.c_int64
 
+class IkParams(C.Structure):
+    """naf_chain_ik_params_t (include/naf_hip.h)"""
+    _fields_ = [("iterations", C.c_int32), ("lam2", C.c_float), ("e_max", C.c_float), ("dq_max", C.c_float)]
+
+
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/naf_hip.h one to one
 _PROTOS = {
     "naf_hip_abi_version": [],
@@ -262,6 +267,8 @@ _PROTOS = {
     "naf_chain_env_rollout_step": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "naf_replay_gather_rows_hindsight": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp],
     "naf_chain_env_step_tagged": [_vp, _vp, _vp, _vp, _vp, _i, _u64, _vp, _i, _vp, _i, _vp],
+    "naf_chain_ik_solve": [_vp, _vp, _vp, _vp, _i, _i, IkParams, _vp, _vp, _vp, _vp],
+    "naf_chain_ik_select": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp],
 }
 _RESTYPES = {"naf_hip_arch": C.c_char_p}
 EXPORTED_SYMBOLS = tuple(_PROTOS)

@@ -65,6 +65,7 @@ struct naf_chain_env {
     float ranges[NAF_CHAIN_RANGE_FLOATS];      // set_scene_ranges: target half-widths | obstacle half-widths | margin
     float centre[6];                // target | obstacle of the last reset's scene_host: the boxes' centres and the fallback
     bool scene_on, scene_ready;     // a half-width is non-zero; a reset has run since the ranges were set
+    int ee_frame;                  // the end-effector frame: the goal-pose solver walks the joints before it
 };
 #ifndef CH_MAX_WAVES
 #define CH_MAX_WAVES 16                      // (-DCH_MAX_WAVES=1 through NAF_BUILD_DEFINES: the one-wave pair loop, NOTEBOOK §15)
@@ -893,6 +894,7 @@ extern "C" int naf_chain_env_create(const float* model_host, int n_floats, naf_c
     h->n_seg = (int)model_host[2];
     h->n_pairs = (int)model_host[9];
     h->n_box = (int)model_host[12];
+    h->ee_frame = (int)model_host[4];
     h->n_cell = (int)model_host[10] + (int)model_host[11] + h->n_box;
     h->lanes = 64;
     h->waves = 1;
@@ -1115,6 +1117,246 @@ extern "C" int naf_chain_env_rollout_step(naf_chain_env_t* h, float* env_state, 
     else
         chain_env_rollout_kernel<false><<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(h->model_dev, env_state, actions, obs_next, outcome,
                                                                                        traj, E, h->A, h->n_seg, max_frames, 0, 64);
+    NAF_CHECK_LAUNCH();
+    return NAF_OK;
+}
+
+// ---- goal poses: damped least squares on the end effector's positional Jacobian (include/naf_hip.h, "Goal poses") ----------------
+// One lane per candidate (query n, restart r), the R candidates of a query in adjacent lanes, one wave per workgroup: no barrier
+// anywhere, an inactive tail lane returns at once. The pose lives in q_out (read and written as the walk and the update reach each
+// joint, as the step kernels keep theirs in env_state); the walk leaves every driven joint's world axis a_m and a point p_m on
+// it in LDS as [m][6][lane] floats — lane-contiguous, conflict-free, and no per-lane array is indexed at run time. Each lane
+// reads back only what it wrote. Joints behind the end-effector frame are not walked: their columns are 0.
+
+// walks joints 0 .. ee_frame - 1 at the joint values q; STORE: a_m | p_m to ax[(m * 6 + k) * 64]; returns the end effector in ee
+template <bool STORE>
+__device__ static inline void ik_walk(const float* __restrict__ model, int n_joints, const float* q, float* ax, float* ee) {
+    Frame F = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
+    for (int m = 0; m < n_joints; ++m) {
+        const float* j = model + CH_HDR + m * CH_JNT;
+        const float qm = q[m];
+        F.px += F.r00 * j[9] + F.r01 * j[10] + F.r02 * j[11];
+        F.py += F.r10 * j[9] + F.r11 * j[10] + F.r12 * j[11];
+        F.pz += F.r20 * j[9] + F.r21 * j[10] + F.r22 * j[11];
+        Frame G;
+        G.r00 = F.r00 * j[0] + F.r01 * j[3] + F.r02 * j[6];
+        G.r01 = F.r00 * j[1] + F.r01 * j[4] + F.r02 * j[7];
+        G.r02 = F.r00 * j[2] + F.r01 * j[5] + F.r02 * j[8];
+        G.r10 = F.r10 * j[0] + F.r11 * j[3] + F.r12 * j[6];
+        G.r11 = F.r10 * j[1] + F.r11 * j[4] + F.r12 * j[7];
+        G.r12 = F.r10 * j[2] + F.r11 * j[5] + F.r12 * j[8];
+        G.r20 = F.r20 * j[0] + F.r21 * j[3] + F.r22 * j[6];
+        G.r21 = F.r20 * j[1] + F.r21 * j[4] + F.r22 * j[7];
+        G.r22 = F.r20 * j[2] + F.r21 * j[5] + F.r22 * j[8];
+        const float x = j[12], y = j[13], z = j[14];
+        const float wx = G.r00 * x + G.r01 * y + G.r02 * z, wy = G.r10 * x + G.r11 * y + G.r12 * z,
+                    wz = G.r20 * x + G.r21 * y + G.r22 * z;
+        if constexpr (STORE) {
+            float* w = ax + m * 6 * 64;
+            w[0] = wx; w[64] = wy; w[128] = wz;
+            w[192] = F.px; w[256] = F.py; w[320] = F.pz;
+        }
+        if (j[15] != 0.f) {      // prismatic
+            F.r00 = G.r00; F.r01 = G.r01; F.r02 = G.r02;
+            F.r10 = G.r10; F.r11 = G.r11; F.r12 = G.r12;
+            F.r20 = G.r20; F.r21 = G.r21; F.r22 = G.r22;
+            F.px += wx * qm;
+            F.py += wy * qm;
+            F.pz += wz * qm;
+        } else {                 // revolute: chain_walk's Rodrigues form
+            float s, c;
+            sincosf(qm, &s, &c);
+            const float v = 1.f - c;
+            const float m00 = 1.f - v * (y * y + z * z), m01 = v * x * y - s * z, m02 = v * x * z + s * y;
+            const float m10 = v * x * y + s * z, m11 = 1.f - v * (x * x + z * z), m12 = v * y * z - s * x;
+            const float m20 = v * x * z - s * y, m21 = v * y * z + s * x, m22 = 1.f - v * (x * x + y * y);
+            F.r00 = G.r00 * m00 + G.r01 * m10 + G.r02 * m20;
+            F.r01 = G.r00 * m01 + G.r01 * m11 + G.r02 * m21;
+            F.r02 = G.r00 * m02 + G.r01 * m12 + G.r02 * m22;
+            F.r10 = G.r10 * m00 + G.r11 * m10 + G.r12 * m20;
+            F.r11 = G.r10 * m01 + G.r11 * m11 + G.r12 * m21;
+            F.r12 = G.r10 * m02 + G.r11 * m12 + G.r12 * m22;
+            F.r20 = G.r20 * m00 + G.r21 * m10 + G.r22 * m20;
+            F.r21 = G.r20 * m01 + G.r21 * m11 + G.r22 * m21;
+            F.r22 = G.r20 * m02 + G.r21 * m12 + G.r22 * m22;
+        }
+    }
+    ee[0] = F.px + F.r00 * model[5] + F.r01 * model[6] + F.r02 * model[7];
+    ee[1] = F.py + F.r10 * model[5] + F.r11 * model[6] + F.r12 * model[7];
+    ee[2] = F.pz + F.r20 * model[5] + F.r21 * model[6] + F.r22 * model[7];
+}
+
+// Jacobian column of joint m from its LDS record: a x (ee - p), or a for a prismatic joint
+__device__ static inline void ik_column(const float* __restrict__ model, int m, const float* ax, const float* ee, float* c) {
+    const float* w = ax + m * 6 * 64;
+    const float a0 = w[0], a1 = w[64], a2 = w[128];
+    if (model[CH_HDR + m * CH_JNT + 15] != 0.f) {
+        c[0] = a0; c[1] = a1; c[2] = a2;
+    } else {
+        const float d0 = ee[0] - w[192], d1 = ee[1] - w[256], d2 = ee[2] - w[320];
+        c[0] = a1 * d2 - a2 * d1;
+        c[1] = a2 * d0 - a0 * d2;
+        c[2] = a0 * d1 - a1 * d0;
+    }
+}
+
+// REC: iters_out [K + 1][N R][A] receives the pose before the first and after every update
+template <bool REC>
+__global__ void __launch_bounds__(64)
+chain_ik_solve_kernel(const float* __restrict__ model, const float* __restrict__ targets, const float* __restrict__ q_start,
+                      const float* __restrict__ seeds, int N, int R, int A, const naf_chain_ik_params_t prm, float* q_out,
+                      float* __restrict__ residual_out, float* __restrict__ iters_out) {
+    extern __shared__ __attribute__((aligned(16))) float ch_lds[];
+    const int64_t total = (int64_t)N * R;
+    const int64_t cand = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (cand >= total) return;      // (one wave per workgroup and no barrier below)
+    const int64_t n = cand / R;
+    const int r = (int)(cand - n * R);
+    const int n_joints = (int)model[4];      // the end-effector frame: joints m >= it do not move the end effector
+    float* ax = ch_lds + threadIdx.x;
+    float* q = q_out + cand * A;
+    const float* src = r == 0 ? q_start + n * A : seeds + cand * A;
+    for (int m = 0; m < A; ++m) {
+        const float v = src[m];
+        q[m] = v;
+        if constexpr (REC) iters_out[cand * A + m] = v;
+    }
+    const float g0 = targets[n * 3], g1 = targets[n * 3 + 1], g2 = targets[n * 3 + 2];
+    float ee[3];
+    for (int k = 0; k < prm.iterations; ++k) {
+        ik_walk<true>(model, n_joints, q, ax, ee);
+        float e0 = g0 - ee[0], e1 = g1 - ee[1], e2 = g2 - ee[2];
+        const float len = sqrtf(e0 * e0 + e1 * e1 + e2 * e2);
+        if (len > prm.e_max) {
+            const float s = prm.e_max / len;
+            e0 *= s; e1 *= s; e2 *= s;
+        }
+        // pass 1 over LDS: M = sum c c^T + lam^2 I
+        float m00 = prm.lam2, m01 = 0.f, m02 = 0.f, m11 = prm.lam2, m12 = 0.f, m22 = prm.lam2;
+        for (int m = 0; m < n_joints; ++m) {
+            float c[3];
+            ik_column(model, m, ax, ee, c);
+            m00 += c[0] * c[0]; m01 += c[0] * c[1]; m02 += c[0] * c[2];
+            m11 += c[1] * c[1]; m12 += c[1] * c[2]; m22 += c[2] * c[2];
+        }
+        // M y = e in closed form: the adjugate over the determinant
+        const float c00 = m11 * m22 - m12 * m12, c01 = m02 * m12 - m01 * m22, c02 = m01 * m12 - m02 * m11;
+        const float c11 = m00 * m22 - m02 * m02, c12 = m01 * m02 - m00 * m12, c22 = m00 * m11 - m01 * m01;
+        const float det = m00 * c00 + m01 * c01 + m02 * c02;
+        const float y0 = (c00 * e0 + c01 * e1 + c02 * e2) / det, y1 = (c01 * e0 + c11 * e1 + c12 * e2) / det,
+                    y2 = (c02 * e0 + c12 * e1 + c22 * e2) / det;
+        // pass 2: dq_m = c_m . y, kept in the record's first float, and max |dq_m|
+        float big = 0.f;
+        for (int m = 0; m < n_joints; ++m) {
+            float c[3];
+            ik_column(model, m, ax, ee, c);
+            const float dq = c[0] * y0 + c[1] * y1 + c[2] * y2;
+            ax[m * 6 * 64] = dq;
+            big = fmaxf(big, fabsf(dq));
+        }
+        const float scale = big > prm.dq_max ? prm.dq_max / big : 1.f;
+        for (int m = 0; m < A; ++m) {
+            const float* j = model + CH_HDR + m * CH_JNT;
+            float v = q[m];
+            if (m < n_joints) v += scale * ax[m * 6 * 64];
+            if (j[16] != 0.f) {      // the position limits, as a step applies them
+                if (v > j[18]) v = j[18];
+                if (v < j[17]) v = j[17];
+            }
+            q[m] = v;
+            if constexpr (REC) iters_out[((int64_t)(k + 1) * total + cand) * A + m] = v;
+        }
+    }
+    ik_walk<false>(model, n_joints, q, ax, ee);
+    const float e0 = g0 - ee[0], e1 = g1 - ee[1], e2 = g2 - ee[2];
+    residual_out[cand] = sqrtf(e0 * e0 + e1 * e1 + e2 * e2);
+}
+
+// The selection among the R adjacent lanes of a query: key (class, joint distance or residual, r), a butterfly of shuffles
+// inside the group. A group lies inside one wave and is active or inactive as a whole (R divides 64).
+__global__ void __launch_bounds__(64)
+chain_ik_select_kernel(const float* __restrict__ q_out, const float* __restrict__ q_start, const float* __restrict__ residual,
+                       const float* __restrict__ probe, const float* __restrict__ cell, int N, int R, int A, float tolerance,
+                       float margin, int* __restrict__ choice_out, int* __restrict__ class_out, float* __restrict__ jd_out) {
+    const int64_t total = (int64_t)N * R;
+    int64_t cand = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    const bool active = cand < total;
+    if (!active) cand = 0;      // (addresses stay inside the arrays; nothing is written through them)
+    const int64_t n = cand / R;
+    int r = (int)(cand - n * R);
+    float jd = 0.f;
+    for (int m = 0; m < A; ++m) jd = fmaxf(jd, fabsf(q_out[cand * A + m] - q_start[n * A + m]));
+    const float res = residual[cand];
+    const float* p = probe + cand * NAF_CHAIN_PROBE_FLOATS;
+    const bool free_ = p[3] >= margin && p[4] >= margin && (!cell || cell[cand] >= margin);
+    int cls = res <= tolerance ? (free_ ? 0 : 1) : 2;
+    float val = cls == 2 ? res : jd;
+    if (active) jd_out[cand] = jd;
+    for (int off = 1; off < R; off <<= 1) {
+        const int o_cls = __shfl_xor(cls, off), o_r = __shfl_xor(r, off);
+        const float o_val = __shfl_xor(val, off);
+        const bool take = o_cls < cls || (o_cls == cls && (o_val < val || (o_val == val && o_r < r)));
+        cls = take ? o_cls : cls;
+        val = take ? o_val : val;
+        r = take ? o_r : r;
+    }
+    if (active && cand - n * R == 0) {
+        choice_out[n] = r;
+        class_out[n] = cls;
+    }
+}
+
+// the solve kernels' dynamic LDS (1536 bytes per walked joint) may exceed the 64 KB a kernel gets unasked: raised once per device
+static int ch_ik_raise_lds_limit() {
+    static bool raised_dev[64];
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return (int)e;
+    if (dev < 0 || dev >= 64) return NAF_ERR_ARG;
+    if (raised_dev[dev]) return NAF_OK;
+    for (const void* k : {(const void*)chain_ik_solve_kernel<false>, (const void*)chain_ik_solve_kernel<true>}) {
+        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, CH_MAX_DYN_LDS);
+        if (e != hipSuccess) return (int)e;
+    }
+    raised_dev[dev] = true;
+    return NAF_OK;
+}
+
+static inline bool ch_ik_counts_ok(int N, int R) {
+    return N >= 1 && R >= 1 && R <= 64 && (R & (R - 1)) == 0 && (int64_t)N * R <= (int64_t)1 << 30;
+}
+
+extern "C" int naf_chain_ik_solve(naf_chain_env_t* h, const float* targets_dev, const float* q_start_dev, const float* seeds_dev, int N,
+                                  int R, naf_chain_ik_params_t params, float* q_out, float* residual_out, float* iters_out,
+                                  void* stream) {
+    if (!h || !targets_dev || !q_start_dev || !seeds_dev || !q_out || !residual_out || !ch_ik_counts_ok(N, R)) return NAF_ERR_ARG;
+    if (params.iterations < 1 || !std::isfinite(params.lam2) || !(params.lam2 > 0.f) || !std::isfinite(params.e_max) ||
+        !(params.e_max > 0.f) || !std::isfinite(params.dq_max) || !(params.dq_max > 0.f))
+        return NAF_ERR_ARG;
+    const size_t lds = (size_t)std::max(h->ee_frame, 1) * 6 * 64 * sizeof(float);
+    if (lds > CH_MAX_DYN_LDS) return NAF_CHAIN_ERR_LDS;
+    const int rc = ch_ik_raise_lds_limit();
+    if (rc != NAF_OK) return rc;
+    const unsigned grid = (unsigned)(((int64_t)N * R + 63) / 64);
+    if (iters_out)
+        chain_ik_solve_kernel<true><<<grid, 64, lds, (hipStream_t)stream>>>(h->model_dev, targets_dev, q_start_dev, seeds_dev, N, R, h->A,
+                                                                           params, q_out, residual_out, iters_out);
+    else
+        chain_ik_solve_kernel<false><<<grid, 64, lds, (hipStream_t)stream>>>(h->model_dev, targets_dev, q_start_dev, seeds_dev, N, R, h->A,
+                                                                            params, q_out, residual_out, nullptr);
+    NAF_CHECK_LAUNCH();
+    return NAF_OK;
+}
+
+extern "C" int naf_chain_ik_select(naf_chain_env_t* h, const float* q_out, const float* q_start_dev, const float* residual_out,
+                                   const float* probe_dev, const float* cell_dev, int N, int R, float tolerance, float margin,
+                                   int* choice_out, int* class_out, float* joint_distance_out, void* stream) {
+    if (!h || !q_out || !q_start_dev || !residual_out || !probe_dev || !choice_out || !class_out || !joint_distance_out ||
+        !ch_ik_counts_ok(N, R))
+        return NAF_ERR_ARG;
+    if (!std::isfinite(tolerance) || !(tolerance >= 0.f) || !std::isfinite(margin)) return NAF_ERR_ARG;
+    chain_ik_select_kernel<<<(unsigned)(((int64_t)N * R + 63) / 64), 64, 0, (hipStream_t)stream>>>(
+        q_out, q_start_dev, residual_out, probe_dev, cell_dev, N, R, h->A, tolerance, margin, choice_out, class_out, joint_distance_out);
     NAF_CHECK_LAUNCH();
     return NAF_OK;
 }

@@ -10,6 +10,8 @@
                    U = E * num_updates / update_freq so the reference's update-to-data ratio is kept.
   DeviceRollout  : the policy run as a QUERY on a chain model: given start poses and scenes, act -> rollout step as ONE graph per
                    frame, an env held at the end of its episode; outcome, clearances and joint paths come back (ReachResult).
+  GoalPoseSolver : joint values that reach given targets on a chain model: batched damped least squares over queries x restarts,
+                   the pinned clearances at the solved poses, the selection per query (GoalPoses). No agent, no graph.
 
 Graph capture goes through torch.cuda.CUDAGraph (= hipGraph on ROCm): the ctypes kernel launches use the
 stream torch reports as current, which inside the capture context is the capturing stream.
@@ -26,6 +28,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
+from .environment.kinematic import GoalPoses, gather_goal_poses, ik_seeds
 from .learner import ActPath, Learner
 from .presets import ROBOT_PRESETS, device_env_preset
 from .utils.replay_buffer import ReplayBuffer
@@ -1045,6 +1048,9 @@ class ReachResult:
     start_self_clearance: np.ndarray
     min_cell_clearance: np.ndarray             # [N] float32: least workcell clearance over the steps, +inf without a workcell
     start_cell_clearance: np.ndarray           # [N] float32: the workcell clearance at the start pose, +inf without a workcell
+    goal: Optional["GoalPoses"] = None         # reach_targets(goal_poses=True): the goal poses of the same queries and start poses
+    path_ratio: Optional[np.ndarray] = None    # [N] float64: the policy's joint path length (max-norm, summed over its frames) over
+                                               # goal.joint_distance; NaN where the query did not reach or has no free goal pose
 
 
 class DeviceRollout:
@@ -1155,3 +1161,95 @@ class DeviceRollout:
         return ReachResult(OUTCOME_NAMES[outcome[:, 0].astype(np.int64)], outcome[:, 1].astype(np.int64), outcome[:, 2].copy(),
                            outcome[:, 3].copy(), outcome[:, 4].copy(), outcome[:, 5].copy(), paths, target_start, start[:, 3].copy(),
                            start[:, 4].copy(), outcome[:, 6].copy() if self.has_cell else np.full(N, np.inf, np.float32), start_cell)
+
+
+class GoalPoseSolver:
+    """Goal poses on a chain model (csrc/chain_env.hip, "goal poses"): per chunk of candidates naf_chain_ik_solve, then the
+    clearances of the solved poses by naf_chain_env_reset_given + naf_chain_env_probe (+ naf_chain_env_probe_cell with a workcell),
+    then naf_chain_ik_select. Owns the handle and the buffers; needs no agent. A chunk holds a fixed number of candidates,
+    `chunk` rounded down to whole queries; a query's result does not depend on the chunk or the lane it lands in."""
+    CHUNK = 32768
+
+    def __init__(self, chain, obstacle_radius: float = 0.06, chunk: Optional[int] = None, device=None):
+        import ctypes
+        _lib.require_gpu()
+        self.lib, self.chain, self.A = _lib.load(), chain, chain.A
+        self.dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        self.obstacle_radius = float(np.float32(obstacle_radius))
+        self.chunk = int(self.CHUNK if chunk is None else chunk)
+        if self.chunk < 64:
+            raise ValueError("GoalPoseSolver: a chunk holds at least 64 candidates")
+        blob = np.ascontiguousarray(chain.pack(), np.float32)
+        self._chain_env = ctypes.c_void_p()
+        check(self.lib.naf_chain_env_create(blob.ctypes.data, int(blob.size), ctypes.byref(self._chain_env)), "chain_env_create")
+        self.has_cell = bool(chain.cell_spheres or chain.cell_planes or chain.cell_boxes)
+        C, A = self.chunk, self.A
+        f32, i32 = dict(dtype=torch.float32, device=self.dev), dict(dtype=torch.int32, device=self.dev)
+        self.targets, self.q_start, self.seeds = torch.zeros(C, 3, **f32), torch.zeros(C, A, **f32), torch.zeros(C, A, **f32)
+        self.q, self.residual, self.distance = torch.zeros(C, A, **f32), torch.zeros(C, **f32), torch.zeros(C, **f32)
+        self.env_state = torch.zeros(C, self.lib.naf_chain_env_state_floats(self._chain_env), **f32)
+        self.obs, self.scene = torch.zeros(C, 2 * A + 9, **f32), torch.zeros(C, 6, **f32)
+        self.probe, self.cell = torch.zeros(C, 5, **f32), torch.full((C,), float("inf"), **f32)
+        self.choice, self.cls = torch.zeros(C, **i32), torch.zeros(C, **i32)
+
+    def __del__(self):
+        if getattr(self, "_chain_env", None) is not None:
+            self.lib.naf_chain_env_destroy(self._chain_env)
+            self._chain_env = None
+
+    def params(self, iterations: int, lam=None, e_max=None, dq_max=None) -> "_lib.IkParams":
+        reach = self.chain.reach
+        lam = 0.05 * reach if lam is None else lam
+        return _lib.IkParams(int(iterations), float(lam) ** 2, float(0.25 * reach if e_max is None else e_max),
+                             float(0.5 if dq_max is None else dq_max))
+
+    def launch(self, n: int, R: int, prm, tolerance: float, margin: float, solve_only: bool = False) -> None:
+        """the launches of one chunk of n queries x R restarts already in the buffers, on the current stream"""
+        st, E = stream_ptr(), n * R
+        check(self.lib.naf_chain_ik_solve(self._chain_env, ptr(self.targets), ptr(self.q_start), ptr(self.seeds), n, R, prm, ptr(self.q),
+                                          ptr(self.residual), None, st), "chain_ik_solve")
+        if solve_only:
+            return
+        check(self.lib.naf_chain_env_reset_given(self._chain_env, ptr(self.env_state), ptr(self.obs), E, ptr(self.q), ptr(self.scene),
+                                                 self.obstacle_radius, st), "chain_env_reset_given")
+        check(self.lib.naf_chain_env_probe(self._chain_env, ptr(self.env_state), ptr(self.probe), E, st), "chain_env_probe")
+        if self.has_cell:
+            check(self.lib.naf_chain_env_probe_cell(self._chain_env, ptr(self.env_state), ptr(self.cell), E, st), "chain_env_probe_cell")
+        check(self.lib.naf_chain_ik_select(self._chain_env, ptr(self.q), ptr(self.q_start), ptr(self.residual), ptr(self.probe),
+                                           ptr(self.cell) if self.has_cell else None, n, R, tolerance, margin, ptr(self.choice),
+                                           ptr(self.cls), ptr(self.distance), st), "chain_ik_select")
+
+    def load(self, q0, targets, obstacles, seeds) -> None:
+        """a chunk's queries into the buffers: q0[n][A], targets[n][3], obstacles[n][3], seeds[n][R][A] (float32)"""
+        n, R = seeds.shape[:2]
+        self.targets[:n].copy_(torch.from_numpy(np.ascontiguousarray(targets, np.float32)))
+        self.q_start[:n].copy_(torch.from_numpy(np.ascontiguousarray(q0, np.float32)))
+        self.seeds[:n * R].copy_(torch.from_numpy(np.ascontiguousarray(seeds, np.float32).reshape(n * R, self.A)))
+        scene = np.concatenate([np.asarray(targets, np.float32), np.asarray(obstacles, np.float32)], axis=1)
+        self.scene[:n * R].copy_(torch.from_numpy(np.repeat(scene, R, axis=0)))
+
+    def solve(self, q0, targets, obstacles, restarts: int = 8, iterations: int = 32, tolerance: float = 1e-3, margin: float = 0.0,
+              seed: int = 0, **constants) -> GoalPoses:
+        """q0[N][A] (action order), targets[N][3], obstacles[N][3] -> GoalPoses of numpy arrays (float32 where the device's)."""
+        A, R = self.A, int(restarts)
+        q0 = np.ascontiguousarray(q0, np.float32).reshape(-1, A)
+        N = len(q0)
+        targets, obstacles = np.asarray(targets, np.float32).reshape(N, 3), np.asarray(obstacles, np.float32).reshape(N, 3)
+        seeds = ik_seeds(self.chain, N, R, seed)
+        prm = self.params(iterations, **constants)
+        tolerance, margin = float(np.float32(tolerance)), float(np.float32(margin))
+        per = self.chunk // R
+        parts = []
+        for first in range(0, N, per):
+            n = min(per, N - first)
+            sl = slice(first, first + n)
+            self.load(q0[sl], targets[sl], obstacles[sl], seeds[sl])
+            self.launch(n, R, prm, tolerance, margin)
+            E = n * R
+            cell = self.cell[:E].cpu().numpy() if self.has_cell else np.full(E, np.inf, np.float32)
+            probe = self.probe[:E].cpu().numpy().reshape(n, R, 5)
+            parts.append(gather_goal_poses(self.choice[:n].cpu().numpy(), self.cls[:n].cpu().numpy(),
+                                           self.q[:E].cpu().numpy().reshape(n, R, A), self.residual[:E].cpu().numpy().reshape(n, R),
+                                           probe[:, :, 3], probe[:, :, 4], cell.reshape(n, R),
+                                           self.distance[:E].cpu().numpy().reshape(n, R), np.float32(tolerance)))
+        return GoalPoses(*[np.concatenate([getattr(p, f) for p in parts]) for f in GoalPoses._fields])

@@ -269,6 +269,71 @@ class KinematicEnvironment:
             return np.full(lead, np.inf) if lead else float("inf")
         return np.min(self.cell_clearances(q), axis=0)
 
+    # ---- goal poses: damped least squares on the end effector's positional Jacobian (include/naf_hip.h, "Goal poses") ----
+    def jacobian(self, q: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """(ee[..., 3], J[..., 3, A]) at the driven joint values q: column m is a_m x (ee - p_m) for a revolute joint, a_m for a
+        prismatic one and 0 for a joint behind the end-effector frame (m >= ee_frame), with a_m = (F.R R_pre) axis the joint's axis
+        in the world and p_m = F.p + F.R t_pre a point on it — what frames() forms before it applies the joint's motion."""
+        q = self.q if q is None else np.asarray(q, float)
+        lead = q.shape[:-1]
+        R, p = np.broadcast_to(np.eye(3), lead + (3, 3)), np.zeros(lead + (3,))
+        axes, points = [], []
+        for m, j in enumerate(self.model.joints[:self.model.ee_frame]):
+            p = p + R @ j.pre_xyz
+            R = R @ j.pre_rot
+            a = R @ j.axis
+            axes.append(a)
+            points.append(p)
+            if j.type == PRISMATIC:
+                p = p + a * q[..., m, None]
+            else:
+                R = R @ axis_rotation(j.axis, q[..., m])
+        ee = p + R @ self.model.ee_point
+        J = np.zeros(lead + (3, self.n))
+        for m, j in enumerate(self.model.joints[:self.model.ee_frame]):
+            J[..., m] = axes[m] if j.type == PRISMATIC else np.cross(axes[m], ee - points[m])
+        return ee, J
+
+    def joint_limits(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(lower[A], upper[A]) as a step applies them: -inf / +inf for a joint without limits"""
+        return (np.array([j.lower if j.limited else -np.inf for j in self.model.joints]),
+                np.array([j.upper if j.limited else np.inf for j in self.model.joints]))
+
+    def ik_step(self, q, g, lam: float, e_max: float, dq_max: float) -> np.ndarray:
+        """One update of the goal-pose iteration at q[..., A] towards g[..., 3]: e = g - ee, scaled to length e_max when longer;
+        M = J J^T + lam^2 I; M y = e (spd3_solve); dq = J^T y, the whole of it scaled so that max |dq_m| <= dq_max; q + dq, then
+        the position limits exactly as a step applies them."""
+        q = np.asarray(q, float)
+        ee, J = self.jacobian(q)
+        e = np.asarray(g, float) - ee
+        n = np.sqrt(np.sum(e * e, axis=-1))[..., None]
+        e = np.where(n > e_max, e * (e_max / np.where(n > 0.0, n, 1.0)), e)
+        M = J @ np.swapaxes(J, -1, -2) + (lam * lam) * np.eye(3)
+        dq = np.sum(J * spd3_solve(M, e)[..., :, None], axis=-2)
+        big = np.max(np.abs(dq), axis=-1)[..., None]
+        dq = np.where(big > dq_max, dq * (dq_max / np.where(big > 0.0, big, 1.0)), dq)
+        lo, hi = self.joint_limits()
+        return np.minimum(np.maximum(q + dq, lo), hi)
+
+    def ik_defaults(self) -> dict:
+        """the iteration's constants where the caller names none: lam = 0.05 reach, e_max = 0.25 reach, dq_max = 0.5"""
+        return dict(lam=0.05 * self.model.reach, e_max=0.25 * self.model.reach, dq_max=0.5)
+
+    def solve_ik(self, targets, seeds, lam: Optional[float] = None, e_max: Optional[float] = None, dq_max: Optional[float] = None,
+                 iterations: int = 32) -> Tuple[np.ndarray, np.ndarray]:
+        """(q[..., A], residual[...]) per candidate: from the pose seeds[..., A], `iterations` updates by ik_step towards
+        targets[..., 3] (broadcast against the seeds' lead) — a fixed trip count, nothing loops until converged — then
+        residual = |g - ee(q)|."""
+        d = self.ik_defaults()
+        lam, e_max, dq_max = (d["lam"] if lam is None else lam, d["e_max"] if e_max is None else e_max,
+                              d["dq_max"] if dq_max is None else dq_max)
+        q = np.array(seeds, float)
+        g = np.broadcast_to(np.asarray(targets, float), q.shape[:-1] + (3,))
+        for _ in range(int(iterations)):
+            q = self.ik_step(q, g, lam, e_max, dq_max)
+        d = g - self.end_effector(q)
+        return q, np.sqrt(np.sum(d * d, axis=-1))
+
     def get_state(self) -> np.ndarray:
         A = self.n
         out = np.empty(2 * A + 9)
@@ -372,6 +437,102 @@ class KinematicEnvironment:
             code = np.where(live, np.where(reached, 1, np.where(hit, 2, np.where(self_hit, 3, np.where(cell_hit, 4, 0)))), code)
             live = live & ~(reached | hit | self_hit | cell_hit)
         return Trace(code, steps, dist, min_clear, min_self, score, path, margins, min_cell, cell_margins)
+
+
+def spd3_solve(M, e):
+    """y with M y = e for symmetric positive definite M[..., 3, 3] and e[..., 3], in closed form: the adjugate over the determinant
+    (only M's upper triangle is read)."""
+    M, e = np.asarray(M, float), np.asarray(e, float)
+    m00, m01, m02, m11, m12, m22 = M[..., 0, 0], M[..., 0, 1], M[..., 0, 2], M[..., 1, 1], M[..., 1, 2], M[..., 2, 2]
+    c00, c01, c02 = m11 * m22 - m12 * m12, m02 * m12 - m01 * m22, m01 * m12 - m02 * m11
+    c11, c12, c22 = m00 * m22 - m02 * m02, m01 * m02 - m00 * m12, m00 * m11 - m01 * m01
+    det = m00 * c00 + m01 * c01 + m02 * c02
+    e0, e1, e2 = e[..., 0], e[..., 1], e[..., 2]
+    return np.stack([c00 * e0 + c01 * e1 + c02 * e2, c01 * e0 + c11 * e1 + c12 * e2, c02 * e0 + c12 * e1 + c22 * e2], axis=-1) / det[..., None]
+
+
+def joint_distance32(q, q_start) -> np.ndarray:
+    """max_m |q_m - q_start_m| in float32, operation for operation what the device forms (one subtraction per joint, exact abs / max)"""
+    q, q_start = np.asarray(q, np.float32), np.asarray(q_start, np.float32)
+    return np.max(np.abs(q - q_start), axis=-1)
+
+
+def select_goal_pose(residual, joint_distance, clearance, self_clearance, cell_clearance, tolerance: float, margin: float = 0.0):
+    """The selection among the R candidates of each query, arrays [..., R] (clearance already minus the obstacle radius; +inf where
+    there are no pairs / no workcell): class 0 = converged (residual <= tolerance) and free (all three clearances >= margin),
+    1 = converged but not free, 2 = not converged. The lowest class wins; inside classes 0 and 1 the smallest joint_distance,
+    inside class 2 the smallest residual; ties go to the lowest r. Returns (choice[...], class[...]): reachable iff class <= 1, free
+    iff class == 0. Every comparison is made on the values as given, so float32 inputs give the device's answer bit for bit."""
+    residual, jd = np.asarray(residual), np.asarray(joint_distance)
+    free = (np.asarray(clearance) >= margin) & (np.asarray(self_clearance) >= margin) & (np.asarray(cell_clearance) >= margin)
+    cls = np.where(residual <= tolerance, np.where(free, 0, 1), 2)
+    value = np.where(cls == 2, residual, jd).astype(np.float64)
+    R = cls.shape[-1]
+    best_c, best_v, best_r = cls[..., 0], value[..., 0], np.zeros(cls.shape[:-1], np.int64)
+    for r in range(1, R):
+        c, v = cls[..., r], value[..., r]
+        take = (c < best_c) | ((c == best_c) & (v < best_v))
+        best_c, best_v, best_r = np.where(take, c, best_c), np.where(take, v, best_v), np.where(take, r, best_r)
+    return best_r, best_c
+
+
+class GoalPoses(NamedTuple):
+    """Goal poses of N queries (ManipulatorFramework.solve_goal_poses): per query the restart the selection rule chose."""
+    reachable: np.ndarray             # [N] bool: a restart converged (|target - end effector| <= tolerance)
+    free: np.ndarray                  # [N] bool: ... and its pose keeps clearance_margin from obstacle, arm and workcell
+    joint_positions: np.ndarray       # [N][A]: the chosen pose, entry m = involved_joints[m] (not a goal pose where not reachable)
+    residual: np.ndarray              # [N]: |target - end effector| at that pose
+    clearance: np.ndarray             # [N]: arm to obstacle surface at that pose
+    self_clearance: np.ndarray        # [N]: +inf without self-collision pairs
+    cell_clearance: np.ndarray        # [N]: +inf without a workcell
+    joint_distance: np.ndarray        # [N]: max_m |pose_m - start pose_m|, the straight joint-space distance in the max-norm
+    restart: np.ndarray               # [N] int: the chosen restart; 0 is the one seeded with the start pose
+    converged_restarts: np.ndarray    # [N] int: how many of the restarts converged
+
+
+def ik_restarts_ok(restarts) -> bool:
+    return isinstance(restarts, (int, np.integer)) and not isinstance(restarts, bool) and 1 <= restarts <= 64 and \
+        (restarts & (restarts - 1)) == 0
+
+
+def ik_seeds(model: ChainModel, n_queries: int, restarts: int, seed: int) -> np.ndarray:
+    """[N][R][A] float32: the seed poses of restarts 1 .. R - 1, uniform inside the limits (+-pi for a revolute joint without
+    limits) from numpy's default Generator of `seed`; entry [n][0] is not a seed (restart 0 starts at the query's start pose) and
+    holds zeros."""
+    lo = np.array([j.lower if j.limited else -np.pi for j in model.joints])
+    hi = np.array([j.upper if j.limited else np.pi for j in model.joints])
+    out = np.zeros((n_queries, restarts, model.A), np.float32)
+    draw = np.random.default_rng(seed).uniform(lo, hi, (n_queries, restarts - 1, model.A)).astype(np.float32)
+    out[:, 1:] = np.minimum(np.maximum(draw, lo.astype(np.float32)), hi.astype(np.float32))     # (the limits as the device holds them)
+    return out
+
+
+def gather_goal_poses(choice, cls, q, residual, clearance, self_clearance, cell_clearance, joint_distance, tolerance) -> GoalPoses:
+    """GoalPoses from the per-candidate arrays [N][R](, [A]) and the selection (choice[N], class[N])"""
+    pick = np.asarray(choice, np.int64)[:, None]
+    take = lambda a: np.take_along_axis(np.asarray(a), pick, axis=1)[:, 0]      # noqa: E731
+    cls = np.asarray(cls)
+    return GoalPoses(cls <= 1, cls == 0, np.take_along_axis(np.asarray(q), pick[:, :, None], axis=1)[:, 0], take(residual),
+                     take(clearance), take(self_clearance), take(cell_clearance), take(joint_distance), pick[:, 0],
+                     np.sum(np.asarray(residual) <= tolerance, axis=1))
+
+
+def goal_poses_host(twin: KinematicEnvironment, q0, targets, obstacles, restarts: int = 8, iterations: int = 32,
+                    tolerance: float = 1e-3, margin: float = 0.0, seed: int = 0, **constants) -> GoalPoses:
+    """solve_goal_poses through the twin alone, under the device's rule and on the values the device is given: start poses,
+    targets, obstacles and seeds rounded to float32, the iteration and the clearances in float64, joint_distance in float32."""
+    r32 = lambda a: np.asarray(a, np.float64).astype(np.float32).astype(np.float64)      # noqa: E731
+    q0, targets, obstacles = r32(q0), r32(targets), r32(obstacles)
+    N, R = len(q0), int(restarts)
+    seeds = ik_seeds(twin.model, N, R, seed).astype(np.float64)
+    seeds[:, 0] = q0
+    q, residual = twin.solve_ik(targets[:, None, :], seeds, iterations=iterations, **constants)
+    obstacle = np.broadcast_to(obstacles[:, None, :], q.shape[:-1] + (3,))
+    clear = twin.clearance(q, obstacle) - twin.obstacle_radius
+    self_clear, cell_clear = twin.self_clearance(q) + np.zeros(clear.shape), twin.cell_clearance(q) + np.zeros(clear.shape)
+    jd = joint_distance32(q, q0[:, None, :])
+    choice, cls = select_goal_pose(residual, jd, clear, self_clear, cell_clear, tolerance, margin)
+    return gather_goal_poses(choice, cls, q, residual, clear, self_clear, cell_clear, jd, tolerance)
 
 
 def cell_box_gaps(model: ChainModel, centre, half) -> np.ndarray:

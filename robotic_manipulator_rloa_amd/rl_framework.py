@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from .environment.kinematic import (SCENE_CONDITIONS, KinematicEnvironment, build_kinematic, cell_box_gaps, choose_scene,
-                                    reach_queries)
+                                    goal_poses_host, ik_restarts_ok, reach_queries)
 from .environment.synthetic import SyntheticEnvironment
 from .environment.urdf_chain import SCENE_TRIES, TARGET_THRESHOLD, cell_geometry_name
 from .naf_components.naf_algorithm import NAFAgent
@@ -258,7 +258,7 @@ class ManipulatorFramework:
         return summary
 
     def reach_targets(self, targets, obstacles=None, initial_joint_positions=None, frames: int = 400, noise_scale: float = 0.0,
-                      n_envs: Optional[int] = None, trajectories: bool = True):
+                      n_envs: Optional[int] = None, trajectories: bool = True, goal_poses: bool = False):
         """Roll the trained policy out to GIVEN targets (kinematic environment only; on the device, thousands at once): query i
         starts at initial_joint_positions[i], with target targets[i] and obstacle obstacles[i], and runs until it reaches the
         target, touches the obstacle, itself or the workcell, or has taken `frames` steps. A query whose start pose is already in contact or at
@@ -273,7 +273,10 @@ class ManipulatorFramework:
         'frames'), frames, final_distance, min_clearance, min_self_clearance, min_cell_clearance, score, joint_positions
         [N][frames + 1][A] (None with trajectories=False; a finished query repeats its final pose) and start_distance /
         start_clearance / start_self_clearance / start_cell_clearance, the measures at the start pose (the workcell's are +inf
-        without a workcell). The agent is only read: training can go on afterwards."""
+        without a workcell). The agent is only read: training can go on afterwards.
+        goal_poses=True (needs trajectories): the result's `goal` is solve_goal_poses() of the same queries and start poses, and
+        `path_ratio` [N] the policy's joint path length — max-norm per frame, summed over its frames — over goal.joint_distance,
+        NaN where the query did not reach or has no free goal pose. Both are None otherwise, and nothing else changes."""
         if not self.env:
             raise EnvironmentNotInitialized
         if not self.naf_agent:
@@ -292,9 +295,68 @@ class ManipulatorFramework:
                                                            nominal_obstacle=nominal, nominal_start=env.initial_joint_positions)
         except ValueError as err:
             raise InvalidEnvironmentParameter(str(err)) from None
-        return self.naf_agent.rollout_vectorized(env.model, targets, obstacles, q0, frames=frames, noise_scale=float(noise_scale),
-                                                 n_envs=n_envs, trajectories=bool(trajectories),
-                                                 scene={'obstacle_radius': env.obstacle_radius})
+        if goal_poses and not trajectories:
+            raise InvalidEnvironmentParameter('reach_targets(goal_poses=True) measures the joint path: it needs trajectories=True')
+        result = self.naf_agent.rollout_vectorized(env.model, targets, obstacles, q0, frames=frames, noise_scale=float(noise_scale),
+                                                   n_envs=n_envs, trajectories=bool(trajectories),
+                                                   scene={'obstacle_radius': env.obstacle_radius})
+        if goal_poses:
+            result.goal = self.solve_goal_poses(targets, obstacles, q0)
+            path = np.asarray(result.joint_positions, np.float64)
+            length = np.sum(np.max(np.abs(np.diff(path, axis=1)), axis=2), axis=1)
+            with np.errstate(divide='ignore', invalid='ignore'):
+                ratio = length / np.asarray(result.goal.joint_distance, np.float64)
+            result.path_ratio = np.where((np.asarray(result.outcome) == 'reached') & result.goal.free, ratio, np.nan)
+        return result
+
+    def solve_goal_poses(self, targets, obstacles=None, initial_joint_positions=None, restarts: int = 8, iterations: int = 32,
+                         tolerance: float = 1e-3, clearance_margin: float = 0.0, seed: int = 0, on_device: Optional[bool] = None):
+        """Joint values that put the end effector on GIVEN targets (kinematic environment only; needs no agent): per query a
+        damped least-squares iteration on the end effector's positional Jacobian from `restarts` seeds — the start pose and
+        restarts - 1 poses drawn uniformly inside the limits from `seed` — for `iterations` updates each, then the choice among
+        them: a converged (|target - end effector| <= tolerance) pose that keeps clearance_margin from the obstacle, the arm itself
+        and the workcell before a converged one in contact before the nearest miss, and among equals the one nearest the start
+        pose in the joints' max-norm (environment/kinematic.py: ik_step, select_goal_pose). Contact plays no part in the iteration.
+          targets, obstacles, initial_joint_positions : as reach_targets() takes them
+          restarts    : a power of two, 1 .. 64
+          on_device   : None: the device when there is one; False: the float64 host twin under the same rule (slow: a chain walk
+                        per update and candidate)
+        Returns environment.kinematic.GoalPoses, arrays over the queries: reachable, free, joint_positions [N][A], residual,
+        clearance, self_clearance, cell_clearance, joint_distance, restart, converged_restarts."""
+        if not self.env:
+            raise EnvironmentNotInitialized
+        if not isinstance(self.env, KinematicEnvironment):
+            raise ConfigurationIncomplete('solve_goal_poses() needs the kinematic environment (initialize_kinematic_environment()): '
+                                          'PyBullet and the synthetic stand-in have no chain model to solve on')
+        env = self.env
+        if not ik_restarts_ok(restarts):
+            raise InvalidEnvironmentParameter(f'restarts is a power of two from 1 to 64: got {restarts!r}')
+        if not _positive_int(iterations):
+            raise InvalidEnvironmentParameter(f'iterations is a positive number of updates: got {iterations!r}')
+        if not (isinstance(tolerance, (int, float)) and np.isfinite(tolerance) and tolerance > 0.0):
+            raise InvalidEnvironmentParameter(f'tolerance is a positive length: got {tolerance!r}')
+        if not (isinstance(clearance_margin, (int, float)) and np.isfinite(clearance_margin)):
+            raise InvalidEnvironmentParameter(f'clearance_margin is a finite length: got {clearance_margin!r}')
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or seed < 0:
+            raise InvalidEnvironmentParameter(f'seed is a non-negative integer: got {seed!r}')
+        nominal = env.obstacle_centre if env.scene_ranges_on else env.obstacle_pos
+        try:
+            q0, targets, obstacles, _ = reach_queries(env.model, targets, obstacles, initial_joint_positions, 1,
+                                                      nominal_obstacle=nominal, nominal_start=env.initial_joint_positions)
+        except ValueError as err:
+            raise InvalidEnvironmentParameter(str(err)) from None
+        kw = dict(restarts=int(restarts), iterations=int(iterations), tolerance=float(tolerance), margin=float(clearance_margin),
+                  seed=int(seed))
+        if on_device is None:
+            on_device = torch.cuda.is_available()
+        if not on_device:
+            return goal_poses_host(env, q0, targets, obstacles, **kw)
+        from .engine import GoalPoseSolver
+        key = (env.model.digest(), float(env.obstacle_radius))
+        if getattr(self, '_goal_solver', None) is None or self._goal_solver[0] != key:
+            self._goal_solver = None
+            self._goal_solver = (key, GoalPoseSolver(env.model, env.obstacle_radius))
+        return self._goal_solver[1].solve(q0, targets, obstacles, **kw)
 
     # ---- environment ------------------------------------------------------------------------------------------------
     def initialize_environment(self, manipulator_file: str, endeffector_index: int, fixed_joints: List[int],
