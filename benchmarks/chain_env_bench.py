@@ -41,6 +41,16 @@ launches are the box instantiations, which test the floor and the spheres too.
       two unmeasured ones; the reachable and free shares; and the float64 host twin's seconds on the first 64 of the queries,
       with its time for all N EXTRAPOLATED from those 64 (it is linear in N) — that figure is not a measurement.
 
+  python benchmarks/chain_env_bench.py path [--envs 2048] [--launches 20] [--boxes]
+      collision-checked joint paths on --urdf with self-collision inside the --workcell cell (always on for this subcommand): N =
+      --envs queries (default 2048 here) x C = 16 candidate vias x S = 256 samples. Microseconds per naf_chain_path_check launch
+      between device events (median and minimum of `--launches` after two unmeasured ones), and in the same process the
+      composition it replaces — naf_chain_env_reset_given + naf_chain_env_probe + naf_chain_env_probe_cell at E = N C S over the
+      materialised poses (the fused launch's own poses_out), in chunks of 2^20 envs — with the bytes each form allocates and the
+      largest difference between their minima. Then the README's question on 2000 targets around the nominal one: the goal poses
+      (GoalPoseSolver), the paths to them (JointPathChecker, 16 candidates, resolution 0.02) and the shares of 'straight' / 'via' /
+      'blocked' among the queries with a free goal pose.
+
 `--hindsight R` (rate): the chain runs relabel a share R of every minibatch (NAFAgent.run_vectorized(hindsight=R)). Such a run
 wants an empty ring, so with the flag — also `--hindsight 0`, the figure to compare with — the warm-up steps run on an agent of
 their own and the timed run starts on a fresh one (its graph captures are inside the timed window, in both).
@@ -322,6 +332,92 @@ def ik(a):
                       "kernel_registers": regs}))
 
 
+def paths(a):
+    import numpy as np
+    import torch
+    from robotic_manipulator_rloa_amd import _lib
+    from robotic_manipulator_rloa_amd.engine import GoalPoseSolver, JointPathChecker
+    from robotic_manipulator_rloa_amd.environment.kinematic import path_vias
+    from robotic_manipulator_rloa_amd.environment.urdf_chain import compile_chain, load_urdf
+    N, C, S, n = (2048 if a.envs == 64 else a.envs), 16, 256, a.joints
+    launches = min(a.launches, 50)
+    a.workcell = True
+    urdf = os.path.abspath(a.urdf) if os.path.isabs(a.urdf) else os.path.join(ROOT, a.urdf)
+    init = ([0.0, 0.6, 0.0, -1.2, 0.0, 0.8, 0.0] + [0.0] * n)[:n]
+    model = compile_chain(load_urdf(urdf), n - 1, list(range(n)), [n], init, [0.1] * n, 0.03, consider_autocollision=True, **_workcell(a))
+    lib, dev, stream = _lib.load(), torch.device("cuda:0"), torch.cuda.current_stream().cuda_stream
+    rng = np.random.default_rng(5)
+    lo = np.array([j.lower if j.limited else -np.pi for j in model.joints])
+    hi = np.array([j.upper if j.limited else np.pi for j in model.joints])
+    q_start, q_goal = np.tile(np.float32(init), (N, 1)), rng.uniform(lo, hi, (N, n)).astype(np.float32)
+    obstacles = (np.array([0.35, 0.2, 0.45]) + rng.uniform(-0.2, 0.2, (N, 3))).astype(np.float32)
+    checker = JointPathChecker(model, 0.06)
+    checker.load(q_start, q_goal, obstacles, path_vias(model, q_start, q_goal, C, 0))
+    fused = []
+    for i in range(launches + 2):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        checker.launch(N, C, S, 0.0)
+        t1.record()
+        t1.synchronize()
+        if i >= 2:
+            fused.append(1e3 * t0.elapsed_time(t1))
+    # the composition, over the very poses the fused launch forms
+    E, chunk = N * C * S, 1 << 20
+    poses = torch.empty(E, n, device=dev)
+    _lib.check(lib.naf_chain_path_check(checker._chain_env, checker.q_start.data_ptr(), checker.q_goal.data_ptr(), checker.vias.data_ptr(),
+                                        checker.obstacles.data_ptr(), 0.06, N, C, S, 0.0, checker.out.data_ptr(), poses.data_ptr(), stream),
+               "path_check")
+    scene = torch.zeros(E, 6, device=dev)
+    scene[:, 3:] = checker.obstacles[:N].repeat_interleave(C * S, dim=0)
+    st = torch.zeros(chunk, lib.naf_chain_env_state_floats(checker._chain_env), device=dev)
+    obs, probe, cell = torch.zeros(chunk, 2 * n + 9, device=dev), torch.zeros(E, 5, device=dev), torch.zeros(E, device=dev)
+    composed = []
+    for i in range(max(2, launches // 5) + 1):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for first in range(0, E, chunk):
+            e = min(chunk, E - first)
+            _lib.check(lib.naf_chain_env_reset_given(checker._chain_env, st.data_ptr(), obs.data_ptr(), e, poses[first:].data_ptr(),
+                                                     scene[first:].data_ptr(), 0.06, stream), "reset_given")
+            _lib.check(lib.naf_chain_env_probe(checker._chain_env, st.data_ptr(), probe[first:].data_ptr(), e, stream), "probe")
+            _lib.check(lib.naf_chain_env_probe_cell(checker._chain_env, st.data_ptr(), cell[first:].data_ptr(), e, stream), "probe_cell")
+        t1.record()
+        t1.synchronize()
+        if i >= 1:
+            composed.append(1e3 * t0.elapsed_time(t1))
+    rec = checker.out[:N * C]
+    mins = torch.stack([probe[:, 3].view(N * C, S).min(dim=1).values, probe[:, 4].view(N * C, S).min(dim=1).values,
+                        cell.view(N * C, S).min(dim=1).values], dim=1)
+    gap = float((rec[:, :3] - mins).abs().max())
+    floats = lambda *ts: int(sum(t.numel() for t in ts) * 4)      # noqa: E731
+    fused_bytes = floats(checker.q_start[:N], checker.q_goal[:N], checker.obstacles[:N], checker.vias[:N * C], checker.out[:N * C])
+    composed_bytes = floats(poses, scene, st, obs, probe, cell)
+    del poses, scene, st, obs, probe, cell
+    # the README's question: can the goal be driven to? 2000 targets around the nominal one
+    M = 2000
+    targets = np.array([0.45, 0.3, 0.6]) + rng.uniform(-0.25, 0.25, (M, 3))
+    start, obstacle = np.tile(init, (M, 1)), np.tile([0.35, 0.2, 0.45], (M, 1))
+    goal = GoalPoseSolver(model, 0.06).solve(start, targets, obstacle)
+    ok = goal.free
+    found = checker.check(start[ok], goal.joint_positions[ok], obstacle[ok], candidates=C, resolution=0.02)
+    usage = json.load(open(_lib.USAGE_PATH)) if os.path.exists(_lib.USAGE_PATH) else {}
+    regs = {name: {q: v.get(q) for q in ("vgprs", "sgprs", "scratch_bytes_per_lane", "lds_bytes", "occupancy")}
+            for name, v in usage.items() if "chain_path_" in name}
+    print(json.dumps({"arm": os.path.basename(urdf), "queries": N, "candidates": C, "samples": S, "self_pairs": len(model.self_pairs),
+                      "workcell_pairs": len(model.cell_pairs), "boxes": bool(a.boxes),
+                      "us_per_path_check_launch": {"median": round(float(np.median(fused)), 1), "min": round(float(np.min(fused)), 1)},
+                      "us_per_reset_given_probe_probe_cell_over_all_poses": {"median": round(float(np.median(composed)), 1),
+                                                                            "min": round(float(np.min(composed)), 1)},
+                      "bytes_fused": fused_bytes, "bytes_composed": composed_bytes, "largest_difference_of_the_minima": gap,
+                      "blocked_candidates_share": round(float((rec[:, 4] > 0).float().mean()), 4),
+                      "targets": M, "free_goal_poses": int(ok.sum()),
+                      "outcome_shares_among_free_goals": {k: round(float(np.mean(found.outcome == k)), 4)
+                                                          for k in ("straight", "via", "blocked", "start", "goal")},
+                      "median_samples": int(np.median(found.samples)), "largest_sample_step": round(float(found.sample_step.max()), 5),
+                      "kernel_registers": regs}))
+
+
 def kernels(a):
     import numpy as np
     import torch
@@ -360,7 +456,7 @@ def kernels(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["rate", "kernels", "step", "rollout", "gather", "ik"])
+    ap.add_argument("what", choices=["rate", "kernels", "step", "rollout", "gather", "ik", "path"])
     ap.add_argument("--urdf", default=os.path.join("tests", "golden", "urdf", "iiwa_like7.urdf"))
     ap.add_argument("--joints", type=int, default=7)
     ap.add_argument("--envs", type=int, default=64)
@@ -372,7 +468,7 @@ def main():
     ap.add_argument("--standin-only", action="store_true")
     ap.add_argument("--autocollision", action="store_true")
     ap.add_argument("--workcell", action="store_true", help="step / rollout: a floor and two spheres in the chain model")
-    ap.add_argument("--boxes", action="store_true", help="step / rollout, with --workcell: three boxes beside the floor and the spheres")
+    ap.add_argument("--boxes", action="store_true", help="step / rollout / path, with --workcell: three boxes beside the floor and the spheres")
     ap.add_argument("--trajectory", action="store_true", help="rollout: record the joint values of every frame")
     ap.add_argument("--arm", default="", help="rate: a fixture arm of tests/golden/urdf by name, --joints its joint count")
     ap.add_argument("--target-range", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))
@@ -380,7 +476,7 @@ def main():
     ap.add_argument("--hindsight", type=float, default=None, help="rate, gather: the share of rows replayed under a hindsight goal")
     ap.add_argument("--horizon", type=int, default=None, help="rate, gather: hindsight_horizon (rate: max_frames; gather: 400)")
     a = ap.parse_args()
-    {"rate": rate, "kernels": kernels, "step": step, "rollout": rollout, "gather": gather, "ik": ik}[a.what](a)
+    {"rate": rate, "kernels": kernels, "step": step, "rollout": rollout, "gather": gather, "ik": ik, "path": paths}[a.what](a)
 
 
 if __name__ == "__main__":

@@ -894,6 +894,31 @@ int naf_chain_ik_select(naf_chain_env_t* h, const float* q_out, const float* q_s
                         const float* probe_dev, const float* cell_dev, int N, int R, float tolerance, float margin, int* choice_out,
                         int* class_out, float* joint_distance_out, void* stream);
 
+/* Joint paths (an addition within ABI 40): the sampled collision check of joint-space polylines start -> via -> goal, batched over
+ * queries and candidate vias. environment/kinematic.py (path_pose, check_joint_path) is the float64 statement. The check is SAMPLED:
+ * a verdict holds at the S poses and says nothing between them; out[6] reports how far apart they are.
+ *   A candidate is (query n, via c), index n C + c: the polyline q_start_dev[n] -> vias_dev[n][c] -> q_goal_dev[n] in the scene
+ *   obstacles_dev[n] with obstacle_radius. C is 1 .. 64; S a multiple of 64 in 64 .. 2048; h = S / 2.
+ *   the poses   : sample i < h lies on leg 1 at f = (float)i / (float)h (the start included, the via not), sample i >= h on leg 2
+ *                 at f = (float)(i - h) / (float)(h - 1) (the via and the goal included); q_m = fmaf(f, b_m - a_m, a_m) between the
+ *                 leg's end poses a and b. No limits are applied and nothing wraps: the end poses lie inside the limits.
+ *   per sample  : the obstacle clearance minus obstacle_radius and the self-clearance as naf_chain_env_probe reports them, and
+ *                 the workcell clearance as naf_chain_env_probe_cell does (+inf without pairs / without a workcell): the same
+ *                 walk. A sample is blocked iff one of the three is < margin.
+ *   out         : [N C][NAF_CHAIN_PATH_FLOATS] (DEVICE) = [0 .. 2] the minima over the samples of the three clearances | [3] the
+ *                 index of the first blocked sample, -1: none | [4] how many are blocked | [5] L1 + L2, L = max_m |b_m - a_m| of
+ *                 a leg (float32) | [6] max(L1 / h, L2 / (h - 1)), the sample step | [7] 1 iff sample S - 1, the goal pose, is
+ *                 blocked.
+ *   poses_out   : NULL, or DEVICE [N C][S][A]: every sample's pose (for tests).
+ * One workgroup per candidate, a lane per sample of a pass, S / lanes passes, one reduction by shuffles at the end, no atomics. With
+ * pairs the launch has the probe's shape (the handle's lanes and waves, its LDS). NAF_ERR_ARG, and no launch, for a null pointer
+ * other than poses_out, N < 1, N C > 2^30, C outside 1 .. 64, S no multiple of 64 in 64 .. 2048, a margin or radius that is not
+ * finite, or a negative radius. */
+#define NAF_CHAIN_PATH_FLOATS 8
+int naf_chain_path_check(naf_chain_env_t* h, const float* q_start_dev, const float* q_goal_dev, const float* vias_dev,
+                         const float* obstacles_dev, float obstacle_radius, int N, int C, int S, float margin, float* out,
+                         float* poses_out, void* stream);
+
 /* ---- one-shot gradient all-reduce over peer-mapped memory (no reference counterpart) ----------
  * The data-parallel exchange that follows loss.backward() (naf_algorithm.py:207-210 on every rank): sum of the flat
  * gradient over the W <= 8 GPUs of one node, each rank pushing its gradient into a receive slot on every peer over

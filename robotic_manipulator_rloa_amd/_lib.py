@@ -6,7 +6,9 @@ __graft_entry__.build() calls; hipcc cross-compiles without a GPU.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import gc
 import os
 import re
 import shutil
@@ -269,6 +271,7 @@ _PROTOS = {
     "naf_chain_env_step_tagged": [_vp, _vp, _vp, _vp, _vp, _i, _u64, _vp, _i, _vp, _i, _vp],
     "naf_chain_ik_solve": [_vp, _vp, _vp, _vp, _i, _i, IkParams, _vp, _vp, _vp, _vp],
     "naf_chain_ik_select": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp],
+    "naf_chain_path_check": [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _f, _vp, _vp, _vp],
 }
 _RESTYPES = {"naf_hip_arch": C.c_char_p}
 EXPORTED_SYMBOLS = tuple(_PROTOS)
@@ -419,3 +422,20 @@ def stream_ptr() -> int:
 
 def ptr(t) -> int:
     return t.data_ptr() if t is not None else None
+
+
+@contextlib.contextmanager
+def graph_capture(graph):
+    """torch.cuda.graph(graph) with the cyclic garbage collector held off. A collection that starts inside a capture runs the
+    finalizers of whatever dead cycles it finds — agents, engines and solvers of earlier work, whose __del__ free HIP resources
+    (hipFree of a handle, a captured graph's or an event's destruction) — and a capturing stream allows none of that: the process
+    aborts. torch collects before a capture only on request since 2.8, so nothing else keeps a collection out."""
+    import torch
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph):
+            yield
+    finally:
+        if was:
+            gc.enable()

@@ -41,6 +41,7 @@
 #include "../../include/naf_hip.h"
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <new>
 #include <type_traits>
@@ -299,17 +300,19 @@ __device__ static inline bool frame_geometry(const float* __restrict__ model, in
 // effector, target and obstacle into the observation `o` (not with PROBE: o is unused); the DRIVEN joints' velocity slots are the
 // caller's. Returns contact with the obstacle. CLEAR (the probe's walk, and the rollout step's beside its observation) also collects
 // the obstacle clearance in aux.clear. CELL: the workcell is tested too (frame_geometry).
-template <bool SC, bool PROBE, bool SCENE = false, bool CLEAR = PROBE, bool CELL = false, bool BOX = false>
-__device__ static inline bool chain_walk(const float* __restrict__ model, int A, int n_seg, const float* st, float* o, float* ee,
-                                         WalkAux& aux, SceneCand* cand = nullptr) {
+// chain_walk_at is the walk itself: joint m's value is joint(m), asked for once, in joint order, and the obstacle is given;
+// st is read only for the observation (not with PROBE). chain_walk below is the walk of a pose that lies in env_state.
+template <bool SC, bool PROBE, bool SCENE = false, bool CLEAR = PROBE, bool CELL = false, bool BOX = false, class Joint>
+__device__ static inline bool chain_walk_at(const float* __restrict__ model, int A, int n_seg, const Joint& joint, float ox, float oy,
+                                            float oz, float orad, const float* st, float* o, float* ee, WalkAux& aux,
+                                            SceneCand* cand = nullptr) {
     const int ee_frame = (int)model[4];
-    const float ox = st[A + 3], oy = st[A + 4], oz = st[A + 5], orad = st[A + 6];
     Frame F = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
     ee[0] = ee[1] = ee[2] = 0.f;
     bool hit = frame_geometry<SC, PROBE, SCENE, CLEAR, CELL, BOX>(model, A, 0, F, ox, oy, oz, orad, ee_frame, ee, aux, cand);
     for (int m = 0; m < A; ++m) {
         const float* j = model + CH_HDR + m * CH_JNT;
-        const float q = st[m];
+        const float q = joint(m);
         if constexpr (!PROBE) {
             const int slot = (int)j[21];
             if (slot >= 0) o[slot] = q;
@@ -362,6 +365,13 @@ __device__ static inline bool chain_walk(const float* __restrict__ model, int A,
         for (int k = 0; k < 3; ++k) { o[2 * A + k] = ee[k]; o[2 * A + 3 + k] = st[A + k]; o[2 * A + 6 + k] = st[A + 3 + k]; }
     }
     return hit;
+}
+
+template <bool SC, bool PROBE, bool SCENE = false, bool CLEAR = PROBE, bool CELL = false, bool BOX = false>
+__device__ static inline bool chain_walk(const float* __restrict__ model, int A, int n_seg, const float* st, float* o, float* ee,
+                                         WalkAux& aux, SceneCand* cand = nullptr) {
+    return chain_walk_at<SC, PROBE, SCENE, CLEAR, CELL, BOX>(
+        model, A, n_seg, [st](int m) { return st[m]; }, st[A + 3], st[A + 4], st[A + 5], st[A + 6], st, o, ee, aux, cand);
 }
 
 // The pair phase of an SC workgroup, entered by EVERY thread after the walking wave has stored the end points: returns, to
@@ -1357,6 +1367,145 @@ extern "C" int naf_chain_ik_select(naf_chain_env_t* h, const float* q_out, const
     if (!std::isfinite(tolerance) || !(tolerance >= 0.f) || !std::isfinite(margin)) return NAF_ERR_ARG;
     chain_ik_select_kernel<<<(unsigned)(((int64_t)N * R + 63) / 64), 64, 0, (hipStream_t)stream>>>(
         q_out, q_start_dev, residual_out, probe_dev, cell_dev, N, R, h->A, tolerance, margin, choice_out, class_out, joint_distance_out);
+    NAF_CHECK_LAUNCH();
+    return NAF_OK;
+}
+
+// ---- joint paths: the sampled collision check of start -> via -> goal polylines (include/naf_hip.h, "Joint paths") ---------------
+// One workgroup per candidate path (query n, via c); a lane is one sample of a pass, and the workgroup makes S / lanes passes — a
+// trip count the arguments fix. The sample's pose is never stored: the leg's two end poses are the same for the whole workgroup
+// (uniform loads), the lane's fraction f = (float)k / (float)n is its own, and the walk asks for joint m's value when it reaches
+// joint m: one fmaf. So there is no per-lane pose array, no LDS beside the pair phase's end points, and nothing in scratch.
+// SC is the probe's shape: wave 0 walks `lanes` samples and stages their capsules' end points as [segment][6][lane], every wave
+// joins the pair phase of every pass (its barriers), and only wave 0's lanes keep the running minima, the blocked count and the
+// first blocked index. Behind the last pass wave 0 reduces them by a butterfly of shuffles and lane 0 writes the record.
+template <bool SC, class... Cell>
+__global__ void __launch_bounds__(SC ? 64 * CH_MAX_WAVES : 64)
+chain_path_check_kernel(const float* __restrict__ model, const float* __restrict__ q_start, const float* __restrict__ q_goal,
+                        const float* __restrict__ vias, const float* __restrict__ obstacles, float orad, int C, int S, int A, int n_seg,
+                        int n_pairs, int lanes, float margin, float* __restrict__ out, float* __restrict__ poses_out, const Cell... cell) {
+    constexpr bool CELL = (std::is_same_v<Cell, ChainCell> || ... || false);
+    constexpr bool BOX = (std::is_same_v<Cell, ChainBox> || ... || false);
+    extern __shared__ __attribute__((aligned(16))) float ch_lds[];
+    const int64_t cand = blockIdx.x;
+    const int64_t n = cand / C;
+    const float* start = q_start + n * A;
+    const float* via = vias + cand * A;
+    const float* goal = q_goal + n * A;
+    const float ox = obstacles[n * 3], oy = obstacles[n * 3 + 1], oz = obstacles[n * 3 + 2];
+    const int lane = threadIdx.x & 63;
+    const bool active = lane < lanes;
+    const bool walker = active && threadIdx.x < 64;
+    const int h = S >> 1;
+    float min_clear = INFINITY, min_self = INFINITY, min_cell = INFINITY;
+    int first = INT_MAX, count = 0, goal_blocked = 0;
+    for (int base = 0; base < S; base += lanes) {      // (uniform: every thread takes every pass)
+        const int i = base + lane;
+        const bool second = i >= h;
+        const float f = second ? (float)(i - h) / (float)(h - 1) : (float)i / (float)h;
+        float ee[3];
+        WalkAux aux = {SC ? ch_lds + lane : nullptr, lanes, INFINITY, INFINITY};
+        if (walker) {
+            float* rec = poses_out ? poses_out + (cand * S + i) * A : nullptr;
+            chain_walk_at<SC, true, false, true, CELL, BOX>(
+                model, A, n_seg,
+                [=](int m) {
+                    const float v = via[m];
+                    const float a = second ? v : start[m], b = second ? goal[m] : v;
+                    const float q = fmaf(f, b - a, a);
+                    if (rec) rec[m] = q;
+                    return q;
+                },
+                ox, oy, oz, orad, nullptr, nullptr, ee, aux);
+        }
+        float self_clear = INFINITY;
+        if constexpr (SC) self_clear = self_clearance_phase(model, A, n_seg, n_pairs, ch_lds, lanes, lane, active);
+        if (walker) {
+            const float clear = aux.clear - orad;
+            const bool blocked = clear < margin || self_clear < margin || (CELL && aux.cell < margin);
+            min_clear = fminf(min_clear, clear);
+            min_self = fminf(min_self, self_clear);
+            if constexpr (CELL) min_cell = fminf(min_cell, aux.cell);
+            first = blocked && i < first ? i : first;
+            count += blocked ? 1 : 0;
+            goal_blocked |= blocked && i == S - 1 ? 1 : 0;
+        }
+    }
+    if (threadIdx.x >= 64) return;      // (behind the last barrier; wave 0 is whole: the lanes that walked nothing hold the identities)
+    for (int off = 32; off > 0; off >>= 1) {
+        min_clear = fminf(min_clear, __shfl_xor(min_clear, off));
+        min_self = fminf(min_self, __shfl_xor(min_self, off));
+        min_cell = fminf(min_cell, __shfl_xor(min_cell, off));
+        first = min(first, __shfl_xor(first, off));
+        count += __shfl_xor(count, off);
+        goal_blocked |= __shfl_xor(goal_blocked, off);
+    }
+    if (threadIdx.x != 0) return;
+    float l1 = 0.f, l2 = 0.f;
+    for (int m = 0; m < A; ++m) {
+        l1 = fmaxf(l1, fabsf(via[m] - start[m]));
+        l2 = fmaxf(l2, fabsf(goal[m] - via[m]));
+    }
+    float* o = out + cand * NAF_CHAIN_PATH_FLOATS;
+    o[0] = min_clear;
+    o[1] = min_self;
+    o[2] = min_cell;
+    o[3] = first == INT_MAX ? -1.f : (float)first;
+    o[4] = (float)count;
+    o[5] = l1 + l2;
+    o[6] = fmaxf(l1 / (float)h, l2 / (float)(h - 1));
+    o[7] = (float)goal_blocked;
+}
+
+// the SC path kernels' dynamic LDS is the probe's and may exceed the 64 KB a kernel gets unasked: raised once per device
+static int ch_path_raise_lds_limit() {
+    static bool raised_dev[64];
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return (int)e;
+    if (dev < 0 || dev >= 64) return NAF_ERR_ARG;
+    if (raised_dev[dev]) return NAF_OK;
+    for (const void* k : {(const void*)chain_path_check_kernel<true>, (const void*)chain_path_check_kernel<true, ChainCell>,
+                          (const void*)chain_path_check_kernel<true, ChainCell, ChainBox>}) {
+        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, CH_MAX_DYN_LDS);
+        if (e != hipSuccess) return (int)e;
+    }
+    raised_dev[dev] = true;
+    return NAF_OK;
+}
+
+template <class... Cell>
+static void ch_path_launch(naf_chain_env_t* h, const float* q_start, const float* q_goal, const float* vias, const float* obstacles,
+                           float orad, int N, int C, int S, float margin, float* out, float* poses_out, void* stream,
+                           const Cell... cell) {
+    const unsigned grid = (unsigned)((int64_t)N * C);
+    if (h->n_pairs > 0)
+        chain_path_check_kernel<true, Cell...><<<grid, 64 * h->waves, ch_lds_bytes(h->n_seg, h->lanes, h->waves), (hipStream_t)stream>>>(
+            h->model_dev, q_start, q_goal, vias, obstacles, orad, C, S, h->A, h->n_seg, h->n_pairs, h->lanes, margin, out, poses_out,
+            cell...);
+    else
+        chain_path_check_kernel<false, Cell...><<<grid, 64, 0, (hipStream_t)stream>>>(
+            h->model_dev, q_start, q_goal, vias, obstacles, orad, C, S, h->A, h->n_seg, 0, 64, margin, out, poses_out, cell...);
+}
+
+extern "C" int naf_chain_path_check(naf_chain_env_t* h, const float* q_start_dev, const float* q_goal_dev, const float* vias_dev,
+                                    const float* obstacles_dev, float obstacle_radius, int N, int C, int S, float margin, float* out,
+                                    float* poses_out, void* stream) {
+    if (!h || !q_start_dev || !q_goal_dev || !vias_dev || !obstacles_dev || !out) return NAF_ERR_ARG;
+    if (N < 1 || C < 1 || C > 64 || S < 64 || S > 2048 || S % 64 != 0 || (int64_t)N * C > (int64_t)1 << 30) return NAF_ERR_ARG;
+    if (!std::isfinite(margin) || !std::isfinite(obstacle_radius) || obstacle_radius < 0.f) return NAF_ERR_ARG;
+    if (h->n_pairs > 0) {
+        const int rc = ch_path_raise_lds_limit();
+        if (rc != NAF_OK) return rc;
+    }
+    if (h->n_box > 0)
+        ch_path_launch(h, q_start_dev, q_goal_dev, vias_dev, obstacles_dev, obstacle_radius, N, C, S, margin, out, poses_out, stream,
+                       ChainCell{}, ChainBox{});
+    else if (h->n_cell > 0)
+        ch_path_launch(h, q_start_dev, q_goal_dev, vias_dev, obstacles_dev, obstacle_radius, N, C, S, margin, out, poses_out, stream,
+                       ChainCell{});
+    else
+        ch_path_launch(h, q_start_dev, q_goal_dev, vias_dev, obstacles_dev, obstacle_radius, N, C, S, margin, out, poses_out, stream);
     NAF_CHECK_LAUNCH();
     return NAF_OK;
 }

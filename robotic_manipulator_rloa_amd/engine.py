@@ -12,6 +12,8 @@
                    frame, an env held at the end of its episode; outcome, clearances and joint paths come back (ReachResult).
   GoalPoseSolver : joint values that reach given targets on a chain model: batched damped least squares over queries x restarts,
                    the pinned clearances at the solved poses, the selection per query (GoalPoses). No agent, no graph.
+  JointPathChecker : sampled collision checks of start -> via -> goal joint paths on a chain model: ONE launch over queries x
+                   candidate vias x samples, eight floats per candidate back, the choice per query on the host (JointPaths).
 
 Graph capture goes through torch.cuda.CUDAGraph (= hipGraph on ROCm): the ctypes kernel launches use the
 stream torch reports as current, which inside the capture context is the capturing stream.
@@ -28,7 +30,8 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
-from .environment.kinematic import GoalPoses, gather_goal_poses, ik_seeds
+from .environment.kinematic import (PATH_CHUNK, PATH_FLOATS, GoalPoses, JointPaths, gather_goal_poses, gather_joint_paths, ik_seeds,
+                                    path_chunks, path_leg_lengths, path_vias)
 from .learner import ActPath, Learner
 from .presets import ROBOT_PRESETS, device_env_preset
 from .utils.replay_buffer import ReplayBuffer
@@ -61,7 +64,7 @@ def _capture(body, snapshot: _StateSnapshot, warmup: int = 2, after_warmup=None)
     if after_warmup is not None:
         after_warmup()
     g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
+    with _lib.graph_capture(g):
         body()
     snapshot.restore()                 # capture does not execute, but keep the contract explicit
     torch.cuda.synchronize()
@@ -1051,6 +1054,9 @@ class ReachResult:
     goal: Optional["GoalPoses"] = None         # reach_targets(goal_poses=True): the goal poses of the same queries and start poses
     path_ratio: Optional[np.ndarray] = None    # [N] float64: the policy's joint path length (max-norm, summed over its frames) over
                                                # goal.joint_distance; NaN where the query did not reach or has no free goal pose
+    path: Optional["JointPaths"] = None        # reach_targets(joint_paths=True): the collision-checked joint paths to goal's poses
+    planned_ratio: Optional[np.ndarray] = None  # [N] float64: the same joint path length over path.length; NaN where the query did
+                                               # not reach or no free path was found
 
 
 class DeviceRollout:
@@ -1253,3 +1259,70 @@ class GoalPoseSolver:
                                            probe[:, :, 3], probe[:, :, 4], cell.reshape(n, R),
                                            self.distance[:E].cpu().numpy().reshape(n, R), np.float32(tolerance)))
         return GoalPoses(*[np.concatenate([getattr(p, f) for p in parts]) for f in GoalPoses._fields])
+
+
+class JointPathChecker:
+    """Collision-checked joint paths on a chain model (csrc/chain_env.hip, "joint paths"): per chunk of queries ONE
+    naf_chain_path_check launch over queries x candidate vias, S sampled poses each, formed on the fly — no pose is materialised and
+    eight floats per candidate come back; the choice among a query's candidates is environment.kinematic.select_joint_path on the
+    host. Owns the handle and the buffers; needs no agent. A chunk holds at most `chunk` candidate-samples (queries x candidates x
+    S, whole queries) and its S is path_samples of its own legs (path_chunks); a candidate's record does not depend on where in a
+    launch it lies. The check is SAMPLED: see JointPaths."""
+
+    def __init__(self, chain, obstacle_radius: float = 0.06, chunk: Optional[int] = None, device=None):
+        import ctypes
+        _lib.require_gpu()
+        self.lib, self.chain, self.A = _lib.load(), chain, chain.A
+        self.dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        self.obstacle_radius = float(np.float32(obstacle_radius))
+        self.chunk = int(PATH_CHUNK if chunk is None else chunk)
+        if self.chunk < 64:
+            raise ValueError("JointPathChecker: a chunk holds at least 64 candidate-samples, one candidate path")
+        blob = np.ascontiguousarray(chain.pack(), np.float32)
+        self._chain_env = ctypes.c_void_p()
+        check(self.lib.naf_chain_env_create(blob.ctypes.data, int(blob.size), ctypes.byref(self._chain_env)), "chain_env_create")
+        K, A = self.chunk // 64, self.A                      # the most candidates a chunk can hold: S is at least 64
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        self.q_start, self.q_goal, self.obstacles = torch.zeros(K, A, **f32), torch.zeros(K, A, **f32), torch.zeros(K, 3, **f32)
+        self.vias, self.out = torch.zeros(K, A, **f32), torch.zeros(K, PATH_FLOATS, **f32)
+
+    def __del__(self):
+        if getattr(self, "_chain_env", None) is not None:
+            self.lib.naf_chain_env_destroy(self._chain_env)
+            self._chain_env = None
+
+    def launch(self, n: int, C: int, S: int, margin: float) -> None:
+        """the launch of one chunk of n queries x C candidates already in the buffers, on the current stream"""
+        check(self.lib.naf_chain_path_check(self._chain_env, ptr(self.q_start), ptr(self.q_goal), ptr(self.vias), ptr(self.obstacles),
+                                            self.obstacle_radius, n, C, S, margin, ptr(self.out), None, stream_ptr()),
+              "chain_path_check")
+
+    def load(self, q_start, q_goal, obstacles, vias) -> None:
+        """a chunk's queries into the buffers: q_start[n][A], q_goal[n][A], obstacles[n][3], vias[n][C][A] (float32)"""
+        n, C = vias.shape[:2]
+        self.q_start[:n].copy_(torch.from_numpy(np.ascontiguousarray(q_start, np.float32)))
+        self.q_goal[:n].copy_(torch.from_numpy(np.ascontiguousarray(q_goal, np.float32)))
+        self.obstacles[:n].copy_(torch.from_numpy(np.ascontiguousarray(obstacles, np.float32)))
+        self.vias[:n * C].copy_(torch.from_numpy(np.ascontiguousarray(vias, np.float32).reshape(n * C, self.A)))
+
+    def check(self, q_start, q_goal, obstacles, candidates: int = 16, resolution: float = 0.02, margin: float = 0.0,
+              seed: int = 0) -> JointPaths:
+        """q_start[N][A], q_goal[N][A] (action order), obstacles[N][3] -> JointPaths of numpy arrays (float32 where the device's)."""
+        A, C = self.A, int(candidates)
+        q_start = np.ascontiguousarray(q_start, np.float32).reshape(-1, A)
+        N = len(q_start)
+        q_goal, obstacles = np.ascontiguousarray(q_goal, np.float32).reshape(N, A), np.asarray(obstacles, np.float32).reshape(N, 3)
+        if 64 * C > self.chunk:
+            raise ValueError(f"JointPathChecker: a chunk of {self.chunk} candidate-samples does not hold one query's {C} candidates")
+        vias = path_vias(self.chain, q_start, q_goal, C, seed)
+        margin = float(np.float32(margin))
+        records, samples = np.empty((N, C, PATH_FLOATS), np.float32), np.empty(N, np.int64)
+        for first, n, S in path_chunks(path_leg_lengths(vias, q_start, q_goal), C, resolution, self.chunk):
+            if n * C * S > self.chunk:
+                raise ValueError(f"JointPathChecker: one query's {C} candidates at {S} samples exceed the chunk of {self.chunk}")
+            sl = slice(first, first + n)
+            self.load(q_start[sl], q_goal[sl], obstacles[sl], vias[sl])
+            self.launch(n, C, S, margin)
+            records[sl] = self.out[:n * C].cpu().numpy().reshape(n, C, PATH_FLOATS)
+            samples[sl] = S
+        return gather_joint_paths(records, vias, q_start, q_goal, samples)

@@ -535,6 +535,208 @@ def goal_poses_host(twin: KinematicEnvironment, q0, targets, obstacles, restarts
     return gather_goal_poses(choice, cls, q, residual, clear, self_clear, cell_clear, jd, tolerance)
 
 
+# ---- joint paths: the sampled collision check of start -> via -> goal polylines (include/naf_hip.h, "Joint paths") ----------------
+PATH_FLOATS = 8                       # NAF_CHAIN_PATH_FLOATS
+PATH_SAMPLES_MIN, PATH_SAMPLES_MAX = 64, 2048
+PATH_CANDIDATES_MAX = 64
+PATH_CHUNK = 1 << 23                  # candidate-samples per chunk, on the device and through the twin alike
+PATH_OUTCOMES = ("straight", "via", "blocked", "start", "goal")
+
+
+def path_samples_ok(S) -> bool:
+    return isinstance(S, (int, np.integer)) and not isinstance(S, bool) and PATH_SAMPLES_MIN <= S <= PATH_SAMPLES_MAX and S % 64 == 0
+
+
+def path_pose(a, via, b, i, S: int) -> np.ndarray:
+    """Sample i of the S poses of the joint-space polyline a -> via -> b, in float64; a, via, b [..., A] and i [...] broadcast.
+    With h = S / 2: i < h lies on leg 1 at f = i / h (the start included, the via not), i >= h on leg 2 at f = (i - h) / (h - 1)
+    (the via and the goal included); q_m = lo_m + f (hi_m - lo_m) between the leg's end poses, and the end pose itself at f = 1. No
+    limits are applied and an unlimited revolute joint is interpolated numerically, with no wrap-around."""
+    a, via, b = np.asarray(a, float), np.asarray(via, float), np.asarray(b, float)
+    i, h = np.asarray(i), int(S) // 2
+    second = i >= h
+    f = np.where(second, (i - h) / (h - 1), i / h)[..., None]
+    lo, hi = np.where(second[..., None], via, a), np.where(second[..., None], b, via)
+    return np.where(f == 1.0, hi, lo + f * (hi - lo))
+
+
+def check_joint_path(twin: KinematicEnvironment, q_start, via, q_goal, obstacle, S: int, margin: float = 0.0) -> np.ndarray:
+    """[..., PATH_FLOATS] float64: the record of the candidate paths q_start[..., A] -> via[..., A] -> q_goal[..., A] in the scenes
+    obstacle[..., 3] (all broadcast), sampled at the S poses of path_pose: [0] [1] [2] the minima over the samples of the obstacle
+    clearance (the obstacle radius subtracted), the self-clearance and the workcell clearance | [3] the index of the first blocked
+    sample, -1: none | [4] how many are blocked | [5] L1 + L2 with L = joint_distance32 of a leg, in float32 | [6] the sample step
+    max(L1 / h, L2 / (h - 1)), in float32 | [7] 1 iff the last sample, the goal pose, is blocked. A sample is blocked iff one of
+    its three clearances is < margin. SAMPLED: the verdict holds at the samples and says nothing between them."""
+    if not path_samples_ok(S):
+        raise ValueError(f"S is a multiple of 64 from {PATH_SAMPLES_MIN} to {PATH_SAMPLES_MAX}: got {S!r}")
+    q_start, via, q_goal = np.broadcast_arrays(np.asarray(q_start, float), np.asarray(via, float), np.asarray(q_goal, float))
+    lead = via.shape[:-1]
+    obstacle = np.broadcast_to(np.asarray(obstacle, float), lead + (3,))
+    q = path_pose(q_start[..., None, :], via[..., None, :], q_goal[..., None, :], np.arange(S), S)
+    clear = twin.clearance(q, obstacle[..., None, :]) - twin.obstacle_radius
+    self_clear, cell_clear = twin.self_clearance(q) + np.zeros(clear.shape), twin.cell_clearance(q) + np.zeros(clear.shape)
+    blocked = (clear < margin) | (self_clear < margin) | (cell_clear < margin)
+    h = np.float32(S // 2)
+    l1, l2 = joint_distance32(via, q_start), joint_distance32(q_goal, via)
+    out = np.empty(lead + (PATH_FLOATS,))
+    out[..., 0], out[..., 1], out[..., 2] = clear.min(axis=-1), self_clear.min(axis=-1), cell_clear.min(axis=-1)
+    out[..., 3] = np.where(blocked.any(axis=-1), np.argmax(blocked, axis=-1), -1)
+    out[..., 4] = blocked.sum(axis=-1)
+    out[..., 5] = l1 + l2
+    out[..., 6] = np.maximum(l1 / h, l2 / (h - np.float32(1.0)))
+    out[..., 7] = blocked[..., -1]
+    return out
+
+
+def path_vias(model: ChainModel, q_start, q_goal, candidates: int, seed: int) -> np.ndarray:
+    """[N][C][A] float32: the via poses of the C candidate paths of each query, from the poses as float32 holds them. Candidate 0
+    is the midpoint 0.5 (a + b): the straight line. Candidate c >= 1 is mid + (2u - 1) w_c per joint, w_c = 0.5 2^((c - 1) mod 3)
+    max(D, 0.5) with D the straight max-norm distance, u from ONE np.random.default_rng(seed).random((N, C - 1, A)) call; clipped
+    into the limits of limited joints (as the device holds them), so every sample of every candidate lies inside the limits."""
+    a = np.asarray(q_start, np.float32).astype(np.float64).reshape(-1, model.A)
+    b = np.asarray(q_goal, np.float32).astype(np.float64).reshape(-1, model.A)
+    N, C = len(a), int(candidates)
+    mid = 0.5 * (a + b)
+    D = np.max(np.abs(b - a), axis=-1)
+    out = np.empty((N, C, model.A))
+    out[:, 0] = mid
+    if C > 1:
+        u = np.random.default_rng(seed).random((N, C - 1, model.A))
+        w = 0.5 * 2.0 ** ((np.arange(1, C) - 1) % 3)[None, :, None] * np.maximum(D, 0.5)[:, None, None]
+        out[:, 1:] = mid[:, None, :] + (2.0 * u - 1.0) * w
+    lo = np.array([j.lower if j.limited else -np.inf for j in model.joints]).astype(np.float32)
+    hi = np.array([j.upper if j.limited else np.inf for j in model.joints]).astype(np.float32)
+    return np.minimum(np.maximum(out.astype(np.float32), lo), hi)
+
+
+def path_samples(lengths, resolution: float) -> int:
+    """S for legs of the given max-norm lengths: the smallest multiple of 64 whose sample step is <= resolution on the longest of
+    them — L / (S / 2 - 1), the coarser of the two legs' steps — capped at PATH_SAMPLES_MAX (the step is then what it is)."""
+    longest = float(np.max(lengths)) if np.size(lengths) else 0.0
+    for S in range(PATH_SAMPLES_MIN, PATH_SAMPLES_MAX, 64):
+        if longest / (S // 2 - 1) <= resolution:
+            return S
+    return PATH_SAMPLES_MAX
+
+
+def path_chunks(leg_lengths, candidates: int, resolution: float, budget: int = PATH_CHUNK) -> List[Tuple[int, int, int]]:
+    """[(first query, queries, S)]: consecutive queries share a chunk, and its S = path_samples of all its legs
+    (leg_lengths[N][C][2]), as long as queries x candidates x S stays within `budget` candidate-samples; a chunk holds at least
+    one query."""
+    longest = np.max(np.asarray(leg_lengths, float).reshape(len(leg_lengths), -1), axis=1)
+    out, first, N = [], 0, len(longest)
+    while first < N:
+        n, S = 1, path_samples(longest[first], resolution)
+        while first + n < N:
+            S2 = max(S, path_samples(longest[first + n], resolution))
+            if (n + 1) * candidates * S2 > budget:
+                break
+            n, S = n + 1, S2
+        out.append((first, n, S))
+        first += n
+    return out
+
+
+def select_joint_path(records) -> Tuple[np.ndarray, np.ndarray]:
+    """(outcome[N] str, candidate[N] int) from records[N][C][PATH_FLOATS]. A candidate is free iff [4] == 0; the free candidate
+    with the smallest length [5] wins, ties to the lowest c (candidate 0, the straight line, whenever it is free). 'start': candidate 0's [3] == 0, the start pose itself is blocked;
+    'goal': [7] == 1, the goal pose is; 'straight': candidate 0 wins; 'via': a candidate c >= 1 does; 'blocked': none is free.
+    start before goal before the rest; candidate is -1 wherever no path is returned. Every comparison is made on the values as
+    given, so the device's float32 records and the twin's are chosen from by the same rule."""
+    rec = np.asarray(records)
+    free = rec[..., 4] == 0
+    length = np.where(free, rec[..., 5].astype(np.float64), np.inf)
+    # No polyline is shorter than the straight line (the triangle inequality), and in the max-norm many are exactly as long; the
+    # float32 sum L1 + L2 may then come out an ulp below candidate 0's. A free candidate 0 wins: the rule in exact arithmetic.
+    length[..., 0] = np.where(free[..., 0], -np.inf, np.inf)
+    best = np.argmin(length, axis=-1)                        # (the first of equal minima: ties to the lowest c)
+    found = free.any(axis=-1)
+    outcome = np.where(found, np.where(best == 0, "straight", "via"), "blocked").astype("<U8")
+    outcome = np.where(rec[..., 0, 7] == 1, "goal", outcome)
+    outcome = np.where(rec[..., 0, 3] == 0, "start", outcome)
+    return outcome, np.where((outcome == "straight") | (outcome == "via"), best, -1)
+
+
+class JointPaths(NamedTuple):
+    """Collision-checked joint paths of N queries (ManipulatorFramework.plan_joint_paths). The check is SAMPLED: a free verdict
+    holds at the `samples` poses of the path, `sample_step` apart in the joints' max-norm; nothing certifies the path between them."""
+    outcome: np.ndarray                 # [N] str: 'straight' | 'via' | 'blocked' | 'start' | 'goal' (select_joint_path)
+    candidate: np.ndarray               # [N] int: the chosen candidate, 0 = the straight line; -1: no free path
+    via: np.ndarray                     # [N][A]: its via pose, entry m = involved_joints[m]; NaN: no free path
+    length: np.ndarray                  # [N]: its length L1 + L2 in the joints' max-norm ('straight': straight_length); NaN: none
+    straight_length: np.ndarray         # [N]: max_m |goal_m - start_m|, what GoalPoses.joint_distance reports
+    min_clearance: np.ndarray           # [N]: least obstacle clearance over the samples of the chosen path; of the straight line
+    min_self_clearance: np.ndarray      # [N]: ... self-clearance, +inf without pairs         for 'blocked', 'start' and 'goal'
+    min_cell_clearance: np.ndarray      # [N]: ... workcell clearance, +inf without a workcell
+    straight_first_blocked: np.ndarray  # [N] int: the first blocked sample of the straight line, -1: it is free
+    sample_step: np.ndarray             # [N]: the largest max-norm distance between neighbouring samples of the reported path
+    samples: np.ndarray                 # [N] int: S, the samples per candidate path of the query's chunk
+    start: Optional[np.ndarray] = None  # [N][A]: the queries' start and goal poses, as checked (waypoints() needs them)
+    goal: Optional[np.ndarray] = None
+
+    def waypoints(self, n: int) -> np.ndarray:
+        """[N][n][A]: n >= 2 poses along each query's path, start and goal included, uniform in the path's length (max-norm):
+        the first leg takes the share L1 / (L1 + L2) of them. Resampled on the host, not the checked samples. NaN rows where
+        there is no free path."""
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 2:
+            raise ValueError(f"waypoints(n): n is a number of poses, at least 2: got {n!r}")
+        a, b, via = np.asarray(self.start, float), np.asarray(self.goal, float), np.asarray(self.via, float)
+        l1, l2 = np.max(np.abs(via - a), axis=-1), np.max(np.abs(b - via), axis=-1)
+        total = l1 + l2
+        with np.errstate(divide="ignore", invalid="ignore"):
+            split = np.where(total > 0.0, l1 / np.where(total > 0.0, total, 1.0), 0.5)[:, None]
+            t = np.linspace(0.0, 1.0, n)[None, :]
+            f1 = np.where(split > 0.0, t / np.where(split > 0.0, split, 1.0), 1.0)
+            f2 = np.where(split < 1.0, (t - split) / np.where(split < 1.0, 1.0 - split, 1.0), 0.0)
+        first = (t < split)[..., None]
+        leg1 = a[:, None, :] + f1[..., None] * (via - a)[:, None, :]
+        leg2 = np.where((f2 >= 1.0)[..., None], b[:, None, :], via[:, None, :] + f2[..., None] * (b - via)[:, None, :])
+        out = np.where(first, leg1, leg2)
+        return np.where((np.asarray(self.candidate) >= 0)[:, None, None], out, np.nan)
+
+
+def gather_joint_paths(records, vias, q_start, q_goal, samples) -> JointPaths:
+    """JointPaths from the records[N][C][PATH_FLOATS] of the vias[N][C][A] between q_start[N][A] and q_goal[N][A], and S per query"""
+    rec, vias = np.asarray(records), np.asarray(vias)
+    outcome, cand = select_joint_path(rec)
+    has = cand >= 0
+    pick = np.maximum(cand, 0)[:, None]
+    row = np.take_along_axis(rec, pick[:, :, None], axis=1)[:, 0]
+    straight = joint_distance32(q_goal, q_start)
+    length = np.where(has, np.where(cand == 0, straight, row[:, 5]), np.nan).astype(rec.dtype)
+    via = np.where(has[:, None], np.take_along_axis(vias, pick[:, :, None], axis=1)[:, 0], np.nan)
+    return JointPaths(outcome, cand, via, length, straight.astype(rec.dtype), row[:, 0].copy(), row[:, 1].copy(), row[:, 2].copy(),
+                      rec[:, 0, 3].astype(np.int64), row[:, 6].copy(), np.asarray(samples, np.int64), np.array(q_start),
+                      np.array(q_goal))
+
+
+def path_leg_lengths(vias, q_start, q_goal) -> np.ndarray:
+    """[N][C][2]: joint_distance32 of both legs of every candidate"""
+    vias = np.asarray(vias, np.float32)
+    a, b = np.asarray(q_start, np.float32)[:, None, :], np.asarray(q_goal, np.float32)[:, None, :]
+    return np.stack([joint_distance32(vias, a), joint_distance32(b, vias)], axis=-1)
+
+
+def joint_paths_host(twin: KinematicEnvironment, q_start, q_goal, obstacles, candidates: int = 16, resolution: float = 0.02,
+                     margin: float = 0.0, seed: int = 0, chunk: int = PATH_CHUNK) -> JointPaths:
+    """plan_joint_paths through the twin alone, under the device's rule and on the values the device is given: start and goal
+    poses, vias and obstacles rounded to float32, the poses and the clearances in float64, the lengths in float32. Chunks and
+    their S are the device's (path_chunks)."""
+    r32 = lambda a: np.asarray(a, np.float64).astype(np.float32).astype(np.float64)      # noqa: E731
+    q_start, q_goal, obstacles = r32(q_start), r32(q_goal), r32(obstacles)
+    N, C = len(q_start), int(candidates)
+    vias = path_vias(twin.model, q_start, q_goal, C, seed)
+    records, samples = np.empty((N, C, PATH_FLOATS)), np.empty(N, np.int64)
+    for first, n, S in path_chunks(path_leg_lengths(vias, q_start, q_goal), C, resolution, chunk):
+        samples[first:first + n] = S
+        block = max(1, 65536 // (C * S))                      # the twin holds every sample's segments at once: a few at a time
+        for k in range(first, first + n, block):
+            sl = slice(k, min(k + block, first + n))
+            records[sl] = check_joint_path(twin, q_start[sl, None, :], vias[sl].astype(np.float64), q_goal[sl, None, :],
+                                           obstacles[sl, None, :], S, margin)
+    return gather_joint_paths(records, vias, q_start, q_goal, samples)
+
+
 def cell_box_gaps(model: ChainModel, centre, half) -> np.ndarray:
     """[G + H + B]: how near the box centre +- half (a point when half is 0) comes to each workcell geometry. Against a half-space
     the box corner with the smallest n.x decides: min over the box of n.x - d = n.centre - |n|.half - d. Against a sphere: the

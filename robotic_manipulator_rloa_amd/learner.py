@@ -561,7 +561,7 @@ class Learner:
                 torch.cuda.synchronize(dev)
                 if capturable:
                     graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph):
+                    with _lib.graph_capture(graph):
                         body()
                     torch.cuda.synchronize(dev)
             except Exception as e:                           # noqa: BLE001

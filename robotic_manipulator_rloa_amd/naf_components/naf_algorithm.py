@@ -293,7 +293,7 @@ class NAFAgent:
                 torch.cuda.current_stream().wait_stream(side)
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
+                with _lib.graph_capture(g):
                     a.act()
                 a.counter.copy_(saved[0])
                 self._act_graph = g

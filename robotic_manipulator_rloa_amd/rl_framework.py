@@ -31,7 +31,8 @@ import numpy as np
 import torch
 
 from .environment.kinematic import (SCENE_CONDITIONS, KinematicEnvironment, build_kinematic, cell_box_gaps, choose_scene,
-                                    goal_poses_host, ik_restarts_ok, reach_queries)
+                                    goal_poses_host, ik_restarts_ok, joint_paths_host, reach_queries, JointPaths,
+                                    PATH_CANDIDATES_MAX)
 from .environment.synthetic import SyntheticEnvironment
 from .environment.urdf_chain import SCENE_TRIES, TARGET_THRESHOLD, cell_geometry_name
 from .naf_components.naf_algorithm import NAFAgent
@@ -258,7 +259,7 @@ class ManipulatorFramework:
         return summary
 
     def reach_targets(self, targets, obstacles=None, initial_joint_positions=None, frames: int = 400, noise_scale: float = 0.0,
-                      n_envs: Optional[int] = None, trajectories: bool = True, goal_poses: bool = False):
+                      n_envs: Optional[int] = None, trajectories: bool = True, goal_poses: bool = False, joint_paths: bool = False):
         """Roll the trained policy out to GIVEN targets (kinematic environment only; on the device, thousands at once): query i
         starts at initial_joint_positions[i], with target targets[i] and obstacle obstacles[i], and runs until it reaches the
         target, touches the obstacle, itself or the workcell, or has taken `frames` steps. A query whose start pose is already in contact or at
@@ -276,7 +277,11 @@ class ManipulatorFramework:
         without a workcell). The agent is only read: training can go on afterwards.
         goal_poses=True (needs trajectories): the result's `goal` is solve_goal_poses() of the same queries and start poses, and
         `path_ratio` [N] the policy's joint path length — max-norm per frame, summed over its frames — over goal.joint_distance,
-        NaN where the query did not reach or has no free goal pose. Both are None otherwise, and nothing else changes."""
+        NaN where the query did not reach or has no free goal pose. Both are None otherwise, and nothing else changes.
+        joint_paths=True (implies goal_poses): the result's `path` is plan_joint_paths() from the start poses to goal's poses, with
+        its defaults (queries without a reachable goal pose: outcome 'goal', NaN numbers), and `planned_ratio` [N] the same joint
+        path length over path.length — a path that can be driven at its samples, where the straight line may not be — NaN where
+        the query did not reach or no free path was found. Both are None otherwise, and nothing else changes."""
         if not self.env:
             raise EnvironmentNotInitialized
         if not self.naf_agent:
@@ -295,6 +300,7 @@ class ManipulatorFramework:
                                                            nominal_obstacle=nominal, nominal_start=env.initial_joint_positions)
         except ValueError as err:
             raise InvalidEnvironmentParameter(str(err)) from None
+        goal_poses = bool(goal_poses or joint_paths)
         if goal_poses and not trajectories:
             raise InvalidEnvironmentParameter('reach_targets(goal_poses=True) measures the joint path: it needs trajectories=True')
         result = self.naf_agent.rollout_vectorized(env.model, targets, obstacles, q0, frames=frames, noise_scale=float(noise_scale),
@@ -307,7 +313,116 @@ class ManipulatorFramework:
             with np.errstate(divide='ignore', invalid='ignore'):
                 ratio = length / np.asarray(result.goal.joint_distance, np.float64)
             result.path_ratio = np.where((np.asarray(result.outcome) == 'reached') & result.goal.free, ratio, np.nan)
+        if joint_paths:
+            result.path = self._paths_to_goals(result.goal, q0, obstacles, {})
+            with np.errstate(divide='ignore', invalid='ignore'):
+                ratio = length / np.asarray(result.path.length, np.float64)
+            result.planned_ratio = np.where((np.asarray(result.outcome) == 'reached') & (result.path.candidate >= 0), ratio, np.nan)
         return result
+
+    def _paths_to_goals(self, goal, q0, obstacles, kw) -> JointPaths:
+        """plan_joint_paths to the poses of `goal` (GoalPoses): queries without a reachable pose get outcome 'goal' and NaN numbers"""
+        ok = np.asarray(goal.reachable, bool)
+        N, A = len(ok), self.env.model.A
+        if ok.all():
+            return self._plan_checked(q0, np.asarray(goal.joint_positions, np.float64), obstacles, **kw)
+        # (the poses a solver returned lie inside the limits: they are not put through the refusals again)
+        found = self._plan_checked(q0[ok], np.asarray(goal.joint_positions, np.float64)[ok], obstacles[ok], **kw) if ok.any() else None
+        kind = np.float32 if found is None else found.length.dtype
+        nan = lambda *shape: np.full((N,) + shape, np.nan, kind)      # noqa: E731
+        parts = [np.full(N, 'goal', '<U8'), np.full(N, -1, np.int64), nan(A), nan(), nan(), nan(), nan(), nan(), np.full(N, -1, np.int64),
+                 nan(), np.zeros(N, np.int64), np.asarray(q0, kind), nan(A)]
+        for dst, src in zip(parts, found or ()):
+            dst[ok] = src
+        return JointPaths(*parts)
+
+    def _plan_checked(self, q0, q_goal, obstacles, candidates=16, resolution=0.02, clearance_margin=0.0, seed=0, on_device=None):
+        env = self.env
+        if on_device is None:
+            on_device = torch.cuda.is_available()
+        kw = dict(candidates=int(candidates), resolution=float(resolution), margin=float(clearance_margin), seed=int(seed))
+        if not on_device:
+            out = joint_paths_host(env, q0, q_goal, obstacles, **kw)
+        else:
+            from .engine import JointPathChecker
+            key = (env.model.digest(), float(env.obstacle_radius))
+            if getattr(self, '_path_checker', None) is None or self._path_checker[0] != key:
+                self._path_checker = None
+                self._path_checker = (key, JointPathChecker(env.model, env.obstacle_radius))
+            out = self._path_checker[1].check(q0, q_goal, obstacles, **kw)
+        with np.errstate(invalid='ignore'):
+            coarse = np.asarray(out.sample_step, np.float64) > resolution
+        if coarse.any() and not getattr(self, '_path_step_warned', False):
+            self._path_step_warned = True
+            logger.warning(f'plan_joint_paths: {int(coarse.sum())} queries are sampled at the cap of 2048 poses per path, '
+                           f'{float(np.max(np.asarray(out.sample_step)[coarse])):.4g} apart, coarser than resolution={resolution!r}')
+        return out
+
+    def plan_joint_paths(self, targets=None, obstacles=None, initial_joint_positions=None, goal_joint_positions=None,
+                         candidates: int = 16, resolution: float = 0.02, clearance_margin: float = 0.0, seed: int = 0,
+                         on_device: Optional[bool] = None):
+        """Collision-checked joint paths from start poses to goal poses (kinematic environment only; needs no agent): per query
+        `candidates` joint-space polylines start -> via -> goal — candidate 0 through the midpoint, the straight line, the others
+        through vias drawn around it from `seed` (environment/kinematic.py: path_vias) — are SAMPLED at poses at most `resolution`
+        apart in the joints' max-norm (a multiple of 64 poses per path, at most 2048; beyond that the step is coarser and a warning
+        says so once), each sample tested against the obstacle, the arm itself and the workcell under the rule of reach_targets()
+        with clearance_margin to spare, and the shortest candidate with no blocked sample is returned. A free verdict holds AT THE
+        SAMPLES; sample_step says how far apart they are. There is no continuous-collision certificate.
+          targets              : [N][3] or [3]: the goal poses are solve_goal_poses(targets, ...) with its defaults and `seed`;
+                                 queries without a reachable pose get outcome 'goal' and NaN numbers
+          goal_joint_positions : [N][A] or [A]: the goal poses themselves. Exactly one of the two is given.
+          obstacles, initial_joint_positions : as reach_targets() takes them
+          candidates           : 1 .. 64
+          on_device            : None: the device when there is one; False: the float64 host twin under the same rule (slow)
+        Returns environment.kinematic.JointPaths, arrays over the queries: outcome ('straight' | 'via' | 'blocked' | 'start' |
+        'goal': the start / goal pose itself is blocked), candidate, via, length, straight_length, min_clearance,
+        min_self_clearance, min_cell_clearance, straight_first_blocked, sample_step, samples; waypoints(n) resamples the paths."""
+        if not self.env:
+            raise EnvironmentNotInitialized
+        if not isinstance(self.env, KinematicEnvironment):
+            raise ConfigurationIncomplete('plan_joint_paths() needs the kinematic environment (initialize_kinematic_environment()): '
+                                          'PyBullet and the synthetic stand-in have no chain model to solve on')
+        env = self.env
+        if (targets is None) == (goal_joint_positions is None):
+            raise InvalidEnvironmentParameter('plan_joint_paths() takes exactly one of targets and goal_joint_positions')
+        if not _positive_int(candidates) or candidates > PATH_CANDIDATES_MAX:
+            raise InvalidEnvironmentParameter(f'candidates is a number of paths from 1 to {PATH_CANDIDATES_MAX}: got {candidates!r}')
+        if not (isinstance(resolution, (int, float)) and not isinstance(resolution, bool) and np.isfinite(resolution) and resolution > 0.0):
+            raise InvalidEnvironmentParameter(f'resolution is a positive joint-space distance: got {resolution!r}')
+        if not (isinstance(clearance_margin, (int, float)) and np.isfinite(clearance_margin)):
+            raise InvalidEnvironmentParameter(f'clearance_margin is a finite length: got {clearance_margin!r}')
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or seed < 0:
+            raise InvalidEnvironmentParameter(f'seed is a non-negative integer: got {seed!r}')
+        nominal = env.obstacle_centre if env.scene_ranges_on else env.obstacle_pos
+        kw = dict(candidates=candidates, resolution=resolution, clearance_margin=clearance_margin, seed=seed, on_device=on_device)
+        try:
+            if targets is not None:
+                q0, targets, obstacles, _ = reach_queries(env.model, targets, obstacles, initial_joint_positions, 1,
+                                                          nominal_obstacle=nominal, nominal_start=env.initial_joint_positions)
+            else:
+                # the goal poses go through the same refusals as start poses do: shape, finite numbers, the joints' limits
+                try:
+                    goals = np.array(goal_joint_positions, float)
+                except (TypeError, ValueError):
+                    raise ValueError('goal_joint_positions is not an array of numbers') from None
+                if goals.shape == (env.model.A,):
+                    goals = goals[None]
+                if goals.ndim != 2 or goals.shape[1] != env.model.A or len(goals) == 0:
+                    raise ValueError(f'goal_joint_positions is [N][{env.model.A}], or [{env.model.A}] for one query (one value per '
+                                     f'involved joint): got shape {goals.shape}')
+                far = np.zeros((len(goals), 3))
+                try:
+                    q_goal = reach_queries(env.model, far, far, goals, 1)[0]
+                except ValueError as err:
+                    raise ValueError(str(err).replace('initial_joint_positions', 'goal_joint_positions')) from None
+                q0, _, obstacles, _ = reach_queries(env.model, far, obstacles, initial_joint_positions, 1, nominal_obstacle=nominal,
+                                                    nominal_start=env.initial_joint_positions)
+        except ValueError as err:
+            raise InvalidEnvironmentParameter(str(err)) from None
+        if targets is not None:
+            goal = self.solve_goal_poses(targets, obstacles, q0, seed=seed, on_device=on_device)
+            return self._paths_to_goals(goal, q0, obstacles, kw)
+        return self._plan_checked(q0, q_goal, obstacles, **kw)
 
     def solve_goal_poses(self, targets, obstacles=None, initial_joint_positions=None, restarts: int = 8, iterations: int = 32,
                          tolerance: float = 1e-3, clearance_margin: float = 0.0, seed: int = 0, on_device: Optional[bool] = None):
