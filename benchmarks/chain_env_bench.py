@@ -51,6 +51,13 @@ launches are the box instantiations, which test the floor and the spheres too.
       (GoalPoseSolver), the paths to them (JointPathChecker, 16 candidates, resolution 0.02) and the shares of 'straight' / 'via' /
       'blocked' among the queries with a free goal pose.
 
+  python benchmarks/chain_env_bench.py demo [--envs 2048] [--launches 20] [--boxes]
+      planned joint paths as replay rows, same arm and cell: N = --envs demonstrations (default 2048 here) of T = 400 ticks.
+      Microseconds per naf_chain_demo_rows launch between device events (median and minimum of `--launches`, at most 30, after two
+      unmeasured ones), and in the same process the composed form it replaces — 400 x naf_chain_env_step at E = N behind one
+      naf_chain_env_reset_given, the actions already on the device — with their ratio, the mean number of valid rows, the shares of
+      the end codes and the new kernels' registers.
+
 `--hindsight R` (rate): the chain runs relabel a share R of every minibatch (NAFAgent.run_vectorized(hindsight=R)). Such a run
 wants an empty ring, so with the flag — also `--hindsight 0`, the figure to compare with — the warm-up steps run on an agent of
 their own and the timed run starts on a fresh one (its graph captures are inside the timed window, in both).
@@ -418,6 +425,79 @@ def paths(a):
                       "kernel_registers": regs}))
 
 
+def demo(a):
+    """the one naf_chain_demo_rows launch (N x T rows) against the composed form: T x naf_chain_env_step at E = N, the actions
+    already on the device, between device events"""
+    import numpy as np
+    import torch
+    from robotic_manipulator_rloa_amd import _lib
+    from robotic_manipulator_rloa_amd.engine import DemonstrationWriter
+    from robotic_manipulator_rloa_amd.environment.kinematic import demo_actions, demonstration_plan
+    from robotic_manipulator_rloa_amd.environment.urdf_chain import compile_chain, load_urdf
+    N, T, n = (2048 if a.envs == 64 else a.envs), 400, a.joints
+    launches = min(a.launches, 30)
+    a.workcell = True
+    urdf = os.path.abspath(a.urdf) if os.path.isabs(a.urdf) else os.path.join(ROOT, a.urdf)
+    init = ([0.0, 0.6, 0.0, -1.2, 0.0, 0.8, 0.0] + [0.0] * n)[:n]
+    model = compile_chain(load_urdf(urdf), n - 1, list(range(n)), [n], init, [0.1] * n, 0.03, consider_autocollision=True, **_workcell(a))
+    lib, dev, stream = _lib.load(), torch.device("cuda:0"), torch.cuda.current_stream().cuda_stream
+    rng = np.random.default_rng(5)
+    lo = np.array([j.lower if j.limited else -np.pi for j in model.joints])
+    hi = np.array([j.upper if j.limited else np.pi for j in model.joints])
+    # paths of T ticks or more at speed 1, so that every demonstration has T rows to write unless an outcome ends it
+    q_start = np.tile(np.float32(init), (N, 1))
+    q_goal = np.clip(q_start + rng.choice([-1.0, 1.0], (N, n)) * rng.uniform(0.6, 1.0, (N, n)) * (T / 240.0), lo, hi).astype(np.float32)
+    via = (0.5 * (q_start + q_goal) + rng.uniform(-0.2, 0.2, (N, n))).astype(np.float32)
+    targets = np.tile(np.float32([0.0, 0.0, 5.0]), (N, 1))
+    obstacles = (np.array([0.35, 0.2, 0.45]) + rng.uniform(-0.2, 0.2, (N, 3))).astype(np.float32)
+    plan = demonstration_plan(q_start, via, q_goal, 1.0, T)
+    writer = DemonstrationWriter(model, 0.06, chunk=N * T)
+    writer.load(plan, targets, obstacles, slice(0, N))
+    fused = []
+    for i in range(launches + 2):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        writer.launch(N, T)
+        t1.record()
+        t1.synchronize()
+        if i >= 2:
+            fused.append(1e3 * t0.elapsed_time(t1))
+    rec = writer.records[:N].cpu().numpy()
+    h = writer._chain_env
+    S = 2 * n + 9
+    rf = lib.naf_replay_row_floats(S, n)
+    act = torch.from_numpy(np.ascontiguousarray(demo_actions(plan, T).transpose(1, 0, 2), np.float32)).to(dev)
+    scene = torch.from_numpy(np.concatenate([targets, obstacles], axis=1)).to(dev)
+    st, obs = torch.zeros(N, lib.naf_chain_env_state_floats(h), device=dev), torch.zeros(N, S, device=dev)
+    rows = torch.zeros(T, N, rf, device=dev)
+    composed = []
+    for i in range(max(2, launches // 5) + 1):
+        _lib.check(lib.naf_chain_env_reset_given(h, st.data_ptr(), obs.data_ptr(), N, writer.q_start.data_ptr(), scene.data_ptr(), 0.06,
+                                                 stream), "reset_given")
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for t in range(T):
+            _lib.check(lib.naf_chain_env_step(h, st.data_ptr(), act[t].data_ptr(), rows[t].data_ptr(), obs.data_ptr(), N, 0, None, 0, None,
+                                              0, stream), "step")
+        t1.record()
+        t1.synchronize()
+        if i >= 1:
+            composed.append(1e3 * t0.elapsed_time(t1))
+    # the first rows of both forms: the same positions and actions to the bit
+    first = torch.equal(writer.rows[:N * T].view(N, T, rf)[:, 0, :n], rows[0, :, :n])
+    usage = json.load(open(_lib.USAGE_PATH)) if os.path.exists(_lib.USAGE_PATH) else {}
+    regs = {name: {q: v.get(q) for q in ("vgprs", "sgprs", "scratch_bytes_per_lane", "lds_bytes", "occupancy")}
+            for name, v in usage.items() if "chain_demo_" in name}
+    f_med, c_med = float(np.median(fused)), float(np.median(composed))
+    print(json.dumps({"arm": os.path.basename(urdf), "demonstrations": N, "ticks": T, "self_pairs": len(model.self_pairs),
+                      "workcell_pairs": len(model.cell_pairs), "boxes": bool(a.boxes),
+                      "us_per_demo_rows_launch": {"median": round(f_med, 1), "min": round(float(np.min(fused)), 1)},
+                      "us_per_composed_steps": {"median": round(c_med, 1), "min": round(float(np.min(composed)), 1)},
+                      "composed_over_fused": round(c_med / f_med, 3), "mean_valid_rows": round(float(rec[:, 0].mean()), 1),
+                      "end_code_shares": {str(k): round(float(np.mean(rec[:, 1] == k)), 4) for k in range(6)},
+                      "first_rows_bit_equal": bool(first), "kernel_registers": regs}))
+
+
 def kernels(a):
     import numpy as np
     import torch
@@ -456,7 +536,7 @@ def kernels(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["rate", "kernels", "step", "rollout", "gather", "ik", "path"])
+    ap.add_argument("what", choices=["rate", "kernels", "step", "rollout", "gather", "ik", "path", "demo"])
     ap.add_argument("--urdf", default=os.path.join("tests", "golden", "urdf", "iiwa_like7.urdf"))
     ap.add_argument("--joints", type=int, default=7)
     ap.add_argument("--envs", type=int, default=64)
@@ -476,7 +556,7 @@ def main():
     ap.add_argument("--hindsight", type=float, default=None, help="rate, gather: the share of rows replayed under a hindsight goal")
     ap.add_argument("--horizon", type=int, default=None, help="rate, gather: hindsight_horizon (rate: max_frames; gather: 400)")
     a = ap.parse_args()
-    {"rate": rate, "kernels": kernels, "step": step, "rollout": rollout, "gather": gather, "ik": ik, "path": paths}[a.what](a)
+    {"rate": rate, "kernels": kernels, "step": step, "rollout": rollout, "gather": gather, "ik": ik, "path": paths, "demo": demo}[a.what](a)
 
 
 if __name__ == "__main__":

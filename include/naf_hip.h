@@ -919,6 +919,32 @@ int naf_chain_path_check(naf_chain_env_t* h, const float* q_start_dev, const flo
                          const float* obstacles_dev, float obstacle_radius, int N, int C, int S, float margin, float* out,
                          float* poses_out, void* stream);
 
+/* Demonstrations (an addition within ABI 40): N planned joint paths turned into the replay rows of the episodes that follow them
+ * open loop, one launch. environment/kinematic.py (demonstration_plan, demonstration_rows_host) is the float64 statement.
+ *   Demonstration n starts at q_start_dev[n] clamped into the limits (p_0) in the scene targets_dev[n] / obstacles_dev[n] with
+ *   obstacle_radius, and applies leg_actions_dev[n][0] for n_ticks_dev[n][0] ticks, then leg_actions_dev[n][1] for n_ticks_dev[n][1]
+ *   (both counts >= 1; the caller validates them before the upload). T_n = min(n1 + n2, T_cap) rows.
+ *   the poses   : p_{t+1} = limits(fmaf(DT, a_t, p_t)) joint by joint — naf_chain_env_step's recurrence, bit for bit, not a closed form.
+ *   rows_out    : [N][T_cap][row_floats] (DEVICE), row_floats = naf_replay_row_floats(2A+9, A). Row t < T_n is the row
+ *                 naf_chain_env_step writes for that tick: state = obs(p_t), its velocity slots what step t - 1 reported (0 at
+ *                 t = 0 and where a limit stopped the joint) | a_t | reward and done from the walk of p_{t+1} against the target, the
+ *                 obstacle, the pairs and the workcell | next_state = obs(p_{t+1}), bit for bit the state of row t + 1 | zeros behind
+ *                 done, the tag float included. Rows T_n .. T_cap - 1 are not written. Rows behind the first one whose done is 1
+ *                 are written and are NOT part of the demonstration: records_out[n][0] says how many are.
+ *   records_out : [N][NAF_CHAIN_DEMO_FLOATS] (DEVICE) = [0] valid rows: up to and including the first done, else T_n | [1] end
+ *                 code: 0 T_cap cut it, 1 reached, 2 obstacle, 3 self, 4 workcell, 5 the path ended short of the target | [2]
+ *                 |ee - target| after the last valid row | [3] [4] [5] minima over the valid rows of the obstacle clearance minus
+ *                 obstacle_radius, the self-clearance and the workcell clearance (+inf without pairs / a workcell) | [6] n1 + n2 | [7] 0.
+ *   poses_out   : NULL, or DEVICE [N][T_cap + 1][A]: p_0 .. p_{T_n} (for tests).
+ * One workgroup per demonstration, a lane per pose of a pass, the handle's lanes and waves as naf_chain_path_check; no atomics.
+ * NAF_ERR_ARG, and no launch, for a null pointer other than poses_out, N < 1, T_cap outside 1 .. NAF_CHAIN_DEMO_MAX_TICKS, a
+ * row_floats that is not the arm's, or a radius that is negative or not finite. */
+#define NAF_CHAIN_DEMO_FLOATS 8
+#define NAF_CHAIN_DEMO_MAX_TICKS 1024
+int naf_chain_demo_rows(naf_chain_env_t* h, const float* q_start_dev, const float* leg_actions_dev, const int32_t* n_ticks_dev,
+                        const float* targets_dev, const float* obstacles_dev, float obstacle_radius, int N, int T_cap, float* rows_out,
+                        int row_floats, float* records_out, float* poses_out, void* stream);
+
 /* ---- one-shot gradient all-reduce over peer-mapped memory (no reference counterpart) ----------
  * The data-parallel exchange that follows loss.backward() (naf_algorithm.py:207-210 on every rank): sum of the flat
  * gradient over the W <= 8 GPUs of one node, each rank pushing its gradient into a receive slot on every peer over

@@ -1509,3 +1509,224 @@ extern "C" int naf_chain_path_check(naf_chain_env_t* h, const float* q_start_dev
     NAF_CHECK_LAUNCH();
     return NAF_OK;
 }
+
+// ---- demonstrations: planned joint paths as replay rows (include/naf_hip.h, "Demonstrations") -------------------------------------
+// One workgroup per demonstration; a lane is one POSE of a pass: lane t walks p_t once with the walk that writes an observation,
+// straight into row t's `state`, copies it into row t - 1's `next_state` and writes row t - 1's action, reward, done and zero tail
+// from the outcome of that walk. A row is thus filled by two lanes with disjoint floats, and nothing is atomic. The poses follow the
+// step kernel's recurrence, not a closed form: the pass's base pose (and the velocities the step before it reported) lies in LDS
+// laid out as env_state is — pose[A] | target | obstacle | velocity[A] — so that the walk reads the scene from it as it does from
+// env_state; the walk's accessor advances joint m from the base by one fused step per tick up to the lane's own tick (at most
+// `lanes` trips), and behind the pass wave 0 advances the base by `lanes` ticks, a joint per lane. No per-lane pose array, nothing in
+// scratch. Only wave 0 ever touches the base, in program order, so it needs no barrier: demo_wave_order keeps the compiler from
+// moving the accesses across it. SC is the path kernel's shape: every wave joins the pair phase of every pass.
+__device__ static inline void demo_tick(const float* j, float a, float& q, float& vel) {
+    q = fmaf(CH_DT, a, q);      // the step kernels' `st[m] + CH_DT * a`, which the compiler contracts to this one operation in each
+    vel = a;
+    if (j[16] != 0.f) {
+        if (q > j[18]) { q = j[18]; vel = 0.f; }
+        if (q < j[17]) { q = j[17]; vel = 0.f; }
+    }
+}
+
+__device__ static inline void demo_wave_order() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+__host__ __device__ static inline int ch_demo_base_floats(int A) { return 2 * A + 6; }
+
+template <bool SC, class... Cell>
+__global__ void __launch_bounds__(SC ? 64 * CH_MAX_WAVES : 64)
+chain_demo_rows_kernel(const float* __restrict__ model, const float* __restrict__ q_start, const float* __restrict__ leg_actions,
+                       const int* __restrict__ n_ticks, const float* __restrict__ targets, const float* __restrict__ obstacles,
+                       float orad, int T_cap, int A, int n_seg, int n_pairs, int lanes, int row_floats, float* __restrict__ rows_out,
+                       float* __restrict__ records_out, float* __restrict__ poses_out, const Cell... cell) {
+    constexpr bool CELL = (std::is_same_v<Cell, ChainCell> || ... || false);
+    constexpr bool BOX = (std::is_same_v<Cell, ChainBox> || ... || false);
+    extern __shared__ __attribute__((aligned(16))) float ch_lds[];
+    const int64_t n = blockIdx.x;
+    const int S = 2 * A + 9;
+    const int off_s2 = naf_row_off_s2(S, A), off_d = naf_row_off_done(S, A);
+    // (the host validated the counts; the clamps only keep a wrong upload inside the arrays)
+    const int n1 = min(max(n_ticks[2 * n], 1), 1 << 20), n12 = n1 + min(max(n_ticks[2 * n + 1], 1), 1 << 20);
+    const int T = min(n12, T_cap);                       // rows of this demonstration; poses 0 .. T
+    const float* a1 = leg_actions + n * 2 * A;
+    const float* a2 = a1 + A;
+    const float ox = obstacles[n * 3], oy = obstacles[n * 3 + 1], oz = obstacles[n * 3 + 2];
+    const float tx = targets[n * 3], ty = targets[n * 3 + 1], tz = targets[n * 3 + 2];
+    const int lane = threadIdx.x & 63;
+    const bool active = lane < lanes;
+    const bool wave0 = threadIdx.x < 64;
+    float* base = ch_lds + (SC ? ch_lds_bytes(n_seg, lanes, blockDim.x >> 6) / sizeof(float) : 0);
+    float* rows = rows_out + n * T_cap * row_floats;
+    if (wave0) {
+        for (int m = lane; m < A; m += 64) {
+            const float* j = model + CH_HDR + m * CH_JNT;
+            float q = q_start[n * A + m];
+            if (j[16] != 0.f) {      // p_0: the start pose clamped into the limits, as naf_chain_env_reset_given clamps it
+                if (q > j[18]) q = j[18];
+                if (q < j[17]) q = j[17];
+            }
+            base[m] = q;
+            base[A + 6 + m] = 0.f;
+        }
+        if (lane < 3) {
+            base[A + lane] = targets[n * 3 + lane];
+            base[A + 3 + lane] = obstacles[n * 3 + lane];
+        }
+        demo_wave_order();
+    }
+    float min_clear = INFINITY, min_self = INFINITY, min_cell = INFINITY, final_dist = -1.f;
+    int first_key = INT_MAX;      // 8 x (row of the first done) + its end code
+    bool stopped = false;         // (uniform in wave 0) a pass before this one held the first done
+    for (int b = 0; b <= T; b += lanes) {      // (uniform: every thread takes every pass)
+        const int t = b + lane;
+        const bool walks = active && wave0 && t <= T;
+        float* prev = rows + (int64_t)(t - 1) * row_floats;      // row t - 1: used only where t >= 1
+        float* o = t < T ? prev + row_floats : prev + off_s2;    // obs(p_t): row t's state, or the last row's next_state
+        float ee[3];
+        bool hit = false;
+        WalkAux aux = {SC ? ch_lds + lane : nullptr, lanes, INFINITY, INFINITY};
+        if (walks) {
+            float* rec = poses_out ? poses_out + ((n * (T_cap + 1)) + t) * A : nullptr;
+            hit = chain_walk_at<SC, false, false, true, CELL, BOX>(
+                model, A, n_seg,
+                [=](int m) {
+                    const float* j = model + CH_HDR + m * CH_JNT;
+                    const float u = a1[m], v = a2[m];
+                    float q = base[m], vel = base[A + 6 + m];
+                    for (int k = b; k < t; ++k) demo_tick(j, k < n1 ? u : v, q, vel);
+                    const int slot = (int)j[21];
+                    if (slot >= 0) o[A + slot] = vel;      // what step t - 1 reported (0 at t = 0, 0 where a limit stopped the joint)
+                    if (rec) rec[m] = q;
+                    return q;
+                },
+                ox, oy, oz, orad, base, o, ee, aux);
+        }
+        float self_clear = INFINITY;
+        if constexpr (SC) self_clear = self_clearance_phase(model, A, n_seg, n_pairs, ch_lds, lanes, lane, active && t <= T);
+        if (wave0) {
+            const bool outcome = walks && t >= 1;      // the walk of p_t is the outcome of row t - 1
+            float dist = 0.f, clear = INFINITY, cellc = INFINITY;
+            bool done = false;
+            int code = 0;
+            if (outcome) {
+                const float dx = ee[0] - tx, dy = ee[1] - ty, dz = ee[2] - tz;
+                dist = sqrtf(dx * dx + dy * dy + dz * dz);
+                clear = aux.clear - orad;
+                if constexpr (CELL) cellc = aux.cell;
+                const bool reached = dist < CH_REACHED, self_hit = self_clear < 0.f, cell_hit = CELL && aux.cell < 0.f;
+                const bool any = hit || self_hit || cell_hit;
+                done = reached || any;
+                code = reached ? 1 : (hit ? 2 : (self_hit ? 3 : (cell_hit ? 4 : 0)));
+                const float* act = t - 1 < n1 ? a1 : a2;
+                for (int m = 0; m < A; ++m) prev[S + m] = act[m];
+                prev[S + A] = reached ? 250.f : (any ? -1000.f : -(dist - CH_REACHED));
+                for (int k = S + A + 1; k < off_s2; ++k) prev[k] = 0.f;
+                if (t < T)
+                    for (int k = 0; k < S; ++k) prev[off_s2 + k] = o[k];
+                prev[off_d] = done ? 1.f : 0.f;
+                for (int k = off_d + 1; k < row_floats; ++k) prev[k] = 0.f;      // the tag float included: an untagged row
+            }
+            const unsigned long long mask = __ballot(outcome && done);
+            const int first_lane = mask ? __ffsll(mask) - 1 : 64;
+            if (!stopped && outcome && lane <= first_lane) {      // rows up to the first done are the demonstration's
+                min_clear = fminf(min_clear, clear);
+                min_self = fminf(min_self, self_clear);
+                min_cell = fminf(min_cell, cellc);
+                if (lane == first_lane) { first_key = (t - 1) * 8 + code; final_dist = dist; }
+                else if (t == T && !mask) final_dist = dist;
+            }
+            stopped = stopped || mask != 0ull;
+            if (b + lanes <= T) {      // another pass: the base moves on by `lanes` ticks, a joint per lane
+                demo_wave_order();
+                for (int m = lane; m < A; m += 64) {
+                    const float* j = model + CH_HDR + m * CH_JNT;
+                    const float u = a1[m], v = a2[m];
+                    float q = base[m], vel = base[A + 6 + m];
+                    for (int k = b; k < b + lanes; ++k) demo_tick(j, k < n1 ? u : v, q, vel);
+                    base[m] = q;
+                    base[A + 6 + m] = vel;
+                }
+                demo_wave_order();
+            }
+        }
+    }
+    if (!wave0) return;      // (behind the last barrier; wave 0 is whole: the lanes that walked nothing hold the identities)
+    for (int off = 32; off > 0; off >>= 1) {
+        min_clear = fminf(min_clear, __shfl_xor(min_clear, off));
+        min_self = fminf(min_self, __shfl_xor(min_self, off));
+        min_cell = fminf(min_cell, __shfl_xor(min_cell, off));
+        first_key = min(first_key, __shfl_xor(first_key, off));
+        final_dist = fmaxf(final_dist, __shfl_xor(final_dist, off));
+    }
+    if (threadIdx.x != 0) return;
+    float* r = records_out + n * NAF_CHAIN_DEMO_FLOATS;
+    r[0] = first_key == INT_MAX ? (float)T : (float)(first_key / 8 + 1);
+    r[1] = first_key == INT_MAX ? (T < n12 ? 0.f : 5.f) : (float)(first_key % 8);
+    r[2] = final_dist;
+    r[3] = min_clear;
+    r[4] = min_self;
+    r[5] = min_cell;
+    r[6] = (float)n12;
+    r[7] = 0.f;
+}
+
+// the SC demonstration kernels' dynamic LDS is the probe's and the base behind it: raised once per device
+static int ch_demo_raise_lds_limit() {
+    static bool raised_dev[64];
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return (int)e;
+    if (dev < 0 || dev >= 64) return NAF_ERR_ARG;
+    if (raised_dev[dev]) return NAF_OK;
+    for (const void* k : {(const void*)chain_demo_rows_kernel<true>, (const void*)chain_demo_rows_kernel<true, ChainCell>,
+                          (const void*)chain_demo_rows_kernel<true, ChainCell, ChainBox>}) {
+        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, CH_MAX_DYN_LDS + 1024);
+        if (e != hipSuccess) return (int)e;
+    }
+    raised_dev[dev] = true;
+    return NAF_OK;
+}
+
+template <class... Cell>
+static void ch_demo_launch(naf_chain_env_t* h, const float* q_start, const float* leg_actions, const int* n_ticks, const float* targets,
+                           const float* obstacles, float orad, int N, int T_cap, int rf, float* rows_out, float* records_out,
+                           float* poses_out, void* stream, const Cell... cell) {
+    const size_t base = (size_t)ch_demo_base_floats(h->A) * sizeof(float);
+    if (h->n_pairs > 0)
+        chain_demo_rows_kernel<true, Cell...><<<(unsigned)N, 64 * h->waves, ch_lds_bytes(h->n_seg, h->lanes, h->waves) + base,
+                                              (hipStream_t)stream>>>(h->model_dev, q_start, leg_actions, n_ticks, targets, obstacles, orad,
+                                                                     T_cap, h->A, h->n_seg, h->n_pairs, h->lanes, rf, rows_out,
+                                                                     records_out, poses_out, cell...);
+    else
+        chain_demo_rows_kernel<false, Cell...><<<(unsigned)N, 64, base, (hipStream_t)stream>>>(
+            h->model_dev, q_start, leg_actions, n_ticks, targets, obstacles, orad, T_cap, h->A, h->n_seg, 0, 64, rf, rows_out,
+            records_out, poses_out, cell...);
+}
+
+extern "C" int naf_chain_demo_rows(naf_chain_env_t* h, const float* q_start_dev, const float* leg_actions_dev, const int32_t* n_ticks_dev,
+                                   const float* targets_dev, const float* obstacles_dev, float obstacle_radius, int N, int T_cap,
+                                   float* rows_out, int row_floats, float* records_out, float* poses_out, void* stream) {
+    if (!h || !q_start_dev || !leg_actions_dev || !n_ticks_dev || !targets_dev || !obstacles_dev || !rows_out || !records_out)
+        return NAF_ERR_ARG;
+    if (N < 1 || N > 1 << 30 || T_cap < 1 || T_cap > NAF_CHAIN_DEMO_MAX_TICKS) return NAF_ERR_ARG;
+    if (row_floats <= 0 || row_floats != naf_replay_row_floats(2 * h->A + 9, h->A)) return NAF_ERR_ARG;
+    if (!std::isfinite(obstacle_radius) || obstacle_radius < 0.f) return NAF_ERR_ARG;
+    if (h->n_pairs > 0) {
+        const int rc = ch_demo_raise_lds_limit();
+        if (rc != NAF_OK) return rc;
+    }
+    if (h->n_box > 0)
+        ch_demo_launch(h, q_start_dev, leg_actions_dev, n_ticks_dev, targets_dev, obstacles_dev, obstacle_radius, N, T_cap, row_floats,
+                       rows_out, records_out, poses_out, stream, ChainCell{}, ChainBox{});
+    else if (h->n_cell > 0)
+        ch_demo_launch(h, q_start_dev, leg_actions_dev, n_ticks_dev, targets_dev, obstacles_dev, obstacle_radius, N, T_cap, row_floats,
+                       rows_out, records_out, poses_out, stream, ChainCell{});
+    else
+        ch_demo_launch(h, q_start_dev, leg_actions_dev, n_ticks_dev, targets_dev, obstacles_dev, obstacle_radius, N, T_cap, row_floats,
+                       rows_out, records_out, poses_out, stream);
+    NAF_CHECK_LAUNCH();
+    return NAF_OK;
+}

@@ -1326,3 +1326,110 @@ class JointPathChecker:
             records[sl] = self.out[:n * C].cpu().numpy().reshape(n, C, PATH_FLOATS)
             samples[sl] = S
         return gather_joint_paths(records, vias, q_start, q_goal, samples)
+
+
+def demonstration_chunks(rows_of, budget: int) -> List[Tuple[int, int, int]]:
+    """[(first query, queries, T_cap)]: consecutive queries share a chunk, and its T_cap is the largest T_n among them, as long as
+    queries x T_cap stays within `budget` rows; a chunk holds at least one query."""
+    rows_of = np.asarray(rows_of, np.int64)
+    out, first, N = [], 0, len(rows_of)
+    while first < N:
+        n, T = 1, int(rows_of[first])
+        while first + n < N:
+            T2 = max(T, int(rows_of[first + n]))
+            if (n + 1) * T2 > budget:
+                break
+            n, T = n + 1, T2
+        out.append((first, n, T))
+        first += n
+    return out
+
+
+class DemonstrationWriter:
+    """Planned joint paths as replay rows on a chain model (csrc/chain_env.hip, "demonstrations"): per chunk of queries ONE
+    naf_chain_demo_rows launch that writes every row of every demonstration, then torch plumbing — the mask `t < valid[n] and
+    kept[n]` and a boolean index — to a contiguous device tensor of the kept rows in query order, then tick order. Owns the handle
+    and staging buffers for `chunk` rows; needs no agent. A demonstration's rows do not depend on where in a launch it lies."""
+
+    def __init__(self, chain, obstacle_radius: float = 0.06, chunk: Optional[int] = None, device=None):
+        import ctypes
+        from .environment.kinematic import DEMO_CHUNK, DEMO_FLOATS, demo_row_layout
+        _lib.require_gpu()
+        self.lib, self.chain, self.A = _lib.load(), chain, chain.A
+        self.dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        self.obstacle_radius = float(np.float32(obstacle_radius))
+        self.chunk = int(DEMO_CHUNK if chunk is None else chunk)
+        if self.chunk < 1:
+            raise ValueError("DemonstrationWriter: a chunk holds at least one row")
+        self.row_floats = self.lib.naf_replay_row_floats(2 * self.A + 9, self.A)
+        assert self.row_floats == demo_row_layout(self.A)[3]
+        blob = np.ascontiguousarray(chain.pack(), np.float32)
+        self._chain_env = ctypes.c_void_p()
+        check(self.lib.naf_chain_env_create(blob.ctypes.data, int(blob.size), ctypes.byref(self._chain_env)), "chain_env_create")
+        K, A = self.chunk, self.A                            # the most queries a chunk can hold: T_cap is at least 1
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        self.q_start, self.leg_actions = torch.zeros(K, A, **f32), torch.zeros(K, 2, A, **f32)
+        self.n_ticks = torch.ones(K, 2, dtype=torch.int32, device=self.dev)
+        self.targets, self.obstacles = torch.zeros(K, 3, **f32), torch.zeros(K, 3, **f32)
+        self.records = torch.zeros(K, DEMO_FLOATS, **f32)
+        self.rows = torch.zeros(self.chunk, self.row_floats, **f32)
+        self.launches = 0
+
+    def __del__(self):
+        if getattr(self, "_chain_env", None) is not None:
+            self.lib.naf_chain_env_destroy(self._chain_env)
+            self._chain_env = None
+
+    def launch(self, n: int, T_cap: int) -> None:
+        """the launch of one chunk of n demonstrations already in the buffers, on the current stream"""
+        check(self.lib.naf_chain_demo_rows(self._chain_env, ptr(self.q_start), ptr(self.leg_actions), ptr(self.n_ticks), ptr(self.targets),
+                                           ptr(self.obstacles), self.obstacle_radius, n, T_cap, ptr(self.rows), self.row_floats,
+                                           ptr(self.records), None, stream_ptr()), "chain_demo_rows")
+        self.launches += 1
+
+    def load(self, plan, targets, obstacles, sl: slice) -> int:
+        n = sl.stop - sl.start
+        up = lambda a, kind: torch.from_numpy(np.ascontiguousarray(a[sl], kind))      # noqa: E731
+        self.q_start[:n].copy_(up(plan.q_start, np.float32))
+        self.leg_actions[:n].copy_(up(plan.leg_actions, np.float32))
+        self.n_ticks[:n].copy_(up(plan.n_ticks, np.int32))
+        self.targets[:n].copy_(up(targets, np.float32))
+        self.obstacles[:n].copy_(up(obstacles, np.float32))
+        return n
+
+    def write(self, plan, targets, obstacles, keep_contact: bool = False, has_path=None):
+        """plan (environment.kinematic.DemonstrationPlan of N queries), targets[N][3], obstacles[N][3] -> Demonstrations whose `rows`
+        is a device tensor [rows_total][row_floats]. has_path[N] (default all): queries without one are launched with whatever
+        plan holds for them and reported 'none'."""
+        from .environment.kinematic import DEMO_FLOATS, DEMO_MAX_TICKS, gather_demonstrations
+        N = len(plan.q_start)
+        ticks = np.asarray(plan.n_ticks)
+        if ticks.shape != (N, 2) or (N and ticks.min() < 1):
+            raise ValueError("DemonstrationWriter: every leg of a plan takes at least one tick")
+        T_of = np.asarray(plan.rows, np.int64)
+        if N and (T_of.min() < 1 or T_of.max() > DEMO_MAX_TICKS):
+            raise ValueError(f"DemonstrationWriter: a demonstration holds 1 .. {DEMO_MAX_TICKS} rows")
+        if N and T_of.max() > self.chunk:
+            raise ValueError(f"DemonstrationWriter: a chunk of {self.chunk} rows does not hold one demonstration of {int(T_of.max())}")
+        targets, obstacles = np.asarray(targets, np.float32).reshape(N, 3), np.asarray(obstacles, np.float32).reshape(N, 3)
+        has = np.ones(N, bool) if has_path is None else np.asarray(has_path, bool)
+        records, parts = np.zeros((N, DEMO_FLOATS), np.float32), []
+        for first, n, T_cap in demonstration_chunks(T_of, self.chunk):
+            sl = slice(first, first + n)
+            self.load(plan, targets, obstacles, sl)
+            self.launch(n, T_cap)
+            records[sl] = self.records[:n].cpu().numpy()
+            # (the staging rows are reused by the next chunk: this chunk's kept rows are taken now)
+            parts.append(self._kept_of(self.rows[:n * T_cap].view(n, T_cap, self.row_floats), records[sl], has[sl], keep_contact))
+        rows = torch.cat(parts) if parts else torch.zeros(0, self.row_floats, device=self.dev)
+        return gather_demonstrations(records, has, lambda kept, valid: rows, keep_contact)._replace(action_size=self.A)
+
+    def _kept_of(self, rows, rec, has, keep_contact):
+        """the kept rows of one chunk: gather_demonstrations' keep rule on this chunk's records"""
+        from .environment.kinematic import gather_demonstrations
+        box = []
+        gather_demonstrations(rec, has, lambda kept, valid: box.append((kept, valid)), keep_contact)
+        kept, valid = box[0]
+        t = torch.arange(rows.shape[1], device=self.dev)[None, :]
+        mask = torch.from_numpy(kept).to(self.dev)[:, None] & (t < torch.from_numpy(valid).to(self.dev)[:, None])
+        return rows[mask]

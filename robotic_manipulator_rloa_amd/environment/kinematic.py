@@ -737,6 +737,168 @@ def joint_paths_host(twin: KinematicEnvironment, q_start, q_goal, obstacles, can
     return gather_joint_paths(records, vias, q_start, q_goal, samples)
 
 
+# ---- demonstrations: planned joint paths as replay rows (include/naf_hip.h, "Demonstrations") --------------------------------------
+DEMO_FLOATS = 8                       # NAF_CHAIN_DEMO_FLOATS
+DEMO_MAX_TICKS = 1024                 # NAF_CHAIN_DEMO_MAX_TICKS
+DEMO_CHUNK = 1 << 19                  # rows per chunk of a DemonstrationWriter (128 MiB of 64-float rows)
+DEMO_END_CODES = ("frames", "reached", "obstacle", "self", "workcell", "end")      # by end code: records_out[n][1]
+DEMO_KEPT = ("reached", "frames", "end")
+
+
+class DemonstrationPlan(NamedTuple):
+    """The time parametrisation of N paths start -> via -> goal (demonstration_plan): all the kernel sees of them."""
+    q_start: np.ndarray               # [N][A] float32: the start poses
+    leg_actions: np.ndarray           # [N][2][A] float32: the constant action of each leg
+    n_ticks: np.ndarray               # [N][2] int32: ticks per leg, each >= 1
+    rows: np.ndarray                  # [N] int: T_n = min(n1 + n2, frames)
+
+
+class Demonstrations(NamedTuple):
+    """Planned joint paths as replay rows (ManipulatorFramework.demonstrate_joint_paths): the episodes the environment's own step
+    rule produces when the arm is driven along each path open loop."""
+    outcome: np.ndarray               # [N] str: 'reached' | 'frames' | 'end' (the path ended short of 0.05 from the target) |
+                                      # 'obstacle' | 'self' | 'workcell' | 'none' (the query had no path)
+    frames: np.ndarray                # [N] int: rows of the demonstration, up to and including the first done; 0 for 'none'
+    final_distance: np.ndarray        # [N]: |ee - target| after its last row; NaN for 'none'
+    min_clearance: np.ndarray         # [N]: minima over its rows of the obstacle clearance (radius subtracted),
+    min_self_clearance: np.ndarray    # [N]: ... the self-clearance (+inf without pairs)
+    min_cell_clearance: np.ndarray    # [N]: ... and the workcell clearance (+inf without a workcell)
+    planned_ticks: np.ndarray         # [N] int: n1 + n2; 0 for 'none'
+    kept: np.ndarray                  # [N] bool: its rows are in `rows`
+    rows: object                      # [rows_total][row_floats] float32, query order then tick order: a device tensor, or numpy
+                                      # through the twin
+    rows_total: int
+    action_size: int = 0              # A of the arm the rows belong to
+
+
+def demonstration_speed_ok(speed) -> bool:
+    return isinstance(speed, (int, float, np.integer, np.floating)) and not isinstance(speed, bool) and 0.0 < float(speed) <= 1.0
+
+
+def demonstration_plan(q_start, via, q_goal, speed: float = 1.0, frames: int = 400) -> DemonstrationPlan:
+    """q_start, via, q_goal [N][A] (taken as float32 holds them) -> the plan. Leg k of length L_k = joint_distance32 takes
+    n_k = max(1, ceil(L_k / (speed DT))) ticks (float64) at the constant action (b - a) / (n_k DT), formed in float64 from the float32
+    end poses and rounded to float32; |a|_inf <= speed (a leg whose rounded action would exceed it — L_k rounds the exact max
+    difference, and the action rounds again — gets one tick more). A leg of length 0 is one tick at action 0."""
+    if not demonstration_speed_ok(speed):
+        raise ValueError(f"speed is a share of the unit action, 0 < speed <= 1: got {speed!r}")
+    if isinstance(frames, bool) or not isinstance(frames, (int, np.integer)) or not 1 <= frames <= DEMO_MAX_TICKS:
+        raise ValueError(f"frames is a number of steps from 1 to {DEMO_MAX_TICKS}: got {frames!r}")
+    a = np.asarray(q_start, np.float32)
+    a = a.reshape(-1, a.shape[-1])
+    v, b = np.asarray(via, np.float32).reshape(a.shape), np.asarray(q_goal, np.float32).reshape(a.shape)
+    ticks, acts = np.empty((len(a), 2), np.int64), np.empty((len(a), 2, a.shape[1]), np.float32)
+    for k, (lo, hi) in enumerate(((a, v), (v, b))):
+        L = joint_distance32(hi, lo).astype(np.float64)
+        n = np.maximum(1, np.ceil(L / (float(speed) * DT))).astype(np.int64)
+        d = hi.astype(np.float64) - lo.astype(np.float64)
+        act = (d / (n * DT)[:, None]).astype(np.float32)
+        over = np.max(np.abs(act), axis=-1) > np.float32(speed) if len(a) else np.zeros(0, bool)
+        n = n + over
+        ticks[:, k], acts[:, k] = n, np.where(over[:, None], (d / (n * DT)[:, None]).astype(np.float32), act)
+    if len(a) and (ticks.max() > 1 << 20 or not np.all(np.isfinite(acts))):
+        raise ValueError("demonstration_plan: a leg is too long for this speed, or a pose is not finite")
+    return DemonstrationPlan(a.copy(), acts, ticks.astype(np.int32), np.minimum(ticks.sum(axis=1), int(frames)))
+
+
+def demo_row_layout(A: int) -> Tuple[int, int, int, int]:
+    """(S, next_state offset, done offset, row floats) of the chain environment's replay row (include/naf_hip.h)"""
+    S = 2 * A + 9
+    off_s2 = (S + A + 1 + 3) // 4 * 4
+    need, rf = off_s2 + S + 1, 32
+    while rf < need:
+        rf *= 2
+    return S, off_s2, off_s2 + S, rf
+
+
+def demo_observations(twin: KinematicEnvironment, q, qd, target, obstacle) -> np.ndarray:
+    """[..., 2A + 9]: get_state() for batches of poses q[..., A], reported velocities qd[..., A] and scenes"""
+    q = np.asarray(q, float)
+    A = twin.n
+    out = np.empty(q.shape[:-1] + (2 * A + 9,))
+    for k, (src, const) in enumerate(twin.model.slots):
+        out[..., k] = q[..., src] if src >= 0 else const
+        out[..., A + k] = qd[..., src] if src >= 0 else 0.0
+    out[..., 2 * A:2 * A + 3] = twin.end_effector(q)
+    out[..., 2 * A + 3:2 * A + 6] = target
+    out[..., 2 * A + 6:] = obstacle
+    return out
+
+
+def demo_actions(plan: DemonstrationPlan, T: int) -> np.ndarray:
+    """[N][T][A] float64: a_t of every demonstration — leg 1's action for t < n1, leg 2's after (also past n1 + n2: never used)"""
+    first = (np.arange(T)[None, :] < plan.n_ticks[:, :1])[..., None]
+    return np.where(first, plan.leg_actions[:, None, 0, :], plan.leg_actions[:, None, 1, :]).astype(np.float64)
+
+
+def gather_demonstrations(records, has_path, kept_rows_of, keep_contact: bool) -> Demonstrations:
+    """Demonstrations from records[N][DEMO_FLOATS] (rows of queries without a path are ignored), has_path[N] and the rows that
+    kept_rows_of(kept[N], valid[N]) selects — the one place that states keep / drop."""
+    rec = np.asarray(records)
+    has = np.asarray(has_path, bool)
+    code = np.where(has, rec[:, 1], 0).astype(np.int64)
+    outcome = np.where(has, np.array(DEMO_END_CODES)[code], "none").astype("<U8")
+    kept = has & (np.isin(outcome, DEMO_KEPT) | bool(keep_contact))
+    valid = np.where(has, rec[:, 0], 0).astype(np.int64)
+    nan = lambda k: np.where(has, rec[:, k], np.nan).astype(rec.dtype)      # noqa: E731
+    out_rows = kept_rows_of(kept, valid)
+    return Demonstrations(outcome, valid, nan(2), nan(3), nan(4), nan(5), np.where(has, rec[:, 6], 0).astype(np.int64), kept, out_rows,
+                          int(np.sum(valid[kept])))
+
+
+def demonstration_rows_host(twin: KinematicEnvironment, plan: DemonstrationPlan, targets, obstacles, frames: int = 400,
+                            keep_contact: bool = False, has_path=None, full: bool = False):
+    """naf_chain_demo_rows through the twin alone: KinematicEnvironment.trace — the float64 episode under given actions — from
+    the plan's start poses under its actions, cut at T_n = min(n1 + n2, frames); the rows are get_state() before and after every
+    step, the velocity slots what the step before reported. Returns Demonstrations with `rows` a float32 numpy array; full=True
+    returns (demonstrations, records[N][8] float64, rows[N][T][row floats] float64 with NaN where there is no row, poses[N][T + 1][A])."""
+    N, A = plan.q_start.shape
+    S, off_s2, off_d, rf = demo_row_layout(A)
+    has = np.ones(N, bool) if has_path is None else np.asarray(has_path, bool)
+    targets = np.broadcast_to(np.asarray(targets, np.float32).astype(np.float64), (N, 3))
+    obstacles = np.broadcast_to(np.asarray(obstacles, np.float32).astype(np.float64), (N, 3))
+    Tn = np.minimum(plan.n_ticks.astype(np.int64).sum(axis=1), int(frames))
+    T = int(Tn.max()) if N else 1
+    actions = demo_actions(plan, T)
+    tr = twin.trace(plan.q_start.astype(np.float64), actions, targets, obstacles, T)
+    valid = np.minimum(tr.frames, Tn)
+    done = (tr.code != 0) & (tr.frames <= Tn)
+    m = np.concatenate([tr.margins, tr.cell_margins[..., None]], axis=-1)                 # [N, T, 4]
+    live = np.arange(T)[None, :] < valid[:, None]
+    last = np.take_along_axis(m, (valid - 1)[:, None, None], axis=1)[:, 0]
+    records = np.zeros((N, DEMO_FLOATS))
+    records[:, 0] = valid
+    records[:, 1] = np.where(done, tr.code, np.where(Tn < plan.n_ticks.astype(np.int64).sum(axis=1), 0, 5))
+    records[:, 2] = last[:, 0] + TARGET_THRESHOLD
+    for k, col in ((3, 1), (4, 2), (5, 3)):
+        records[:, k] = np.min(np.where(live, m[:, :, col], np.inf), axis=1)
+    records[:, 6] = plan.n_ticks.astype(np.int64).sum(axis=1)
+    # the rows: state t = obs(p_t) with step t - 1's reported velocities, next_state t = state t + 1
+    lo, hi = twin.joint_limits()
+    path = tr.joint_positions                                                              # [N, T + 1, A], held behind the end
+    pre = path[:, :-1] + DT * actions
+    vel = np.where((pre < lo) | (pre > hi), 0.0, actions)
+    qd = np.concatenate([np.zeros((N, 1, A)), vel], axis=1)
+    obs = demo_observations(twin, path, qd, targets[:, None, :], obstacles[:, None, :])    # [N, T + 1, S]
+    dist = m[:, :, 0] + TARGET_THRESHOLD
+    reached = dist < TARGET_THRESHOLD
+    hit = (m[:, :, 1] < 0.0) | (m[:, :, 2] < 0.0) | (m[:, :, 3] < 0.0)
+    rows = np.zeros((N, T, rf))
+    rows[:, :, :S] = obs[:, :-1]
+    rows[:, :, S:S + A] = actions
+    with np.errstate(invalid="ignore"):
+        rows[:, :, S + A] = np.where(reached, 250.0, np.where(hit, -1000.0, -(dist - TARGET_THRESHOLD)))
+    rows[:, :, off_s2:off_s2 + S] = obs[:, 1:]
+    rows[:, :, off_d] = reached | hit
+    rows[~live] = np.nan
+
+    def kept_rows(kept, valid_):
+        mask = kept[:, None] & (np.arange(T)[None, :] < valid_[:, None])
+        return rows[mask].astype(np.float32)
+    demos = gather_demonstrations(records, has, kept_rows, keep_contact)._replace(action_size=A)
+    return (demos, records, rows, path) if full else demos
+
+
 def cell_box_gaps(model: ChainModel, centre, half) -> np.ndarray:
     """[G + H + B]: how near the box centre +- half (a point when half is 0) comes to each workcell geometry. Against a half-space
     the box corner with the smallest n.x decides: min over the box of n.x - d = n.centre - |n|.half - d. Against a sphere: the

@@ -476,7 +476,7 @@ class NAFAgent:
                        noise_scale: float = 1.0, robot: str = "kuka", obstacle_jitter: float = 0.0, *,
                        episodes: Optional[int] = None, preset=None, variation=None, drain_every: int = 64,
                        verbose: bool = False, resume: bool = False, chain=None, scene: Optional[dict] = None,
-                       hindsight: float = 0.0, hindsight_horizon: Optional[int] = None) -> dict:
+                       hindsight: float = 0.0, hindsight_horizon: Optional[int] = None, demonstrations=None) -> dict:
         """NAFAgent.run (naf_algorithm.py:228-292) re-hosted for E synthetic arms on the GPU feeding the HBM replay ring;
         each vector step is followed by E * num_updates / update_freq learn() calls, i.e. the reference's update-to-data
         ratio. Everything stays on the device, no host sync per step.
@@ -511,9 +511,16 @@ class NAFAgent:
         The step kernel then tags every row with its episode and the gather relabels goal, reward and done; nothing else changes.
         The ring must be empty when such a run starts (a resume continues its own ring), and last_run_stats gains
         hindsight_relabelled_share / hindsight_shortened_share / hindsight_reached_share, a sample of the LAST chunk's rows.
-        0 (the default): the launches, the rows and the training state of a run without the argument."""
+        0 (the default): the launches, the rows and the training state of a run without the argument.
+
+        demonstrations (chain only; environment.kinematic.Demonstrations): its kept rows are appended to the ring before the
+        first tick (add_demonstrations), so learning starts at the first tick once they exceed the batch size; last_run_stats
+        gains demonstration_rows / demonstrations_kept / demonstrations_dropped_contact. Refused on a resume (the saved ring
+        holds them already) and together with hindsight. None (the default): nothing of a run without the argument changes."""
         E = int(n_envs)
         hs = self._hindsight_arguments(hindsight, hindsight_horizon, max_frames, chain, resume)
+        if demonstrations is not None:
+            self._demonstration_refusals(chain, resume, hs, E)
         if (E * self.num_updates) % self.update_freq != 0:
             raise ValueError("n_envs * num_updates must be a multiple of update_freq")
         if vector_steps is None and episodes is None:
@@ -527,6 +534,7 @@ class NAFAgent:
         chunk = UpdateChunk(self.learner, self.memory, U, use_graph=self.use_graph, hindsight=hs and (hs[0], hs[1], E))
         ledger = self._ledger(episodes)
         self.memory.flush()
+        demo_stats = None if demonstrations is None else self.add_demonstrations(demonstrations)
         updates = steps = 0
         dropped = []                       # episodes the budget left unrecorded (a resume with a larger budget books them)
         position = dict(n_envs=E, max_frames=int(max_frames), noise_scale=float(noise_scale), robot=robot,
@@ -589,7 +597,56 @@ class NAFAgent:
             off_d = self.learner.lay.S + self.memory.off_s2
             self.last_run_stats.update(shares(chunk.k_out.cpu().numpy(), chunk.k0_out.cpu().numpy(),
                                               chunk.batch[..., off_d].cpu().numpy()))
+        if demo_stats is not None:
+            self.last_run_stats.update(demo_stats)
         return self.last_run_stats
+
+    def _demonstration_refusals(self, chain, resume, hs, E) -> None:
+        """every reason a run cannot take demonstrations, named"""
+        if chain is None:
+            raise ValueError("demonstrations need the kinematic arm environment's rows (a chain model): the stand-in, PyBullet "
+                             "and host environments have no planned joint paths")
+        if E <= 1:
+            raise ValueError("demonstrations need n_envs > 1: the one-env loop does not read device rows")
+        if self.world_size > 1:
+            raise ValueError("demonstrations are not available in a data-parallel run")
+        if resume:
+            raise ValueError("demonstrations cannot be added on a resume: the saved ring, demonstrations included, is already "
+                             "in the training state")
+        if hs:
+            raise ValueError("demonstrations cannot be combined with hindsight goals: hindsight needs a ring filled by this run "
+                             "alone (rows i and i + n_envs must be the same env one tick apart)")
+
+    def add_demonstrations(self, demos) -> dict:
+        """Append the kept rows of `demos` (environment.kinematic.Demonstrations) to the replay ring, in their order, with
+        add_rows_device: NAF is off-policy, and a transition of the environment is a legitimate row whoever chose its action.
+        Returns {demonstration_rows, demonstrations_kept, demonstrations_dropped_contact}."""
+        if self.world_size > 1:
+            raise ValueError("demonstrations are not available in a data-parallel run")
+        rows = demos.rows
+        if isinstance(rows, np.ndarray):
+            rows = torch.from_numpy(np.ascontiguousarray(rows, np.float32))
+        if not torch.is_tensor(rows) or rows.dim() != 2 or rows.dtype != torch.float32:
+            raise ValueError("demonstrations: rows is a [rows_total][row_floats] float32 array")
+        m = self.memory
+        if m.A is None:
+            m._allocate(int(self.state_size), int(self.action_size))
+        if int(demos.action_size) != m.A or 2 * int(demos.action_size) + 9 != m.S:
+            raise ValueError(f"demonstrations: the rows belong to an arm of {int(demos.action_size)} joints, the agent's has "
+                             f"{m.A} (state size {m.S})")
+        if rows.shape[1] != m.row_floats:
+            raise ValueError(f"demonstrations: a row is {rows.shape[1]} floats wide, the agent's replay ring holds rows of {m.row_floats}")
+        n = int(rows.shape[0])
+        if n != int(demos.rows_total):
+            raise ValueError(f"demonstrations: rows_total says {int(demos.rows_total)}, rows holds {n}")
+        if n > m.buffer_size:
+            raise ValueError(f"demonstrations: {n} rows are more than the replay buffer holds ({m.buffer_size})")
+        if n > 0:
+            m.flush()
+            m.add_rows_device(rows.to(m.device).contiguous(), n)
+        outcome, kept = np.asarray(demos.outcome), np.asarray(demos.kept, bool)
+        return {"demonstration_rows": n, "demonstrations_kept": int(kept.sum()),
+                "demonstrations_dropped_contact": int(np.sum(~kept & np.isin(outcome, ("obstacle", "self", "workcell"))))}
 
     def _hindsight_arguments(self, hindsight, horizon, max_frames, chain, resume):
         """(ratio, horizon) of a run with hindsight goals, None without; every refusal names its reason."""

@@ -32,7 +32,8 @@ import torch
 
 from .environment.kinematic import (SCENE_CONDITIONS, KinematicEnvironment, build_kinematic, cell_box_gaps, choose_scene,
                                     goal_poses_host, ik_restarts_ok, joint_paths_host, reach_queries, JointPaths,
-                                    PATH_CANDIDATES_MAX)
+                                    PATH_CANDIDATES_MAX, DEMO_MAX_TICKS, Demonstrations, demonstration_plan,
+                                    demonstration_rows_host, demonstration_speed_ok)
 from .environment.synthetic import SyntheticEnvironment
 from .environment.urdf_chain import SCENE_TRIES, TARGET_THRESHOLD, cell_geometry_name
 from .naf_components.naf_algorithm import NAFAgent
@@ -424,6 +425,82 @@ class ManipulatorFramework:
             return self._paths_to_goals(goal, q0, obstacles, kw)
         return self._plan_checked(q0, q_goal, obstacles, **kw)
 
+    def demonstrate_joint_paths(self, paths, targets=None, obstacles=None, speed: float = 1.0, frames: int = 400,
+                                keep_contact: bool = False, on_device: Optional[bool] = None):
+        """Planned joint paths as demonstrations (kinematic environment only; needs no agent): query n drives the arm along
+        paths' chosen polyline start -> via -> goal under the environment's own step rule, open loop — leg k in
+        n_k = max(1, ceil(L_k / (speed DT))) ticks at one constant action, |a| <= speed — and every tick becomes the replay row
+        run_training's environment would have written: an episode it could have produced. The poses follow the step's float32
+        recurrence, so the arm reaches via and goal within its accumulated rounding (about 1e-4 rad at 400 ticks).
+          paths        : JointPaths of plan_joint_paths(); queries with candidate < 0 get outcome 'none'
+          targets      : [N][3], or None: the end effector at each path's goal pose; obstacles: as reach_targets() takes them
+          speed        : 0 < speed <= 1, the share of the unit action — the policy's mean action is a tanh
+          frames       : the episode budget, 1 .. 1024: a longer path is cut there (outcome 'frames')
+          keep_contact : demonstrations that touch the obstacle, the arm or the workcell are dropped whole (the path was checked
+                         at its samples only) unless this is set
+          on_device    : None: the device when there is one; False: the float64 host twin, `rows` a numpy array (slow)
+        Returns environment.kinematic.Demonstrations: outcome ('reached' | 'frames' | 'end' | 'obstacle' | 'self' | 'workcell' |
+        'none'), frames, final_distance, the three minima, planned_ticks, kept, rows [rows_total][row floats], rows_total."""
+        if not self.env:
+            raise EnvironmentNotInitialized
+        if not isinstance(self.env, KinematicEnvironment):
+            raise ConfigurationIncomplete('demonstrate_joint_paths() needs the kinematic environment '
+                                          '(initialize_kinematic_environment()): PyBullet and the synthetic stand-in have no chain '
+                                          'model to drive')
+        env = self.env
+        if not isinstance(paths, JointPaths) or paths.start is None or paths.goal is None:
+            raise InvalidEnvironmentParameter('paths is the JointPaths that plan_joint_paths() returned')
+        if not demonstration_speed_ok(speed):
+            raise InvalidEnvironmentParameter(f'speed is a share of the unit action, 0 < speed <= 1: got {speed!r}')
+        if not _positive_int(frames) or frames > DEMO_MAX_TICKS:
+            raise InvalidEnvironmentParameter(f'frames is a number of steps from 1 to {DEMO_MAX_TICKS}: got {frames!r}')
+        has = np.asarray(paths.candidate) >= 0
+        start = np.asarray(paths.start, np.float64)
+        N, A = start.shape
+        if A != env.model.A:
+            raise InvalidEnvironmentParameter(f'paths holds poses of {A} joints, the environment\'s arm has {env.model.A}')
+        # a query without a path stands still at its start pose for the launch and is reported 'none'
+        via = np.where(has[:, None], np.asarray(paths.via, np.float64), start)
+        goal = np.where(has[:, None], np.asarray(paths.goal, np.float64), start)
+        nominal = env.obstacle_centre if env.scene_ranges_on else env.obstacle_pos
+        try:
+            if targets is None:
+                targets = env.end_effector(np.asarray(goal, np.float32).astype(np.float64))
+            _, targets, obstacles, _ = reach_queries(env.model, targets, obstacles, None, 1, nominal_obstacle=nominal,
+                                                     nominal_start=env.initial_joint_positions)
+            if len(targets) != N:
+                raise ValueError(f'targets is [N][3] with N = {N}, the number of paths: got {len(targets)}')
+        except ValueError as err:
+            raise InvalidEnvironmentParameter(str(err)) from None
+        plan = demonstration_plan(start, via, goal, float(speed), int(frames))
+        if on_device is None:
+            on_device = torch.cuda.is_available()
+        if not on_device:
+            return demonstration_rows_host(env, plan, targets, obstacles, int(frames), bool(keep_contact), has)
+        from .engine import DemonstrationWriter
+        key = (env.model.digest(), float(env.obstacle_radius))
+        if getattr(self, '_demo_writer', None) is None or self._demo_writer[0] != key:
+            self._demo_writer = None
+            self._demo_writer = (key, DemonstrationWriter(env.model, env.obstacle_radius))
+        return self._demo_writer[1].write(plan, targets, obstacles, bool(keep_contact), has)
+
+    def _check_demonstrations(self, demos, E) -> None:
+        if not isinstance(demos, Demonstrations):
+            raise InvalidNAFAgentParameter('demonstrations is the Demonstrations that demonstrate_joint_paths() returned')
+        if not isinstance(self.env, KinematicEnvironment):
+            raise ValueError('demonstrations need the kinematic arm environment (a chain model on the device): the synthetic '
+                             'stand-in and PyBullet have no planned joint paths')
+        if E is None or E <= 1:
+            raise ValueError('demonstrations need n_envs > 1: the one-env loop does not read device rows')
+
+    def add_demonstrations(self, demos) -> dict:
+        """Append the kept rows of `demos` (demonstrate_joint_paths()) to the agent's replay ring, in query order then tick order.
+        Returns the counts run_training(demonstrations=) leaves in last_run_stats."""
+        if not self.naf_agent or not self.env:
+            raise ConfigurationIncomplete
+        self._check_demonstrations(demos, 2)
+        return self.naf_agent.add_demonstrations(demos)
+
     def solve_goal_poses(self, targets, obstacles=None, initial_joint_positions=None, restarts: int = 8, iterations: int = 32,
                          tolerance: float = 1e-3, clearance_margin: float = 0.0, seed: int = 0, on_device: Optional[bool] = None):
         """Joint values that put the end effector on GIVEN targets (kinematic environment only; needs no agent): per query a
@@ -722,15 +799,20 @@ class ManipulatorFramework:
 
     # ---- training ---------------------------------------------------------------------------------------------------
     def run_training(self, episodes: int, frames: Optional[int] = 500, verbose: bool = True, n_envs: Optional[int] = None,
-                     hindsight: float = 0.0, hindsight_horizon: Optional[int] = None):
+                     hindsight: float = 0.0, hindsight_horizon: Optional[int] = None, demonstrations=None):
         """rl_framework.py:478-501 -> NAFAgent.run(frames, episodes, verbose): {episode: (score, last_frame)}, checkpoints,
         model.p. n_envs=E (or the n_envs given to initialize_naf_agent): the same outputs from E environments at once —
         episodes numbered in completion order, `frames` the budget of each; counters in naf_agent.last_run_stats.
-        hindsight / hindsight_horizon (kinematic environment with n_envs=E only): NAFAgent.run_vectorized's hindsight goals."""
+        hindsight / hindsight_horizon (kinematic environment with n_envs=E only): NAFAgent.run_vectorized's hindsight goals.
+        demonstrations (kinematic environment with n_envs=E only): the Demonstrations of demonstrate_joint_paths(), whose kept rows
+        seed the replay ring before the first tick; not together with hindsight, not on a resume."""
         if not self.naf_agent or not self.env:
             raise ConfigurationIncomplete
         E = n_envs if n_envs is not None else self._n_envs
         hs = self._hindsight_arguments(hindsight, hindsight_horizon, E)
+        if demonstrations is not None:
+            self._check_demonstrations(demonstrations, E)
+            hs = dict(hs, demonstrations=demonstrations)
         if E is None or E <= 1:
             return self.naf_agent.run(frames, episodes, verbose)
         if isinstance(self.env, _DEVICE_ENVS):
@@ -754,12 +836,16 @@ class ManipulatorFramework:
         return {'hindsight': float(hindsight), 'hindsight_horizon': hindsight_horizon}
 
     def resume_training(self, episode: int, episodes: int, frames: Optional[int] = 500, verbose: bool = True,
-                        n_envs: Optional[int] = None, hindsight: float = 0.0, hindsight_horizon: Optional[int] = None):
+                        n_envs: Optional[int] = None, hindsight: float = 0.0, hindsight_horizon: Optional[int] = None,
+                        demonstrations=None):
         """Continue the run_training() whose checkpoint `episode` holds a training_state.pt (an agent initialised with
         save_training_state=True writes one beside weights.p) up to `episodes` episodes: the same run as if it had never
         stopped. Returns the whole scores dict. frames / n_envs must be those of the saved run."""
         if not self.naf_agent or not self.env:
             raise ConfigurationIncomplete
+        if demonstrations is not None:
+            raise ValueError('demonstrations cannot be added on a resume: the saved ring, demonstrations included, is already in '
+                             'the training state')
         if not isinstance(episode, int) or isinstance(episode, bool) or episode < 1:
             raise InvalidNAFAgentParameter('The checkpoint episode received is not a positive integer')
         if not isinstance(episodes, int) or isinstance(episodes, bool) or episodes < episode:

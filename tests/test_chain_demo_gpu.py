@@ -1,0 +1,252 @@
+"""GPU (`-m gpu`): naf_chain_demo_rows (csrc/chain_env.hip) against the step kernel it restates (reset_given, then T_cap x
+naf_chain_env_step fed the plan's actions), against the float64 rule of environment/kinematic.py (demonstration_rows_host) and for
+chain exactness, through the C ABI with poisoned pad rows behind every output; placement independence; engine.DemonstrationWriter
+across chunks and the ring after add_demonstrations; and plan_joint_paths -> demonstrate_joint_paths -> run_training end to end.
+tests/test_chain_demo_cpu.py rehearses every case with a float32 restatement."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import chain_demo_common as D
+import chain_rollout_common as C
+from test_chain_env_gpu import _agent
+from test_chain_rollout_gpu import IIWA_RANGED
+
+from robotic_manipulator_rloa_amd.environment.kinematic import demo_actions, demo_row_layout, gather_demonstrations
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+PAD = 3                        # demonstrations behind the N of the launch that no lane may write
+bits = D.bits
+
+
+@pytest.fixture()
+def scratch_cwd(tmp_path):
+    old = os.getcwd()
+    os.chdir(tmp_path)
+    yield tmp_path
+    os.chdir(old)
+
+
+class DemoRig:
+    """The launch of one case through the C ABI; rows, records and poses have PAD poisoned demonstrations behind the launch's."""
+
+    def __init__(self, case):
+        from robotic_manipulator_rloa_amd import _lib
+        self.lib = _lib.load()
+        self.case = case
+        model = case.model
+        self.N, self.T, self.A = case.N, case.T_cap, model.A
+        self.S, self.off_s2, self.off_d, self.rf = demo_row_layout(self.A)
+        assert self.rf == self.lib.naf_replay_row_floats(self.S, self.A)
+        blob = np.ascontiguousarray(model.pack())
+        self.h = ctypes.c_void_p()
+        assert self.lib.naf_chain_env_create(blob.ctypes.data, int(blob.size), ctypes.byref(self.h)) == 0
+        dev = lambda a, kind=np.float32: torch.from_numpy(np.ascontiguousarray(a, kind)).to(DEV)      # noqa: E731
+        plan = case.plan
+        self.q_start, self.actions, self.ticks = dev(plan.q_start), dev(plan.leg_actions), dev(plan.n_ticks, np.int32)
+        self.targets, self.obstacles = dev(case.targets), dev(case.obstacles)
+        nan = dict(fill_value=float("nan"), device=DEV)
+        self.rows = torch.full((self.N + PAD, self.T, self.rf), **nan)
+        self.records = torch.full((self.N + PAD, 8), **nan)
+        self.poses = torch.full((self.N + PAD, self.T + 1, self.A), **nan)
+
+    def run(self, poses=True, stream=None):
+        """returns (rows[N, T_cap, rf], records[N, 8], poses[N, T_cap + 1, A]) as numpy copies; NaN where nothing was written"""
+        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        p = lambda t: t.data_ptr()      # noqa: E731
+        for t in (self.rows, self.records, self.poses):
+            t.fill_(float("nan"))
+        assert self.lib.naf_chain_demo_rows(self.h, p(self.q_start), p(self.actions), p(self.ticks), p(self.targets), p(self.obstacles),
+                                            D.ORAD, self.N, self.T, p(self.rows), self.rf, p(self.records),
+                                            p(self.poses) if poses else None, st) == 0
+        torch.cuda.synchronize()
+        N = self.N
+        assert torch.isnan(self.rows[N:]).all() and torch.isnan(self.records[N:]).all() and torch.isnan(self.poses[N:]).all()
+        rows, poses_ = self.rows[:N].cpu().numpy(), self.poses[:N].cpu().numpy()
+        Tn = self.case.plan.rows
+        assert np.isnan(rows[np.arange(self.T)[None, :] >= Tn[:, None]]).all()             # rows T_n .. T_cap - 1 are not written
+        if poses:
+            assert np.isnan(poses_[np.arange(self.T + 1)[None, :] > Tn[:, None]]).all()
+        return rows, self.records[:N].cpu().numpy(), poses_
+
+    def steps(self):
+        """rows[N, T_cap, rf] of the composed form: reset_given at the start poses and scenes, then T_cap x naf_chain_env_step at
+        E = N fed the plan's actions from the device. An env that is done resets itself: its later rows are another episode's."""
+        lib, case, N, T, A = self.lib, self.case, self.N, self.T, self.A
+        p = lambda t: t.data_ptr()      # noqa: E731
+        scene = torch.from_numpy(np.concatenate([case.targets, case.obstacles], axis=1).astype(np.float32)).to(DEV)
+        act = torch.from_numpy(np.ascontiguousarray(demo_actions(case.plan, T).transpose(1, 0, 2), np.float32)).to(DEV)      # [T, N, A]
+        st = torch.zeros(N, lib.naf_chain_env_state_floats(self.h), device=DEV)
+        obs = torch.zeros(N, self.S, device=DEV)
+        out = torch.zeros(T, N, self.rf, device=DEV)
+        s = torch.cuda.current_stream().cuda_stream
+        assert lib.naf_chain_env_reset_given(self.h, p(st), p(obs), N, p(self.q_start), p(scene), D.ORAD, s) == 0
+        for t in range(T):
+            assert lib.naf_chain_env_step(self.h, p(st), p(act[t]), p(out[t]), p(obs), N, 0, None, 0, None, 0, s) == 0
+        torch.cuda.synchronize()
+        return out.cpu().numpy().transpose(1, 0, 2)
+
+    def close(self):
+        torch.cuda.synchronize()
+        assert self.lib.naf_chain_env_destroy(self.h) == 0
+
+
+CASES = [(name, N, T) for name in D.ARMS for N, T in D.COUNTS] + D.EXTRA
+
+
+@pytest.mark.parametrize("name,N,T_cap", CASES)
+def test_demo_rows_against_the_step_kernel_and_the_rule(name, N, T_cap):
+    """One case through the C ABI, poses_out on.
+    Against the step kernel: for the rows up to each demonstration's first done, joint positions, velocities and actions of state
+    and next_state are bit for bit the composed form's; every other float within 1 tol (chain_rollout_common.tol_of, the path
+    PR's parity standard: the same source expressions are contracted differently in a kernel of another shape); reward class and
+    done equal wherever the twin's margins at the recorded poses lie outside the bands (at most 1 % of the ticks inside); the
+    record's count is the composed form's first done, and its code that row's class.
+    Against the float64 rule and for chain exactness: chain_demo_common.check_rows. A run without poses_out gives the same bits,
+    and the PAD demonstrations and the rows behind T_n keep their poison."""
+    case = D.build_case(name, N, T_cap)
+    rig = DemoRig(case)
+    rows, rec, poses = rig.run()
+    plain_rows, plain_rec, _ = rig.run(poses=False)
+    ref = rig.steps()
+    rig.close()
+    assert np.array_equal(bits(np.nan_to_num(rows)), bits(np.nan_to_num(plain_rows))) and np.array_equal(bits(rec), bits(plain_rec))
+    D.check_rows(case, rows, rec, poses)
+    A, S, off_s2, off_d = rig.A, rig.S, rig.off_s2, rig.off_d
+    tol = C.tol_of(case.model)
+    valid = rec[:, 0].astype(np.int64)
+    live = np.arange(T_cap)[None, :] < valid[:, None]
+    exact = np.zeros(rig.rf, bool)
+    for lead in (0, off_s2):
+        exact[lead:lead + 2 * A] = True                       # positions and velocities
+        exact[lead + 2 * A + 3:lead + 2 * A + 9] = True       # target and obstacle
+    exact[S:S + A] = True                                     # the action
+    exact[S + A + 1:off_s2] = exact[off_d + 1:] = True        # the zeros, the tag float included
+    got, want = rows[live], ref[live]
+    assert np.array_equal(bits(got[:, exact]), bits(want[:, exact]))
+    band = D.band_of(case, D.margins_at(case, np.nan_to_num(poses)))[live]
+    assert band.sum() <= D.CAP * live.sum()
+    ee = np.zeros(rig.rf, bool)
+    ee[2 * A:2 * A + 3] = ee[off_s2 + 2 * A:off_s2 + 2 * A + 3] = True
+    err = float(np.abs(got[:, ee].astype(np.float64) - want[:, ee]).max())
+    print(f"{name} N={N} T_cap={T_cap}: end effector against the step kernel {err:.2e} (tol {tol:.2e}); "
+          f"{'every float bit-equal' if np.array_equal(bits(got), bits(want)) else 'not to the bit'}")
+    assert err <= tol
+    sure = ~band
+    assert np.array_equal(got[sure, off_d], want[sure, off_d])
+    r_got, r_want = got[sure, S + A].astype(np.float64), want[sure, S + A].astype(np.float64)
+    terminal = (r_want == 250.0) | (r_want == -1000.0)
+    assert np.array_equal(r_got[terminal], r_want[terminal]) and np.abs(r_got - r_want)[~terminal].max(initial=0.0) <= tol
+    # the record follows: the composed form's first done, where no tick up to it lies inside a band
+    first_band = np.array([D.band_of(case, D.margins_at(case, np.nan_to_num(poses)))[n, :valid[n]].any() for n in range(N)])
+    ref_done = ref[..., off_d] == 1.0
+    ref_valid = np.where(ref_done.any(axis=1), ref_done.argmax(axis=1) + 1, T_cap + 1)
+    Tn = case.plan.rows
+    assert np.array_equal(valid[~first_band], np.minimum(ref_valid, Tn)[~first_band])
+    # ... and what the twin said of the case: outcome and count of every demonstration (the cases hold no tick inside a band)
+    _, h_rec, _, _ = case.host()
+    if not first_band.any():
+        assert np.array_equal(rec[:, 0], h_rec[:, 0]) and np.array_equal(rec[:, 1], h_rec[:, 1])
+
+
+def test_placement_independence_through_the_c_abi():
+    """Demonstration 9 of the 16 x 256 case gives the same rows, record and poses alone at index 0 of a launch of one as deep
+    inside the launch of 16, bit for bit; a launch on a side stream gives the current stream's bits."""
+    case = D.build_case("iiwa_like7", 16, 256)
+    rig = DemoRig(case)
+    big = rig.run()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    on_side = rig.run(stream=side.cuda_stream)
+    rig.close()
+    for a, b in zip(big, on_side):
+        assert np.array_equal(bits(np.nan_to_num(a)), bits(np.nan_to_num(b)))
+    for n in (9, 2):
+        one = DemoRig(case.sub(n))
+        alone = one.run()
+        one.close()
+        for a, b in zip(big, alone):
+            assert np.array_equal(bits(np.nan_to_num(a[n])), bits(np.nan_to_num(b[0])))
+
+
+@pytest.mark.parametrize("name,N,T_cap,chunk", [("iiwa_like7", 16, 256, 2 * 256), ("long12", 3, 130, 130), ("slider4", 16, 256, None)])
+def test_demonstration_writer_across_chunks_and_the_ring(name, N, T_cap, chunk):
+    """engine.DemonstrationWriter in forced small chunks (two demonstrations / one a chunk) and in one chunk gives the kept rows of
+    one C-ABI launch, in query order then tick order, and its numbers; keep_contact adds the dropped ones' rows. After
+    add_demonstrations on a fresh agent (action_mode='float': the default gather truncates the actions on the way out, as the
+    reference's .long() does), gather_rows with idx = arange reads back exactly those rows, and len(memory) is their count."""
+    from robotic_manipulator_rloa_amd.engine import DemonstrationWriter
+    case = D.build_case(name, N, T_cap)
+    rig = DemoRig(case)
+    rows, rec, _ = rig.run(poses=False)
+    rig.close()
+    for keep_contact in (False, True):
+        def kept_rows(kept, valid):
+            return rows[kept[:, None] & (np.arange(T_cap)[None, :] < valid[:, None])]
+        want = gather_demonstrations(rec, np.ones(N, bool), kept_rows, keep_contact)
+        whole = DemonstrationWriter(case.model, D.ORAD).write(case.plan, case.targets, case.obstacles, keep_contact)
+        parts = DemonstrationWriter(case.model, D.ORAD, chunk=chunk).write(case.plan, case.targets, case.obstacles, keep_contact)
+        for f, a, b, c in zip(want._fields[:8], whole, parts, want):
+            assert a.dtype == b.dtype == c.dtype and a.tobytes() == b.tobytes() == c.tobytes(), f
+        assert whole.rows.is_cuda and whole.rows.is_contiguous() and whole.rows_total == parts.rows_total == want.rows_total
+        assert np.array_equal(bits(whole.rows.cpu().numpy()), bits(want.rows)) and torch.equal(whole.rows, parts.rows)
+    assert (~want.kept).sum() == 0 and (~gather_demonstrations(rec, np.ones(N, bool), kept_rows, False).kept).sum() >= 1
+    demos = DemonstrationWriter(case.model, D.ORAD, chunk=chunk).write(case.plan, case.targets, case.obstacles)
+    agent = _agent(case.model, action_mode="float")
+    stats = agent.add_demonstrations(demos)
+    n = demos.rows_total
+    assert len(agent.memory) == n == stats["demonstration_rows"] and stats["demonstrations_kept"] == int(demos.kept.sum())
+    assert stats["demonstrations_dropped_contact"] == int((~demos.kept).sum()) >= 1
+    back = torch.zeros(n, agent.memory.row_floats, device=DEV)
+    agent.memory.gather_rows(torch.arange(n, dtype=torch.int32, device=DEV), back, n)
+    torch.cuda.synchronize()
+    assert torch.equal(back, demos.rows)
+
+
+def test_framework_demonstrations_end_to_end(scratch_cwd, monkeypatch):
+    """plan_joint_paths -> demonstrate_joint_paths -> run_training(8, 50, n_envs=16, demonstrations=...) on iiwa_like7: the stats
+    fields are there, the ring starts above the batch size so that every tick of the run is followed by its updates, and the
+    device's demonstrations carry the twin's outcomes. Off means off: the same short run without the argument ends with weights
+    bit-equal to a second run without it, and launches no demonstration kernel."""
+    from chain_resume_worker import make_framework
+    from robotic_manipulator_rloa_amd import engine
+    N = 24
+    rng = np.random.default_rng(8)
+    targets = np.array(IIWA_RANGED["target_position"]) + rng.uniform(-0.15, 0.15, (N, 3))
+    f = make_framework(IIWA_RANGED, checkpoint_frequency=64, save=False)
+    paths = f.plan_joint_paths(targets, candidates=8, seed=3)
+    assert (paths.candidate >= 0).sum() >= N // 2
+    demos = f.demonstrate_joint_paths(paths, frames=400)
+    host = f.demonstrate_joint_paths(paths, frames=400, on_device=False)
+    assert demos.rows.is_cuda and demos.rows_total == demos.rows.shape[0] > f.naf_agent.batch_size
+    assert np.array_equal(demos.planned_ticks, host.planned_ticks) and np.array_equal(demos.outcome == "none", paths.candidate < 0)
+    same = demos.outcome == host.outcome                      # (a tick inside a band may end one differently: few, if any)
+    assert same.mean() >= 0.9 and np.array_equal(demos.frames[same], host.frames[same])
+    assert set(demos.outcome[demos.kept]) <= {"reached", "frames", "end"} and (demos.outcome == "reached").sum() >= 1
+    before = len(f.naf_agent.memory)
+    f.run_training(8, 50, verbose=False, n_envs=16, demonstrations=demos)
+    stats = f.naf_agent.last_run_stats
+    assert before == 0 and stats["demonstration_rows"] == demos.rows_total and stats["demonstrations_kept"] == int(demos.kept.sum())
+    assert stats["demonstrations_dropped_contact"] == int(np.isin(demos.outcome, ("obstacle", "self", "workcell")).sum())
+    steps = stats["env_steps"] // 16
+    per_step = 16 * f.naf_agent.num_updates // f.naf_agent.update_freq
+    assert stats["updates"] == steps * per_step > 0            # learning started at the first tick
+    assert len(f.naf_agent.memory) == demos.rows_total + stats["env_steps"]
+    with pytest.raises(ValueError, match="ring filled by this run alone"):
+        f.run_training(8, 50, verbose=False, n_envs=16, demonstrations=demos, hindsight=0.5)
+
+    def no_launch(self, *a, **kw):
+        raise AssertionError("a run without demonstrations launched the demonstration kernel")
+    monkeypatch.setattr(engine.DemonstrationWriter, "launch", no_launch)
+    digests = []
+    for _ in range(2):
+        g = make_framework(IIWA_RANGED, checkpoint_frequency=64, save=False)
+        g.run_training(8, 50, verbose=False, n_envs=16)
+        assert "demonstration_rows" not in g.naf_agent.last_run_stats
+        assert g.naf_agent.last_run_stats["updates"] < g.naf_agent.last_run_stats["env_steps"] // 16 * per_step     # (it waited for the ring)
+        digests.append(g.naf_agent.training_state_digest())
+    assert digests[0] == digests[1] and digests[0] != f.naf_agent.training_state_digest()
