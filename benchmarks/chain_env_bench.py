@@ -50,6 +50,10 @@ launches are the box instantiations, which test the floor and the spheres too.
       largest difference between their minima. Then the README's question on 2000 targets around the nominal one: the goal poses
       (GoalPoseSolver), the paths to them (JointPathChecker, 16 candidates, resolution 0.02) and the shares of 'straight' / 'via' /
       'blocked' among the queries with a free goal pose.
+      --certify: instead, microseconds per naf_chain_path_certify launch and per naf_chain_path_check launch on the same inputs,
+      alternating in the same process, with their ratio and the share of certified candidates; then the README's question with
+      JointPathChecker(certify=True): the shares of 'straight' / 'via' / 'sampled' / 'blocked', the distribution of `refinements`
+      and the seconds all rounds took together.
 
   python benchmarks/chain_env_bench.py demo [--envs 2048] [--launches 20] [--boxes]
       planned joint paths as replay rows, same arm and cell: N = --envs demonstrations (default 2048 here) of T = 400 ticks.
@@ -358,8 +362,10 @@ def paths(a):
     hi = np.array([j.upper if j.limited else np.pi for j in model.joints])
     q_start, q_goal = np.tile(np.float32(init), (N, 1)), rng.uniform(lo, hi, (N, n)).astype(np.float32)
     obstacles = (np.array([0.35, 0.2, 0.45]) + rng.uniform(-0.2, 0.2, (N, 3))).astype(np.float32)
-    checker = JointPathChecker(model, 0.06)
+    checker = JointPathChecker(model, 0.06, certify=bool(a.certify))
     checker.load(q_start, q_goal, obstacles, path_vias(model, q_start, q_goal, C, 0))
+    if a.certify:
+        return _paths_certified(a, checker, model, N, C, S, launches, init, rng, urdf)
     fused = []
     for i in range(launches + 2):
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -423,6 +429,52 @@ def paths(a):
                                                           for k in ("straight", "via", "blocked", "start", "goal")},
                       "median_samples": int(np.median(found.samples)), "largest_sample_step": round(float(found.sample_step.max()), 5),
                       "kernel_registers": regs}))
+
+
+def _paths_certified(a, checker, model, N, C, S, launches, init, rng, urdf):
+    import time
+    import numpy as np
+    import torch
+    from robotic_manipulator_rloa_amd import _lib
+    from robotic_manipulator_rloa_amd.engine import GoalPoseSolver
+    times = {"check": [], "certify": []}
+    for i in range(launches + 2):                              # alternating, so that both see the same clocks
+        for name, launch in (("check", checker.launch), ("certify", checker.launch_certify)):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            launch(N, C, S, 0.0)
+            t1.record()
+            t1.synchronize()
+            if i >= 2:
+                times[name].append(1e3 * t0.elapsed_time(t1))
+    rec, plain = checker.out_cert[:N * C], checker.out[:N * C]
+    gap = float((rec[:, :3] - plain[:, :3]).nan_to_num(posinf=0.0).abs().max())
+    M = 2000
+    targets = np.array([0.45, 0.3, 0.6]) + rng.uniform(-0.25, 0.25, (M, 3))
+    start, obstacle = np.tile(init, (M, 1)), np.tile([0.35, 0.2, 0.45], (M, 1))
+    goal = GoalPoseSolver(model, 0.06).solve(start, targets, obstacle)
+    ok = goal.free
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    found = checker.check(start[ok], goal.joint_positions[ok], obstacle[ok], candidates=C, resolution=0.02)
+    seconds = time.perf_counter() - t
+    usage = json.load(open(_lib.USAGE_PATH)) if os.path.exists(_lib.USAGE_PATH) else {}
+    regs = {name: {q: v.get(q) for q in ("vgprs", "sgprs", "scratch_bytes_per_lane", "lds_bytes", "occupancy")}
+            for name, v in usage.items() if "chain_path_" in name and "ChainCert" in name}
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    print(json.dumps({"arm": os.path.basename(urdf), "queries": N, "candidates": C, "samples": S, "self_pairs": len(model.self_pairs),
+                      "workcell_pairs": len(model.cell_pairs), "boxes": bool(a.boxes),
+                      "us_per_path_check_launch": {"median": round(med["check"], 1), "min": round(float(np.min(times["check"])), 1)},
+                      "us_per_path_certify_launch": {"median": round(med["certify"], 1), "min": round(float(np.min(times["certify"])), 1)},
+                      "certify_over_check": round(med["certify"] / med["check"], 3), "largest_difference_of_the_minima": gap,
+                      "free_candidates_share": round(float((rec[:, 4] == 0).float().mean()), 4),
+                      "certified_candidates_share": round(float((rec[:, 11] == -1).float().mean()), 4),
+                      "targets": M, "free_goal_poses": int(ok.sum()),
+                      "outcome_shares_among_free_goals": {k: round(float(np.mean(found.outcome == k)), 4)
+                                                          for k in ("straight", "via", "sampled", "blocked", "start", "goal")},
+                      "refinements": {str(k): int(v) for k, v in zip(*np.unique(found.refinements, return_counts=True))},
+                      "samples": {str(k): int(v) for k, v in zip(*np.unique(found.samples, return_counts=True))},
+                      "seconds_all_rounds": round(seconds, 3), "kernel_registers": regs}))
 
 
 def demo(a):
@@ -549,6 +601,7 @@ def main():
     ap.add_argument("--autocollision", action="store_true")
     ap.add_argument("--workcell", action="store_true", help="step / rollout: a floor and two spheres in the chain model")
     ap.add_argument("--boxes", action="store_true", help="step / rollout / path, with --workcell: three boxes beside the floor and the spheres")
+    ap.add_argument("--certify", action="store_true", help="path: time naf_chain_path_certify beside naf_chain_path_check, and certify the README's paths")
     ap.add_argument("--trajectory", action="store_true", help="rollout: record the joint values of every frame")
     ap.add_argument("--arm", default="", help="rate: a fixture arm of tests/golden/urdf by name, --joints its joint count")
     ap.add_argument("--target-range", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))

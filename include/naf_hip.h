@@ -919,6 +919,31 @@ int naf_chain_path_check(naf_chain_env_t* h, const float* q_start_dev, const flo
                          const float* obstacles_dev, float obstacle_radius, int N, int C, int S, float margin, float* out,
                          float* poses_out, void* stream);
 
+/* Certified joint paths (an addition within ABI 40): naf_chain_path_check's samples, and with them a statement about the poses
+ * BETWEEN the samples. environment/kinematic.py (reach_table, path_half_steps, certify_joint_path) is the float64 statement.
+ *   reach_dev   : [A][n_seg] (DEVICE), reach[m][s] an upper bound, at every pose inside the limits, on the distance from joint m's
+ *                 axis to any point of capsule s's axis (1 for a prismatic joint m, 0 where joint m does not move segment s).
+ *   half-steps  : all intervals of a leg share one joint displacement (b - a) / n, n = h on leg 1 and h - 1 on leg 2, so over half an
+ *                 interval no point of capsule s travels farther than beta[s] = (sum_m |b_m - a_m| reach[m][s]) / (2 n), and capsule t
+ *                 no farther relative to capsule s (frames f_s <= f_t) than the same sum over m = f_s .. f_t - 1 with reach[m][t].
+ *                 float32: the joint sum by fmaf in joint order from 0, then one division. Sample i < h takes leg 1's beta, i > h leg
+ *                 2's, and the via sample i == h, which ends leg 1's last interval and begins leg 2's first, the larger of the two.
+ *   per sample  : three slacks, each the minimum over the sample's tests of (clearance - beta - guard) with the tested capsule's (or
+ *                 pair's) beta: the obstacle's (obstacle_radius subtracted), the pairs', the workcell's. If all three are >= margin
+ *                 at both ends of an interval, no pose of the interval is closer than margin to anything that is tested.
+ *   guard       : a length >= 0 subtracted from every slack: what float32 may cost a clearance and a beta, so that the verdict is
+ *                 one about the exact geometry (environment/kinematic.py, certificate_guard).
+ *   out         : [N C][NAF_CHAIN_PATH_CERT_FLOATS] (DEVICE) = [0 .. 7] as naf_chain_path_check | [8] [9] [10] the minima over the
+ *                 samples of the three slacks (+inf without pairs / without a workcell) | [11] the index of the first sample one of
+ *                 whose slacks is < margin, -1: none — the candidate is CERTIFIED, which implies [4] == 0.
+ * The launch is naf_chain_path_check's with three tables of n_seg + P floats in LDS, filled before the first pass, and with pairs a
+ * second reduction row per wave. Refusals as naf_chain_path_check, and NAF_ERR_ARG for a null reach_dev or a guard that is negative
+ * or not finite; NAF_CHAIN_ERR_LDS when the tables do not fit beside the handle's rows. */
+#define NAF_CHAIN_PATH_CERT_FLOATS 12
+int naf_chain_path_certify(naf_chain_env_t* h, const float* q_start_dev, const float* q_goal_dev, const float* vias_dev,
+                           const float* obstacles_dev, float obstacle_radius, const float* reach_dev, float guard, int N, int C, int S,
+                           float margin, float* out, float* poses_out, void* stream);
+
 /* Demonstrations (an addition within ABI 40): N planned joint paths turned into the replay rows of the episodes that follow them
  * open loop, one launch. environment/kinematic.py (demonstration_plan, demonstration_rows_host) is the float64 statement.
  *   Demonstration n starts at q_start_dev[n] clamped into the limits (p_0) in the scene targets_dev[n] / obstacles_dev[n] with

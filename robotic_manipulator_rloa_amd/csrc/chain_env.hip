@@ -202,17 +202,22 @@ __device__ static inline float seg_box_dist2(float px, float py, float pz, float
 // Where the SC instantiations keep the capsules' world end points: `ends` is the LDS array already offset by the lane, `lanes`
 // its innermost extent. CLEAR: `clear` collects min over the capsules of (distance to the obstacle centre - capsule radius),
 // and with CELL `cell` the workcell clearance: min over the tested (capsule, geometry) pairs.
+// CERT (the certifying path kernel): `beta` is the lane's table of half-steps, one entry per segment, and `slack` / `cell_slack`
+// collect the same two minima with the segment's entry subtracted from every test.
 struct WalkAux {
     float* ends;
     int lanes;
     float clear;
     float cell;
+    const float* beta;
+    float slack;
+    float cell_slack;
 };
 
 // contact of the capsules of frame f with the obstacle sphere, and the end-effector point when it lives in f. CELL: also their
 // contact with the workcell — ORed into the result, except with CLEAR, where aux.cell < 0 says it and the result stays the
 // obstacle's own (the rollout tells the two apart).
-template <bool SC, bool PROBE, bool SCENE = false, bool CLEAR = PROBE, bool CELL = false, bool BOX = false>
+template <bool SC, bool PROBE, bool SCENE = false, bool CLEAR = PROBE, bool CELL = false, bool BOX = false, bool CERT = false>
 __device__ static inline bool frame_geometry(const float* __restrict__ model, int A, int f, const Frame& F, float ox, float oy,
                                              float oz, float orad, int ee_frame, float* ee, WalkAux& aux, SceneCand* cand = nullptr) {
     const float* begin = model + ch_off_begin(A);
@@ -236,6 +241,7 @@ __device__ static inline bool frame_geometry(const float* __restrict__ model, in
             w[3 * aux.lanes] = bx; w[4 * aux.lanes] = by; w[5 * aux.lanes] = bz;
         }
         if constexpr (CLEAR) aux.clear = fminf(aux.clear, sqrtf(d2) - g[7]);
+        if constexpr (CERT) aux.slack = fminf(aux.slack, sqrtf(d2) - g[7] - aux.beta[s]);
         if constexpr (CELL) {
             const int n_sph = (int)model[10], n_geo = n_sph + (int)model[11];
             const float* geo = model + ch_off_cell(A, (int)model[2], (int)model[9]);
@@ -272,6 +278,8 @@ __device__ static inline bool frame_geometry(const float* __restrict__ model, in
             }
             if constexpr (CLEAR) aux.cell = fminf(aux.cell, least);
             else hit |= least < 0.f;
+            // (the entry is the segment's, the same for every geometry: one subtraction behind the minimum over them)
+            if constexpr (CERT) aux.cell_slack = fminf(aux.cell_slack, least - aux.beta[s]);
         }
         if constexpr (SCENE) {
             // seg_point_dist2 for CH_TRIES centres against ONE segment: its direction and 1 / |u|^2 are computed once, and the
@@ -302,14 +310,15 @@ __device__ static inline bool frame_geometry(const float* __restrict__ model, in
 // the obstacle clearance in aux.clear. CELL: the workcell is tested too (frame_geometry).
 // chain_walk_at is the walk itself: joint m's value is joint(m), asked for once, in joint order, and the obstacle is given;
 // st is read only for the observation (not with PROBE). chain_walk below is the walk of a pose that lies in env_state.
-template <bool SC, bool PROBE, bool SCENE = false, bool CLEAR = PROBE, bool CELL = false, bool BOX = false, class Joint>
+template <bool SC, bool PROBE, bool SCENE = false, bool CLEAR = PROBE, bool CELL = false, bool BOX = false, bool CERT = false,
+          class Joint>
 __device__ static inline bool chain_walk_at(const float* __restrict__ model, int A, int n_seg, const Joint& joint, float ox, float oy,
                                             float oz, float orad, const float* st, float* o, float* ee, WalkAux& aux,
                                             SceneCand* cand = nullptr) {
     const int ee_frame = (int)model[4];
     Frame F = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
     ee[0] = ee[1] = ee[2] = 0.f;
-    bool hit = frame_geometry<SC, PROBE, SCENE, CLEAR, CELL, BOX>(model, A, 0, F, ox, oy, oz, orad, ee_frame, ee, aux, cand);
+    bool hit = frame_geometry<SC, PROBE, SCENE, CLEAR, CELL, BOX, CERT>(model, A, 0, F, ox, oy, oz, orad, ee_frame, ee, aux, cand);
     for (int m = 0; m < A; ++m) {
         const float* j = model + CH_HDR + m * CH_JNT;
         const float q = joint(m);
@@ -356,7 +365,7 @@ __device__ static inline bool chain_walk_at(const float* __restrict__ model, int
             F.r21 = G.r20 * m01 + G.r21 * m11 + G.r22 * m21;
             F.r22 = G.r20 * m02 + G.r21 * m12 + G.r22 * m22;
         }
-        hit |= frame_geometry<SC, PROBE, SCENE, CLEAR, CELL, BOX>(model, A, m + 1, F, ox, oy, oz, orad, ee_frame, ee, aux, cand);
+        hit |= frame_geometry<SC, PROBE, SCENE, CLEAR, CELL, BOX, CERT>(model, A, m + 1, F, ox, oy, oz, orad, ee_frame, ee, aux, cand);
     }
     if constexpr (!PROBE) {
         const float* slots = model + ch_off_slot(A, n_seg);
@@ -376,15 +385,19 @@ __device__ static inline bool chain_walk(const float* __restrict__ model, int A,
 
 // The pair phase of an SC workgroup, entered by EVERY thread after the walking wave has stored the end points: returns, to
 // every thread, min over the blob's pairs of distance(segment s, segment t) - radius s - radius t for the env of its lane.
+// CERT: `beta` is the lane's table of half-steps, one entry per pair; *slack receives the minimum with the pair's entry subtracted
+// from every clearance, through a second row per wave behind the first.
+template <bool CERT = false>
 __device__ static inline float self_clearance_phase(const float* __restrict__ model, int A, int n_seg, int n_pairs, float* lds,
-                                                    int lanes, int lane, bool active) {
+                                                    int lanes, int lane, bool active, const float* beta = nullptr,
+                                                    float* slack = nullptr) {
     const int waves = blockDim.x >> 6;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const float* segs = model + ch_off_seg(A);
     const float* pairs = model + ch_off_pair(A, n_seg);
     float* red = lds + (size_t)n_seg * 6 * lanes;
     __syncthreads();
-    float best = INFINITY;
+    float best = INFINITY, low = INFINITY;
     if (active) {
         const float* ends = lds + lane;
         for (int p = wave; p < n_pairs; p += waves) {
@@ -394,12 +407,18 @@ __device__ static inline float self_clearance_phase(const float* __restrict__ mo
             const float d2 = seg_seg_dist2(u[0], u[lanes], u[2 * lanes], u[3 * lanes], u[4 * lanes], u[5 * lanes], v[0], v[lanes],
                                            v[2 * lanes], v[3 * lanes], v[4 * lanes], v[5 * lanes]);
             best = fminf(best, sqrtf(d2) - (segs[s * CH_SEG + 7] + segs[t * CH_SEG + 7]));
+            if constexpr (CERT) low = fminf(low, sqrtf(d2) - (segs[s * CH_SEG + 7] + segs[t * CH_SEG + 7]) - beta[p]);
         }
         red[wave * lanes + lane] = best;
+        if constexpr (CERT) red[(waves + wave) * lanes + lane] = low;
     }
     __syncthreads();
     if (active)
-        for (int w = 0; w < waves; ++w) best = fminf(best, red[w * lanes + lane]);
+        for (int w = 0; w < waves; ++w) {
+            best = fminf(best, red[w * lanes + lane]);
+            if constexpr (CERT) low = fminf(low, red[(waves + w) * lanes + lane]);
+        }
+    if constexpr (CERT) *slack = low;
     return best;
 }
 
@@ -1379,6 +1398,29 @@ extern "C" int naf_chain_ik_select(naf_chain_env_t* h, const float* q_out, const
 // SC is the probe's shape: wave 0 walks `lanes` samples and stages their capsules' end points as [segment][6][lane], every wave
 // joins the pair phase of every pass (its barriers), and only wave 0's lanes keep the running minima, the blocked count and the
 // first blocked index. Behind the last pass wave 0 reduces them by a butterfly of shuffles and lane 0 writes the record.
+//
+// A leading ChainCert in the pack (CERT below) is naf_chain_path_certify's kernel: the record has NAF_CHAIN_PATH_CERT_FLOATS floats.
+// Every interval of a leg has the same joint displacement, so how far a point of capsule s can travel over half an interval is one
+// number per leg: beta[s] = sum_m |b_m - a_m| reach[m][s] / (2 n), and for a pair (s, t) the same sum over the joints between the
+// two frames with reach[m][t]. Before the first pass the workgroup's threads fill three tables of n_seg + P such entries in LDS,
+// behind the pair phase's rows — leg 1, leg 2, and their entry-wise maximum for the via sample, which ends one leg's last interval
+// and begins the other's first — an entry per thread, the joint sum in joint order by fmaf. A lane picks its table by i < h,
+// i > h or i == h; the walk and the pair phase subtract the entry from every clearance they form and keep those minima beside
+// the plain ones. No per-lane array, nothing atomic; the kernels without ChainCert keep their arguments and their code.
+struct ChainCert {
+    const float* reach;      // [A][n_seg] (DEVICE)
+    float guard;
+};
+template <class... Rest>
+__device__ static inline const ChainCert& path_cert(const ChainCert& c, const Rest&...) { return c; }
+// dynamic LDS of a certifying launch: the SC rows with a second reduction row per wave (none without pairs), then the tables
+__host__ __device__ static inline size_t ch_cert_table_floats(int n_seg, int n_pairs, int lanes, int waves) {
+    return n_pairs > 0 ? ((size_t)n_seg * 6 + 2 * waves) * lanes : 0;
+}
+__host__ __device__ static inline size_t ch_cert_lds_bytes(int n_seg, int n_pairs, int lanes, int waves) {
+    return (ch_cert_table_floats(n_seg, n_pairs, lanes, waves) + 3 * (size_t)(n_seg + n_pairs)) * sizeof(float);
+}
+
 template <bool SC, class... Cell>
 __global__ void __launch_bounds__(SC ? 64 * CH_MAX_WAVES : 64)
 chain_path_check_kernel(const float* __restrict__ model, const float* __restrict__ q_start, const float* __restrict__ q_goal,
@@ -1386,6 +1428,7 @@ chain_path_check_kernel(const float* __restrict__ model, const float* __restrict
                         int n_pairs, int lanes, float margin, float* __restrict__ out, float* __restrict__ poses_out, const Cell... cell) {
     constexpr bool CELL = (std::is_same_v<Cell, ChainCell> || ... || false);
     constexpr bool BOX = (std::is_same_v<Cell, ChainBox> || ... || false);
+    constexpr bool CERT = (std::is_same_v<Cell, ChainCert> || ... || false);
     extern __shared__ __attribute__((aligned(16))) float ch_lds[];
     const int64_t cand = blockIdx.x;
     const int64_t n = cand / C;
@@ -1399,15 +1442,46 @@ chain_path_check_kernel(const float* __restrict__ model, const float* __restrict
     const int h = S >> 1;
     float min_clear = INFINITY, min_self = INFINITY, min_cell = INFINITY;
     int first = INT_MAX, count = 0, goal_blocked = 0;
+    float low_clear = INFINITY, low_self = INFINITY, low_cell = INFINITY, guard = 0.f;
+    int first_low = INT_MAX;
+    const int n_tab = n_seg + n_pairs;
+    const float* tab = nullptr;
+    if constexpr (CERT) {
+        const ChainCert& cert = path_cert(cell...);
+        const float* segs = model + ch_off_seg(A);
+        const float* pairs = model + ch_off_pair(A, n_seg);
+        float* t = ch_lds + ch_cert_table_floats(n_seg, n_pairs, lanes, blockDim.x >> 6);
+        for (int e = threadIdx.x; e < n_tab; e += blockDim.x) {
+            // entry e < n_seg: segment e against the world, joints 0 .. frame - 1; else pair (s, t): t against s, joints frame s ..
+            const int s = e < n_seg ? e : (int)pairs[2 * (e - n_seg) + 1];
+            const int m0 = e < n_seg ? 0 : (int)segs[(int)pairs[2 * (e - n_seg)] * CH_SEG];
+            const int m1 = (int)segs[s * CH_SEG];
+            float b1 = 0.f, b2 = 0.f;
+            for (int m = m0; m < m1; ++m) {
+                const float v = via[m], r = cert.reach[m * n_seg + s];
+                b1 = fmaf(fabsf(v - start[m]), r, b1);
+                b2 = fmaf(fabsf(goal[m] - v), r, b2);
+            }
+            b1 = b1 / (float)(2 * h);
+            b2 = b2 / (float)(2 * (h - 1));
+            t[e] = b1;
+            t[n_tab + e] = b2;
+            t[2 * n_tab + e] = fmaxf(b1, b2);
+        }
+        __syncthreads();
+        tab = t;
+        guard = cert.guard;
+    }
     for (int base = 0; base < S; base += lanes) {      // (uniform: every thread takes every pass)
         const int i = base + lane;
         const bool second = i >= h;
         const float f = second ? (float)(i - h) / (float)(h - 1) : (float)i / (float)h;
         float ee[3];
-        WalkAux aux = {SC ? ch_lds + lane : nullptr, lanes, INFINITY, INFINITY};
+        WalkAux aux = {SC ? ch_lds + lane : nullptr, lanes, INFINITY, INFINITY,
+                       CERT ? tab + (i < h ? 0 : (i == h ? 2 : 1)) * n_tab : nullptr, INFINITY, INFINITY};
         if (walker) {
             float* rec = poses_out ? poses_out + (cand * S + i) * A : nullptr;
-            chain_walk_at<SC, true, false, true, CELL, BOX>(
+            chain_walk_at<SC, true, false, true, CELL, BOX, CERT>(
                 model, A, n_seg,
                 [=](int m) {
                     const float v = via[m];
@@ -1418,8 +1492,10 @@ chain_path_check_kernel(const float* __restrict__ model, const float* __restrict
                 },
                 ox, oy, oz, orad, nullptr, nullptr, ee, aux);
         }
-        float self_clear = INFINITY;
-        if constexpr (SC) self_clear = self_clearance_phase(model, A, n_seg, n_pairs, ch_lds, lanes, lane, active);
+        float self_clear = INFINITY, self_slack = INFINITY;
+        if constexpr (SC)
+            self_clear = self_clearance_phase<CERT>(model, A, n_seg, n_pairs, ch_lds, lanes, lane, active,
+                                                    CERT ? aux.beta + n_seg : nullptr, &self_slack);
         if (walker) {
             const float clear = aux.clear - orad;
             const bool blocked = clear < margin || self_clear < margin || (CELL && aux.cell < margin);
@@ -1429,6 +1505,13 @@ chain_path_check_kernel(const float* __restrict__ model, const float* __restrict
             first = blocked && i < first ? i : first;
             count += blocked ? 1 : 0;
             goal_blocked |= blocked && i == S - 1 ? 1 : 0;
+            if constexpr (CERT) {
+                const float s0 = aux.slack - orad - guard, s1 = self_slack - guard, s2 = aux.cell_slack - guard;
+                low_clear = fminf(low_clear, s0);
+                low_self = fminf(low_self, s1);
+                if constexpr (CELL) low_cell = fminf(low_cell, s2);
+                first_low = (s0 < margin || s1 < margin || (CELL && s2 < margin)) && i < first_low ? i : first_low;
+            }
         }
     }
     if (threadIdx.x >= 64) return;      // (behind the last barrier; wave 0 is whole: the lanes that walked nothing hold the identities)
@@ -1439,6 +1522,12 @@ chain_path_check_kernel(const float* __restrict__ model, const float* __restrict
         first = min(first, __shfl_xor(first, off));
         count += __shfl_xor(count, off);
         goal_blocked |= __shfl_xor(goal_blocked, off);
+        if constexpr (CERT) {
+            low_clear = fminf(low_clear, __shfl_xor(low_clear, off));
+            low_self = fminf(low_self, __shfl_xor(low_self, off));
+            low_cell = fminf(low_cell, __shfl_xor(low_cell, off));
+            first_low = min(first_low, __shfl_xor(first_low, off));
+        }
     }
     if (threadIdx.x != 0) return;
     float l1 = 0.f, l2 = 0.f;
@@ -1446,7 +1535,7 @@ chain_path_check_kernel(const float* __restrict__ model, const float* __restrict
         l1 = fmaxf(l1, fabsf(via[m] - start[m]));
         l2 = fmaxf(l2, fabsf(goal[m] - via[m]));
     }
-    float* o = out + cand * NAF_CHAIN_PATH_FLOATS;
+    float* o = out + cand * (CERT ? NAF_CHAIN_PATH_CERT_FLOATS : NAF_CHAIN_PATH_FLOATS);
     o[0] = min_clear;
     o[1] = min_self;
     o[2] = min_cell;
@@ -1455,6 +1544,12 @@ chain_path_check_kernel(const float* __restrict__ model, const float* __restrict
     o[5] = l1 + l2;
     o[6] = fmaxf(l1 / (float)h, l2 / (float)(h - 1));
     o[7] = (float)goal_blocked;
+    if constexpr (CERT) {
+        o[8] = low_clear;
+        o[9] = low_self;
+        o[10] = low_cell;
+        o[11] = first_low == INT_MAX ? -1.f : (float)first_low;
+    }
 }
 
 // the SC path kernels' dynamic LDS is the probe's and may exceed the 64 KB a kernel gets unasked: raised once per device
@@ -1466,7 +1561,10 @@ static int ch_path_raise_lds_limit() {
     if (dev < 0 || dev >= 64) return NAF_ERR_ARG;
     if (raised_dev[dev]) return NAF_OK;
     for (const void* k : {(const void*)chain_path_check_kernel<true>, (const void*)chain_path_check_kernel<true, ChainCell>,
-                          (const void*)chain_path_check_kernel<true, ChainCell, ChainBox>}) {
+                          (const void*)chain_path_check_kernel<true, ChainCell, ChainBox>,
+                          (const void*)chain_path_check_kernel<true, ChainCert>,
+                          (const void*)chain_path_check_kernel<true, ChainCert, ChainCell>,
+                          (const void*)chain_path_check_kernel<true, ChainCert, ChainCell, ChainBox>}) {
         e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, CH_MAX_DYN_LDS);
         if (e != hipSuccess) return (int)e;
     }
@@ -1506,6 +1604,49 @@ extern "C" int naf_chain_path_check(naf_chain_env_t* h, const float* q_start_dev
                        ChainCell{});
     else
         ch_path_launch(h, q_start_dev, q_goal_dev, vias_dev, obstacles_dev, obstacle_radius, N, C, S, margin, out, poses_out, stream);
+    NAF_CHECK_LAUNCH();
+    return NAF_OK;
+}
+
+template <class... Cell>
+static void ch_cert_launch(naf_chain_env_t* h, const float* q_start, const float* q_goal, const float* vias, const float* obstacles,
+                           float orad, int N, int C, int S, float margin, float* out, float* poses_out, void* stream,
+                           const ChainCert cert, const Cell... cell) {
+    const unsigned grid = (unsigned)((int64_t)N * C);
+    const size_t lds = ch_cert_lds_bytes(h->n_seg, h->n_pairs, h->lanes, h->waves);
+    if (h->n_pairs > 0)
+        chain_path_check_kernel<true, ChainCert, Cell...><<<grid, 64 * h->waves, lds, (hipStream_t)stream>>>(
+            h->model_dev, q_start, q_goal, vias, obstacles, orad, C, S, h->A, h->n_seg, h->n_pairs, h->lanes, margin, out, poses_out,
+            cert, cell...);
+    else
+        chain_path_check_kernel<false, ChainCert, Cell...><<<grid, 64, lds, (hipStream_t)stream>>>(
+            h->model_dev, q_start, q_goal, vias, obstacles, orad, C, S, h->A, h->n_seg, 0, 64, margin, out, poses_out, cert, cell...);
+}
+
+extern "C" int naf_chain_path_certify(naf_chain_env_t* h, const float* q_start_dev, const float* q_goal_dev, const float* vias_dev,
+                                      const float* obstacles_dev, float obstacle_radius, const float* reach_dev, float guard, int N,
+                                      int C, int S, float margin, float* out, float* poses_out, void* stream) {
+    if (!h || !q_start_dev || !q_goal_dev || !vias_dev || !obstacles_dev || !reach_dev || !out) return NAF_ERR_ARG;
+    if (N < 1 || C < 1 || C > 64 || S < 64 || S > 2048 || S % 64 != 0 || (int64_t)N * C > (int64_t)1 << 30) return NAF_ERR_ARG;
+    if (!std::isfinite(margin) || !std::isfinite(obstacle_radius) || obstacle_radius < 0.f) return NAF_ERR_ARG;
+    if (!std::isfinite(guard) || guard < 0.f) return NAF_ERR_ARG;
+    // the tables and the second reduction row on top of the handle's rows: an arm they do not fit with is refused, not shrunk
+    if (ch_cert_lds_bytes(h->n_seg, h->n_pairs, h->lanes, h->waves) > (h->n_pairs > 0 ? CH_MAX_DYN_LDS : 64 * 1024))
+        return NAF_CHAIN_ERR_LDS;
+    if (h->n_pairs > 0) {
+        const int rc = ch_path_raise_lds_limit();
+        if (rc != NAF_OK) return rc;
+    }
+    const ChainCert cert = {reach_dev, guard};
+    if (h->n_box > 0)
+        ch_cert_launch(h, q_start_dev, q_goal_dev, vias_dev, obstacles_dev, obstacle_radius, N, C, S, margin, out, poses_out, stream,
+                       cert, ChainCell{}, ChainBox{});
+    else if (h->n_cell > 0)
+        ch_cert_launch(h, q_start_dev, q_goal_dev, vias_dev, obstacles_dev, obstacle_radius, N, C, S, margin, out, poses_out, stream,
+                       cert, ChainCell{});
+    else
+        ch_cert_launch(h, q_start_dev, q_goal_dev, vias_dev, obstacles_dev, obstacle_radius, N, C, S, margin, out, poses_out, stream,
+                       cert);
     NAF_CHECK_LAUNCH();
     return NAF_OK;
 }

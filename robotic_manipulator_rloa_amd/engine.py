@@ -14,6 +14,7 @@
                    the pinned clearances at the solved poses, the selection per query (GoalPoses). No agent, no graph.
   JointPathChecker : sampled collision checks of start -> via -> goal joint paths on a chain model: ONE launch over queries x
                    candidate vias x samples, eight floats per candidate back, the choice per query on the host (JointPaths).
+                   certify=True: naf_chain_path_certify's twelve floats and the refinement rounds over the open queries.
 
 Graph capture goes through torch.cuda.CUDAGraph (= hipGraph on ROCm): the ctypes kernel launches use the
 stream torch reports as current, which inside the capture context is the capturing stream.
@@ -30,8 +31,9 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
-from .environment.kinematic import (PATH_CHUNK, PATH_FLOATS, GoalPoses, JointPaths, gather_goal_poses, gather_joint_paths, ik_seeds,
-                                    path_chunks, path_leg_lengths, path_vias)
+from .environment.kinematic import (PATH_CERT_FLOATS, PATH_CHUNK, PATH_FLOATS, GoalPoses, JointPaths, certificate_guard,
+                                    certify_rounds, gather_certified_paths, gather_goal_poses, gather_joint_paths, ik_seeds,
+                                    path_chunks, path_leg_lengths, path_vias, reach_table)
 from .learner import ActPath, Learner
 from .presets import ROBOT_PRESETS, device_env_preset
 from .utils.replay_buffer import ReplayBuffer
@@ -1267,9 +1269,13 @@ class JointPathChecker:
     eight floats per candidate come back; the choice among a query's candidates is environment.kinematic.select_joint_path on the
     host. Owns the handle and the buffers; needs no agent. A chunk holds at most `chunk` candidate-samples (queries x candidates x
     S, whole queries) and its S is path_samples of its own legs (path_chunks); a candidate's record does not depend on where in a
-    launch it lies. The check is SAMPLED: see JointPaths."""
+    launch it lies. The check is SAMPLED: see JointPaths. certify=True: the launches are naf_chain_path_certify's, twelve floats per
+    candidate, with the model's reach table uploaded once; check() then runs the refinement rounds over the open queries
+    (environment.kinematic.certify_rounds) and fills JointPaths' last three fields. The certifying launch keeps the handle's lanes
+    and adds a reduction row and three small tables to its LDS: an arm with pairs whose rows only just fit a workgroup is refused
+    (NAF_CHAIN_ERR_LDS) where the sampled check runs; joint_paths_host(certify=True) answers it."""
 
-    def __init__(self, chain, obstacle_radius: float = 0.06, chunk: Optional[int] = None, device=None):
+    def __init__(self, chain, obstacle_radius: float = 0.06, chunk: Optional[int] = None, device=None, certify: bool = False):
         import ctypes
         _lib.require_gpu()
         self.lib, self.chain, self.A = _lib.load(), chain, chain.A
@@ -1285,6 +1291,11 @@ class JointPathChecker:
         f32 = dict(dtype=torch.float32, device=self.dev)
         self.q_start, self.q_goal, self.obstacles = torch.zeros(K, A, **f32), torch.zeros(K, A, **f32), torch.zeros(K, 3, **f32)
         self.vias, self.out = torch.zeros(K, A, **f32), torch.zeros(K, PATH_FLOATS, **f32)
+        self.certify = bool(certify)
+        if self.certify:
+            self.reach = torch.from_numpy(reach_table(chain)).to(self.dev).contiguous()
+            self.guard = certificate_guard(chain)
+            self.out_cert = torch.zeros(K, PATH_CERT_FLOATS, **f32)
 
     def __del__(self):
         if getattr(self, "_chain_env", None) is not None:
@@ -1296,6 +1307,12 @@ class JointPathChecker:
         check(self.lib.naf_chain_path_check(self._chain_env, ptr(self.q_start), ptr(self.q_goal), ptr(self.vias), ptr(self.obstacles),
                                             self.obstacle_radius, n, C, S, margin, ptr(self.out), None, stream_ptr()),
               "chain_path_check")
+
+    def launch_certify(self, n: int, C: int, S: int, margin: float) -> None:
+        """the certifying launch of one chunk already in the buffers, into out_cert, on the current stream"""
+        check(self.lib.naf_chain_path_certify(self._chain_env, ptr(self.q_start), ptr(self.q_goal), ptr(self.vias), ptr(self.obstacles),
+                                              self.obstacle_radius, ptr(self.reach), self.guard, n, C, S, margin, ptr(self.out_cert),
+                                              None, stream_ptr()), "chain_path_certify")
 
     def load(self, q_start, q_goal, obstacles, vias) -> None:
         """a chunk's queries into the buffers: q_start[n][A], q_goal[n][A], obstacles[n][3], vias[n][C][A] (float32)"""
@@ -1316,6 +1333,17 @@ class JointPathChecker:
             raise ValueError(f"JointPathChecker: a chunk of {self.chunk} candidate-samples does not hold one query's {C} candidates")
         vias = path_vias(self.chain, q_start, q_goal, C, seed)
         margin = float(np.float32(margin))
+        if self.certify:
+            def run(idx, S):
+                if len(idx) * C * S > self.chunk:
+                    raise ValueError(f"JointPathChecker: one query's {C} candidates at {S} samples exceed the chunk of {self.chunk}")
+                self.load(q_start[idx], q_goal[idx], obstacles[idx], vias[idx])
+                self.launch_certify(len(idx), C, S, margin)
+                return self.out_cert[:len(idx) * C].cpu().numpy().reshape(len(idx), C, PATH_CERT_FLOATS)
+
+            records, samples, refinements = certify_rounds(run, path_leg_lengths(vias, q_start, q_goal), C, resolution, self.chunk,
+                                                           np.float32)
+            return gather_certified_paths(records, vias, q_start, q_goal, samples, refinements)
         records, samples = np.empty((N, C, PATH_FLOATS), np.float32), np.empty(N, np.int64)
         for first, n, S in path_chunks(path_leg_lengths(vias, q_start, q_goal), C, resolution, self.chunk):
             if n * C * S > self.chunk:

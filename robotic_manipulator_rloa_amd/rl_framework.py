@@ -260,7 +260,8 @@ class ManipulatorFramework:
         return summary
 
     def reach_targets(self, targets, obstacles=None, initial_joint_positions=None, frames: int = 400, noise_scale: float = 0.0,
-                      n_envs: Optional[int] = None, trajectories: bool = True, goal_poses: bool = False, joint_paths: bool = False):
+                      n_envs: Optional[int] = None, trajectories: bool = True, goal_poses: bool = False, joint_paths: bool = False,
+                      certify: bool = False):
         """Roll the trained policy out to GIVEN targets (kinematic environment only; on the device, thousands at once): query i
         starts at initial_joint_positions[i], with target targets[i] and obstacle obstacles[i], and runs until it reaches the
         target, touches the obstacle, itself or the workcell, or has taken `frames` steps. A query whose start pose is already in contact or at
@@ -282,7 +283,9 @@ class ManipulatorFramework:
         joint_paths=True (implies goal_poses): the result's `path` is plan_joint_paths() from the start poses to goal's poses, with
         its defaults (queries without a reachable goal pose: outcome 'goal', NaN numbers), and `planned_ratio` [N] the same joint
         path length over path.length — a path that can be driven at its samples, where the straight line may not be — NaN where
-        the query did not reach or no free path was found. Both are None otherwise, and nothing else changes."""
+        the query did not reach or no free path was found. Both are None otherwise, and nothing else changes.
+        certify=True (with joint_paths): the paths are plan_joint_paths(certify=True)'s, and `path.certified` says which of them
+        hold between their samples too."""
         if not self.env:
             raise EnvironmentNotInitialized
         if not self.naf_agent:
@@ -302,6 +305,8 @@ class ManipulatorFramework:
         except ValueError as err:
             raise InvalidEnvironmentParameter(str(err)) from None
         goal_poses = bool(goal_poses or joint_paths)
+        if not isinstance(certify, (bool, np.bool_)) or (certify and not joint_paths):
+            raise InvalidEnvironmentParameter('reach_targets(certify=True) certifies the joint paths: it is a bool and needs joint_paths=True')
         if goal_poses and not trajectories:
             raise InvalidEnvironmentParameter('reach_targets(goal_poses=True) measures the joint path: it needs trajectories=True')
         result = self.naf_agent.rollout_vectorized(env.model, targets, obstacles, q0, frames=frames, noise_scale=float(noise_scale),
@@ -315,7 +320,7 @@ class ManipulatorFramework:
                 ratio = length / np.asarray(result.goal.joint_distance, np.float64)
             result.path_ratio = np.where((np.asarray(result.outcome) == 'reached') & result.goal.free, ratio, np.nan)
         if joint_paths:
-            result.path = self._paths_to_goals(result.goal, q0, obstacles, {})
+            result.path = self._paths_to_goals(result.goal, q0, obstacles, {'certify': True} if certify else {})
             with np.errstate(divide='ignore', invalid='ignore'):
                 ratio = length / np.asarray(result.path.length, np.float64)
             result.planned_ratio = np.where((np.asarray(result.outcome) == 'reached') & (result.path.candidate >= 0), ratio, np.nan)
@@ -332,25 +337,27 @@ class ManipulatorFramework:
         kind = np.float32 if found is None else found.length.dtype
         nan = lambda *shape: np.full((N,) + shape, np.nan, kind)      # noqa: E731
         parts = [np.full(N, 'goal', '<U8'), np.full(N, -1, np.int64), nan(A), nan(), nan(), nan(), nan(), nan(), np.full(N, -1, np.int64),
-                 nan(), np.zeros(N, np.int64), np.asarray(q0, kind), nan(A)]
+                 nan(), np.zeros(N, np.int64), np.asarray(q0, kind), nan(A), np.zeros(N, bool), nan(), np.zeros(N, np.int64)]
         for dst, src in zip(parts, found or ()):
             dst[ok] = src
         return JointPaths(*parts)
 
-    def _plan_checked(self, q0, q_goal, obstacles, candidates=16, resolution=0.02, clearance_margin=0.0, seed=0, on_device=None):
+    def _plan_checked(self, q0, q_goal, obstacles, candidates=16, resolution=0.02, clearance_margin=0.0, seed=0, on_device=None,
+                      certify=False):
         env = self.env
         if on_device is None:
             on_device = torch.cuda.is_available()
         kw = dict(candidates=int(candidates), resolution=float(resolution), margin=float(clearance_margin), seed=int(seed))
         if not on_device:
-            out = joint_paths_host(env, q0, q_goal, obstacles, **kw)
+            out = joint_paths_host(env, q0, q_goal, obstacles, **kw, **({'certify': True} if certify else {}))
         else:
             from .engine import JointPathChecker
-            key = (env.model.digest(), float(env.obstacle_radius))
-            if getattr(self, '_path_checker', None) is None or self._path_checker[0] != key:
-                self._path_checker = None
-                self._path_checker = (key, JointPathChecker(env.model, env.obstacle_radius))
-            out = self._path_checker[1].check(q0, q_goal, obstacles, **kw)
+            # one cached checker for each kind: plain and certified calls may alternate without rebuilding handle and buffers
+            slot, key = ('_cert_checker' if certify else '_path_checker'), (env.model.digest(), float(env.obstacle_radius))
+            if getattr(self, slot, None) is None or getattr(self, slot)[0] != key:
+                setattr(self, slot, None)
+                setattr(self, slot, (key, JointPathChecker(env.model, env.obstacle_radius, **({'certify': True} if certify else {}))))
+            out = getattr(self, slot)[1].check(q0, q_goal, obstacles, **kw)
         with np.errstate(invalid='ignore'):
             coarse = np.asarray(out.sample_step, np.float64) > resolution
         if coarse.any() and not getattr(self, '_path_step_warned', False):
@@ -361,20 +368,32 @@ class ManipulatorFramework:
 
     def plan_joint_paths(self, targets=None, obstacles=None, initial_joint_positions=None, goal_joint_positions=None,
                          candidates: int = 16, resolution: float = 0.02, clearance_margin: float = 0.0, seed: int = 0,
-                         on_device: Optional[bool] = None):
+                         on_device: Optional[bool] = None, certify: bool = False):
         """Collision-checked joint paths from start poses to goal poses (kinematic environment only; needs no agent): per query
         `candidates` joint-space polylines start -> via -> goal — candidate 0 through the midpoint, the straight line, the others
         through vias drawn around it from `seed` (environment/kinematic.py: path_vias) — are SAMPLED at poses at most `resolution`
         apart in the joints' max-norm (a multiple of 64 poses per path, at most 2048; beyond that the step is coarser and a warning
         says so once), each sample tested against the obstacle, the arm itself and the workcell under the rule of reach_targets()
         with clearance_margin to spare, and the shortest candidate with no blocked sample is returned. A free verdict holds AT THE
-        SAMPLES; sample_step says how far apart they are. There is no continuous-collision certificate.
+        SAMPLES; sample_step says how far apart they are. Without `certify` there is no continuous-collision certificate.
           targets              : [N][3] or [3]: the goal poses are solve_goal_poses(targets, ...) with its defaults and `seed`;
                                  queries without a reachable pose get outcome 'goal' and NaN numbers
           goal_joint_positions : [N][A] or [A]: the goal poses themselves. Exactly one of the two is given.
           obstacles, initial_joint_positions : as reach_targets() takes them
           candidates           : 1 .. 64
           on_device            : None: the device when there is one; False: the float64 host twin under the same rule (slow)
+          certify              : True: a candidate counts only when every test at every sample keeps clearance_margin plus how
+                                 far the tested capsule can travel over half a sample interval (environment/kinematic.py:
+                                 certify_joint_path) — then NO pose of the polyline, between the samples included, is closer than
+                                 clearance_margin to anything. The shortest certified candidate wins; queries without one, or with
+                                 a shorter candidate that is free at its samples only, are run again at twice the samples, up to
+                                 2048. 'straight' and 'via' then name certified paths, the new outcome 'sampled' a path free at its
+                                 samples only, and the result's certified, certified_slack and refinements are filled. The
+                                 certificate is about the capsule model and the polyline; a controller's tracking error is not in it.
+                                 On the device the certifying launch needs a little more LDS than the sampled one (a second
+                                 reduction row and the tables of half-steps): an arm with pairs whose capsules only just fit a
+                                 workgroup is refused there (NAF_CHAIN_ERR_LDS) though the sampled check serves it;
+                                 on_device=False answers such an arm.
         Returns environment.kinematic.JointPaths, arrays over the queries: outcome ('straight' | 'via' | 'blocked' | 'start' |
         'goal': the start / goal pose itself is blocked), candidate, via, length, straight_length, min_clearance,
         min_self_clearance, min_cell_clearance, straight_first_blocked, sample_step, samples; waypoints(n) resamples the paths."""
@@ -394,8 +413,12 @@ class ManipulatorFramework:
             raise InvalidEnvironmentParameter(f'clearance_margin is a finite length: got {clearance_margin!r}')
         if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or seed < 0:
             raise InvalidEnvironmentParameter(f'seed is a non-negative integer: got {seed!r}')
+        if not isinstance(certify, (bool, np.bool_)):
+            raise InvalidEnvironmentParameter(f'certify is a bool: got {certify!r}')
         nominal = env.obstacle_centre if env.scene_ranges_on else env.obstacle_pos
         kw = dict(candidates=candidates, resolution=resolution, clearance_margin=clearance_margin, seed=seed, on_device=on_device)
+        if certify:
+            kw['certify'] = True
         try:
             if targets is not None:
                 q0, targets, obstacles, _ = reach_queries(env.model, targets, obstacles, initial_joint_positions, 1,
