@@ -13,9 +13,9 @@ from test_oracle_golden import assert_adam_stepped_close
 pytestmark = pytest.mark.gpu
 
 
-def make_learner(S, A, B, sd_main, sd_target, H=256, **kw):
+def make_learner(S, A, B, sd_main, sd_target, H=256, lr=1e-3, tau=1e-3, gamma=0.99, **kw):
     from robotic_manipulator_rloa_amd.learner import Learner
-    L = Learner(S, A, H, B, 1e-3, 1e-3, 0.99, torch.device("cuda"), **kw)
+    L = Learner(S, A, H, B, lr, tau, gamma, torch.device("cuda"), **kw)
     L.load_params(0, sd_main)
     L.load_params(1, sd_target)
     return L
@@ -576,6 +576,15 @@ def test_chunk_graph_equals_eager_and_sampler_advances():
 @pytest.mark.parametrize("S,A,B,U", [(21, 6, 256, 7), (21, 6, 512, 3), (21, 6, 1024, 4), (23, 7, 2048, 3), (21, 6, 64, 5), (21, 6, 320, 3),
                                      (21, 6, 100, 4), (21, 6, 1000, 3), (21, 6, 2500, 2)])
 def test_deferred_optimizer_step_is_the_same_bits(S, A, B, U, monkeypatch):
+    _deferred_step_is_the_same_bits(S, A, B, U, monkeypatch)
+
+
+@pytest.mark.parametrize("S,A,B,U", [(21, 6, 256, 7), (21, 6, 1024, 4)])
+def test_deferred_optimizer_step_is_the_same_bits_at_other_values(S, A, B, U, monkeypatch):
+    _deferred_step_is_the_same_bits(S, A, B, U, monkeypatch, lr=3e-3, tau=0.05, gamma=0.9)
+
+
+def _deferred_step_is_the_same_bits(S, A, B, U, monkeypatch, **hyper):
     """The optimizer step of update k carried by the first two launches of update k + 1 (csrc/adam_body.h; TrainChunk) against
     the step as a launch of its own: parameters of both nets, Adam moments, BatchNorm buffers, step count and every loss
     bit-identical after several chunks — eagerly and as replayed graphs (naf_algorithm.py:209-213 semantics unchanged)."""
@@ -589,7 +598,7 @@ def test_deferred_optimizer_step_is_the_same_bits(S, A, B, U, monkeypatch):
     res = {}
     for mode, use_graph in (("0", False), ("1", False), ("1", True)):
         monkeypatch.setenv("NAF_DEFER_ADAM", mode)
-        L = make_learner(S, A, B, sd, sd)
+        L = make_learner(S, A, B, sd, sd, **hyper)
         assert L.defer_ok == (mode == "1")
         buf = ReplayBuffer(n_rows, B, "cuda", 0, state_size=S, action_size=A)
         buf.add_rows_device(torch.from_numpy(O.pack_rows(st, ac, rw, ns, dn, 64)).cuda(), n_rows)
