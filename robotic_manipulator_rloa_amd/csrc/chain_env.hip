@@ -881,34 +881,71 @@ extern "C" int naf_chain_env_model_check(const float* m, int n_floats) {
     return NAF_OK;
 }
 
-// the SC kernels' dynamic LDS may exceed the 64 KB a kernel gets unasked: raised once per device
-static int ch_raise_lds_limit() {
+// ---- how a handle's model is launched --------------------------------------------------------------------------------------------
+// Three things, each stated here once; the entry points below are their argument checks and one launch expression through them.
+// ch_with_cell: the pack a model's kernels take behind their fixed arguments. ch_with_pack: std::true_type in front of it for a
+// model with collision pairs (the kernels' SC). A launch with more in its pack puts it around these: ChainRanges in front and
+// ChainTag behind in the step, ChainCert in front in the certifying launch.
+template <class F>
+static int ch_with_cell(const naf_chain_env* h, F&& f) {
+    if (h->n_box > 0) return f(ChainCell{}, ChainBox{});
+    if (h->n_cell > 0) return f(ChainCell{});
+    return f();
+}
+template <class F>
+static int ch_with_sc(const naf_chain_env* h, F&& f) {
+    return h->n_pairs > 0 ? f(std::true_type{}) : f(std::false_type{});
+}
+template <class F>
+static int ch_with_pack(const naf_chain_env* h, F&& f) {
+    return ch_with_sc(h, [&](auto sc) { return ch_with_cell(h, [&](auto... cell) { return f(sc, cell...); }); });
+}
+
+// The launch shape that goes with SC: workgroup size, dynamic LDS, the kernels' n_pairs and lanes arguments, the grid for E envs.
+// Without pairs a workgroup is one wave of 64 envs and has no LDS.
+struct ChShape {
+    unsigned block;
+    size_t lds;
+    int n_pairs, lanes;
+    unsigned grid(int E) const { return (unsigned)((E + lanes - 1) / lanes); }
+};
+template <bool SC>
+static ChShape ch_shape(const naf_chain_env* h, int waves) {
+    if constexpr (SC) return {64u * waves, ch_lds_bytes(h->n_seg, h->lanes, waves), h->n_pairs, h->lanes};
+    return {64u, 0, 0, 64};
+}
+
+// Kernel K's dynamic LDS may exceed the 64 KB a kernel gets unasked: raised once per device, and the flag is K's own
+template <auto K>
+static int ch_raise(int bytes = CH_MAX_DYN_LDS) {
     static bool raised_dev[64];
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return (int)e;
     if (dev < 0 || dev >= 64) return NAF_ERR_ARG;
     if (raised_dev[dev]) return NAF_OK;
-    const void* ks[16] = {(const void*)chain_env_step_kernel<true, false>, (const void*)chain_env_step_kernel<true, true, ChainRanges>,
-                         (const void*)chain_env_probe_kernel<true>, (const void*)chain_env_rollout_kernel<true>,
-                         (const void*)chain_env_step_kernel<true, false, ChainCell>,
-                         (const void*)chain_env_step_kernel<true, true, ChainRanges, ChainCell>,
-                         (const void*)chain_env_rollout_kernel<true, ChainCell>,
-                         (const void*)chain_env_step_kernel<true, false, ChainTag>,
-                         (const void*)chain_env_step_kernel<true, true, ChainRanges, ChainTag>,
-                         (const void*)chain_env_step_kernel<true, false, ChainCell, ChainTag>,
-                         (const void*)chain_env_step_kernel<true, true, ChainRanges, ChainCell, ChainTag>,
-                         (const void*)chain_env_step_kernel<true, false, ChainCell, ChainBox>,
-                         (const void*)chain_env_step_kernel<true, true, ChainRanges, ChainCell, ChainBox>,
-                         (const void*)chain_env_rollout_kernel<true, ChainCell, ChainBox>,
-                         (const void*)chain_env_step_kernel<true, false, ChainCell, ChainBox, ChainTag>,
-                         (const void*)chain_env_step_kernel<true, true, ChainRanges, ChainCell, ChainBox, ChainTag>};
-    for (const void* k : ks) {
-        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, CH_MAX_DYN_LDS);
-        if (e != hipSuccess) return (int)e;
-    }
+    e = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return (int)e;
     raised_dev[dev] = true;
     return NAF_OK;
+}
+
+// One launch of kernel K in shape w. The kernels whose launches engine.py captures into graphs (step, probe, rollout) go through
+// this one: naf_chain_env_create raised their limits, and nothing here calls the runtime but the launch.
+template <auto K, class... Args>
+static int ch_launch(unsigned grid, const ChShape& w, void* stream, Args... args) {
+    K<<<grid, w.block, w.lds, (hipStream_t)stream>>>(args...);
+    NAF_CHECK_LAUNCH();
+    return NAF_OK;
+}
+// The same for an entry point no graph captures (path, certify, demonstrations): an SC launch first raises K's limit to `bytes`
+template <auto K, class... Args>
+static int ch_launch_raising(int bytes, unsigned grid, const ChShape& w, void* stream, Args... args) {
+    if (w.n_pairs > 0) {
+        const int rc = ch_raise<K>(bytes);
+        if (rc != NAF_OK) return rc;
+    }
+    return ch_launch<K>(grid, w, stream, args...);
 }
 
 extern "C" int naf_chain_env_create(const float* model_host, int n_floats, naf_chain_env_t** out) {
@@ -931,7 +968,18 @@ extern "C" int naf_chain_env_create(const float* model_host, int n_floats, naf_c
         // fewer envs per workgroup for an arm whose end points do not fit with 64; a refusal when one env's do not fit
         h->waves = std::min(CH_MAX_WAVES, (h->n_pairs + CH_PAIRS_PER_WAVE - 1) / CH_PAIRS_PER_WAVE);
         while (h->lanes > 1 && ch_lds_bytes(h->n_seg, h->lanes, h->waves) > CH_MAX_DYN_LDS) h->lanes >>= 1;
-        rc = ch_lds_bytes(h->n_seg, h->lanes, h->waves) > CH_MAX_DYN_LDS ? NAF_CHAIN_ERR_LDS : ch_raise_lds_limit();
+        rc = ch_lds_bytes(h->n_seg, h->lanes, h->waves) > CH_MAX_DYN_LDS ? NAF_CHAIN_ERR_LDS : NAF_OK;
+        // raised here, eagerly, for the kernels whose launches are captured into graphs: this handle's own step, probe and rollout
+        if (rc == NAF_OK)
+            rc = ch_with_cell(h, [](auto... cell) {
+                int r = ch_raise<chain_env_step_kernel<true, false, decltype(cell)...>>();
+                if (r == NAF_OK) r = ch_raise<chain_env_step_kernel<true, true, ChainRanges, decltype(cell)...>>();
+                if (r == NAF_OK) r = ch_raise<chain_env_step_kernel<true, false, decltype(cell)..., ChainTag>>();
+                if (r == NAF_OK) r = ch_raise<chain_env_step_kernel<true, true, ChainRanges, decltype(cell)..., ChainTag>>();
+                if (r == NAF_OK) r = ch_raise<chain_env_probe_kernel<true>>();
+                if (r == NAF_OK) r = ch_raise<chain_env_rollout_kernel<true, decltype(cell)...>>();
+                return r;
+            });
         if (rc != NAF_OK) {
             delete h;
             return rc;
@@ -998,75 +1046,26 @@ extern "C" int naf_chain_env_reset(naf_chain_env_t* h, float* env_state, float* 
     return NAF_OK;
 }
 
-// The four workcell launches of a step. Cell: ChainCell, or ChainCell, ChainBox for a model with boxes; then the tag, if any
-template <class... Cell>
-static void ch_step_launch_cell(naf_chain_env_t* h, float* env_state, const float* actions, float* out_rows, float* obs_next, int E,
-                                int rf, uint64_t seed, const uint64_t* counter_dev, int max_frames, naf_episode_record_t* records,
-                                int record_slots, void* stream, const Cell... cell) {
-    const int A = h->A;
-    const int waves = h->scene_on ? std::min(h->waves, CH_SCENE_WAVES) : h->waves;
-    const dim3 grid_sc((E + h->lanes - 1) / h->lanes), grid((E + 63) / 64);
-    const size_t lds = ch_lds_bytes(h->n_seg, h->lanes, waves);
-    hipStream_t s = (hipStream_t)stream;
-    if (h->scene_on && h->n_pairs > 0)
-        chain_env_step_kernel<true, true, ChainRanges, Cell...><<<grid_sc, 64 * waves, lds, s>>>(
-            h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
-            record_slots, h->n_pairs, h->lanes, ch_ranges(h), cell...);
-    else if (h->scene_on)
-        chain_env_step_kernel<false, true, ChainRanges, Cell...><<<grid, 64, 0, s>>>(
-            h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
-            record_slots, 0, 64, ch_ranges(h), cell...);
-    else if (h->n_pairs > 0)
-        chain_env_step_kernel<true, false, Cell...><<<grid_sc, 64 * waves, lds, s>>>(
-            h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
-            record_slots, h->n_pairs, h->lanes, cell...);
-    else
-        chain_env_step_kernel<false, false, Cell...><<<grid, 64, 0, s>>>(
-            h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
-            record_slots, 0, 64, cell...);
-}
-
-// Tag: nothing (naf_chain_env_step: the launches are the ones they always were) or one ChainTag (naf_chain_env_step_tagged)
+// Tag: nothing (naf_chain_env_step: the launches are the ones they always were) or one ChainTag (naf_chain_env_step_tagged).
+// The scene choice is the step's own: ChainRanges leads the pack of a SCENE launch, whose workgroups are at most CH_SCENE_WAVES waves.
 template <class... Tag>
 static int ch_step_launch(naf_chain_env_t* h, float* env_state, const float* actions, float* out_rows, float* obs_next,
                           int E, uint64_t seed, const uint64_t* counter_dev, int max_frames, naf_episode_record_t* records,
                           int record_slots, void* stream, const Tag... tag) {
     if (!h || !env_state || !actions || !out_rows || !obs_next || E <= 0) return NAF_ERR_ARG;
     if (records && (record_slots <= 0 || !counter_dev)) return NAF_ERR_ARG;
-    const int A = h->A;
-    const int rf = naf_replay_row_floats(2 * A + 9, A);
+    const int rf = naf_replay_row_floats(2 * h->A + 9, h->A);
     if (rf <= 0) return NAF_ERR_ARG;
-    if (h->n_cell > 0) {      // the workcell's instantiations, launched as their CELL-less counterparts below are
-        if (h->scene_on && !h->scene_ready) return NAF_ERR_STATE;
-        if (h->n_box > 0)
-            ch_step_launch_cell(h, env_state, actions, out_rows, obs_next, E, rf, seed, counter_dev, max_frames, records, record_slots,
-                                stream, ChainCell{}, ChainBox{}, tag...);
-        else
-            ch_step_launch_cell(h, env_state, actions, out_rows, obs_next, E, rf, seed, counter_dev, max_frames, records, record_slots,
-                                stream, ChainCell{}, tag...);
-    } else if (h->scene_on) {
-        if (!h->scene_ready) return NAF_ERR_STATE;
-        const int waves = std::min(h->waves, CH_SCENE_WAVES);
-        if (h->n_pairs > 0)
-            chain_env_step_kernel<true, true, ChainRanges, Tag...><<<(E + h->lanes - 1) / h->lanes, 64 * waves, ch_lds_bytes(h->n_seg, h->lanes, waves),
-                                                (hipStream_t)stream>>>(
-                h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
-                record_slots, h->n_pairs, h->lanes, ch_ranges(h), tag...);
-        else
-            chain_env_step_kernel<false, true, ChainRanges, Tag...><<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(
-                h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
-                record_slots, 0, 64, ch_ranges(h), tag...);
-    } else if (h->n_pairs > 0)
-        chain_env_step_kernel<true, false, Tag...><<<(E + h->lanes - 1) / h->lanes, 64 * h->waves, ch_lds_bytes(h->n_seg, h->lanes, h->waves),
-                                      (hipStream_t)stream>>>(h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf,
-                                                             seed, counter_dev, max_frames, records, record_slots, h->n_pairs,
-                                                             h->lanes, tag...);
-    else
-        chain_env_step_kernel<false, false, Tag...><<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(
-            h->model_dev, env_state, actions, out_rows, obs_next, E, A, h->n_seg, rf, seed, counter_dev, max_frames, records,
-            record_slots, 0, 64, tag...);
-    NAF_CHECK_LAUNCH();
-    return NAF_OK;
+    if (h->scene_on && !h->scene_ready) return NAF_ERR_STATE;
+    return ch_with_pack(h, [&](auto sc, auto... cell) {
+        const ChShape w = ch_shape<sc()>(h, h->scene_on ? std::min(h->waves, CH_SCENE_WAVES) : h->waves);
+        auto launch = [&](auto scene, auto... rg) {
+            return ch_launch<chain_env_step_kernel<sc(), scene(), decltype(rg)..., decltype(cell)..., Tag...>>(
+                w.grid(E), w, stream, h->model_dev, env_state, actions, out_rows, obs_next, E, h->A, h->n_seg, rf, seed, counter_dev,
+                max_frames, records, record_slots, w.n_pairs, w.lanes, rg..., cell..., tag...);
+        };
+        return h->scene_on ? launch(std::true_type{}, ch_ranges(h)) : launch(std::false_type{});
+    });
 }
 
 extern "C" int naf_chain_env_step(naf_chain_env_t* h, float* env_state, const float* actions, float* out_rows, float* obs_next,
@@ -1089,25 +1088,19 @@ extern "C" int naf_chain_env_step_tagged(naf_chain_env_t* h, float* env_state, c
 
 extern "C" int naf_chain_env_probe(naf_chain_env_t* h, const float* env_state, float* out, int E, void* stream) {
     if (!h || !env_state || !out || E <= 0) return NAF_ERR_ARG;
-    if (h->n_pairs > 0)
-        chain_env_probe_kernel<true><<<(E + h->lanes - 1) / h->lanes, 64 * h->waves, ch_lds_bytes(h->n_seg, h->lanes, h->waves),
-                                       (hipStream_t)stream>>>(h->model_dev, env_state, out, E, h->A, h->n_seg, h->n_pairs, h->lanes);
-    else
-        chain_env_probe_kernel<false><<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(h->model_dev, env_state, out, E, h->A, h->n_seg,
-                                                                                     0, 64);
-    NAF_CHECK_LAUNCH();
-    return NAF_OK;
+    return ch_with_sc(h, [&](auto sc) {
+        const ChShape w = ch_shape<sc()>(h, h->waves);
+        return ch_launch<chain_env_probe_kernel<sc()>>(w.grid(E), w, stream, h->model_dev, env_state, out, E, h->A, h->n_seg, w.n_pairs,
+                                                       w.lanes);
+    });
 }
 
 extern "C" int naf_chain_env_probe_cell(naf_chain_env_t* h, const float* env_state, float* out, int E, void* stream) {
     if (!h || !env_state || !out || E <= 0) return NAF_ERR_ARG;
     if (h->n_cell == 0) return NAF_ERR_STATE;
-    if (h->n_box > 0)
-        chain_env_probe_cell_box_kernel<<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(h->model_dev, env_state, out, E, h->A, h->n_seg);
-    else
-        chain_env_probe_cell_kernel<<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(h->model_dev, env_state, out, E, h->A, h->n_seg);
-    NAF_CHECK_LAUNCH();
-    return NAF_OK;
+    const ChShape w = ch_shape<false>(h, 1);      // one wave per workgroup: the workcell needs no pair phase
+    if (h->n_box > 0) return ch_launch<chain_env_probe_cell_box_kernel>(w.grid(E), w, stream, h->model_dev, env_state, out, E, h->A, h->n_seg);
+    return ch_launch<chain_env_probe_cell_kernel>(w.grid(E), w, stream, h->model_dev, env_state, out, E, h->A, h->n_seg);
 }
 
 extern "C" int naf_chain_env_reset_given(naf_chain_env_t* h, float* env_state, float* obs, int E, const float* q0_dev,
@@ -1122,32 +1115,12 @@ extern "C" int naf_chain_env_reset_given(naf_chain_env_t* h, float* env_state, f
 extern "C" int naf_chain_env_rollout_step(naf_chain_env_t* h, float* env_state, const float* actions, float* obs_next, float* outcome,
                                           float* traj, int E, int max_frames, void* stream) {
     if (!h || !env_state || !actions || !obs_next || !outcome || E <= 0 || max_frames < 1) return NAF_ERR_ARG;
-    if (h->n_box > 0 && h->n_pairs > 0)
-        chain_env_rollout_kernel<true, ChainCell, ChainBox><<<(E + h->lanes - 1) / h->lanes, 64 * h->waves, ch_lds_bytes(h->n_seg, h->lanes, h->waves),
-                                                         (hipStream_t)stream>>>(h->model_dev, env_state, actions, obs_next, outcome, traj, E,
-                                                                                h->A, h->n_seg, max_frames, h->n_pairs, h->lanes,
-                                                                                ChainCell{}, ChainBox{});
-    else if (h->n_box > 0)
-        chain_env_rollout_kernel<false, ChainCell, ChainBox><<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(
-            h->model_dev, env_state, actions, obs_next, outcome, traj, E, h->A, h->n_seg, max_frames, 0, 64, ChainCell{}, ChainBox{});
-    else if (h->n_cell > 0 && h->n_pairs > 0)
-        chain_env_rollout_kernel<true, ChainCell><<<(E + h->lanes - 1) / h->lanes, 64 * h->waves, ch_lds_bytes(h->n_seg, h->lanes, h->waves),
-                                               (hipStream_t)stream>>>(h->model_dev, env_state, actions, obs_next, outcome, traj, E,
-                                                                      h->A, h->n_seg, max_frames, h->n_pairs, h->lanes,
-                                                                      ChainCell{});
-    else if (h->n_cell > 0)
-        chain_env_rollout_kernel<false, ChainCell><<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(h->model_dev, env_state, actions, obs_next,
-                                                                                             outcome, traj, E, h->A, h->n_seg, max_frames,
-                                                                                             0, 64, ChainCell{});
-    else if (h->n_pairs > 0)
-        chain_env_rollout_kernel<true><<<(E + h->lanes - 1) / h->lanes, 64 * h->waves, ch_lds_bytes(h->n_seg, h->lanes, h->waves),
-                                         (hipStream_t)stream>>>(h->model_dev, env_state, actions, obs_next, outcome, traj, E, h->A,
-                                                                h->n_seg, max_frames, h->n_pairs, h->lanes);
-    else
-        chain_env_rollout_kernel<false><<<(E + 63) / 64, 64, 0, (hipStream_t)stream>>>(h->model_dev, env_state, actions, obs_next, outcome,
-                                                                                       traj, E, h->A, h->n_seg, max_frames, 0, 64);
-    NAF_CHECK_LAUNCH();
-    return NAF_OK;
+    return ch_with_pack(h, [&](auto sc, auto... cell) {
+        const ChShape w = ch_shape<sc()>(h, h->waves);
+        return ch_launch<chain_env_rollout_kernel<sc(), decltype(cell)...>>(w.grid(E), w, stream, h->model_dev, env_state, actions, obs_next,
+                                                                            outcome, traj, E, h->A, h->n_seg, max_frames, w.n_pairs,
+                                                                            w.lanes, cell...);
+    });
 }
 
 // ---- goal poses: damped least squares on the end effector's positional Jacobian (include/naf_hip.h, "Goal poses") ----------------
@@ -1335,22 +1308,6 @@ chain_ik_select_kernel(const float* __restrict__ q_out, const float* __restrict_
     }
 }
 
-// the solve kernels' dynamic LDS (1536 bytes per walked joint) may exceed the 64 KB a kernel gets unasked: raised once per device
-static int ch_ik_raise_lds_limit() {
-    static bool raised_dev[64];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return (int)e;
-    if (dev < 0 || dev >= 64) return NAF_ERR_ARG;
-    if (raised_dev[dev]) return NAF_OK;
-    for (const void* k : {(const void*)chain_ik_solve_kernel<false>, (const void*)chain_ik_solve_kernel<true>}) {
-        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, CH_MAX_DYN_LDS);
-        if (e != hipSuccess) return (int)e;
-    }
-    raised_dev[dev] = true;
-    return NAF_OK;
-}
-
 static inline bool ch_ik_counts_ok(int N, int R) {
     return N >= 1 && R >= 1 && R <= 64 && (R & (R - 1)) == 0 && (int64_t)N * R <= (int64_t)1 << 30;
 }
@@ -1364,7 +1321,9 @@ extern "C" int naf_chain_ik_solve(naf_chain_env_t* h, const float* targets_dev, 
         return NAF_ERR_ARG;
     const size_t lds = (size_t)std::max(h->ee_frame, 1) * 6 * 64 * sizeof(float);
     if (lds > CH_MAX_DYN_LDS) return NAF_CHAIN_ERR_LDS;
-    const int rc = ch_ik_raise_lds_limit();
+    // the solve kernels' dynamic LDS (1536 bytes per walked joint) may exceed the 64 KB a kernel gets unasked: both are raised here
+    int rc = ch_raise<chain_ik_solve_kernel<false>>();
+    if (rc == NAF_OK) rc = ch_raise<chain_ik_solve_kernel<true>>();
     if (rc != NAF_OK) return rc;
     const unsigned grid = (unsigned)(((int64_t)N * R + 63) / 64);
     if (iters_out)
@@ -1552,103 +1511,43 @@ chain_path_check_kernel(const float* __restrict__ model, const float* __restrict
     }
 }
 
-// the SC path kernels' dynamic LDS is the probe's and may exceed the 64 KB a kernel gets unasked: raised once per device
-static int ch_path_raise_lds_limit() {
-    static bool raised_dev[64];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return (int)e;
-    if (dev < 0 || dev >= 64) return NAF_ERR_ARG;
-    if (raised_dev[dev]) return NAF_OK;
-    for (const void* k : {(const void*)chain_path_check_kernel<true>, (const void*)chain_path_check_kernel<true, ChainCell>,
-                          (const void*)chain_path_check_kernel<true, ChainCell, ChainBox>,
-                          (const void*)chain_path_check_kernel<true, ChainCert>,
-                          (const void*)chain_path_check_kernel<true, ChainCert, ChainCell>,
-                          (const void*)chain_path_check_kernel<true, ChainCert, ChainCell, ChainBox>}) {
-        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, CH_MAX_DYN_LDS);
-        if (e != hipSuccess) return (int)e;
-    }
-    raised_dev[dev] = true;
-    return NAF_OK;
+// what naf_chain_path_check and naf_chain_path_certify ask of the arguments they share
+static inline bool ch_path_args_ok(int N, int C, int S, float margin, float obstacle_radius) {
+    if (N < 1 || C < 1 || C > 64 || S < 64 || S > 2048 || S % 64 != 0 || (int64_t)N * C > (int64_t)1 << 30) return false;
+    return std::isfinite(margin) && std::isfinite(obstacle_radius) && obstacle_radius >= 0.f;
 }
 
-template <class... Cell>
-static void ch_path_launch(naf_chain_env_t* h, const float* q_start, const float* q_goal, const float* vias, const float* obstacles,
-                           float orad, int N, int C, int S, float margin, float* out, float* poses_out, void* stream,
-                           const Cell... cell) {
-    const unsigned grid = (unsigned)((int64_t)N * C);
-    if (h->n_pairs > 0)
-        chain_path_check_kernel<true, Cell...><<<grid, 64 * h->waves, ch_lds_bytes(h->n_seg, h->lanes, h->waves), (hipStream_t)stream>>>(
-            h->model_dev, q_start, q_goal, vias, obstacles, orad, C, S, h->A, h->n_seg, h->n_pairs, h->lanes, margin, out, poses_out,
-            cell...);
-    else
-        chain_path_check_kernel<false, Cell...><<<grid, 64, 0, (hipStream_t)stream>>>(
-            h->model_dev, q_start, q_goal, vias, obstacles, orad, C, S, h->A, h->n_seg, 0, 64, margin, out, poses_out, cell...);
-}
-
+// The SC path kernels' dynamic LDS is the probe's. One workgroup per candidate path.
 extern "C" int naf_chain_path_check(naf_chain_env_t* h, const float* q_start_dev, const float* q_goal_dev, const float* vias_dev,
                                     const float* obstacles_dev, float obstacle_radius, int N, int C, int S, float margin, float* out,
                                     float* poses_out, void* stream) {
     if (!h || !q_start_dev || !q_goal_dev || !vias_dev || !obstacles_dev || !out) return NAF_ERR_ARG;
-    if (N < 1 || C < 1 || C > 64 || S < 64 || S > 2048 || S % 64 != 0 || (int64_t)N * C > (int64_t)1 << 30) return NAF_ERR_ARG;
-    if (!std::isfinite(margin) || !std::isfinite(obstacle_radius) || obstacle_radius < 0.f) return NAF_ERR_ARG;
-    if (h->n_pairs > 0) {
-        const int rc = ch_path_raise_lds_limit();
-        if (rc != NAF_OK) return rc;
-    }
-    if (h->n_box > 0)
-        ch_path_launch(h, q_start_dev, q_goal_dev, vias_dev, obstacles_dev, obstacle_radius, N, C, S, margin, out, poses_out, stream,
-                       ChainCell{}, ChainBox{});
-    else if (h->n_cell > 0)
-        ch_path_launch(h, q_start_dev, q_goal_dev, vias_dev, obstacles_dev, obstacle_radius, N, C, S, margin, out, poses_out, stream,
-                       ChainCell{});
-    else
-        ch_path_launch(h, q_start_dev, q_goal_dev, vias_dev, obstacles_dev, obstacle_radius, N, C, S, margin, out, poses_out, stream);
-    NAF_CHECK_LAUNCH();
-    return NAF_OK;
-}
-
-template <class... Cell>
-static void ch_cert_launch(naf_chain_env_t* h, const float* q_start, const float* q_goal, const float* vias, const float* obstacles,
-                           float orad, int N, int C, int S, float margin, float* out, float* poses_out, void* stream,
-                           const ChainCert cert, const Cell... cell) {
-    const unsigned grid = (unsigned)((int64_t)N * C);
-    const size_t lds = ch_cert_lds_bytes(h->n_seg, h->n_pairs, h->lanes, h->waves);
-    if (h->n_pairs > 0)
-        chain_path_check_kernel<true, ChainCert, Cell...><<<grid, 64 * h->waves, lds, (hipStream_t)stream>>>(
-            h->model_dev, q_start, q_goal, vias, obstacles, orad, C, S, h->A, h->n_seg, h->n_pairs, h->lanes, margin, out, poses_out,
-            cert, cell...);
-    else
-        chain_path_check_kernel<false, ChainCert, Cell...><<<grid, 64, lds, (hipStream_t)stream>>>(
-            h->model_dev, q_start, q_goal, vias, obstacles, orad, C, S, h->A, h->n_seg, 0, 64, margin, out, poses_out, cert, cell...);
+    if (!ch_path_args_ok(N, C, S, margin, obstacle_radius)) return NAF_ERR_ARG;
+    return ch_with_pack(h, [&](auto sc, auto... cell) {
+        const ChShape w = ch_shape<sc()>(h, h->waves);
+        return ch_launch_raising<chain_path_check_kernel<sc(), decltype(cell)...>>(
+            CH_MAX_DYN_LDS, (unsigned)((int64_t)N * C), w, stream, h->model_dev, q_start_dev, q_goal_dev, vias_dev, obstacles_dev,
+            obstacle_radius, C, S, h->A, h->n_seg, w.n_pairs, w.lanes, margin, out, poses_out, cell...);
+    });
 }
 
 extern "C" int naf_chain_path_certify(naf_chain_env_t* h, const float* q_start_dev, const float* q_goal_dev, const float* vias_dev,
                                       const float* obstacles_dev, float obstacle_radius, const float* reach_dev, float guard, int N,
                                       int C, int S, float margin, float* out, float* poses_out, void* stream) {
     if (!h || !q_start_dev || !q_goal_dev || !vias_dev || !obstacles_dev || !reach_dev || !out) return NAF_ERR_ARG;
-    if (N < 1 || C < 1 || C > 64 || S < 64 || S > 2048 || S % 64 != 0 || (int64_t)N * C > (int64_t)1 << 30) return NAF_ERR_ARG;
-    if (!std::isfinite(margin) || !std::isfinite(obstacle_radius) || obstacle_radius < 0.f) return NAF_ERR_ARG;
+    if (!ch_path_args_ok(N, C, S, margin, obstacle_radius)) return NAF_ERR_ARG;
     if (!std::isfinite(guard) || guard < 0.f) return NAF_ERR_ARG;
     // the tables and the second reduction row on top of the handle's rows: an arm they do not fit with is refused, not shrunk
-    if (ch_cert_lds_bytes(h->n_seg, h->n_pairs, h->lanes, h->waves) > (h->n_pairs > 0 ? CH_MAX_DYN_LDS : 64 * 1024))
-        return NAF_CHAIN_ERR_LDS;
-    if (h->n_pairs > 0) {
-        const int rc = ch_path_raise_lds_limit();
-        if (rc != NAF_OK) return rc;
-    }
+    const size_t lds = ch_cert_lds_bytes(h->n_seg, h->n_pairs, h->lanes, h->waves);
+    if (lds > (h->n_pairs > 0 ? CH_MAX_DYN_LDS : 64 * 1024)) return NAF_CHAIN_ERR_LDS;
     const ChainCert cert = {reach_dev, guard};
-    if (h->n_box > 0)
-        ch_cert_launch(h, q_start_dev, q_goal_dev, vias_dev, obstacles_dev, obstacle_radius, N, C, S, margin, out, poses_out, stream,
-                       cert, ChainCell{}, ChainBox{});
-    else if (h->n_cell > 0)
-        ch_cert_launch(h, q_start_dev, q_goal_dev, vias_dev, obstacles_dev, obstacle_radius, N, C, S, margin, out, poses_out, stream,
-                       cert, ChainCell{});
-    else
-        ch_cert_launch(h, q_start_dev, q_goal_dev, vias_dev, obstacles_dev, obstacle_radius, N, C, S, margin, out, poses_out, stream,
-                       cert);
-    NAF_CHECK_LAUNCH();
-    return NAF_OK;
+    return ch_with_pack(h, [&](auto sc, auto... cell) {
+        ChShape w = ch_shape<sc()>(h, h->waves);
+        w.lds = lds;      // (the tables: also without pairs)
+        return ch_launch_raising<chain_path_check_kernel<sc(), ChainCert, decltype(cell)...>>(
+            CH_MAX_DYN_LDS, (unsigned)((int64_t)N * C), w, stream, h->model_dev, q_start_dev, q_goal_dev, vias_dev, obstacles_dev,
+            obstacle_radius, C, S, h->A, h->n_seg, w.n_pairs, w.lanes, margin, out, poses_out, cert, cell...);
+    });
 }
 
 // ---- demonstrations: planned joint paths as replay rows (include/naf_hip.h, "Demonstrations") -------------------------------------
@@ -1814,39 +1713,6 @@ chain_demo_rows_kernel(const float* __restrict__ model, const float* __restrict_
     r[7] = 0.f;
 }
 
-// the SC demonstration kernels' dynamic LDS is the probe's and the base behind it: raised once per device
-static int ch_demo_raise_lds_limit() {
-    static bool raised_dev[64];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return (int)e;
-    if (dev < 0 || dev >= 64) return NAF_ERR_ARG;
-    if (raised_dev[dev]) return NAF_OK;
-    for (const void* k : {(const void*)chain_demo_rows_kernel<true>, (const void*)chain_demo_rows_kernel<true, ChainCell>,
-                          (const void*)chain_demo_rows_kernel<true, ChainCell, ChainBox>}) {
-        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, CH_MAX_DYN_LDS + 1024);
-        if (e != hipSuccess) return (int)e;
-    }
-    raised_dev[dev] = true;
-    return NAF_OK;
-}
-
-template <class... Cell>
-static void ch_demo_launch(naf_chain_env_t* h, const float* q_start, const float* leg_actions, const int* n_ticks, const float* targets,
-                           const float* obstacles, float orad, int N, int T_cap, int rf, float* rows_out, float* records_out,
-                           float* poses_out, void* stream, const Cell... cell) {
-    const size_t base = (size_t)ch_demo_base_floats(h->A) * sizeof(float);
-    if (h->n_pairs > 0)
-        chain_demo_rows_kernel<true, Cell...><<<(unsigned)N, 64 * h->waves, ch_lds_bytes(h->n_seg, h->lanes, h->waves) + base,
-                                              (hipStream_t)stream>>>(h->model_dev, q_start, leg_actions, n_ticks, targets, obstacles, orad,
-                                                                     T_cap, h->A, h->n_seg, h->n_pairs, h->lanes, rf, rows_out,
-                                                                     records_out, poses_out, cell...);
-    else
-        chain_demo_rows_kernel<false, Cell...><<<(unsigned)N, 64, base, (hipStream_t)stream>>>(
-            h->model_dev, q_start, leg_actions, n_ticks, targets, obstacles, orad, T_cap, h->A, h->n_seg, 0, 64, rf, rows_out,
-            records_out, poses_out, cell...);
-}
-
 extern "C" int naf_chain_demo_rows(naf_chain_env_t* h, const float* q_start_dev, const float* leg_actions_dev, const int32_t* n_ticks_dev,
                                    const float* targets_dev, const float* obstacles_dev, float obstacle_radius, int N, int T_cap,
                                    float* rows_out, int row_floats, float* records_out, float* poses_out, void* stream) {
@@ -1855,19 +1721,11 @@ extern "C" int naf_chain_demo_rows(naf_chain_env_t* h, const float* q_start_dev,
     if (N < 1 || N > 1 << 30 || T_cap < 1 || T_cap > NAF_CHAIN_DEMO_MAX_TICKS) return NAF_ERR_ARG;
     if (row_floats <= 0 || row_floats != naf_replay_row_floats(2 * h->A + 9, h->A)) return NAF_ERR_ARG;
     if (!std::isfinite(obstacle_radius) || obstacle_radius < 0.f) return NAF_ERR_ARG;
-    if (h->n_pairs > 0) {
-        const int rc = ch_demo_raise_lds_limit();
-        if (rc != NAF_OK) return rc;
-    }
-    if (h->n_box > 0)
-        ch_demo_launch(h, q_start_dev, leg_actions_dev, n_ticks_dev, targets_dev, obstacles_dev, obstacle_radius, N, T_cap, row_floats,
-                       rows_out, records_out, poses_out, stream, ChainCell{}, ChainBox{});
-    else if (h->n_cell > 0)
-        ch_demo_launch(h, q_start_dev, leg_actions_dev, n_ticks_dev, targets_dev, obstacles_dev, obstacle_radius, N, T_cap, row_floats,
-                       rows_out, records_out, poses_out, stream, ChainCell{});
-    else
-        ch_demo_launch(h, q_start_dev, leg_actions_dev, n_ticks_dev, targets_dev, obstacles_dev, obstacle_radius, N, T_cap, row_floats,
-                       rows_out, records_out, poses_out, stream);
-    NAF_CHECK_LAUNCH();
-    return NAF_OK;
+    return ch_with_pack(h, [&](auto sc, auto... cell) {
+        ChShape w = ch_shape<sc()>(h, h->waves);
+        w.lds += (size_t)ch_demo_base_floats(h->A) * sizeof(float);      // the probe's rows and the base behind them
+        return ch_launch_raising<chain_demo_rows_kernel<sc(), decltype(cell)...>>(
+            CH_MAX_DYN_LDS + 1024, (unsigned)N, w, stream, h->model_dev, q_start_dev, leg_actions_dev, n_ticks_dev, targets_dev,
+            obstacles_dev, obstacle_radius, T_cap, h->A, h->n_seg, w.n_pairs, w.lanes, row_floats, rows_out, records_out, poses_out, cell...);
+    });
 }

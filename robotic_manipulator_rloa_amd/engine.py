@@ -823,7 +823,26 @@ class EpisodeLedger:
         return self.scores
 
 
-class DeviceEnvLoop:
+class _ChainHandle:
+    """The one owner of a chain model's device handle (csrc/chain_env.hip): packs the blob, creates the handle on `self.lib` and
+    destroys it with the object. `_chain_env` stays None until a model is opened."""
+    _chain_env = None
+
+    def _create_chain_env(self, chain) -> None:
+        import ctypes
+        blob = np.ascontiguousarray(chain.pack(), np.float32)
+        handle = ctypes.c_void_p()
+        check(self.lib.naf_chain_env_create(blob.ctypes.data, int(blob.size), ctypes.byref(handle)), "chain_env_create")
+        self.chain, self._chain_env = chain, handle
+        self.has_cell = bool(chain.cell_spheres or chain.cell_planes or chain.cell_boxes)
+
+    def __del__(self):
+        if self._chain_env is not None:
+            self.lib.naf_chain_env_destroy(self._chain_env)
+            self._chain_env = None
+
+
+class DeviceEnvLoop(_ChainHandle):
     """E manipulator envs living on the GPU, driven by the agent's policy: the synthetic stand-in (csrc/synth_env.hip) or, with
     `chain`, E copies of the arm a URDF describes (csrc/chain_env.hip; environment/urdf_chain.py compiles the model).
 
@@ -865,7 +884,7 @@ class DeviceEnvLoop:
         self.max_frames = int(max_frames)
         self.noise_scale = float(noise_scale)
         self.actor = ActPath(learner, self.E, seed=self.seed ^ 0xA5A5A5A5)
-        self.chain, self._chain_env = chain, None
+        self.chain = chain
         import ctypes
         if chain is not None:
             self._open_chain(chain, target, obstacle, obstacle_radius, obstacle_jitter, target_range, obstacle_range, scene_margin)
@@ -909,10 +928,7 @@ class DeviceEnvLoop:
                              f"was built for action_size {lay.A} / state_size {lay.S}")
         if target is None or obstacle is None or len(target) != 3 or len(obstacle) != 3:
             raise ValueError("DeviceEnvLoop(chain=...): give target and obstacle as xyz")
-        blob = np.ascontiguousarray(chain.pack(), np.float32)
-        handle = ctypes.c_void_p()
-        check(self.lib.naf_chain_env_create(blob.ctypes.data, int(blob.size), ctypes.byref(handle)), "chain_env_create")
-        self._chain_env = handle
+        self._create_chain_env(chain)
         self.scene = [float(v) for v in target] + [float(v) for v in obstacle] + [float(obstacle_jitter), float(obstacle_radius)]
         self._scene = (ctypes.c_float * 8)(*self.scene)
         ranges = [float(v) for r in (target_range, obstacle_range) for v in ((0.0, 0.0, 0.0) if r is None else r)]
@@ -924,13 +940,8 @@ class DeviceEnvLoop:
             ranges.append(float(scene_margin))
             if obstacle_jitter:
                 raise ValueError("DeviceEnvLoop(chain=...): obstacle_jitter and scene ranges exclude each other")
-            check(self.lib.naf_chain_env_set_scene_ranges(handle, (ctypes.c_float * 7)(*ranges)), "chain_env_set_scene_ranges")
+            check(self.lib.naf_chain_env_set_scene_ranges(self._chain_env, (ctypes.c_float * 7)(*ranges)), "chain_env_set_scene_ranges")
             self.scene = self.scene + ranges
-
-    def __del__(self):
-        if getattr(self, "_chain_env", None) is not None:
-            self.lib.naf_chain_env_destroy(self._chain_env)
-            self._chain_env = None
 
     def reset(self) -> None:
         if self._chain_env is not None:
@@ -1061,13 +1072,12 @@ class ReachResult:
                                                # not reach or no free path was found
 
 
-class DeviceRollout:
+class DeviceRollout(_ChainHandle):
     """E copies of a chain model (csrc/chain_env.hip) that run the learner's policy from GIVEN start poses in GIVEN scenes:
     naf_chain_env_reset_given, then per frame one batched act() and one naf_chain_env_rollout_step — a captured one-step graph, as
     DeviceEnvLoop's (use_graph=False: direct launches). Nothing is appended anywhere and the learner is only read."""
 
     def __init__(self, learner: Learner, chain, n_envs: int, obstacle_radius: float = 0.06, seed: int = 0, use_graph: bool = True):
-        import ctypes
         self.L, self.E, self.lib, self.chain = learner, int(n_envs), learner.lib, chain
         lay, dev = learner.lay, learner.dev
         if chain.A != lay.A or chain.state_size != lay.S:
@@ -1078,25 +1088,17 @@ class DeviceRollout:
         self.obstacle_radius = float(obstacle_radius)
         self.use_graph = use_graph
         self.actor = ActPath(learner, self.E, seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
-        blob = np.ascontiguousarray(chain.pack(), np.float32)
-        self._chain_env = ctypes.c_void_p()
-        check(self.lib.naf_chain_env_create(blob.ctypes.data, int(blob.size), ctypes.byref(self._chain_env)), "chain_env_create")
+        self._create_chain_env(chain)
         f32 = dict(dtype=torch.float32, device=dev)
         self.env_state = torch.zeros(self.E, self.lib.naf_chain_env_state_floats(self._chain_env), **f32)
         self.outcome = torch.zeros(self.E, 8, **f32)
         self.start = torch.zeros(self.E, 5, **f32)           # naf_chain_env_probe behind the reset
-        self.has_cell = bool(chain.cell_spheres or chain.cell_planes or chain.cell_boxes)
         self.start_cell = torch.full((self.E,), float("inf"), **f32)      # naf_chain_env_probe_cell, when the model has a workcell
         self.q0 = torch.zeros(self.E, lay.A, **f32)
         self.scene = torch.zeros(self.E, 6, **f32)
         self.traj: Optional[torch.Tensor] = None             # [frames + 1][E][A], kept once a run has recorded trajectories
         self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}  # one-step graphs by (frames, noise scale, trajectory pointer)
         self._key = None
-
-    def __del__(self):
-        if getattr(self, "_chain_env", None) is not None:
-            self.lib.naf_chain_env_destroy(self._chain_env)
-            self._chain_env = None
 
     @staticmethod
     def chunks(n: int, e: int) -> List[Tuple[int, int, int]]:
@@ -1171,7 +1173,7 @@ class DeviceRollout:
                            start[:, 4].copy(), outcome[:, 6].copy() if self.has_cell else np.full(N, np.inf, np.float32), start_cell)
 
 
-class GoalPoseSolver:
+class GoalPoseSolver(_ChainHandle):
     """Goal poses on a chain model (csrc/chain_env.hip, "goal poses"): per chunk of candidates naf_chain_ik_solve, then the
     clearances of the solved poses by naf_chain_env_reset_given + naf_chain_env_probe (+ naf_chain_env_probe_cell with a workcell),
     then naf_chain_ik_select. Owns the handle and the buffers; needs no agent. A chunk holds a fixed number of candidates,
@@ -1179,7 +1181,6 @@ class GoalPoseSolver:
     CHUNK = 32768
 
     def __init__(self, chain, obstacle_radius: float = 0.06, chunk: Optional[int] = None, device=None):
-        import ctypes
         _lib.require_gpu()
         self.lib, self.chain, self.A = _lib.load(), chain, chain.A
         self.dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
@@ -1187,10 +1188,7 @@ class GoalPoseSolver:
         self.chunk = int(self.CHUNK if chunk is None else chunk)
         if self.chunk < 64:
             raise ValueError("GoalPoseSolver: a chunk holds at least 64 candidates")
-        blob = np.ascontiguousarray(chain.pack(), np.float32)
-        self._chain_env = ctypes.c_void_p()
-        check(self.lib.naf_chain_env_create(blob.ctypes.data, int(blob.size), ctypes.byref(self._chain_env)), "chain_env_create")
-        self.has_cell = bool(chain.cell_spheres or chain.cell_planes or chain.cell_boxes)
+        self._create_chain_env(chain)
         C, A = self.chunk, self.A
         f32, i32 = dict(dtype=torch.float32, device=self.dev), dict(dtype=torch.int32, device=self.dev)
         self.targets, self.q_start, self.seeds = torch.zeros(C, 3, **f32), torch.zeros(C, A, **f32), torch.zeros(C, A, **f32)
@@ -1199,11 +1197,6 @@ class GoalPoseSolver:
         self.obs, self.scene = torch.zeros(C, 2 * A + 9, **f32), torch.zeros(C, 6, **f32)
         self.probe, self.cell = torch.zeros(C, 5, **f32), torch.full((C,), float("inf"), **f32)
         self.choice, self.cls = torch.zeros(C, **i32), torch.zeros(C, **i32)
-
-    def __del__(self):
-        if getattr(self, "_chain_env", None) is not None:
-            self.lib.naf_chain_env_destroy(self._chain_env)
-            self._chain_env = None
 
     def params(self, iterations: int, lam=None, e_max=None, dq_max=None) -> "_lib.IkParams":
         reach = self.chain.reach
@@ -1263,7 +1256,7 @@ class GoalPoseSolver:
         return GoalPoses(*[np.concatenate([getattr(p, f) for p in parts]) for f in GoalPoses._fields])
 
 
-class JointPathChecker:
+class JointPathChecker(_ChainHandle):
     """Collision-checked joint paths on a chain model (csrc/chain_env.hip, "joint paths"): per chunk of queries ONE
     naf_chain_path_check launch over queries x candidate vias, S sampled poses each, formed on the fly — no pose is materialised and
     eight floats per candidate come back; the choice among a query's candidates is environment.kinematic.select_joint_path on the
@@ -1276,7 +1269,6 @@ class JointPathChecker:
     (NAF_CHAIN_ERR_LDS) where the sampled check runs; joint_paths_host(certify=True) answers it."""
 
     def __init__(self, chain, obstacle_radius: float = 0.06, chunk: Optional[int] = None, device=None, certify: bool = False):
-        import ctypes
         _lib.require_gpu()
         self.lib, self.chain, self.A = _lib.load(), chain, chain.A
         self.dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
@@ -1284,9 +1276,7 @@ class JointPathChecker:
         self.chunk = int(PATH_CHUNK if chunk is None else chunk)
         if self.chunk < 64:
             raise ValueError("JointPathChecker: a chunk holds at least 64 candidate-samples, one candidate path")
-        blob = np.ascontiguousarray(chain.pack(), np.float32)
-        self._chain_env = ctypes.c_void_p()
-        check(self.lib.naf_chain_env_create(blob.ctypes.data, int(blob.size), ctypes.byref(self._chain_env)), "chain_env_create")
+        self._create_chain_env(chain)
         K, A = self.chunk // 64, self.A                      # the most candidates a chunk can hold: S is at least 64
         f32 = dict(dtype=torch.float32, device=self.dev)
         self.q_start, self.q_goal, self.obstacles = torch.zeros(K, A, **f32), torch.zeros(K, A, **f32), torch.zeros(K, 3, **f32)
@@ -1296,11 +1286,6 @@ class JointPathChecker:
             self.reach = torch.from_numpy(reach_table(chain)).to(self.dev).contiguous()
             self.guard = certificate_guard(chain)
             self.out_cert = torch.zeros(K, PATH_CERT_FLOATS, **f32)
-
-    def __del__(self):
-        if getattr(self, "_chain_env", None) is not None:
-            self.lib.naf_chain_env_destroy(self._chain_env)
-            self._chain_env = None
 
     def launch(self, n: int, C: int, S: int, margin: float) -> None:
         """the launch of one chunk of n queries x C candidates already in the buffers, on the current stream"""
@@ -1373,14 +1358,13 @@ def demonstration_chunks(rows_of, budget: int) -> List[Tuple[int, int, int]]:
     return out
 
 
-class DemonstrationWriter:
+class DemonstrationWriter(_ChainHandle):
     """Planned joint paths as replay rows on a chain model (csrc/chain_env.hip, "demonstrations"): per chunk of queries ONE
     naf_chain_demo_rows launch that writes every row of every demonstration, then torch plumbing — the mask `t < valid[n] and
     kept[n]` and a boolean index — to a contiguous device tensor of the kept rows in query order, then tick order. Owns the handle
     and staging buffers for `chunk` rows; needs no agent. A demonstration's rows do not depend on where in a launch it lies."""
 
     def __init__(self, chain, obstacle_radius: float = 0.06, chunk: Optional[int] = None, device=None):
-        import ctypes
         from .environment.kinematic import DEMO_CHUNK, DEMO_FLOATS, demo_row_layout
         _lib.require_gpu()
         self.lib, self.chain, self.A = _lib.load(), chain, chain.A
@@ -1391,9 +1375,7 @@ class DemonstrationWriter:
             raise ValueError("DemonstrationWriter: a chunk holds at least one row")
         self.row_floats = self.lib.naf_replay_row_floats(2 * self.A + 9, self.A)
         assert self.row_floats == demo_row_layout(self.A)[3]
-        blob = np.ascontiguousarray(chain.pack(), np.float32)
-        self._chain_env = ctypes.c_void_p()
-        check(self.lib.naf_chain_env_create(blob.ctypes.data, int(blob.size), ctypes.byref(self._chain_env)), "chain_env_create")
+        self._create_chain_env(chain)
         K, A = self.chunk, self.A                            # the most queries a chunk can hold: T_cap is at least 1
         f32 = dict(dtype=torch.float32, device=self.dev)
         self.q_start, self.leg_actions = torch.zeros(K, A, **f32), torch.zeros(K, 2, A, **f32)
@@ -1402,11 +1384,6 @@ class DemonstrationWriter:
         self.records = torch.zeros(K, DEMO_FLOATS, **f32)
         self.rows = torch.zeros(self.chunk, self.row_floats, **f32)
         self.launches = 0
-
-    def __del__(self):
-        if getattr(self, "_chain_env", None) is not None:
-            self.lib.naf_chain_env_destroy(self._chain_env)
-            self._chain_env = None
 
     def launch(self, n: int, T_cap: int) -> None:
         """the launch of one chunk of n demonstrations already in the buffers, on the current stream"""

@@ -17,7 +17,8 @@ ORAD = C.ORAD
 CAP = C.CAP                        # the project's band rule: at most 1 % of a case's ticks inside a band
 COUNTS = [(1, 64), (3, 130), (16, 256)]      # (N, T_cap): one demonstration; odd, a partial last pass; 16 demonstrations of many passes
 ARMS = P.ARMS                      # chain_path_common's: planar3 (CELL), iiwa_like7 (pairs, CELL + BOX), long12 (pairs, CELL), slider4
-EXTRA = [("iiwa_like7_bare", 4, 130)]        # pairs and no workcell: the sixth instantiation, at one count
+# pairs and no workcell, and boxes without pairs (one wave, CELL + BOX): the other two instantiations, at one count
+EXTRA = [("iiwa_like7_bare", 4, 130), ("planar3_boxes", 4, 130)]
 POOL = 8                           # candidates drawn per query and role; the first the twin accepts is taken
 BANDS = np.array([2.0, 2.0, 4.0, 2.0])       # x tol: distance - 0.05 | obstacle clearance | self-clearance | workcell clearance
 
@@ -35,7 +36,7 @@ WANT = {0: 1, 1: 2, 2: 0, 3: 5}              # the end code each role is built f
 # The pose bound. test_chain_demo_cpu.test_rehearsal measures, over every pose of every case below, the largest deviation of the
 # float32 restatement's recurrence (poses32: p + DT a as one rounding of the float64 sum of the exact product, then the limits) from
 # the twin's float64 recurrence under the same float32 actions:
-#     planar3 1.31e-5, iiwa_like7 2.07e-5, long12 8.08e-6, slider4 7.84e-6, iiwa_like7_bare 1.17e-5   ->   POSE_DEVIATION = 2.1e-5, rounded up
+#     planar3 1.31e-5, iiwa_like7 2.07e-5, long12 8.08e-6, slider4 7.84e-6, iiwa_like7_bare 1.17e-5, planar3_boxes 9.94e-6   ->   POSE_DEVIATION = 2.1e-5, rounded up
 # — up to half an ulp of the joint value (1.2e-7 near 3 rad) per tick, and a leg repeats ONE increment, so its roundings lean one way
 # and add up nearly linearly over the case's up to 256 ticks instead of as a random walk; float32(DT) adds 2e-8 of the leg. The bound is
 # 8 x that, the margin the path and goal-pose tests use and for the same reason: another legal rounding of the one fused step

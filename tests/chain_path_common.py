@@ -6,6 +6,7 @@ import functools
 
 import numpy as np
 
+import chain_box_common as BX
 import chain_cell_common as CC
 import chain_ik_common as IK
 import chain_rollout_common as C
@@ -55,6 +56,8 @@ def arm(name):
         return CC.arm(name)
     if name == "iiwa_like7_bare":
         return C.arm("iiwa_like7", True)
+    if name == "planar3_boxes":      # no pairs, among chain_box_common's boxes: one wave with CELL + BOX (chain_demo_common's EXTRA)
+        return BX.arm("planar3")
     return IK.arm(name)
 
 

@@ -161,9 +161,10 @@ def test_precedence_on_the_device():
 
 # ---- (3) training step -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name,ranged,tagged", [("planar3", False, False), ("planar3", True, False), ("iiwa_like7", False, False),
-                                                ("iiwa_like7", True, False), ("iiwa_like7", True, True)])
+                                                ("iiwa_like7", True, False), ("iiwa_like7", True, True), ("planar3", False, True),
+                                                ("planar3", True, True), ("iiwa_like7", False, True)])
 def test_step_kernel_against_twin(name, ranged, tagged):
-    """The four SC x SCENE instantiations (self-collision pairs: iiwa_like7; scene ranges: `ranged`) and one tagged one. E = 100 envs
+    """The four SC x SCENE instantiations (self-collision pairs: iiwa_like7; scene ranges: `ranged`), each also tagged. E = 100 envs
     are put on the case's start poses and scenes by writing env_state, then stepped 40 times with the case's actions, records on.
     Every row's reward and done are held to the twin's rule at the pose the row was stepped to (float64 from the device's own
     previous joint values), outside the band; a row that ends in box contact alone carries -1000 / 1, its env starts a new episode

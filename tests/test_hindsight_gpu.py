@@ -198,7 +198,11 @@ def _step_models():
             "iiwa_like7-selfcol": (lambda: model_of("iiwa_like7", consider_autocollision=True), None),
             "iiwa_like7-ranges": (lambda: model_of("iiwa_like7"), (0.1, 0.1, 0.1, 0.05, 0.05, 0.05, 0.02)),
             "iiwa_like7-workcell": (lambda: K.arm("iiwa_like7")[0], None),
-            "planar3-workcell-ranges": (lambda: K.arm("planar3")[0], (0.1, 0.1, 0.0, 0.05, 0.05, 0.0, 0.02))}
+            "planar3-workcell-ranges": (lambda: K.arm("planar3")[0], (0.1, 0.1, 0.0, 0.05, 0.05, 0.0, 0.02)),
+            # the tagged instantiations the five above leave out: pairs with ranges, a workcell without pairs, all three together
+            "iiwa_like7-selfcol-ranges": (lambda: model_of("iiwa_like7", consider_autocollision=True), (0.1, 0.1, 0.1, 0.05, 0.05, 0.05, 0.02)),
+            "planar3-workcell": (lambda: K.arm("planar3")[0], None),
+            "iiwa_like7-workcell-ranges": (lambda: K.arm("iiwa_like7")[0], (0.1, 0.1, 0.1, 0.05, 0.05, 0.05, 0.02))}
 
 
 @pytest.mark.parametrize("E", [1, 64, 100])
