@@ -41,7 +41,7 @@ launches are the box instantiations, which test the floor and the spheres too.
       two unmeasured ones; the reachable and free shares; and the float64 host twin's seconds on the first 64 of the queries,
       with its time for all N EXTRAPOLATED from those 64 (it is linear in N) — that figure is not a measurement.
 
-  python benchmarks/chain_env_bench.py path [--envs 2048] [--launches 20] [--boxes]
+  python benchmarks/chain_env_bench.py path [--envs 2048] [--launches 20] [--boxes] [--certify | --roadmap M]
       collision-checked joint paths on --urdf with self-collision inside the --workcell cell (always on for this subcommand): N =
       --envs queries (default 2048 here) x C = 16 candidate vias x S = 256 samples. Microseconds per naf_chain_path_check launch
       between device events (median and minimum of `--launches` after two unmeasured ones), and in the same process the
@@ -54,6 +54,12 @@ launches are the box instantiations, which test the floor and the spheres too.
       alternating in the same process, with their ratio and the share of certified candidates; then the README's question with
       JointPathChecker(certify=True): the shares of 'straight' / 'via' / 'sampled' / 'blocked', the distribution of `refinements`
       and the seconds all rounds took together.
+
+      --roadmap M: instead, microseconds per naf_chain_edge_check launch beside the naf_chain_path_check launch, alternating in
+      the same process: the roadmaps (start, goal and M milestones, all their E edges) of as many of the N queries as give the
+      path launch's number of workgroups or fewer, at the same S = 256, with both launches' time per sample. Then the README's
+      question with and without JointPathChecker.check(roadmap=M): the outcome shares among the queries with a free goal pose,
+      how many 'blocked' ones the roadmap turned into 'roadmap', the node counts of those, and the seconds each call took.
 
   python benchmarks/chain_env_bench.py demo [--envs 2048] [--launches 20] [--boxes]
       planned joint paths as replay rows, same arm and cell: N = --envs demonstrations (default 2048 here) of T = 400 ticks.
@@ -366,6 +372,8 @@ def paths(a):
     checker.load(q_start, q_goal, obstacles, path_vias(model, q_start, q_goal, C, 0))
     if a.certify:
         return _paths_certified(a, checker, model, N, C, S, launches, init, rng, urdf)
+    if a.roadmap:
+        return _paths_roadmap(a, checker, model, N, C, S, launches, init, rng, urdf, q_start, q_goal, obstacles)
     fused = []
     for i in range(launches + 2):
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -475,6 +483,66 @@ def _paths_certified(a, checker, model, N, C, S, launches, init, rng, urdf):
                       "refinements": {str(k): int(v) for k, v in zip(*np.unique(found.refinements, return_counts=True))},
                       "samples": {str(k): int(v) for k, v in zip(*np.unique(found.samples, return_counts=True))},
                       "seconds_all_rounds": round(seconds, 3), "kernel_registers": regs}))
+
+
+def _paths_roadmap(a, checker, model, N, C, S, launches, init, rng, urdf, q_start, q_goal, obstacles):
+    import time
+    import numpy as np
+    import torch
+    from robotic_manipulator_rloa_amd import _lib
+    from robotic_manipulator_rloa_amd.engine import GoalPoseSolver
+    from robotic_manipulator_rloa_amd.environment.kinematic import roadmap_edges, roadmap_milestones, roadmap_nodes
+    M, V = a.roadmap, a.roadmap + 2
+    edges = roadmap_edges(V)
+    E = len(edges)
+    n = max(1, min(N, N * C // E))                             # roadmaps whose edges are about as many workgroups as the N C paths
+    nodes = roadmap_nodes(q_start, q_goal, roadmap_milestones(model, q_start, q_goal, M, 0))[:n]
+    checker.load_edges(nodes, edges, obstacles[:n])
+    times = {"check": [], "edges": []}
+    for i in range(launches + 2):                              # alternating, so that both see the same clocks
+        for name, launch in (("check", lambda: checker.launch(N, C, S, 0.0)), ("edges", lambda: checker.launch_edges(n, V, E, S, 0.0))):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            launch()
+            t1.record()
+            t1.synchronize()
+            if i >= 2:
+                times[name].append(1e3 * t0.elapsed_time(t1))
+    rec = checker.edge_out[:n * E]
+    T = 2000
+    targets = np.array([0.45, 0.3, 0.6]) + rng.uniform(-0.25, 0.25, (T, 3))
+    start, obstacle = np.tile(init, (T, 1)), np.tile([0.35, 0.2, 0.45], (T, 1))
+    goal = GoalPoseSolver(model, 0.06).solve(start, targets, obstacle)
+    ok = goal.free
+    found, seconds = {}, {}
+    for name, kw in (("one_via", {}), ("roadmap", {"roadmap": M})):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        found[name] = checker.check(start[ok], goal.joint_positions[ok], obstacle[ok], candidates=C, resolution=0.02, **kw)
+        seconds[name] = round(time.perf_counter() - t, 3)
+    kinds = ("straight", "via", "roadmap", "blocked", "start", "goal")
+    with_map = found["roadmap"]
+    rescued = with_map.outcome == "roadmap"
+    usage = json.load(open(_lib.USAGE_PATH)) if os.path.exists(_lib.USAGE_PATH) else {}
+    regs = {name: {q: v.get(q) for q in ("vgprs", "sgprs", "scratch_bytes_per_lane", "lds_bytes", "occupancy")}
+            for name, v in usage.items() if "chain_edge_" in name}
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    print(json.dumps({"arm": os.path.basename(urdf), "queries": N, "candidates": C, "samples": S, "self_pairs": len(model.self_pairs),
+                      "workcell_pairs": len(model.cell_pairs), "boxes": bool(a.boxes), "milestones": M, "roadmaps": n, "edges": E,
+                      "us_per_path_check_launch": {"median": round(med["check"], 1), "min": round(float(np.min(times["check"])), 1)},
+                      "us_per_edge_check_launch": {"median": round(med["edges"], 1), "min": round(float(np.min(times["edges"])), 1)},
+                      "ns_per_sample": {"path_check": round(1e3 * med["check"] / (N * C * S), 4),
+                                        "edge_check": round(1e3 * med["edges"] / (n * E * S), 4)},
+                      "free_edges_share": round(float((rec[:, 4] == 0).float().mean()), 4),
+                      "targets": T, "free_goal_poses": int(ok.sum()),
+                      "outcome_shares_among_free_goals": {name: {k: round(float(np.mean(p.outcome == k)), 4) for k in kinds}
+                                                          for name, p in found.items()},
+                      "blocked_without": int(np.sum(found["one_via"].outcome == "blocked")), "rescued": int(rescued.sum()),
+                      "node_counts": {str(k): int(v) for k, v in zip(*np.unique(with_map.n_nodes[rescued], return_counts=True))},
+                      "median_length_over_straight": (round(float(np.median(with_map.length[rescued] / with_map.straight_length[rescued])), 3)
+                                                      if rescued.any() else None),
+                      "roadmap_samples": {str(k): int(v) for k, v in zip(*np.unique(with_map.samples[rescued], return_counts=True))},
+                      "edge_launches": checker.edge_launches - (launches + 2), "seconds": seconds, "kernel_registers": regs}))
 
 
 def demo(a):
@@ -602,6 +670,8 @@ def main():
     ap.add_argument("--workcell", action="store_true", help="step / rollout: a floor and two spheres in the chain model")
     ap.add_argument("--boxes", action="store_true", help="step / rollout / path, with --workcell: three boxes beside the floor and the spheres")
     ap.add_argument("--certify", action="store_true", help="path: time naf_chain_path_certify beside naf_chain_path_check, and certify the README's paths")
+    ap.add_argument("--roadmap", type=int, default=0, metavar="M",
+                    help="path: time naf_chain_edge_check beside naf_chain_path_check, and answer the README's paths with M milestones")
     ap.add_argument("--trajectory", action="store_true", help="rollout: record the joint values of every frame")
     ap.add_argument("--arm", default="", help="rate: a fixture arm of tests/golden/urdf by name, --joints its joint count")
     ap.add_argument("--target-range", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))
@@ -609,6 +679,8 @@ def main():
     ap.add_argument("--hindsight", type=float, default=None, help="rate, gather: the share of rows replayed under a hindsight goal")
     ap.add_argument("--horizon", type=int, default=None, help="rate, gather: hindsight_horizon (rate: max_frames; gather: 400)")
     a = ap.parse_args()
+    if a.roadmap and a.certify:
+        ap.error("--roadmap and --certify are two measurements: roadmap edges are checked at their samples only")
     {"rate": rate, "kernels": kernels, "step": step, "rollout": rollout, "gather": gather, "ik": ik, "path": paths, "demo": demo}[a.what](a)
 
 

@@ -944,6 +944,33 @@ int naf_chain_path_certify(naf_chain_env_t* h, const float* q_start_dev, const f
                            const float* obstacles_dev, float obstacle_radius, const float* reach_dev, float guard, int N, int C, int S,
                            float margin, float* out, float* poses_out, void* stream);
 
+/* Roadmap edges (an addition within ABI 40): the sampled collision check of straight joint-space edges between indexed poses,
+ * batched over queries and edges: naf_chain_path_check with one leg. environment/kinematic.py (edge_pose, check_joint_edge) is the
+ * float64 statement; roadmap_milestones, roadmap_edges and roadmap_search there are what the host builds around it. SAMPLED, as
+ * naf_chain_path_check: a verdict holds at the S poses and says nothing between them; out[6] reports how far apart they are.
+ *   nodes_dev   : [N][V][A] (DEVICE): the V poses of each query's roadmap, V in 2 .. 64.
+ *   edges_dev   : [E][2] int32 (DEVICE): edge e joins nodes edges[e][0] and edges[e][1] of EVERY query of the launch, E in
+ *                 1 .. V (V - 1) / 2. The caller validates 0 <= i < j < V for every edge before the upload.
+ *   An item is (query n, edge e), index n E + e: the edge a -> b, a = nodes_dev[n][i], b = nodes_dev[n][j], in the scene
+ *   obstacles_dev[n] with obstacle_radius. S is a multiple of 64 in 64 .. 2048.
+ *   the poses   : sample i lies at f = (float)i / (float)(S - 1), both ends included; q_m = fmaf(f, b_m - a_m, a_m). No limits are
+ *                 applied and nothing wraps: the nodes lie inside the limits.
+ *   per sample  : the three clearances of naf_chain_path_check, by the same walk. A sample is blocked iff one is < margin.
+ *   out         : [N E][NAF_CHAIN_EDGE_FLOATS] (DEVICE) = [0 .. 2] the minima over the samples of the three clearances (the obstacle's
+ *                 minus obstacle_radius; +inf without pairs / without a workcell) | [3] the index of the first blocked sample, -1:
+ *                 none | [4] how many are blocked | [5] L = max_m |b_m - a_m| (float32) | [6] L / (float)(S - 1), the sample step |
+ *                 [7] 0.
+ *   poses_out   : NULL, or DEVICE [N E][S][A]: every sample's pose (for tests).
+ * One workgroup per item, a lane per sample of a pass, S / lanes passes, one reduction by shuffles at the end, no atomics. With
+ * pairs the launch has the probe's shape (the handle's lanes and waves, its LDS). An item's record does not depend on where in a
+ * launch, or in edges_dev, it lies. NAF_ERR_ARG, and no launch, for a null pointer other than poses_out, N < 1, V outside 2 .. 64,
+ * E outside 1 .. V (V - 1) / 2, N E > 2^30, S no multiple of 64 in 64 .. 2048, a margin or radius that is not finite, or a negative
+ * radius. */
+#define NAF_CHAIN_EDGE_FLOATS 8
+int naf_chain_edge_check(naf_chain_env_t* h, const float* nodes_dev, const int32_t* edges_dev, const float* obstacles_dev,
+                         float obstacle_radius, int N, int V, int E, int S, float margin, float* out, float* poses_out,
+                         void* stream);
+
 /* Demonstrations (an addition within ABI 40): N planned joint paths turned into the replay rows of the episodes that follow them
  * open loop, one launch. environment/kinematic.py (demonstration_plan, demonstration_rows_host) is the float64 statement.
  *   Demonstration n starts at q_start_dev[n] clamped into the limits (p_0) in the scene targets_dev[n] / obstacles_dev[n] with

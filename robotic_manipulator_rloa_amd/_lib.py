@@ -274,6 +274,7 @@ _PROTOS = {
     "naf_chain_path_check": [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _f, _vp, _vp, _vp],
     "naf_chain_path_certify": [_vp, _vp, _vp, _vp, _vp, _f, _vp, _f, _i, _i, _i, _f, _vp, _vp, _vp],
     "naf_chain_demo_rows": [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _i, _vp, _vp, _vp],
+    "naf_chain_edge_check": [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _f, _vp, _vp, _vp],
 }
 _RESTYPES = {"naf_hip_arch": C.c_char_p}
 EXPORTED_SYMBOLS = tuple(_PROTOS)

@@ -1550,6 +1550,102 @@ extern "C" int naf_chain_path_certify(naf_chain_env_t* h, const float* q_start_d
     });
 }
 
+// ---- roadmap edges: the sampled collision check of straight joint-space edges (include/naf_hip.h, "Roadmap edges") ---------------
+// The path kernel with one leg and indexed end poses. One workgroup per (query n, edge e); the edge's two nodes are read from
+// edges[e] (the same list for every query of the launch) and their poses from nodes[n] — uniform loads. A lane is one sample of a
+// pass: f = (float)i / (float)(S - 1), both ends included, and the walk forms fmaf(f, b_m - a_m, a_m) when it reaches joint m.
+// No pose record, no per-lane array, nothing in scratch, no atomics. SC is the probe's shape, as in chain_path_check_kernel: wave
+// 0 walks, stages the end points as [segment][6][lane], and every wave joins the pair phase of every pass; without pairs a
+// workgroup is one wave with no barrier and no LDS. One butterfly of shuffles at the end; lane 0 writes the record.
+template <bool SC, class... Cell>
+__global__ void __launch_bounds__(SC ? 64 * CH_MAX_WAVES : 64)
+chain_edge_check_kernel(const float* __restrict__ model, const float* __restrict__ nodes, const int32_t* __restrict__ edges,
+                        const float* __restrict__ obstacles, float orad, int V, int E, int S, int A, int n_seg, int n_pairs, int lanes,
+                        float margin, float* __restrict__ out, float* __restrict__ poses_out, const Cell... cell) {
+    constexpr bool CELL = (std::is_same_v<Cell, ChainCell> || ... || false);
+    constexpr bool BOX = (std::is_same_v<Cell, ChainBox> || ... || false);
+    extern __shared__ __attribute__((aligned(16))) float ch_lds[];
+    const int64_t item = blockIdx.x;
+    const int64_t n = item / E;
+    const int e = (int)(item - n * E);
+    // (the host validated 0 <= i < j < V for every edge before the upload; the clamp keeps a stray index inside the query's nodes)
+    const int ni = min(max(edges[2 * e], 0), V - 1), nj = min(max(edges[2 * e + 1], 0), V - 1);
+    const float* a = nodes + (n * V + ni) * A;
+    const float* b = nodes + (n * V + nj) * A;
+    const float ox = obstacles[n * 3], oy = obstacles[n * 3 + 1], oz = obstacles[n * 3 + 2];
+    const int lane = threadIdx.x & 63;
+    const bool active = lane < lanes;
+    const bool walker = active && threadIdx.x < 64;
+    const float last = (float)(S - 1);
+    float min_clear = INFINITY, min_self = INFINITY, min_cell = INFINITY;
+    int first = INT_MAX, count = 0;
+    for (int base = 0; base < S; base += lanes) {      // (uniform: every thread takes every pass)
+        const int i = base + lane;
+        const float f = (float)i / last;
+        float ee[3];
+        WalkAux aux = {SC ? ch_lds + lane : nullptr, lanes, INFINITY, INFINITY, nullptr, INFINITY, INFINITY};
+        if (walker) {
+            float* rec = poses_out ? poses_out + (item * S + i) * A : nullptr;
+            chain_walk_at<SC, true, false, true, CELL, BOX>(
+                model, A, n_seg,
+                [=](int m) {
+                    const float lo = a[m];
+                    const float q = fmaf(f, b[m] - lo, lo);
+                    if (rec) rec[m] = q;
+                    return q;
+                },
+                ox, oy, oz, orad, nullptr, nullptr, ee, aux);
+        }
+        float self_clear = INFINITY;
+        if constexpr (SC) self_clear = self_clearance_phase<false>(model, A, n_seg, n_pairs, ch_lds, lanes, lane, active, nullptr, nullptr);
+        if (walker) {
+            const float clear = aux.clear - orad;
+            const bool blocked = clear < margin || self_clear < margin || (CELL && aux.cell < margin);
+            min_clear = fminf(min_clear, clear);
+            min_self = fminf(min_self, self_clear);
+            if constexpr (CELL) min_cell = fminf(min_cell, aux.cell);
+            first = blocked && i < first ? i : first;
+            count += blocked ? 1 : 0;
+        }
+    }
+    if (threadIdx.x >= 64) return;      // (behind the last barrier; wave 0 is whole: the lanes that walked nothing hold the identities)
+    for (int off = 32; off > 0; off >>= 1) {
+        min_clear = fminf(min_clear, __shfl_xor(min_clear, off));
+        min_self = fminf(min_self, __shfl_xor(min_self, off));
+        min_cell = fminf(min_cell, __shfl_xor(min_cell, off));
+        first = min(first, __shfl_xor(first, off));
+        count += __shfl_xor(count, off);
+    }
+    if (threadIdx.x != 0) return;
+    float len = 0.f;
+    for (int m = 0; m < A; ++m) len = fmaxf(len, fabsf(b[m] - a[m]));
+    float* o = out + item * NAF_CHAIN_EDGE_FLOATS;
+    o[0] = min_clear;
+    o[1] = min_self;
+    o[2] = min_cell;
+    o[3] = first == INT_MAX ? -1.f : (float)first;
+    o[4] = (float)count;
+    o[5] = len;
+    o[6] = len / last;
+    o[7] = 0.f;
+}
+
+// One workgroup per (query, edge); the SC kernels' dynamic LDS is the probe's.
+extern "C" int naf_chain_edge_check(naf_chain_env_t* h, const float* nodes_dev, const int32_t* edges_dev, const float* obstacles_dev,
+                                    float obstacle_radius, int N, int V, int E, int S, float margin, float* out, float* poses_out,
+                                    void* stream) {
+    if (!h || !nodes_dev || !edges_dev || !obstacles_dev || !out) return NAF_ERR_ARG;
+    if (N < 1 || V < 2 || V > 64 || E < 1 || E > V * (V - 1) / 2 || (int64_t)N * E > (int64_t)1 << 30) return NAF_ERR_ARG;
+    if (S < 64 || S > 2048 || S % 64 != 0) return NAF_ERR_ARG;
+    if (!std::isfinite(margin) || !std::isfinite(obstacle_radius) || obstacle_radius < 0.f) return NAF_ERR_ARG;
+    return ch_with_pack(h, [&](auto sc, auto... cell) {
+        const ChShape w = ch_shape<sc()>(h, h->waves);
+        return ch_launch_raising<chain_edge_check_kernel<sc(), decltype(cell)...>>(
+            CH_MAX_DYN_LDS, (unsigned)((int64_t)N * E), w, stream, h->model_dev, nodes_dev, edges_dev, obstacles_dev, obstacle_radius,
+            V, E, S, h->A, h->n_seg, w.n_pairs, w.lanes, margin, out, poses_out, cell...);
+    });
+}
+
 // ---- demonstrations: planned joint paths as replay rows (include/naf_hip.h, "Demonstrations") -------------------------------------
 // One workgroup per demonstration; a lane is one POSE of a pass: lane t walks p_t once with the walk that writes an observation,
 // straight into row t's `state`, copies it into row t - 1's `next_state` and writes row t - 1's action, reward, done and zero tail

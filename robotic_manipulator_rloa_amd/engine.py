@@ -31,9 +31,9 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
-from .environment.kinematic import (PATH_CERT_FLOATS, PATH_CHUNK, PATH_FLOATS, GoalPoses, JointPaths, certificate_guard,
-                                    certify_rounds, gather_certified_paths, gather_goal_poses, gather_joint_paths, ik_seeds,
-                                    path_chunks, path_leg_lengths, path_vias, reach_table)
+from .environment.kinematic import (EDGE_FLOATS, PATH_CERT_FLOATS, PATH_CHUNK, PATH_FLOATS, ROADMAP_MAX, GoalPoses, JointPaths,
+                                    certificate_guard, certify_rounds, gather_certified_paths, gather_goal_poses, gather_joint_paths,
+                                    ik_seeds, path_chunks, path_leg_lengths, path_vias, reach_table, roadmap_round, roadmap_size_ok)
 from .learner import ActPath, Learner
 from .presets import ROBOT_PRESETS, device_env_preset
 from .utils.replay_buffer import ReplayBuffer
@@ -1266,7 +1266,11 @@ class JointPathChecker(_ChainHandle):
     candidate, with the model's reach table uploaded once; check() then runs the refinement rounds over the open queries
     (environment.kinematic.certify_rounds) and fills JointPaths' last three fields. The certifying launch keeps the handle's lanes
     and adds a reduction row and three small tables to its LDS: an arm with pairs whose rows only just fit a workgroup is refused
-    (NAF_CHAIN_ERR_LDS) where the sampled check runs; joint_paths_host(certify=True) answers it."""
+    (NAF_CHAIN_ERR_LDS) where the sampled check runs; joint_paths_host(certify=True) answers it.
+    check(roadmap=M): behind the one-via chunks, the queries that ended 'blocked' get a roadmap of M milestones each
+    (environment.kinematic.roadmap_round): per chunk of whole queries ONE naf_chain_edge_check launch over queries x E edges, S
+    samples each, within the same budget; the node, edge and record buffers are allocated on the first such call. The records — a
+    few KB per blocked query — are downloaded and roadmap_search runs on the host, as the one-via selection does."""
 
     def __init__(self, chain, obstacle_radius: float = 0.06, chunk: Optional[int] = None, device=None, certify: bool = False):
         _lib.require_gpu()
@@ -1286,6 +1290,39 @@ class JointPathChecker(_ChainHandle):
             self.reach = torch.from_numpy(reach_table(chain)).to(self.dev).contiguous()
             self.guard = certificate_guard(chain)
             self.out_cert = torch.zeros(K, PATH_CERT_FLOATS, **f32)
+        self.edge_nodes = self.edge_list = self.edge_out = self.edge_obstacles = None
+        self.edge_launches = 0
+
+    def _edge_buffers(self, n: int, V: int, E: int) -> None:
+        """room for n queries of V nodes and E edges: allocated on the first roadmap call, and again only to grow"""
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        if self.edge_nodes is None or self.edge_nodes.numel() < n * V * self.A:
+            self.edge_nodes = torch.zeros(n * V * self.A, **f32)
+        if self.edge_obstacles is None or len(self.edge_obstacles) < n:
+            self.edge_obstacles = torch.zeros(n, 3, **f32)
+        if self.edge_list is None or len(self.edge_list) < E:
+            self.edge_list = torch.zeros(E, 2, dtype=torch.int32, device=self.dev)
+        if self.edge_out is None or len(self.edge_out) < n * E:
+            self.edge_out = torch.zeros(n * E, EDGE_FLOATS, **f32)
+
+    def load_edges(self, nodes, edges, obstacles) -> None:
+        """a chunk's roadmaps into the buffers: nodes[n][V][A] (float32), edges[E][2] (int32, shared by the chunk's queries),
+        obstacles[n][3]. Every edge is validated here, before the upload: 0 <= i < j < V."""
+        nodes, edges = np.ascontiguousarray(nodes, np.float32), np.ascontiguousarray(edges, np.int32).reshape(-1, 2)
+        n, V = nodes.shape[:2]
+        if len(edges) < 1 or not (np.all(edges[:, 0] >= 0) and np.all(edges[:, 0] < edges[:, 1]) and np.all(edges[:, 1] < V)):
+            raise ValueError(f"JointPathChecker: every roadmap edge is (i, j) with 0 <= i < j < {V}")
+        self._edge_buffers(n, V, len(edges))
+        self.edge_nodes[:nodes.size].copy_(torch.from_numpy(nodes.reshape(-1)))
+        self.edge_list[:len(edges)].copy_(torch.from_numpy(edges))
+        self.edge_obstacles[:n].copy_(torch.from_numpy(np.ascontiguousarray(obstacles, np.float32).reshape(n, 3)))
+
+    def launch_edges(self, n: int, V: int, E: int, S: int, margin: float) -> None:
+        """the edge launch of one chunk of n roadmaps already in the buffers, on the current stream"""
+        check(self.lib.naf_chain_edge_check(self._chain_env, ptr(self.edge_nodes), ptr(self.edge_list), ptr(self.edge_obstacles),
+                                            self.obstacle_radius, n, V, E, S, margin, ptr(self.edge_out), None, stream_ptr()),
+              "chain_edge_check")
+        self.edge_launches += 1
 
     def launch(self, n: int, C: int, S: int, margin: float) -> None:
         """the launch of one chunk of n queries x C candidates already in the buffers, on the current stream"""
@@ -1308,8 +1345,13 @@ class JointPathChecker(_ChainHandle):
         self.vias[:n * C].copy_(torch.from_numpy(np.ascontiguousarray(vias, np.float32).reshape(n * C, self.A)))
 
     def check(self, q_start, q_goal, obstacles, candidates: int = 16, resolution: float = 0.02, margin: float = 0.0,
-              seed: int = 0) -> JointPaths:
-        """q_start[N][A], q_goal[N][A] (action order), obstacles[N][3] -> JointPaths of numpy arrays (float32 where the device's)."""
+              seed: int = 0, roadmap: int = 0) -> JointPaths:
+        """q_start[N][A], q_goal[N][A] (action order), obstacles[N][3] -> JointPaths of numpy arrays (float32 where the device's).
+        roadmap = M in 1 .. 62: the queries that end 'blocked' get a roadmap of M milestones; not with a certifying checker."""
+        if not roadmap_size_ok(roadmap):
+            raise ValueError(f"JointPathChecker: roadmap is a number of milestones from 0 to {ROADMAP_MAX}: got {roadmap!r}")
+        if roadmap and self.certify:
+            raise ValueError("JointPathChecker: roadmap edges are checked at their samples only, so not by a certifying checker")
         A, C = self.A, int(candidates)
         q_start = np.ascontiguousarray(q_start, np.float32).reshape(-1, A)
         N = len(q_start)
@@ -1338,7 +1380,19 @@ class JointPathChecker(_ChainHandle):
             self.launch(n, C, S, margin)
             records[sl] = self.out[:n * C].cpu().numpy().reshape(n, C, PATH_FLOATS)
             samples[sl] = S
-        return gather_joint_paths(records, vias, q_start, q_goal, samples)
+        base = gather_joint_paths(records, vias, q_start, q_goal, samples)
+        if not roadmap:
+            return base
+
+        def run(queries, nodes, edges, S):
+            n, V, E = len(nodes), nodes.shape[1], len(edges)
+            if n * E * S > self.chunk:
+                raise ValueError(f"JointPathChecker: one query's {E} roadmap edges at {S} samples exceed the chunk of {self.chunk}")
+            self.load_edges(nodes, edges, obstacles[queries])
+            self.launch_edges(n, V, E, S, margin)
+            return self.edge_out[:n * E].cpu().numpy().reshape(n, E, EDGE_FLOATS)
+
+        return roadmap_round(base, self.chain, int(roadmap), seed, resolution, self.chunk, run, np.float32)
 
 
 def demonstration_chunks(rows_of, budget: int) -> List[Tuple[int, int, int]]:

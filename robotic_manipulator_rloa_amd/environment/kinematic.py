@@ -658,14 +658,12 @@ def select_joint_path(records) -> Tuple[np.ndarray, np.ndarray]:
     return outcome, np.where((outcome == "straight") | (outcome == "via"), best, -1)
 
 
-class JointPaths(NamedTuple):
-    """Collision-checked joint paths of N queries (ManipulatorFramework.plan_joint_paths). Without `certify` the check is SAMPLED: a
-    free verdict holds at the `samples` poses of the path, `sample_step` apart in the joints' max-norm, and nothing certifies the
-    path between them. With `certify` the last three fields are filled: where `certified`, no pose of the polyline, between the
-    samples included, brings a capsule closer than the margin to anything the samples are tested against (certify_joint_path)."""
+class _JointPathFields(NamedTuple):
+    """the sixteen members of JointPaths' tuple"""
     outcome: np.ndarray                 # [N] str: 'straight' | 'via' | 'blocked' | 'start' | 'goal' (select_joint_path); with
                                         # certify 'straight' and 'via' name a certified path, and 'sampled' one that is free at
-                                        # its samples only (select_certified_path)
+                                        # its samples only (select_certified_path); with roadmap 'roadmap' names a polyline
+                                        # over the query's roadmap (roadmap_search)
     candidate: np.ndarray               # [N] int: the chosen candidate, 0 = the straight line; -1: no free path
     via: np.ndarray                     # [N][A]: its via pose, entry m = involved_joints[m]; NaN: no free path
     length: np.ndarray                  # [N]: its length L1 + L2 in the joints' max-norm ('straight': straight_length); NaN: none
@@ -684,10 +682,31 @@ class JointPaths(NamedTuple):
                                                   # reported); certified iff >= margin
     refinements: Optional[np.ndarray] = None      # [N] int: how often the query's samples were doubled
 
+
+
+class JointPaths(_JointPathFields):
+    """Collision-checked joint paths of N queries (ManipulatorFramework.plan_joint_paths). Without `certify` the check is SAMPLED: a
+    free verdict holds at the `samples` poses of the path, `sample_step` apart in the joints' max-norm, and nothing certifies the
+    path between them. With `certify` the last three fields are filled: where `certified`, no pose of the polyline, between the
+    samples included, brings a capsule closer than the margin to anything the samples are tested against (certify_joint_path).
+    With `roadmap` the three attributes below are filled too, and the outcome 'roadmap' names a polyline over the query's roadmap
+    (roadmap_search): its candidate is -1 and its via NaN, so whatever reads start -> via -> goal sees a query without such a path;
+    length, the three minima, sample_step and samples are its edges'. They are attributes behind the tuple, not members of it: the
+    tuple's sixteen fields are what they were, and every loop over them runs as before. _replace keeps them."""
+    nodes: Optional[np.ndarray] = None               # [N][K][A]: the polyline start .. goal of a 'roadmap' query, NaN-padded; K is
+                                                     # the largest node count of the call
+    n_nodes: Optional[np.ndarray] = None             # [N] int: its node count, 0 where there is no roadmap path
+    roadmap_free_edges: Optional[np.ndarray] = None  # [N] int: how many of the roadmap's E edges were free; -1: no roadmap was built
+
+    def _replace(self, **kw):
+        out = super()._replace(**kw)
+        out.nodes, out.n_nodes, out.roadmap_free_edges = self.nodes, self.n_nodes, self.roadmap_free_edges
+        return out
+
     def waypoints(self, n: int) -> np.ndarray:
         """[N][n][A]: n >= 2 poses along each query's path, start and goal included, uniform in the path's length (max-norm):
-        the first leg takes the share L1 / (L1 + L2) of them. Resampled on the host, not the checked samples. NaN rows where
-        there is no free path."""
+        the first leg takes the share L1 / (L1 + L2) of them, and an edge of a 'roadmap' polyline its length's share likewise.
+        Resampled on the host, not the checked samples. NaN rows where there is no free path."""
         if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 2:
             raise ValueError(f"waypoints(n): n is a number of poses, at least 2: got {n!r}")
         a, b, via = np.asarray(self.start, float), np.asarray(self.goal, float), np.asarray(self.via, float)
@@ -702,7 +721,10 @@ class JointPaths(NamedTuple):
         leg1 = a[:, None, :] + f1[..., None] * (via - a)[:, None, :]
         leg2 = np.where((f2 >= 1.0)[..., None], b[:, None, :], via[:, None, :] + f2[..., None] * (b - via)[:, None, :])
         out = np.where(first, leg1, leg2)
-        return np.where((np.asarray(self.candidate) >= 0)[:, None, None], out, np.nan)
+        out = np.where((np.asarray(self.candidate) >= 0)[:, None, None], out, np.nan)
+        for q in np.nonzero(np.asarray(self.n_nodes) >= 2)[0] if self.n_nodes is not None else ():
+            out[q] = polyline_waypoints(np.asarray(self.nodes, float)[q, :int(self.n_nodes[q])], n)
+        return out
 
 
 def gather_joint_paths(records, vias, q_start, q_goal, samples) -> JointPaths:
@@ -728,10 +750,16 @@ def path_leg_lengths(vias, q_start, q_goal) -> np.ndarray:
 
 
 def joint_paths_host(twin: KinematicEnvironment, q_start, q_goal, obstacles, candidates: int = 16, resolution: float = 0.02,
-                     margin: float = 0.0, seed: int = 0, chunk: int = PATH_CHUNK, certify: bool = False) -> JointPaths:
+                     margin: float = 0.0, seed: int = 0, chunk: int = PATH_CHUNK, certify: bool = False, roadmap: int = 0) -> JointPaths:
     """plan_joint_paths through the twin alone, under the device's rule and on the values the device is given: start and goal
     poses, vias and obstacles rounded to float32, the poses and the clearances in float64, the lengths in float32. Chunks and
-    their S are the device's (path_chunks). certify: certify_joint_path's records and the device's rounds (certify_rounds)."""
+    their S are the device's (path_chunks). certify: certify_joint_path's records and the device's rounds (certify_rounds).
+    roadmap = M > 0: the 'blocked' queries get a roadmap of M milestones (roadmap_round: the device's chunks and S, check_joint_edge's
+    records); roadmap edges are checked at their samples only, so not together with certify."""
+    if not roadmap_size_ok(roadmap):
+        raise ValueError(f"roadmap is a number of milestones from 0 to {ROADMAP_MAX}: got {roadmap!r}")
+    if roadmap and certify:
+        raise ValueError("roadmap edges are checked at their samples only: roadmap > 0 does not go with certify=True")
     r32 = lambda a: np.asarray(a, np.float64).astype(np.float32).astype(np.float64)      # noqa: E731
     q_start, q_goal, obstacles = r32(q_start), r32(q_goal), r32(obstacles)
     N, C = len(q_start), int(candidates)
@@ -758,7 +786,250 @@ def joint_paths_host(twin: KinematicEnvironment, q_start, q_goal, obstacles, can
             sl = slice(k, min(k + block, first + n))
             records[sl] = check_joint_path(twin, q_start[sl, None, :], vias[sl].astype(np.float64), q_goal[sl, None, :],
                                            obstacles[sl, None, :], S, margin)
-    return gather_joint_paths(records, vias, q_start, q_goal, samples)
+    base = gather_joint_paths(records, vias, q_start, q_goal, samples)
+    if not roadmap:
+        return base
+
+    def run(queries, nodes, edges, S):
+        ob, nodes = obstacles[queries], nodes.astype(np.float64)
+        out = np.empty((len(nodes), len(edges), EDGE_FLOATS))
+        block = max(1, 65536 // S)                            # edges at a time, as above
+        for n in range(len(nodes)):
+            for k in range(0, len(edges), block):
+                e = edges[k:k + block]
+                out[n, k:k + block] = check_joint_edge(twin, nodes[n, e[:, 0]], nodes[n, e[:, 1]], ob[n], S, margin)
+        return out
+
+    return roadmap_round(base, twin.model, roadmap, seed, resolution, chunk, run, np.float64)
+
+
+# ---- roadmaps: several straight edges where one via is blocked (include/naf_hip.h, "Roadmap edges") --------------------------------
+ROADMAP_MAX = 62                      # milestones per query: V = M + 2 nodes, at most 64
+EDGE_FLOATS = 8                       # NAF_CHAIN_EDGE_FLOATS
+ROADMAP_STREAM = 0x726F6164           # what the milestones' Generator is seeded with beside `seed`: not path_vias' draws again
+
+
+def roadmap_size_ok(M) -> bool:
+    return isinstance(M, (int, np.integer)) and not isinstance(M, bool) and 0 <= M <= ROADMAP_MAX
+
+
+def roadmap_milestones(model: ChainModel, q_start, q_goal, M: int, seed: int) -> np.ndarray:
+    """[N][M][A] float32: the milestones of every query's roadmap, from the poses as float32 holds them and ONE
+    np.random.default_rng([seed, ROADMAP_STREAM]).random((N, M, A)) call — drawn for all N queries of the call, whichever of them
+    get a roadmap, so that a query's milestones do not depend on the others' outcomes. The first ceil(M / 2) are "near": path_vias'
+    rule, mid + (2u - 1) w_k with w_k = 0.5 2^(k mod 3) max(D, 0.5) around the midpoint of the straight line. The rest are uniform
+    inside the limits, lo + u (hi - lo), +-pi for a revolute joint without limits. Clipped into the limits of limited joints as the
+    device holds them. A prismatic joint without limits has no range to draw from and is refused by name."""
+    for m, j in enumerate(model.joints):
+        if j.type == PRISMATIC and not j.limited:
+            raise ValueError(f"roadmap_milestones: joint {m} (involved_joints[{m}]) is a prismatic joint without limits: there is no "
+                             f"range to draw its milestones from")
+    a = np.asarray(q_start, np.float32).astype(np.float64).reshape(-1, model.A)
+    b = np.asarray(q_goal, np.float32).astype(np.float64).reshape(-1, model.A)
+    N, M = len(a), int(M)
+    near = (M + 1) // 2
+    u = np.random.default_rng([int(seed), ROADMAP_STREAM]).random((N, M, model.A))
+    out = np.empty((N, M, model.A))
+    mid, D = 0.5 * (a + b), np.max(np.abs(b - a), axis=-1)
+    w = 0.5 * 2.0 ** (np.arange(near) % 3)[None, :, None] * np.maximum(D, 0.5)[:, None, None]
+    out[:, :near] = mid[:, None, :] + (2.0 * u[:, :near] - 1.0) * w
+    lo = np.array([j.lower if j.limited else -np.pi for j in model.joints])
+    hi = np.array([j.upper if j.limited else np.pi for j in model.joints])
+    out[:, near:] = lo + u[:, near:] * (hi - lo)
+    lo32 = np.array([j.lower if j.limited else -np.inf for j in model.joints]).astype(np.float32)
+    hi32 = np.array([j.upper if j.limited else np.inf for j in model.joints]).astype(np.float32)
+    return np.minimum(np.maximum(out.astype(np.float32), lo32), hi32)
+
+
+def edge_pose(a, b, i, S: int) -> np.ndarray:
+    """Sample i of the S poses of the straight joint-space edge a -> b, in float64; a, b [..., A] and i [...] broadcast. Sample i
+    lies at f = i / (S - 1), both ends included: q_m = a_m + f (b_m - a_m), and b itself at f = 1. No limits are applied and
+    nothing wraps."""
+    a, b = np.asarray(a, float), np.asarray(b, float)
+    f = (np.asarray(i) / (int(S) - 1))[..., None]
+    return np.where(f == 1.0, b, a + f * (b - a))
+
+
+def check_joint_edge(twin: KinematicEnvironment, a, b, obstacle, S: int, margin: float = 0.0) -> np.ndarray:
+    """[..., EDGE_FLOATS] float64: the record of the edges a[..., A] -> b[..., A] in the scenes obstacle[..., 3] (all broadcast),
+    sampled at the S poses of edge_pose: [0] [1] [2] the minima over the samples of the obstacle clearance (the obstacle radius
+    subtracted), the self-clearance and the workcell clearance (+inf where the model has none) | [3] the index of the first
+    blocked sample, -1: none | [4] how many are blocked | [5] L = joint_distance32(b, a), in float32 | [6] the sample step
+    L / (S - 1), in float32 | [7] 0. A sample is blocked iff one of its three clearances is < margin. SAMPLED, as check_joint_path."""
+    if not path_samples_ok(S):
+        raise ValueError(f"S is a multiple of 64 from {PATH_SAMPLES_MIN} to {PATH_SAMPLES_MAX}: got {S!r}")
+    a, b = np.broadcast_arrays(np.asarray(a, float), np.asarray(b, float))
+    lead = a.shape[:-1]
+    obstacle = np.broadcast_to(np.asarray(obstacle, float), lead + (3,))
+    q = edge_pose(a[..., None, :], b[..., None, :], np.arange(S), S)
+    clear = twin.clearance(q, obstacle[..., None, :]) - twin.obstacle_radius
+    self_clear, cell_clear = twin.self_clearance(q) + np.zeros(clear.shape), twin.cell_clearance(q) + np.zeros(clear.shape)
+    blocked = (clear < margin) | (self_clear < margin) | (cell_clear < margin)
+    length = joint_distance32(b, a)
+    out = np.empty(lead + (EDGE_FLOATS,))
+    out[..., 0], out[..., 1], out[..., 2] = clear.min(axis=-1), self_clear.min(axis=-1), cell_clear.min(axis=-1)
+    out[..., 3] = np.where(blocked.any(axis=-1), np.argmax(blocked, axis=-1), -1)
+    out[..., 4] = blocked.sum(axis=-1)
+    out[..., 5] = length
+    out[..., 6] = length / np.float32(S - 1)
+    out[..., 7] = 0.0
+    return out
+
+
+def roadmap_edges(V: int) -> np.ndarray:
+    """[E][2] int32, E = V (V - 1) / 2: every pair i < j of the V nodes in np.triu_indices(V, 1) order; edge 0 = (0, 1) is the
+    straight line start -> goal"""
+    return np.stack(np.triu_indices(int(V), 1), axis=1).astype(np.int32)
+
+
+def edge_samples(lengths, resolution: float) -> int:
+    """S for edges of the given max-norm lengths: the smallest multiple of 64 whose sample step L / (S - 1) is <= resolution on the
+    longest of them, capped at PATH_SAMPLES_MAX (the step is then what it is)."""
+    longest = float(np.max(lengths)) if np.size(lengths) else 0.0
+    for S in range(PATH_SAMPLES_MIN, PATH_SAMPLES_MAX, 64):
+        if longest / (S - 1) <= resolution:
+            return S
+    return PATH_SAMPLES_MAX
+
+
+def roadmap_chunks(edge_lengths, resolution: float, budget: int = PATH_CHUNK) -> List[Tuple[int, int, int]]:
+    """[(first query, queries, S)] over edge_lengths[N][E]: path_chunks' rule with edge_samples — consecutive queries share a
+    chunk and its S while queries x E x S stays within `budget` edge-samples; a chunk holds at least one query."""
+    lengths = np.asarray(edge_lengths, float).reshape(len(edge_lengths), -1)
+    longest, E = np.max(lengths, axis=1), lengths.shape[1]
+    out, first, N = [], 0, len(longest)
+    while first < N:
+        n, S = 1, edge_samples(longest[first], resolution)
+        while first + n < N:
+            S2 = max(S, edge_samples(longest[first + n], resolution))
+            if (n + 1) * E * S2 > budget:
+                break
+            n, S = n + 1, S2
+        out.append((first, n, S))
+        first += n
+    return out
+
+
+def roadmap_nodes(q_start, q_goal, milestones) -> np.ndarray:
+    """[N][M + 2][A] float32: node 0 the start pose, node 1 the goal pose, nodes 2 .. the milestones"""
+    a, b = np.asarray(q_start, np.float32), np.asarray(q_goal, np.float32)
+    return np.concatenate([a[:, None, :], b[:, None, :], np.asarray(milestones, np.float32)], axis=1)
+
+
+def roadmap_edge_lengths(nodes, edges) -> np.ndarray:
+    """[N][E] float32: joint_distance32 of every edge of every query's nodes[N][V][A]"""
+    nodes, edges = np.asarray(nodes, np.float32), np.asarray(edges)
+    return joint_distance32(nodes[:, edges[:, 1]], nodes[:, edges[:, 0]])
+
+
+def roadmap_search(records, edges, V: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(n_nodes[N] int, node_index[N][V] int, length[N] float32) from records[N][E][EDGE_FLOATS] of the edges[E][2] over V nodes:
+    the shortest path from node 0 to node 1 over the usable edges. An edge is usable iff [4] == 0; its weight is [5] as float32,
+    the same in both directions. Bellman-Ford in Jacobi rounds in float32: d = 0 at node 0 and +inf elsewhere; a round forms
+    d[i] + w[i][j] for all i from the PREVIOUS round's d, the lowest i among equal minima is the predecessor, and a node changes
+    only on a strict improvement; the rounds end when nothing changes, after at most V - 1. The path is read back from node 1 along
+    the predecessors: node_index holds it from 0 to 1, -1 behind it, n_nodes its node count (0: node 1 was not reached) and length
+    the float32 sum of its edges' weights in path order from node 0 (NaN: none). No polyline is shorter than a free straight line
+    (the triangle inequality), and in the max-norm many are exactly as long, so that a float32 sum may come out an ulp below it: a
+    usable edge (0, 1) wins outright, select_joint_path's refinement. Every comparison is made on the values as given, so the
+    device's float32 records and the twin's are searched by the same rule."""
+    rec, edges, V = np.asarray(records), np.asarray(edges, np.int64).reshape(-1, 2), int(V)
+    N = len(rec)
+    if edges.size and not (np.all(edges[:, 0] >= 0) and np.all(edges[:, 0] < edges[:, 1]) and np.all(edges[:, 1] < V)):
+        raise ValueError(f"roadmap_search: every edge is (i, j) with 0 <= i < j < {V}")
+    inf = np.float32(np.inf)
+    w = np.full((N, V, V), inf, np.float32)
+    weight = np.where(rec[..., 4] == 0, rec[..., 5].astype(np.float32), inf)
+    w[:, edges[:, 0], edges[:, 1]] = weight
+    w[:, edges[:, 1], edges[:, 0]] = weight
+    d = np.full((N, V), inf, np.float32)
+    d[:, 0] = 0.0
+    pred = np.full((N, V), -1, np.int64)
+    for _ in range(V - 1):
+        through = d[:, :, None] + w                          # [n][i][j], float32
+        best, arg = through.min(axis=1), through.argmin(axis=1)      # (argmin: the first of equal minima, the lowest i)
+        better = best < d
+        if not better.any():
+            break
+        d, pred = np.where(better, best, d), np.where(better, arg, pred)
+    straight = np.zeros(N, bool)
+    for e in np.nonzero((edges[:, 0] == 0) & (edges[:, 1] == 1))[0]:
+        straight |= np.isfinite(weight[:, e])
+    n_nodes, index, length = np.zeros(N, np.int64), np.full((N, V), -1, np.int64), np.full(N, np.nan, np.float32)
+    for n in np.nonzero(np.isfinite(d[:, 1]))[0]:
+        back = [1]
+        while back[-1] != 0 and len(back) <= V:
+            back.append(0 if straight[n] else int(pred[n, back[-1]]))
+        assert back[-1] == 0, "roadmap_search: the predecessors do not lead back to node 0"
+        path = back[::-1]
+        total = np.float32(0.0)
+        for i, j in zip(path[:-1], path[1:]):
+            total = np.float32(total + w[n, i, j])
+        n_nodes[n], index[n, :len(path)], length[n] = len(path), path, total
+    return n_nodes, index, length
+
+
+def polyline_waypoints(nodes, n: int) -> np.ndarray:
+    """[n][A]: n poses along the polyline nodes[K][A], uniform in its max-norm length, both ends included (the end pose itself at
+    the end of the last edge)"""
+    nodes = np.asarray(nodes, float)
+    legs = np.max(np.abs(np.diff(nodes, axis=0)), axis=1)
+    ends = np.cumsum(legs)
+    total = ends[-1]
+    out = np.empty((n, nodes.shape[1]))
+    for k, t in enumerate(np.linspace(0.0, 1.0, n)):
+        s = t * total
+        e = min(int(np.searchsorted(ends, s, side="left")), len(legs) - 1)
+        f = (s - (ends[e] - legs[e])) / legs[e] if legs[e] > 0.0 else 1.0
+        out[k] = nodes[e + 1] if f >= 1.0 else nodes[e] + f * (nodes[e + 1] - nodes[e])
+    out[0], out[-1] = nodes[0], nodes[-1]
+    return out
+
+
+def gather_roadmap_paths(base: JointPaths, blocked, records, nodes, edges, samples) -> JointPaths:
+    """`base` (the one-via round's JointPaths of N queries) with the roadmaps of its queries blocked[Nb] (indices) filled in:
+    records[Nb][E][EDGE_FLOATS] of the edges[E][2] between nodes[Nb][V][A], samples[Nb] their S. A query with a path over its
+    usable edges becomes 'roadmap': candidate -1 and via NaN as before, length the float32 sum of its edges, the three minima the
+    minima over its edges' records, sample_step the largest [6] among them, samples their S. The others stay as they are. Sets
+    nodes, n_nodes and roadmap_free_edges."""
+    blocked, rec, nodes = np.asarray(blocked, np.int64), np.asarray(records), np.asarray(nodes)
+    N, A, V = len(base.outcome), np.asarray(base.start).shape[1], nodes.shape[1] if nodes.ndim == 3 else 2
+    n_nodes, free_edges = np.zeros(N, np.int64), np.full(N, -1, np.int64)
+    fields = {name: np.array(getattr(base, name)) for name in ("outcome", "length", "min_clearance", "min_self_clearance",
+                                                               "min_cell_clearance", "sample_step", "samples")}
+    polylines = {}
+    if len(blocked):
+        count, index, length = roadmap_search(rec, edges, V)
+        edge_of = {(int(i), int(j)): e for e, (i, j) in enumerate(np.asarray(edges))}
+        free_edges[blocked] = np.sum(rec[..., 4] == 0, axis=1)
+        for k in np.nonzero(count > 0)[0]:
+            q, path = blocked[k], index[k, :count[k]]
+            rows = rec[k, [edge_of[(min(i, j), max(i, j))] for i, j in zip(path[:-1], path[1:])]]
+            n_nodes[q], polylines[q] = count[k], nodes[k, path]
+            fields["outcome"][q], fields["length"][q], fields["samples"][q] = "roadmap", length[k], samples[k]
+            fields["min_clearance"][q], fields["min_self_clearance"][q] = rows[:, 0].min(), rows[:, 1].min()
+            fields["min_cell_clearance"][q], fields["sample_step"][q] = rows[:, 2].min(), rows[:, 6].max()
+    out = base._replace(**fields)
+    K = int(n_nodes.max()) if N else 0
+    out.nodes = np.full((N, K, A), np.nan, np.asarray(base.start).dtype)
+    for q, poly in polylines.items():
+        out.nodes[q, :len(poly)] = poly
+    out.n_nodes, out.roadmap_free_edges = n_nodes, free_edges
+    return out
+
+
+def roadmap_round(base: JointPaths, model: ChainModel, M: int, seed: int, resolution: float, budget: int, run, dtype) -> JointPaths:
+    """The roadmap round behind the one-via round's `base`, on the device and through the twin alike: the milestones of all N
+    queries, the nodes of the blocked ones, their chunks (roadmap_chunks) and run(queries[n], nodes[n][V][A] float32, edges, S) ->
+    records[n][E][EDGE_FLOATS] per chunk (queries: the chunk's indices into the call's N), then gather_roadmap_paths."""
+    blocked = np.nonzero(np.asarray(base.outcome) == "blocked")[0]
+    V = int(M) + 2
+    edges = roadmap_edges(V)
+    nodes = roadmap_nodes(base.start, base.goal, roadmap_milestones(model, base.start, base.goal, M, seed))[blocked]
+    records, samples = np.empty((len(blocked), len(edges), EDGE_FLOATS), dtype), np.zeros(len(blocked), np.int64)
+    for first, n, S in roadmap_chunks(roadmap_edge_lengths(nodes, edges), resolution, budget) if len(blocked) else ():
+        records[first:first + n], samples[first:first + n] = run(blocked[first:first + n], nodes[first:first + n], edges, S), S
+    return gather_roadmap_paths(base, blocked, records, nodes, edges, samples)
 
 
 # ---- certified joint paths: the samples, and a statement about the poses between them (include/naf_hip.h) --------------------------

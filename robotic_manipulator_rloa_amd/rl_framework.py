@@ -32,6 +32,7 @@ import torch
 
 from .environment.kinematic import (SCENE_CONDITIONS, KinematicEnvironment, build_kinematic, cell_box_gaps, choose_scene,
                                     goal_poses_host, ik_restarts_ok, joint_paths_host, reach_queries, JointPaths,
+                                    ROADMAP_MAX, roadmap_milestones, roadmap_size_ok,
                                     PATH_CANDIDATES_MAX, DEMO_MAX_TICKS, Demonstrations, demonstration_plan,
                                     demonstration_rows_host, demonstration_speed_ok)
 from .environment.synthetic import SyntheticEnvironment
@@ -261,7 +262,7 @@ class ManipulatorFramework:
 
     def reach_targets(self, targets, obstacles=None, initial_joint_positions=None, frames: int = 400, noise_scale: float = 0.0,
                       n_envs: Optional[int] = None, trajectories: bool = True, goal_poses: bool = False, joint_paths: bool = False,
-                      certify: bool = False):
+                      certify: bool = False, roadmap: int = 0):
         """Roll the trained policy out to GIVEN targets (kinematic environment only; on the device, thousands at once): query i
         starts at initial_joint_positions[i], with target targets[i] and obstacle obstacles[i], and runs until it reaches the
         target, touches the obstacle, itself or the workcell, or has taken `frames` steps. A query whose start pose is already in contact or at
@@ -285,7 +286,9 @@ class ManipulatorFramework:
         path length over path.length — a path that can be driven at its samples, where the straight line may not be — NaN where
         the query did not reach or no free path was found. Both are None otherwise, and nothing else changes.
         certify=True (with joint_paths): the paths are plan_joint_paths(certify=True)'s, and `path.certified` says which of them
-        hold between their samples too."""
+        hold between their samples too.
+        roadmap=M (with joint_paths, not with certify): the paths are plan_joint_paths(roadmap=M)'s; a query whose path is a
+        'roadmap' polyline has its planned_ratio over that polyline's length."""
         if not self.env:
             raise EnvironmentNotInitialized
         if not self.naf_agent:
@@ -307,6 +310,9 @@ class ManipulatorFramework:
         goal_poses = bool(goal_poses or joint_paths)
         if not isinstance(certify, (bool, np.bool_)) or (certify and not joint_paths):
             raise InvalidEnvironmentParameter('reach_targets(certify=True) certifies the joint paths: it is a bool and needs joint_paths=True')
+        self._check_roadmap(roadmap, certify, 'reach_targets')
+        if roadmap and not joint_paths:
+            raise InvalidEnvironmentParameter('reach_targets(roadmap=M) builds roadmaps for the joint paths: it needs joint_paths=True')
         if goal_poses and not trajectories:
             raise InvalidEnvironmentParameter('reach_targets(goal_poses=True) measures the joint path: it needs trajectories=True')
         result = self.naf_agent.rollout_vectorized(env.model, targets, obstacles, q0, frames=frames, noise_scale=float(noise_scale),
@@ -320,10 +326,13 @@ class ManipulatorFramework:
                 ratio = length / np.asarray(result.goal.joint_distance, np.float64)
             result.path_ratio = np.where((np.asarray(result.outcome) == 'reached') & result.goal.free, ratio, np.nan)
         if joint_paths:
-            result.path = self._paths_to_goals(result.goal, q0, obstacles, {'certify': True} if certify else {})
+            result.path = self._paths_to_goals(result.goal, q0, obstacles,
+                                               {'certify': True} if certify else {'roadmap': int(roadmap)} if roadmap else {})
             with np.errstate(divide='ignore', invalid='ignore'):
                 ratio = length / np.asarray(result.path.length, np.float64)
-            result.planned_ratio = np.where((np.asarray(result.outcome) == 'reached') & (result.path.candidate >= 0), ratio, np.nan)
+            # a query has a path when its length is a number: a candidate of the one-via round, or a 'roadmap' polyline
+            has_path = np.isfinite(np.asarray(result.path.length, np.float64))
+            result.planned_ratio = np.where((np.asarray(result.outcome) == 'reached') & has_path, ratio, np.nan)
         return result
 
     def _paths_to_goals(self, goal, q0, obstacles, kw) -> JointPaths:
@@ -340,14 +349,33 @@ class ManipulatorFramework:
                  nan(), np.zeros(N, np.int64), np.asarray(q0, kind), nan(A), np.zeros(N, bool), nan(), np.zeros(N, np.int64)]
         for dst, src in zip(parts, found or ()):
             dst[ok] = src
-        return JointPaths(*parts)
+        out = JointPaths(*parts)
+        if found is not None and found.n_nodes is not None:      # the roadmap's attributes, padded as the fields are
+            out.nodes = np.full((N,) + found.nodes.shape[1:], np.nan, found.nodes.dtype)
+            out.n_nodes, out.roadmap_free_edges = np.zeros(N, np.int64), np.full(N, -1, np.int64)
+            out.nodes[ok], out.n_nodes[ok], out.roadmap_free_edges[ok] = found.nodes, found.n_nodes, found.roadmap_free_edges
+        elif kw.get('roadmap'):
+            out.nodes = np.full((N, 0, A), np.nan, kind)
+            out.n_nodes, out.roadmap_free_edges = np.zeros(N, np.int64), np.full(N, -1, np.int64)
+        return out
+
+    @staticmethod
+    def _check_roadmap(roadmap, certify, who) -> None:
+        if not roadmap_size_ok(roadmap):
+            raise InvalidEnvironmentParameter(f'roadmap is a number of milestones from 0 to {ROADMAP_MAX} (0: no roadmap): '
+                                              f'got {roadmap!r}')
+        if roadmap and certify:
+            raise InvalidEnvironmentParameter(f'{who}(roadmap={roadmap!r}, certify=True): roadmap edges are checked at their samples '
+                                              f'only, and nothing certifies a \'roadmap\' path between them')
 
     def _plan_checked(self, q0, q_goal, obstacles, candidates=16, resolution=0.02, clearance_margin=0.0, seed=0, on_device=None,
-                      certify=False):
+                      certify=False, roadmap=0):
         env = self.env
         if on_device is None:
             on_device = torch.cuda.is_available()
         kw = dict(candidates=int(candidates), resolution=float(resolution), margin=float(clearance_margin), seed=int(seed))
+        if roadmap:
+            kw['roadmap'] = int(roadmap)
         if not on_device:
             out = joint_paths_host(env, q0, q_goal, obstacles, **kw, **({'certify': True} if certify else {}))
         else:
@@ -368,7 +396,7 @@ class ManipulatorFramework:
 
     def plan_joint_paths(self, targets=None, obstacles=None, initial_joint_positions=None, goal_joint_positions=None,
                          candidates: int = 16, resolution: float = 0.02, clearance_margin: float = 0.0, seed: int = 0,
-                         on_device: Optional[bool] = None, certify: bool = False):
+                         on_device: Optional[bool] = None, certify: bool = False, roadmap: int = 0):
         """Collision-checked joint paths from start poses to goal poses (kinematic environment only; needs no agent): per query
         `candidates` joint-space polylines start -> via -> goal — candidate 0 through the midpoint, the straight line, the others
         through vias drawn around it from `seed` (environment/kinematic.py: path_vias) — are SAMPLED at poses at most `resolution`
@@ -394,6 +422,17 @@ class ManipulatorFramework:
                                  reduction row and the tables of half-steps): an arm with pairs whose capsules only just fit a
                                  workgroup is refused there (NAF_CHAIN_ERR_LDS) though the sampled check serves it;
                                  on_device=False answers such an arm.
+          roadmap              : M in 1 .. 62 (0, the default: none): every query that ends 'blocked' gets a roadmap of its own — its
+                                 start pose, its goal pose and M milestones, half drawn around the straight line's midpoint as the
+                                 vias are, half uniformly inside the joint limits, from `seed` (environment/kinematic.py:
+                                 roadmap_milestones) — whose (M + 2)(M + 1) / 2 straight edges are sampled and tested as the
+                                 candidates are, `resolution` apart; the shortest polyline start .. goal over the free edges is
+                                 returned with the new outcome 'roadmap': candidate -1 and via NaN, length / the minima /
+                                 sample_step / samples those of its edges, and the result's nodes [N][K][A] (NaN-padded), n_nodes
+                                 and roadmap_free_edges filled (None without roadmap). Every other query is what it is without
+                                 the argument. SAMPLED and random: 'blocked' after a roadmap is no proof that no path exists.
+                                 Not together with certify: nothing certifies a roadmap's edges between their samples. An arm
+                                 with a prismatic joint that has no limits is refused.
         Returns environment.kinematic.JointPaths, arrays over the queries: outcome ('straight' | 'via' | 'blocked' | 'start' |
         'goal': the start / goal pose itself is blocked), candidate, via, length, straight_length, min_clearance,
         min_self_clearance, min_cell_clearance, straight_first_blocked, sample_step, samples; waypoints(n) resamples the paths."""
@@ -415,10 +454,18 @@ class ManipulatorFramework:
             raise InvalidEnvironmentParameter(f'seed is a non-negative integer: got {seed!r}')
         if not isinstance(certify, (bool, np.bool_)):
             raise InvalidEnvironmentParameter(f'certify is a bool: got {certify!r}')
+        self._check_roadmap(roadmap, certify, 'plan_joint_paths')
+        if roadmap:
+            try:
+                roadmap_milestones(env.model, np.zeros((0, env.model.A)), np.zeros((0, env.model.A)), int(roadmap), 0)
+            except ValueError as err:
+                raise InvalidEnvironmentParameter(f'roadmap: {err}') from None
         nominal = env.obstacle_centre if env.scene_ranges_on else env.obstacle_pos
         kw = dict(candidates=candidates, resolution=resolution, clearance_margin=clearance_margin, seed=seed, on_device=on_device)
         if certify:
             kw['certify'] = True
+        if roadmap:
+            kw['roadmap'] = int(roadmap)
         try:
             if targets is not None:
                 q0, targets, obstacles, _ = reach_queries(env.model, targets, obstacles, initial_joint_positions, 1,
@@ -455,7 +502,8 @@ class ManipulatorFramework:
         n_k = max(1, ceil(L_k / (speed DT))) ticks at one constant action, |a| <= speed — and every tick becomes the replay row
         run_training's environment would have written: an episode it could have produced. The poses follow the step's float32
         recurrence, so the arm reaches via and goal within its accumulated rounding (about 1e-4 rad at 400 ticks).
-          paths        : JointPaths of plan_joint_paths(); queries with candidate < 0 get outcome 'none'
+          paths        : JointPaths of plan_joint_paths(); queries with candidate < 0 get outcome 'none' — a 'roadmap' query
+                         among them: the launch drives two legs, and its polyline may have more
           targets      : [N][3], or None: the end effector at each path's goal pose; obstacles: as reach_targets() takes them
           speed        : 0 < speed <= 1, the share of the unit action — the policy's mean action is a tanh
           frames       : the episode budget, 1 .. 1024: a longer path is cut there (outcome 'frames')
