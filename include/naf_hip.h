@@ -698,6 +698,39 @@ int naf_synth_env_reset(float* env_state, float* obs, int E, int A, uint64_t see
                         const float* preset_host, int preset_floats, void* stream);
 int naf_synth_env_state_floats(int A);
 
+/* ---- the launches around a vector step's updates, fused (csrc/vector_step.hip; two entry points added, no signature changed: ABI 40 stands) ----------------------------------
+ * A many-env vector step is act -> env step -> step counter -> append, then draw -> stream counter -> gather -> moments, then
+ * the updates. The two entry points below run each group of four launches as ONE, from the bodies the separate launches
+ * compile: every device word (actions, observations, rows, env state, records, ring, meta, the three counters, idx, batch,
+ * moments) holds the same bits afterwards. What happens once per launch is done by the last workgroup to arrive at `ticket`
+ * (a zero-initialised uint32 the library puts back to zero); no workgroup waits for another. */
+typedef struct naf_vec_env {
+    float* env_state;                /* [E][naf_synth_env_state_floats] */
+    float* rows;                     /* [E][naf_replay_row_floats]: the step's transition rows */
+    uint64_t env_seed;
+    uint64_t* step_ctr;              /* the vector-step counter: read, advanced by one */
+    int32_t max_frames;
+    int32_t record_slots;
+    naf_episode_record_t* records;   /* nullable, as naf_synth_env_step's */
+    naf_replay_t* replay;            /* nullable: the ring the E rows are appended to, as naf_replay_add_batch does */
+} naf_vec_env_t;
+/* naf_policy_act for obs[E][S] (A <= 8, S = 2 A + 9), naf_synth_env_step on the actions it leaves (obs receives the next
+ * observations), *step_ctr += 1 and the append of the E rows at (head + e) % capacity: E workgroups, workgroup e all of
+ * state / env / row e. The ring must hold E rows and E rows must be at most 1024 float4 (the one-workgroup append's regime). */
+int naf_vec_act_env_append(float* obs, int S, const float* W1, const float* b1, const float* g1, const float* be1,
+                           const float* W2, const float* b2, const float* g2, const float* be2, const float* Wh, int ldw, int NH,
+                           const float* running_mean1, const float* running_var1, const float* running_mean2,
+                           const float* running_var2, float eps, int H, float* heads_out, int ldh, float* action_out,
+                           uint64_t seed, uint64_t* counter_dev, uint32_t* ticket, float noise_scale, int E, int A, int p_mode,
+                           const naf_vec_env_t* env, void* stream);
+/* naf_replay_sample_indices of n_batches minibatches at stream positions *counter_dev + u, *counter_dev += n_batches,
+ * naf_replay_gather_rows of them into out_rows[n_batches][B][out_ld] and naf_bb_moments of both nets into
+ * mom[n_batches][2][naf_bb_moments_floats]: n_batches workgroups, a minibatch held in LDS between its gather and its moments.
+ * B <= 256, out_ld = naf_replay_batch_row_floats, B * out_ld * 4 <= 65536, and a net's 6 or 8 float4 of a row inside out_ld. */
+int naf_vec_draw_gather_moments(naf_replay_t* h, uint64_t seed, uint64_t* counter_dev, uint32_t* ticket, int32_t* idx_out,
+                                float* out_rows, int out_ld, int action_mode, float* mom, int B, int n_batches,
+                                int without_replacement, void* stream);
+
 /* ---- kinematic environment of a URDF manipulator (ABI 36; self-collision and probe: ABI 37; scene ranges: ABI 38; rollout: ABI 39; workcell: ABI 40) ----------------------------------------------------------------
  * E copies of the serial chain environment/urdf_chain.py compiles from the user's URDF, stepped on the device under the
  * reference's environment rule (environment/environment.py:431-485: state layout, reward, terminal rule, velocity control

@@ -19,8 +19,9 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(CSRC, "libnaf_hip.so")
 SOURCES = ["lib.hip", "replay.hip", "naf_head.hip", "bn_relu.hip", "fused_layers.hip", "big_batch.hip", "gemm_bundle.hip", "optim.hip",
            "synth_env.hip", "xgmi_reduce.hip", "policy_act.hip", "step_path.hip", "naf_head_wide.hip",
-           "state_digest.hip", "chain_env.hip"]
-HEADERS = ["common.h", "head_body.h", "bn_tile.h", "xgmi_dev.h", "adam_body.h", "bn2bwd_fold.h", "act_body.h", "moments_body.h", "sample_body.h", "replay_dev.h", os.path.join("..", "..", "include", "naf_hip.h")]
+           "state_digest.hip", "chain_env.hip", "vector_step.hip"]
+HEADERS = ["common.h", "head_body.h", "bn_tile.h", "xgmi_dev.h", "adam_body.h", "bn2bwd_fold.h", "act_body.h", "moments_body.h", "sample_body.h", "replay_dev.h", "policy_act_body.h",
+           "synth_env_body.h", os.path.join("..", "..", "include", "naf_hip.h")]
 
 P_HADAMARD, P_MATMUL = 0, 1
 ACTION_TRUNC_INT, ACTION_FLOAT = 0, 1
@@ -275,6 +276,9 @@ _PROTOS = {
     "naf_chain_path_certify": [_vp, _vp, _vp, _vp, _vp, _f, _vp, _f, _i, _i, _i, _f, _vp, _vp, _vp],
     "naf_chain_demo_rows": [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _i, _vp, _vp, _vp],
     "naf_chain_edge_check": [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _f, _vp, _vp, _vp],
+    "naf_vec_act_env_append": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _f, _i, _vp, _i,
+                               _vp, _u64, _vp, _vp, _f, _i, _i, _i, _vp, _vp],
+    "naf_vec_draw_gather_moments": [_vp, _u64, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp],
 }
 _RESTYPES = {"naf_hip_arch": C.c_char_p}
 EXPORTED_SYMBOLS = tuple(_PROTOS)
@@ -291,6 +295,12 @@ class Hindsight(C.Structure):
     _fields_ = [("stride", C.c_int32), ("horizon", C.c_int32), ("ratio", C.c_float), ("rows_per_batch", C.c_int32),
                 ("seed", C.c_uint64), ("counter_dev", C.c_void_p), ("counter_off", C.c_uint64), ("tag_col", C.c_int32),
                 ("k_out", C.c_void_p), ("k0_out", C.c_void_p)]
+
+
+class VecEnv(C.Structure):
+    """naf_vec_env_t (include/naf_hip.h)"""
+    _fields_ = [("env_state", C.c_void_p), ("rows", C.c_void_p), ("env_seed", C.c_uint64), ("step_ctr", C.c_void_p),
+                ("max_frames", C.c_int32), ("record_slots", C.c_int32), ("records", C.c_void_p), ("replay", C.c_void_p)]
 
 
 class SlabSeg(C.Structure):

@@ -14,3 +14,17 @@ struct naf_replay {
 
 enum { META_HEAD = 0, META_SIZE = 1, META_TOTAL = 2, META_SAMPLE_CTR = 3, META_BAD_IDX = 7 };
 
+#ifdef __HIPCC__
+// the leading floats of a ring row as the learner sees them: `.long()` of the reference on the action columns [lo, hi); f0 = the
+// column of v.x (the gathers of csrc/step_path.hip and csrc/vector_step.hip)
+__device__ __forceinline__ static float4 naf_row_trunc4(float4 v, int f0, int lo, int hi) {
+    if (f0 + 3 >= lo && f0 < hi) {
+        if (f0 + 0 >= lo && f0 + 0 < hi) v.x = truncf(v.x);
+        if (f0 + 1 >= lo && f0 + 1 < hi) v.y = truncf(v.y);
+        if (f0 + 2 >= lo && f0 + 2 < hi) v.z = truncf(v.z);
+        if (f0 + 3 >= lo && f0 + 3 < hi) v.w = truncf(v.w);
+    }
+    return v;
+}
+#endif
+

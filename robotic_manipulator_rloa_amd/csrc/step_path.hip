@@ -98,16 +98,7 @@ struct StepPrepArgs {
 enum { SP_REC_VALID = 0, SP_REC_B, SP_REC_CTR, SP_REC_HEAD = 4, SP_REC_SIZE = 6, SP_REC_TAKEN = 8, SP_REC_DRAWN = 9, SP_REC_INTS = 12 };
 static_assert(SP_REC_INTS == NAF_STEP_SPEC_INTS, "include/naf_hip.h");
 
-// the leading floats of a ring row as the learner sees them: `.long()` of the reference on the action columns
-__device__ __forceinline__ static float4 sp_trunc(float4 v, int f0, int lo, int hi) {
-    if (f0 + 3 >= lo && f0 < hi) {
-        if (f0 + 0 >= lo && f0 + 0 < hi) v.x = truncf(v.x);
-        if (f0 + 1 >= lo && f0 + 1 < hi) v.y = truncf(v.y);
-        if (f0 + 2 >= lo && f0 + 2 < hi) v.z = truncf(v.z);
-        if (f0 + 3 >= lo && f0 + 3 < hi) v.w = truncf(v.w);
-    }
-    return v;
-}
+// (the leading floats of a ring row as the learner sees them: naf_row_trunc4, csrc/replay_dev.h)
 
 // The body of the launch, and of the PREFETCH that adam_act_kernel's extra workgroup runs for the next timestep (SPEC):
 //
@@ -353,7 +344,7 @@ __device__ __forceinline__ static void step_prep_body(const StepPrepArgs& P, uns
             const int j = j0 + SP_THREADS * k;
             if (j < total4) {
                 if (!SPEC && cache && pos[k] == newpos) v[k] = sNew[col[k]];        // (the row this launch appends: not in the ring yet)
-                const float4 t = sp_trunc(v[k], 4 * col[k], P.trunc_lo, P.trunc_hi);
+                const float4 t = naf_row_trunc4(v[k], 4 * col[k], P.trunc_lo, P.trunc_hi);
                 if (cache) sRows[j] = t;
                 else P.out_rows[j] = t;
             }
@@ -376,7 +367,7 @@ __device__ __forceinline__ static void step_prep_body(const StepPrepArgs& P, uns
             }
             const int rr = row < B ? row : 0;
             float4 v = cache ? sRows[rr * P.w4 + c]
-                             : sp_trunc(P.ring[((int64_t)sPos[rr] << P.rf4_shift) + c], 4 * c, P.trunc_lo, P.trunc_hi);
+                             : naf_row_trunc4(P.ring[((int64_t)sPos[rr] << P.rf4_shift) + c], 4 * c, P.trunc_lo, P.trunc_hi);
             if (row >= B) v = make_float4(0.f, 0.f, 0.f, 0.f);
             return v;
         },

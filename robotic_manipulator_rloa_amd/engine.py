@@ -80,8 +80,11 @@ class UpdateChunk:
     long parity runs use it; the reference's own per-timestep loop is TimestepGraph below."""
 
     def __init__(self, learner: Learner, replay: ReplayBuffer, n_updates: int, teacher_forced: bool = False,
-                 use_graph: bool = True, gather_outside_graph: bool = False, hindsight=None):
-        """gather_outside_graph: launch sample+gather eagerly in front of the graph of U updates, so the caller can
+                 use_graph: bool = True, gather_outside_graph: bool = False, hindsight=None, fused: Optional[bool] = None):
+        """fused: None / True — draw, gather and moments as ONE launch where that fits (ReplayBuffer.draw_gather_moments: the
+        row-split chain, B <= 256, no hindsight gather, not teacher-forced, the gather inside the graph); False — the separate
+        launches, for tests and A/B runs. The same bits either way.
+        gather_outside_graph: launch sample+gather eagerly in front of the graph of U updates, so the caller can
         bracket the gather launch with events (bench.py's live roofline measurement).
         hindsight: (ratio, horizon, stride) — the gather relabels goals (ReplayBuffer.gather_rows_hindsight); k_out / k0_out [U, B]
         then hold what it did to the last chunk's rows. A minibatch's hindsight draw sits at the stream position of its index draw:
@@ -119,6 +122,12 @@ class UpdateChunk:
                         if "bb" in learner.fuse else None)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.use_graph = use_graph
+        self.fused = fused is None or bool(fused)
+        self._ticket = torch.zeros(1, dtype=torch.int32, device=dev)       # (the fused launch's last-arriver ticket)
+
+    def _fused_prelude(self) -> bool:
+        return (self.fused and self.moments is not None and self.hindsight is None and not self.teacher_forced and
+                not self.gather_outside_graph and self.gather_events is None and self.replay.fits_draw_gather_moments())
 
     def _sample_gather(self) -> None:
         if not self.teacher_forced:
@@ -151,12 +160,16 @@ class UpdateChunk:
                               pending=d and k > 0, defer=d and (k < self.U - 1 or defer_last))
 
     def _body(self) -> None:
-        self._sample_gather()
-        self._updates()
+        if self._fused_prelude():
+            self.replay.draw_gather_moments(self.idx, self.batch, self.moments, self.U, self._ticket)
+            self._updates(moments_ready=True)
+        else:
+            self._sample_gather()
+            self._updates()
 
     def _snapshot(self, extra=()) -> _StateSnapshot:
         k = (self.k_out, self.k0_out) if self.hindsight is not None else ()
-        return _StateSnapshot(self.L, self.replay, (self.idx, self.batch, self.loss_parts) + k + tuple(extra))
+        return _StateSnapshot(self.L, self.replay, (self.idx, self.batch, self.loss_parts, self._ticket) + k + tuple(extra))
 
     def capture(self) -> None:
         self.replay.flush()
@@ -859,8 +872,12 @@ class DeviceEnvLoop(_ChainHandle):
                  noise_scale: float = 1.0, use_graph: bool = True, robot: str = "kuka", obstacle_jitter: float = 0.0,
                  preset: Optional[List[float]] = None, variation: Optional[List[float]] = None, records: bool = False,
                  drain_every: int = 64, chain=None, target=None, obstacle=None, obstacle_radius: float = 0.06,
-                 target_range=None, obstacle_range=None, scene_margin: float = 0.02, tag_rows: bool = False):
-        """replay=None: no transitions are appended (evaluation). preset: 14 floats [initial joint positions(8) | target |
+                 target_range=None, obstacle_range=None, scene_margin: float = 0.02, tag_rows: bool = False,
+                 fused: Optional[bool] = None):
+        """fused: None / True — act, env step, step counter and append as ONE launch where that fits (ActPath.act_env_append: a
+        replay, the stand-in env, the one-launch act and at most 1024 float4 of rows); False — the separate launches, for tests
+        and A/B runs. The same bits either way.
+        replay=None: no transitions are appended (evaluation). preset: 14 floats [initial joint positions(8) | target |
         obstacle] instead of a named robot's. variation: per-joint half-width of the reset range (None: 0.1 everywhere,
         the stand-in's historical value).
         chain: an environment.urdf_chain.ChainModel — the envs are E copies of that arm (csrc/chain_env.hip: the blob is checked
@@ -917,7 +934,15 @@ class DeviceEnvLoop(_ChainHandle):
             self.records = torch.zeros(self.drain_every, self.E, 8, dtype=torch.int32, device=dev)
             self._pins = [torch.zeros(self.drain_every, self.E, 8, dtype=torch.int32).pin_memory() for _ in range(2)]
             self._pin_i = 0
+        self.fused = fused is None or bool(fused)
+        self._vec_env = None         # (the fused launch's arguments, built at its first use: the ring may not exist before)
         self.reset()
+
+    def _fused_step(self) -> bool:
+        lay = self.L.lay
+        return (self.fused and self.replay is not None and self._chain_env is None and self.actor.fused and
+                self.replay._handle is not None and self.E * lay.row_floats // 4 <= 1024 and self.E <= self.replay.buffer_size and
+                lay.S == 2 * lay.A + 9)
 
     def _open_chain(self, chain, target, obstacle, obstacle_radius, obstacle_jitter, target_range=None, obstacle_range=None,
                     scene_margin=0.02) -> None:
@@ -957,8 +982,14 @@ class DeviceEnvLoop(_ChainHandle):
 
     def _body(self) -> None:
         st = stream_ptr()
-        self.actor.act(self.noise_scale)                                     # NAFAgent.act for E states
         slots = self.drain_every if self.records is not None else 0
+        if self._fused_step():
+            if self._vec_env is None:
+                self._vec_env = _lib.VecEnv(ptr(self.env_state), ptr(self.rows), self.seed, ptr(self.step_ctr), self.max_frames,
+                                            slots, ptr(self.records), self.replay.handle)
+            self.actor.act_env_append(self.noise_scale, self._vec_env)       # act, environment.step, the counter, ReplayBuffer.add
+            return
+        self.actor.act(self.noise_scale)                                     # NAFAgent.act for E states
         if self._chain_env is not None:
             step = self.lib.naf_chain_env_step_tagged if self.tag_rows else self.lib.naf_chain_env_step
             check(step(self._chain_env, ptr(self.env_state), ptr(self.actor.actions), ptr(self.rows), ptr(self.actor.obs), self.E,
@@ -973,7 +1004,7 @@ class DeviceEnvLoop(_ChainHandle):
 
     def capture(self) -> None:
         warmup = 2
-        extra = (self.env_state, self.rows, self.step_ctr, self.actor.obs, self.actor.counter, self.actor.actions)
+        extra = (self.env_state, self.rows, self.step_ctr, self.actor.obs, self.actor.counter, self.actor.actions, self.actor._ticket)
         if self.records is not None:
             extra += (self.records,)
         snap = _StateSnapshot(self.L, self.replay, extra)

@@ -1087,3 +1087,18 @@ class ActPath:
                                   float(noise_scale), self.E, lay.A, L.p_mode, st), "act_noise")
         check(L.lib.naf_counter_add(ptr(self.counter), 1, st), "counter_add")
         return self.actions
+
+    def act_env_append(self, noise_scale: float, env: "_lib.VecEnv") -> torch.Tensor:
+        """act(), the stand-in envs' step on the actions, the step counter and the append of the rows, in ONE launch
+        (naf_vec_act_env_append, csrc/vector_step.hip): the same bits in every word as the four launches. Only with the fused
+        kernel (engine.DeviceEnvLoop decides)."""
+        L, lay, st = self.L, self.L.lay, stream_ptr()
+        seg, H = lay.seg, lay.H
+        t2p, bnp = L.theta2.data_ptr(), L.bn_stats.data_ptr()
+        off = lambda name: t2p + 4 * seg[name].offset          # noqa: E731
+        check(L.lib.naf_vec_act_env_append(
+            ptr(self.obs), lay.S, off("W1"), off("b1"), off("g1"), off("be1"), off("W2"), off("b2"), off("g2"), off("be2"),
+            off("Wh"), lay.HP, lay.NH, bnp, bnp + 4 * H, bnp + 8 * H, bnp + 12 * H, BN_EPS, H, ptr(self.Gh), lay.NHP,
+            ptr(self.actions), self.seed, ptr(self.counter), ptr(self._ticket), float(noise_scale), self.E, lay.A, L.p_mode,
+            _lib.C.byref(env), st), "vec_act_env_append")
+        return self.actions

@@ -163,6 +163,26 @@ class ReplayBuffer:
                                                      stream_ptr()), "naf_replay_sample_indices")
         check(self.lib.naf_counter_add(ptr(self._sample_ctr), int(n_batches), stream_ptr()), "naf_counter_add")
 
+    def fits_draw_gather_moments(self) -> bool:
+        """Can sample_indices + gather_rows + the learner's moments run as the one launch below? Minibatches of up to 256 rows
+        that fit 64 KB of LDS, and a row that holds all of a net's 6 or 8 float4 (csrc/vector_step.hip)."""
+        if self._handle is None:
+            return False
+        k4d = 6 if (self.S + 3) // 4 <= 6 else 8
+        return (self.batch_size <= 256 and self.batch_size * self.batch_row_floats * 4 <= 65536 and (self.S + 3) // 4 <= 8 and
+                self.off_s2 + 4 * k4d <= self.batch_row_floats)
+
+    def draw_gather_moments(self, idx_out: torch.Tensor, out_rows: torch.Tensor, moments: torch.Tensor, n_batches: int,
+                            ticket: torch.Tensor) -> None:
+        """sample_indices(idx_out, n_batches), gather_rows of them into out_rows [n_batches, B, batch_row_floats] and the moments
+        of layer 1's inputs into moments [n_batches, 2, .] in ONE launch (naf_vec_draw_gather_moments): the same bits."""
+        self._join_side()
+        self._gen += 1
+        check(self.lib.naf_vec_draw_gather_moments(self.handle, self.seed, ptr(self._sample_ctr), ptr(ticket), ptr(idx_out),
+                                                   ptr(out_rows), int(out_rows.shape[-1]), self.action_mode, ptr(moments),
+                                                   self.batch_size, int(n_batches), int(self.without_replacement), stream_ptr()),
+              "naf_vec_draw_gather_moments")
+
     def gather_rows(self, idx: torch.Tensor, out_rows: torch.Tensor, n: int) -> None:
         """out_rows[..., ld] (contiguous) receives the leading ld floats of the n indexed rows; ld = out_rows.shape[-1]
         between batch_row_floats (what the learner reads) and row_floats (the whole padded ring row)."""
