@@ -20,13 +20,14 @@ from __future__ import annotations
 import os
 
 import numpy as np
-from dataclasses import dataclass
-from typing import Dict, Optional, Tuple
+from typing import Dict, Optional
 
 import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
+from .chain_plan import plan_chain
+from .layout import NetLayout
 from .parallel import XgmiAllReduce, all_reduce_flat_grad
 
 BN_EPS = 1e-5
@@ -64,95 +65,6 @@ def configure_blas() -> str:
     return "rocblas"
 
 
-def _round_up(x: int, m: int) -> int:
-    return (x + m - 1) // m * m
-
-
-@dataclass(frozen=True)
-class Segment:
-    offset: int
-    shape: Tuple[int, ...]
-
-    @property
-    def numel(self) -> int:
-        n = 1
-        for s in self.shape:
-            n *= s
-        return n
-
-
-BB_MAX_STATE = 32      # the row-split chain: layer 1's K (csrc/big_batch.hip, BB_MAX_K4)
-BB_MAX_JOINTS = 11     # ... and the fused layer-2 launch's heads tile (FK_MAX_A)
-NATIVE_LAYER = 256     # the width the fused kernels are built for (rl_framework.py's presets; csrc/big_batch.hip, step_path.hip)
-
-
-class NetLayout:
-    """Where each parameter of one NAF network sits inside its flat buffer (units: floats).
-    Segments start on 64-float (256-B) boundaries; the gaps and the pad rows/columns of Wh hold zeros, receive
-    zero gradients and therefore stay zero under Adam.
-
-    layer_size below 256 (the reference takes any; its own agent test builds 128): with pad_layer the network is STORED as a
-    256-wide one whose units beyond layer_size have zero weights, zero biases and zero BatchNorm scale / shift — `H` (what every
-    kernel sees) is 256, `H_ref` (what state_dict() shows and load_state_dict() takes) is layer_size. Such a unit's pre-activation is
-    0 for every sample, its normalised value 0, its activation ReLU(0 * 0 + 0) = 0; nothing downstream multiplies it with anything
-    but a zero weight, so every gradient it receives or passes on is 0 and Adam (m = v = 0) leaves it where it is: the padded network
-    computes the narrow one's numbers, term for term, with exact zeros appended to its sums — and runs the kernels the presets run."""
-
-    def __init__(self, state_size: int, action_size: int, layer_size: int, pad_layer: bool = True):
-        if not (1 <= action_size <= 64):
-            raise ValueError("action_size must be in 1..64 (one sample per 8- or 16-lane group in the fused head kernels, per 16-, "
-                             "32- or 64-lane group in the stand-alone ones: a wavefront has 64 lanes)")
-        self.H_ref = int(layer_size)
-        self.S, self.A = state_size, action_size
-        # (round 6: widths in (256, 512) likewise stored as 512 — the row-split chain runs 512 columns as two 256-column halves)
-        self.H = (NATIVE_LAYER if (pad_layer and 0 < layer_size < NATIVE_LAYER) else
-                  2 * NATIVE_LAYER if (pad_layer and NATIVE_LAYER < layer_size < 2 * NATIVE_LAYER) else int(layer_size))
-        self.T = action_size * (action_size + 1) // 2
-        self.NH = self.A + self.T + 1                  # [mu | l | V]
-        self.NHP = _round_up(self.NH, 16)              # heads row stride (ldh): whole 16-wide MFMA tiles
-        self.HP = self.H + 16                          # activations: H features | 1.0 | 15 zeros (K % 16 == 0)
-        self.seg: Dict[str, Segment] = {}
-        off = 0
-        for name, shape in (("W1", (self.H, self.S)), ("b1", (self.H,)), ("g1", (self.H,)), ("be1", (self.H,)),
-                            ("W2", (self.H, self.H)), ("b2", (self.H,)), ("g2", (self.H,)), ("be2", (self.H,)),
-                            ("Wh", (self.NHP, self.HP))):
-            self.seg[name] = Segment(off, shape)
-            off = _round_up(off + self.seg[name].numel, 64)
-        self.P = off
-        self.row_floats = _lib.load().naf_replay_row_floats(self.S, self.A)              # ring rows (256 B)
-        self.batch_row_floats = _lib.load().naf_replay_batch_row_floats(self.S, self.A)  # gathered minibatch rows
-        # offsets inside a transition row
-        self.off_u = self.S
-        self.off_r = self.S + self.A
-        self.off_s2 = _lib.load().naf_replay_row_off_next_state(self.S, self.A)   # 16-B aligned
-        self.off_d = self.off_s2 + self.S
-
-    def view(self, flat: torch.Tensor, name: str) -> torch.Tensor:
-        s = self.seg[name]
-        return flat[s.offset:s.offset + s.numel].view(*s.shape)
-
-    def n_ref_params(self) -> int:
-        """Number of parameters of the reference module (79,644 at S=21, A=6, H=256)."""
-        h = self.H_ref
-        return h * self.S + h * h + 6 * h + self.NH * (h + 1)
-
-    # ---- mapping to the reference's state_dict keys (naf_neural_network.py:37-54) -------------------------
-    def param_views(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
-        """the reference's tensors, in its shapes: views of the stored ones (of their first layer_size units where the layer is
-        stored padded; the heads' bias column is column H of Wh)"""
-        A, T, H, h = self.A, self.T, self.H, self.H_ref
-        Wh = self.view(flat, "Wh")
-        return {
-            "input_layer.weight": self.view(flat, "W1")[:h], "input_layer.bias": self.view(flat, "b1")[:h],
-            "bn1.weight": self.view(flat, "g1")[:h], "bn1.bias": self.view(flat, "be1")[:h],
-            "hidden_layer.weight": self.view(flat, "W2")[:h, :h], "hidden_layer.bias": self.view(flat, "b2")[:h],
-            "bn2.weight": self.view(flat, "g2")[:h], "bn2.bias": self.view(flat, "be2")[:h],
-            "action_values.weight": Wh[0:A, 0:h], "action_values.bias": Wh[0:A, H],
-            "value.weight": Wh[A + T:A + T + 1, 0:h], "value.bias": Wh[A + T:A + T + 1, H],
-            "matrix_entries.weight": Wh[A:A + T, 0:h], "matrix_entries.bias": Wh[A:A + T, H],
-        }
-
-
 PARAM_ORDER = ["input_layer.weight", "input_layer.bias", "bn1.weight", "bn1.bias", "hidden_layer.weight",
                "hidden_layer.bias", "bn2.weight", "bn2.bias", "action_values.weight", "action_values.bias",
                "value.weight", "value.bias", "matrix_entries.weight", "matrix_entries.bias"]
@@ -166,107 +78,81 @@ class Learner:
                  tau: float, gamma: float, device: torch.device, p_mode: int = _lib.P_HADAMARD,
                  world_size: int = 1, process_group=None, fuse: Optional[str] = None, _force_allreduce: bool = False,
                  _fold_norm: bool = True, pad_layer: bool = True, _xgmi=None):
-        """fuse: "rows" | "columns" | "unfused" | None (= NAF_FUSE or the per-shape default, see below). The underscore
+        """fuse: "rows" | "columns" | "unfused" | None (= NAF_FUSE or the per-shape default, see chain_plan.py). The underscore
         arguments are for tests: run the gradient all-reduce at world size 1 / keep the separate grad-norm launch.
         pad_layer: a layer_size below 256 is stored zero-padded to 256 (NetLayout) and runs the kernels built for that width;
-        False: its own width on the column-tile / unfused chains (tests compare the two)."""
+        False: its own width on the column-tile / unfused chains (tests compare the two).
+        Which chain of launches the shape gets, and every count that follows from it, is chain_plan.plan_chain's to say (self.plan);
+        the methods below allocate by it."""
         _lib.require_gpu()
-        self.lib = _lib.load()
+        self.lib = self._f = _lib.load()
         self.blas = configure_blas()
         self.dev = torch.device(device)
+        self.plan = plan = plan_chain(state_size, action_size, layer_size, batch_size, p_mode=p_mode, world_size=world_size,
+                                      fuse=fuse, pad_layer=pad_layer, force_allreduce=_force_allreduce, fold_norm=_fold_norm)
+        if plan.warning:
+            import warnings
+            warnings.warn(plan.warning, stacklevel=3)
         self.lay = NetLayout(state_size, action_size, layer_size, pad_layer=pad_layer)
         self.B = int(batch_size)
         self.lr, self.tau, self.gamma = float(learning_rate), float(tau), float(gamma)
         self.p_mode = int(p_mode)
         self.world_size = int(world_size)
         self.pg = process_group
-        # Three chains of launches implement one learn(); `fuse` (a set of tags, read by forward_train / learn_rows) says which:
-        #   "rows"     {bb, gb, hk, ep, s2}: the ROW-SPLIT chain of csrc/big_batch.hip — 64-row blocks over the whole chip, two-stage
-        #              BatchNorm statistics, GEMM 2 on f32 MFMA, layer 2 + heads + NAF head + first backward stage in one launch
-        #              (hk), the backward GEMMs as one launch (gb) that also carries the second stage of layer 2's BatchNorm
-        #              backward as its prologue (s2) and the batch pass of layer 1's backward as its epilogue (ep), a finish
-        #              launch — 5 launches per update in a chain of updates. Needs 16 <= B <= 4096 (any size in it), H = 256 | 512, S <= 32,
-        #              A <= 8 (A <= 11 up to B = 2048).
-        #              Default wherever the shape fits (measured at the end of round 3, updates/s, column-tile | row-split: B = 64:
-        #              32.3k | 36.0k, 128: 30.7k | 35.4k, 192: 25.8k | 34.0k, 256: 25.7k | 34.7k, 512: 20.3k | 30.9k; until then the
-        #              column-tile chain led below B = 256 — 32.5k | 29.3k at 64 in round 2).
-        #   "columns"  {l1, b2, gb, s3}: the COLUMN-TILE chain of csrc/fused_layers.hip — a workgroup owns 8 feature columns x all
-        #              B rows (ceil(B/64) <= 8 rows per thread in registers), the K = state-size and N = heads GEMMs folded into
-        #              the BatchNorm kernels, 8 launches per update. B <= 512. Default below B = 16 (and up to 512 where H or S
-        #              do not fit the row-split chain). (B = 16 ... 63 moved to the row-split chain in round 4: one partial
-        #              block — 37.1k against 31.0k updates/s at B = 32, 36.5k against 21.1k at 63.)
-        #   "unfused"  {gb} or {}: torch (rocBLAS) GEMMs + the BatchNorm / head kernels of csrc/bn_relu.hip, naf_head.hip, with
-        #              the backward GEMM bundle where its shapes allow (B, H multiples of 16) — any shape up to B = 4096; 14
-        #              launches per update (round 1's chain: 12.7k updates/s at B = 1024).
-        # NAF_FUSE = rows | columns | unfused overrides the choice (a chain whose shape limits are not met falls to the next).
-        lay0 = self.lay
-        # The reference takes any positive batch_size (rl_framework.py:186-189). Here: every size up to 4096 trains — 16 ... 4096
-        # on the row-split chain, smaller ones on the column-tile chain, other layer / state sizes on the unfused chain (beyond 2048
-        # with the streamed BatchNorm kernels of csrc/bn_relu.hip) with a warning that names the row-split chain's range. 4096 is
-        # the replay sampler's limit (one workgroup draws a minibatch without replacement in LDS, csrc/replay.hip).
-        if self.B < 1 or self.B > (1 << 20):
-            raise ValueError(f"batch_size {self.B}: 1 <= batch_size <= 1,048,576 (the replay sampler's table, csrc/replay.hip)")
-        # (round 4: ANY batch size from 16 to 4096 — the last 64-row block of layer 1 / GEMM 2, the last 16-row workgroup of the fused
-        #  layer-2 + head launch and the last block of the bundle's dA1 product may be partial: rows past the batch read as zeros, are
-        #  never stored and stay out of every statistic and sum. The work buffers hold Bp = the next multiple of 16 rows (of 32 beyond
-        #  B = 2048, where the fused layer-2 + head launch runs 32 rows per workgroup),
-        #  zero-initialised: the weight-gradient products walk Bp rows as their K dimension, and a row past the batch is a zero in at
-        #  least one operand of each — dH and dY2 rows the head body never writes, A1 rows layer 1 never stores.)
-        # (round 6, late: state sizes up to 32 — the layer-1 kernels' K — and 9 .. 11 joints: the fused layer-2 launch then holds one
-        #  sample per 16-lane group and a Wh tile of 64 | 80 rows, 16 rows per workgroup only, hence B <= 2048; csrc/big_batch.hip.
-        #  The reference's state is 9 + 2 A floats, environment.py:261: 27 | 29 | 31 at 9 | 10 | 11 joints)
-        #  (beyond 2048 — 32 rows per workgroup — with the reference's Hadamard head only: the matmul mode's L tiles do not fit there)
-        self.bb_ok = (16 <= self.B <= 4096 and lay0.H in (256, 512) and lay0.S <= BB_MAX_STATE and
-                      (lay0.A <= 8 or (lay0.A <= BB_MAX_JOINTS and (self.B <= 2048 or self.p_mode == _lib.P_HADAMARD))))
-        want = (fuse or os.environ.get("NAF_FUSE", "default")).lower()
-        if want not in ("default", "rows", "columns", "unfused"):
-            raise ValueError(f"NAF_FUSE / fuse = {want!r}: one of default, rows, columns, unfused")
-        if want == "default":
-            want = "rows" if self.bb_ok else ("columns" if self.B <= 512 else "unfused")
-        if want == "rows" and not self.bb_ok:
-            want = "columns" if self.B <= 512 else "unfused"
-        if lay0.A > 8 and want != "rows":
-            want = "unfused"                   # (9 .. 16 joints: the column-tile kernels hold one sample per 8-lane group)
-        if want == "rows":
-            self.fuse = {"bb", "gb", "hk", "ep", "s2"}
-        elif want == "columns" and self.B <= 512:
-            self.fuse = {"l1", "b2", "gb", "s3"}
-            if lay0.S > 32 or (lay0.S > 24 and self.B > 256):
-                self.fuse -= {"l1"}            # (K = 25 .. 32: the layer-1 backward tile holds at most 4 rows per thread)
-            if lay0.H not in (128, 256):
-                self.fuse -= {"s3"}
-        else:
-            want = "unfused"
-            self.fuse = {"gb"}
-        if (self.B % 16 != 0 and want != "rows") or lay0.H % 16 != 0:
-            self.fuse -= {"gb"}                # the MFMA kernels take whole 16 x 16 x 16 steps: M, N, K % 16 == 0
-        self.chain = want
-        if lay0.A > 8 and want != "rows":
-            import warnings
-            warnings.warn(f"action_size {lay0.A} at batch_size {self.B}, state_size {lay0.S} runs the unfused chain: the row-split "
-                          f"chain takes up to {BB_MAX_JOINTS} joints at 16 <= batch_size <= 4096 (2048 with p_mode matmul), state_size <= {BB_MAX_STATE} "
-                          f"(every arm the reference ships has 6 or 7: KUKA / xArm, Panda)", stacklevel=3)
-        elif self.B > 512 and want != "rows":
-            # (a performance cliff, not an error: say so once, with the sizes that avoid it)
-            import warnings
-            warnings.warn(f"batch_size {self.B} at H = {lay0.H}, S = {lay0.S} runs the unfused chain (about half the updates/s of the "
-                          f"row-split chain): the row-split kernels need 16 <= batch_size <= 4096, layer_size <= 512 and "
-                          f"state_size <= {BB_MAX_STATE}", stacklevel=3)
-        # with every gradient element produced by one of our own kernels, those kernels also emit its sum-of-squares partial:
-        # the separate grad-norm launch disappears. Data-parallel runs keep it (the norm is taken on the all-reduced gradient).
-        self.fold_norm = ({"l1", "b2", "gb"} <= self.fuse or {"bb", "gb"} <= self.fuse) and self.world_size == 1 and \
-            not _force_allreduce and _fold_norm
         self._force_allreduce = bool(_force_allreduce)
-        lay, B, dev = self.lay, self.B, self.dev
-        f32 = dict(dtype=torch.float32, device=dev)
-        P, H, HP, NHP = lay.P, lay.H, lay.HP, lay.NHP
-        # rows of the work buffers: whole 16-row groups on the row-split chain (see bb_ok above), B everywhere else
-        # (beyond B = 256 whole 64-row blocks: the K ranges of the weight-gradient products then divide as they do for the next
-        #  multiple of 64 — B = 1000 runs the products of B = 1024 with 24 zero rows, four 256-row ranges instead of three of 336)
-        hk_rows = (self.lib.naf_bb_layer2_head_rows(B) if B <= 256 else 64) if "bb" in self.fuse else 1
-        self.Bp = Bp = -(-B // hk_rows) * hk_rows
+        # what the launch methods, engine.py and the benchmarks read of the plan: plain attributes, copied once
+        self.chain, self.fuse, self.bb_ok, self.Bp, self.hk_rows = plan.chain, plan.fuse, plan.bb_ok, plan.Bp, plan.hk_rows
+        self.fold_norm, self.defer_ok = plan.fold_norm, plan.defer_ok
+        self.n_partials, self.n_partials_fold, self.n_partials_norm = plan.n_partials, plan.n_partials_fold, plan.n_partials_norm
+        self.n_loss_wg = plan.n_loss_wg
+        self._nb1, self._gb_blocks, self._ft_blocks, self._gb_wh_blocks = plan.nb1, plan.gb_blocks, plan.ft_blocks, plan.gb_wh_blocks
+        self.mom_floats, self.n_slabs, self.slab_stride = plan.mom_floats, plan.n_slabs, plan.slab_stride
+        self._f32 = dict(dtype=torch.float32, device=self.dev)
+        self._open_exchange(_xgmi)
+        self._alloc_state()
+        self._alloc_work_buffers()
+        if "s3" in self.fuse:
+            self._alloc_head_slabs()
+        self._make_gemm_views()
+        if "bb" in self.fuse:
+            self._alloc_row_split()
+        if self.world_size > 1:
+            self._pick_exchange()
 
-        # ---- persistent state --------------------------------------------------------------------------
+    def _open_exchange(self, _xgmi) -> None:
+        """The gradient exchange's communicator (data parallel), before anything is sized by it."""
+        # Data parallel inside one node — three forms of the one exchange (the sum of the flat gradient over the ranks, where
+        # loss.backward() -> clip_grad_norm_ sit in the reference, naf_algorithm.py:207-210):
+        #   "oneshot"  the one-shot peer-memory all-reduce as a launch of its own behind the finish launch (csrc/xgmi_reduce.hip; the
+        #              finish launch pushes 91 % of the bytes early)
+        #   "merged"   the whole exchange INSIDE the finish launch of the row-split chain (csrc/big_batch.hip, bb_finish_exchange):
+        #              five launches per update as on one GPU
+        #   "rccl"     torch.distributed's all-reduce (RCCL over xGMI) captured in the graph + a norm launch
+        # The peer-memory forms exist when every rank could map every peer and the exact self-test passed on all of them
+        # (XgmiAllReduce.try_create is collective; NAF_XGMI=0 skips it). WHICH form runs is measured where the job runs:
+        # autotune_exchange() (end of the constructor) times them on this node and every rank takes the collectively fastest —
+        # the one-GPU rehearsal ranks them oneshot < merged < collective, real xGMI may not (a peer's slab is not behind the
+        # writer's L2 there). NAF_DP_EXCHANGE = oneshot | merged | rccl pins the form instead.
+        P = self.lay.P
+        self.xgmi = None
+        self._xg = None                    # the communicator the CURRENT form uses (None: the collective)
+        self.xgmi_merged = False
+        self.exchange = "none" if self.world_size == 1 else "rccl"
+        self.exchange_autotune = None      # {form: us per update ..., "chosen": form} once autotune_exchange() has run
+        self._exchange_pick = "auto"
+        self._push_desc = None
+        if _xgmi is not None:
+            # a communicator handed in (XgmiAllReduce.local_group: the in-process rehearsal of world sizes beyond what a one-GPU
+            # box hosts as processes); the exchange form must then be pinned — nothing here is collective
+            if _xgmi.world != self.world_size or _xgmi.n != P or os.environ.get("NAF_DP_EXCHANGE", "auto") not in ("oneshot", "merged"):
+                raise ValueError("Learner(_xgmi=...): a communicator of this world size and length, NAF_DP_EXCHANGE = oneshot | merged")
+            self.xgmi = _xgmi
+        elif self.world_size > 1 and os.environ.get("NAF_XGMI", "1") != "0":
+            self.xgmi = XgmiAllReduce.try_create(P, self.dev, self.pg)
+
+    def _alloc_state(self) -> None:
+        """Persistent state: parameters, gradient, optimizer state, BatchNorm statistics, norm partials."""
+        P, H, dev, f32 = self.lay.P, self.lay.H, self.dev, self._f32
         self.theta2 = torch.zeros(2, P, **f32)             # [main; target]
         self.grad = torch.zeros(P, **f32)
         self.adam_m = torch.zeros(P, **f32)
@@ -282,71 +168,23 @@ class Learner:
                                    # when CALLED (graph replays do not count): a pipelined chunk's pending gradient is void then
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)   # optimizer steps taken
         self.step_live = self.step_dev
-        ft_tx = self.lib.naf_fused_tile_cols()
-        ft_blocks = (H + ft_tx - 1) // ft_tx                               # workgroups of the column-tile kernels
-        gb_blocks = ((NHP + 31) // 32) * ((HP + 31) // 32) + ((H + 31) // 32) ** 2   # dWh + dW2 blocks of the bundle
-        self.n_partials_norm = (P + _lib.NORM_CHUNK - 1) // _lib.NORM_CHUNK
-        # folded norm partials: the bundle's dWh + dW2 blocks, then the column-tile kernels (two launches of ft_blocks) or,
-        # in the large-batch chain, the workgroups of the layer-1 finish kernel (two columns each)
-        self.n_partials_fold = gb_blocks + 2 * ft_blocks
-        if "bb" in self.fuse:
-            self.n_partials_fold = self.lib.naf_bb_layer1_bwd_finish_blocks(H) + (H * H + 1023) // 1024 + (NHP * HP + 1023) // 1024
-        self.n_partials = self.n_partials_fold if self.fold_norm else self.n_partials_norm
-        # Data parallel inside one node — three forms of the one exchange (the sum of the flat gradient over the ranks, where
-        # loss.backward() -> clip_grad_norm_ sit in the reference, naf_algorithm.py:207-210):
-        #   "oneshot"  the one-shot peer-memory all-reduce as a launch of its own behind the finish launch (csrc/xgmi_reduce.hip; the
-        #              finish launch pushes 91 % of the bytes early)
-        #   "merged"   the whole exchange INSIDE the finish launch of the row-split chain (csrc/big_batch.hip, bb_finish_exchange):
-        #              five launches per update as on one GPU
-        #   "rccl"     torch.distributed's all-reduce (RCCL over xGMI) captured in the graph + a norm launch
-        # The peer-memory forms exist when every rank could map every peer and the exact self-test passed on all of them
-        # (XgmiAllReduce.try_create is collective; NAF_XGMI=0 skips it). WHICH form runs is measured where the job runs:
-        # autotune_exchange() (end of this constructor) times them on this node and every rank takes the collectively fastest —
-        # the one-GPU rehearsal ranks them oneshot < merged < collective, real xGMI may not (a peer's slab is not behind the
-        # writer's L2 there). NAF_DP_EXCHANGE = oneshot | merged | rccl pins the form instead.
-        self.xgmi = None
-        self._xg = None                    # the communicator the CURRENT form uses (None: the collective)
-        self.xgmi_merged = False
-        self.exchange = "none" if self.world_size == 1 else "rccl"
-        self.exchange_autotune = None      # {form: us per update ..., "chosen": form} once autotune_exchange() has run
-        self._exchange_pick = "auto"
-        self._push_desc = None
         n_partials_most = max(self.n_partials_fold + 1, self.n_partials_norm, self.n_partials)
-        if _xgmi is not None:
-            # a communicator handed in (XgmiAllReduce.local_group: the in-process rehearsal of world sizes beyond what a one-GPU
-            # box hosts as processes); the exchange form must then be pinned — nothing here is collective
-            if _xgmi.world != self.world_size or _xgmi.n != P or os.environ.get("NAF_DP_EXCHANGE", "auto") not in ("oneshot", "merged"):
-                raise ValueError("Learner(_xgmi=...): a communicator of this world size and length, NAF_DP_EXCHANGE = oneshot | merged")
-            self.xgmi = _xgmi
+        if self.xgmi is not None:
             n_partials_most = max(n_partials_most, self.xgmi.n_partials)
-        elif self.world_size > 1 and os.environ.get("NAF_XGMI", "1") != "0":
-            self.xgmi = XgmiAllReduce.try_create(P, dev, self.pg)
-            if self.xgmi is not None:
-                n_partials_most = max(n_partials_most, self.xgmi.n_partials)
         self.partials = torch.zeros(n_partials_most + 1, **f32)
-        # the optimizer step of update k carried by the first two launches of update k + 1 (csrc/adam_body.h): the row-split
-        # chain on one rank, gradient norm folded into the producers. NAF_DEFER_ADAM=0 keeps the launch of its own.
-        # Data parallel over peer memory: the one-shot all-reduce launch leaves the norm partials and the step count exactly
-        # as the folded producers do on one rank, so the step can ride there too (the RCCL path keeps its two launches).
-        # The collective path (RCCL, or the test-only forced all-reduce): the norm must be taken on the REDUCED gradient, so a norm
-        # launch stays behind the collective — and the optimizer step rides on the next update behind it all the same (round 4:
-        # one launch and one boundary less per update there too; before, that path kept both launches).
-        self.defer_ok = ("bb" in self.fuse and os.environ.get("NAF_DEFER_ADAM", "1") != "0" and
-                         ((self.fold_norm and self.world_size == 1) or self.world_size > 1 or self._force_allreduce))
         self.adam_bc = torch.zeros(8, **f32)     # the next step's bias corrections, left by the riding optimizer workgroups
         self._adam_args = _lib.AdamArgs(
             ptr(self.theta2[0]), ptr(self.grad), ptr(self.adam_m), ptr(self.adam_v), ptr(self.theta2[1]), ptr(self.partials),
             self.n_partials, MAX_GRAD_NORM, self.lr, ADAM_BETA1, ADAM_BETA2, ADAM_EPS, self.tau, float(1.0 - self.tau),
-            ptr(self.step_dev), 1.0 / self.world_size, P, lay.seg["W2"].offset, ptr(self.adam_bc))
-        self._gb_wh_blocks = ((NHP + 31) // 32) * ((HP + 31) // 32)
-        self._gb_blocks, self._ft_blocks = gb_blocks, ft_blocks
-        # loss partials per update: one per workgroup of the head launch (8 samples each; 4 beyond 32 joints, csrc/naf_head_wide.hip)
-        self.n_loss_wg = (B + 7) // 8 if lay.A <= 32 else (B + 3) // 4
+            ptr(self.step_dev), 1.0 / self.world_size, P, self.lay.seg["W2"].offset, ptr(self.adam_bc))
         # a poll inside a fused launch that gave up on the folded records and folded for itself (csrc/bn2bwd_fold.h) bumps this
         # pinned HOST word; fold_fallbacks reads it without synchronising
         self.err_host = torch.zeros(8, dtype=torch.int64).pin_memory()
 
-        # ---- work buffers for one minibatch ------------------------------------------------------------
+    def _alloc_work_buffers(self) -> None:
+        """Work buffers for one minibatch: Bp rows (chain_plan.py says why), zero-initialised."""
+        lay, B, Bp, f32 = self.lay, self.B, self.Bp, self._f32
+        H, HP, NHP = lay.H, lay.HP, lay.NHP
         self.G1 = torch.zeros(2, Bp, H, **f32)
         self.A1 = torch.zeros(2, Bp, H, **f32)
         self.G2 = torch.zeros(2, Bp, H, **f32)
@@ -361,32 +199,17 @@ class Learner:
         self.save_mean = torch.empty(2, 2, H, **f32)         # [layer][net][H]
         self.save_invstd = torch.empty(2, 2, H, **f32)
         self.q_out = torch.empty(B, **f32)
-        if "bb" in self.fuse:
-            NB = -(-B // 64)                                     # 64-row statistics blocks (the last may hold 16, 32 or 48 rows)
-            NB1 = -(-Bp // 32)                                   # 32-row blocks of the bundle's dA1 product (M = Bp rows)
-            kp = self.lib.naf_bb_layer1_bwd_kp(lay.S)
-            # moments record of one minibatch's layer-1 inputs, [net][Sx | C]: everything layer 1's BatchNorm needs from
-            # the batch dimension (TrainChunk computes the records of all its minibatches in one launch behind the gather)
-            self.mom_floats = self.lib.naf_bb_moments_floats(lay.S)
-            self.bb_mom = torch.zeros(2, self.mom_floats, **f32)
-            self.bb_wc = torch.zeros(H, kp, **f32)               # w_c C of the main net, forward -> finish
-            self.bb_st2 = torch.zeros(2, NB, H, 2, **f32)        # layer-2 statistics partials per 64-row block: (sum, M2)
-            self.hk_rows = self.lib.naf_bb_layer2_head_rows(B)    # rows per block of the fused launch's backward partials
-            self.bb_bw2 = torch.zeros(Bp // self.hk_rows, H, 2, **f32)   # backward partials of layer 2: (sum dy, sum dy*xhat)
-            self.bb_bw1 = torch.zeros(NB1, H, 2, **f32)           # backward partials of layer 1, per 32-row block of the bundle
-            self.bb_dw1 = torch.zeros(NB1, H, kp, **f32)          # per-block shares of P = dY1^T X
-            self._nb1 = NB1
-        if "s3" in self.fuse:
-            # split-K heads: one [B, NHP] slab per 8-column workgroup of layer 2's BN kernel (+ the target's V column)
-            # slabs 256 B further apart than their size: the H/8 pieces of one row, read together by the head kernel,
-            # then sit in different L2 channels instead of one (32-KB stride: 6.6 us per head launch, padded: see DESIGN)
-            self.n_slabs = H // 8
-            self.slab_stride = B * NHP + 64
-            self.heads_partial = torch.zeros(self.n_slabs * self.slab_stride, **f32)
-            self.vnext_partial = torch.zeros(self.n_slabs, B, **f32)
 
-        # ---- GEMM operand views (built once: no per-call tensor construction on the hot path) -------------
-        seg = lay.seg
+    def _alloc_head_slabs(self) -> None:
+        """The column-tile chain's split-K heads: n_slabs slabs of [B, NHP], slab_stride floats apart (chain_plan.py)."""
+        self.heads_partial = torch.zeros(self.n_slabs * self.slab_stride, **self._f32)
+        self.vnext_partial = torch.zeros(self.n_slabs, self.B, **self._f32)
+
+    def _make_gemm_views(self) -> None:
+        """GEMM operand views (built once: no per-call tensor construction on the hot path) and the backward bundle of the
+        column-tile / unfused chains."""
+        lay, B = self.lay, self.B
+        seg, H, HP, NHP = lay.seg, lay.H, lay.HP, lay.NHP
         t2 = self.theta2
         self.W1T2 = t2[:, seg["W1"].offset:seg["W1"].offset + seg["W1"].numel].view(2, H, lay.S).transpose(1, 2)
         self.W2T2 = t2[:, seg["W2"].offset:seg["W2"].offset + seg["W2"].numel].view(2, H, H).transpose(1, 2)
@@ -399,7 +222,6 @@ class Learner:
         self.gW1 = lay.view(self.grad, "W1")
         self.gW2 = lay.view(self.grad, "W2")
         self.gWh = lay.view(self.grad, "Wh")
-        self._f = self.lib  # shorthand
         D = _lib.GemmDesc
         pp = self.partials.data_ptr()
         sq_wh = pp if self.fold_norm else None
@@ -409,93 +231,85 @@ class Learner:
             D(ptr(self.dZ2), ptr(self.A1[0]), ptr(self.gW2), sq_w2, H, H, B, H, H, H, 1, 1),                  # dW2
             D(ptr(self.dZ2), ptr(self.W2_main), ptr(self.dA1), None, B, H, H, H, H, H, 0, 1))                 # dA1
         self._bb_segs, self._bb_nsegs = None, 0
-        if "bb" in self.fuse:
-            # The weight gradients reduce over K = B. Cut K into ranges, one grid of blocks each, writing partial slabs that
-            # the layer-1 finish launch adds in slab order (and takes the norm partials of): 256-row ranges — with every launch
-            # of the chain working by eighths of the batch (csrc/big_batch.hip, bb_place_rows) a 256-row range is what one XCD
-            # (or two) already holds of dY2, Z2 and A1. For dW2 twice as long (512 rows) where the launch would otherwise not fit
-            # the chip at once — more than the 1024 blocks the four-wave form of the bundle has room for: B = 2048 (1096 blocks
-            # with eight ranges, 840 with four). Updates/s with 256- | 512-row ranges, A/B/A/B on one box at the end of round 3:
-            # B = 1024 28.0k | 27.0k, 1536 22.7k | 22.0k, 2048 20.9k | 21.3k. (Round 2 had it the other way round at 1024 — 420
-            # blocks in one round of the eight-wave form against 548 — before the rows went to the XCDs by eighths.) Batch sizes
-            # that are not multiples of 256: as many equal ranges (<= 8, whole 64-row blocks) as divide B / 64.
-            def k_ranges(target, most):
-                """largest number of equal K ranges <= most, each whole 16-k steps and at least `target` rows long"""
-                return max([d for d in range(1, most + 1) if Bp % d == 0 and (Bp // d) % 16 == 0 and Bp // d >= target] or [1])
 
-            def blocks(M, N, k_split):
-                """32 x 32 blocks of one product of the bundle (csrc/gemm_bundle.hip)"""
-                return ((M + 31) // 32) * ((N + 31) // 32) * k_split
-            ks = Bp // 256 if (Bp % 256 == 0 and Bp <= 2048) else k_ranges(256, 8)      # (at most 8 slabs: csrc/big_batch.hip)
-            ks_w2 = ks_wh = ks
-            # (round 4's LDS-DMA ring form of this launch measured slower at every size: benchmarks/experimental/gemm_ring.h)
-            if blocks(Bp, H, 1) + blocks(H, H, ks) + blocks(NHP, HP, ks) + 8 > 1024 and ks % 2 == 0 and \
-                    (Bp // (ks // 2)) % 256 == 0:
-                ks_w2 = ks // 2
-            self.bb_slab_w2 = torch.zeros(ks_w2, H * H, **f32)
-            self.bb_slab_wh = torch.zeros(ks_wh, NHP * HP, **f32)
-            t2p_, seg_, gp_ = self.theta2.data_ptr(), lay.seg, self.grad.data_ptr()
-            # ep: the batch pass of layer 1's backward as the epilogue of the dA1 blocks (x / ldx: set per minibatch)
-            # (xhat of layer 1 kept by the forward pass for the epilogue up to B = 512 — one round of blocks, where recomputing it
-            # sat on the critical path: updates/s 36.0k -> 36.8k at B = 64, 35.2k -> 36.0k at 128, 34.6k -> 35.1k at 256, 31.25k ->
-            # 31.5k at 512; beyond that the recomputation hides and the extra B x H floats each way do not: 28.3k -> 27.7k at 1024)
-            self.XH1 = torch.zeros(Bp, H, **f32) if B <= 512 else None
-            self._epi = _lib.GemmL1Bwd(None, t2p_ + 4 * seg_["W1"].offset, t2p_ + 4 * seg_["b1"].offset, ptr(self.A1[0]),
-                                       ptr(self.save_mean[0, 0]), ptr(self.save_invstd[0, 0]), ptr(self.bb_bw1), ptr(self.bb_dw1),
-                                       0, lay.S, self.lib.naf_bb_layer1_bwd_kp(lay.S), H, ptr(self.XH1),
-                                       t2p_ + 4 * seg_["g1"].offset, t2p_ + 4 * seg_["be1"].offset, B)
-            # s2: dY2 -> dZ2 while the two products that read it stage their A panels; the block sums folded once per launch
-            # by the bundle's first workgroups and handed on as tagged records (csrc/gemm_bundle.hip, gemm_bn2bwd_fold_block)
-            self.bb_cst = torch.zeros(H, 4, **f32)                                        # per-column constants of the launch
-            self.bb_fold_flag = torch.ones(1, dtype=torch.int32, device=dev)              # launch number: finish advances it; never restored
-            self._pro = _lib.GemmBn2Bwd(ptr(self.G2[0]), ptr(self.bb_bw2), t2p_ + 4 * seg_["g2"].offset, ptr(self.save_mean[1, 0]),
-                                        ptr(self.save_invstd[1, 0]), gp_ + 4 * seg_["g2"].offset, gp_ + 4 * seg_["be2"].offset,
-                                        Bp // self.hk_rows, B, H, ptr(self.bb_cst), ptr(self.bb_fold_flag), self.err_host.data_ptr())
-            pro_ = _lib.C.addressof(self._pro)
-            # layer 2's forward statistics folded once per launch too where a workgroup would pull more than 16 blocks of them
-            # (B > 1024; the library decides): records of their own, the same launch counter and error word
-            self.bb_stat_rec = torch.zeros(2 * H, 4, **f32)
-            # (H = 512: the fused layer-2 launch runs two workgroups per row block, one per 256-column half; their partial heads meet here)
-            self.bb_exchange = torch.zeros(max(4, self.lib.naf_bb_layer2_head_exchange_floats(B, NHP)), **f32) if H > 256 else None
-            self._stats_once_s = _lib.BbStatsOnce(ptr(self.bb_stat_rec), ptr(self.bb_fold_flag), self.err_host.data_ptr(),
-                                                  ptr(self.bb_exchange))
-            self._stats_once = _lib.C.byref(self._stats_once_s)
-            # dA1 FIRST: its blocks carry the layer-1 epilogue and run longest; dispatched first, the short weight-gradient
-            # blocks fill in behind them instead of the other way round
-            self._bundle = (D * 3)(
-                D(ptr(self.dZ2), ptr(self.W2_main), None, None, Bp, H, H, H, H, H, 0, 1, 1, 0, _lib.C.addressof(self._epi), pro_),
-                D(ptr(self.dZ2), ptr(self.A1[0]), ptr(self.bb_slab_w2), None, H, H, Bp, H, H, H, 1, 1, ks_w2, H * H, None, pro_),
-                D(ptr(self.dH), ptr(self.A2[0]), ptr(self.bb_slab_wh), None, NHP, HP, Bp, NHP, HP, HP, 1, 1, ks_wh, NHP * HP))
-            SS = _lib.SlabSeg
-            self._bb_segs = (SS * 2)(SS(ptr(self.bb_slab_w2), ptr(self.gW2), H * H, H * H, ks_w2),
-                                     SS(ptr(self.bb_slab_wh), ptr(self.gWh), NHP * HP, NHP * HP, ks_wh))
-            self._bb_nsegs = 2
-        # ---- which form the gradient exchange takes (data parallel) -------------------------------------------------------
-        if self.world_size > 1:
-            want_x = os.environ.get("NAF_DP_EXCHANGE", "auto").lower()
-            if want_x not in ("auto", "fastest", "oneshot", "merged", "rccl"):
-                raise ValueError(f"NAF_DP_EXCHANGE = {want_x!r}: one of auto, fastest, oneshot, merged, rccl")
-            forms = self.exchange_forms()
-            self._exchange_pick = want_x
-            if want_x in ("auto", "fastest"):
-                self._set_exchange(forms[0])
-                if len(forms) > 1:
-                    self.autotune_exchange()
-            else:
-                if want_x not in forms:
-                    raise _lib.NafHipError(f"NAF_DP_EXCHANGE={want_x}: not available here (forms: {forms})")
-                self._set_exchange(want_x)
+    def _alloc_row_split(self) -> None:
+        """The row-split chain's own buffers and the descriptors of its backward bundle (prologue s2, epilogue ep); the counts are
+        the plan's."""
+        plan, lay, B, Bp, dev, f32 = self.plan, self.lay, self.B, self.Bp, self.dev, self._f32
+        H, HP, NHP, kp = lay.H, lay.HP, lay.NHP, plan.kp
+        ks_w2, ks_wh = plan.ks_w2, plan.ks_wh
+        # moments record of one minibatch's layer-1 inputs, [net][Sx | C]: everything layer 1's BatchNorm needs from
+        # the batch dimension (TrainChunk computes the records of all its minibatches in one launch behind the gather)
+        self.bb_mom = torch.zeros(2, self.mom_floats, **f32)
+        self.bb_wc = torch.zeros(H, kp, **f32)               # w_c C of the main net, forward -> finish
+        self.bb_st2 = torch.zeros(2, plan.nb, H, 2, **f32)   # layer-2 statistics partials per 64-row block: (sum, M2)
+        self.bb_bw2 = torch.zeros(Bp // self.hk_rows, H, 2, **f32)   # backward partials of layer 2: (sum dy, sum dy*xhat)
+        self.bb_bw1 = torch.zeros(self._nb1, H, 2, **f32)    # backward partials of layer 1, per 32-row block of the bundle
+        self.bb_dw1 = torch.zeros(self._nb1, H, kp, **f32)   # per-block shares of P = dY1^T X
+        # the split-K slabs of the two weight-gradient products, added in slab order by the finish launch
+        self.bb_slab_w2 = torch.zeros(ks_w2, H * H, **f32)
+        self.bb_slab_wh = torch.zeros(ks_wh, NHP * HP, **f32)
+        t2p_, seg_, gp_ = self.theta2.data_ptr(), lay.seg, self.grad.data_ptr()
+        # ep: the batch pass of layer 1's backward as the epilogue of the dA1 blocks (x / ldx: set per minibatch)
+        # (xhat of layer 1 kept by the forward pass for the epilogue where the plan says so: keep_xhat1)
+        self.XH1 = torch.zeros(Bp, H, **f32) if plan.keep_xhat1 else None
+        self._epi = _lib.GemmL1Bwd(None, t2p_ + 4 * seg_["W1"].offset, t2p_ + 4 * seg_["b1"].offset, ptr(self.A1[0]),
+                                   ptr(self.save_mean[0, 0]), ptr(self.save_invstd[0, 0]), ptr(self.bb_bw1), ptr(self.bb_dw1),
+                                   0, lay.S, kp, H, ptr(self.XH1),
+                                   t2p_ + 4 * seg_["g1"].offset, t2p_ + 4 * seg_["be1"].offset, B)
+        # s2: dY2 -> dZ2 while the two products that read it stage their A panels; the block sums folded once per launch
+        # by the bundle's first workgroups and handed on as tagged records (csrc/gemm_bundle.hip, gemm_bn2bwd_fold_block)
+        self.bb_cst = torch.zeros(H, 4, **f32)                                        # per-column constants of the launch
+        self.bb_fold_flag = torch.ones(1, dtype=torch.int32, device=dev)              # launch number: finish advances it; never restored
+        self._pro = _lib.GemmBn2Bwd(ptr(self.G2[0]), ptr(self.bb_bw2), t2p_ + 4 * seg_["g2"].offset, ptr(self.save_mean[1, 0]),
+                                    ptr(self.save_invstd[1, 0]), gp_ + 4 * seg_["g2"].offset, gp_ + 4 * seg_["be2"].offset,
+                                    Bp // self.hk_rows, B, H, ptr(self.bb_cst), ptr(self.bb_fold_flag), self.err_host.data_ptr())
+        pro_ = _lib.C.addressof(self._pro)
+        # layer 2's forward statistics folded once per launch too where a workgroup would pull more than 16 blocks of them
+        # (B > 1024; the library decides): records of their own, the same launch counter and error word
+        self.bb_stat_rec = torch.zeros(2 * H, 4, **f32)
+        # (H = 512: the two workgroups of a row block of the fused layer-2 launch meet here)
+        self.bb_exchange = torch.zeros(plan.exchange_floats, **f32) if plan.exchange_floats is not None else None
+        self._stats_once_s = _lib.BbStatsOnce(ptr(self.bb_stat_rec), ptr(self.bb_fold_flag), self.err_host.data_ptr(),
+                                              ptr(self.bb_exchange))
+        self._stats_once = _lib.C.byref(self._stats_once_s)
+        # dA1 FIRST: its blocks carry the layer-1 epilogue and run longest; dispatched first, the short weight-gradient
+        # blocks fill in behind them instead of the other way round
+        D = _lib.GemmDesc
+        self._bundle = (D * 3)(
+            D(ptr(self.dZ2), ptr(self.W2_main), None, None, Bp, H, H, H, H, H, 0, 1, 1, 0, _lib.C.addressof(self._epi), pro_),
+            D(ptr(self.dZ2), ptr(self.A1[0]), ptr(self.bb_slab_w2), None, H, H, Bp, H, H, H, 1, 1, ks_w2, H * H, None, pro_),
+            D(ptr(self.dH), ptr(self.A2[0]), ptr(self.bb_slab_wh), None, NHP, HP, Bp, NHP, HP, HP, 1, 1, ks_wh, NHP * HP))
+        SS = _lib.SlabSeg
+        self._bb_segs = (SS * 2)(SS(ptr(self.bb_slab_w2), ptr(self.gW2), H * H, H * H, ks_w2),
+                                 SS(ptr(self.bb_slab_wh), ptr(self.gWh), NHP * HP, NHP * HP, ks_wh))
+        self._bb_nsegs = 2
+
+    def _pick_exchange(self) -> None:
+        """Which form the gradient exchange takes (data parallel): the pinned one, or the fastest measured here."""
+        want_x = os.environ.get("NAF_DP_EXCHANGE", "auto").lower()
+        if want_x not in ("auto", "fastest", "oneshot", "merged", "rccl"):
+            raise ValueError(f"NAF_DP_EXCHANGE = {want_x!r}: one of auto, fastest, oneshot, merged, rccl")
+        forms = self.exchange_forms()
+        self._exchange_pick = want_x
+        if want_x in ("auto", "fastest"):
+            self._set_exchange(forms[0])
+            if len(forms) > 1:
+                self.autotune_exchange()
+        else:
+            if want_x not in forms:
+                raise _lib.NafHipError(f"NAF_DP_EXCHANGE={want_x}: not available here (forms: {forms})")
+            self._set_exchange(want_x)
 
     # ---- data parallel: the form of the gradient exchange -------------------------------------------------------------
     def exchange_forms(self):
         """The forms this learner can run, fastest-in-the-rehearsal first: see the constructor."""
         if self.world_size == 1:
             return ["none"]
-        seg, P = self.lay.seg, self.lay.P
         forms = []
         if self.xgmi is not None:
             forms.append("oneshot")
-            if "bb" in self.fuse and seg["Wh"].offset + seg["Wh"].numel == P:
+            if "bb" in self.fuse and self.lay.ends_with_wh:
                 forms.append("merged")
         return forms + ["rccl"]
 
@@ -843,7 +657,7 @@ class Learner:
         # all-reduce launch behind this one sends only the layer-1 / BatchNorm segments before it raises its flags
         push = None
         merged = False
-        if self._xg is not None and seg["Wh"].offset + seg["Wh"].numel == P:      # (Wh ends the buffer: no pad behind it)
+        if self._xg is not None and lay.ends_with_wh:                             # (Wh ends the buffer: no pad behind it)
             if self._push_desc is None:
                 self._push_desc = self._xg.push_desc()
             push = _lib.C.byref(self._push_desc)
@@ -976,11 +790,9 @@ class ActPath:
         self.actions = torch.zeros(E, lay.A, **f32)
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.counter = torch.zeros(1, dtype=torch.int64, device=dev)   # noise stream position (uint64 on device)
-        # one launch for the whole act() (csrc/policy_act.hip) when the shapes are the framework's (H = 256, S <= 32);
+        # one launch for the whole act() (csrc/policy_act.hip) where the plan says the shape takes it (chain_plan.py: act_fused);
         # other shapes take the seven-launch path (3 GEMMs, 2 BN kernels, noise, counter)
-        # (round 6: up to 11 joints — the state's group in the noise body is then 16 lanes wide)
-        #  and layer sizes up to 512 — stored as 512: policy_act_512_kernel)
-        self.fused = lay.H in (256, 512) and lay.S <= 32 and lay.A <= BB_MAX_JOINTS
+        self.fused = learner.plan.act_fused
         self._ticket = torch.zeros(1, dtype=torch.int32, device=dev)
         self.host_io = bool(host_io) and self.fused
         if self.host_io:

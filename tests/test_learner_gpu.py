@@ -176,6 +176,57 @@ def test_learn_vs_oracle_both_modes(p_mode, S, A, B, fused, monkeypatch):
         np.testing.assert_allclose(cur[name], Or.main[name], rtol=2e-2, atol=2e-3)
 
 
+@pytest.mark.parametrize("S,A,H,B,pad", [(21, 6, 256, 16, True), (21, 6, 256, 15, True), (40, 4, 256, 32, True), (27, 9, 256, 2048, True),
+                                         (23, 7, 256, 2049, True), (21, 6, 512, 300, True), (21, 6, 384, 64, False)])
+def test_learner_carries_what_plan_chain_says(S, A, H, B, pad, monkeypatch):
+    """The learner on the device against chain_plan.plan_chain (which tests/test_chain_plan_cpu.py holds to the recorded table):
+    every attribute copied from the plan, the buffers sized by it — at one shape per chain and padding rule (16-row groups, 64-row
+    blocks beyond B = 256, the column-tile chain with and without its split-K heads, both halves of H = 512) — and one update
+    through the launches that read them."""
+    monkeypatch.delenv("NAF_FUSE", raising=False)
+    from robotic_manipulator_rloa_amd.chain_plan import plan_chain
+    from robotic_manipulator_rloa_amd.learner import Learner
+    plan = plan_chain(S, A, H, B, pad_layer=pad)
+    assert plan.warning is None
+    L = Learner(S, A, H, B, 1e-3, 1e-3, 0.99, torch.device("cuda"), pad_layer=pad)
+    lay = L.lay
+    assert L.plan == plan
+    assert (L.chain, L.fuse, L.bb_ok, L.Bp, L.hk_rows, L.fold_norm, L.defer_ok) == \
+        (plan.chain, plan.fuse, plan.bb_ok, plan.Bp, plan.hk_rows, plan.fold_norm, plan.defer_ok)
+    assert (L.n_partials, L.n_partials_fold, L.n_partials_norm, L.n_loss_wg) == \
+        (plan.n_partials, plan.n_partials_fold, plan.n_partials_norm, plan.n_loss_wg)
+    assert (L._nb1, L._gb_blocks, L._ft_blocks, L._gb_wh_blocks, L.mom_floats, L.n_slabs, L.slab_stride) == \
+        (plan.nb1, plan.gb_blocks, plan.ft_blocks, plan.gb_wh_blocks, plan.mom_floats, plan.n_slabs, plan.slab_stride)
+    assert L.A1.shape == (2, plan.Bp, lay.H)
+    assert L.partials.numel() == max(plan.n_partials_fold + 1, plan.n_partials_norm, plan.n_partials) + 1
+    if plan.chain == "rows":
+        assert L.bb_slab_w2.shape == (plan.ks_w2, lay.H * lay.H) and L.bb_slab_wh.shape == (plan.ks_wh, lay.NHP * lay.HP)
+        assert (L.XH1.shape == (plan.Bp, lay.H)) if plan.keep_xhat1 else L.XH1 is None
+        assert L.bb_st2.shape == (2, plan.nb, lay.H, 2) and L.bb_dw1.shape == (plan.nb1, lay.H, plan.kp)
+        assert (L.bb_exchange.numel() if lay.H > 256 else L.bb_exchange) == plan.exchange_floats
+    else:
+        assert not hasattr(L, "bb_slab_w2") and not hasattr(L, "bb_slab_wh") and not hasattr(L, "XH1")
+    if "s3" in plan.fuse:
+        assert L.heads_partial.shape == (plan.n_slabs * plan.slab_stride,)
+    else:
+        assert not hasattr(L, "heads_partial") and plan.n_slabs is None
+    from robotic_manipulator_rloa_amd.learner import ActPath
+    assert ActPath(L, 1, seed=0).fused == plan.act_fused
+    g = torch.Generator(device="cuda").manual_seed(5)
+    for v in L.main_views().values():
+        v.normal_(0, 0.05, generator=g)
+    L.main_views()["bn1.weight"].fill_(1.0)
+    L.main_views()["bn2.weight"].fill_(1.0)
+    L.theta2[1].copy_(L.theta2[0])
+    rows = torch.randn(B, lay.row_floats, generator=g, device="cuda")
+    rows[:, S:S + A].clamp_(-1, 1).trunc_()
+    lp = torch.zeros(L.n_loss_wg, device="cuda")
+    L.learn_rows(rows, lp)
+    torch.cuda.synchronize()
+    assert torch.isfinite(lp).all() and torch.isfinite(L.theta2).all()
+    assert L.fold_fallbacks == 0
+
+
 def test_learn_at_batch_20000_vs_oracle():
     """the reference takes any positive batch_size (rl_framework.py:186-189); round 5 stopped at 16384 (the
     device-memory sampler packed a table slot into 16 bits). Now 2^20: three updates at B = 20000 on the unfused chain (streamed
