@@ -300,7 +300,7 @@ def ik(a):
     import numpy as np
     import torch
     from robotic_manipulator_rloa_amd import _lib
-    from robotic_manipulator_rloa_amd.engine import GoalPoseSolver
+    from robotic_manipulator_rloa_amd.chain_tools import GoalPoseSolver
     from robotic_manipulator_rloa_amd.environment.kinematic import KinematicEnvironment, goal_poses_host
     from robotic_manipulator_rloa_amd.environment.urdf_chain import compile_chain, load_urdf
     N, R, K, n = (4096 if a.envs == 64 else a.envs), 8, 32, a.joints
@@ -353,7 +353,7 @@ def paths(a):
     import numpy as np
     import torch
     from robotic_manipulator_rloa_amd import _lib
-    from robotic_manipulator_rloa_amd.engine import GoalPoseSolver, JointPathChecker
+    from robotic_manipulator_rloa_amd.chain_tools import GoalPoseSolver, JointPathChecker
     from robotic_manipulator_rloa_amd.environment.kinematic import path_vias
     from robotic_manipulator_rloa_amd.environment.urdf_chain import compile_chain, load_urdf
     N, C, S, n = (2048 if a.envs == 64 else a.envs), 16, 256, a.joints
@@ -444,7 +444,7 @@ def _paths_certified(a, checker, model, N, C, S, launches, init, rng, urdf):
     import numpy as np
     import torch
     from robotic_manipulator_rloa_amd import _lib
-    from robotic_manipulator_rloa_amd.engine import GoalPoseSolver
+    from robotic_manipulator_rloa_amd.chain_tools import GoalPoseSolver
     times = {"check": [], "certify": []}
     for i in range(launches + 2):                              # alternating, so that both see the same clocks
         for name, launch in (("check", checker.launch), ("certify", checker.launch_certify)):
@@ -490,7 +490,7 @@ def _paths_roadmap(a, checker, model, N, C, S, launches, init, rng, urdf, q_star
     import numpy as np
     import torch
     from robotic_manipulator_rloa_amd import _lib
-    from robotic_manipulator_rloa_amd.engine import GoalPoseSolver
+    from robotic_manipulator_rloa_amd.chain_tools import GoalPoseSolver
     from robotic_manipulator_rloa_amd.environment.kinematic import roadmap_edges, roadmap_milestones, roadmap_nodes
     M, V = a.roadmap, a.roadmap + 2
     edges = roadmap_edges(V)
@@ -551,7 +551,7 @@ def demo(a):
     import numpy as np
     import torch
     from robotic_manipulator_rloa_amd import _lib
-    from robotic_manipulator_rloa_amd.engine import DemonstrationWriter
+    from robotic_manipulator_rloa_amd.chain_tools import DemonstrationWriter
     from robotic_manipulator_rloa_amd.environment.kinematic import demo_actions, demonstration_plan
     from robotic_manipulator_rloa_amd.environment.urdf_chain import compile_chain, load_urdf
     N, T, n = (2048 if a.envs == 64 else a.envs), 400, a.joints

@@ -10,11 +10,8 @@
                    U = E * num_updates / update_freq so the reference's update-to-data ratio is kept.
   DeviceRollout  : the policy run as a QUERY on a chain model: given start poses and scenes, act -> rollout step as ONE graph per
                    frame, an env held at the end of its episode; outcome, clearances and joint paths come back (ReachResult).
-  GoalPoseSolver : joint values that reach given targets on a chain model: batched damped least squares over queries x restarts,
-                   the pinned clearances at the solved poses, the selection per query (GoalPoses). No agent, no graph.
-  JointPathChecker : sampled collision checks of start -> via -> goal joint paths on a chain model: ONE launch over queries x
-                   candidate vias x samples, eight floats per candidate back, the choice per query on the host (JointPaths).
-                   certify=True: naf_chain_path_certify's twelve floats and the refinement rounds over the open queries.
+(The chain-model tools that need no agent and capture no graph — GoalPoseSolver, JointPathChecker, DemonstrationWriter — and the
+owner of a model's device handle are chain_tools.py's.)
 
 Graph capture goes through torch.cuda.CUDAGraph (= hipGraph on ROCm): the ctypes kernel launches use the
 stream torch reports as current, which inside the capture context is the capturing stream.
@@ -31,9 +28,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
-from .environment.kinematic import (EDGE_FLOATS, PATH_CERT_FLOATS, PATH_CHUNK, PATH_FLOATS, ROADMAP_MAX, GoalPoses, JointPaths,
-                                    certificate_guard, certify_rounds, gather_certified_paths, gather_goal_poses, gather_joint_paths,
-                                    ik_seeds, path_chunks, path_leg_lengths, path_vias, reach_table, roadmap_round, roadmap_size_ok)
+from .chain_tools import _ChainHandle
 from .learner import ActPath, Learner
 from .presets import ROBOT_PRESETS, device_env_preset
 from .utils.replay_buffer import ReplayBuffer
@@ -836,25 +831,6 @@ class EpisodeLedger:
         return self.scores
 
 
-class _ChainHandle:
-    """The one owner of a chain model's device handle (csrc/chain_env.hip): packs the blob, creates the handle on `self.lib` and
-    destroys it with the object. `_chain_env` stays None until a model is opened."""
-    _chain_env = None
-
-    def _create_chain_env(self, chain) -> None:
-        import ctypes
-        blob = np.ascontiguousarray(chain.pack(), np.float32)
-        handle = ctypes.c_void_p()
-        check(self.lib.naf_chain_env_create(blob.ctypes.data, int(blob.size), ctypes.byref(handle)), "chain_env_create")
-        self.chain, self._chain_env = chain, handle
-        self.has_cell = bool(chain.cell_spheres or chain.cell_planes or chain.cell_boxes)
-
-    def __del__(self):
-        if self._chain_env is not None:
-            self.lib.naf_chain_env_destroy(self._chain_env)
-            self._chain_env = None
-
-
 class DeviceEnvLoop(_ChainHandle):
     """E manipulator envs living on the GPU, driven by the agent's policy: the synthetic stand-in (csrc/synth_env.hip) or, with
     `chain`, E copies of the arm a URDF describes (csrc/chain_env.hip; environment/urdf_chain.py compiles the model).
@@ -1202,324 +1178,3 @@ class DeviceRollout(_ChainHandle):
         return ReachResult(OUTCOME_NAMES[outcome[:, 0].astype(np.int64)], outcome[:, 1].astype(np.int64), outcome[:, 2].copy(),
                            outcome[:, 3].copy(), outcome[:, 4].copy(), outcome[:, 5].copy(), paths, target_start, start[:, 3].copy(),
                            start[:, 4].copy(), outcome[:, 6].copy() if self.has_cell else np.full(N, np.inf, np.float32), start_cell)
-
-
-class GoalPoseSolver(_ChainHandle):
-    """Goal poses on a chain model (csrc/chain_env.hip, "goal poses"): per chunk of candidates naf_chain_ik_solve, then the
-    clearances of the solved poses by naf_chain_env_reset_given + naf_chain_env_probe (+ naf_chain_env_probe_cell with a workcell),
-    then naf_chain_ik_select. Owns the handle and the buffers; needs no agent. A chunk holds a fixed number of candidates,
-    `chunk` rounded down to whole queries; a query's result does not depend on the chunk or the lane it lands in."""
-    CHUNK = 32768
-
-    def __init__(self, chain, obstacle_radius: float = 0.06, chunk: Optional[int] = None, device=None):
-        _lib.require_gpu()
-        self.lib, self.chain, self.A = _lib.load(), chain, chain.A
-        self.dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-        self.obstacle_radius = float(np.float32(obstacle_radius))
-        self.chunk = int(self.CHUNK if chunk is None else chunk)
-        if self.chunk < 64:
-            raise ValueError("GoalPoseSolver: a chunk holds at least 64 candidates")
-        self._create_chain_env(chain)
-        C, A = self.chunk, self.A
-        f32, i32 = dict(dtype=torch.float32, device=self.dev), dict(dtype=torch.int32, device=self.dev)
-        self.targets, self.q_start, self.seeds = torch.zeros(C, 3, **f32), torch.zeros(C, A, **f32), torch.zeros(C, A, **f32)
-        self.q, self.residual, self.distance = torch.zeros(C, A, **f32), torch.zeros(C, **f32), torch.zeros(C, **f32)
-        self.env_state = torch.zeros(C, self.lib.naf_chain_env_state_floats(self._chain_env), **f32)
-        self.obs, self.scene = torch.zeros(C, 2 * A + 9, **f32), torch.zeros(C, 6, **f32)
-        self.probe, self.cell = torch.zeros(C, 5, **f32), torch.full((C,), float("inf"), **f32)
-        self.choice, self.cls = torch.zeros(C, **i32), torch.zeros(C, **i32)
-
-    def params(self, iterations: int, lam=None, e_max=None, dq_max=None) -> "_lib.IkParams":
-        reach = self.chain.reach
-        lam = 0.05 * reach if lam is None else lam
-        return _lib.IkParams(int(iterations), float(lam) ** 2, float(0.25 * reach if e_max is None else e_max),
-                             float(0.5 if dq_max is None else dq_max))
-
-    def launch(self, n: int, R: int, prm, tolerance: float, margin: float, solve_only: bool = False) -> None:
-        """the launches of one chunk of n queries x R restarts already in the buffers, on the current stream"""
-        st, E = stream_ptr(), n * R
-        check(self.lib.naf_chain_ik_solve(self._chain_env, ptr(self.targets), ptr(self.q_start), ptr(self.seeds), n, R, prm, ptr(self.q),
-                                          ptr(self.residual), None, st), "chain_ik_solve")
-        if solve_only:
-            return
-        check(self.lib.naf_chain_env_reset_given(self._chain_env, ptr(self.env_state), ptr(self.obs), E, ptr(self.q), ptr(self.scene),
-                                                 self.obstacle_radius, st), "chain_env_reset_given")
-        check(self.lib.naf_chain_env_probe(self._chain_env, ptr(self.env_state), ptr(self.probe), E, st), "chain_env_probe")
-        if self.has_cell:
-            check(self.lib.naf_chain_env_probe_cell(self._chain_env, ptr(self.env_state), ptr(self.cell), E, st), "chain_env_probe_cell")
-        check(self.lib.naf_chain_ik_select(self._chain_env, ptr(self.q), ptr(self.q_start), ptr(self.residual), ptr(self.probe),
-                                           ptr(self.cell) if self.has_cell else None, n, R, tolerance, margin, ptr(self.choice),
-                                           ptr(self.cls), ptr(self.distance), st), "chain_ik_select")
-
-    def load(self, q0, targets, obstacles, seeds) -> None:
-        """a chunk's queries into the buffers: q0[n][A], targets[n][3], obstacles[n][3], seeds[n][R][A] (float32)"""
-        n, R = seeds.shape[:2]
-        self.targets[:n].copy_(torch.from_numpy(np.ascontiguousarray(targets, np.float32)))
-        self.q_start[:n].copy_(torch.from_numpy(np.ascontiguousarray(q0, np.float32)))
-        self.seeds[:n * R].copy_(torch.from_numpy(np.ascontiguousarray(seeds, np.float32).reshape(n * R, self.A)))
-        scene = np.concatenate([np.asarray(targets, np.float32), np.asarray(obstacles, np.float32)], axis=1)
-        self.scene[:n * R].copy_(torch.from_numpy(np.repeat(scene, R, axis=0)))
-
-    def solve(self, q0, targets, obstacles, restarts: int = 8, iterations: int = 32, tolerance: float = 1e-3, margin: float = 0.0,
-              seed: int = 0, **constants) -> GoalPoses:
-        """q0[N][A] (action order), targets[N][3], obstacles[N][3] -> GoalPoses of numpy arrays (float32 where the device's)."""
-        A, R = self.A, int(restarts)
-        q0 = np.ascontiguousarray(q0, np.float32).reshape(-1, A)
-        N = len(q0)
-        targets, obstacles = np.asarray(targets, np.float32).reshape(N, 3), np.asarray(obstacles, np.float32).reshape(N, 3)
-        seeds = ik_seeds(self.chain, N, R, seed)
-        prm = self.params(iterations, **constants)
-        tolerance, margin = float(np.float32(tolerance)), float(np.float32(margin))
-        per = self.chunk // R
-        parts = []
-        for first in range(0, N, per):
-            n = min(per, N - first)
-            sl = slice(first, first + n)
-            self.load(q0[sl], targets[sl], obstacles[sl], seeds[sl])
-            self.launch(n, R, prm, tolerance, margin)
-            E = n * R
-            cell = self.cell[:E].cpu().numpy() if self.has_cell else np.full(E, np.inf, np.float32)
-            probe = self.probe[:E].cpu().numpy().reshape(n, R, 5)
-            parts.append(gather_goal_poses(self.choice[:n].cpu().numpy(), self.cls[:n].cpu().numpy(),
-                                           self.q[:E].cpu().numpy().reshape(n, R, A), self.residual[:E].cpu().numpy().reshape(n, R),
-                                           probe[:, :, 3], probe[:, :, 4], cell.reshape(n, R),
-                                           self.distance[:E].cpu().numpy().reshape(n, R), np.float32(tolerance)))
-        return GoalPoses(*[np.concatenate([getattr(p, f) for p in parts]) for f in GoalPoses._fields])
-
-
-class JointPathChecker(_ChainHandle):
-    """Collision-checked joint paths on a chain model (csrc/chain_env.hip, "joint paths"): per chunk of queries ONE
-    naf_chain_path_check launch over queries x candidate vias, S sampled poses each, formed on the fly — no pose is materialised and
-    eight floats per candidate come back; the choice among a query's candidates is environment.kinematic.select_joint_path on the
-    host. Owns the handle and the buffers; needs no agent. A chunk holds at most `chunk` candidate-samples (queries x candidates x
-    S, whole queries) and its S is path_samples of its own legs (path_chunks); a candidate's record does not depend on where in a
-    launch it lies. The check is SAMPLED: see JointPaths. certify=True: the launches are naf_chain_path_certify's, twelve floats per
-    candidate, with the model's reach table uploaded once; check() then runs the refinement rounds over the open queries
-    (environment.kinematic.certify_rounds) and fills JointPaths' last three fields. The certifying launch keeps the handle's lanes
-    and adds a reduction row and three small tables to its LDS: an arm with pairs whose rows only just fit a workgroup is refused
-    (NAF_CHAIN_ERR_LDS) where the sampled check runs; joint_paths_host(certify=True) answers it.
-    check(roadmap=M): behind the one-via chunks, the queries that ended 'blocked' get a roadmap of M milestones each
-    (environment.kinematic.roadmap_round): per chunk of whole queries ONE naf_chain_edge_check launch over queries x E edges, S
-    samples each, within the same budget; the node, edge and record buffers are allocated on the first such call. The records — a
-    few KB per blocked query — are downloaded and roadmap_search runs on the host, as the one-via selection does."""
-
-    def __init__(self, chain, obstacle_radius: float = 0.06, chunk: Optional[int] = None, device=None, certify: bool = False):
-        _lib.require_gpu()
-        self.lib, self.chain, self.A = _lib.load(), chain, chain.A
-        self.dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-        self.obstacle_radius = float(np.float32(obstacle_radius))
-        self.chunk = int(PATH_CHUNK if chunk is None else chunk)
-        if self.chunk < 64:
-            raise ValueError("JointPathChecker: a chunk holds at least 64 candidate-samples, one candidate path")
-        self._create_chain_env(chain)
-        K, A = self.chunk // 64, self.A                      # the most candidates a chunk can hold: S is at least 64
-        f32 = dict(dtype=torch.float32, device=self.dev)
-        self.q_start, self.q_goal, self.obstacles = torch.zeros(K, A, **f32), torch.zeros(K, A, **f32), torch.zeros(K, 3, **f32)
-        self.vias, self.out = torch.zeros(K, A, **f32), torch.zeros(K, PATH_FLOATS, **f32)
-        self.certify = bool(certify)
-        if self.certify:
-            self.reach = torch.from_numpy(reach_table(chain)).to(self.dev).contiguous()
-            self.guard = certificate_guard(chain)
-            self.out_cert = torch.zeros(K, PATH_CERT_FLOATS, **f32)
-        self.edge_nodes = self.edge_list = self.edge_out = self.edge_obstacles = None
-        self.edge_launches = 0
-
-    def _edge_buffers(self, n: int, V: int, E: int) -> None:
-        """room for n queries of V nodes and E edges: allocated on the first roadmap call, and again only to grow"""
-        f32 = dict(dtype=torch.float32, device=self.dev)
-        if self.edge_nodes is None or self.edge_nodes.numel() < n * V * self.A:
-            self.edge_nodes = torch.zeros(n * V * self.A, **f32)
-        if self.edge_obstacles is None or len(self.edge_obstacles) < n:
-            self.edge_obstacles = torch.zeros(n, 3, **f32)
-        if self.edge_list is None or len(self.edge_list) < E:
-            self.edge_list = torch.zeros(E, 2, dtype=torch.int32, device=self.dev)
-        if self.edge_out is None or len(self.edge_out) < n * E:
-            self.edge_out = torch.zeros(n * E, EDGE_FLOATS, **f32)
-
-    def load_edges(self, nodes, edges, obstacles) -> None:
-        """a chunk's roadmaps into the buffers: nodes[n][V][A] (float32), edges[E][2] (int32, shared by the chunk's queries),
-        obstacles[n][3]. Every edge is validated here, before the upload: 0 <= i < j < V."""
-        nodes, edges = np.ascontiguousarray(nodes, np.float32), np.ascontiguousarray(edges, np.int32).reshape(-1, 2)
-        n, V = nodes.shape[:2]
-        if len(edges) < 1 or not (np.all(edges[:, 0] >= 0) and np.all(edges[:, 0] < edges[:, 1]) and np.all(edges[:, 1] < V)):
-            raise ValueError(f"JointPathChecker: every roadmap edge is (i, j) with 0 <= i < j < {V}")
-        self._edge_buffers(n, V, len(edges))
-        self.edge_nodes[:nodes.size].copy_(torch.from_numpy(nodes.reshape(-1)))
-        self.edge_list[:len(edges)].copy_(torch.from_numpy(edges))
-        self.edge_obstacles[:n].copy_(torch.from_numpy(np.ascontiguousarray(obstacles, np.float32).reshape(n, 3)))
-
-    def launch_edges(self, n: int, V: int, E: int, S: int, margin: float) -> None:
-        """the edge launch of one chunk of n roadmaps already in the buffers, on the current stream"""
-        check(self.lib.naf_chain_edge_check(self._chain_env, ptr(self.edge_nodes), ptr(self.edge_list), ptr(self.edge_obstacles),
-                                            self.obstacle_radius, n, V, E, S, margin, ptr(self.edge_out), None, stream_ptr()),
-              "chain_edge_check")
-        self.edge_launches += 1
-
-    def launch(self, n: int, C: int, S: int, margin: float) -> None:
-        """the launch of one chunk of n queries x C candidates already in the buffers, on the current stream"""
-        check(self.lib.naf_chain_path_check(self._chain_env, ptr(self.q_start), ptr(self.q_goal), ptr(self.vias), ptr(self.obstacles),
-                                            self.obstacle_radius, n, C, S, margin, ptr(self.out), None, stream_ptr()),
-              "chain_path_check")
-
-    def launch_certify(self, n: int, C: int, S: int, margin: float) -> None:
-        """the certifying launch of one chunk already in the buffers, into out_cert, on the current stream"""
-        check(self.lib.naf_chain_path_certify(self._chain_env, ptr(self.q_start), ptr(self.q_goal), ptr(self.vias), ptr(self.obstacles),
-                                              self.obstacle_radius, ptr(self.reach), self.guard, n, C, S, margin, ptr(self.out_cert),
-                                              None, stream_ptr()), "chain_path_certify")
-
-    def load(self, q_start, q_goal, obstacles, vias) -> None:
-        """a chunk's queries into the buffers: q_start[n][A], q_goal[n][A], obstacles[n][3], vias[n][C][A] (float32)"""
-        n, C = vias.shape[:2]
-        self.q_start[:n].copy_(torch.from_numpy(np.ascontiguousarray(q_start, np.float32)))
-        self.q_goal[:n].copy_(torch.from_numpy(np.ascontiguousarray(q_goal, np.float32)))
-        self.obstacles[:n].copy_(torch.from_numpy(np.ascontiguousarray(obstacles, np.float32)))
-        self.vias[:n * C].copy_(torch.from_numpy(np.ascontiguousarray(vias, np.float32).reshape(n * C, self.A)))
-
-    def check(self, q_start, q_goal, obstacles, candidates: int = 16, resolution: float = 0.02, margin: float = 0.0,
-              seed: int = 0, roadmap: int = 0) -> JointPaths:
-        """q_start[N][A], q_goal[N][A] (action order), obstacles[N][3] -> JointPaths of numpy arrays (float32 where the device's).
-        roadmap = M in 1 .. 62: the queries that end 'blocked' get a roadmap of M milestones; not with a certifying checker."""
-        if not roadmap_size_ok(roadmap):
-            raise ValueError(f"JointPathChecker: roadmap is a number of milestones from 0 to {ROADMAP_MAX}: got {roadmap!r}")
-        if roadmap and self.certify:
-            raise ValueError("JointPathChecker: roadmap edges are checked at their samples only, so not by a certifying checker")
-        A, C = self.A, int(candidates)
-        q_start = np.ascontiguousarray(q_start, np.float32).reshape(-1, A)
-        N = len(q_start)
-        q_goal, obstacles = np.ascontiguousarray(q_goal, np.float32).reshape(N, A), np.asarray(obstacles, np.float32).reshape(N, 3)
-        if 64 * C > self.chunk:
-            raise ValueError(f"JointPathChecker: a chunk of {self.chunk} candidate-samples does not hold one query's {C} candidates")
-        vias = path_vias(self.chain, q_start, q_goal, C, seed)
-        margin = float(np.float32(margin))
-        if self.certify:
-            def run(idx, S):
-                if len(idx) * C * S > self.chunk:
-                    raise ValueError(f"JointPathChecker: one query's {C} candidates at {S} samples exceed the chunk of {self.chunk}")
-                self.load(q_start[idx], q_goal[idx], obstacles[idx], vias[idx])
-                self.launch_certify(len(idx), C, S, margin)
-                return self.out_cert[:len(idx) * C].cpu().numpy().reshape(len(idx), C, PATH_CERT_FLOATS)
-
-            records, samples, refinements = certify_rounds(run, path_leg_lengths(vias, q_start, q_goal), C, resolution, self.chunk,
-                                                           np.float32)
-            return gather_certified_paths(records, vias, q_start, q_goal, samples, refinements)
-        records, samples = np.empty((N, C, PATH_FLOATS), np.float32), np.empty(N, np.int64)
-        for first, n, S in path_chunks(path_leg_lengths(vias, q_start, q_goal), C, resolution, self.chunk):
-            if n * C * S > self.chunk:
-                raise ValueError(f"JointPathChecker: one query's {C} candidates at {S} samples exceed the chunk of {self.chunk}")
-            sl = slice(first, first + n)
-            self.load(q_start[sl], q_goal[sl], obstacles[sl], vias[sl])
-            self.launch(n, C, S, margin)
-            records[sl] = self.out[:n * C].cpu().numpy().reshape(n, C, PATH_FLOATS)
-            samples[sl] = S
-        base = gather_joint_paths(records, vias, q_start, q_goal, samples)
-        if not roadmap:
-            return base
-
-        def run(queries, nodes, edges, S):
-            n, V, E = len(nodes), nodes.shape[1], len(edges)
-            if n * E * S > self.chunk:
-                raise ValueError(f"JointPathChecker: one query's {E} roadmap edges at {S} samples exceed the chunk of {self.chunk}")
-            self.load_edges(nodes, edges, obstacles[queries])
-            self.launch_edges(n, V, E, S, margin)
-            return self.edge_out[:n * E].cpu().numpy().reshape(n, E, EDGE_FLOATS)
-
-        return roadmap_round(base, self.chain, int(roadmap), seed, resolution, self.chunk, run, np.float32)
-
-
-def demonstration_chunks(rows_of, budget: int) -> List[Tuple[int, int, int]]:
-    """[(first query, queries, T_cap)]: consecutive queries share a chunk, and its T_cap is the largest T_n among them, as long as
-    queries x T_cap stays within `budget` rows; a chunk holds at least one query."""
-    rows_of = np.asarray(rows_of, np.int64)
-    out, first, N = [], 0, len(rows_of)
-    while first < N:
-        n, T = 1, int(rows_of[first])
-        while first + n < N:
-            T2 = max(T, int(rows_of[first + n]))
-            if (n + 1) * T2 > budget:
-                break
-            n, T = n + 1, T2
-        out.append((first, n, T))
-        first += n
-    return out
-
-
-class DemonstrationWriter(_ChainHandle):
-    """Planned joint paths as replay rows on a chain model (csrc/chain_env.hip, "demonstrations"): per chunk of queries ONE
-    naf_chain_demo_rows launch that writes every row of every demonstration, then torch plumbing — the mask `t < valid[n] and
-    kept[n]` and a boolean index — to a contiguous device tensor of the kept rows in query order, then tick order. Owns the handle
-    and staging buffers for `chunk` rows; needs no agent. A demonstration's rows do not depend on where in a launch it lies."""
-
-    def __init__(self, chain, obstacle_radius: float = 0.06, chunk: Optional[int] = None, device=None):
-        from .environment.kinematic import DEMO_CHUNK, DEMO_FLOATS, demo_row_layout
-        _lib.require_gpu()
-        self.lib, self.chain, self.A = _lib.load(), chain, chain.A
-        self.dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-        self.obstacle_radius = float(np.float32(obstacle_radius))
-        self.chunk = int(DEMO_CHUNK if chunk is None else chunk)
-        if self.chunk < 1:
-            raise ValueError("DemonstrationWriter: a chunk holds at least one row")
-        self.row_floats = self.lib.naf_replay_row_floats(2 * self.A + 9, self.A)
-        assert self.row_floats == demo_row_layout(self.A)[3]
-        self._create_chain_env(chain)
-        K, A = self.chunk, self.A                            # the most queries a chunk can hold: T_cap is at least 1
-        f32 = dict(dtype=torch.float32, device=self.dev)
-        self.q_start, self.leg_actions = torch.zeros(K, A, **f32), torch.zeros(K, 2, A, **f32)
-        self.n_ticks = torch.ones(K, 2, dtype=torch.int32, device=self.dev)
-        self.targets, self.obstacles = torch.zeros(K, 3, **f32), torch.zeros(K, 3, **f32)
-        self.records = torch.zeros(K, DEMO_FLOATS, **f32)
-        self.rows = torch.zeros(self.chunk, self.row_floats, **f32)
-        self.launches = 0
-
-    def launch(self, n: int, T_cap: int) -> None:
-        """the launch of one chunk of n demonstrations already in the buffers, on the current stream"""
-        check(self.lib.naf_chain_demo_rows(self._chain_env, ptr(self.q_start), ptr(self.leg_actions), ptr(self.n_ticks), ptr(self.targets),
-                                           ptr(self.obstacles), self.obstacle_radius, n, T_cap, ptr(self.rows), self.row_floats,
-                                           ptr(self.records), None, stream_ptr()), "chain_demo_rows")
-        self.launches += 1
-
-    def load(self, plan, targets, obstacles, sl: slice) -> int:
-        n = sl.stop - sl.start
-        up = lambda a, kind: torch.from_numpy(np.ascontiguousarray(a[sl], kind))      # noqa: E731
-        self.q_start[:n].copy_(up(plan.q_start, np.float32))
-        self.leg_actions[:n].copy_(up(plan.leg_actions, np.float32))
-        self.n_ticks[:n].copy_(up(plan.n_ticks, np.int32))
-        self.targets[:n].copy_(up(targets, np.float32))
-        self.obstacles[:n].copy_(up(obstacles, np.float32))
-        return n
-
-    def write(self, plan, targets, obstacles, keep_contact: bool = False, has_path=None):
-        """plan (environment.kinematic.DemonstrationPlan of N queries), targets[N][3], obstacles[N][3] -> Demonstrations whose `rows`
-        is a device tensor [rows_total][row_floats]. has_path[N] (default all): queries without one are launched with whatever
-        plan holds for them and reported 'none'."""
-        from .environment.kinematic import DEMO_FLOATS, DEMO_MAX_TICKS, gather_demonstrations
-        N = len(plan.q_start)
-        ticks = np.asarray(plan.n_ticks)
-        if ticks.shape != (N, 2) or (N and ticks.min() < 1):
-            raise ValueError("DemonstrationWriter: every leg of a plan takes at least one tick")
-        T_of = np.asarray(plan.rows, np.int64)
-        if N and (T_of.min() < 1 or T_of.max() > DEMO_MAX_TICKS):
-            raise ValueError(f"DemonstrationWriter: a demonstration holds 1 .. {DEMO_MAX_TICKS} rows")
-        if N and T_of.max() > self.chunk:
-            raise ValueError(f"DemonstrationWriter: a chunk of {self.chunk} rows does not hold one demonstration of {int(T_of.max())}")
-        targets, obstacles = np.asarray(targets, np.float32).reshape(N, 3), np.asarray(obstacles, np.float32).reshape(N, 3)
-        has = np.ones(N, bool) if has_path is None else np.asarray(has_path, bool)
-        records, parts = np.zeros((N, DEMO_FLOATS), np.float32), []
-        for first, n, T_cap in demonstration_chunks(T_of, self.chunk):
-            sl = slice(first, first + n)
-            self.load(plan, targets, obstacles, sl)
-            self.launch(n, T_cap)
-            records[sl] = self.records[:n].cpu().numpy()
-            # (the staging rows are reused by the next chunk: this chunk's kept rows are taken now)
-            parts.append(self._kept_of(self.rows[:n * T_cap].view(n, T_cap, self.row_floats), records[sl], has[sl], keep_contact))
-        rows = torch.cat(parts) if parts else torch.zeros(0, self.row_floats, device=self.dev)
-        return gather_demonstrations(records, has, lambda kept, valid: rows, keep_contact)._replace(action_size=self.A)
-
-    def _kept_of(self, rows, rec, has, keep_contact):
-        """the kept rows of one chunk: gather_demonstrations' keep rule on this chunk's records"""
-        from .environment.kinematic import gather_demonstrations
-        box = []
-        gather_demonstrations(rec, has, lambda kept, valid: box.append((kept, valid)), keep_contact)
-        kept, valid = box[0]
-        t = torch.arange(rows.shape[1], device=self.dev)[None, :]
-        mask = torch.from_numpy(kept).to(self.dev)[:, None] & (t < torch.from_numpy(valid).to(self.dev)[:, None])
-        return rows[mask]

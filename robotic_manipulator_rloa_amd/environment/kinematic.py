@@ -727,19 +727,24 @@ class JointPaths(_JointPathFields):
         return out
 
 
-def gather_joint_paths(records, vias, q_start, q_goal, samples) -> JointPaths:
-    """JointPaths from the records[N][C][PATH_FLOATS] of the vias[N][C][A] between q_start[N][A] and q_goal[N][A], and S per query"""
-    rec, vias = np.asarray(records), np.asarray(vias)
-    outcome, cand = select_joint_path(rec)
+def _gather_paths(rec, vias, q_start, q_goal, samples, outcome, cand) -> Tuple[list, np.ndarray]:
+    """JointPaths' first thirteen fields for the choice (outcome[N], cand[N]) among records[N][C][>= PATH_FLOATS], and each query's
+    chosen record (candidate 0's where none is chosen)"""
     has = cand >= 0
     pick = np.maximum(cand, 0)[:, None]
     row = np.take_along_axis(rec, pick[:, :, None], axis=1)[:, 0]
     straight = joint_distance32(q_goal, q_start)
     length = np.where(has, np.where(cand == 0, straight, row[:, 5]), np.nan).astype(rec.dtype)
-    via = np.where(has[:, None], np.take_along_axis(vias, pick[:, :, None], axis=1)[:, 0], np.nan)
-    return JointPaths(outcome, cand, via, length, straight.astype(rec.dtype), row[:, 0].copy(), row[:, 1].copy(), row[:, 2].copy(),
-                      rec[:, 0, 3].astype(np.int64), row[:, 6].copy(), np.asarray(samples, np.int64), np.array(q_start),
-                      np.array(q_goal), np.zeros(len(rec), bool), np.full(len(rec), np.nan, rec.dtype), np.zeros(len(rec), np.int64))
+    via = np.where(has[:, None], np.take_along_axis(np.asarray(vias), pick[:, :, None], axis=1)[:, 0], np.nan)
+    return [outcome, cand, via, length, straight.astype(rec.dtype), row[:, 0].copy(), row[:, 1].copy(), row[:, 2].copy(),
+            rec[:, 0, 3].astype(np.int64), row[:, 6].copy(), np.asarray(samples, np.int64), np.array(q_start), np.array(q_goal)], row
+
+
+def gather_joint_paths(records, vias, q_start, q_goal, samples) -> JointPaths:
+    """JointPaths from the records[N][C][PATH_FLOATS] of the vias[N][C][A] between q_start[N][A] and q_goal[N][A], and S per query"""
+    rec = np.asarray(records)
+    fields, _ = _gather_paths(rec, vias, q_start, q_goal, samples, *select_joint_path(rec))
+    return JointPaths(*fields, np.zeros(len(rec), bool), np.full(len(rec), np.nan, rec.dtype), np.zeros(len(rec), np.int64))
 
 
 def path_leg_lengths(vias, q_start, q_goal) -> np.ndarray:
@@ -756,51 +761,89 @@ def joint_paths_host(twin: KinematicEnvironment, q_start, q_goal, obstacles, can
     their S are the device's (path_chunks). certify: certify_joint_path's records and the device's rounds (certify_rounds).
     roadmap = M > 0: the 'blocked' queries get a roadmap of M milestones (roadmap_round: the device's chunks and S, check_joint_edge's
     records); roadmap edges are checked at their samples only, so not together with certify."""
+    return plan_paths(_TwinPaths(twin), q_start, q_goal, obstacles, candidates, resolution, margin, seed, chunk, certify, roadmap)
+
+
+def plan_paths(backend, q_start, q_goal, obstacles, candidates: int = 16, resolution: float = 0.02, margin: float = 0.0, seed: int = 0,
+               budget: int = PATH_CHUNK, certify: bool = False, roadmap: int = 0) -> JointPaths:
+    """The one orchestration of collision-checked joint paths, run by the device (chain_tools.JointPathChecker.check) and by the
+    twin (joint_paths_host) alike: the refusals, the vias, then either the refinement rounds of certify (certify_rounds) or the
+    one-via chunks (path_chunks) and, with roadmap = M > 0, the roadmap round over the queries they left 'blocked' (roadmap_round).
+    Chunks, their S and the choice among the records are the same for both; what differs is the backend, an object with
+      dtype, prefix, roadmap_certify_refusal : the records' dtype and the words of its refusals
+      chain                                  : the ChainModel
+      prepare(q_start, q_goal, obstacles, C) : the queries as the backend takes them, [N][A], [N][A], [N][3]
+      path_records / certified_records (q_start[n], q_goal[n], obstacles[n], vias[n][C], S, margin) : records[n][C][PATH_FLOATS] /
+                                               [n][C][PATH_CERT_FLOATS] of one chunk of whole queries at S samples
+      edge_records(nodes[n][V][A], edges[E][2], obstacles[n], S, margin) : records[n][E][EDGE_FLOATS] of one chunk of roadmaps
+    A backend with a budget of its own refuses in its evaluators what exceeds it."""
     if not roadmap_size_ok(roadmap):
-        raise ValueError(f"roadmap is a number of milestones from 0 to {ROADMAP_MAX}: got {roadmap!r}")
+        raise ValueError(f"{backend.prefix}roadmap is a number of milestones from 0 to {ROADMAP_MAX}: got {roadmap!r}")
     if roadmap and certify:
-        raise ValueError("roadmap edges are checked at their samples only: roadmap > 0 does not go with certify=True")
-    r32 = lambda a: np.asarray(a, np.float64).astype(np.float32).astype(np.float64)      # noqa: E731
-    q_start, q_goal, obstacles = r32(q_start), r32(q_goal), r32(obstacles)
-    N, C = len(q_start), int(candidates)
-    vias = path_vias(twin.model, q_start, q_goal, C, seed)
+        raise ValueError(backend.prefix + backend.roadmap_certify_refusal)
+    C = int(candidates)
+    q_start, q_goal, obstacles = backend.prepare(q_start, q_goal, obstacles, C)
+    vias = path_vias(backend.chain, q_start, q_goal, C, seed)
+    legs = path_leg_lengths(vias, q_start, q_goal)
     if certify:
-        reach, guard = reach_table(twin.model), certificate_guard(twin.model)
-
         def run(idx, S):
-            out = np.empty((len(idx), C, PATH_CERT_FLOATS))
-            block = max(1, 65536 // (C * S))
-            for k in range(0, len(idx), block):
-                sl = idx[k:k + block]
-                out[k:k + block] = certify_joint_path(twin, q_start[sl, None, :], vias[sl].astype(np.float64), q_goal[sl, None, :],
-                                                      obstacles[sl, None, :], S, margin, reach=reach, guard=guard)
-            return out
+            return backend.certified_records(q_start[idx], q_goal[idx], obstacles[idx], vias[idx], S, margin)
 
-        records, samples, refinements = certify_rounds(run, path_leg_lengths(vias, q_start, q_goal), C, resolution, chunk, np.float64)
+        records, samples, refinements = certify_rounds(run, legs, C, resolution, budget, backend.dtype)
         return gather_certified_paths(records, vias, q_start, q_goal, samples, refinements)
-    records, samples = np.empty((N, C, PATH_FLOATS)), np.empty(N, np.int64)
-    for first, n, S in path_chunks(path_leg_lengths(vias, q_start, q_goal), C, resolution, chunk):
-        samples[first:first + n] = S
-        block = max(1, 65536 // (C * S))                      # the twin holds every sample's segments at once: a few at a time
-        for k in range(first, first + n, block):
-            sl = slice(k, min(k + block, first + n))
-            records[sl] = check_joint_path(twin, q_start[sl, None, :], vias[sl].astype(np.float64), q_goal[sl, None, :],
-                                           obstacles[sl, None, :], S, margin)
+    records, samples = np.empty((len(legs), C, PATH_FLOATS), backend.dtype), np.empty(len(legs), np.int64)
+    for first, n, S in path_chunks(legs, C, resolution, budget):
+        sl = slice(first, first + n)
+        records[sl], samples[sl] = backend.path_records(q_start[sl], q_goal[sl], obstacles[sl], vias[sl], S, margin), S
     base = gather_joint_paths(records, vias, q_start, q_goal, samples)
     if not roadmap:
         return base
 
     def run(queries, nodes, edges, S):
-        ob, nodes = obstacles[queries], nodes.astype(np.float64)
+        return backend.edge_records(nodes, edges, obstacles[queries], S, margin)
+
+    return roadmap_round(base, backend.chain, int(roadmap), seed, resolution, budget, run, backend.dtype)
+
+
+class _TwinPaths:
+    """plan_paths' backend through the twin alone: the poses and the clearances in float64 on the values the device is given, a few
+    queries (or edges) at a time — the twin holds every sample's segments at once, 65536 samples here. It has no budget and refuses
+    nothing."""
+    dtype, prefix = np.float64, ""
+    roadmap_certify_refusal = "roadmap edges are checked at their samples only: roadmap > 0 does not go with certify=True"
+
+    def __init__(self, twin: KinematicEnvironment):
+        self.twin, self.chain = twin, twin.model
+
+    def prepare(self, q_start, q_goal, obstacles, C: int):
+        r32 = lambda a: np.asarray(a, np.float64).astype(np.float32).astype(np.float64)      # noqa: E731
+        return r32(q_start), r32(q_goal), r32(obstacles)
+
+    def _records(self, rule, floats, q_start, q_goal, obstacles, vias, S, margin) -> np.ndarray:
+        n, C = vias.shape[:2]
+        out = np.empty((n, C, floats))
+        block = max(1, 65536 // (C * S))
+        for k in range(0, n, block):
+            sl = slice(k, k + block)
+            out[sl] = rule(self.twin, q_start[sl, None, :], vias[sl].astype(np.float64), q_goal[sl, None, :], obstacles[sl, None, :],
+                           S, margin)
+        return out
+
+    def path_records(self, *chunk) -> np.ndarray:
+        return self._records(check_joint_path, PATH_FLOATS, *chunk)
+
+    def certified_records(self, *chunk) -> np.ndarray:
+        return self._records(certify_joint_path, PATH_CERT_FLOATS, *chunk)
+
+    def edge_records(self, nodes, edges, obstacles, S, margin) -> np.ndarray:
+        nodes = nodes.astype(np.float64)
         out = np.empty((len(nodes), len(edges), EDGE_FLOATS))
-        block = max(1, 65536 // S)                            # edges at a time, as above
+        block = max(1, 65536 // S)
         for n in range(len(nodes)):
             for k in range(0, len(edges), block):
                 e = edges[k:k + block]
-                out[n, k:k + block] = check_joint_edge(twin, nodes[n, e[:, 0]], nodes[n, e[:, 1]], ob[n], S, margin)
+                out[n, k:k + block] = check_joint_edge(self.twin, nodes[n, e[:, 0]], nodes[n, e[:, 1]], obstacles[n], S, margin)
         return out
-
-    return roadmap_round(base, twin.model, roadmap, seed, resolution, chunk, run, np.float64)
 
 
 # ---- roadmaps: several straight edges where one via is blocked (include/naf_hip.h, "Roadmap edges") --------------------------------
@@ -1179,17 +1222,10 @@ def select_certified_path(records, samples) -> Tuple[np.ndarray, np.ndarray, np.
 
 def gather_certified_paths(records, vias, q_start, q_goal, samples, refinements) -> JointPaths:
     """JointPaths, its last three fields filled, from the last round's records[N][C][PATH_CERT_FLOATS]"""
-    rec, vias = np.asarray(records), np.asarray(vias)
+    rec = np.asarray(records)
     outcome, cand, _ = select_certified_path(rec, samples)
-    has = cand >= 0
-    pick = np.maximum(cand, 0)[:, None]
-    row = np.take_along_axis(rec, pick[:, :, None], axis=1)[:, 0]
-    straight = joint_distance32(q_goal, q_start)
-    length = np.where(has, np.where(cand == 0, straight, row[:, 5]), np.nan).astype(rec.dtype)
-    via = np.where(has[:, None], np.take_along_axis(vias, pick[:, :, None], axis=1)[:, 0], np.nan)
-    return JointPaths(outcome, cand, via, length, straight.astype(rec.dtype), row[:, 0].copy(), row[:, 1].copy(), row[:, 2].copy(),
-                      rec[:, 0, 3].astype(np.int64), row[:, 6].copy(), np.asarray(samples, np.int64), np.array(q_start),
-                      np.array(q_goal), has & (row[:, 11] == -1), row[:, 8:11].min(axis=1), np.asarray(refinements, np.int64))
+    fields, row = _gather_paths(rec, vias, q_start, q_goal, samples, outcome, cand)
+    return JointPaths(*fields, (cand >= 0) & (row[:, 11] == -1), row[:, 8:11].min(axis=1), np.asarray(refinements, np.int64))
 
 
 def certify_rounds(run, leg_lengths, candidates: int, resolution: float, budget: int, dtype) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:

@@ -28,13 +28,10 @@ from dataclasses import dataclass, fields
 from typing import List, Optional, Union
 
 import numpy as np
-import torch
 
-from .environment.kinematic import (SCENE_CONDITIONS, KinematicEnvironment, build_kinematic, cell_box_gaps, choose_scene,
-                                    goal_poses_host, ik_restarts_ok, joint_paths_host, reach_queries, JointPaths,
-                                    ROADMAP_MAX, roadmap_milestones, roadmap_size_ok,
-                                    PATH_CANDIDATES_MAX, DEMO_MAX_TICKS, Demonstrations, demonstration_plan,
-                                    demonstration_rows_host, demonstration_speed_ok)
+from .arm_planner import ArmPlanner, _positive_int
+from .environment.kinematic import (SCENE_CONDITIONS, Demonstrations, KinematicEnvironment, build_kinematic, cell_box_gaps,
+                                    choose_scene)
 from .environment.synthetic import SyntheticEnvironment
 from .environment.urdf_chain import SCENE_TRIES, TARGET_THRESHOLD, cell_geometry_name
 from .naf_components.naf_algorithm import NAFAgent
@@ -57,10 +54,6 @@ class HyperParameters:
     learning_rate: float = 0.001
     update_freq: int = 1
     num_updates: int = 1
-
-
-def _positive_int(v) -> bool:
-    return isinstance(v, int) and v > 0
 
 
 # accepted spellings -> (field, validity predicate, error text) — the reference's table (rl_framework.py:179-230),
@@ -289,110 +282,28 @@ class ManipulatorFramework:
         hold between their samples too.
         roadmap=M (with joint_paths, not with certify): the paths are plan_joint_paths(roadmap=M)'s; a query whose path is a
         'roadmap' polyline has its planned_ratio over that polyline's length."""
-        if not self.env:
-            raise EnvironmentNotInitialized
-        if not self.naf_agent:
-            raise NAFAgentNotInitialized
-        if not isinstance(self.env, KinematicEnvironment):
-            raise ConfigurationIncomplete('reach_targets() needs the kinematic environment (initialize_kinematic_environment()): '
-                                          'PyBullet and the synthetic stand-in have no given-scene reset')
+        self._require_env_and_agent()
+        planner = self._kinematic_planner('reach_targets', 'given-scene reset')
         if getattr(self.naf_agent, 'world_size', 1) > 1:
             raise InvalidNAFAgentParameter('reach_targets() answers a query on one GPU: not with a data-parallel agent')
         if n_envs is not None and not _positive_int(n_envs):
             raise InvalidNAFAgentParameter('Number of environments received is not a positive integer')
-        env = self.env
-        nominal = env.obstacle_centre if env.scene_ranges_on else env.obstacle_pos
-        try:
-            q0, targets, obstacles, frames = reach_queries(env.model, targets, obstacles, initial_joint_positions, frames,
-                                                           nominal_obstacle=nominal, nominal_start=env.initial_joint_positions)
-        except ValueError as err:
-            raise InvalidEnvironmentParameter(str(err)) from None
-        goal_poses = bool(goal_poses or joint_paths)
-        if not isinstance(certify, (bool, np.bool_)) or (certify and not joint_paths):
-            raise InvalidEnvironmentParameter('reach_targets(certify=True) certifies the joint paths: it is a bool and needs joint_paths=True')
-        self._check_roadmap(roadmap, certify, 'reach_targets')
-        if roadmap and not joint_paths:
-            raise InvalidEnvironmentParameter('reach_targets(roadmap=M) builds roadmaps for the joint paths: it needs joint_paths=True')
-        if goal_poses and not trajectories:
-            raise InvalidEnvironmentParameter('reach_targets(goal_poses=True) measures the joint path: it needs trajectories=True')
-        result = self.naf_agent.rollout_vectorized(env.model, targets, obstacles, q0, frames=frames, noise_scale=float(noise_scale),
-                                                   n_envs=n_envs, trajectories=bool(trajectories),
-                                                   scene={'obstacle_radius': env.obstacle_radius})
-        if goal_poses:
-            result.goal = self.solve_goal_poses(targets, obstacles, q0)
-            path = np.asarray(result.joint_positions, np.float64)
-            length = np.sum(np.max(np.abs(np.diff(path, axis=1)), axis=2), axis=1)
-            with np.errstate(divide='ignore', invalid='ignore'):
-                ratio = length / np.asarray(result.goal.joint_distance, np.float64)
-            result.path_ratio = np.where((np.asarray(result.outcome) == 'reached') & result.goal.free, ratio, np.nan)
-        if joint_paths:
-            result.path = self._paths_to_goals(result.goal, q0, obstacles,
-                                               {'certify': True} if certify else {'roadmap': int(roadmap)} if roadmap else {})
-            with np.errstate(divide='ignore', invalid='ignore'):
-                ratio = length / np.asarray(result.path.length, np.float64)
-            # a query has a path when its length is a number: a candidate of the one-via round, or a 'roadmap' polyline
-            has_path = np.isfinite(np.asarray(result.path.length, np.float64))
-            result.planned_ratio = np.where((np.asarray(result.outcome) == 'reached') & has_path, ratio, np.nan)
-        return result
+        return planner.reach_targets(self.naf_agent, targets, obstacles, initial_joint_positions, frames, noise_scale, n_envs,
+                                     trajectories, goal_poses, joint_paths, certify, roadmap)
 
-    def _paths_to_goals(self, goal, q0, obstacles, kw) -> JointPaths:
-        """plan_joint_paths to the poses of `goal` (GoalPoses): queries without a reachable pose get outcome 'goal' and NaN numbers"""
-        ok = np.asarray(goal.reachable, bool)
-        N, A = len(ok), self.env.model.A
-        if ok.all():
-            return self._plan_checked(q0, np.asarray(goal.joint_positions, np.float64), obstacles, **kw)
-        # (the poses a solver returned lie inside the limits: they are not put through the refusals again)
-        found = self._plan_checked(q0[ok], np.asarray(goal.joint_positions, np.float64)[ok], obstacles[ok], **kw) if ok.any() else None
-        kind = np.float32 if found is None else found.length.dtype
-        nan = lambda *shape: np.full((N,) + shape, np.nan, kind)      # noqa: E731
-        parts = [np.full(N, 'goal', '<U8'), np.full(N, -1, np.int64), nan(A), nan(), nan(), nan(), nan(), nan(), np.full(N, -1, np.int64),
-                 nan(), np.zeros(N, np.int64), np.asarray(q0, kind), nan(A), np.zeros(N, bool), nan(), np.zeros(N, np.int64)]
-        for dst, src in zip(parts, found or ()):
-            dst[ok] = src
-        out = JointPaths(*parts)
-        if found is not None and found.n_nodes is not None:      # the roadmap's attributes, padded as the fields are
-            out.nodes = np.full((N,) + found.nodes.shape[1:], np.nan, found.nodes.dtype)
-            out.n_nodes, out.roadmap_free_edges = np.zeros(N, np.int64), np.full(N, -1, np.int64)
-            out.nodes[ok], out.n_nodes[ok], out.roadmap_free_edges[ok] = found.nodes, found.n_nodes, found.roadmap_free_edges
-        elif kw.get('roadmap'):
-            out.nodes = np.full((N, 0, A), np.nan, kind)
-            out.n_nodes, out.roadmap_free_edges = np.zeros(N, np.int64), np.full(N, -1, np.int64)
-        return out
+    @functools.cached_property
+    def arm_planner(self) -> ArmPlanner:
+        """what the arm-planning methods delegate to, with its cache of device tools; made on first use, kept for good"""
+        return ArmPlanner(self)
 
-    @staticmethod
-    def _check_roadmap(roadmap, certify, who) -> None:
-        if not roadmap_size_ok(roadmap):
-            raise InvalidEnvironmentParameter(f'roadmap is a number of milestones from 0 to {ROADMAP_MAX} (0: no roadmap): '
-                                              f'got {roadmap!r}')
-        if roadmap and certify:
-            raise InvalidEnvironmentParameter(f'{who}(roadmap={roadmap!r}, certify=True): roadmap edges are checked at their samples '
-                                              f'only, and nothing certifies a \'roadmap\' path between them')
-
-    def _plan_checked(self, q0, q_goal, obstacles, candidates=16, resolution=0.02, clearance_margin=0.0, seed=0, on_device=None,
-                      certify=False, roadmap=0):
-        env = self.env
-        if on_device is None:
-            on_device = torch.cuda.is_available()
-        kw = dict(candidates=int(candidates), resolution=float(resolution), margin=float(clearance_margin), seed=int(seed))
-        if roadmap:
-            kw['roadmap'] = int(roadmap)
-        if not on_device:
-            out = joint_paths_host(env, q0, q_goal, obstacles, **kw, **({'certify': True} if certify else {}))
-        else:
-            from .engine import JointPathChecker
-            # one cached checker for each kind: plain and certified calls may alternate without rebuilding handle and buffers
-            slot, key = ('_cert_checker' if certify else '_path_checker'), (env.model.digest(), float(env.obstacle_radius))
-            if getattr(self, slot, None) is None or getattr(self, slot)[0] != key:
-                setattr(self, slot, None)
-                setattr(self, slot, (key, JointPathChecker(env.model, env.obstacle_radius, **({'certify': True} if certify else {}))))
-            out = getattr(self, slot)[1].check(q0, q_goal, obstacles, **kw)
-        with np.errstate(invalid='ignore'):
-            coarse = np.asarray(out.sample_step, np.float64) > resolution
-        if coarse.any() and not getattr(self, '_path_step_warned', False):
-            self._path_step_warned = True
-            logger.warning(f'plan_joint_paths: {int(coarse.sum())} queries are sampled at the cap of 2048 poses per path, '
-                           f'{float(np.max(np.asarray(out.sample_step)[coarse])):.4g} apart, coarser than resolution={resolution!r}')
-        return out
+    def _kinematic_planner(self, who: str, lacking: str) -> ArmPlanner:
+        """the planner, for a method that needs the kinematic environment"""
+        if not self.env:
+            raise EnvironmentNotInitialized
+        if not isinstance(self.env, KinematicEnvironment):
+            raise ConfigurationIncomplete(f'{who}() needs the kinematic environment (initialize_kinematic_environment()): '
+                                          f'PyBullet and the synthetic stand-in have no {lacking}')
+        return self.arm_planner
 
     def plan_joint_paths(self, targets=None, obstacles=None, initial_joint_positions=None, goal_joint_positions=None,
                          candidates: int = 16, resolution: float = 0.02, clearance_margin: float = 0.0, seed: int = 0,
@@ -436,64 +347,9 @@ class ManipulatorFramework:
         Returns environment.kinematic.JointPaths, arrays over the queries: outcome ('straight' | 'via' | 'blocked' | 'start' |
         'goal': the start / goal pose itself is blocked), candidate, via, length, straight_length, min_clearance,
         min_self_clearance, min_cell_clearance, straight_first_blocked, sample_step, samples; waypoints(n) resamples the paths."""
-        if not self.env:
-            raise EnvironmentNotInitialized
-        if not isinstance(self.env, KinematicEnvironment):
-            raise ConfigurationIncomplete('plan_joint_paths() needs the kinematic environment (initialize_kinematic_environment()): '
-                                          'PyBullet and the synthetic stand-in have no chain model to solve on')
-        env = self.env
-        if (targets is None) == (goal_joint_positions is None):
-            raise InvalidEnvironmentParameter('plan_joint_paths() takes exactly one of targets and goal_joint_positions')
-        if not _positive_int(candidates) or candidates > PATH_CANDIDATES_MAX:
-            raise InvalidEnvironmentParameter(f'candidates is a number of paths from 1 to {PATH_CANDIDATES_MAX}: got {candidates!r}')
-        if not (isinstance(resolution, (int, float)) and not isinstance(resolution, bool) and np.isfinite(resolution) and resolution > 0.0):
-            raise InvalidEnvironmentParameter(f'resolution is a positive joint-space distance: got {resolution!r}')
-        if not (isinstance(clearance_margin, (int, float)) and np.isfinite(clearance_margin)):
-            raise InvalidEnvironmentParameter(f'clearance_margin is a finite length: got {clearance_margin!r}')
-        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or seed < 0:
-            raise InvalidEnvironmentParameter(f'seed is a non-negative integer: got {seed!r}')
-        if not isinstance(certify, (bool, np.bool_)):
-            raise InvalidEnvironmentParameter(f'certify is a bool: got {certify!r}')
-        self._check_roadmap(roadmap, certify, 'plan_joint_paths')
-        if roadmap:
-            try:
-                roadmap_milestones(env.model, np.zeros((0, env.model.A)), np.zeros((0, env.model.A)), int(roadmap), 0)
-            except ValueError as err:
-                raise InvalidEnvironmentParameter(f'roadmap: {err}') from None
-        nominal = env.obstacle_centre if env.scene_ranges_on else env.obstacle_pos
-        kw = dict(candidates=candidates, resolution=resolution, clearance_margin=clearance_margin, seed=seed, on_device=on_device)
-        if certify:
-            kw['certify'] = True
-        if roadmap:
-            kw['roadmap'] = int(roadmap)
-        try:
-            if targets is not None:
-                q0, targets, obstacles, _ = reach_queries(env.model, targets, obstacles, initial_joint_positions, 1,
-                                                          nominal_obstacle=nominal, nominal_start=env.initial_joint_positions)
-            else:
-                # the goal poses go through the same refusals as start poses do: shape, finite numbers, the joints' limits
-                try:
-                    goals = np.array(goal_joint_positions, float)
-                except (TypeError, ValueError):
-                    raise ValueError('goal_joint_positions is not an array of numbers') from None
-                if goals.shape == (env.model.A,):
-                    goals = goals[None]
-                if goals.ndim != 2 or goals.shape[1] != env.model.A or len(goals) == 0:
-                    raise ValueError(f'goal_joint_positions is [N][{env.model.A}], or [{env.model.A}] for one query (one value per '
-                                     f'involved joint): got shape {goals.shape}')
-                far = np.zeros((len(goals), 3))
-                try:
-                    q_goal = reach_queries(env.model, far, far, goals, 1)[0]
-                except ValueError as err:
-                    raise ValueError(str(err).replace('initial_joint_positions', 'goal_joint_positions')) from None
-                q0, _, obstacles, _ = reach_queries(env.model, far, obstacles, initial_joint_positions, 1, nominal_obstacle=nominal,
-                                                    nominal_start=env.initial_joint_positions)
-        except ValueError as err:
-            raise InvalidEnvironmentParameter(str(err)) from None
-        if targets is not None:
-            goal = self.solve_goal_poses(targets, obstacles, q0, seed=seed, on_device=on_device)
-            return self._paths_to_goals(goal, q0, obstacles, kw)
-        return self._plan_checked(q0, q_goal, obstacles, **kw)
+        planner = self._kinematic_planner('plan_joint_paths', 'chain model to solve on')
+        return planner.plan_joint_paths(targets, obstacles, initial_joint_positions, goal_joint_positions, candidates, resolution,
+                                        clearance_margin, seed, on_device, certify, roadmap)
 
     def demonstrate_joint_paths(self, paths, targets=None, obstacles=None, speed: float = 1.0, frames: int = 400,
                                 keep_contact: bool = False, on_device: Optional[bool] = None):
@@ -512,48 +368,8 @@ class ManipulatorFramework:
           on_device    : None: the device when there is one; False: the float64 host twin, `rows` a numpy array (slow)
         Returns environment.kinematic.Demonstrations: outcome ('reached' | 'frames' | 'end' | 'obstacle' | 'self' | 'workcell' |
         'none'), frames, final_distance, the three minima, planned_ticks, kept, rows [rows_total][row floats], rows_total."""
-        if not self.env:
-            raise EnvironmentNotInitialized
-        if not isinstance(self.env, KinematicEnvironment):
-            raise ConfigurationIncomplete('demonstrate_joint_paths() needs the kinematic environment '
-                                          '(initialize_kinematic_environment()): PyBullet and the synthetic stand-in have no chain '
-                                          'model to drive')
-        env = self.env
-        if not isinstance(paths, JointPaths) or paths.start is None or paths.goal is None:
-            raise InvalidEnvironmentParameter('paths is the JointPaths that plan_joint_paths() returned')
-        if not demonstration_speed_ok(speed):
-            raise InvalidEnvironmentParameter(f'speed is a share of the unit action, 0 < speed <= 1: got {speed!r}')
-        if not _positive_int(frames) or frames > DEMO_MAX_TICKS:
-            raise InvalidEnvironmentParameter(f'frames is a number of steps from 1 to {DEMO_MAX_TICKS}: got {frames!r}')
-        has = np.asarray(paths.candidate) >= 0
-        start = np.asarray(paths.start, np.float64)
-        N, A = start.shape
-        if A != env.model.A:
-            raise InvalidEnvironmentParameter(f'paths holds poses of {A} joints, the environment\'s arm has {env.model.A}')
-        # a query without a path stands still at its start pose for the launch and is reported 'none'
-        via = np.where(has[:, None], np.asarray(paths.via, np.float64), start)
-        goal = np.where(has[:, None], np.asarray(paths.goal, np.float64), start)
-        nominal = env.obstacle_centre if env.scene_ranges_on else env.obstacle_pos
-        try:
-            if targets is None:
-                targets = env.end_effector(np.asarray(goal, np.float32).astype(np.float64))
-            _, targets, obstacles, _ = reach_queries(env.model, targets, obstacles, None, 1, nominal_obstacle=nominal,
-                                                     nominal_start=env.initial_joint_positions)
-            if len(targets) != N:
-                raise ValueError(f'targets is [N][3] with N = {N}, the number of paths: got {len(targets)}')
-        except ValueError as err:
-            raise InvalidEnvironmentParameter(str(err)) from None
-        plan = demonstration_plan(start, via, goal, float(speed), int(frames))
-        if on_device is None:
-            on_device = torch.cuda.is_available()
-        if not on_device:
-            return demonstration_rows_host(env, plan, targets, obstacles, int(frames), bool(keep_contact), has)
-        from .engine import DemonstrationWriter
-        key = (env.model.digest(), float(env.obstacle_radius))
-        if getattr(self, '_demo_writer', None) is None or self._demo_writer[0] != key:
-            self._demo_writer = None
-            self._demo_writer = (key, DemonstrationWriter(env.model, env.obstacle_radius))
-        return self._demo_writer[1].write(plan, targets, obstacles, bool(keep_contact), has)
+        planner = self._kinematic_planner('demonstrate_joint_paths', 'chain model to drive')
+        return planner.demonstrate_joint_paths(paths, targets, obstacles, speed, frames, keep_contact, on_device)
 
     def _check_demonstrations(self, demos, E) -> None:
         if not isinstance(demos, Demonstrations):
@@ -586,40 +402,9 @@ class ManipulatorFramework:
                         per update and candidate)
         Returns environment.kinematic.GoalPoses, arrays over the queries: reachable, free, joint_positions [N][A], residual,
         clearance, self_clearance, cell_clearance, joint_distance, restart, converged_restarts."""
-        if not self.env:
-            raise EnvironmentNotInitialized
-        if not isinstance(self.env, KinematicEnvironment):
-            raise ConfigurationIncomplete('solve_goal_poses() needs the kinematic environment (initialize_kinematic_environment()): '
-                                          'PyBullet and the synthetic stand-in have no chain model to solve on')
-        env = self.env
-        if not ik_restarts_ok(restarts):
-            raise InvalidEnvironmentParameter(f'restarts is a power of two from 1 to 64: got {restarts!r}')
-        if not _positive_int(iterations):
-            raise InvalidEnvironmentParameter(f'iterations is a positive number of updates: got {iterations!r}')
-        if not (isinstance(tolerance, (int, float)) and np.isfinite(tolerance) and tolerance > 0.0):
-            raise InvalidEnvironmentParameter(f'tolerance is a positive length: got {tolerance!r}')
-        if not (isinstance(clearance_margin, (int, float)) and np.isfinite(clearance_margin)):
-            raise InvalidEnvironmentParameter(f'clearance_margin is a finite length: got {clearance_margin!r}')
-        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or seed < 0:
-            raise InvalidEnvironmentParameter(f'seed is a non-negative integer: got {seed!r}')
-        nominal = env.obstacle_centre if env.scene_ranges_on else env.obstacle_pos
-        try:
-            q0, targets, obstacles, _ = reach_queries(env.model, targets, obstacles, initial_joint_positions, 1,
-                                                      nominal_obstacle=nominal, nominal_start=env.initial_joint_positions)
-        except ValueError as err:
-            raise InvalidEnvironmentParameter(str(err)) from None
-        kw = dict(restarts=int(restarts), iterations=int(iterations), tolerance=float(tolerance), margin=float(clearance_margin),
-                  seed=int(seed))
-        if on_device is None:
-            on_device = torch.cuda.is_available()
-        if not on_device:
-            return goal_poses_host(env, q0, targets, obstacles, **kw)
-        from .engine import GoalPoseSolver
-        key = (env.model.digest(), float(env.obstacle_radius))
-        if getattr(self, '_goal_solver', None) is None or self._goal_solver[0] != key:
-            self._goal_solver = None
-            self._goal_solver = (key, GoalPoseSolver(env.model, env.obstacle_radius))
-        return self._goal_solver[1].solve(q0, targets, obstacles, **kw)
+        planner = self._kinematic_planner('solve_goal_poses', 'chain model to solve on')
+        return planner.solve_goal_poses(targets, obstacles, initial_joint_positions, restarts, iterations, tolerance, clearance_margin,
+                                        seed, on_device)
 
     # ---- environment ------------------------------------------------------------------------------------------------
     def initialize_environment(self, manipulator_file: str, endeffector_index: int, fixed_joints: List[int],

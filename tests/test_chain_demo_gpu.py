@@ -1,6 +1,6 @@
 """GPU (`-m gpu`): naf_chain_demo_rows (csrc/chain_env.hip) against the step kernel it restates (reset_given, then T_cap x
 naf_chain_env_step fed the plan's actions), against the float64 rule of environment/kinematic.py (demonstration_rows_host) and for
-chain exactness, through the C ABI with poisoned pad rows behind every output; placement independence; engine.DemonstrationWriter
+chain exactness, through the C ABI with poisoned pad rows behind every output; placement independence; chain_tools.DemonstrationWriter
 across chunks and the ring after add_demonstrations; and plan_joint_paths -> demonstrate_joint_paths -> run_training end to end.
 tests/test_chain_demo_cpu.py rehearses every case with a float32 restatement."""
 import ctypes
@@ -175,11 +175,11 @@ def test_placement_independence_through_the_c_abi():
 
 @pytest.mark.parametrize("name,N,T_cap,chunk", [("iiwa_like7", 16, 256, 2 * 256), ("long12", 3, 130, 130), ("slider4", 16, 256, None)])
 def test_demonstration_writer_across_chunks_and_the_ring(name, N, T_cap, chunk):
-    """engine.DemonstrationWriter in forced small chunks (two demonstrations / one a chunk) and in one chunk gives the kept rows of
+    """chain_tools.DemonstrationWriter in forced small chunks (two demonstrations / one a chunk) and in one chunk gives the kept rows of
     one C-ABI launch, in query order then tick order, and its numbers; keep_contact adds the dropped ones' rows. After
     add_demonstrations on a fresh agent (action_mode='float': the default gather truncates the actions on the way out, as the
     reference's .long() does), gather_rows with idx = arange reads back exactly those rows, and len(memory) is their count."""
-    from robotic_manipulator_rloa_amd.engine import DemonstrationWriter
+    from robotic_manipulator_rloa_amd.chain_tools import DemonstrationWriter
     case = D.build_case(name, N, T_cap)
     rig = DemoRig(case)
     rows, rec, _ = rig.run(poses=False)
@@ -213,7 +213,7 @@ def test_framework_demonstrations_end_to_end(scratch_cwd, monkeypatch):
     device's demonstrations carry the twin's outcomes. Off means off: the same short run without the argument ends with weights
     bit-equal to a second run without it, and launches no demonstration kernel."""
     from chain_resume_worker import make_framework
-    from robotic_manipulator_rloa_amd import engine
+    from robotic_manipulator_rloa_amd import chain_tools
     N = 24
     rng = np.random.default_rng(8)
     targets = np.array(IIWA_RANGED["target_position"]) + rng.uniform(-0.15, 0.15, (N, 3))
@@ -241,7 +241,7 @@ def test_framework_demonstrations_end_to_end(scratch_cwd, monkeypatch):
 
     def no_launch(self, *a, **kw):
         raise AssertionError("a run without demonstrations launched the demonstration kernel")
-    monkeypatch.setattr(engine.DemonstrationWriter, "launch", no_launch)
+    monkeypatch.setattr(chain_tools.DemonstrationWriter, "launch", no_launch)
     digests = []
     for _ in range(2):
         g = make_framework(IIWA_RANGED, checkpoint_frequency=64, save=False)

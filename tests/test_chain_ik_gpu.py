@@ -1,5 +1,5 @@
 """GPU (`-m gpu`): naf_chain_ik_solve / naf_chain_ik_select (csrc/chain_env.hip) against the float64 rule of environment/kinematic.py,
-through the C ABI; engine.GoalPoseSolver, ManipulatorFramework.solve_goal_poses and reach_targets(goal_poses=True) against that
+through the C ABI; chain_tools.GoalPoseSolver, ManipulatorFramework.solve_goal_poses and reach_targets(goal_poses=True) against that
 path; and that training launches are untouched. tests/test_chain_ik_cpu.py rehearses every case with a float32 restatement."""
 import ctypes
 import os
@@ -173,10 +173,10 @@ def test_placement_independence_through_the_c_abi():
 
 @pytest.mark.parametrize("name,N,R,chunk", [("iiwa_like7", 65, 1, 64), ("iiwa_like7", 17, 4, 64), ("long12", 5, 4, None)])
 def test_goal_pose_solver_equals_the_c_abi_path(name, N, R, chunk):
-    """engine.GoalPoseSolver end to end, with the seeds it draws, against the C-ABI launches fed ik_seeds of the same seed: every
+    """chain_tools.GoalPoseSolver end to end, with the seeds it draws, against the C-ABI launches fed ik_seeds of the same seed: every
     field of GoalPoses bit for bit. Chunks of 64 candidates: N R = 65 is one more than a chunk, 17 x 4 a chunk of 16 queries and one
     of a single query."""
-    from robotic_manipulator_rloa_amd.engine import GoalPoseSolver
+    from robotic_manipulator_rloa_amd.chain_tools import GoalPoseSolver
     from robotic_manipulator_rloa_amd.environment.kinematic import gather_goal_poses
     base = IK.build_case(name, N, R)
     seeds = ik_seeds(base.model, N, R, seed=11).astype(np.float64)
@@ -202,7 +202,7 @@ def test_framework_goal_poses_end_to_end(scratch_cwd):
     wherever it converges with room to spare."""
     from chain_resume_worker import make_framework
     from robotic_manipulator_rloa_amd import ManipulatorFramework
-    from robotic_manipulator_rloa_amd.engine import GoalPoseSolver
+    from robotic_manipulator_rloa_amd.chain_tools import GoalPoseSolver
     N, F = 48, 20
     rng = np.random.default_rng(8)
     targets = np.array(IIWA_RANGED["target_position"]) + rng.uniform(-0.15, 0.15, (N, 3))
@@ -243,7 +243,7 @@ def test_framework_goal_poses_end_to_end(scratch_cwd):
 def test_off_means_off():
     """A fixed-seed DeviceEnvLoop stream (test_chain_rollout_gpu's: 100 steps, E = 64, iiwa_like7 with self-collision) hashes the
     same before and after goal poses have been solved for the same model in the same process."""
-    from robotic_manipulator_rloa_amd.engine import GoalPoseSolver
+    from robotic_manipulator_rloa_amd.chain_tools import GoalPoseSolver
     model, _ = C.arm("iiwa_like7", True)
     agent = _agent(model)
     before = _training_stream_digest(agent, model, False)

@@ -1,5 +1,5 @@
 """GPU (`-m gpu`): naf_chain_path_check (csrc/chain_env.hip) against the float64 rule of environment/kinematic.py (path_pose,
-check_joint_path) and against the existing launches at the same poses, through the C ABI; engine.JointPathChecker,
+check_joint_path) and against the existing launches at the same poses, through the C ABI; chain_tools.JointPathChecker,
 ManipulatorFramework.plan_joint_paths and reach_targets(joint_paths=True) against that path; and that training launches are
 untouched. tests/test_chain_path_cpu.py rehearses every case with a float32 restatement."""
 import ctypes
@@ -148,10 +148,10 @@ def test_placement_independence_through_the_c_abi():
 
 @pytest.mark.parametrize("name,N,Cn,chunk", [("iiwa_like7", 5, 4, 2 * 4 * 64), ("long12", 3, 5, 5 * 64), ("slider4", 9, 16, None)])
 def test_joint_path_checker_equals_the_c_abi_path_across_chunks(name, N, Cn, chunk):
-    """engine.JointPathChecker end to end, with the vias it draws, against the C-ABI launch fed path_vias of the same seed, and in
+    """chain_tools.JointPathChecker end to end, with the vias it draws, against the C-ABI launch fed path_vias of the same seed, and in
     chunks of two queries / one query against one chunk: every field of JointPaths bit for bit. resolution = 1 rad puts every chunk
     at S = 64, so that the chunks sample as the one launch does."""
-    from robotic_manipulator_rloa_amd.engine import JointPathChecker
+    from robotic_manipulator_rloa_amd.chain_tools import JointPathChecker
     base = P.build_case(name, N, Cn, 64)
     vias = path_vias(base.model, base.q_start, base.q_goal, Cn, seed=11)
     assert path_chunks(path_leg_lengths(vias, base.q_start, base.q_goal), Cn, 1.0) == [(0, N, 64)]
@@ -234,7 +234,7 @@ def test_framework_joint_paths_end_to_end(scratch_cwd):
 def test_off_means_off():
     """A fixed-seed DeviceEnvLoop stream (test_chain_rollout_gpu's: 100 steps, E = 64, iiwa_like7 with self-collision) hashes the
     same before and after joint paths have been checked for the same model in the same process."""
-    from robotic_manipulator_rloa_amd.engine import JointPathChecker
+    from robotic_manipulator_rloa_amd.chain_tools import JointPathChecker
     model, twin = C.arm("iiwa_like7", True)
     agent = _agent(model)
     before = _training_stream_digest(agent, model, False)

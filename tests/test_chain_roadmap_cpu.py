@@ -460,7 +460,7 @@ def test_reach_targets_with_a_roadmap_against_a_stub_agent(monkeypatch):
         asked.append(kw)
         return planned
 
-    monkeypatch.setattr(f, "_paths_to_goals", paths_to_goals)
+    monkeypatch.setattr(f.arm_planner, "paths_to_goals", paths_to_goals)
     out = f.reach_targets(targets, obstacles=ob, initial_joint_positions=q0, frames=F, joint_paths=True, roadmap=R.ROADMAP)
     plain = f.reach_targets(targets, obstacles=ob, initial_joint_positions=q0, frames=F, joint_paths=True)
     assert asked == [{"roadmap": R.ROADMAP}, {}] and out.path is planned

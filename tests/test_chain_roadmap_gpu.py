@@ -1,5 +1,5 @@
 """GPU (`-m gpu`): naf_chain_edge_check (csrc/chain_env.hip) against the float64 rule of environment/kinematic.py (edge_pose,
-check_joint_edge) through the C ABI; engine.JointPathChecker.check(roadmap=M), ManipulatorFramework.plan_joint_paths(roadmap=M) and
+check_joint_edge) through the C ABI; chain_tools.JointPathChecker.check(roadmap=M), ManipulatorFramework.plan_joint_paths(roadmap=M) and
 reach_targets(joint_paths=True, roadmap=M) against that rule and roadmap_search; and that training launches are untouched.
 tests/test_chain_roadmap_cpu.py rehearses every case with a float32 restatement."""
 import ctypes
@@ -145,7 +145,7 @@ def test_argument_errors_launch_nothing():
 # ---- the checker ----------------------------------------------------------------------------------------------------------------------
 def checked_with_records(monkeypatch, name, cut=None, chunk=None):
     """JointPathChecker.check(roadmap=14) on a value set, without and with the roadmap, and what the roadmap round gathered from"""
-    from robotic_manipulator_rloa_amd.engine import JointPathChecker
+    from robotic_manipulator_rloa_amd.chain_tools import JointPathChecker
     q0, q1, ob, margin = R.value_queries(name, cut)
     seen = {}
     gather = GATHER
@@ -198,7 +198,7 @@ def test_joint_path_checker_with_a_roadmap_end_to_end(monkeypatch, name, cut):
 def test_joint_path_checker_roadmap_chunks_and_refusals(monkeypatch):
     """A budget that holds one query's 120 edges at a time gives the fields of the single chunk wherever both sample alike (the
     chunk's S is its own queries'), the launches counted; refusals of check()."""
-    from robotic_manipulator_rloa_amd.engine import JointPathChecker
+    from robotic_manipulator_rloa_amd.chain_tools import JointPathChecker
     _, _, whole, seen, (q0, q1, ob, margin) = checked_with_records(monkeypatch, "planar3")
     E = len(seen["edges"])
     small, _, parts, seen_parts, _ = checked_with_records(monkeypatch, "planar3", chunk=E * int(seen["samples"].max()))
@@ -278,7 +278,7 @@ def test_framework_roadmap_end_to_end(scratch_cwd):
 def test_off_means_off():
     """A fixed-seed DeviceEnvLoop stream (test_chain_rollout_gpu's: 100 steps, E = 64, iiwa_like7 with self-collision) hashes the
     same before and after roadmaps have been checked for the same model in the same process."""
-    from robotic_manipulator_rloa_amd.engine import JointPathChecker
+    from robotic_manipulator_rloa_amd.chain_tools import JointPathChecker
     model, twin = C.arm("iiwa_like7", True)
     agent = _agent(model)
     before = _training_stream_digest(agent, model, False)

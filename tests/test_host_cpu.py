@@ -713,11 +713,50 @@ def test_engine_classes_stay_small():
     # VERDICT r06 weak point 9: Learner.__init__ chose the chain, derived its counts, allocated, described the bundle and set up the
     # exchange in one body of 323 lines. The choice is chain_plan.plan_chain now (table-tested on the CPU, test_chain_plan_cpu.py) and
     # no function of the two files is longer than 120 lines. (The class Learner is not bounded: its launch methods are argument lists.)
-    for name in ("learner.py", "chain_plan.py"):
+    for name in ("learner.py", "chain_plan.py", "arm_planner.py", "chain_tools.py"):
         tree = ast.parse(open(os.path.join(ROOT, "robotic_manipulator_rloa_amd", name)).read())
         long = {n.name: n.end_lineno - n.lineno + 1 for n in ast.walk(tree)
                 if isinstance(n, (ast.FunctionDef, ast.AsyncFunctionDef)) and n.end_lineno - n.lineno + 1 > 120}
         assert not long, (name, long)
+    # The class bound above made engine.py grow by whole classes: the chain-model tools that need no agent and capture no graph are
+    # chain_tools.py's now, which knows neither the engine nor the learner, and the facade's arm-planning methods are guards and one
+    # delegating call to arm_planner.ArmPlanner, whose one cache replaces the facade's four attributes.
+    def parsed(*path):
+        return ast.parse(open(os.path.join(ROOT, "robotic_manipulator_rloa_amd", *path)).read())
+
+    def functions(tree):
+        return {n.name: n for n in ast.walk(tree) if isinstance(n, ast.FunctionDef)}
+    assert not {"GoalPoseSolver", "JointPathChecker", "DemonstrationWriter"} & set(sizes)
+    imported = {(n.module or "") if isinstance(n, ast.ImportFrom) else a.name for n in ast.walk(parsed("chain_tools.py"))
+                if isinstance(n, (ast.Import, ast.ImportFrom)) for a in n.names}
+    assert imported and not {m for m in imported if m.split(".")[-1] in ("engine", "learner")}, imported
+    facade_src = open(os.path.join(ROOT, "robotic_manipulator_rloa_amd", "rl_framework.py")).read()
+    facade = functions(ast.parse(facade_src))
+    for name in ("reach_targets", "plan_joint_paths", "demonstrate_joint_paths", "solve_goal_poses"):
+        body = facade[name].body
+        assert isinstance(body[0].value, ast.Constant) and isinstance(body[0].value.value, str), name      # the docstring stays
+        assert body[-1].end_lineno - body[1].lineno + 1 <= 20, name
+    for gone in ("_path_checker", "_cert_checker", "_goal_solver", "_demo_writer"):
+        assert gone not in facade_src, gone
+    # one orchestration of the joint paths: the twin's entry and the device's reach the chunk loop, the refinement rounds and the
+    # roadmap round through kinematic.plan_paths alone
+    host, check = functions(parsed("environment", "kinematic.py"))["joint_paths_host"], functions(parsed("chain_tools.py"))["check"]
+    for fn in (host, check):
+        named = {n.id for n in ast.walk(fn) if isinstance(n, ast.Name)} | {n.attr for n in ast.walk(fn) if isinstance(n, ast.Attribute)}
+        assert "plan_paths" in named and not named & {"path_chunks", "certify_rounds", "roadmap_round"}, (fn.name, named)
+
+    # net size: the five files hold fewer non-blank, non-docstring lines than the three did before the move (3,061)
+    def code_lines(tree, src):
+        doc = set()
+        for n in ast.walk(tree):
+            if isinstance(n, (ast.Module, ast.ClassDef, ast.FunctionDef, ast.AsyncFunctionDef)) and ast.get_docstring(n, clean=False) is not None:
+                doc.update(range(n.body[0].lineno, n.body[0].end_lineno + 1))
+        return sum(1 for i, line in enumerate(src.splitlines(), 1) if line.strip() and i not in doc)
+    total = 0
+    for path in (("rl_framework.py",), ("engine.py",), ("environment", "kinematic.py"), ("arm_planner.py",), ("chain_tools.py",)):
+        text = open(os.path.join(ROOT, "robotic_manipulator_rloa_amd", *path)).read()
+        total += code_lines(ast.parse(text), text)
+    assert total < 3061, total
 
 
 def test_no_kernel_spills_to_scratch_and_the_switch_list_is_short():
