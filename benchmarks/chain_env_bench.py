@@ -60,6 +60,9 @@ launches are the box instantiations, which test the floor and the spheres too.
       path launch's number of workgroups or fewer, at the same S = 256, with both launches' time per sample. Then the README's
       question with and without JointPathChecker.check(roadmap=M): the outcome shares among the queries with a free goal pose,
       how many 'blocked' ones the roadmap turned into 'roadmap', the node counts of those, and the seconds each call took.
+      --roadmap M --shortcut W: the question a third time with check(roadmap=M, shortcut=W), and under "shortcut" the 'roadmap'
+      polylines before and after the round: length over the straight line, node counts, planned ticks at speed 1, and how their
+      demonstrations along all legs (demonstration_plan_legs, frames = 400, through DemonstrationWriter) end.
 
   python benchmarks/chain_env_bench.py demo [--envs 2048] [--launches 20] [--boxes]
       planned joint paths as replay rows, same arm and cell: N = --envs demonstrations (default 2048 here) of T = 400 ticks.
@@ -67,6 +70,9 @@ launches are the box instantiations, which test the floor and the spheres too.
       unmeasured ones), and in the same process the composed form it replaces — 400 x naf_chain_env_step at E = N behind one
       naf_chain_env_reset_given, the actions already on the device — with their ratio, the mean number of valid rows, the shares of
       the end codes and the new kernels' registers.
+      --legs K: instead, microseconds per naf_chain_demo_rows_legs launch beside the naf_chain_demo_rows launch, alternating in the
+      same process, on the same two-leg plans: the legs launch takes them split into K legs of the same actions, and the valid rows
+      and records of the two are compared to the bit.
 
 `--hindsight R` (rate): the chain runs relabel a share R of every minibatch (NAFAgent.run_vectorized(hindsight=R)). Such a run
 wants an empty ring, so with the flag — also `--hindsight 0`, the figure to compare with — the warm-up steps run on an agent of
@@ -515,7 +521,8 @@ def _paths_roadmap(a, checker, model, N, C, S, launches, init, rng, urdf, q_star
     goal = GoalPoseSolver(model, 0.06).solve(start, targets, obstacle)
     ok = goal.free
     found, seconds = {}, {}
-    for name, kw in (("one_via", {}), ("roadmap", {"roadmap": M})):
+    for name, kw in (("one_via", {}), ("roadmap", {"roadmap": M})) + ((("shortcut", {"roadmap": M, "shortcut": a.shortcut}),)
+                                                                     if a.shortcut else ()):
         torch.cuda.synchronize()
         t = time.perf_counter()
         found[name] = checker.check(start[ok], goal.joint_positions[ok], obstacle[ok], candidates=C, resolution=0.02, **kw)
@@ -523,6 +530,7 @@ def _paths_roadmap(a, checker, model, N, C, S, launches, init, rng, urdf, q_star
     kinds = ("straight", "via", "roadmap", "blocked", "start", "goal")
     with_map = found["roadmap"]
     rescued = with_map.outcome == "roadmap"
+    shortcut = _shortcut_report(a, model, found, rescued, targets[ok], obstacle[ok]) if a.shortcut else None
     usage = json.load(open(_lib.USAGE_PATH)) if os.path.exists(_lib.USAGE_PATH) else {}
     regs = {name: {q: v.get(q) for q in ("vgprs", "sgprs", "scratch_bytes_per_lane", "lds_bytes", "occupancy")}
             for name, v in usage.items() if "chain_edge_" in name}
@@ -542,7 +550,31 @@ def _paths_roadmap(a, checker, model, N, C, S, launches, init, rng, urdf, q_star
                       "median_length_over_straight": (round(float(np.median(with_map.length[rescued] / with_map.straight_length[rescued])), 3)
                                                       if rescued.any() else None),
                       "roadmap_samples": {str(k): int(v) for k, v in zip(*np.unique(with_map.samples[rescued], return_counts=True))},
-                      "edge_launches": checker.edge_launches - (launches + 2), "seconds": seconds, "kernel_registers": regs}))
+                      "edge_launches": checker.edge_launches - (launches + 2), "seconds": seconds, "shortcut": shortcut,
+                      "kernel_registers": regs}))
+
+
+def _shortcut_report(a, model, found, rescued, targets, obstacles):
+    """--shortcut W: the 'roadmap' polylines before and after the shortcut round — length over the straight line, node counts,
+    ticks at speed 1 — and how their demonstrations along all legs (demonstration_plan_legs, frames = 400) end"""
+    import numpy as np
+    from robotic_manipulator_rloa_amd.chain_tools import DemonstrationWriter
+    from robotic_manipulator_rloa_amd.environment.kinematic import demonstration_plan_legs
+    writer = DemonstrationWriter(model, 0.06)
+    out = {"nodes": a.shortcut, "roadmap_queries": int(rescued.sum()),
+           "shortened": int(np.sum(found["shortcut"].length[rescued] < found["roadmap"].length[rescued]))}
+    for name in ("roadmap", "shortcut"):
+        p = found[name]
+        ratio = (p.length / p.straight_length)[rescued]
+        plan = demonstration_plan_legs(p.nodes[rescued], p.n_nodes[rescued], 1.0, 400)
+        demos = writer.write(plan, targets[rescued], obstacles[rescued], keep_contact=True)
+        out[name] = {"median_length_over_straight": round(float(np.median(ratio)), 3), "max_length_over_straight": round(float(ratio.max()), 3),
+                     "node_counts": {str(k): int(v) for k, v in zip(*np.unique(p.n_nodes[rescued], return_counts=True))},
+                     "median_planned_ticks": int(np.median(demos.planned_ticks)),
+                     "planned_ticks_within_400": int(np.sum(demos.planned_ticks <= 400)),
+                     "demonstration_outcomes": {str(k): int(v) for k, v in zip(*np.unique(demos.outcome, return_counts=True))}}
+    out["legs_launches"] = writer.legs_launches
+    return out
 
 
 def demo(a):
@@ -573,6 +605,8 @@ def demo(a):
     plan = demonstration_plan(q_start, via, q_goal, 1.0, T)
     writer = DemonstrationWriter(model, 0.06, chunk=N * T)
     writer.load(plan, targets, obstacles, slice(0, N))
+    if a.legs:
+        return _demo_legs(a, writer, plan, targets, obstacles, N, T, launches, urdf, model)
     fused = []
     for i in range(launches + 2):
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -616,6 +650,58 @@ def demo(a):
                       "composed_over_fused": round(c_med / f_med, 3), "mean_valid_rows": round(float(rec[:, 0].mean()), 1),
                       "end_code_shares": {str(k): round(float(np.mean(rec[:, 1] == k)), 4) for k in range(6)},
                       "first_rows_bit_equal": bool(first), "kernel_registers": regs}))
+
+
+def _demo_legs(a, writer, plan, targets, obstacles, N, T, launches, urdf, model):
+    """--legs K: naf_chain_demo_rows_legs beside naf_chain_demo_rows, alternating in one process, on the same two-leg plans — the
+    legs launch takes them split into K legs of the same actions (each leg of the plan cut into near-equal pieces), so that both
+    write the same rows"""
+    import numpy as np
+    import torch
+    from robotic_manipulator_rloa_amd import _lib
+    K = a.legs
+    ticks, acts = np.zeros((N, K), np.int32), np.zeros((N, K) + plan.leg_actions.shape[2:], np.float32)
+    for n in range(N):
+        col = 0
+        for leg, parts in ((0, max(1, K // 2)), (1, K - max(1, K // 2))):
+            total = int(plan.n_ticks[n, leg])
+            parts = min(parts, total)
+            for k in range(parts):
+                ticks[n, col], acts[n, col] = total * (k + 1) // parts - total * k // parts, plan.leg_actions[n, leg]
+                col += 1
+    assert K >= 2 and np.array_equal(ticks.sum(axis=1), plan.n_ticks.sum(axis=1))
+    two_rows = writer.rows
+    legs_rows, legs_records, two_records = torch.zeros_like(two_rows), torch.zeros_like(writer.records), writer.records
+    writer.load_legs(plan._replace(n_ticks=ticks, leg_actions=acts), targets, obstacles, slice(0, N))
+
+    def launch_legs():
+        writer.rows, writer.records = legs_rows, legs_records
+        writer.launch_legs(N, K, T)
+        writer.rows, writer.records = two_rows, two_records
+
+    times = {"two_legs": [], "legs": []}
+    for i in range(launches + 2):                              # alternating, so that both see the same clocks
+        for name, launch in (("two_legs", lambda: writer.launch(N, T)), ("legs", launch_legs)):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            launch()
+            t1.record()
+            t1.synchronize()
+            if i >= 2:
+                times[name].append(1e3 * t0.elapsed_time(t1))
+    rec = two_records[:N].cpu().numpy()
+    live = (torch.arange(T, device=two_rows.device)[None, :] < two_records[:N, 0].long()[:, None]).reshape(-1)
+    same = torch.equal(two_rows[:N * T][live], legs_rows[:N * T][live]) and torch.equal(two_records[:N], legs_records[:N])
+    usage = json.load(open(_lib.USAGE_PATH)) if os.path.exists(_lib.USAGE_PATH) else {}
+    regs = {name: {q: v.get(q) for q in ("vgprs", "sgprs", "scratch_bytes_per_lane", "lds_bytes", "occupancy")}
+            for name, v in usage.items() if "chain_demo_" in name}
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    print(json.dumps({"arm": os.path.basename(urdf), "demonstrations": N, "ticks": T, "legs": K, "self_pairs": len(model.self_pairs),
+                      "workcell_pairs": len(model.cell_pairs), "boxes": bool(a.boxes),
+                      "us_per_demo_rows_launch": {"median": round(med["two_legs"], 1), "min": round(float(np.min(times["two_legs"])), 1)},
+                      "us_per_demo_rows_legs_launch": {"median": round(med["legs"], 1), "min": round(float(np.min(times["legs"])), 1)},
+                      "legs_over_two_legs": round(med["legs"] / med["two_legs"], 3), "mean_valid_rows": round(float(rec[:, 0].mean()), 1),
+                      "valid_rows_and_records_bit_equal": bool(same), "kernel_registers": regs}))
 
 
 def kernels(a):
@@ -672,6 +758,10 @@ def main():
     ap.add_argument("--certify", action="store_true", help="path: time naf_chain_path_certify beside naf_chain_path_check, and certify the README's paths")
     ap.add_argument("--roadmap", type=int, default=0, metavar="M",
                     help="path: time naf_chain_edge_check beside naf_chain_path_check, and answer the README's paths with M milestones")
+    ap.add_argument("--shortcut", type=int, default=0, metavar="W",
+                    help="path, with --roadmap: answer the README's paths again with a shortcut round over W nodes, and demonstrate them")
+    ap.add_argument("--legs", type=int, default=0, metavar="K",
+                    help="demo: time naf_chain_demo_rows_legs, the same plans split into K legs, beside naf_chain_demo_rows")
     ap.add_argument("--trajectory", action="store_true", help="rollout: record the joint values of every frame")
     ap.add_argument("--arm", default="", help="rate: a fixture arm of tests/golden/urdf by name, --joints its joint count")
     ap.add_argument("--target-range", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))
@@ -681,6 +771,10 @@ def main():
     a = ap.parse_args()
     if a.roadmap and a.certify:
         ap.error("--roadmap and --certify are two measurements: roadmap edges are checked at their samples only")
+    if a.shortcut and not a.roadmap:
+        ap.error("--shortcut shortens roadmap paths: it needs --roadmap M")
+    if a.legs and not 2 <= a.legs <= 63:
+        ap.error("--legs K splits two-leg plans into K legs, 2 .. 63")
     {"rate": rate, "kernels": kernels, "step": step, "rollout": rollout, "gather": gather, "ik": ik, "path": paths, "demo": demo}[a.what](a)
 
 

@@ -1030,6 +1030,23 @@ int naf_chain_demo_rows(naf_chain_env_t* h, const float* q_start_dev, const floa
                         const float* targets_dev, const float* obstacles_dev, float obstacle_radius, int N, int T_cap, float* rows_out,
                         int row_floats, float* records_out, float* poses_out, void* stream);
 
+/* Demonstrations along K legs (an addition within ABI 40): naf_chain_demo_rows with "leg 1 then leg 2" replaced by a schedule, for
+ * polylines of any number of legs. environment/kinematic.py (demonstration_plan_legs, demo_actions) is the float64 statement.
+ *   leg_actions_dev : [N][K][A] (DEVICE), n_ticks_dev : [N][K] (DEVICE). Demonstration n applies leg_actions_dev[n][l] for
+ *                 n_ticks_dev[n][l] ticks, l = 0 .. K - 1 in turn: tick t applies the action of the leg whose cumulative range
+ *                 holds t. Leg 0 takes at least 1 tick; a count of 0 marks padding behind the query's last leg and is stepped over
+ *                 (the caller validates the counts before the upload; the kernel clamps a wrong upload into the arrays).
+ *                 T_n = min(sum_l n_l, T_cap) rows, and records_out[n][6] = sum_l n_l.
+ *   Everything else — the poses, rows_out, records_out, poses_out — is as documented for naf_chain_demo_rows; with K = 2 and both
+ *   counts >= 1, rows, records and poses are bit for bit that entry's on the same inputs.
+ * One workgroup per demonstration as there; wave 0 stages the K cumulative ends in LDS behind the base pose. No atomics.
+ * NAF_ERR_ARG, and no launch, for naf_chain_demo_rows' refusals and for K outside 1 .. NAF_CHAIN_DEMO_MAX_LEGS. */
+#define NAF_CHAIN_DEMO_MAX_LEGS 63
+int naf_chain_demo_rows_legs(naf_chain_env_t* h, const float* q_start_dev, const float* leg_actions_dev /* [N][K][A] */,
+                             const int32_t* n_ticks_dev /* [N][K] */, int K, const float* targets_dev, const float* obstacles_dev,
+                             float obstacle_radius, int N, int T_cap, float* rows_out, int row_floats, float* records_out,
+                             float* poses_out, void* stream);
+
 /* ---- one-shot gradient all-reduce over peer-mapped memory (no reference counterpart) ----------
  * The data-parallel exchange that follows loss.backward() (naf_algorithm.py:207-210 on every rank): sum of the flat
  * gradient over the W <= 8 GPUs of one node, each rank pushing its gradient into a receive slot on every peer over

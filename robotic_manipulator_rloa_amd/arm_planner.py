@@ -17,7 +17,8 @@ import torch
 
 from .environment.kinematic import (DEMO_MAX_TICKS, PATH_CANDIDATES_MAX, ROADMAP_MAX, JointPaths, demonstration_plan,
                                     demonstration_rows_host, demonstration_speed_ok, goal_poses_host, ik_restarts_ok, joint_paths_host,
-                                    reach_queries, roadmap_milestones, roadmap_size_ok)
+                                    reach_queries, roadmap_milestones, roadmap_size_ok, shortcut_size_ok)
+from .environment.polyline import SHORTCUT_MAX, SHORTCUT_MIN, pad_shortcut, polyline_plan, roadmap_arguments, roadmap_queries
 from .utils.exceptions import InvalidEnvironmentParameter
 from .utils.logger import get_global_logger
 
@@ -58,6 +59,8 @@ _ARGUMENT_RULES = {
     'certify': (lambda v: isinstance(v, (bool, np.bool_)), 'a bool'),
     'speed': (demonstration_speed_ok, 'a share of the unit action, 0 < speed <= 1'),
     'frames': (lambda v: _positive_int(v) and v <= DEMO_MAX_TICKS, f'a number of steps from 1 to {DEMO_MAX_TICKS}'),
+    'shortcut': (shortcut_size_ok, f'a number of nodes, 0 (no shortcut round) or from {SHORTCUT_MIN} to {SHORTCUT_MAX}'),
+    'polylines': (lambda v: isinstance(v, (bool, np.bool_)), 'a bool'),
 }
 
 
@@ -69,13 +72,16 @@ def check_arguments(**given) -> None:
             raise InvalidEnvironmentParameter(f'{name} is {words}: got {v!r}')
 
 
-def check_roadmap(roadmap, certify, who) -> None:
+def check_roadmap(roadmap, certify, who, shortcut=0) -> None:
     if not roadmap_size_ok(roadmap):
         raise InvalidEnvironmentParameter(f'roadmap is a number of milestones from 0 to {ROADMAP_MAX} (0: no roadmap): '
                                           f'got {roadmap!r}')
     if roadmap and certify:
         raise InvalidEnvironmentParameter(f'{who}(roadmap={roadmap!r}, certify=True): roadmap edges are checked at their samples '
                                           f'only, and nothing certifies a \'roadmap\' path between them')
+    check_arguments(shortcut=shortcut)
+    if shortcut and not roadmap:
+        raise InvalidEnvironmentParameter(f'{who}(shortcut={shortcut!r}) shortens \'roadmap\' polylines: it needs roadmap=M with M > 0')
 
 
 class ArmPlanner:
@@ -147,19 +153,19 @@ class ArmPlanner:
         return q0, q_goal, obstacles
 
     def plan_joint_paths(self, targets, obstacles, initial_joint_positions, goal_joint_positions, candidates, resolution,
-                         clearance_margin, seed, on_device, certify, roadmap):
+                         clearance_margin, seed, on_device, certify, roadmap, shortcut=0):
         model = self.env.model
         if (targets is None) == (goal_joint_positions is None):
             raise InvalidEnvironmentParameter('plan_joint_paths() takes exactly one of targets and goal_joint_positions')
         check_arguments(candidates=candidates, resolution=resolution, clearance_margin=clearance_margin, seed=seed, certify=certify)
-        check_roadmap(roadmap, certify, 'plan_joint_paths')
+        check_roadmap(roadmap, certify, 'plan_joint_paths', shortcut)
         if roadmap:
             try:
                 roadmap_milestones(model, np.zeros((0, model.A)), np.zeros((0, model.A)), int(roadmap), 0)
             except ValueError as err:
                 raise InvalidEnvironmentParameter(f'roadmap: {err}') from None
         kw = dict(candidates=candidates, resolution=resolution, clearance_margin=clearance_margin, seed=seed, on_device=on_device,
-                  certify=bool(certify), roadmap=int(roadmap))
+                  certify=bool(certify), roadmap=int(roadmap), shortcut=int(shortcut))
         if targets is None:
             return self.plan_checked(*self._goal_queries(goal_joint_positions, obstacles, initial_joint_positions), **kw)
         q0, targets, obstacles, _ = self.queries(targets, obstacles, initial_joint_positions)
@@ -167,10 +173,10 @@ class ArmPlanner:
         return self.paths_to_goals(goal, q0, obstacles, kw)
 
     def plan_checked(self, q0, q_goal, obstacles, candidates=16, resolution=0.02, clearance_margin=0.0, seed=0, on_device=None,
-                     certify=False, roadmap=0) -> JointPaths:
+                     certify=False, roadmap=0, shortcut=0) -> JointPaths:
         """the paths of queries that have passed the refusals: the twin's, or the cached checker's of the kind asked for"""
         kw = dict(candidates=int(candidates), resolution=float(resolution), margin=float(clearance_margin), seed=int(seed),
-                  roadmap=int(roadmap))
+                  roadmap=int(roadmap), shortcut=int(shortcut))
         if not _on_device(on_device):
             out = joint_paths_host(self.env, q0, q_goal, obstacles, certify=bool(certify), **kw)
         else:
@@ -208,14 +214,15 @@ class ArmPlanner:
         elif kw.get('roadmap'):
             out.nodes = np.full((N, 0, A), np.nan, kind)
             out.n_nodes, out.roadmap_free_edges = np.zeros(N, np.int64), np.full(N, -1, np.int64)
+        pad_shortcut(out, found, ok, kind, kw.get('shortcut'))
         return out
 
     # ---- demonstrations -----------------------------------------------------------------------------------------------------------
-    def demonstrate_joint_paths(self, paths, targets, obstacles, speed, frames, keep_contact, on_device):
+    def demonstrate_joint_paths(self, paths, targets, obstacles, speed, frames, keep_contact, on_device, polylines=False):
         env = self.env
         if not isinstance(paths, JointPaths) or paths.start is None or paths.goal is None:
             raise InvalidEnvironmentParameter('paths is the JointPaths that plan_joint_paths() returned')
-        check_arguments(speed=speed, frames=frames)
+        check_arguments(speed=speed, frames=frames, polylines=polylines)
         has = np.asarray(paths.candidate) >= 0
         start = np.asarray(paths.start, np.float64)
         N, A = start.shape
@@ -223,13 +230,15 @@ class ArmPlanner:
             raise InvalidEnvironmentParameter(f'paths holds poses of {A} joints, the environment\'s arm has {env.model.A}')
         # a query without a path stands still at its start pose for the launch and is reported 'none'
         via = np.where(has[:, None], np.asarray(paths.via, np.float64), start)
+        has = has | roadmap_queries(paths, polylines)         # polylines: a 'roadmap' query has a path too, all its nodes
         goal = np.where(has[:, None], np.asarray(paths.goal, np.float64), start)
         if targets is None:
             targets = env.end_effector(np.asarray(goal, np.float32).astype(np.float64))
         _, targets, obstacles, _ = self.queries(targets, obstacles, None)
         if len(targets) != N:
             raise InvalidEnvironmentParameter(f'targets is [N][3] with N = {N}, the number of paths: got {len(targets)}')
-        plan = demonstration_plan(start, via, goal, float(speed), int(frames))
+        plan = (polyline_plan(paths, start, via, goal, float(speed), int(frames)) if polylines else
+                demonstration_plan(start, via, goal, float(speed), int(frames)))
         if not _on_device(on_device):
             return demonstration_rows_host(env, plan, targets, obstacles, int(frames), bool(keep_contact), has)
         from .chain_tools import DemonstrationWriter
@@ -237,14 +246,14 @@ class ArmPlanner:
 
     # ---- rollouts to given targets ------------------------------------------------------------------------------------------------
     def reach_targets(self, agent, targets, obstacles, initial_joint_positions, frames, noise_scale, n_envs, trajectories, goal_poses,
-                      joint_paths, certify, roadmap):
+                      joint_paths, certify, roadmap, shortcut=0):
         """the queries and the refusals of reach_targets(), the agent's rollout, then the goal poses, the paths and their ratios"""
         env = self.env
         q0, targets, obstacles, frames = self.queries(targets, obstacles, initial_joint_positions, frames)
         goal_poses = bool(goal_poses or joint_paths)
         if not isinstance(certify, (bool, np.bool_)) or (certify and not joint_paths):
             raise InvalidEnvironmentParameter('reach_targets(certify=True) certifies the joint paths: it is a bool and needs joint_paths=True')
-        check_roadmap(roadmap, certify, 'reach_targets')
+        check_roadmap(roadmap, certify, 'reach_targets', shortcut)
         if roadmap and not joint_paths:
             raise InvalidEnvironmentParameter('reach_targets(roadmap=M) builds roadmaps for the joint paths: it needs joint_paths=True')
         if goal_poses and not trajectories:
@@ -260,7 +269,7 @@ class ArmPlanner:
             result.path_ratio = np.where((np.asarray(result.outcome) == 'reached') & result.goal.free, ratio, np.nan)
         if joint_paths:
             result.path = self.paths_to_goals(result.goal, q0, obstacles,
-                                              {'certify': True} if certify else {'roadmap': int(roadmap)} if roadmap else {})
+                                              {'certify': True} if certify else roadmap_arguments(roadmap, shortcut))
             with np.errstate(divide='ignore', invalid='ignore'):
                 ratio = length / np.asarray(result.path.length, np.float64)
             # a query has a path when its length is a number: a candidate of the one-via round, or a 'roadmap' polyline

@@ -23,6 +23,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
+from .chain_legs import LegsLaunch
 from .environment.kinematic import (DEMO_CHUNK, DEMO_FLOATS, DEMO_MAX_TICKS, EDGE_FLOATS, PATH_CERT_FLOATS, PATH_CHUNK, PATH_FLOATS,
                                     GoalPoses, JointPaths, certificate_guard, demo_row_layout, gather_demonstrations,
                                     gather_goal_poses, ik_seeds, plan_paths, reach_table)
@@ -270,10 +271,12 @@ class JointPathChecker(_ChainTool):
         return self._download(self.edge_out, n * E, n, E, EDGE_FLOATS)
 
     def check(self, q_start, q_goal, obstacles, candidates: int = 16, resolution: float = 0.02, margin: float = 0.0,
-              seed: int = 0, roadmap: int = 0) -> JointPaths:
+              seed: int = 0, roadmap: int = 0, shortcut: int = 0) -> JointPaths:
         """q_start[N][A], q_goal[N][A] (action order), obstacles[N][3] -> JointPaths of numpy arrays (float32 where the device's).
-        roadmap = M in 1 .. 62: the queries that end 'blocked' get a roadmap of M milestones; not with a certifying checker."""
-        return plan_paths(self, q_start, q_goal, obstacles, candidates, resolution, margin, seed, self.chunk, self.certify, roadmap)
+        roadmap = M in 1 .. 62: the queries that end 'blocked' get a roadmap of M milestones; not with a certifying checker.
+        shortcut = W in 4 .. 64 (with roadmap): the 'roadmap' polylines are searched again over W nodes of their own, all pairs
+        through the same edge launch (environment.polyline.shortcut_round)."""
+        return plan_paths(self, q_start, q_goal, obstacles, candidates, resolution, margin, seed, self.chunk, self.certify, roadmap, shortcut)
 
 
 def demonstration_chunks(rows_of, budget: int) -> List[Tuple[int, int, int]]:
@@ -293,11 +296,14 @@ def demonstration_chunks(rows_of, budget: int) -> List[Tuple[int, int, int]]:
     return out
 
 
-class DemonstrationWriter(_ChainTool):
+class DemonstrationWriter(LegsLaunch, _ChainTool):
     """Planned joint paths as replay rows on a chain model (csrc/chain_env.hip, "demonstrations"): per chunk of queries ONE
     naf_chain_demo_rows launch that writes every row of every demonstration, then torch plumbing — the mask `t < valid[n] and
     kept[n]` and a boolean index — to a contiguous device tensor of the kept rows in query order, then tick order. Owns the handle
-    and staging buffers for `chunk` rows; needs no agent. A demonstration's rows do not depend on where in a launch it lies."""
+    and staging buffers for `chunk` rows; needs no agent. A demonstration's rows do not depend on where in a launch it lies.
+    A plan of two legs of at least one tick each takes that launch; any other plan of K <= 63 legs (demonstration_plan_legs: a
+    polyline, 0 ticks for the padding behind a query's last leg) takes naf_chain_demo_rows_legs (chain_legs.LegsLaunch), whose staging
+    [chunk][K][A] / [chunk][K] is allocated on the first such call. Chunks, keep / drop and the gather are the same for both."""
     CHUNK, CHUNK_MIN, CHUNK_REFUSAL = DEMO_CHUNK, 1, "DemonstrationWriter: a chunk holds at least one row"
 
     def __init__(self, chain, obstacle_radius: float = 0.06, chunk: Optional[int] = None, device=None):
@@ -332,9 +338,7 @@ class DemonstrationWriter(_ChainTool):
         is a device tensor [rows_total][row_floats]. has_path[N] (default all): queries without one are launched with whatever
         plan holds for them and reported 'none'."""
         N = len(plan.q_start)
-        ticks = np.asarray(plan.n_ticks)
-        if ticks.shape != (N, 2) or (N and ticks.min() < 1):
-            raise ValueError("DemonstrationWriter: every leg of a plan takes at least one tick")
+        load, launch = self.entry_for(plan)                   # the two-leg entry or, for any other plan of K legs, the legs entry
         T_of = np.asarray(plan.rows, np.int64)
         if N and (T_of.min() < 1 or T_of.max() > DEMO_MAX_TICKS):
             raise ValueError(f"DemonstrationWriter: a demonstration holds 1 .. {DEMO_MAX_TICKS} rows")
@@ -345,8 +349,8 @@ class DemonstrationWriter(_ChainTool):
         records, parts = np.zeros((N, DEMO_FLOATS), np.float32), []
         for first, n, T_cap in demonstration_chunks(T_of, self.chunk):
             sl = slice(first, first + n)
-            self.load(plan, targets, obstacles, sl)
-            self.launch(n, T_cap)
+            load(plan, targets, obstacles, sl)
+            launch(n, T_cap)
             records[sl] = self._download(self.records, n)
             # (the staging rows are reused by the next chunk: this chunk's kept rows are taken now)
             parts.append(self._kept_of(self.rows[:n * T_cap].view(n, T_cap, self.row_floats), records[sl], has[sl], keep_contact))

@@ -1825,3 +1825,193 @@ extern "C" int naf_chain_demo_rows(naf_chain_env_t* h, const float* q_start_dev,
             obstacles_dev, obstacle_radius, T_cap, h->A, h->n_seg, w.n_pairs, w.lanes, row_floats, rows_out, records_out, poses_out, cell...);
     });
 }
+
+// ---- demonstrations along polylines of any number of legs (include/naf_hip.h, "Demonstrations along K legs") -----------------------
+// chain_demo_rows_kernel with "leg 1 then leg 2" replaced by a schedule: ends[l] = the ticks of legs 0 .. l, staged once in LDS behind
+// the base by thread 0 (at most NAF_CHAIN_DEMO_MAX_LEGS ints). Tick k belongs to the first leg whose end lies beyond it; a leg of 0
+// ticks — the padding behind a query's last — has the end of the leg before it and is stepped over, and the search stops at leg
+// K - 1. A tick loop keeps a leg index that only grows and reloads the leg's action only when the index changes; it starts from
+// the leg of the pass's first tick, which wave 0 carries from pass to pass beside the leg of the tick before it (row b - 1's
+// action is that leg's). Both are uniform. The ends are only read by wave 0, behind the demo_wave_order that orders the base.
+__device__ static inline int demo_leg_of(const int* ends, int K, int l, int k) {      // the leg of tick k, searched upwards from leg l
+    while (l < K - 1 && k >= ends[l]) ++l;
+    return l;
+}
+
+// ticks k0 .. k1 - 1 of joint m from the leg l of tick k0; acts = leg_actions[n] + m, a leg A floats on
+__device__ static inline void demo_run_legs(const float* j, const float* acts, int A, const int* ends, int K, int l, int k0, int k1,
+                                            float& q, float& vel) {
+    int end = ends[l];
+    float u = acts[l * A];
+    for (int k = k0; k < k1; ++k) {
+        if (k >= end && l < K - 1) {
+            do end = ends[++l];
+            while (k >= end && l < K - 1);
+            u = acts[l * A];
+        }
+        demo_tick(j, u, q, vel);
+    }
+}
+
+template <bool SC, class... Cell>
+__global__ void __launch_bounds__(SC ? 64 * CH_MAX_WAVES : 64)
+chain_demo_legs_kernel(const float* __restrict__ model, const float* __restrict__ q_start, const float* __restrict__ leg_actions,
+                       const int* __restrict__ n_ticks, int K, const float* __restrict__ targets, const float* __restrict__ obstacles,
+                       float orad, int T_cap, int A, int n_seg, int n_pairs, int lanes, int row_floats, float* __restrict__ rows_out,
+                       float* __restrict__ records_out, float* __restrict__ poses_out, const Cell... cell) {
+    constexpr bool CELL = (std::is_same_v<Cell, ChainCell> || ... || false);
+    constexpr bool BOX = (std::is_same_v<Cell, ChainBox> || ... || false);
+    extern __shared__ __attribute__((aligned(16))) float ch_lds[];
+    const int64_t n = blockIdx.x;
+    const int S = 2 * A + 9;
+    const int off_s2 = naf_row_off_s2(S, A), off_d = naf_row_off_done(S, A);
+    const float* acts = leg_actions + n * K * A;
+    const float ox = obstacles[n * 3], oy = obstacles[n * 3 + 1], oz = obstacles[n * 3 + 2];
+    const float tx = targets[n * 3], ty = targets[n * 3 + 1], tz = targets[n * 3 + 2];
+    const int lane = threadIdx.x & 63;
+    const bool active = lane < lanes;
+    const bool wave0 = threadIdx.x < 64;
+    float* base = ch_lds + (SC ? ch_lds_bytes(n_seg, lanes, blockDim.x >> 6) / sizeof(float) : 0);
+    int* ends = (int*)(base + ch_demo_base_floats(A));
+    // (the host validated the counts; the clamps only keep a wrong upload inside the arrays. Every thread sums them: T is uniform)
+    int total = 0;
+    for (int l = 0; l < K; ++l) {
+        total += min(max(n_ticks[n * K + l], l == 0 ? 1 : 0), 1 << 20);
+        if (threadIdx.x == 0) ends[l] = total;
+    }
+    const int T = min(total, T_cap);                     // rows of this demonstration; poses 0 .. T
+    float* rows = rows_out + n * T_cap * row_floats;
+    if (wave0) {
+        for (int m = lane; m < A; m += 64) {
+            const float* j = model + CH_HDR + m * CH_JNT;
+            float q = q_start[n * A + m];
+            if (j[16] != 0.f) {      // p_0: the start pose clamped into the limits, as naf_chain_env_reset_given clamps it
+                if (q > j[18]) q = j[18];
+                if (q < j[17]) q = j[17];
+            }
+            base[m] = q;
+            base[A + 6 + m] = 0.f;
+        }
+        if (lane < 3) {
+            base[A + lane] = targets[n * 3 + lane];
+            base[A + 3 + lane] = obstacles[n * 3 + lane];
+        }
+        demo_wave_order();
+    }
+    float min_clear = INFINITY, min_self = INFINITY, min_cell = INFINITY, final_dist = -1.f;
+    int first_key = INT_MAX;      // 8 x (row of the first done) + its end code
+    bool stopped = false;         // (uniform in wave 0) a pass before this one held the first done
+    int leg_b = 0, leg_prev = 0;  // (uniform in wave 0) the legs of tick b and of tick max(b - 1, 0)
+    for (int b = 0; b <= T; b += lanes) {      // (uniform: every thread takes every pass)
+        const int t = b + lane;
+        const bool walks = active && wave0 && t <= T;
+        float* prev = rows + (int64_t)(t - 1) * row_floats;      // row t - 1: used only where t >= 1
+        float* o = t < T ? prev + row_floats : prev + off_s2;    // obs(p_t): row t's state, or the last row's next_state
+        float ee[3];
+        bool hit = false;
+        WalkAux aux = {SC ? ch_lds + lane : nullptr, lanes, INFINITY, INFINITY};
+        if (walks) {
+            float* rec = poses_out ? poses_out + ((n * (T_cap + 1)) + t) * A : nullptr;
+            hit = chain_walk_at<SC, false, false, true, CELL, BOX>(
+                model, A, n_seg,
+                [=](int m) {
+                    const float* j = model + CH_HDR + m * CH_JNT;
+                    float q = base[m], vel = base[A + 6 + m];
+                    demo_run_legs(j, acts + m, A, ends, K, leg_b, b, t, q, vel);
+                    const int slot = (int)j[21];
+                    if (slot >= 0) o[A + slot] = vel;      // what step t - 1 reported (0 at t = 0, 0 where a limit stopped the joint)
+                    if (rec) rec[m] = q;
+                    return q;
+                },
+                ox, oy, oz, orad, base, o, ee, aux);
+        }
+        float self_clear = INFINITY;
+        if constexpr (SC) self_clear = self_clearance_phase(model, A, n_seg, n_pairs, ch_lds, lanes, lane, active && t <= T);
+        if (wave0) {
+            const bool outcome = walks && t >= 1;      // the walk of p_t is the outcome of row t - 1
+            float dist = 0.f, clear = INFINITY, cellc = INFINITY;
+            bool done = false;
+            int code = 0;
+            if (outcome) {
+                const float dx = ee[0] - tx, dy = ee[1] - ty, dz = ee[2] - tz;
+                dist = sqrtf(dx * dx + dy * dy + dz * dz);
+                clear = aux.clear - orad;
+                if constexpr (CELL) cellc = aux.cell;
+                const bool reached = dist < CH_REACHED, self_hit = self_clear < 0.f, cell_hit = CELL && aux.cell < 0.f;
+                const bool any = hit || self_hit || cell_hit;
+                done = reached || any;
+                code = reached ? 1 : (hit ? 2 : (self_hit ? 3 : (cell_hit ? 4 : 0)));
+                const float* act = acts + demo_leg_of(ends, K, leg_prev, t - 1) * A;      // the action of tick t - 1's leg
+                for (int m = 0; m < A; ++m) prev[S + m] = act[m];
+                prev[S + A] = reached ? 250.f : (any ? -1000.f : -(dist - CH_REACHED));
+                for (int k = S + A + 1; k < off_s2; ++k) prev[k] = 0.f;
+                if (t < T)
+                    for (int k = 0; k < S; ++k) prev[off_s2 + k] = o[k];
+                prev[off_d] = done ? 1.f : 0.f;
+                for (int k = off_d + 1; k < row_floats; ++k) prev[k] = 0.f;      // the tag float included: an untagged row
+            }
+            const unsigned long long mask = __ballot(outcome && done);
+            const int first_lane = mask ? __ffsll(mask) - 1 : 64;
+            if (!stopped && outcome && lane <= first_lane) {      // rows up to the first done are the demonstration's
+                min_clear = fminf(min_clear, clear);
+                min_self = fminf(min_self, self_clear);
+                min_cell = fminf(min_cell, cellc);
+                if (lane == first_lane) { first_key = (t - 1) * 8 + code; final_dist = dist; }
+                else if (t == T && !mask) final_dist = dist;
+            }
+            stopped = stopped || mask != 0ull;
+            if (b + lanes <= T) {      // another pass: the base moves on by `lanes` ticks, a joint per lane
+                demo_wave_order();
+                for (int m = lane; m < A; m += 64) {
+                    const float* j = model + CH_HDR + m * CH_JNT;
+                    float q = base[m], vel = base[A + 6 + m];
+                    demo_run_legs(j, acts + m, A, ends, K, leg_b, b, b + lanes, q, vel);
+                    base[m] = q;
+                    base[A + 6 + m] = vel;
+                }
+                leg_prev = demo_leg_of(ends, K, leg_b, b + lanes - 1);
+                leg_b = demo_leg_of(ends, K, leg_prev, b + lanes);
+                demo_wave_order();
+            }
+        }
+    }
+    if (!wave0) return;      // (behind the last barrier; wave 0 is whole: the lanes that walked nothing hold the identities)
+    for (int off = 32; off > 0; off >>= 1) {
+        min_clear = fminf(min_clear, __shfl_xor(min_clear, off));
+        min_self = fminf(min_self, __shfl_xor(min_self, off));
+        min_cell = fminf(min_cell, __shfl_xor(min_cell, off));
+        first_key = min(first_key, __shfl_xor(first_key, off));
+        final_dist = fmaxf(final_dist, __shfl_xor(final_dist, off));
+    }
+    if (threadIdx.x != 0) return;
+    float* r = records_out + n * NAF_CHAIN_DEMO_FLOATS;
+    r[0] = first_key == INT_MAX ? (float)T : (float)(first_key / 8 + 1);
+    r[1] = first_key == INT_MAX ? (T < total ? 0.f : 5.f) : (float)(first_key % 8);
+    r[2] = final_dist;
+    r[3] = min_clear;
+    r[4] = min_self;
+    r[5] = min_cell;
+    r[6] = (float)total;
+    r[7] = 0.f;
+}
+
+extern "C" int naf_chain_demo_rows_legs(naf_chain_env_t* h, const float* q_start_dev, const float* leg_actions_dev,
+                                        const int32_t* n_ticks_dev, int K, const float* targets_dev, const float* obstacles_dev,
+                                        float obstacle_radius, int N, int T_cap, float* rows_out, int row_floats, float* records_out,
+                                        float* poses_out, void* stream) {
+    if (!h || !q_start_dev || !leg_actions_dev || !n_ticks_dev || !targets_dev || !obstacles_dev || !rows_out || !records_out)
+        return NAF_ERR_ARG;
+    if (K < 1 || K > NAF_CHAIN_DEMO_MAX_LEGS) return NAF_ERR_ARG;
+    if (N < 1 || N > 1 << 30 || T_cap < 1 || T_cap > NAF_CHAIN_DEMO_MAX_TICKS) return NAF_ERR_ARG;
+    if (row_floats <= 0 || row_floats != naf_replay_row_floats(2 * h->A + 9, h->A)) return NAF_ERR_ARG;
+    if (!std::isfinite(obstacle_radius) || obstacle_radius < 0.f) return NAF_ERR_ARG;
+    return ch_with_pack(h, [&](auto sc, auto... cell) {
+        ChShape w = ch_shape<sc()>(h, h->waves);
+        // the probe's rows, the base behind them and the K ends behind the base
+        w.lds += (size_t)ch_demo_base_floats(h->A) * sizeof(float) + (size_t)K * sizeof(int);
+        return ch_launch_raising<chain_demo_legs_kernel<sc(), decltype(cell)...>>(
+            CH_MAX_DYN_LDS + 1024 + NAF_CHAIN_DEMO_MAX_LEGS * (int)sizeof(int), (unsigned)N, w, stream, h->model_dev, q_start_dev,
+            leg_actions_dev, n_ticks_dev, K, targets_dev, obstacles_dev, obstacle_radius, T_cap, h->A, h->n_seg, w.n_pairs, w.lanes,
+            row_floats, rows_out, records_out, poses_out, cell...);
+    });
+}

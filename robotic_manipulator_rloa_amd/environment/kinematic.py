@@ -697,10 +697,13 @@ class JointPaths(_JointPathFields):
                                                      # the largest node count of the call
     n_nodes: Optional[np.ndarray] = None             # [N] int: its node count, 0 where there is no roadmap path
     roadmap_free_edges: Optional[np.ndarray] = None  # [N] int: how many of the roadmap's E edges were free; -1: no roadmap was built
+    roadmap_length: Optional[np.ndarray] = None      # with shortcut (polyline.shortcut_round; nodes, n_nodes, length and the rest are
+                                                     # then the shortened polyline's): [N] the 'roadmap' length before the round; NaN: none
+    shortcut_free_edges: Optional[np.ndarray] = None  # [N] int: how many of the round's all-pairs edges were free; -1: no round ran
 
     def _replace(self, **kw):
         out = super()._replace(**kw)
-        out.nodes, out.n_nodes, out.roadmap_free_edges = self.nodes, self.n_nodes, self.roadmap_free_edges
+        out.__dict__.update(self.__dict__)               # the attributes behind the tuple, those that are set
         return out
 
     def waypoints(self, n: int) -> np.ndarray:
@@ -755,20 +758,23 @@ def path_leg_lengths(vias, q_start, q_goal) -> np.ndarray:
 
 
 def joint_paths_host(twin: KinematicEnvironment, q_start, q_goal, obstacles, candidates: int = 16, resolution: float = 0.02,
-                     margin: float = 0.0, seed: int = 0, chunk: int = PATH_CHUNK, certify: bool = False, roadmap: int = 0) -> JointPaths:
+                     margin: float = 0.0, seed: int = 0, chunk: int = PATH_CHUNK, certify: bool = False, roadmap: int = 0,
+                     shortcut: int = 0) -> JointPaths:
     """plan_joint_paths through the twin alone, under the device's rule and on the values the device is given: start and goal
     poses, vias and obstacles rounded to float32, the poses and the clearances in float64, the lengths in float32. Chunks and
     their S are the device's (path_chunks). certify: certify_joint_path's records and the device's rounds (certify_rounds).
     roadmap = M > 0: the 'blocked' queries get a roadmap of M milestones (roadmap_round: the device's chunks and S, check_joint_edge's
-    records); roadmap edges are checked at their samples only, so not together with certify."""
-    return plan_paths(_TwinPaths(twin), q_start, q_goal, obstacles, candidates, resolution, margin, seed, chunk, certify, roadmap)
+    records); roadmap edges are checked at their samples only, so not together with certify. shortcut = W > 0 (with roadmap): the
+    'roadmap' polylines are searched again over W nodes of their own (polyline.shortcut_round)."""
+    return plan_paths(_TwinPaths(twin), q_start, q_goal, obstacles, candidates, resolution, margin, seed, chunk, certify, roadmap, shortcut)
 
 
 def plan_paths(backend, q_start, q_goal, obstacles, candidates: int = 16, resolution: float = 0.02, margin: float = 0.0, seed: int = 0,
-               budget: int = PATH_CHUNK, certify: bool = False, roadmap: int = 0) -> JointPaths:
+               budget: int = PATH_CHUNK, certify: bool = False, roadmap: int = 0, shortcut: int = 0) -> JointPaths:
     """The one orchestration of collision-checked joint paths, run by the device (chain_tools.JointPathChecker.check) and by the
     twin (joint_paths_host) alike: the refusals, the vias, then either the refinement rounds of certify (certify_rounds) or the
-    one-via chunks (path_chunks) and, with roadmap = M > 0, the roadmap round over the queries they left 'blocked' (roadmap_round).
+    one-via chunks (path_chunks) and, with roadmap = M > 0, the roadmap round over the queries they left 'blocked' (roadmap_round)
+    and, with shortcut = W > 0 behind it, the shortcut round over the 'roadmap' polylines (polyline.shortcut_round; the same evaluator).
     Chunks, their S and the choice among the records are the same for both; what differs is the backend, an object with
       dtype, prefix, roadmap_certify_refusal : the records' dtype and the words of its refusals
       chain                                  : the ChainModel
@@ -781,6 +787,7 @@ def plan_paths(backend, q_start, q_goal, obstacles, candidates: int = 16, resolu
         raise ValueError(f"{backend.prefix}roadmap is a number of milestones from 0 to {ROADMAP_MAX}: got {roadmap!r}")
     if roadmap and certify:
         raise ValueError(backend.prefix + backend.roadmap_certify_refusal)
+    check_shortcut(backend.prefix, shortcut, roadmap)
     C = int(candidates)
     q_start, q_goal, obstacles = backend.prepare(q_start, q_goal, obstacles, C)
     vias = path_vias(backend.chain, q_start, q_goal, C, seed)
@@ -802,7 +809,8 @@ def plan_paths(backend, q_start, q_goal, obstacles, candidates: int = 16, resolu
     def run(queries, nodes, edges, S):
         return backend.edge_records(nodes, edges, obstacles[queries], S, margin)
 
-    return roadmap_round(base, backend.chain, int(roadmap), seed, resolution, budget, run, backend.dtype)
+    return shortcut_round(roadmap_round(base, backend.chain, int(roadmap), seed, resolution, budget, run, backend.dtype), int(shortcut),
+                          resolution, budget, run, backend.dtype)
 
 
 class _TwinPaths:
@@ -1265,9 +1273,9 @@ DEMO_KEPT = ("reached", "frames", "end")
 class DemonstrationPlan(NamedTuple):
     """The time parametrisation of N paths start -> via -> goal (demonstration_plan): all the kernel sees of them."""
     q_start: np.ndarray               # [N][A] float32: the start poses
-    leg_actions: np.ndarray           # [N][2][A] float32: the constant action of each leg
-    n_ticks: np.ndarray               # [N][2] int32: ticks per leg, each >= 1
-    rows: np.ndarray                  # [N] int: T_n = min(n1 + n2, frames)
+    leg_actions: np.ndarray           # [N][2][A] float32: the constant action of each leg ([N][K][A] of demonstration_plan_legs)
+    n_ticks: np.ndarray               # [N][2] int32: ticks per leg, each >= 1 ([N][K]: 0 for the padding behind a query's last leg)
+    rows: np.ndarray                  # [N] int: T_n = min(sum of the ticks, frames)
 
 
 class Demonstrations(NamedTuple):
@@ -1293,29 +1301,15 @@ def demonstration_speed_ok(speed) -> bool:
 
 
 def demonstration_plan(q_start, via, q_goal, speed: float = 1.0, frames: int = 400) -> DemonstrationPlan:
-    """q_start, via, q_goal [N][A] (taken as float32 holds them) -> the plan. Leg k of length L_k = joint_distance32 takes
-    n_k = max(1, ceil(L_k / (speed DT))) ticks (float64) at the constant action (b - a) / (n_k DT), formed in float64 from the float32
-    end poses and rounded to float32; |a|_inf <= speed (a leg whose rounded action would exceed it — L_k rounds the exact max
-    difference, and the action rounds again — gets one tick more). A leg of length 0 is one tick at action 0."""
-    if not demonstration_speed_ok(speed):
-        raise ValueError(f"speed is a share of the unit action, 0 < speed <= 1: got {speed!r}")
-    if isinstance(frames, bool) or not isinstance(frames, (int, np.integer)) or not 1 <= frames <= DEMO_MAX_TICKS:
-        raise ValueError(f"frames is a number of steps from 1 to {DEMO_MAX_TICKS}: got {frames!r}")
+    """q_start, via, q_goal [N][A] (taken as float32 holds them) -> the plan: polyline.demonstration_plan_legs of the three nodes
+    start, via, goal. Leg k of length L_k = joint_distance32 takes n_k = max(1, ceil(L_k / (speed DT))) ticks (float64) at the
+    constant action (b - a) / (n_k DT), formed in float64 from the float32 end poses and rounded to float32; |a|_inf <= speed (a leg
+    whose rounded action would exceed it gets one tick more). A leg of length 0 is one tick at action 0
+    (polyline.leg_ticks_and_action, where the per-leg rule is written once)."""
     a = np.asarray(q_start, np.float32)
     a = a.reshape(-1, a.shape[-1])
     v, b = np.asarray(via, np.float32).reshape(a.shape), np.asarray(q_goal, np.float32).reshape(a.shape)
-    ticks, acts = np.empty((len(a), 2), np.int64), np.empty((len(a), 2, a.shape[1]), np.float32)
-    for k, (lo, hi) in enumerate(((a, v), (v, b))):
-        L = joint_distance32(hi, lo).astype(np.float64)
-        n = np.maximum(1, np.ceil(L / (float(speed) * DT))).astype(np.int64)
-        d = hi.astype(np.float64) - lo.astype(np.float64)
-        act = (d / (n * DT)[:, None]).astype(np.float32)
-        over = np.max(np.abs(act), axis=-1) > np.float32(speed) if len(a) else np.zeros(0, bool)
-        n = n + over
-        ticks[:, k], acts[:, k] = n, np.where(over[:, None], (d / (n * DT)[:, None]).astype(np.float32), act)
-    if len(a) and (ticks.max() > 1 << 20 or not np.all(np.isfinite(acts))):
-        raise ValueError("demonstration_plan: a leg is too long for this speed, or a pose is not finite")
-    return DemonstrationPlan(a.copy(), acts, ticks.astype(np.int32), np.minimum(ticks.sum(axis=1), int(frames)))
+    return demonstration_plan_legs(np.stack([a, v, b], axis=1), np.full(len(a), 3), speed, frames)
 
 
 def demo_row_layout(A: int) -> Tuple[int, int, int, int]:
@@ -1340,12 +1334,6 @@ def demo_observations(twin: KinematicEnvironment, q, qd, target, obstacle) -> np
     out[..., 2 * A + 3:2 * A + 6] = target
     out[..., 2 * A + 6:] = obstacle
     return out
-
-
-def demo_actions(plan: DemonstrationPlan, T: int) -> np.ndarray:
-    """[N][T][A] float64: a_t of every demonstration — leg 1's action for t < n1, leg 2's after (also past n1 + n2: never used)"""
-    first = (np.arange(T)[None, :] < plan.n_ticks[:, :1])[..., None]
-    return np.where(first, plan.leg_actions[:, None, 0, :], plan.leg_actions[:, None, 1, :]).astype(np.float64)
 
 
 def gather_demonstrations(records, has_path, kept_rows_of, keep_contact: bool) -> Demonstrations:
@@ -1509,3 +1497,8 @@ def build_kinematic(manipulator_file, endeffector_index, fixed_joints, involved_
                           workcell_boxes)
     return KinematicEnvironment(model, target_position, obstacle_position, obstacle_radius, target_range, obstacle_range,
                                 scene_margin)
+
+
+# polylines of any number of legs and the shortcut round are stated in environment/polyline.py and belong to the rule as these do
+from .polyline import (DEMO_MAX_LEGS, SHORTCUT_MAX, SHORTCUT_MIN, check_shortcut, demo_actions, demonstration_plan_legs,  # noqa: E402,F401
+                       leg_ticks_and_action, shortcut_nodes, shortcut_round, shortcut_size_ok)

@@ -255,7 +255,7 @@ class ManipulatorFramework:
 
     def reach_targets(self, targets, obstacles=None, initial_joint_positions=None, frames: int = 400, noise_scale: float = 0.0,
                       n_envs: Optional[int] = None, trajectories: bool = True, goal_poses: bool = False, joint_paths: bool = False,
-                      certify: bool = False, roadmap: int = 0):
+                      certify: bool = False, roadmap: int = 0, shortcut: int = 0):
         """Roll the trained policy out to GIVEN targets (kinematic environment only; on the device, thousands at once): query i
         starts at initial_joint_positions[i], with target targets[i] and obstacle obstacles[i], and runs until it reaches the
         target, touches the obstacle, itself or the workcell, or has taken `frames` steps. A query whose start pose is already in contact or at
@@ -281,7 +281,9 @@ class ManipulatorFramework:
         certify=True (with joint_paths): the paths are plan_joint_paths(certify=True)'s, and `path.certified` says which of them
         hold between their samples too.
         roadmap=M (with joint_paths, not with certify): the paths are plan_joint_paths(roadmap=M)'s; a query whose path is a
-        'roadmap' polyline has its planned_ratio over that polyline's length."""
+        'roadmap' polyline has its planned_ratio over that polyline's length.
+        shortcut=W (with roadmap): the paths are plan_joint_paths(roadmap=M, shortcut=W)'s, and planned_ratio divides by the
+        shortened length."""
         self._require_env_and_agent()
         planner = self._kinematic_planner('reach_targets', 'given-scene reset')
         if getattr(self.naf_agent, 'world_size', 1) > 1:
@@ -289,7 +291,7 @@ class ManipulatorFramework:
         if n_envs is not None and not _positive_int(n_envs):
             raise InvalidNAFAgentParameter('Number of environments received is not a positive integer')
         return planner.reach_targets(self.naf_agent, targets, obstacles, initial_joint_positions, frames, noise_scale, n_envs,
-                                     trajectories, goal_poses, joint_paths, certify, roadmap)
+                                     trajectories, goal_poses, joint_paths, certify, roadmap, shortcut)
 
     @functools.cached_property
     def arm_planner(self) -> ArmPlanner:
@@ -307,7 +309,7 @@ class ManipulatorFramework:
 
     def plan_joint_paths(self, targets=None, obstacles=None, initial_joint_positions=None, goal_joint_positions=None,
                          candidates: int = 16, resolution: float = 0.02, clearance_margin: float = 0.0, seed: int = 0,
-                         on_device: Optional[bool] = None, certify: bool = False, roadmap: int = 0):
+                         on_device: Optional[bool] = None, certify: bool = False, roadmap: int = 0, shortcut: int = 0):
         """Collision-checked joint paths from start poses to goal poses (kinematic environment only; needs no agent): per query
         `candidates` joint-space polylines start -> via -> goal — candidate 0 through the midpoint, the straight line, the others
         through vias drawn around it from `seed` (environment/kinematic.py: path_vias) — are SAMPLED at poses at most `resolution`
@@ -344,32 +346,44 @@ class ManipulatorFramework:
                                  the argument. SAMPLED and random: 'blocked' after a roadmap is no proof that no path exists.
                                  Not together with certify: nothing certifies a roadmap's edges between their samples. An arm
                                  with a prismatic joint that has no limits is refused.
+          shortcut             : W in 4 .. 64 (0, the default: none; needs roadmap): one shortcut round behind the roadmaps. Every
+                                 'roadmap' polyline is subdivided to W nodes — its corners, and points handed to its longest
+                                 pieces (environment/polyline.py: shortcut_nodes) — all W (W - 1) / 2 straight edges between
+                                 them are sampled and tested by the same launch, and the shortest path over the free ones
+                                 replaces the polyline where it is strictly shorter: nodes, n_nodes, length, the minima,
+                                 sample_step and samples are then the new edges'. The result's roadmap_length [N] holds the
+                                 lengths before the round (NaN: no roadmap path) and shortcut_free_edges [N] the free edges of
+                                 each round (-1: none ran); both None without shortcut. One round, SAMPLED as the roadmap is.
         Returns environment.kinematic.JointPaths, arrays over the queries: outcome ('straight' | 'via' | 'blocked' | 'start' |
         'goal': the start / goal pose itself is blocked), candidate, via, length, straight_length, min_clearance,
         min_self_clearance, min_cell_clearance, straight_first_blocked, sample_step, samples; waypoints(n) resamples the paths."""
         planner = self._kinematic_planner('plan_joint_paths', 'chain model to solve on')
         return planner.plan_joint_paths(targets, obstacles, initial_joint_positions, goal_joint_positions, candidates, resolution,
-                                        clearance_margin, seed, on_device, certify, roadmap)
+                                        clearance_margin, seed, on_device, certify, roadmap, shortcut)
 
     def demonstrate_joint_paths(self, paths, targets=None, obstacles=None, speed: float = 1.0, frames: int = 400,
-                                keep_contact: bool = False, on_device: Optional[bool] = None):
+                                keep_contact: bool = False, on_device: Optional[bool] = None, polylines: bool = False):
         """Planned joint paths as demonstrations (kinematic environment only; needs no agent): query n drives the arm along
         paths' chosen polyline start -> via -> goal under the environment's own step rule, open loop — leg k in
         n_k = max(1, ceil(L_k / (speed DT))) ticks at one constant action, |a| <= speed — and every tick becomes the replay row
         run_training's environment would have written: an episode it could have produced. The poses follow the step's float32
         recurrence, so the arm reaches via and goal within its accumulated rounding (about 1e-4 rad at 400 ticks).
-          paths        : JointPaths of plan_joint_paths(); queries with candidate < 0 get outcome 'none' — a 'roadmap' query
-                         among them: the launch drives two legs, and its polyline may have more
+          paths        : JointPaths of plan_joint_paths(); queries with candidate < 0 get outcome 'none' — without polylines a
+                         'roadmap' query among them: the two-leg launch drives two legs, and its polyline may have more
           targets      : [N][3], or None: the end effector at each path's goal pose; obstacles: as reach_targets() takes them
           speed        : 0 < speed <= 1, the share of the unit action — the policy's mean action is a tanh
           frames       : the episode budget, 1 .. 1024: a longer path is cut there (outcome 'frames')
           keep_contact : demonstrations that touch the obstacle, the arm or the workcell are dropped whole (the path was checked
                          at its samples only) unless this is set
           on_device    : None: the device when there is one; False: the float64 host twin, `rows` a numpy array (slow)
+          polylines    : True: every query is planned as a polyline of any number of legs (environment/polyline.py:
+                         demonstration_plan_legs; on the device naf_chain_demo_rows_legs) — a one-via query as its three nodes
+                         start, via, goal, a 'roadmap' query as its nodes[:n_nodes], each leg under the per-leg rule above; only a
+                         query with neither stands still and is 'none'. planned_ticks is then the sum over all legs.
         Returns environment.kinematic.Demonstrations: outcome ('reached' | 'frames' | 'end' | 'obstacle' | 'self' | 'workcell' |
         'none'), frames, final_distance, the three minima, planned_ticks, kept, rows [rows_total][row floats], rows_total."""
         planner = self._kinematic_planner('demonstrate_joint_paths', 'chain model to drive')
-        return planner.demonstrate_joint_paths(paths, targets, obstacles, speed, frames, keep_contact, on_device)
+        return planner.demonstrate_joint_paths(paths, targets, obstacles, speed, frames, keep_contact, on_device, polylines)
 
     def _check_demonstrations(self, demos, E) -> None:
         if not isinstance(demos, Demonstrations):
