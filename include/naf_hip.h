@@ -341,6 +341,14 @@ int naf_bb_layer1_adam(const float* x, int64_t x_net_stride, int ldx, int K, con
                        float* xhat_out /* nullable: [B][ldo], xhat of net 0 — for naf_gemm_l1bwd_t.xhat */, int B, int H, int nets,
                        float momentum, float eps, const naf_adam_args_t* adam /* nullable (HOST pointer, copied into the launch) */,
                        void* stream);
+/* The same launch with the width of a workgroup's column tile stated: cols = 0 (the library's choice: what naf_bb_layer1_adam
+ * runs), 64, 32 or 16; any other value is NAF_ERR_ARG. 32 and 16 exist for adam != NULL and K <= 24 (NAF_ERR_ARG otherwise) and deal
+ * the same rows, statistics and z elements to 2 x / 4 x the workgroups: every output is the same bits at every width. */
+int naf_bb_layer1_adam_tile(const float* x, int64_t x_net_stride, int ldx, int K, const float* W, const float* bias,
+                            const float* gamma, const float* beta, int64_t param_net_stride, const float* mom, float* running_mean,
+                            float* running_var, int64_t stat_net_stride, float* out, int64_t out_net_stride, int ldo,
+                            float* save_mean, float* save_invstd, float* wc_out, float* xhat_out /* nullable */, int B, int H,
+                            int nets, float momentum, float eps, int cols, const naf_adam_args_t* adam /* nullable */, void* stream);
 /* z[net] = a[net] W[net]^T + bias[net] (torch Linear, K = 256, N % 64 == 0) on f32 MFMA, 64 x 32 tiles (64 x 16 up to B = 512),
  * with the column statistics partials of every 64-row block written by the epilogue: replaces `self.hidden_layer(x)`
  * (naf_neural_network.py:78) and the statistics pass of bn2 for both networks. */

@@ -213,6 +213,8 @@ _PROTOS = {
     "naf_bb_moments": [_vp, _i64, _i64, _i, _i, _vp, _i, _i, _i, _vp],
     "naf_bb_layer1_adam": [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _i, _i,
                            _f, _f, _vp, _vp],
+    "naf_bb_layer1_adam_tile": [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _i,
+                                _i, _f, _f, _i, _vp, _vp],
     "naf_bb_linear_stats_adam": [_vp, _i64, _i, _vp, _vp, _i64, _vp, _i64, _i, _vp, _i, _i, _i, _i, _vp, _vp],
     "naf_bb_layer2_head_rows": [_i],
     "naf_bb_layer2_head_exchange_floats": [_i, _i],

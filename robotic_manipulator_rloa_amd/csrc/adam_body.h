@@ -226,6 +226,54 @@ __device__ __forceinline__ static naf_f32x4 adam_fly_apply4(const AdamArgs& A, c
     return out;
 }
 
+// The same for N = 4 | 2 | 1 consecutive parameters (o a multiple of N), in lanes 0 .. N-1 of the float4 (N = 4: the functions
+// above as they are). Below four, `skip` — uniform over the launch — is tested ONCE, so that a thread's elements are one basic
+// block and their dependent chains interleave; adam_one is the same code, so the value is the same bits.
+template <int N>
+__device__ __forceinline__ static naf_f32x4 adam_ld_n(const float* p) {
+    naf_f32x4 r = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (N == 4) {
+        r = *(const naf_f32x4*)p;
+    } else if constexpr (N == 2) {
+        const naf_f32x2 t = *(const naf_f32x2*)p;
+        r[0] = t[0];
+        r[1] = t[1];
+    } else {
+        r[0] = *p;
+    }
+    return r;
+}
+template <int N>
+__device__ __forceinline__ static AdamFly4 adam_fly_load_n(const AdamArgs& A, int64_t o, bool is_target) {
+    if constexpr (N == 4) {
+        return adam_fly_load4(A, o, is_target);
+    } else {
+        AdamFly4 p;
+        p.g = adam_ld_n<N>(A.g + o);
+        p.m = adam_ld_n<N>(A.m + o);
+        p.v = adam_ld_n<N>(A.v + o);
+        p.thm = adam_ld_n<N>(A.theta + (is_target ? o : 0));
+        return p;
+    }
+}
+template <int N>
+__device__ __forceinline__ static naf_f32x4 adam_fly_apply_n(const AdamArgs& A, const AdamScalars& sc, const AdamFly4& p, naf_f32x4 cur,
+                                                             bool is_target) {
+    if constexpr (N == 4) {
+        return adam_fly_apply4(A, sc, p, cur, is_target);
+    } else {
+        if (sc.skip) return cur;
+        naf_f32x4 out = cur;
+#pragma unroll
+        for (int q = 0; q < N; ++q) {
+            float th = is_target ? p.thm[q] : cur[q], m = p.m[q], v = p.v[q], tg = cur[q];
+            adam_one(th, p.g[q], m, v, tg, is_target, sc, A.beta1, A.beta2, A.eps, A.tau, A.one_minus_tau);
+            out[q] = is_target ? tg : th;
+        }
+        return out;
+    }
+}
+
 __host__ static inline bool adam_args_from(const naf_adam_args_t& s, AdamArgs& a) {
     if (!s.theta || !s.grad || !s.m || !s.v || !s.partials || !s.step_dev || s.n_partials <= 0) return false;
     if ((((uintptr_t)s.theta | (uintptr_t)s.grad | (uintptr_t)s.m | (uintptr_t)s.v | (uintptr_t)s.theta_target) & 15) != 0) return false;

@@ -516,6 +516,19 @@ __global__ __launch_bounds__(ADAM ? 2 * BB_THREADS : BB_THREADS) void bb_layer1_
     __shared__ BbL1Shared<K4, ADAM> SM;
     bb_layer1_impl<K4, ADAM, FULL>(SM, (int)blockIdx.x, x, x_net_stride, ldx, K, W, bias, gamma, beta, param_net_stride, mom, running_mean, running_var, stat_net_stride, out, out_net_stride, ldo, save_mean, save_invstd, wc_out, B, H, momentum, eps, n_main, ad, l1_4, n4, n_adam, xcd_rows, xhat_out);
 }
+// the ADAM form on column tiles of COLS = 32 | 16 (csrc/layer1_body.h): H / COLS workgroups per row block and network. A kernel of
+// its own name, so that the 64-column one above is the very symbol it was.
+template <int K4, bool FULL, int COLS>
+__global__ __launch_bounds__(2 * BB_THREADS) void bb_layer1_tile_kernel(
+    const float* __restrict__ x, int64_t x_net_stride, int ldx, int K, const float* __restrict__ W,
+    const float* __restrict__ bias, const float* __restrict__ gamma, const float* __restrict__ beta,
+    int64_t param_net_stride, const float* __restrict__ mom, float* __restrict__ running_mean,
+    float* __restrict__ running_var, int64_t stat_net_stride, float* __restrict__ out, int64_t out_net_stride, int ldo,
+    float* __restrict__ save_mean, float* __restrict__ save_invstd, float* __restrict__ wc_out, int B, int H, float momentum,
+    float eps, int n_main, const AdamArgs ad, int64_t l1_4, int64_t n4, int n_adam, int xcd_rows, float* __restrict__ xhat_out) {
+    __shared__ BbL1Shared<K4, true, COLS> SM;
+    bb_layer1_impl<K4, true, FULL, BbL1NoHook, COLS>(SM, (int)blockIdx.x, x, x_net_stride, ldx, K, W, bias, gamma, beta, param_net_stride, mom, running_mean, running_var, stat_net_stride, out, out_net_stride, ldo, save_mean, save_invstd, wc_out, B, H, momentum, eps, n_main, ad, l1_4, n4, n_adam, xcd_rows, xhat_out);
+}
 
 // ------------------------------------------------------------------------------------------------------------
 // GEMM 2 (and any Linear with K <= 256): Z[net] = A[net] W[net]^T + bias on v_mfma_f32_16x16x4_f32, 64 x 32 output tile
@@ -1276,12 +1289,34 @@ static bool bb_adam_setup(const naf_adam_args_t* adam, AdamArgs& ad, int64_t& l1
 }
 static int bb_adam_blocks(int64_t lo4, int64_t hi4, int threads) { return (int)((hi4 - lo4 + threads - 1) / threads); }
 
-extern "C" int naf_bb_layer1_adam(const float* x, int64_t x_net_stride, int ldx, int K, const float* W, const float* bias,
-                                  const float* gamma, const float* beta, int64_t param_net_stride, const float* mom,
-                                  float* running_mean, float* running_var, int64_t stat_net_stride, float* out,
-                                  int64_t out_net_stride, int ldo, float* save_mean, float* save_invstd, float* wc_out,
-                                  float* xhat_out, int B, int H, int nets, float momentum, float eps, const naf_adam_args_t* adam,
-                                  void* stream) {
+// The column-tile width of launch 1 where the caller leaves it to the library (cols = 0). Narrow tiles exist for the ADAM form at
+// K <= 24 (csrc/layer1_body.h) and were measured at H = 256; everything else runs 64.
+// bench.py, updates/s, the three widths interleaved twice on one box (1500 vector steps; the two runs of a width within 0.5 %):
+//     B      kuka   64       32       16      |  panda  64       32       16
+//     64          37.00k   38.07k   38.63k    |       35.56k   36.49k   37.09k
+//    128          36.41k   37.28k   38.07k    |       34.76k   35.63k     -
+//    256          35.39k   36.57k   37.15k    |       33.88k   34.75k   35.46k
+//    512          31.46k   32.30k   31.98k    |       30.13k   30.80k     -
+//   1024          28.12k   28.16k     -       |          -        -       -
+//   2048             -        -       -       |       21.33k   20.69k     -
+// 16 wins while the launch stays one workgroup per CU with the riding step's 37 (2 x 4 x 16 + 37 = 165 of 256 at B = 256); at
+// B = 512 that is 32 (2 x 8 x 8 + 37), 16 would be a second round; from 1024 on every narrowing is a second round: nothing, then a loss.
+static int bb_l1_cols(int B, int H, int k4d, bool adam) {
+    if (!adam || k4d != 6 || H != 256) return BB_COLS;
+#ifdef NAF_L1_COLS                       // (A/B builds: NAF_BUILD_DEFINES=-DNAF_L1_COLS=32)
+    return NAF_L1_COLS;
+#else
+    return B <= 256 ? 16 : B <= 512 ? 32 : BB_COLS;
+#endif
+}
+
+extern "C" int naf_bb_layer1_adam_tile(const float* x, int64_t x_net_stride, int ldx, int K, const float* W, const float* bias,
+                                       const float* gamma, const float* beta, int64_t param_net_stride, const float* mom,
+                                       float* running_mean, float* running_var, int64_t stat_net_stride, float* out,
+                                       int64_t out_net_stride, int ldo, float* save_mean, float* save_invstd, float* wc_out,
+                                       float* xhat_out, int B, int H, int nets, float momentum, float eps, int cols,
+                                       const naf_adam_args_t* adam, void* stream) {
+    if (cols != 0 && cols != 64 && cols != 32 && cols != 16) return NAF_ERR_ARG;
     if (xhat_out && ((uintptr_t)xhat_out & 15)) return NAF_ERR_ARG;
     if (!x || !W || !bias || !mom || !gamma || !beta || !running_mean || !running_var || !out || !save_mean || !save_invstd ||
         !bb_shape_ok(B, H) || nets <= 0 || K <= 0 || K > 4 * BB_MAX_K4 || ldo < H || (ldo & 3))
@@ -1303,10 +1338,24 @@ extern "C" int naf_bb_layer1_adam(const float* x, int64_t x_net_stride, int ldx,
             return NAF_ERR_ARG;
     }
     hipStream_t st = (hipStream_t)stream;
-    const int n_main = bb_blocks(B) * (H / BB_COLS) * nets;
+    if (cols == 0) cols = bb_l1_cols(B, H, k4d, adam != nullptr);
+    if (cols != BB_COLS && (!adam || k4d != 6)) return NAF_ERR_ARG;      // (narrow tiles: the ADAM form, K <= 24)
+    const int n_main = bb_blocks(B) * (H / cols) * nets;
     const int n_adam = adam ? bb_adam_blocks(l1_4, n4, 2 * BB_THREADS) : 0;
     const int grid = n_main + n_adam;
     const int xcd_rows = 1;      // rows by eighths (bb_place_rows)
+#define BB_L1T_(FL, CW)                                                                                                        \
+    bb_layer1_tile_kernel<6, FL, CW><<<grid, 2 * BB_THREADS, 0, st>>>(x, x_net_stride, ldx, K, W, bias, gamma, beta, param_net_stride, mom, \
+                                                           running_mean, running_var, stat_net_stride, out, out_net_stride, ldo, \
+                                                           save_mean, save_invstd, wc_out, B, H, momentum, eps, n_main, ad, l1_4, n4, n_adam, xcd_rows, xhat_out)
+    if (cols != BB_COLS) {
+        const bool full = B % BB_ROWS == 0;
+        if (cols == 32) { if (full) BB_L1T_(true, 32); else BB_L1T_(false, 32); }
+        else { if (full) BB_L1T_(true, 16); else BB_L1T_(false, 16); }
+        NAF_CHECK_LAUNCH();
+        return NAF_OK;
+    }
+#undef BB_L1T_
 #define BB_L1_(K4V, AD, FL)                                                                                                    \
     bb_layer1_kernel<K4V, AD, FL><<<grid, (AD) ? 2 * BB_THREADS : BB_THREADS, 0, st>>>(x, x_net_stride, ldx, K, W, bias, gamma, beta, param_net_stride, mom, \
                                                            running_mean, running_var, stat_net_stride, out, out_net_stride, ldo, \
@@ -1322,6 +1371,16 @@ extern "C" int naf_bb_layer1_adam(const float* x, int64_t x_net_stride, int ldx,
 #undef BB_L1_
     NAF_CHECK_LAUNCH();
     return NAF_OK;
+}
+extern "C" int naf_bb_layer1_adam(const float* x, int64_t x_net_stride, int ldx, int K, const float* W, const float* bias,
+                                  const float* gamma, const float* beta, int64_t param_net_stride, const float* mom,
+                                  float* running_mean, float* running_var, int64_t stat_net_stride, float* out,
+                                  int64_t out_net_stride, int ldo, float* save_mean, float* save_invstd, float* wc_out,
+                                  float* xhat_out, int B, int H, int nets, float momentum, float eps, const naf_adam_args_t* adam,
+                                  void* stream) {
+    return naf_bb_layer1_adam_tile(x, x_net_stride, ldx, K, W, bias, gamma, beta, param_net_stride, mom, running_mean, running_var,
+                                   stat_net_stride, out, out_net_stride, ldo, save_mean, save_invstd, wc_out, xhat_out, B, H, nets,
+                                   momentum, eps, 0, adam, stream);
 }
 extern "C" int naf_bb_linear_stats_adam(const float* a, int64_t a_net_stride, int lda, const float* W, const float* bias,
                                         int64_t param_net_stride, float* z, int64_t z_net_stride, int ldz, float* partials, int B,

@@ -66,6 +66,30 @@ __device__ static inline void bb_l1_tile(const float (*sXt)[BB_ROWS + 4], const 
             for (int j = 0; j < 4; ++j) z[i][j] = __builtin_fmaf(av[i], wv[j], z[i][j]);
     }
 }
+// the same on a tile of 64 rows x COLS columns, COLS = 32 | 16: a thread owns R = COLS / 16 rows (R ty .. +R-1) and four columns, so
+// that the 256 threads still cover the tile; every element is the same chain of FMAs
+template <int K4, int COLS>
+__device__ static inline void bb_l1_tile_n(const float (*sXt)[BB_ROWS + 4], const float (*sWt)[COLS + 4], const float4 bias4,
+                                           int ty, int tx, float (&z)[COLS / 16][4]) {
+    constexpr int R = COLS / 16;
+    const float bb[4] = {bias4.x, bias4.y, bias4.z, bias4.w};
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) z[i][j] = bb[j];
+#pragma unroll
+    for (int k = 0; k < 4 * K4; ++k) {
+        float av[R];
+#pragma unroll
+        for (int i = 0; i < R; ++i) av[i] = sXt[k][R * ty + i];
+        const float4 w = *(const float4*)&sWt[k][4 * tx];
+        const float wv[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int i = 0; i < R; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) z[i][j] = __builtin_fmaf(av[i], wv[j], z[i][j]);
+    }
+}
 
 // layer 1 forward for `nets` networks: statistics from the moments, z tile, normalise, ReLU -> out
 // Prologue: every global operand — the row tile, the 64 columns' weights (ONE contiguous run of 64 K floats, read as float4
@@ -81,15 +105,20 @@ __device__ static inline void bb_l1_tile(const float (*sXt)[BB_ROWS + 4], const 
 // resource bounds of the partial last block fold away at compile time (with them at run time an update at B = 256 was 0.3 us slower)
 // (the kernel's body as a device function: bb_layer1_kernel below is it on a launch of its own; adam_act_kernel of csrc/step_path.hip
 //  runs it — ADAM = false — in extra workgroups of the per-timestep path's first launch, behind that launch's own optimizer step)
-template <int K4, bool ADAM>
+// COLS: the feature columns of a workgroup's tile, 64 | 32 | 16 (ADAM only below 64). A narrower tile is the same rows, statistics
+// and z elements dealt to 2 x / 4 x the workgroups: what a workgroup has on its critical path in front of the first FMA — the
+// riding step evaluated for COLS (K + 3) parameters, the scatter of the weights to LDS — and behind the last — COLS / 16 float4
+// stores per thread — shrinks with it, and the launch spreads over that many more CUs. Per column nothing changes: the same wave
+// lanes finish a column's statistics from the same MFMA accumulators, and z is the same chain of FMAs.
+template <int K4, bool ADAM, int COLS = BB_COLS>
 struct BbL1Shared {
     static constexpr int KP = 4 * K4, REC = KP + KP * KP;
     __attribute__((aligned(16))) float sXt[KP][BB_ROWS + 4];
-    __attribute__((aligned(16))) float sWt[KP][BB_COLS + 4];
+    __attribute__((aligned(16))) float sWt[KP][COLS + 4];
     __attribute__((aligned(16))) float sMom[REC];
-    float sStat[4][BB_COLS];
+    float sStat[4][COLS];
     AdamScalars shA[ADAM ? 1 : 0];                                        // (the riding optimizer step's scalars and the parameters as
-    __attribute__((aligned(16))) float sPar[ADAM ? 3 : 0][BB_COLS];       //  it leaves them: ADAM only)
+    __attribute__((aligned(16))) float sPar[ADAM ? 3 : 0][COLS];          //  it leaves them: ADAM only)
 };
 // Hooks — nothing in the launches of csrc/big_batch.hip; the riders of adam_act_kernel (csrc/step_path.hip) use both:
 //   parameters_loaded()     one thread, once every parameter (and, ADAM, its gradient and optimizer state) this workgroup reads has
@@ -100,8 +129,8 @@ struct BbL1NoHook {
     __device__ __forceinline__ void parameters_loaded() const {}
     __device__ __forceinline__ void before_running_stats() const {}
 };
-template <int K4, bool ADAM, bool FULL, typename Hook = BbL1NoHook>
-__device__ __forceinline__ static void bb_layer1_impl(BbL1Shared<K4, ADAM>& SM, const int block,
+template <int K4, bool ADAM, bool FULL, typename Hook = BbL1NoHook, int COLS = BB_COLS>
+__device__ __forceinline__ static void bb_layer1_impl(BbL1Shared<K4, ADAM, COLS>& SM, const int block,
     const float* __restrict__ x, int64_t x_net_stride, int ldx, int K, const float* __restrict__ W,
     const float* __restrict__ bias, const float* __restrict__ gamma, const float* __restrict__ beta,
     int64_t param_net_stride, const float* __restrict__ mom, float* __restrict__ running_mean,
@@ -112,13 +141,18 @@ __device__ __forceinline__ static void bb_layer1_impl(BbL1Shared<K4, ADAM>& SM, 
     constexpr int KP = 4 * K4, REC = KP + KP * KP;
     constexpr int XN = (BB_ROWS * K4 + BB_THREADS - 1) / BB_THREADS;           // float4 of the row tile per thread: 2
     constexpr int MN = (REC / 4 + BB_THREADS - 1) / BB_THREADS;                // of the moments record: 1 or 2
+    // a narrow tile: EPT = COLS / 16 consecutive parameters per thread in the evaluation (the same 16 K + 48 threads take the
+    // weights and [b | gamma | beta] as at 64), EPT rows x 4 columns per thread in the z tile, one wave per 16 columns in the
+    // statistics (waves COLS / 16 .. 3 have none)
+    constexpr int EPT = COLS / 16, TXN = COLS / 4;
+    static_assert(COLS == 64 || ((COLS == 32 || COLS == 16) && ADAM && K4 <= 6), "narrow tiles: ADAM, K <= 24 (16 K + 48 threads)");
     float (&sXt)[KP][BB_ROWS + 4] = SM.sXt;
-    float (&sWt)[KP][BB_COLS + 4] = SM.sWt;
+    float (&sWt)[KP][COLS + 4] = SM.sWt;
     float (&sMom)[REC] = SM.sMom;
-    float (&sStat)[4][BB_COLS] = SM.sStat;  // mean, invstd, gamma, beta of this workgroup's columns
+    float (&sStat)[4][COLS] = SM.sStat;     // mean, invstd, gamma, beta of this workgroup's columns
     AdamScalars& shA = SM.shA[0];           // (ADAM only: zero-length arrays otherwise, never touched)
-    float (*sPar)[BB_COLS] = SM.sPar;       // ADAM: b, gamma, beta of the columns as the step leaves them
-    const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
+    float (*sPar)[COLS] = SM.sPar;          // ADAM: b, gamma, beta of the columns as the step leaves them
+    const int tid = threadIdx.x, ty = tid >> (TXN == 16 ? 4 : TXN == 8 ? 3 : 2), tx = tid & (TXN - 1);
     // every kernel argument, requested NOW in one batch of scalar loads: fetched where they are first used they came in five
     // dependent batches threaded through the prologue (~0.25 us each against a scalar cache that is cold when a launch starts), each
     // holding back the vector loads behind it
@@ -140,10 +174,10 @@ __device__ __forceinline__ static void bb_layer1_impl(BbL1Shared<K4, ADAM>& SM, 
         BB_L1_TL(12, ra == 0, ra == n_adam - 1);
         return;
     }
-    const int gx = (B + BB_ROWS - 1) / BB_ROWS, gy = H / BB_COLS;
+    const int gx = (B + BB_ROWS - 1) / BB_ROWS, gy = H / COLS;
     int rb = widx % gx, ct_ = (widx / gx) % gy, net = widx / (gx * gy);
     if (xcd_rows && n_main == 2 * gx * gy) bb_place_rows(widx, n_ride, gx, gy, net, rb, ct_);
-    const int col0 = ct_ * BB_COLS;
+    const int col0 = ct_ * COLS;
     const int64_t po = net * param_net_stride;
 #define L1_TL(slot) BB_L1_TL(slot, widx == 0, widx == n_main - 1)
     L1_TL(0);
@@ -156,11 +190,12 @@ __device__ __forceinline__ static void bb_layer1_impl(BbL1Shared<K4, ADAM>& SM, 
     // instructions per element — a division and a square root, correctly rounded), then waves 4 .. 7 are done.
     const bool mainw = !ADAM || tid < BB_THREADS;
     f32x4 xv[XN], wv[2], mv[MN];
-    const int wn4 = (BB_COLS * K) >> 2;                                          // 16 K float4 (<= 512)
+    const int wn4 = (COLS * K) >> (EPT == 4 ? 2 : EPT - 1);                      // 16 K float4 (<= 512), or pairs, or floats
     const f32x4* wsrc = (const f32x4*)(W + po + (int64_t)col0 * K);
     // the statistics of column cl are finished by lane (r < 4, g) of wave cl / 16 (see below): its constants
     const int lane = tid & 63, wave = (tid >> 6) & 3, mr = lane & 15, mg = lane >> 4;
-    const int cl = 16 * wave + 4 * mg + (mr & 3);
+    const bool statw = COLS == BB_COLS || wave < COLS / 16;                      // (a narrow tile: this wave has columns)
+    const int cl = statw ? 16 * wave + 4 * mg + (mr & 3) : 0;
     float4 b4v = make_float4(0.f, 0.f, 0.f, 0.f);
     float bias_cv = 0.f, gmv = 0.f, btv = 0.f;
     float rm_ = 0.f, rv_ = 0.f;
@@ -179,7 +214,8 @@ __device__ __forceinline__ static void bb_layer1_impl(BbL1Shared<K4, ADAM>& SM, 
             wv[i] = wsrc[e < wn4 ? e : 0];
         }
     } else {
-        wv[0] = wsrc[tid < wn4 ? tid : 0];
+        if constexpr (EPT == 4) wv[0] = wsrc[tid < wn4 ? tid : 0];
+        else wv[0] = adam_ld_n<EPT>((const float*)wsrc + EPT * (tid < wn4 ? tid : 0));
     }
     if (mainw) {
 #pragma unroll
@@ -193,7 +229,7 @@ __device__ __forceinline__ static void bb_layer1_impl(BbL1Shared<K4, ADAM>& SM, 
             gmv = gamma[po + col0 + cl];
             btv = beta[po + col0 + cl];
         }
-        if (rb == 0 && mr < 4) {
+        if (rb == 0 && mr < 4 && statw) {
             rm_ = running_mean[net * stat_net_stride + col0 + cl];
             rv_ = running_var[net * stat_net_stride + col0 + cl];
         }
@@ -201,26 +237,27 @@ __device__ __forceinline__ static void bb_layer1_impl(BbL1Shared<K4, ADAM>& SM, 
     // deferred step: everything it needs for the parameters this workgroup reads, in flight with the operands above. Every
     // parameter is evaluated ONCE per workgroup and handed on through LDS (evaluated where they are used — the per-column
     // parameters 16 x redundantly — a thread ran the formula 15 times: 2.6 us in front of the first barrier): thread t takes
-    // float4 t of the weight tile (t < 16 K), the last 48 threads one float4 each of [b | gamma | beta].
+    // float4 t of the weight tile (t < 16 K), the last 48 threads one float4 each of [b | gamma | beta]. (A narrow tile: the same
+    // threads, EPT = 2 | 1 consecutive floats each instead of the float4.)
     const bool tgt = net != 0;
-    constexpr int NPAR4 = 3 * BB_COLS / 4;
+    constexpr int NPAR4 = 3 * COLS / EPT;
     const int pj = tid - (2 * BB_THREADS - NPAR4);            // ADAM: >= 0 for the threads that take a parameter float4
     AdamFly4 fw, fp;
     f32x4 pcur;
     AdamPrefetch apf;
     int64_t ofw = 0, ofp = 0;                                 // flat offsets of this thread's two float4 (main network)
     if (ADAM) {
-        ofw = (W - ad.theta) + (int64_t)col0 * K + 4 * (tid < wn4 ? tid : 0);
-        fw = adam_fly_load4(ad, ofw, tgt);
-        const int jc = pj >= 0 ? pj : 0, c4 = 4 * (jc & (BB_COLS / 4 - 1));
-        const float* pb = jc < BB_COLS / 4 ? bias : jc < BB_COLS / 2 ? gamma : beta;
-        pcur = *(const f32x4*)(pb + po + col0 + c4);
+        ofw = (W - ad.theta) + (int64_t)col0 * K + EPT * (tid < wn4 ? tid : 0);
+        fw = adam_fly_load_n<EPT>(ad, ofw, tgt);
+        const int jc = pj >= 0 ? pj : 0, c4 = EPT * (jc & (COLS / EPT - 1));
+        const float* pb = jc < COLS / EPT ? bias : jc < 2 * COLS / EPT ? gamma : beta;
+        pcur = adam_ld_n<EPT>(pb + po + col0 + c4);
         ofp = (pb - ad.theta) + col0 + c4;
-        fp = adam_fly_load4(ad, ofp, tgt);
+        fp = adam_fly_load_n<EPT>(ad, ofp, tgt);
         apf = adam_prefetch(ad, tid);
     }
     // rows k >= K of the weight tile meet the padding columns of the row tile: zero
-    for (int e = tid; e < (KP - K) * BB_COLS; e += BB_THREADS) sWt[K + e / BB_COLS][e % BB_COLS] = 0.f;
+    for (int e = tid; e < (KP - K) * COLS; e += BB_THREADS) sWt[K + e / COLS][e % COLS] = 0.f;
     if (mainw) {
 #pragma unroll
         for (int i = 0; i < XN; ++i) {
@@ -246,8 +283,16 @@ __device__ __forceinline__ static void bb_layer1_impl(BbL1Shared<K4, ADAM>& SM, 
         __syncthreads();
         L1_TL(9);
         const AdamScalars sc = shA;
-        if (tid < wn4) wv[0] = adam_fly_apply4(ad, sc, fw, wv[0], tgt);
-        if (pj >= 0) *(f32x4*)(&sPar[0][0] + 4 * pj) = adam_fly_apply4(ad, sc, fp, pcur, tgt);
+        if (tid < wn4) wv[0] = adam_fly_apply_n<EPT>(ad, sc, fw, wv[0], tgt);
+        if (pj >= 0) {
+            const f32x4 pn = adam_fly_apply_n<EPT>(ad, sc, fp, pcur, tgt);
+            if constexpr (EPT == 4) {
+                *(f32x4*)(&sPar[0][0] + 4 * pj) = pn;
+            } else {
+#pragma unroll
+                for (int q = 0; q < EPT; ++q) (&sPar[0][0])[EPT * pj + q] = pn[q];
+            }
+        }
         L1_TL(10);
     }
     {
@@ -257,8 +302,8 @@ __device__ __forceinline__ static void bb_layer1_impl(BbL1Shared<K4, ADAM>& SM, 
             const int e = tid + BB_THREADS * i;
             if (e < wn4) {
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const unsigned idx = 4u * (unsigned)e + (unsigned)q;
+                for (int q = 0; q < EPT; ++q) {
+                    const unsigned idx = (unsigned)EPT * (unsigned)e + (unsigned)q;
                     const unsigned c = (idx * kinv) >> 16;
                     sWt[idx - c * (unsigned)K][c] = wv[i][q];
                 }
@@ -268,10 +313,10 @@ __device__ __forceinline__ static void bb_layer1_impl(BbL1Shared<K4, ADAM>& SM, 
     __syncthreads();
     if (tid == 0) hook.parameters_loaded();
     float* oz = out + net * out_net_stride;
-    // normalise + ReLU + store of a thread's 4 x 4 piece of the tile (statistics in sStat)
-    auto tile_out = [&](const float (&zt)[4][4], int ty_, int tx_) {
+    // normalise + ReLU + store of a thread's 4 x 4 piece of the tile (statistics in sStat) (a narrow tile: EPT x 4)
+    auto tile_out = [&](const float (&zt)[EPT][4], int ty_, int tx_) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < EPT; ++i) {
             float4 y;
             float* yp = (float*)&y;
             f32x4 xh4;
@@ -283,21 +328,22 @@ __device__ __forceinline__ static void bb_layer1_impl(BbL1Shared<K4, ADAM>& SM, 
                 xh4[j] = xh;
                 yp[j] = t > 0.f ? t : 0.f;
             }
-            const unsigned obytes = FULL ? 0x7fffffffu : ((unsigned)(valid - 1) * (unsigned)ldo + BB_COLS) * 4u;
-            naf_buf_st_f4(naf_buf(oz + (int64_t)(rb * BB_ROWS) * ldo + col0, obytes), 4u * (unsigned)((4 * ty_ + i) * ldo + 4 * tx_), 0,
+            const unsigned obytes = FULL ? 0x7fffffffu : ((unsigned)(valid - 1) * (unsigned)ldo + COLS) * 4u;
+            naf_buf_st_f4(naf_buf(oz + (int64_t)(rb * BB_ROWS) * ldo + col0, obytes), 4u * (unsigned)((EPT * ty_ + i) * ldo + 4 * tx_), 0,
                           (f32x4){y.x, y.y, y.z, y.w}, B >= NAF_WT_MIN_B);
             // the main network's xhat too where the backward wants it ready-made (naf_gemm_l1bwd_t.xhat: small batches)
             if (xhat_out && net == 0)
-                naf_buf_st_f4(naf_buf(xhat_out + (int64_t)(rb * BB_ROWS) * ldo + col0, obytes), 4u * (unsigned)((4 * ty_ + i) * ldo + 4 * tx_), 0, xh4,
+                naf_buf_st_f4(naf_buf(xhat_out + (int64_t)(rb * BB_ROWS) * ldo + col0, obytes), 4u * (unsigned)((EPT * ty_ + i) * ldo + 4 * tx_), 0, xh4,
                               B >= NAF_WT_MIN_B);
         }
     };
     if (ADAM && tid >= BB_THREADS) {
         // waves 4 .. 7: the z tile, WHILE waves 0 .. 3 derive the statistics — neither needs the other, only the normalisation
         // needs both (in one sequence in the same four waves: 1.24 + 0.68 us of this kernel's 5.0; side by side: 1.24)
-        const int ty2 = ty - BB_THREADS / 16;
-        float z[4][4];
-        bb_l1_tile<K4>(sXt, sWt, *(const float4*)&sPar[0][4 * tx], ty2, tx, z);
+        const int ty2 = ty - BB_THREADS / TXN;
+        float z[EPT][4];
+        if constexpr (COLS == BB_COLS) bb_l1_tile<K4>(sXt, sWt, *(const float4*)&sPar[0][4 * tx], ty2, tx, z);
+        else bb_l1_tile_n<K4, COLS>(sXt, sWt, *(const float4*)&sPar[0][4 * tx], ty2, tx, z);
         __syncthreads();                         // the statistics of waves 0 .. 3 are in sStat
         BB_L1_TL_T(3, widx == 0, widx == n_main - 1, BB_THREADS);
         tile_out(z, ty2, tx);
@@ -311,7 +357,7 @@ __device__ __forceinline__ static void bb_layer1_impl(BbL1Shared<K4, ADAM>& SM, 
         btv = sPar[2][cl];
     }
     L1_TL(1);
-    {
+    if (statw) {
         // statistics of the 64 columns from the moments on MFMA: U = W C (64 x KP; wave w owns columns 16 w .. +15, both
         // 16-wide halves of the KP dimension), then var_c B = U[c] . w_c and (mean_c - b_c) B = w_c . Sx as 16-lane reductions
         // of the accumulator rows. A[m = column][k] = sWt[k][column]; B[k][n] = C[k][n] = C[n][k] (symmetric): one 16-byte
@@ -386,12 +432,14 @@ __device__ __forceinline__ static void bb_layer1_impl(BbL1Shared<K4, ADAM>& SM, 
         __syncthreads();
         return;
     }
-    float z[4][4];
-    bb_l1_tile<K4>(sXt, sWt, b4v, ty, tx, z);
-    __syncthreads();
-    L1_TL(3);
-    tile_out(z, ty, tx);
-    L1_TL(4);
+    if constexpr (!ADAM) {
+        float z[4][4];
+        bb_l1_tile<K4>(sXt, sWt, b4v, ty, tx, z);
+        __syncthreads();
+        L1_TL(3);
+        tile_out(z, ty, tx);
+        L1_TL(4);
+    }
 #undef L1_TL
 }
 
