@@ -64,6 +64,15 @@ launches are the box instantiations, which test the floor and the spheres too.
       polylines before and after the round: length over the straight line, node counts, planned ticks at speed 1, and how their
       demonstrations along all legs (demonstration_plan_legs, frames = 400, through DemonstrationWriter) end.
 
+  python benchmarks/chain_env_bench.py edgecert [--launches 20] [--boxes] [--roadmap 14] [--shortcut 16]
+      certificates for roadmap and shortcut polylines, same arm and cell. Microseconds per naf_chain_edge_certify launch beside the
+      naf_chain_edge_check launch over the same nodes and edges, alternating in the same process (median and minimum of
+      `--launches`, at most 50, after two unmeasured ones), at two shapes: the README's roadmaps (273 roadmaps x all 120 edges of
+      M = 14 milestones x 256 samples) and the polyline shape (the same 273 x 16 nodes, the 15 legs (l, l + 1) only), with their
+      ratios and the new kernels' registers. Then the README's 'roadmap' polylines (JointPathChecker.check(roadmap=M) on 2000
+      targets, and again with shortcut=W) through PolylineCertifier.certify at clearance_margin 0 and at 2e-4 A reach: how many end
+      'certified', 'sampled' and 'blocked', the distribution of `refinements`, the launches and the seconds each call took.
+
   python benchmarks/chain_env_bench.py demo [--envs 2048] [--launches 20] [--boxes]
       planned joint paths as replay rows, same arm and cell: N = --envs demonstrations (default 2048 here) of T = 400 ticks.
       Microseconds per naf_chain_demo_rows launch between device events (median and minimum of `--launches`, at most 30, after two
@@ -704,6 +713,85 @@ def _demo_legs(a, writer, plan, targets, obstacles, N, T, launches, urdf, model)
                       "valid_rows_and_records_bit_equal": bool(same), "kernel_registers": regs}))
 
 
+def edgecert(a):
+    import time
+    import numpy as np
+    import torch
+    from robotic_manipulator_rloa_amd import _lib
+    from robotic_manipulator_rloa_amd.chain_certify import PolylineCertifier
+    from robotic_manipulator_rloa_amd.chain_tools import GoalPoseSolver, JointPathChecker
+    from robotic_manipulator_rloa_amd.environment.kinematic import roadmap_edges, roadmap_milestones, roadmap_nodes
+    from robotic_manipulator_rloa_amd.environment.urdf_chain import compile_chain, load_urdf
+    n_joints, S, M, W = a.joints, 256, a.roadmap or 14, a.shortcut or 16
+    V, n = M + 2, 273
+    launches = min(a.launches, 50)
+    a.workcell = True
+    urdf = os.path.abspath(a.urdf) if os.path.isabs(a.urdf) else os.path.join(ROOT, a.urdf)
+    init = ([0.0, 0.6, 0.0, -1.2, 0.0, 0.8, 0.0] + [0.0] * n_joints)[:n_joints]
+    model = compile_chain(load_urdf(urdf), n_joints - 1, list(range(n_joints)), [n_joints], init, [0.1] * n_joints, 0.03,
+                          consider_autocollision=True, **_workcell(a))
+    rng = np.random.default_rng(5)
+    lo = np.array([j.lower if j.limited else -np.pi for j in model.joints])
+    hi = np.array([j.upper if j.limited else np.pi for j in model.joints])
+    q_start, q_goal = np.tile(np.float32(init), (n, 1)), rng.uniform(lo, hi, (n, n_joints)).astype(np.float32)
+    obstacles = (np.array([0.35, 0.2, 0.45]) + rng.uniform(-0.2, 0.2, (n, 3))).astype(np.float32)
+    nodes = roadmap_nodes(q_start, q_goal, roadmap_milestones(model, q_start, q_goal, M, 0))
+    checker, certifier = JointPathChecker(model, 0.06), PolylineCertifier(model, 0.06)
+    shapes = {"roadmaps": roadmap_edges(V), "polylines": np.stack([np.arange(V - 1), np.arange(1, V)], axis=1).astype(np.int32)}
+    timing = {}
+    for shape, edges in shapes.items():
+        E = len(edges)
+        checker.load_edges(nodes, edges, obstacles)
+        certifier.edge_records(nodes, edges, obstacles, S, 0.0)              # (uploads, and one unmeasured launch)
+        times = {"check": [], "certify": []}
+        for i in range(launches + 2):                          # alternating, so that both see the same clocks
+            for name, launch in (("check", lambda: checker.launch_edges(n, V, E, S, 0.0)), ("certify", lambda: certifier.launch(n, V, E, S, 0.0))):
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+                launch()
+                t1.record()
+                t1.synchronize()
+                if i >= 2:
+                    times[name].append(1e3 * t0.elapsed_time(t1))
+        rec, plain = certifier.out[:n * E], checker.edge_out[:n * E]
+        med = {k: float(np.median(v)) for k, v in times.items()}
+        timing[shape] = {"items": n, "edges": E, "samples": S,
+                         "us_per_edge_check_launch": {"median": round(med["check"], 1), "min": round(float(np.min(times["check"])), 1)},
+                         "us_per_edge_certify_launch": {"median": round(med["certify"], 1), "min": round(float(np.min(times["certify"])), 1)},
+                         "certify_over_check": round(med["certify"] / med["check"], 3),
+                         "largest_difference_of_the_minima": float((rec[:, :3] - plain[:, :3]).nan_to_num(posinf=0.0).abs().max()),
+                         "free_edges_share": round(float((rec[:, 4] == 0).float().mean()), 4),
+                         "certified_edges_share": round(float((rec[:, 11] == -1).float().mean()), 4)}
+    # the README's polylines: 2000 targets around the nominal one, the 'roadmap' answers without and with the shortcut round
+    T = 2000
+    targets = np.array([0.45, 0.3, 0.6]) + rng.uniform(-0.25, 0.25, (T, 3))
+    start, obstacle = np.tile(init, (T, 1)), np.tile([0.35, 0.2, 0.45], (T, 1))
+    goal = GoalPoseSolver(model, 0.06).solve(start, targets, obstacle)
+    ok = goal.free
+    census = {}
+    for name, kw in (("roadmap", {"roadmap": M}), ("shortcut", {"roadmap": M, "shortcut": W})):
+        found = checker.check(start[ok], goal.joint_positions[ok], obstacle[ok], candidates=16, resolution=0.02, **kw)
+        rescued = found.outcome == "roadmap"
+        census[name] = {"roadmap_queries": int(rescued.sum())}
+        for label, margin in (("margin_0", 0.0), ("margin_2e-4_A_reach", 2e-4 * model.A * model.reach)):
+            before = certifier.launches
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            cert = certifier.certify(found, obstacle[ok], margin, 0.02)
+            seconds = time.perf_counter() - t
+            count = lambda x: {str(k): int(v) for k, v in zip(*np.unique(x, return_counts=True))}      # noqa: E731
+            census[name][label] = {"margin": round(float(margin), 6), "roadmap_outcomes": count(cert.outcome[rescued]),
+                                   "roadmap_refinements": count(cert.refinements[rescued]), "all_outcomes": count(cert.outcome),
+                                   "all_refinements": count(cert.refinements), "launches": certifier.launches - before,
+                                   "seconds": round(seconds, 3)}
+    usage = json.load(open(_lib.USAGE_PATH)) if os.path.exists(_lib.USAGE_PATH) else {}
+    regs = {name: {q: v.get(q) for q in ("vgprs", "sgprs", "scratch_bytes_per_lane", "lds_bytes", "occupancy")}
+            for name, v in usage.items() if "chain_edge_" in name and "ChainCert" in name}
+    print(json.dumps({"arm": os.path.basename(urdf), "self_pairs": len(model.self_pairs), "workcell_pairs": len(model.cell_pairs),
+                      "boxes": bool(a.boxes), "milestones": M, "shortcut_nodes": W, "launch": timing, "targets": T,
+                      "free_goal_poses": int(ok.sum()), "polylines": census, "kernel_registers": regs}))
+
+
 def kernels(a):
     import numpy as np
     import torch
@@ -742,7 +830,7 @@ def kernels(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["rate", "kernels", "step", "rollout", "gather", "ik", "path", "demo"])
+    ap.add_argument("what", choices=["rate", "kernels", "step", "rollout", "gather", "ik", "path", "demo", "edgecert"])
     ap.add_argument("--urdf", default=os.path.join("tests", "golden", "urdf", "iiwa_like7.urdf"))
     ap.add_argument("--joints", type=int, default=7)
     ap.add_argument("--envs", type=int, default=64)
@@ -769,13 +857,14 @@ def main():
     ap.add_argument("--hindsight", type=float, default=None, help="rate, gather: the share of rows replayed under a hindsight goal")
     ap.add_argument("--horizon", type=int, default=None, help="rate, gather: hindsight_horizon (rate: max_frames; gather: 400)")
     a = ap.parse_args()
-    if a.roadmap and a.certify:
+    if a.roadmap and a.certify and a.what != "edgecert":
         ap.error("--roadmap and --certify are two measurements: roadmap edges are checked at their samples only")
-    if a.shortcut and not a.roadmap:
+    if a.shortcut and not a.roadmap and a.what != "edgecert":
         ap.error("--shortcut shortens roadmap paths: it needs --roadmap M")
     if a.legs and not 2 <= a.legs <= 63:
         ap.error("--legs K splits two-leg plans into K legs, 2 .. 63")
-    {"rate": rate, "kernels": kernels, "step": step, "rollout": rollout, "gather": gather, "ik": ik, "path": paths, "demo": demo}[a.what](a)
+    {"rate": rate, "kernels": kernels, "step": step, "rollout": rollout, "gather": gather, "ik": ik, "path": paths, "demo": demo,
+     "edgecert": edgecert}[a.what](a)
 
 
 if __name__ == "__main__":

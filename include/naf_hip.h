@@ -1012,6 +1012,27 @@ int naf_chain_edge_check(naf_chain_env_t* h, const float* nodes_dev, const int32
                          float obstacle_radius, int N, int V, int E, int S, float margin, float* out, float* poses_out,
                          void* stream);
 
+/* Certified roadmap edges (an addition within ABI 40): naf_chain_edge_check's samples, and with them a statement about the poses
+ * BETWEEN the samples of every edge. environment/edge_certificate.py (edge_half_steps, certify_joint_edge) is the float64 statement.
+ *   reach_dev   : [A][n_seg] (DEVICE), as naf_chain_path_certify takes it.
+ *   half-steps  : an edge is ONE leg of S - 1 intervals, all with the joint displacement (b - a) / (S - 1), so there is one table per
+ *                 edge and every sample uses it: beta[s] = (sum_m |b_m - a_m| reach[m][s]) / (2 (S - 1)), and for a pair (s, t) the
+ *                 same sum over m = f_s .. f_t - 1 with reach[m][t]. float32: the joint sum by fmaf in joint order from 0, then one
+ *                 division by (float)(2 (S - 1)).
+ *   per sample  : the three slacks of naf_chain_path_certify, each the minimum over the sample's tests of (clearance - beta - guard).
+ *   out         : [N E][NAF_CHAIN_EDGE_CERT_FLOATS] (DEVICE) = [0 .. 7] as naf_chain_edge_check | [8] [9] [10] the minima over the
+ *                 samples of the three slacks (+inf without pairs / without a workcell) | [11] the index of the first sample one of
+ *                 whose slacks is < margin, -1: none — the edge is CERTIFIED, which implies [4] == 0. The record of an edge does not
+ *                 depend on its direction but for [3] and [11], which count from a.
+ *   poses_out   : NULL, or DEVICE [N E][S][A], as naf_chain_edge_check.
+ * The launch is naf_chain_edge_check's with one table of n_seg + P floats in LDS, filled before the first pass, and with pairs a
+ * second reduction row per wave. Refusals as naf_chain_edge_check, and NAF_ERR_ARG for a null reach_dev or a guard that is negative
+ * or not finite; NAF_CHAIN_ERR_LDS, and no launch, when the table does not fit beside the handle's rows. */
+#define NAF_CHAIN_EDGE_CERT_FLOATS 12
+int naf_chain_edge_certify(naf_chain_env_t* h, const float* nodes_dev, const int32_t* edges_dev, const float* obstacles_dev,
+                           float obstacle_radius, const float* reach_dev, float guard, int N, int V, int E, int S, float margin,
+                           float* out, float* poses_out, void* stream);
+
 /* Demonstrations (an addition within ABI 40): N planned joint paths turned into the replay rows of the episodes that follow them
  * open loop, one launch. environment/kinematic.py (demonstration_plan, demonstration_rows_host) is the float64 statement.
  *   Demonstration n starts at q_start_dev[n] clamped into the limits (p_0) in the scene targets_dev[n] / obstacles_dev[n] with

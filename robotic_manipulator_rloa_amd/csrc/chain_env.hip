@@ -1557,6 +1557,13 @@ extern "C" int naf_chain_path_certify(naf_chain_env_t* h, const float* q_start_d
 // No pose record, no per-lane array, nothing in scratch, no atomics. SC is the probe's shape, as in chain_path_check_kernel: wave
 // 0 walks, stages the end points as [segment][6][lane], and every wave joins the pair phase of every pass; without pairs a
 // workgroup is one wave with no barrier and no LDS. One butterfly of shuffles at the end; lane 0 writes the record.
+//
+// A leading ChainCert in the pack (CERT below) is naf_chain_edge_certify's kernel: the record has NAF_CHAIN_EDGE_CERT_FLOATS floats.
+// An edge is ONE leg of S - 1 intervals, all with the joint displacement (b - a) / (S - 1), so there is one table of n_seg + P
+// half-steps per edge and every sample uses it: beta[s] = sum_m |b_m - a_m| reach[m][s] / (2 (S - 1)), chain_path_check_kernel's
+// span for a pair. The workgroup's threads fill it in LDS behind the pair phase's rows before the first pass — an entry per
+// thread, the joint sum in joint order by fmaf, one division, one barrier — and the passes are what they were, with the entry
+// subtracted from every clearance beside the plain minima. The kernels without ChainCert keep their arguments and their code.
 template <bool SC, class... Cell>
 __global__ void __launch_bounds__(SC ? 64 * CH_MAX_WAVES : 64)
 chain_edge_check_kernel(const float* __restrict__ model, const float* __restrict__ nodes, const int32_t* __restrict__ edges,
@@ -1564,6 +1571,7 @@ chain_edge_check_kernel(const float* __restrict__ model, const float* __restrict
                         float margin, float* __restrict__ out, float* __restrict__ poses_out, const Cell... cell) {
     constexpr bool CELL = (std::is_same_v<Cell, ChainCell> || ... || false);
     constexpr bool BOX = (std::is_same_v<Cell, ChainBox> || ... || false);
+    constexpr bool CERT = (std::is_same_v<Cell, ChainCert> || ... || false);
     extern __shared__ __attribute__((aligned(16))) float ch_lds[];
     const int64_t item = blockIdx.x;
     const int64_t n = item / E;
@@ -1579,14 +1587,35 @@ chain_edge_check_kernel(const float* __restrict__ model, const float* __restrict
     const float last = (float)(S - 1);
     float min_clear = INFINITY, min_self = INFINITY, min_cell = INFINITY;
     int first = INT_MAX, count = 0;
+    float low_clear = INFINITY, low_self = INFINITY, low_cell = INFINITY, guard = 0.f;
+    int first_low = INT_MAX;
+    const float* tab = nullptr;
+    if constexpr (CERT) {
+        const ChainCert& cert = path_cert(cell...);
+        const float* segs = model + ch_off_seg(A);
+        const float* pairs = model + ch_off_pair(A, n_seg);
+        float* t = ch_lds + ch_cert_table_floats(n_seg, n_pairs, lanes, blockDim.x >> 6);
+        for (int k = threadIdx.x; k < n_seg + n_pairs; k += blockDim.x) {
+            // entry k < n_seg: segment k against the world, joints 0 .. frame - 1; else pair (s, t): t against s, joints frame s ..
+            const int s = k < n_seg ? k : (int)pairs[2 * (k - n_seg) + 1];
+            const int m0 = k < n_seg ? 0 : (int)segs[(int)pairs[2 * (k - n_seg)] * CH_SEG];
+            const int m1 = (int)segs[s * CH_SEG];
+            float acc = 0.f;
+            for (int m = m0; m < m1; ++m) acc = fmaf(fabsf(b[m] - a[m]), cert.reach[m * n_seg + s], acc);
+            t[k] = acc / (float)(2 * (S - 1));
+        }
+        __syncthreads();
+        tab = t;
+        guard = cert.guard;
+    }
     for (int base = 0; base < S; base += lanes) {      // (uniform: every thread takes every pass)
         const int i = base + lane;
         const float f = (float)i / last;
         float ee[3];
-        WalkAux aux = {SC ? ch_lds + lane : nullptr, lanes, INFINITY, INFINITY, nullptr, INFINITY, INFINITY};
+        WalkAux aux = {SC ? ch_lds + lane : nullptr, lanes, INFINITY, INFINITY, tab, INFINITY, INFINITY};
         if (walker) {
             float* rec = poses_out ? poses_out + (item * S + i) * A : nullptr;
-            chain_walk_at<SC, true, false, true, CELL, BOX>(
+            chain_walk_at<SC, true, false, true, CELL, BOX, CERT>(
                 model, A, n_seg,
                 [=](int m) {
                     const float lo = a[m];
@@ -1596,8 +1625,10 @@ chain_edge_check_kernel(const float* __restrict__ model, const float* __restrict
                 },
                 ox, oy, oz, orad, nullptr, nullptr, ee, aux);
         }
-        float self_clear = INFINITY;
-        if constexpr (SC) self_clear = self_clearance_phase<false>(model, A, n_seg, n_pairs, ch_lds, lanes, lane, active, nullptr, nullptr);
+        float self_clear = INFINITY, self_slack = INFINITY;
+        if constexpr (SC)
+            self_clear = self_clearance_phase<CERT>(model, A, n_seg, n_pairs, ch_lds, lanes, lane, active, CERT ? tab + n_seg : nullptr,
+                                                    CERT ? &self_slack : nullptr);
         if (walker) {
             const float clear = aux.clear - orad;
             const bool blocked = clear < margin || self_clear < margin || (CELL && aux.cell < margin);
@@ -1606,6 +1637,13 @@ chain_edge_check_kernel(const float* __restrict__ model, const float* __restrict
             if constexpr (CELL) min_cell = fminf(min_cell, aux.cell);
             first = blocked && i < first ? i : first;
             count += blocked ? 1 : 0;
+            if constexpr (CERT) {
+                const float s0 = aux.slack - orad - guard, s1 = self_slack - guard, s2 = aux.cell_slack - guard;
+                low_clear = fminf(low_clear, s0);
+                low_self = fminf(low_self, s1);
+                if constexpr (CELL) low_cell = fminf(low_cell, s2);
+                first_low = (s0 < margin || s1 < margin || (CELL && s2 < margin)) && i < first_low ? i : first_low;
+            }
         }
     }
     if (threadIdx.x >= 64) return;      // (behind the last barrier; wave 0 is whole: the lanes that walked nothing hold the identities)
@@ -1615,11 +1653,17 @@ chain_edge_check_kernel(const float* __restrict__ model, const float* __restrict
         min_cell = fminf(min_cell, __shfl_xor(min_cell, off));
         first = min(first, __shfl_xor(first, off));
         count += __shfl_xor(count, off);
+        if constexpr (CERT) {
+            low_clear = fminf(low_clear, __shfl_xor(low_clear, off));
+            low_self = fminf(low_self, __shfl_xor(low_self, off));
+            low_cell = fminf(low_cell, __shfl_xor(low_cell, off));
+            first_low = min(first_low, __shfl_xor(first_low, off));
+        }
     }
     if (threadIdx.x != 0) return;
     float len = 0.f;
     for (int m = 0; m < A; ++m) len = fmaxf(len, fabsf(b[m] - a[m]));
-    float* o = out + item * NAF_CHAIN_EDGE_FLOATS;
+    float* o = out + item * (CERT ? NAF_CHAIN_EDGE_CERT_FLOATS : NAF_CHAIN_EDGE_FLOATS);
     o[0] = min_clear;
     o[1] = min_self;
     o[2] = min_cell;
@@ -1628,6 +1672,19 @@ chain_edge_check_kernel(const float* __restrict__ model, const float* __restrict
     o[5] = len;
     o[6] = len / last;
     o[7] = 0.f;
+    if constexpr (CERT) {
+        o[8] = low_clear;
+        o[9] = low_self;
+        o[10] = low_cell;
+        o[11] = first_low == INT_MAX ? -1.f : (float)first_low;
+    }
+}
+
+// what naf_chain_edge_check and naf_chain_edge_certify ask of the arguments they share
+static inline bool ch_edge_args_ok(int N, int V, int E, int S, float margin, float obstacle_radius) {
+    if (N < 1 || V < 2 || V > 64 || E < 1 || E > V * (V - 1) / 2 || (int64_t)N * E > (int64_t)1 << 30) return false;
+    if (S < 64 || S > 2048 || S % 64 != 0) return false;
+    return std::isfinite(margin) && std::isfinite(obstacle_radius) && obstacle_radius >= 0.f;
 }
 
 // One workgroup per (query, edge); the SC kernels' dynamic LDS is the probe's.
@@ -1635,14 +1692,32 @@ extern "C" int naf_chain_edge_check(naf_chain_env_t* h, const float* nodes_dev, 
                                     float obstacle_radius, int N, int V, int E, int S, float margin, float* out, float* poses_out,
                                     void* stream) {
     if (!h || !nodes_dev || !edges_dev || !obstacles_dev || !out) return NAF_ERR_ARG;
-    if (N < 1 || V < 2 || V > 64 || E < 1 || E > V * (V - 1) / 2 || (int64_t)N * E > (int64_t)1 << 30) return NAF_ERR_ARG;
-    if (S < 64 || S > 2048 || S % 64 != 0) return NAF_ERR_ARG;
-    if (!std::isfinite(margin) || !std::isfinite(obstacle_radius) || obstacle_radius < 0.f) return NAF_ERR_ARG;
+    if (!ch_edge_args_ok(N, V, E, S, margin, obstacle_radius)) return NAF_ERR_ARG;
     return ch_with_pack(h, [&](auto sc, auto... cell) {
         const ChShape w = ch_shape<sc()>(h, h->waves);
         return ch_launch_raising<chain_edge_check_kernel<sc(), decltype(cell)...>>(
             CH_MAX_DYN_LDS, (unsigned)((int64_t)N * E), w, stream, h->model_dev, nodes_dev, edges_dev, obstacles_dev, obstacle_radius,
             V, E, S, h->A, h->n_seg, w.n_pairs, w.lanes, margin, out, poses_out, cell...);
+    });
+}
+
+// The certifying edge launch: the SC rows with the second reduction row per wave (none without pairs), then the edge's one table.
+extern "C" int naf_chain_edge_certify(naf_chain_env_t* h, const float* nodes_dev, const int32_t* edges_dev, const float* obstacles_dev,
+                                      float obstacle_radius, const float* reach_dev, float guard, int N, int V, int E, int S,
+                                      float margin, float* out, float* poses_out, void* stream) {
+    if (!h || !nodes_dev || !edges_dev || !obstacles_dev || !reach_dev || !out) return NAF_ERR_ARG;
+    if (!ch_edge_args_ok(N, V, E, S, margin, obstacle_radius)) return NAF_ERR_ARG;
+    if (!std::isfinite(guard) || guard < 0.f) return NAF_ERR_ARG;
+    // an arm whose rows do not leave room for the table and the second row is refused, not shrunk: naf_chain_path_certify's rule
+    const size_t lds = (ch_cert_table_floats(h->n_seg, h->n_pairs, h->lanes, h->waves) + (size_t)(h->n_seg + h->n_pairs)) * sizeof(float);
+    if (lds > (h->n_pairs > 0 ? CH_MAX_DYN_LDS : 64 * 1024)) return NAF_CHAIN_ERR_LDS;
+    const ChainCert cert = {reach_dev, guard};
+    return ch_with_pack(h, [&](auto sc, auto... cell) {
+        ChShape w = ch_shape<sc()>(h, h->waves);
+        w.lds = lds;      // (the table: also without pairs)
+        return ch_launch_raising<chain_edge_check_kernel<sc(), ChainCert, decltype(cell)...>>(
+            CH_MAX_DYN_LDS, (unsigned)((int64_t)N * E), w, stream, h->model_dev, nodes_dev, edges_dev, obstacles_dev, obstacle_radius,
+            V, E, S, h->A, h->n_seg, w.n_pairs, w.lanes, margin, out, poses_out, cert, cell...);
     });
 }
 

@@ -385,6 +385,29 @@ class ManipulatorFramework:
         planner = self._kinematic_planner('demonstrate_joint_paths', 'chain model to drive')
         return planner.demonstrate_joint_paths(paths, targets, obstacles, speed, frames, keep_contact, on_device, polylines)
 
+    def certify_joint_paths(self, paths, obstacles=None, clearance_margin: float = 0.0, resolution: float = 0.02,
+                            on_device: Optional[bool] = None):
+        """Certificates for the polylines of planned joint paths, BETWEEN their samples (kinematic environment only; needs no
+        agent): every query of `paths` that has a path — 'straight', 'via' and 'sampled' ones as start -> via -> goal, 'roadmap'
+        ones as their nodes[:n_nodes], shortened by shortcut or not — is sampled leg by leg at poses at most `resolution` apart
+        (a multiple of 64 per leg, at most 2048), and every test at every sample has to keep clearance_margin plus how far the
+        tested capsule can travel over half a sample interval of that leg (environment/edge_certificate.py: certify_joint_edge).
+        Then NO pose of the polyline is closer than clearance_margin to the obstacle, the arm itself or the workcell. A query
+        that is free at its samples but not certified is run again with twice the samples on all its legs, up to 2048.
+          paths            : JointPaths of plan_joint_paths(), of any kind; it is not changed
+          obstacles        : as reach_targets() takes them — the scenes the paths were planned in
+          clearance_margin : the distance every pose keeps where certified; resolution: the first round's sample step
+          on_device        : None: the device when there is one (one naf_chain_edge_certify launch per chunk and round); False:
+                             the float64 host twin under the same rule (slow). An arm with pairs whose capsules only just fit a
+                             workgroup's LDS is refused on the device (NAF_CHAIN_ERR_LDS); on_device=False answers it.
+        Returns environment.edge_certificate.PathCertificates, arrays over the queries: outcome ('certified' | 'sampled': free at
+        the last round's samples, not certified at 2048 | 'blocked': a sample is below the margin | 'none': no path), certified,
+        slack, leg_slack [N][Kmax - 1], weakest_leg, the three minima, samples, sample_step, refinements. The certificate is about
+        the capsule model and the polyline; a controller's tracking error is not in it."""
+        from .arm_certify import certify_joint_paths
+        planner = self._kinematic_planner('certify_joint_paths', 'chain model to certify on')
+        return certify_joint_paths(planner, paths, obstacles, clearance_margin, resolution, on_device)
+
     def _check_demonstrations(self, demos, E) -> None:
         if not isinstance(demos, Demonstrations):
             raise InvalidNAFAgentParameter('demonstrations is the Demonstrations that demonstrate_joint_paths() returned')
