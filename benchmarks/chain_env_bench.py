@@ -346,6 +346,7 @@ def ik(a):
         t1.synchronize()
         if i >= 2:
             kernel.append(1e3 * t0.elapsed_time(t1))
+    oriented = _ik_oriented(a, solver, q0, targets, obstacles, R, K, per, prm) if a.orientation else None
     twin = KinematicEnvironment(model, (0.45, 0.3, 0.6), (0.35, 0.2, 0.45), 0.06)
     t = time.perf_counter()
     host = goal_poses_host(twin, q0[:64], targets[:64], obstacles[:64], restarts=R, iterations=K)
@@ -361,7 +362,39 @@ def ik(a):
                       "twin_seconds_for_64_queries": round(twin_s, 3),
                       "twin_seconds_for_all_queries_EXTRAPOLATED_from_64": round(twin_s * N / 64, 1),
                       "twin_and_device_agree_on_reachable_of_64": int(np.sum(host.reachable == out.reachable[:64])),
-                      "kernel_registers": regs}))
+                      "kernel_registers": regs, **({"orientation": oriented} if oriented else {})}))
+
+
+def _ik_oriented(a, solver, q0, targets, obstacles, R, K, per, prm) -> dict:
+    """ik --orientation full|axis: the same queries with an orientation goal — axis: approach from above; full: the tool's z axis
+    straight down and its x axis along the world's (the quaternion (1, 0, 0, 0)) — solved once for the converged and free shares,
+    then the pose launch timed beside the positional launch in this process, the two alternating launch by launch."""
+    import numpy as np
+    import torch
+    from robotic_manipulator_rloa_amd.environment.kinematic import orientation_goal
+    kw = dict(orientations=[1.0, 0.0, 0.0, 0.0]) if a.orientation == "full" else dict(approach_directions=[0.0, 0.0, -1.0])
+    out = solver.solve(q0, targets, obstacles, restarts=R, iterations=K, **kw)
+    og = orientation_goal(len(q0), tolerance=1e-3, **kw)      # the last chunk's queries and goals are still in the buffers
+    pose = solver.pose_params(og)
+    times = {"positional": [], "pose": []}
+    for i in range(2 * (a.launches + 2)):
+        which = "pose" if i % 2 else "positional"
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        if which == "pose":
+            solver.launch(per, R, prm, 1e-3, 0.0, solve_only=True, mode=og.mode, pose=pose)
+        else:
+            solver.launch(per, R, prm, 1e-3, 0.0, solve_only=True)
+        t1.record()
+        t1.synchronize()
+        if i >= 4:
+            times[which].append(1e3 * t0.elapsed_time(t1))
+    stat = lambda v: {"median": round(float(np.median(v)), 1), "min": round(float(np.min(v)), 1)}      # noqa: E731
+    return {"kind": a.orientation, "iterations": K, "us_per_ik_solve_pose_launch": stat(times["pose"]),
+            "us_per_ik_solve_launch_alternating": stat(times["positional"]),
+            "pose_over_positional_median": round(float(np.median(times["pose"]) / np.median(times["positional"])), 3),
+            "converged_share": round(float(out.reachable.mean()), 4), "free_share": round(float(out.free.mean()), 4),
+            "median_angle_residual_of_converged": float(np.median(out.angle_residual[out.reachable])) if out.reachable.any() else None}
 
 
 def paths(a):
@@ -850,6 +883,8 @@ def main():
                     help="path, with --roadmap: answer the README's paths again with a shortcut round over W nodes, and demonstrate them")
     ap.add_argument("--legs", type=int, default=0, metavar="K",
                     help="demo: time naf_chain_demo_rows_legs, the same plans split into K legs, beside naf_chain_demo_rows")
+    ap.add_argument("--orientation", choices=["full", "axis"], default=None,
+                    help="ik: also solve the section's queries with an orientation goal and time naf_chain_ik_solve_pose beside naf_chain_ik_solve")
     ap.add_argument("--trajectory", action="store_true", help="rollout: record the joint values of every frame")
     ap.add_argument("--arm", default="", help="rate: a fixture arm of tests/golden/urdf by name, --joints its joint count")
     ap.add_argument("--target-range", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))

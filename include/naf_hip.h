@@ -897,8 +897,9 @@ int naf_chain_env_rollout_step(naf_chain_env_t* h, float* env_state, const float
 
 /* Goal poses (additions within ABI 40): joint values that put the end effector on given targets, by a damped least-squares iteration on
  * its positional Jacobian, batched over queries and restarts; and the choice among a query's restarts. environment/kinematic.py
- * (jacobian, ik_step, solve_ik, select_goal_pose) is the float64 statement. Orientation is no goal; contact is not part of the
- * iteration — it is met by restarts and selection only.
+ * (jacobian, ik_step, solve_ik, select_goal_pose) is the float64 statement. Orientation is no goal of naf_chain_ik_solve: it is one
+ * of naf_chain_ik_solve_pose ("Oriented goal poses" below); contact is not part of the iteration — it is met by restarts and
+ * selection only.
  *   A candidate is (query n, restart r), index n R + r: target g = targets_dev[n], start pose q_start_dev[n], seed = q_start_dev[n]
  *   for r = 0 and seeds_dev[n][r] otherwise (seeds_dev[n][0] is not read). R is a power of two, 1 .. 64.
  *   the rule    : q = seed, then `iterations` updates, a fixed trip count:
@@ -934,6 +935,51 @@ int naf_chain_ik_solve(naf_chain_env_t* h, const float* targets_dev, const float
 int naf_chain_ik_select(naf_chain_env_t* h, const float* q_out, const float* q_start_dev, const float* residual_out,
                         const float* probe_dev, const float* cell_dev, int N, int R, float tolerance, float margin, int* choice_out,
                         int* class_out, float* joint_distance_out, void* stream);
+
+/* Oriented goal poses (an addition within ABI 40): naf_chain_ik_solve with an end-effector orientation in the goal. environment/kinematic.py
+ * (end_effector_frame, orientation_error, spd6_solve, ik_pose_step, solve_ik_pose) is the float64 statement. Candidates, seeds, counts
+ * and the clearances are as under "Goal poses"; naf_chain_ik_select is fed merit_out in the place of residual_out and is unchanged.
+ *   R_ee        : the rotation of the frame the walk ends with — the frame whose origin plus R_ee ee_point is ee.
+ *   the goal    : one kind per call. mode 0 (full): goals_dev [N][9] = R_goal, row-major (the host forms it from a unit quaternion
+ *                 (x, y, z, w), a URDF / PyBullet link orientation). mode 1 (axis): goals_dev [N][3] = a unit direction d in the world
+ *                 that t = R_ee tool_axis is to point along; the roll about t is free; tool_normal is a fixed unit vector
+ *                 perpendicular to tool_axis.
+ *   e_w         : the angular error, a rotation vector in the world.
+ *                 full: E = R_goal R_ee^T; its quaternion (v, w) by the largest-of-four rule (Shepperd): the largest of tr E, E00,
+ *                   E11, E22, the first of equals, picks among the four proportional forms of (x, y, z, w)
+ *                     (E21 - E12, E02 - E20, E10 - E01, 1 + tr)              (1 + E00 - E11 - E22, E01 + E10, E02 + E20, E21 - E12)
+ *                     (E01 + E10, 1 + E11 - E00 - E22, E12 + E21, E02 - E20)  (E02 + E20, E12 + E21, 1 + E22 - E00 - E11, E10 - E01)
+ *                   which is scaled to unit length and given the sign with w >= 0; theta = 2 atan2(|v|, w); e_w = v theta / |v|, or
+ *                   2 v where |v| <= 1e-6. Well conditioned at theta -> pi, which the (E - E^T) / 2 form is not.
+ *                 axis: x = t x d, theta = atan2(|x|, t . d), e_w = x theta / |x|; where |x| <= 1e-6: x if t . d > 0, otherwise
+ *                   pi R_ee tool_normal.
+ *   one update  : the walk of "Goal poses", which also gives R_ee; e_p = g - ee cut to e_max; e_w cut to w_max; e6 = [e_p ; L e_w],
+ *                 L = weight (metres per radian); column m of J6 = [c_m ; L a_m] revolute | [a_m ; 0] prismatic | 0 for m >=
+ *                 end-effector frame; M = J6 J6^T + lam2 I (6 x 6); M y = e6 by M = L D L^T without pivoting in a fixed order
+ *                 (column j = 0 .. 5: v_k = l_jk d_k, d_j = M_jj - sum_k l_jk v_k, r_j = 1 / d_j, l_ij = (M_ji - sum_k l_ik v_k) r_j;
+ *                 z upwards; y_i = z_i r_i - sum_{k > i} l_ki y_k downwards); dq_m = J6[:, m] . y; then dq_max and the position
+ *                 limits as in "Goal poses". The trip count is fixed.
+ *   the numbers : after the last update one more walk: residual = |g - ee|, angle = |e_w| uncut, merit = max(residual, angle
+ *                 angle_length) with angle_length = tolerance / orientation_tolerance formed by the host in float32: a candidate is
+ *                 converged iff merit <= tolerance.
+ *   ik_solve_pose: q_out [N R][A], residual_out, angle_out, merit_out [N R] (DEVICE); iters_out as naf_chain_ik_solve's. One lane per
+ *                 candidate, one wave per workgroup, no barrier; the LDS record is naf_chain_ik_solve's (a_m is in it: the angular
+ *                 rows cost none), M's 21 entries, the factorisation and the substitutions live in registers. NAF_ERR_ARG, and no
+ *                 launch, for a null pointer other than iters_out, the counts "Goal poses" refuses, a mode other than 0 / 1,
+ *                 iterations < 1, any of lam2 / e_max / dq_max / weight / w_max / angle_length not finite and positive, a tool axis
+ *                 or normal that is not finite. NAF_CHAIN_ERR_LDS as naf_chain_ik_solve.
+ *   Out of scope: null-space objectives, a collision-aware iteration, orientation tolerances per axis. */
+typedef struct {
+    float weight;           /* L: metres per radian */
+    float w_max;            /* the longest angular error of one update, radians */
+    float angle_length;     /* tolerance / orientation_tolerance */
+    float tool_axis[3];     /* unit, in the end-effector frame (mode 1) */
+    float tool_normal[3];   /* unit, perpendicular to tool_axis (mode 1) */
+} naf_chain_ik_pose_params_t;
+int naf_chain_ik_solve_pose(naf_chain_env_t* h, const float* targets_dev, const float* goals_dev, int mode, const float* q_start_dev,
+                            const float* seeds_dev, int N, int R, naf_chain_ik_params_t params,
+                            naf_chain_ik_pose_params_t pose_params, float* q_out, float* residual_out, float* angle_out,
+                            float* merit_out, float* iters_out, void* stream);
 
 /* Joint paths (an addition within ABI 40): the sampled collision check of joint-space polylines start -> via -> goal, batched over
  * queries and candidate vias. environment/kinematic.py (path_pose, check_joint_path) is the float64 statement. The check is SAMPLED:

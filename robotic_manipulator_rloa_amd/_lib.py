@@ -168,6 +168,12 @@ class IkParams(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("lam2", C.c_float), ("e_max", C.c_float), ("dq_max", C.c_float)]
 
 
+class IkPoseParams(C.Structure):
+    """naf_chain_ik_pose_params_t (include/naf_hip.h)"""
+    _fields_ = [("weight", C.c_float), ("w_max", C.c_float), ("angle_length", C.c_float), ("tool_axis", C.c_float * 3),
+                ("tool_normal", C.c_float * 3)]
+
+
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/naf_hip.h one to one
 _PROTOS = {
     "naf_hip_abi_version": [],
@@ -273,6 +279,7 @@ _PROTOS = {
     "naf_replay_gather_rows_hindsight": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp],
     "naf_chain_env_step_tagged": [_vp, _vp, _vp, _vp, _vp, _i, _u64, _vp, _i, _vp, _i, _vp],
     "naf_chain_ik_solve": [_vp, _vp, _vp, _vp, _i, _i, IkParams, _vp, _vp, _vp, _vp],
+    "naf_chain_ik_solve_pose": [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, IkParams, IkPoseParams, _vp, _vp, _vp, _vp, _vp, _vp],
     "naf_chain_ik_select": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp],
     "naf_chain_path_check": [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _f, _vp, _vp, _vp],
     "naf_chain_path_certify": [_vp, _vp, _vp, _vp, _vp, _f, _vp, _f, _i, _i, _i, _f, _vp, _vp, _vp],

@@ -17,7 +17,7 @@ import torch
 
 from .environment.kinematic import (DEMO_MAX_TICKS, PATH_CANDIDATES_MAX, ROADMAP_MAX, JointPaths, demonstration_plan,
                                     demonstration_rows_host, demonstration_speed_ok, goal_poses_host, ik_restarts_ok, joint_paths_host,
-                                    reach_queries, roadmap_milestones, roadmap_size_ok, shortcut_size_ok)
+                                    orientation_goal, reach_queries, roadmap_milestones, roadmap_size_ok, shortcut_size_ok)
 from .environment.polyline import SHORTCUT_MAX, SHORTCUT_MIN, pad_shortcut, polyline_plan, roadmap_arguments, roadmap_queries
 from .utils.exceptions import InvalidEnvironmentParameter
 from .utils.logger import get_global_logger
@@ -61,7 +61,30 @@ _ARGUMENT_RULES = {
     'frames': (lambda v: _positive_int(v) and v <= DEMO_MAX_TICKS, f'a number of steps from 1 to {DEMO_MAX_TICKS}'),
     'shortcut': (shortcut_size_ok, f'a number of nodes, 0 (no shortcut round) or from {SHORTCUT_MIN} to {SHORTCUT_MAX}'),
     'polylines': (lambda v: isinstance(v, (bool, np.bool_)), 'a bool'),
+    'orientation_tolerance': (lambda v: not isinstance(v, bool) and _finite_number(v) and v > 0.0, 'a positive angle in radians'),
+    'orientation_weight': (lambda v: v is None or (not isinstance(v, bool) and _finite_number(v) and v > 0.0),
+                           'a positive length per radian, or None for a quarter of the reach'),
 }
+
+ORIENTATION_ARGUMENTS = ('orientations', 'approach_directions', 'tool_axis', 'orientation_tolerance', 'orientation_weight')
+
+
+def orientation_given(orientation) -> bool:
+    """whether a method's orientation keyword arguments ask for an orientation goal"""
+    return bool(orientation) and (orientation.get('orientations') is not None or orientation.get('approach_directions') is not None)
+
+
+def check_orientation(orientation, N: int, tolerance: float = 1e-3) -> dict:
+    """The orientation keyword arguments of a call with N queries through their refusals (environment.kinematic.orientation_goal
+    names the query): {} where no orientation goal is asked for, otherwise the arguments as the solvers take them."""
+    if not orientation_given(orientation):
+        return {}
+    kw = {k: orientation[k] for k in ORIENTATION_ARGUMENTS if k in orientation}
+    check_arguments(orientation_tolerance=kw.get('orientation_tolerance', 1e-3), orientation_weight=kw.get('orientation_weight'))
+    with _refusing():
+        orientation_goal(N, kw.get('orientations'), kw.get('approach_directions'), kw.get('tool_axis', (0.0, 0.0, 1.0)), tolerance,
+                         kw.get('orientation_tolerance', 1e-3))
+    return kw
 
 
 def check_arguments(**given) -> None:
@@ -119,11 +142,11 @@ class ArmPlanner:
 
     # ---- goal poses ---------------------------------------------------------------------------------------------------------------
     def solve_goal_poses(self, targets, obstacles, initial_joint_positions, restarts, iterations, tolerance, clearance_margin, seed,
-                         on_device):
+                         on_device, orientation=None):
         check_arguments(restarts=restarts, iterations=iterations, tolerance=tolerance, clearance_margin=clearance_margin, seed=seed)
         q0, targets, obstacles, _ = self.queries(targets, obstacles, initial_joint_positions)
         kw = dict(restarts=int(restarts), iterations=int(iterations), tolerance=float(tolerance), margin=float(clearance_margin),
-                  seed=int(seed))
+                  seed=int(seed), **check_orientation(orientation, len(q0), float(tolerance)))
         if not _on_device(on_device):
             return goal_poses_host(self.env, q0, targets, obstacles, **kw)
         from .chain_tools import GoalPoseSolver
@@ -153,10 +176,13 @@ class ArmPlanner:
         return q0, q_goal, obstacles
 
     def plan_joint_paths(self, targets, obstacles, initial_joint_positions, goal_joint_positions, candidates, resolution,
-                         clearance_margin, seed, on_device, certify, roadmap, shortcut=0):
+                         clearance_margin, seed, on_device, certify, roadmap, shortcut=0, orientation=None):
         model = self.env.model
         if (targets is None) == (goal_joint_positions is None):
             raise InvalidEnvironmentParameter('plan_joint_paths() takes exactly one of targets and goal_joint_positions')
+        if goal_joint_positions is not None and orientation_given(orientation):
+            raise InvalidEnvironmentParameter('plan_joint_paths(goal_joint_positions=) is given the goal poses themselves: orientations '
+                                              'and approach_directions are goals of the poses solved for targets')
         check_arguments(candidates=candidates, resolution=resolution, clearance_margin=clearance_margin, seed=seed, certify=certify)
         check_roadmap(roadmap, certify, 'plan_joint_paths', shortcut)
         if roadmap:
@@ -169,7 +195,8 @@ class ArmPlanner:
         if targets is None:
             return self.plan_checked(*self._goal_queries(goal_joint_positions, obstacles, initial_joint_positions), **kw)
         q0, targets, obstacles, _ = self.queries(targets, obstacles, initial_joint_positions)
-        goal = self._framework().solve_goal_poses(targets, obstacles, q0, seed=seed, on_device=on_device)
+        goal = self._framework().solve_goal_poses(targets, obstacles, q0, seed=seed, on_device=on_device,
+                                                  **check_orientation(orientation, len(q0)))
         return self.paths_to_goals(goal, q0, obstacles, kw)
 
     def plan_checked(self, q0, q_goal, obstacles, candidates=16, resolution=0.02, clearance_margin=0.0, seed=0, on_device=None,
@@ -246,11 +273,15 @@ class ArmPlanner:
 
     # ---- rollouts to given targets ------------------------------------------------------------------------------------------------
     def reach_targets(self, agent, targets, obstacles, initial_joint_positions, frames, noise_scale, n_envs, trajectories, goal_poses,
-                      joint_paths, certify, roadmap, shortcut=0):
+                      joint_paths, certify, roadmap, shortcut=0, orientation=None):
         """the queries and the refusals of reach_targets(), the agent's rollout, then the goal poses, the paths and their ratios"""
         env = self.env
         q0, targets, obstacles, frames = self.queries(targets, obstacles, initial_joint_positions, frames)
         goal_poses = bool(goal_poses or joint_paths)
+        if orientation_given(orientation) and not goal_poses:
+            raise InvalidEnvironmentParameter('reach_targets(orientations= / approach_directions=) is a goal of the goal poses: it needs '
+                                              'goal_poses=True or joint_paths=True (the policy and its outcome know no orientation)')
+        orientation = check_orientation(orientation, len(q0))
         if not isinstance(certify, (bool, np.bool_)) or (certify and not joint_paths):
             raise InvalidEnvironmentParameter('reach_targets(certify=True) certifies the joint paths: it is a bool and needs joint_paths=True')
         check_roadmap(roadmap, certify, 'reach_targets', shortcut)
@@ -261,7 +292,7 @@ class ArmPlanner:
         result = agent.rollout_vectorized(env.model, targets, obstacles, q0, frames=frames, noise_scale=float(noise_scale),
                                           n_envs=n_envs, trajectories=bool(trajectories), scene={'obstacle_radius': env.obstacle_radius})
         if goal_poses:
-            result.goal = self._framework().solve_goal_poses(targets, obstacles, q0)
+            result.goal = self._framework().solve_goal_poses(targets, obstacles, q0, **orientation)
             path = np.asarray(result.joint_positions, np.float64)
             length = np.sum(np.max(np.abs(np.diff(path, axis=1)), axis=2), axis=1)
             with np.errstate(divide='ignore', invalid='ignore'):

@@ -25,8 +25,8 @@ from . import _lib
 from ._lib import check, ptr, stream_ptr
 from .chain_legs import LegsLaunch
 from .environment.kinematic import (DEMO_CHUNK, DEMO_FLOATS, DEMO_MAX_TICKS, EDGE_FLOATS, PATH_CERT_FLOATS, PATH_CHUNK, PATH_FLOATS,
-                                    GoalPoses, JointPaths, certificate_guard, demo_row_layout, gather_demonstrations,
-                                    gather_goal_poses, ik_seeds, plan_paths, reach_table)
+                                    GoalPoses, JointPaths, certificate_guard, concatenate_goal_poses, demo_row_layout,
+                                    gather_demonstrations, gather_goal_poses, ik_seeds, orientation_goal, plan_paths, reach_table)
 
 
 class _ChainHandle:
@@ -81,7 +81,10 @@ class GoalPoseSolver(_ChainTool):
     """Goal poses on a chain model (csrc/chain_env.hip, "goal poses"): per chunk of candidates naf_chain_ik_solve, then the
     clearances of the solved poses by naf_chain_env_reset_given + naf_chain_env_probe (+ naf_chain_env_probe_cell with a workcell),
     then naf_chain_ik_select. Owns the handle and the buffers; needs no agent. A chunk holds a fixed number of candidates,
-    `chunk` rounded down to whole queries; a query's result does not depend on the chunk or the lane it lands in."""
+    `chunk` rounded down to whole queries; a query's result does not depend on the chunk or the lane it lands in.
+    With an orientation goal (solve(orientations=) or solve(approach_directions=)) the first launch is naf_chain_ik_solve_pose
+    and the selection is fed its merit; the goal, angle and merit buffers are allocated on the first such call. Without one
+    the launches are the ones above and those buffers do not exist."""
     CHUNK, CHUNK_MIN, CHUNK_REFUSAL = 32768, 64, "GoalPoseSolver: a chunk holds at least 64 candidates"
 
     def __init__(self, chain, obstacle_radius: float = 0.06, chunk: Optional[int] = None, device=None):
@@ -93,6 +96,7 @@ class GoalPoseSolver(_ChainTool):
         self.obs, self.scene = z(C, 2 * A + 9), z(C, 6)
         self.probe, self.cell = z(C, 5), torch.full((C,), float("inf"), dtype=torch.float32, device=self.dev)
         self.choice, self.cls = z(C, dtype=torch.int32), z(C, dtype=torch.int32)
+        self.goals = self.angle = self.merit = None      # with an orientation goal only
 
     def params(self, iterations: int, lam=None, e_max=None, dq_max=None) -> "_lib.IkParams":
         reach = self.chain.reach
@@ -100,11 +104,25 @@ class GoalPoseSolver(_ChainTool):
         return _lib.IkParams(int(iterations), float(lam) ** 2, float(0.25 * reach if e_max is None else e_max),
                              float(0.5 if dq_max is None else dq_max))
 
-    def launch(self, n: int, R: int, prm, tolerance: float, margin: float, solve_only: bool = False) -> None:
-        """the launches of one chunk of n queries x R restarts already in the buffers, on the current stream"""
+    def pose_params(self, og, weight=None, w_max=None) -> "_lib.IkPoseParams":
+        """naf_chain_ik_pose_params_t of an OrientationGoal: weight 0.25 reach and w_max 0.5 rad unless given"""
+        f3 = ctypes.c_float * 3
+        return _lib.IkPoseParams(float(0.25 * self.chain.reach if weight is None else weight), float(0.5 if w_max is None else w_max),
+                                 og.angle_length, f3(*map(float, og.tool_axis)), f3(*map(float, og.tool_normal)))
+
+    def launch(self, n: int, R: int, prm, tolerance: float, margin: float, solve_only: bool = False, mode=None, pose=None) -> None:
+        """the launches of one chunk of n queries x R restarts already in the buffers, on the current stream; mode / pose: the
+        chunk's orientation goals are in self.goals and the first launch is naf_chain_ik_solve_pose"""
         st, E = stream_ptr(), n * R
-        check(self.lib.naf_chain_ik_solve(self._chain_env, ptr(self.targets), ptr(self.q_start), ptr(self.seeds), n, R, prm, ptr(self.q),
-                                          ptr(self.residual), None, st), "chain_ik_solve")
+        measure = self.residual
+        if mode is None:
+            check(self.lib.naf_chain_ik_solve(self._chain_env, ptr(self.targets), ptr(self.q_start), ptr(self.seeds), n, R, prm,
+                                              ptr(self.q), ptr(self.residual), None, st), "chain_ik_solve")
+        else:
+            check(self.lib.naf_chain_ik_solve_pose(self._chain_env, ptr(self.targets), ptr(self.goals), int(mode), ptr(self.q_start),
+                                                   ptr(self.seeds), n, R, prm, pose, ptr(self.q), ptr(self.residual), ptr(self.angle),
+                                                   ptr(self.merit), None, st), "chain_ik_solve_pose")
+            measure = self.merit
         if solve_only:
             return
         check(self.lib.naf_chain_env_reset_given(self._chain_env, ptr(self.env_state), ptr(self.obs), E, ptr(self.q), ptr(self.scene),
@@ -112,7 +130,7 @@ class GoalPoseSolver(_ChainTool):
         check(self.lib.naf_chain_env_probe(self._chain_env, ptr(self.env_state), ptr(self.probe), E, st), "chain_env_probe")
         if self.has_cell:
             check(self.lib.naf_chain_env_probe_cell(self._chain_env, ptr(self.env_state), ptr(self.cell), E, st), "chain_env_probe_cell")
-        check(self.lib.naf_chain_ik_select(self._chain_env, ptr(self.q), ptr(self.q_start), ptr(self.residual), ptr(self.probe),
+        check(self.lib.naf_chain_ik_select(self._chain_env, ptr(self.q), ptr(self.q_start), ptr(measure), ptr(self.probe),
                                            ptr(self.cell) if self.has_cell else None, n, R, tolerance, margin, ptr(self.choice),
                                            ptr(self.cls), ptr(self.distance), st), "chain_ik_select")
 
@@ -126,14 +144,24 @@ class GoalPoseSolver(_ChainTool):
         self._upload(self.scene, np.repeat(scene, R, axis=0))
 
     def solve(self, q0, targets, obstacles, restarts: int = 8, iterations: int = 32, tolerance: float = 1e-3, margin: float = 0.0,
-              seed: int = 0, **constants) -> GoalPoses:
-        """q0[N][A] (action order), targets[N][3], obstacles[N][3] -> GoalPoses of numpy arrays (float32 where the device's)."""
+              seed: int = 0, orientations=None, approach_directions=None, tool_axis=(0.0, 0.0, 1.0),
+              orientation_tolerance: float = 1e-3, orientation_weight: Optional[float] = None, w_max: Optional[float] = None,
+              **constants) -> GoalPoses:
+        """q0[N][A] (action order), targets[N][3], obstacles[N][3] -> GoalPoses of numpy arrays (float32 where the device's).
+        orientations[N][4] | [4] (quaternions x, y, z, w) or approach_directions[N][3] | [3] (for tool_axis, in the end-effector
+        frame): an orientation goal (environment.kinematic.orientation_goal); GoalPoses.angle_residual is then filled."""
         A, R = self.A, int(restarts)
         q0 = np.ascontiguousarray(q0, np.float32).reshape(-1, A)
         N = len(q0)
         targets, obstacles = np.asarray(targets, np.float32).reshape(N, 3), np.asarray(obstacles, np.float32).reshape(N, 3)
         seeds = ik_seeds(self.chain, N, R, seed)
         prm = self.params(iterations, **constants)
+        og = orientation_goal(N, orientations, approach_directions, tool_axis, tolerance, orientation_tolerance)
+        mode = pose = None
+        if og is not None:
+            mode, pose = og.mode, self.pose_params(og, orientation_weight, w_max)
+            if self.goals is None:
+                self.goals, self.angle, self.merit = self._zeros(self.chunk, 9), self._zeros(self.chunk), self._zeros(self.chunk)
         tolerance, margin = float(np.float32(tolerance)), float(np.float32(margin))
         per = self.chunk // R
         parts, get = [], self._download
@@ -141,13 +169,17 @@ class GoalPoseSolver(_ChainTool):
             n = min(per, N - first)
             sl = slice(first, first + n)
             self.load(q0[sl], targets[sl], obstacles[sl], seeds[sl])
-            self.launch(n, R, prm, tolerance, margin)
+            if og is not None:      # the chunk's goals, [n][9] or [n][3] rows packed at the front of the buffer
+                self.goals.view(-1)[:og.goals[sl].size].copy_(torch.from_numpy(np.ascontiguousarray(og.goals[sl]).reshape(-1)))
+            self.launch(n, R, prm, tolerance, margin, mode=mode, pose=pose)
             E = n * R
             cell = get(self.cell, E, n, R) if self.has_cell else np.full((n, R), np.inf, np.float32)
             probe = get(self.probe, E, n, R, 5)
+            more = () if og is None else (get(self.angle, E, n, R), get(self.merit, E, n, R))
             parts.append(gather_goal_poses(get(self.choice, n), get(self.cls, n), get(self.q, E, n, R, A), get(self.residual, E, n, R),
-                                           probe[:, :, 3], probe[:, :, 4], cell, get(self.distance, E, n, R), np.float32(tolerance)))
-        return GoalPoses(*[np.concatenate([getattr(p, f) for p in parts]) for f in GoalPoses._fields])
+                                           probe[:, :, 3], probe[:, :, 4], cell, get(self.distance, E, n, R), np.float32(tolerance),
+                                           *more))
+        return concatenate_goal_poses(parts)
 
 
 class JointPathChecker(_ChainTool):

@@ -1131,8 +1131,10 @@ extern "C" int naf_chain_env_rollout_step(naf_chain_env_t* h, float* env_state, 
 // reads back only what it wrote. Joints behind the end-effector frame are not walked: their columns are 0.
 
 // walks joints 0 .. ee_frame - 1 at the joint values q; STORE: a_m | p_m to ax[(m * 6 + k) * 64]; returns the end effector in ee
-template <bool STORE>
-__device__ static inline void ik_walk(const float* __restrict__ model, int n_joints, const float* q, float* ax, float* ee) {
+// and, with ROT, the end frame's rotation R_ee in rot[9], row-major
+template <bool STORE, bool ROT = false>
+__device__ static inline void ik_walk(const float* __restrict__ model, int n_joints, const float* q, float* ax, float* ee,
+                                      float* rot = nullptr) {
     Frame F = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
     for (int m = 0; m < n_joints; ++m) {
         const float* j = model + CH_HDR + m * CH_JNT;
@@ -1186,6 +1188,11 @@ __device__ static inline void ik_walk(const float* __restrict__ model, int n_joi
     ee[0] = F.px + F.r00 * model[5] + F.r01 * model[6] + F.r02 * model[7];
     ee[1] = F.py + F.r10 * model[5] + F.r11 * model[6] + F.r12 * model[7];
     ee[2] = F.pz + F.r20 * model[5] + F.r21 * model[6] + F.r22 * model[7];
+    if constexpr (ROT) {
+        rot[0] = F.r00; rot[1] = F.r01; rot[2] = F.r02;
+        rot[3] = F.r10; rot[4] = F.r11; rot[5] = F.r12;
+        rot[6] = F.r20; rot[7] = F.r21; rot[8] = F.r22;
+    }
 }
 
 // Jacobian column of joint m from its LDS record: a x (ee - p), or a for a prismatic joint
@@ -1347,6 +1354,253 @@ extern "C" int naf_chain_ik_select(naf_chain_env_t* h, const float* q_out, const
         q_out, q_start_dev, residual_out, probe_dev, cell_dev, N, R, h->A, tolerance, margin, choice_out, class_out, joint_distance_out);
     NAF_CHECK_LAUNCH();
     return NAF_OK;
+}
+
+// ---- oriented goal poses: damped least squares on position and end-effector orientation (include/naf_hip.h, "Oriented goal poses")
+// chain_ik_solve_kernel's shape — one lane per candidate, a query's R candidates in adjacent lanes, one wave per workgroup, no
+// barrier, the same [m][6][lane] LDS record: a_m is already in it, so the angular rows cost no LDS. The walk also returns R_ee.
+// Per update pass 1 over LDS accumulates the 21 entries of M = J6 J6^T + lam2 I, the L D L^T factorisation and the two
+// substitutions run in registers (every array below is indexed by unrolled loops' compile-time constants only: nothing goes to
+// scratch), pass 2 forms dq_m and max |dq_m|. MODE 0: the goal is R_goal, 1: a direction for the tool axis.
+#define IK_ORIENT_SMALL 1e-6f
+#define IK_PI 3.14159265358979323846f
+
+// index of M's entry (i, j), i <= j, among the 21 of its upper triangle, row by row
+__host__ __device__ constexpr int ik_tri(int i, int j) { return i * 6 - i * (i - 1) / 2 + (j - i); }
+
+// the angular error e_w of the end frame's rotation rot[9] against goal (MODE 0: R_goal[9], MODE 1: d[3]): orientation_error's rule
+template <int MODE>
+__device__ __forceinline__ void ik_orientation_error(const float* rot, const float* goal, const naf_chain_ik_pose_params_t& pp, float* ew) {
+    if constexpr (MODE == 1) {
+        const float t0 = rot[0] * pp.tool_axis[0] + rot[1] * pp.tool_axis[1] + rot[2] * pp.tool_axis[2];
+        const float t1 = rot[3] * pp.tool_axis[0] + rot[4] * pp.tool_axis[1] + rot[5] * pp.tool_axis[2];
+        const float t2 = rot[6] * pp.tool_axis[0] + rot[7] * pp.tool_axis[1] + rot[8] * pp.tool_axis[2];
+        const float x0 = t1 * goal[2] - t2 * goal[1], x1 = t2 * goal[0] - t0 * goal[2], x2 = t0 * goal[1] - t1 * goal[0];
+        const float nx = sqrtf(x0 * x0 + x1 * x1 + x2 * x2);
+        const float c = t0 * goal[0] + t1 * goal[1] + t2 * goal[2];
+        if (nx <= IK_ORIENT_SMALL) {
+            if (c > 0.f) {
+                ew[0] = x0; ew[1] = x1; ew[2] = x2;
+            } else {      // antiparallel: half a turn about R_ee tool_normal
+                ew[0] = IK_PI * (rot[0] * pp.tool_normal[0] + rot[1] * pp.tool_normal[1] + rot[2] * pp.tool_normal[2]);
+                ew[1] = IK_PI * (rot[3] * pp.tool_normal[0] + rot[4] * pp.tool_normal[1] + rot[5] * pp.tool_normal[2]);
+                ew[2] = IK_PI * (rot[6] * pp.tool_normal[0] + rot[7] * pp.tool_normal[1] + rot[8] * pp.tool_normal[2]);
+            }
+        } else {
+            const float s = atan2f(nx, c) / nx;
+            ew[0] = x0 * s; ew[1] = x1 * s; ew[2] = x2 * s;
+        }
+    } else {
+        // E = R_goal R_ee^T
+        const float e00 = goal[0] * rot[0] + goal[1] * rot[1] + goal[2] * rot[2];
+        const float e01 = goal[0] * rot[3] + goal[1] * rot[4] + goal[2] * rot[5];
+        const float e02 = goal[0] * rot[6] + goal[1] * rot[7] + goal[2] * rot[8];
+        const float e10 = goal[3] * rot[0] + goal[4] * rot[1] + goal[5] * rot[2];
+        const float e11 = goal[3] * rot[3] + goal[4] * rot[4] + goal[5] * rot[5];
+        const float e12 = goal[3] * rot[6] + goal[4] * rot[7] + goal[5] * rot[8];
+        const float e20 = goal[6] * rot[0] + goal[7] * rot[1] + goal[8] * rot[2];
+        const float e21 = goal[6] * rot[3] + goal[7] * rot[4] + goal[8] * rot[5];
+        const float e22 = goal[6] * rot[6] + goal[7] * rot[7] + goal[8] * rot[8];
+        const float tr = e00 + e11 + e22;
+        float x, y, z, w;      // the quaternion of E by the largest-of-four rule, up to a positive factor
+        if (tr >= e00 && tr >= e11 && tr >= e22) {
+            x = e21 - e12; y = e02 - e20; z = e10 - e01; w = 1.f + tr;
+        } else if (e00 >= e11 && e00 >= e22) {
+            x = 1.f + e00 - e11 - e22; y = e01 + e10; z = e02 + e20; w = e21 - e12;
+        } else if (e11 >= e22) {
+            x = e01 + e10; y = 1.f + e11 - e00 - e22; z = e12 + e21; w = e02 - e20;
+        } else {
+            x = e02 + e20; y = e12 + e21; z = 1.f + e22 - e00 - e11; w = e10 - e01;
+        }
+        const float len = sqrtf(x * x + y * y + z * z + w * w);
+        x /= len; y /= len; z /= len; w /= len;
+        if (w < 0.f) {
+            x = -x; y = -y; z = -z; w = -w;
+        }
+        const float nv = sqrtf(x * x + y * y + z * z);
+        const float s = nv <= IK_ORIENT_SMALL ? 2.f : 2.f * atan2f(nv, w) / nv;
+        ew[0] = x * s; ew[1] = y * s; ew[2] = z * s;
+    }
+}
+
+// column m of J6 from the joint's LDS record: [a x (ee - p) ; L a] revolute, [a ; 0] prismatic
+__device__ __forceinline__ void ik_column6(const float* __restrict__ model, int m, const float* ax, const float* ee, float weight, float* c) {
+    const float* w = ax + m * 6 * 64;
+    const float a0 = w[0], a1 = w[64], a2 = w[128];
+    if (model[CH_HDR + m * CH_JNT + 15] != 0.f) {
+        c[0] = a0; c[1] = a1; c[2] = a2;
+        c[3] = 0.f; c[4] = 0.f; c[5] = 0.f;
+    } else {
+        const float d0 = ee[0] - w[192], d1 = ee[1] - w[256], d2 = ee[2] - w[320];
+        c[0] = a1 * d2 - a2 * d1;
+        c[1] = a2 * d0 - a0 * d2;
+        c[2] = a0 * d1 - a1 * d0;
+        c[3] = weight * a0; c[4] = weight * a1; c[5] = weight * a2;
+    }
+}
+
+// M y = e for the symmetric positive definite M (its upper triangle, ik_tri) by L D L^T without pivoting: spd6_solve's eliminations
+__device__ __forceinline__ void ik_spd6_solve(const float* M, const float* e, float* y) {
+    float l[36], d[6], r[6], z[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        float v[6];
+#pragma unroll
+        for (int k = 0; k < j; ++k) v[k] = l[j * 6 + k] * d[k];
+        float s = M[ik_tri(j, j)];
+#pragma unroll
+        for (int k = 0; k < j; ++k) s -= l[j * 6 + k] * v[k];
+        d[j] = s;
+        r[j] = 1.f / s;
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            float t = M[ik_tri(j, i)];
+#pragma unroll
+            for (int k = 0; k < j; ++k) t -= l[i * 6 + k] * v[k];
+            l[i * 6 + j] = t * r[j];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        float s = e[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) s -= l[i * 6 + k] * z[k];
+        z[i] = s;
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        float s = z[i] * r[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; ++k) s -= l[k * 6 + i] * y[k];
+        y[i] = s;
+    }
+}
+
+// MODE 0: goals [N][9] = R_goal, 1: goals [N][3] = d. REC: iters_out as chain_ik_solve_kernel's
+template <int MODE, bool REC>
+__global__ void __launch_bounds__(64)
+chain_ik_pose_kernel(const float* __restrict__ model, const float* __restrict__ targets, const float* __restrict__ goals,
+                     const float* __restrict__ q_start, const float* __restrict__ seeds, int N, int R, int A,
+                     const naf_chain_ik_params_t prm, const naf_chain_ik_pose_params_t pp, float* q_out,
+                     float* __restrict__ residual_out, float* __restrict__ angle_out, float* __restrict__ merit_out,
+                     float* __restrict__ iters_out) {
+    extern __shared__ __attribute__((aligned(16))) float ch_lds[];
+    constexpr int GOAL = MODE == 0 ? 9 : 3;
+    const int64_t total = (int64_t)N * R;
+    const int64_t cand = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (cand >= total) return;      // (one wave per workgroup and no barrier below)
+    const int64_t n = cand / R;
+    const int r = (int)(cand - n * R);
+    const int n_joints = (int)model[4];
+    float* ax = ch_lds + threadIdx.x;
+    float* q = q_out + cand * A;
+    const float* src = r == 0 ? q_start + n * A : seeds + cand * A;
+    for (int m = 0; m < A; ++m) {
+        const float v = src[m];
+        q[m] = v;
+        if constexpr (REC) iters_out[cand * A + m] = v;
+    }
+    const float g0 = targets[n * 3], g1 = targets[n * 3 + 1], g2 = targets[n * 3 + 2];
+    float goal[GOAL];
+#pragma unroll
+    for (int k = 0; k < GOAL; ++k) goal[k] = goals[n * GOAL + k];
+    float ee[3], rot[9], ew[3];
+    for (int k = 0; k < prm.iterations; ++k) {
+        ik_walk<true, true>(model, n_joints, q, ax, ee, rot);
+        float e[6];
+        e[0] = g0 - ee[0]; e[1] = g1 - ee[1]; e[2] = g2 - ee[2];
+        const float len = sqrtf(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+        if (len > prm.e_max) {
+            const float s = prm.e_max / len;
+            e[0] *= s; e[1] *= s; e[2] *= s;
+        }
+        ik_orientation_error<MODE>(rot, goal, pp, ew);
+        const float wlen = sqrtf(ew[0] * ew[0] + ew[1] * ew[1] + ew[2] * ew[2]);
+        const float ws = wlen > pp.w_max ? pp.w_max / wlen : 1.f;
+        e[3] = pp.weight * (ew[0] * ws); e[4] = pp.weight * (ew[1] * ws); e[5] = pp.weight * (ew[2] * ws);
+        // pass 1 over LDS: M = sum c c^T + lam2 I, the 21 entries of its upper triangle
+        float M[21];
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = i; j < 6; ++j) M[ik_tri(i, j)] = i == j ? prm.lam2 : 0.f;
+        for (int m = 0; m < n_joints; ++m) {
+            float c[6];
+            ik_column6(model, m, ax, ee, pp.weight, c);
+#pragma unroll
+            for (int i = 0; i < 6; ++i)
+#pragma unroll
+                for (int j = i; j < 6; ++j) M[ik_tri(i, j)] += c[i] * c[j];
+        }
+        float y[6];
+        ik_spd6_solve(M, e, y);
+        // pass 2: dq_m = c_m . y, kept in the record's first float, and max |dq_m|
+        float big = 0.f;
+        for (int m = 0; m < n_joints; ++m) {
+            float c[6];
+            ik_column6(model, m, ax, ee, pp.weight, c);
+            const float dq = c[0] * y[0] + c[1] * y[1] + c[2] * y[2] + c[3] * y[3] + c[4] * y[4] + c[5] * y[5];
+            ax[m * 6 * 64] = dq;
+            big = fmaxf(big, fabsf(dq));
+        }
+        const float scale = big > prm.dq_max ? prm.dq_max / big : 1.f;
+        for (int m = 0; m < A; ++m) {
+            const float* j = model + CH_HDR + m * CH_JNT;
+            float v = q[m];
+            if (m < n_joints) v += scale * ax[m * 6 * 64];
+            if (j[16] != 0.f) {      // the position limits, as a step applies them
+                if (v > j[18]) v = j[18];
+                if (v < j[17]) v = j[17];
+            }
+            q[m] = v;
+            if constexpr (REC) iters_out[((int64_t)(k + 1) * total + cand) * A + m] = v;
+        }
+    }
+    ik_walk<false, true>(model, n_joints, q, ax, ee, rot);
+    const float e0 = g0 - ee[0], e1 = g1 - ee[1], e2 = g2 - ee[2];
+    const float residual = sqrtf(e0 * e0 + e1 * e1 + e2 * e2);
+    ik_orientation_error<MODE>(rot, goal, pp, ew);
+    const float angle = sqrtf(ew[0] * ew[0] + ew[1] * ew[1] + ew[2] * ew[2]);
+    residual_out[cand] = residual;
+    angle_out[cand] = angle;
+    merit_out[cand] = fmaxf(residual, angle * pp.angle_length);
+}
+
+template <int MODE, bool REC, typename... Args>
+static int ch_ik_pose_launch(unsigned grid, size_t lds, void* stream, Args... args) {
+    const int rc = ch_raise<chain_ik_pose_kernel<MODE, REC>>();
+    if (rc != NAF_OK) return rc;
+    chain_ik_pose_kernel<MODE, REC><<<grid, 64, lds, (hipStream_t)stream>>>(args...);
+    NAF_CHECK_LAUNCH();
+    return NAF_OK;
+}
+
+extern "C" int naf_chain_ik_solve_pose(naf_chain_env_t* h, const float* targets_dev, const float* goals_dev, int mode,
+                                       const float* q_start_dev, const float* seeds_dev, int N, int R, naf_chain_ik_params_t params,
+                                       naf_chain_ik_pose_params_t pose_params, float* q_out, float* residual_out, float* angle_out,
+                                       float* merit_out, float* iters_out, void* stream) {
+    if (!h || !targets_dev || !goals_dev || !q_start_dev || !seeds_dev || !q_out || !residual_out || !angle_out || !merit_out ||
+        !ch_ik_counts_ok(N, R) || (mode != 0 && mode != 1))
+        return NAF_ERR_ARG;
+    const auto positive = [](float v) { return std::isfinite(v) && v > 0.f; };
+    if (params.iterations < 1 || !positive(params.lam2) || !positive(params.e_max) || !positive(params.dq_max) ||
+        !positive(pose_params.weight) || !positive(pose_params.w_max) || !positive(pose_params.angle_length))
+        return NAF_ERR_ARG;
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(pose_params.tool_axis[k]) || !std::isfinite(pose_params.tool_normal[k])) return NAF_ERR_ARG;
+    const size_t lds = (size_t)std::max(h->ee_frame, 1) * 6 * 64 * sizeof(float);
+    if (lds > CH_MAX_DYN_LDS) return NAF_CHAIN_ERR_LDS;
+    const unsigned grid = (unsigned)(((int64_t)N * R + 63) / 64);
+    const auto go = [&](auto launch) {
+        return launch(grid, lds, stream, h->model_dev, targets_dev, goals_dev, q_start_dev, seeds_dev, N, R, h->A, params, pose_params,
+                      q_out, residual_out, angle_out, merit_out, iters_out);
+    };
+    // the dynamic LDS (1536 bytes per walked joint) may exceed the 64 KB a kernel gets unasked: the launched instantiation is raised
+    if (mode == 0)
+        return iters_out ? go([](auto... a) { return ch_ik_pose_launch<0, true>(a...); })
+                         : go([](auto... a) { return ch_ik_pose_launch<0, false>(a...); });
+    return iters_out ? go([](auto... a) { return ch_ik_pose_launch<1, true>(a...); })
+                     : go([](auto... a) { return ch_ik_pose_launch<1, false>(a...); });
 }
 
 // ---- joint paths: the sampled collision check of start -> via -> goal polylines (include/naf_hip.h, "Joint paths") ---------------

@@ -21,6 +21,8 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .orientation import (ORIENT_AXIS, ORIENT_FULL, OrientationGoal, PoseGoalRule, orientation_error,  # noqa: F401
+                          orientation_goal, quaternion_matrix, spd6_solve, tool_normal_of)
 from .urdf_chain import (DT, OBSTACLE_RADIUS, PRISMATIC, SCENE_TRIES, TARGET_THRESHOLD, ChainModel, axis_rotation, compile_chain,
                          load_urdf)
 
@@ -152,7 +154,7 @@ class Trace(NamedTuple):
     cell_margins: np.ndarray          # [..., frames]: the workcell clearance; NaN: no step
 
 
-class KinematicEnvironment:
+class KinematicEnvironment(PoseGoalRule):
 
     def __init__(self, model: ChainModel, target_position: Sequence[float], obstacle_position: Sequence[float],
                  obstacle_radius: float = OBSTACLE_RADIUS, target_range: Optional[Sequence[float]] = None,
@@ -334,6 +336,9 @@ class KinematicEnvironment:
         d = g - self.end_effector(q)
         return q, np.sqrt(np.sum(d * d, axis=-1))
 
+    # Goal poses with an end-effector orientation — end_effector_frame, jacobian6, ik_pose_step, pose_errors, solve_ik_pose — are
+    # this class's too: environment/orientation.py (PoseGoalRule) states them, beside orientation_error and spd6_solve.
+
     def get_state(self) -> np.ndarray:
         A = self.n
         out = np.empty(2 * A + 9)
@@ -476,8 +481,8 @@ def select_goal_pose(residual, joint_distance, clearance, self_clearance, cell_c
     return best_r, best_c
 
 
-class GoalPoses(NamedTuple):
-    """Goal poses of N queries (ManipulatorFramework.solve_goal_poses): per query the restart the selection rule chose."""
+class _GoalPoseFields(NamedTuple):
+    """the ten members of GoalPoses' tuple"""
     reachable: np.ndarray             # [N] bool: a restart converged (|target - end effector| <= tolerance)
     free: np.ndarray                  # [N] bool: ... and its pose keeps clearance_margin from obstacle, arm and workcell
     joint_positions: np.ndarray       # [N][A]: the chosen pose, entry m = involved_joints[m] (not a goal pose where not reachable)
@@ -488,6 +493,19 @@ class GoalPoses(NamedTuple):
     joint_distance: np.ndarray        # [N]: max_m |pose_m - start pose_m|, the straight joint-space distance in the max-norm
     restart: np.ndarray               # [N] int: the chosen restart; 0 is the one seeded with the start pose
     converged_restarts: np.ndarray    # [N] int: how many of the restarts converged
+
+
+class GoalPoses(_GoalPoseFields):
+    """Goal poses of N queries (ManipulatorFramework.solve_goal_poses): per query the restart the selection rule chose. With an
+    orientation goal `angle_residual` is filled, a candidate is converged iff merit = max(residual, angle_residual tolerance /
+    orientation_tolerance) <= tolerance, and `reachable` / `converged_restarts` count that. It is an attribute behind the tuple, as
+    JointPaths' later ones are: the tuple's ten fields are what they were and every loop over them runs as before. _replace keeps it."""
+    angle_residual: Optional[np.ndarray] = None      # [N]: |e_w| at the chosen pose, radians; None without an orientation goal
+
+    def _replace(self, **kw):
+        out = super()._replace(**kw)
+        out.__dict__.update(self.__dict__)
+        return out
 
 
 def ik_restarts_ok(restarts) -> bool:
@@ -507,32 +525,56 @@ def ik_seeds(model: ChainModel, n_queries: int, restarts: int, seed: int) -> np.
     return out
 
 
-def gather_goal_poses(choice, cls, q, residual, clearance, self_clearance, cell_clearance, joint_distance, tolerance) -> GoalPoses:
-    """GoalPoses from the per-candidate arrays [N][R](, [A]) and the selection (choice[N], class[N])"""
+def gather_goal_poses(choice, cls, q, residual, clearance, self_clearance, cell_clearance, joint_distance, tolerance, angle=None,
+                      merit=None) -> GoalPoses:
+    """GoalPoses from the per-candidate arrays [N][R](, [A]) and the selection (choice[N], class[N]); with an orientation goal
+    angle[N][R] and merit[N][R] too: converged_restarts then counts merit <= tolerance"""
     pick = np.asarray(choice, np.int64)[:, None]
     take = lambda a: np.take_along_axis(np.asarray(a), pick, axis=1)[:, 0]      # noqa: E731
     cls = np.asarray(cls)
-    return GoalPoses(cls <= 1, cls == 0, np.take_along_axis(np.asarray(q), pick[:, :, None], axis=1)[:, 0], take(residual),
-                     take(clearance), take(self_clearance), take(cell_clearance), take(joint_distance), pick[:, 0],
-                     np.sum(np.asarray(residual) <= tolerance, axis=1))
+    out = GoalPoses(cls <= 1, cls == 0, np.take_along_axis(np.asarray(q), pick[:, :, None], axis=1)[:, 0], take(residual),
+                    take(clearance), take(self_clearance), take(cell_clearance), take(joint_distance), pick[:, 0],
+                    np.sum(np.asarray(residual if merit is None else merit) <= tolerance, axis=1))
+    if angle is not None:
+        out.angle_residual = take(angle)
+    return out
+
+
+def concatenate_goal_poses(parts: Sequence[GoalPoses]) -> GoalPoses:
+    """the GoalPoses of the chunks of one call, in order"""
+    out = GoalPoses(*[np.concatenate([getattr(p, f) for p in parts]) for f in GoalPoses._fields])
+    if parts[0].angle_residual is not None:
+        out.angle_residual = np.concatenate([p.angle_residual for p in parts])
+    return out
 
 
 def goal_poses_host(twin: KinematicEnvironment, q0, targets, obstacles, restarts: int = 8, iterations: int = 32,
-                    tolerance: float = 1e-3, margin: float = 0.0, seed: int = 0, **constants) -> GoalPoses:
+                    tolerance: float = 1e-3, margin: float = 0.0, seed: int = 0, orientations=None, approach_directions=None,
+                    tool_axis=(0.0, 0.0, 1.0), orientation_tolerance: float = 1e-3, orientation_weight: Optional[float] = None,
+                    **constants) -> GoalPoses:
     """solve_goal_poses through the twin alone, under the device's rule and on the values the device is given: start poses,
-    targets, obstacles and seeds rounded to float32, the iteration and the clearances in float64, joint_distance in float32."""
+    targets, obstacles and seeds rounded to float32, the iteration and the clearances in float64, joint_distance in float32.
+    With orientations or approach_directions (orientation_goal) the iteration is solve_ik_pose on the float32 goal the device is
+    given, and the selection is fed merit in the place of residual."""
     r32 = lambda a: np.asarray(a, np.float64).astype(np.float32).astype(np.float64)      # noqa: E731
     q0, targets, obstacles = r32(q0), r32(targets), r32(obstacles)
     N, R = len(q0), int(restarts)
     seeds = ik_seeds(twin.model, N, R, seed).astype(np.float64)
     seeds[:, 0] = q0
-    q, residual = twin.solve_ik(targets[:, None, :], seeds, iterations=iterations, **constants)
+    og = orientation_goal(N, orientations, approach_directions, tool_axis, tolerance, orientation_tolerance)
+    angle = merit = None
+    if og is None:
+        q, residual = twin.solve_ik(targets[:, None, :], seeds, iterations=iterations, **constants)
+    else:
+        q, residual, angle, merit = twin.solve_ik_pose(
+            targets[:, None, :], og.mode, og.goals.astype(np.float64)[:, None, :], seeds, og.angle_length, weight=orientation_weight,
+            tool_axis=og.tool_axis.astype(np.float64), tool_normal=og.tool_normal.astype(np.float64), iterations=iterations, **constants)
     obstacle = np.broadcast_to(obstacles[:, None, :], q.shape[:-1] + (3,))
     clear = twin.clearance(q, obstacle) - twin.obstacle_radius
     self_clear, cell_clear = twin.self_clearance(q) + np.zeros(clear.shape), twin.cell_clearance(q) + np.zeros(clear.shape)
     jd = joint_distance32(q, q0[:, None, :])
-    choice, cls = select_goal_pose(residual, jd, clear, self_clear, cell_clear, tolerance, margin)
-    return gather_goal_poses(choice, cls, q, residual, clear, self_clear, cell_clear, jd, tolerance)
+    choice, cls = select_goal_pose(residual if merit is None else merit, jd, clear, self_clear, cell_clear, tolerance, margin)
+    return gather_goal_poses(choice, cls, q, residual, clear, self_clear, cell_clear, jd, tolerance, angle, merit)
 
 
 # ---- joint paths: the sampled collision check of start -> via -> goal polylines (include/naf_hip.h, "Joint paths") ----------------

@@ -255,7 +255,8 @@ class ManipulatorFramework:
 
     def reach_targets(self, targets, obstacles=None, initial_joint_positions=None, frames: int = 400, noise_scale: float = 0.0,
                       n_envs: Optional[int] = None, trajectories: bool = True, goal_poses: bool = False, joint_paths: bool = False,
-                      certify: bool = False, roadmap: int = 0, shortcut: int = 0):
+                      certify: bool = False, roadmap: int = 0, shortcut: int = 0, orientations=None, approach_directions=None, tool_axis=(0.0, 0.0, 1.0),
+                      orientation_tolerance: float = 1e-3, orientation_weight: Optional[float] = None):
         """Roll the trained policy out to GIVEN targets (kinematic environment only; on the device, thousands at once): query i
         starts at initial_joint_positions[i], with target targets[i] and obstacle obstacles[i], and runs until it reaches the
         target, touches the obstacle, itself or the workcell, or has taken `frames` steps. A query whose start pose is already in contact or at
@@ -283,7 +284,11 @@ class ManipulatorFramework:
         roadmap=M (with joint_paths, not with certify): the paths are plan_joint_paths(roadmap=M)'s; a query whose path is a
         'roadmap' polyline has its planned_ratio over that polyline's length.
         shortcut=W (with roadmap): the paths are plan_joint_paths(roadmap=M, shortcut=W)'s, and planned_ratio divides by the
-        shortened length."""
+        shortened length.
+        orientations / approach_directions / tool_axis / orientation_tolerance / orientation_weight (with goal_poses or
+        joint_paths): the goal poses are solve_goal_poses()'s with that orientation goal, and the paths lead to them. The
+        rollout's own outcome stays positional — policy, observation and reward know no orientation: 'reached' says that the end
+        effector came within the target threshold, whichever way it pointed."""
         self._require_env_and_agent()
         planner = self._kinematic_planner('reach_targets', 'given-scene reset')
         if getattr(self.naf_agent, 'world_size', 1) > 1:
@@ -291,7 +296,9 @@ class ManipulatorFramework:
         if n_envs is not None and not _positive_int(n_envs):
             raise InvalidNAFAgentParameter('Number of environments received is not a positive integer')
         return planner.reach_targets(self.naf_agent, targets, obstacles, initial_joint_positions, frames, noise_scale, n_envs,
-                                     trajectories, goal_poses, joint_paths, certify, roadmap, shortcut)
+                                     trajectories, goal_poses, joint_paths, certify, roadmap, shortcut,
+                                     dict(orientations=orientations, approach_directions=approach_directions, tool_axis=tool_axis,
+                                          orientation_tolerance=orientation_tolerance, orientation_weight=orientation_weight))
 
     @functools.cached_property
     def arm_planner(self) -> ArmPlanner:
@@ -309,7 +316,9 @@ class ManipulatorFramework:
 
     def plan_joint_paths(self, targets=None, obstacles=None, initial_joint_positions=None, goal_joint_positions=None,
                          candidates: int = 16, resolution: float = 0.02, clearance_margin: float = 0.0, seed: int = 0,
-                         on_device: Optional[bool] = None, certify: bool = False, roadmap: int = 0, shortcut: int = 0):
+                         on_device: Optional[bool] = None, certify: bool = False, roadmap: int = 0, shortcut: int = 0,
+                         orientations=None, approach_directions=None, tool_axis=(0.0, 0.0, 1.0),
+                         orientation_tolerance: float = 1e-3, orientation_weight: Optional[float] = None):
         """Collision-checked joint paths from start poses to goal poses (kinematic environment only; needs no agent): per query
         `candidates` joint-space polylines start -> via -> goal — candidate 0 through the midpoint, the straight line, the others
         through vias drawn around it from `seed` (environment/kinematic.py: path_vias) — are SAMPLED at poses at most `resolution`
@@ -320,6 +329,8 @@ class ManipulatorFramework:
           targets              : [N][3] or [3]: the goal poses are solve_goal_poses(targets, ...) with its defaults and `seed`;
                                  queries without a reachable pose get outcome 'goal' and NaN numbers
           goal_joint_positions : [N][A] or [A]: the goal poses themselves. Exactly one of the two is given.
+          orientations, approach_directions, tool_axis, orientation_tolerance, orientation_weight : with targets, the orientation
+                                 goal of solve_goal_poses(); refused with goal_joint_positions
           obstacles, initial_joint_positions : as reach_targets() takes them
           candidates           : 1 .. 64
           on_device            : None: the device when there is one; False: the float64 host twin under the same rule (slow)
@@ -359,7 +370,9 @@ class ManipulatorFramework:
         min_self_clearance, min_cell_clearance, straight_first_blocked, sample_step, samples; waypoints(n) resamples the paths."""
         planner = self._kinematic_planner('plan_joint_paths', 'chain model to solve on')
         return planner.plan_joint_paths(targets, obstacles, initial_joint_positions, goal_joint_positions, candidates, resolution,
-                                        clearance_margin, seed, on_device, certify, roadmap, shortcut)
+                                        clearance_margin, seed, on_device, certify, roadmap, shortcut,
+                                        dict(orientations=orientations, approach_directions=approach_directions, tool_axis=tool_axis,
+                                             orientation_tolerance=orientation_tolerance, orientation_weight=orientation_weight))
 
     def demonstrate_joint_paths(self, paths, targets=None, obstacles=None, speed: float = 1.0, frames: int = 400,
                                 keep_contact: bool = False, on_device: Optional[bool] = None, polylines: bool = False):
@@ -426,7 +439,9 @@ class ManipulatorFramework:
         return self.naf_agent.add_demonstrations(demos)
 
     def solve_goal_poses(self, targets, obstacles=None, initial_joint_positions=None, restarts: int = 8, iterations: int = 32,
-                         tolerance: float = 1e-3, clearance_margin: float = 0.0, seed: int = 0, on_device: Optional[bool] = None):
+                         tolerance: float = 1e-3, clearance_margin: float = 0.0, seed: int = 0, on_device: Optional[bool] = None,
+                         orientations=None, approach_directions=None, tool_axis=(0.0, 0.0, 1.0),
+                         orientation_tolerance: float = 1e-3, orientation_weight: Optional[float] = None):
         """Joint values that put the end effector on GIVEN targets (kinematic environment only; needs no agent): per query a
         damped least-squares iteration on the end effector's positional Jacobian from `restarts` seeds — the start pose and
         restarts - 1 poses drawn uniformly inside the limits from `seed` — for `iterations` updates each, then the choice among
@@ -437,11 +452,24 @@ class ManipulatorFramework:
           restarts    : a power of two, 1 .. 64
           on_device   : None: the device when there is one; False: the float64 host twin under the same rule (slow: a chain walk
                         per update and candidate)
+          orientations        : [N][4], or [4] for all queries: the end effector's orientation in the world as a quaternion
+                                (x, y, z, w), the convention of a URDF / PyBullet link orientation (it is scaled to unit length)
+          approach_directions : [N][3], or [3] for all queries: a direction in the world that tool_axis, a direction in the
+                                end-effector frame (default its z axis), is to point along — [0, 0, -1] approaches from above; the
+                                roll about it is free. At most one of the two is given; neither: position only, as before.
+          orientation_tolerance : radians; with an orientation goal a pose is converged iff |target - end effector| <= tolerance
+                                and the angle left to the goal <= orientation_tolerance
+          orientation_weight  : metres per radian, how a radian of angular error weighs against a metre (None: 0.25 reach)
+        With an orientation goal the iteration runs on the 6-row Jacobian of position and orientation (environment/kinematic.py:
+        orientation_error, ik_pose_step), and the result's angle_residual [N] holds the angle left at the chosen pose.
         Returns environment.kinematic.GoalPoses, arrays over the queries: reachable, free, joint_positions [N][A], residual,
-        clearance, self_clearance, cell_clearance, joint_distance, restart, converged_restarts."""
+        clearance, self_clearance, cell_clearance, joint_distance, restart, converged_restarts; angle_residual is None without an
+        orientation goal."""
         planner = self._kinematic_planner('solve_goal_poses', 'chain model to solve on')
         return planner.solve_goal_poses(targets, obstacles, initial_joint_positions, restarts, iterations, tolerance, clearance_margin,
-                                        seed, on_device)
+                                        seed, on_device,
+                                        dict(orientations=orientations, approach_directions=approach_directions, tool_axis=tool_axis,
+                                             orientation_tolerance=orientation_tolerance, orientation_weight=orientation_weight))
 
     # ---- environment ------------------------------------------------------------------------------------------------
     def initialize_environment(self, manipulator_file: str, endeffector_index: int, fixed_joints: List[int],
