@@ -30,6 +30,9 @@ MARKS = {
     "bb_layer1_bwd_finish": ["entry", "loads, folds, dW1 / slab sums, norm partial"],
     "adam_polyak": ["entry", "norm folded + update"],
 }
+# bb_layer1_bwd_finish, raw slots 2 .. 6 (csrc/big_batch.hip, BF_TL): row 0 is the FIRST layer-1 workgroup, row 1 the FIRST slab
+# workgroup (not the launch's last one, whose entry and exit are slots 0 / 1 above)
+FINISH_PHASES = ["entry", "last load issued", "loads landed", "results stored", "norm partial stored"]
 
 
 def main():
@@ -39,6 +42,7 @@ def main():
     ap.add_argument("--updates", type=int, default=64)
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=1, help="average the marks of this many replays")
+    ap.add_argument("--finish-form", type=int, default=0, help="form of the finish launch: 0 the library's choice, 1 general, 2 small")
     args = ap.parse_args()
     if "NAF_TIMELINE" not in os.environ.get("NAF_BUILD_DEFINES", ""):
         raise SystemExit("build with NAF_BUILD_DEFINES=-DNAF_TIMELINE")
@@ -54,7 +58,7 @@ def main():
     dev = torch.device("cuda", 0)
     S, A = (23, 7) if args.robot == "panda" else (21, 6)
     B, N = args.batch, 200_000
-    L = Learner(S, A, 256, B, 1e-3, 1e-3, 0.99, dev, p_mode=_lib.P_HADAMARD)
+    L = Learner(S, A, 256, B, 1e-3, 1e-3, 0.99, dev, p_mode=_lib.P_HADAMARD, _finish_form=args.finish_form)
     sd = reference_init_state_dict(S, A, 256, seed=0)
     L.load_params(0, sd)
     L.load_params(1, sd)
@@ -122,6 +126,15 @@ def main():
                 steps = " | ".join(f"{MARKS[name][i]} +{r[i] - r[i - 1]:.2f}" for i in range(1, n))
             print(f"    {tag:16s} entry {r[0]:7.2f} | {steps}")
         prev_end = end
+        if name == "bb_layer1_bwd_finish":
+            form = {0: f"library's choice ({'small' if L.finish_small else 'general'})", 1: "general", 2: "small"}[args.finish_form]
+            print(f"    form: {form}")
+            out["kernels"][name]["form"] = form
+            for w, tag in ((0, "first layer-1 block"), (1, "first slab block")):
+                r = [round((raw[name][w][2 + i] - t0) / 100.0, 2) for i in range(len(FINISH_PHASES))]
+                out["kernels"][name][tag] = r
+                steps = " | ".join(f"{FINISH_PHASES[i]} +{r[i] - r[i - 1]:.2f}" for i in range(1, len(r)))
+                print(f"    {tag:19s} entry {r[0]:7.2f} | {steps} | entry -> end {r[-1] - r[0]:.2f}")
         if os.environ.get("NAF_TL_RAW"):      # every slot as written (extra marks placed while investigating a phase)
             for w, tag in ((0, "first"), (1, "last")):
                 print(f"    raw slots ({tag} wg):", [round((t - t0) / 100.0, 2) if t > 0 else None for t in raw[name][w]])

@@ -431,6 +431,19 @@ int naf_bb_layer1_bwd_finish(const float* p_slabs, int K, const float* partials1
                              (the ranges the segments do not cover, at index [workgroups]), -inf where a wait timed out; *step_dev += 1. No naf_xgmi_allreduce_* call follows (where clip_grad_norm_ sits in
                              the reference, naf_algorithm.py:207-210) */,
                              void* stream);
+/* The same launch with its form named (tests and A/B runs; naf_bb_layer1_bwd_finish is form NAF_FINISH_AUTO). The SMALL form holds
+ * 4 p_slabs values per lane and 2 slabs per thread and reads the layer-1 operands through buffer loads; it runs where push is NULL,
+ * merge_total is 0, nb1 <= 16 (B <= 512), nb <= 64 and every segment has n_slabs <= 2, and leaves the very bits the general form
+ * leaves. NAF_FINISH_SMALL on any other shape, or a form that is none of the three: NAF_ERR_ARG, nothing launched. */
+#define NAF_FINISH_AUTO 0
+#define NAF_FINISH_GENERAL 1
+#define NAF_FINISH_SMALL 2
+int naf_bb_layer1_bwd_finish_form(const float* p_slabs, int K, const float* partials1, int nb1, const float* dz2_col_partials, int nb,
+                                  const float* mom, const float* wc, const float* gamma, const float* save_invstd, float* d_W,
+                                  float* d_gamma, float* d_beta, float* d_bias, float* d_bias2, const float* d_gamma2,
+                                  const float* d_beta2, float* sumsq_partials, int32_t* step_dev, int B, int H,
+                                  const naf_bb_slab_seg_t* segs, int n_segs, int* fold_epoch, const naf_xgmi_push_t* push,
+                                  const float* grad_base, size_t merge_total, int form, void* stream);
 
 /* ---- several small f32 GEMMs in one launch (csrc/gemm_bundle.hip) ------------------------------------------- */
 /* C[M][N] = op(A) op(B): A is [M][K] row-major (a_kmajor = 0) or stored transposed [K][M] (a_kmajor = 1), B is

@@ -26,6 +26,7 @@ HEADERS = ["common.h", "head_body.h", "bn_tile.h", "xgmi_dev.h", "adam_body.h", 
 P_HADAMARD, P_MATMUL = 0, 1
 ACTION_TRUNC_INT, ACTION_FLOAT = 0, 1
 NORM_CHUNK = 4096
+FINISH_AUTO, FINISH_GENERAL, FINISH_SMALL = 0, 1, 2      # NAF_FINISH_* (include/naf_hip.h): naf_bb_layer1_bwd_finish_form
 
 
 class NafHipError(RuntimeError):
@@ -230,6 +231,8 @@ _PROTOS = {
     "naf_bb_layer1_bwd_finish_blocks": [_i],
     "naf_bb_layer1_bwd_finish": [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i,
                                  _vp, _i, _vp, _vp, _vp, _sz, _vp],
+    "naf_bb_layer1_bwd_finish_form": [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i,
+                                      _vp, _i, _vp, _vp, _vp, _sz, _i, _vp],
     "naf_gemm_bundle": [_vp, _i, _vp],
     "naf_grad_norm_partials": [_vp, _sz, _vp, _vp, _vp],
     "naf_adam_polyak_fused": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _f, _f, _f, _f, _vp, _f, _sz, _vp],

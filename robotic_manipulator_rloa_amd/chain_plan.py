@@ -160,6 +160,17 @@ def _split_k(lay: NetLayout, Bp: int) -> Tuple[int, int]:
     return ks_w2, ks_wh
 
 
+FINISH_SMALL_NB1, FINISH_SMALL_SLABS = 16, 2      # BF_SMALL_NB1, BF_SMALL_SLABS of csrc/big_batch.hip
+
+
+def finish_small(nb1: int, nb: int, n_slabs, push: bool = False, merge: bool = False) -> bool:
+    """Whether the finish launch of the row-split chain takes its small form when the library chooses (csrc/big_batch.hip,
+    bb_finish_launch, whose rule this restates): no gradient exchange rides on it, at most 16 blocks of the dA1 product (B <= 512),
+    at most 64 statistics blocks of layer 2's bias gradient, at most 2 slabs in every slab segment (n_slabs: one count per segment)."""
+    return (not push and not merge and nb1 <= FINISH_SMALL_NB1 and nb <= 64 and
+            all(n <= FINISH_SMALL_SLABS for n in n_slabs))
+
+
 def plan_chain(state_size: int, action_size: int, layer_size: int, batch_size: int, p_mode: int = _lib.P_HADAMARD,
                world_size: int = 1, fuse: Optional[str] = None, pad_layer: bool = True, force_allreduce: bool = False,
                fold_norm: bool = True, env: Mapping[str, str] = os.environ) -> ChainPlan:

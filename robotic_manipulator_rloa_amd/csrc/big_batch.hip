@@ -343,11 +343,29 @@ __device__ static inline void bb_finish_exchange(const FinishArgs& F, int block,
 // One workgroup (BB_THREADS threads) of the finish work. MERGE: the gradient exchange of data parallel inside this launch
 // (F.merge; a kernel of its own so that the launch of one GPU — and of the separate all-reduce — carries none of its code: with a
 // run-time flag the single-GPU update was 0.25 us slower, A/B on one box).
-template <bool MERGE, bool BIG>
+// SMALL (one GPU, B <= 512: NB1 <= BF_SMALL_NB1 blocks of the dA1 product, at most BF_SMALL_SLABS slabs per segment — bb_finish_launch):
+// the same sums in the same order from the loads that exist at these sizes — 4 p_slabs values per lane instead of 16, 2 slabs
+// instead of 8 — and the layer-1 path's loads as buffer loads (common.h: naf_buf_*): the column's base in the resource, one lane
+// offset per array. A block past NB1 lies past the resource's end and reads as 0; what it adds to a sum is predicated as before.
+#define BF_SMALL_NB1 16
+#define BF_SMALL_SLABS 2
+// timeline marks 2 .. 6 of the FIRST layer-1 workgroup (row 0) and the FIRST slab workgroup (row 1): entry | last load issued |
+// loads landed (the build with the marks waits for them there) | results stored | norm partial stored
+// (without the marks: no statement at all — the empty `do { } while (0)` of NAF_TL_FL in this body moved the merge kernels' sums)
+#ifdef NAF_TIMELINE
+#define BF_TL(slot) NAF_TL_FL(g_tl_bb, NAF_TL_BB_FINISH, slot, block == 0, block == F.slabs.n_finish_blocks)
+#define BF_TL_LANDED(slot) do { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); BF_TL(slot); } while (0)
+#else
+#define BF_TL(slot) ((void)0)
+#define BF_TL_LANDED(slot) ((void)0)
+#endif
+__device__ __forceinline__ static float2 bb_f2(naf_f32x2 v) { return make_float2(v.x, v.y); }
+template <bool MERGE, bool BIG, bool SMALL = false>
 __device__ static inline void bb_finish_block(const FinishArgs& F, int block, int tid, float* sQ, float (*sP)[2][32]) {
     // (no FP contraction: the gradient of a build rounds the same way whatever the optimizer makes of this body)
 #pragma clang fp contract(off)
     float sq = 0.f;
+    BF_TL(2);
     // every field of the (by-value) argument either branch needs, requested NOW in one batch of scalar loads: fetched where they are
     // first used they came in three dependent batches in front of the first vector load (~0.25 us each: the scalar cache is cold at
     // the start of a launch, and this launch is nothing but one round trip to fresh data and a store)
@@ -368,17 +386,21 @@ __device__ static inline void bb_finish_block(const FinishArgs& F, int block, in
         const BbSlabSeg& sg = (F.slabs.n_seg > 1 && rbk >= F.slabs.seg[1].block0) ? F.slabs.seg[1] : F.slabs.seg[0];
         const int i = (rbk - sg.block0) * (BB_THREADS * 4) + tid * 4;
         if (i < sg.n) {
-            float4 v[BB_MAX_SLABS];
+            constexpr int NS = SMALL ? BF_SMALL_SLABS : BB_MAX_SLABS;
+            float4 v[NS];
 #pragma unroll
-            for (int s_ = 0; s_ < BB_MAX_SLABS; ++s_)
+            for (int s_ = 0; s_ < NS; ++s_)
                 v[s_] = *(const float4*)(sg.src + (int64_t)(s_ < sg.n_slabs ? s_ : 0) * sg.stride + i);
+            BF_TL(3);
+            BF_TL_LANDED(4);
             float4 a = v[0];
 #pragma unroll
-            for (int s_ = 1; s_ < BB_MAX_SLABS; ++s_)
+            for (int s_ = 1; s_ < NS; ++s_)
                 if (s_ < sg.n_slabs) { a.x += v[s_].x; a.y += v[s_].y; a.z += v[s_].z; a.w += v[s_].w; }
             *(float4*)(sg.dst + i) = a;
+            BF_TL(5);
             sq = a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w;
-            if (F.grad_base) {
+            if (!SMALL && F.grad_base) {             // (the small form runs on one GPU only)
                 // branch-free over the ranks (the own slab gets a copy nobody reads), as xg_push_range: with `if (p != rank)`
                 // around each store the compiler waits for every one of them in turn
                 const uint64_t e = F.push.ctrl[0] + 1;           // the epoch of the all-reduce launch that follows
@@ -400,9 +422,10 @@ __device__ static inline void bb_finish_block(const FinishArgs& F, int block, in
         // that tell the peers to read are raised by the NEXT launch of this stream, behind the launch boundary and behind that
         // launch's own system-scope release. (A release fence in each of the 73 pushing workgroups — an L2 write-back each, of
         // lines that have nothing to do with the slabs — cost 7 - 15 us per update in the shared-GPU rehearsal.)
-        if (F.grad_base) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (!SMALL && F.grad_base) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     } else {
-        const int lane = tid & 63, wave = tid >> 6;
+        // (SMALL: the wave's number as a scalar, so that the column and every base below are wave-uniform)
+        const int lane = tid & 63, wave = SMALL ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
         const int cl = wave >> 1, wq = wave & 1, k = lane & 31, hf = lane >> 5;
         const int col = block * BF_COLS + cl;
         const bool col_on = col < F.H;
@@ -410,17 +433,24 @@ __device__ static inline void bb_finish_block(const FinishArgs& F, int block, in
         const int kc = k < F.KP ? k : 0;
         // everything requested up front, branch-free (indices clamped, sums predicated)
         const int Q = (F.NB1 + 3) >> 2, rb0 = (2 * wq + hf) * Q;     // this quarter's run of blocks
-        float pv[BB_MAX_NB1 / 4], pw[BB_MAX_NB1 / 4];
+        constexpr int NPV = SMALL ? BF_SMALL_NB1 / 4 : BB_MAX_NB1 / 4;      // p_slabs values per lane
+        // SMALL, p_slabs: the resource starts at block 0 of this column and ends with block NB1 - 1 of it; the lane's offset is its
+        // quarter's first block and its k (bytes), the i-th block of the run one scalar stride further. A run that reaches past
+        // NB1 (the last quarters of NB1 = 5: blocks 6, 7) reads 0 there. The block sums likewise: block = lane.
+        const unsigned blk = (unsigned)(F.H * F.KP) * 4u, kb = 4u * (unsigned)kc, lp = (unsigned)rb0 * blk + kb;
+        const __amdgpu_buffer_rsrc_t pb = naf_buf(F.p_slabs + colc * F.KP, (unsigned)((F.NB1 * F.H - colc) * F.KP) * 4u);
+        float pv[NPV], pw[NPV];
 #pragma unroll
-        for (int i = 0; i < BB_MAX_NB1 / 4; ++i) {
+        for (int i = 0; i < NPV; ++i) {
             const int rb = rb0 + i;
-            pv[i] = F.p_slabs[((int64_t)((i < Q && rb < F.NB1) ? rb : 0) * F.H + colc) * F.KP + kc];
+            pv[i] = SMALL ? naf_buf_f1(pb, lp + (unsigned)i * blk, 0)
+                          : F.p_slabs[((int64_t)((i < Q && rb < F.NB1) ? rb : 0) * F.H + colc) * F.KP + kc];
         }
         const bool big = BIG;                              // 2048 < B <= 4096 (more than 64 dA1 blocks): the second half of each quarter's run
         if (big) {
 #pragma unroll
-            for (int i = 0; i < BB_MAX_NB1 / 4; ++i) {
-                const int j = BB_MAX_NB1 / 4 + i, rb = rb0 + j;
+            for (int i = 0; i < NPV; ++i) {
+                const int j = NPV + i, rb = rb0 + j;
                 pw[i] = F.p_slabs[((int64_t)((j < Q && rb < F.NB1) ? rb : 0) * F.H + colc) * F.KP + kc];
             }
         }
@@ -428,22 +458,29 @@ __device__ static inline void bb_finish_block(const FinishArgs& F, int block, in
         float2 av = make_float2(0.f, 0.f);
         float dv = 0.f;
         float2 aw = make_float2(0.f, 0.f);
-        if (wq == 0) av = F.partials1[(int64_t)(lane < F.NB1 ? lane : 0) * F.H + colc];
+        if (wq == 0) av = SMALL ? bb_f2(naf_buf_f2(naf_buf(F.partials1 + colc, (unsigned)(F.NB1 * F.H - colc) * 8u), (unsigned)(lane * F.H) * 8u, 0))
+                                : F.partials1[(int64_t)(lane < F.NB1 ? lane : 0) * F.H + colc];
         if (wq == 0 && big) aw = F.partials1[(int64_t)(64 + lane < F.NB1 ? 64 + lane : 0) * F.H + colc];
-        else if (F.NB > 0) dv = F.dz2_col_partials[(int64_t)(lane < F.NB ? lane : 0) * F.H + colc];   // (NB = 0: no such array)
-        const float invstd = F.save_invstd[colc], gm = F.gamma[colc];
-        const float sxk = F.mom[kc], wck = F.wc[(int64_t)colc * F.KP + kc];
+        else if (F.NB > 0) dv = SMALL ? naf_buf_f1(naf_buf(F.dz2_col_partials + colc, (unsigned)(F.NB * F.H - colc) * 4u), (unsigned)(lane * F.H) * 4u, 0)
+                                      : F.dz2_col_partials[(int64_t)(lane < F.NB ? lane : 0) * F.H + colc];   // (NB = 0: no such array)
+        const float invstd = SMALL ? naf_buf_f1(naf_buf(F.save_invstd), 0, (unsigned)colc * 4u) : F.save_invstd[colc],
+                    gm = SMALL ? naf_buf_f1(naf_buf(F.gamma), 0, (unsigned)colc * 4u) : F.gamma[colc];
+        const float sxk = SMALL ? naf_buf_f1(naf_buf(F.mom), kb, 0) : F.mom[kc],
+                    wck = SMALL ? naf_buf_f1(naf_buf(F.wc), kb, (unsigned)(colc * F.KP) * 4u) : F.wc[(int64_t)colc * F.KP + kc];
         float g2 = 0.f, b2 = 0.f;
         if (F.d_gamma2) {
-            g2 = F.d_gamma2[colc];                           // written by bb_bn_bwd_stage2, an earlier launch
-            b2 = F.d_beta2[colc];
+            g2 = SMALL ? naf_buf_f1(naf_buf(F.d_gamma2), 0, (unsigned)colc * 4u) : F.d_gamma2[colc];   // written by bb_bn_bwd_stage2, an earlier launch
+            b2 = SMALL ? naf_buf_f1(naf_buf(F.d_beta2), 0, (unsigned)colc * 4u) : F.d_beta2[colc];
         }
+        BF_TL(3);
+        BF_TL_LANDED(4);
         float P = 0.f;
+        // (SMALL: Q <= NPV, and a step past Q adds +0 to a sum that is never -0: the same bits as the sixteen steps give)
 #pragma unroll
-        for (int i = 0; i < BB_MAX_NB1 / 4; ++i) P += (i < Q && rb0 + i < F.NB1) ? pv[i] : 0.f;
+        for (int i = 0; i < NPV; ++i) P += (i < Q && rb0 + i < F.NB1) ? pv[i] : 0.f;
         if (big) {
 #pragma unroll
-            for (int i = 0; i < BB_MAX_NB1 / 4; ++i) P += (BB_MAX_NB1 / 4 + i < Q && rb0 + BB_MAX_NB1 / 4 + i < F.NB1) ? pw[i] : 0.f;
+            for (int i = 0; i < NPV; ++i) P += (NPV + i < Q && rb0 + NPV + i < F.NB1) ? pw[i] : 0.f;
         }
         {
             const float other = __shfl_xor(P, 32);          // quarters (0, 1) of wave 0, (2, 3) of wave 1: lower + upper
@@ -481,6 +518,7 @@ __device__ static inline void bb_finish_block(const FinishArgs& F, int block, in
                 sq = g2 * g2 + b2 * b2;
             }
         }
+        BF_TL(5);
     }
     if (MERGE) {
         bb_finish_exchange(F, block, tid, ex_a, ex_o, ex_on, sQ);
@@ -493,6 +531,7 @@ __device__ static inline void bb_finish_block(const FinishArgs& F, int block, in
             if (block == 0 && F.step_dev) *F.step_dev += 1;   // read by the NEXT launch (Adam) only
         }
     }
+    BF_TL(6);
 }
 
 template <bool MERGE, bool BIG>
@@ -501,6 +540,17 @@ __global__ __launch_bounds__(BB_THREADS) void bb_layer1_bwd_finish_kernel(const 
     __shared__ float sP[BF_COLS][2][32];
     NAF_TL(g_tl_bb, NAF_TL_BB_FINISH, 0);
     bb_finish_block<MERGE, BIG>(F, (int)blockIdx.x, (int)threadIdx.x, sQ, sP);
+    NAF_TL(g_tl_bb, NAF_TL_BB_FINISH, 1);
+}
+// the SMALL form (bb_finish_block): a template of three parameters beside the one of two, so that <MERGE, BIG> above stay the
+// very symbols they were
+template <bool MERGE, bool BIG, bool SMALL>
+__global__ __launch_bounds__(BB_THREADS) void bb_layer1_bwd_finish_kernel(const FinishArgs F) {
+    static_assert(SMALL && !MERGE && !BIG, "the small form: one GPU, NB1 <= BF_SMALL_NB1");
+    __shared__ float sQ[BB_THREADS / 64];
+    __shared__ float sP[BF_COLS][2][32];
+    NAF_TL(g_tl_bb, NAF_TL_BB_FINISH, 0);
+    bb_finish_block<MERGE, BIG, SMALL>(F, (int)blockIdx.x, (int)threadIdx.x, sQ, sP);
     NAF_TL(g_tl_bb, NAF_TL_BB_FINISH, 1);
 }
 
@@ -1521,12 +1571,17 @@ extern "C" int naf_bb_layer1_bwd_kp(int K) {
 
 extern "C" int naf_bb_layer1_bwd_finish_blocks(int H) { return H > 0 ? (H + BF_COLS - 1) / BF_COLS : NAF_ERR_ARG; }
 
-extern "C" int naf_bb_layer1_bwd_finish(const float* p_slabs, int K, const float* partials1, int nb1,
-                                        const float* dz2_col_partials, int nb, const float* mom, const float* wc, const float* gamma, const float* save_invstd,
-                                        float* d_W, float* d_gamma, float* d_beta, float* d_bias, float* d_bias2,
-                                        const float* d_gamma2, const float* d_beta2, float* sumsq_partials, int32_t* step_dev,
-                                        int B, int H, const naf_bb_slab_seg_t* segs, int n_segs, int* fold_flag,
-                                        const naf_xgmi_push_t* push, const float* grad_base, size_t merge_total, void* stream) {
+// form: NAF_FINISH_AUTO | NAF_FINISH_GENERAL | NAF_FINISH_SMALL. The small form (bb_finish_block<.., SMALL>) runs where no
+// gradient exchange rides on the launch (no push, no merge), nb1 <= BF_SMALL_NB1 (B <= 512), nb <= 64 and every slab segment has at
+// most BF_SMALL_SLABS slabs — chain_plan.finish_small() restates the rule for the host side's table test; asked for elsewhere it is
+// an argument error.
+static int bb_finish_launch(const float* p_slabs, int K, const float* partials1, int nb1,
+                            const float* dz2_col_partials, int nb, const float* mom, const float* wc, const float* gamma, const float* save_invstd,
+                            float* d_W, float* d_gamma, float* d_beta, float* d_bias, float* d_bias2,
+                            const float* d_gamma2, const float* d_beta2, float* sumsq_partials, int32_t* step_dev,
+                            int B, int H, const naf_bb_slab_seg_t* segs, int n_segs, int* fold_flag,
+                            const naf_xgmi_push_t* push, const float* grad_base, size_t merge_total, int form, void* stream) {
+    if (form != NAF_FINISH_AUTO && form != NAF_FINISH_GENERAL && form != NAF_FINISH_SMALL) return NAF_ERR_ARG;
     if ((push != nullptr) != (grad_base != nullptr)) return NAF_ERR_ARG;
     if (merge_total && (!push || n_segs != 2 || (merge_total & 3) || merge_total > push->n_pad || !sumsq_partials || !step_dev ||
                         !(push->timeout_ticks > 0)))
@@ -1579,11 +1634,37 @@ extern "C" int naf_bb_layer1_bwd_finish(const float* p_slabs, int K, const float
             F.merge = 1;
         }
     }
+    bool small_ok = !push && !F.merge && nb1 <= BF_SMALL_NB1 && nb <= 64;
+    for (int i = 0; i < n_segs; ++i) small_ok = small_ok && segs[i].n_slabs <= BF_SMALL_SLABS;
+    if (form == NAF_FINISH_SMALL && !small_ok) return NAF_ERR_ARG;
     const bool big1 = nb1 > BB_MAX_NB1;
-    if (F.merge && big1) bb_layer1_bwd_finish_kernel<true, true><<<F.n_blocks, BB_THREADS, 0, (hipStream_t)stream>>>(F);
+    if (small_ok && form != NAF_FINISH_GENERAL) bb_layer1_bwd_finish_kernel<false, false, true><<<F.n_blocks, BB_THREADS, 0, (hipStream_t)stream>>>(F);
+    else if (F.merge && big1) bb_layer1_bwd_finish_kernel<true, true><<<F.n_blocks, BB_THREADS, 0, (hipStream_t)stream>>>(F);
     else if (F.merge) bb_layer1_bwd_finish_kernel<true, false><<<F.n_blocks, BB_THREADS, 0, (hipStream_t)stream>>>(F);
     else if (big1) bb_layer1_bwd_finish_kernel<false, true><<<F.n_blocks, BB_THREADS, 0, (hipStream_t)stream>>>(F);
     else bb_layer1_bwd_finish_kernel<false, false><<<F.n_blocks, BB_THREADS, 0, (hipStream_t)stream>>>(F);
     NAF_CHECK_LAUNCH();
     return NAF_OK;
+}
+
+extern "C" int naf_bb_layer1_bwd_finish(const float* p_slabs, int K, const float* partials1, int nb1,
+                                        const float* dz2_col_partials, int nb, const float* mom, const float* wc, const float* gamma, const float* save_invstd,
+                                        float* d_W, float* d_gamma, float* d_beta, float* d_bias, float* d_bias2,
+                                        const float* d_gamma2, const float* d_beta2, float* sumsq_partials, int32_t* step_dev,
+                                        int B, int H, const naf_bb_slab_seg_t* segs, int n_segs, int* fold_flag,
+                                        const naf_xgmi_push_t* push, const float* grad_base, size_t merge_total, void* stream) {
+    return bb_finish_launch(p_slabs, K, partials1, nb1, dz2_col_partials, nb, mom, wc, gamma, save_invstd, d_W, d_gamma, d_beta, d_bias,
+                            d_bias2, d_gamma2, d_beta2, sumsq_partials, step_dev, B, H, segs, n_segs, fold_flag, push, grad_base,
+                            merge_total, NAF_FINISH_AUTO, stream);
+}
+
+extern "C" int naf_bb_layer1_bwd_finish_form(const float* p_slabs, int K, const float* partials1, int nb1,
+                                             const float* dz2_col_partials, int nb, const float* mom, const float* wc, const float* gamma, const float* save_invstd,
+                                             float* d_W, float* d_gamma, float* d_beta, float* d_bias, float* d_bias2,
+                                             const float* d_gamma2, const float* d_beta2, float* sumsq_partials, int32_t* step_dev,
+                                             int B, int H, const naf_bb_slab_seg_t* segs, int n_segs, int* fold_flag,
+                                             const naf_xgmi_push_t* push, const float* grad_base, size_t merge_total, int form, void* stream) {
+    return bb_finish_launch(p_slabs, K, partials1, nb1, dz2_col_partials, nb, mom, wc, gamma, save_invstd, d_W, d_gamma, d_beta, d_bias,
+                            d_bias2, d_gamma2, d_beta2, sumsq_partials, step_dev, B, H, segs, n_segs, fold_flag, push, grad_base,
+                            merge_total, form, stream);
 }

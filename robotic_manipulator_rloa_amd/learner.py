@@ -26,7 +26,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
-from .chain_plan import plan_chain
+from .chain_plan import finish_small, plan_chain
 from .layout import NetLayout
 from .parallel import XgmiAllReduce, all_reduce_flat_grad
 
@@ -77,9 +77,10 @@ class Learner:
     def __init__(self, state_size: int, action_size: int, layer_size: int, batch_size: int, learning_rate: float,
                  tau: float, gamma: float, device: torch.device, p_mode: int = _lib.P_HADAMARD,
                  world_size: int = 1, process_group=None, fuse: Optional[str] = None, _force_allreduce: bool = False,
-                 _fold_norm: bool = True, pad_layer: bool = True, _xgmi=None):
+                 _fold_norm: bool = True, pad_layer: bool = True, _xgmi=None, _finish_form: int = _lib.FINISH_AUTO):
         """fuse: "rows" | "columns" | "unfused" | None (= NAF_FUSE or the per-shape default, see chain_plan.py). The underscore
-        arguments are for tests: run the gradient all-reduce at world size 1 / keep the separate grad-norm launch.
+        arguments are for tests: run the gradient all-reduce at world size 1 / keep the separate grad-norm launch; _finish_form
+        (tests and A/B runs): the form of the row-split chain's finish launch, _lib.FINISH_AUTO | FINISH_GENERAL | FINISH_SMALL.
         pad_layer: a layer_size below 256 is stored zero-padded to 256 (NetLayout) and runs the kernels built for that width;
         False: its own width on the column-tile / unfused chains (tests compare the two).
         Which chain of launches the shape gets, and every count that follows from it, is chain_plan.plan_chain's to say (self.plan);
@@ -100,6 +101,7 @@ class Learner:
         self.world_size = int(world_size)
         self.pg = process_group
         self._force_allreduce = bool(_force_allreduce)
+        self._finish_form = int(_finish_form)
         # what the launch methods, engine.py and the benchmarks read of the plan: plain attributes, copied once
         self.chain, self.fuse, self.bb_ok, self.Bp, self.hk_rows = plan.chain, plan.fuse, plan.bb_ok, plan.Bp, plan.hk_rows
         self.fold_norm, self.defer_ok = plan.fold_norm, plan.defer_ok
@@ -666,15 +668,30 @@ class Learner:
             merged = self.xgmi_merged
         elif self.xgmi_merged:
             raise _lib.NafHipError("merged gradient exchange: the flat layout must end with the Wh segment")
+        self._launch_finish(push, merged, self._finish_form)
+
+    @property
+    def finish_small(self) -> bool:
+        """Whether this learner's finish launch takes the small form when the library chooses (chain_plan.finish_small)."""
+        return "bb" in self.fuse and finish_small(self._nb1, 0, (self.plan.ks_w2, self.plan.ks_wh),
+                                                  push=self._xg is not None and self.lay.ends_with_wh, merge=self.xgmi_merged)
+
+    def _launch_finish(self, push, merged: bool, form: int) -> None:
+        """The row-split chain's finish launch on the learner's buffers, in the given form (learn_rows: self._finish_form)."""
+        lay, B, st = self.lay, self.B, stream_ptr()
+        seg, P, H = lay.seg, lay.P, lay.H
+        t2p, gp = self.theta2.data_ptr(), self.grad.data_ptr()
         norm_here = self.fold_norm or merged
-        check(f.naf_bb_layer1_bwd_finish(
-            ptr(self.bb_dw1), lay.S, ptr(self.bb_bw1), self._nb1, None, 0,
-            ptr(self._mom), ptr(self.bb_wc), t2p + 4 * seg["g1"].offset, ptr(self.save_invstd[0, 0]),
-            gp + 4 * seg["W1"].offset, gp + 4 * seg["g1"].offset, gp + 4 * seg["be1"].offset, gp + 4 * seg["b1"].offset,
-            gp + 4 * seg["b2"].offset, gp + 4 * seg["g2"].offset, gp + 4 * seg["be2"].offset,
-            ptr(self.partials) if norm_here else None, ptr(self.step_live) if norm_here else None, B, H,
-            self._bb_segs, self._bb_nsegs, ptr(self.bb_fold_flag), push, gp if push is not None else None, P if merged else 0, st),
-            "bb_layer1_bwd_finish")
+        args = (ptr(self.bb_dw1), lay.S, ptr(self.bb_bw1), self._nb1, None, 0,
+                ptr(self._mom), ptr(self.bb_wc), t2p + 4 * seg["g1"].offset, ptr(self.save_invstd[0, 0]),
+                gp + 4 * seg["W1"].offset, gp + 4 * seg["g1"].offset, gp + 4 * seg["be1"].offset, gp + 4 * seg["b1"].offset,
+                gp + 4 * seg["b2"].offset, gp + 4 * seg["g2"].offset, gp + 4 * seg["be2"].offset,
+                ptr(self.partials) if norm_here else None, ptr(self.step_live) if norm_here else None, B, H,
+                self._bb_segs, self._bb_nsegs, ptr(self.bb_fold_flag), push, gp if push is not None else None, P if merged else 0)
+        if form == _lib.FINISH_AUTO:         # (the entry every caller but a test or an A/B run uses)
+            check(self._f.naf_bb_layer1_bwd_finish(*args, st), "bb_layer1_bwd_finish")
+        else:
+            check(self._f.naf_bb_layer1_bwd_finish_form(*args, form, st), "bb_layer1_bwd_finish_form")
 
     def _learn_rows_tiles(self, rows: torch.Tensor, lp) -> None:
         """The column-tile chain (csrc/fused_layers.hip) and the unfused chain (torch GEMMs + csrc/bn_relu.hip), by `fuse`."""
