@@ -20,8 +20,9 @@ LIB_PATH = os.path.join(CSRC, "libnaf_hip.so")
 SOURCES = ["lib.hip", "replay.hip", "naf_head.hip", "bn_relu.hip", "fused_layers.hip", "big_batch.hip", "gemm_bundle.hip", "optim.hip",
            "synth_env.hip", "xgmi_reduce.hip", "policy_act.hip", "step_path.hip", "naf_head_wide.hip",
            "state_digest.hip", "chain_env.hip", "vector_step.hip"]
-HEADERS = ["common.h", "head_body.h", "bn_tile.h", "xgmi_dev.h", "adam_body.h", "bn2bwd_fold.h", "act_body.h", "moments_body.h", "sample_body.h", "replay_dev.h", "policy_act_body.h",
-           "synth_env_body.h", os.path.join("..", "..", "include", "naf_hip.h")]
+PUBLIC_HEADER = os.path.join("..", "..", "include", "naf_hip.h")
+# what a rebuild looks at beside the sources: every header of csrc/ (found, not listed by hand) and the public one
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [PUBLIC_HEADER]
 
 P_HADAMARD, P_MATMUL = 0, 1
 ACTION_TRUNC_INT, ACTION_FLOAT = 0, 1
@@ -70,7 +71,7 @@ def _stale() -> bool:
 
 def header_abi_version() -> int:
     """NAF_HIP_ABI_VERSION as include/naf_hip.h states it (the header is the contract; the library must answer the same)."""
-    with open(os.path.join(CSRC, HEADERS[-1])) as f:
+    with open(os.path.join(CSRC, PUBLIC_HEADER)) as f:
         m = re.search(r"^#define\s+NAF_HIP_ABI_VERSION\s+(\d+)", f.read(), re.M)
     if not m:
         raise NafHipError("include/naf_hip.h does not define NAF_HIP_ABI_VERSION")

@@ -1209,7 +1209,41 @@ __device__ static inline void ik_column(const float* __restrict__ model, int m, 
     }
 }
 
-// REC: iters_out [K + 1][N R][A] receives the pose before the first and after every update
+// The frame the two solve kernels share. ik_seed: candidate cand = (query n, restart r) starts from q_start[n] (r = 0) or from its
+// seed, copied into its place in q_out, which is returned. REC: iters_out [K + 1][N R][A] receives the pose before the first and
+// after every update.
+template <bool REC>
+__device__ __forceinline__ float* ik_seed(const float* __restrict__ q_start, const float* __restrict__ seeds, int64_t cand, int64_t n,
+                                          int R, int A, float* q_out, float* __restrict__ iters_out) {
+    const int r = (int)(cand - n * R);
+    float* q = q_out + cand * A;
+    const float* src = r == 0 ? q_start + n * A : seeds + cand * A;
+    for (int m = 0; m < A; ++m) {
+        const float v = src[m];
+        q[m] = v;
+        if constexpr (REC) iters_out[cand * A + m] = v;
+    }
+    return q;
+}
+
+// ik_update: q_m += scale dq_m for the walked joints (pass 2 left dq_m in the LDS record's first float), then the position
+// limits, as a step applies them. REC: the pose also goes to `rec`, the candidate's place in the update's slab of iters_out.
+template <bool REC>
+__device__ __forceinline__ void ik_update(const float* __restrict__ model, int n_joints, int A, float scale, const float* ax, float* q,
+                                          float* __restrict__ rec) {
+    for (int m = 0; m < A; ++m) {
+        const float* j = model + CH_HDR + m * CH_JNT;
+        float v = q[m];
+        if (m < n_joints) v += scale * ax[m * 6 * 64];
+        if (j[16] != 0.f) {
+            if (v > j[18]) v = j[18];
+            if (v < j[17]) v = j[17];
+        }
+        q[m] = v;
+        if constexpr (REC) rec[m] = v;
+    }
+}
+
 template <bool REC>
 __global__ void __launch_bounds__(64)
 chain_ik_solve_kernel(const float* __restrict__ model, const float* __restrict__ targets, const float* __restrict__ q_start,
@@ -1220,16 +1254,9 @@ chain_ik_solve_kernel(const float* __restrict__ model, const float* __restrict__
     const int64_t cand = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (cand >= total) return;      // (one wave per workgroup and no barrier below)
     const int64_t n = cand / R;
-    const int r = (int)(cand - n * R);
     const int n_joints = (int)model[4];      // the end-effector frame: joints m >= it do not move the end effector
     float* ax = ch_lds + threadIdx.x;
-    float* q = q_out + cand * A;
-    const float* src = r == 0 ? q_start + n * A : seeds + cand * A;
-    for (int m = 0; m < A; ++m) {
-        const float v = src[m];
-        q[m] = v;
-        if constexpr (REC) iters_out[cand * A + m] = v;
-    }
+    float* q = ik_seed<REC>(q_start, seeds, cand, n, R, A, q_out, iters_out);
     const float g0 = targets[n * 3], g1 = targets[n * 3 + 1], g2 = targets[n * 3 + 2];
     float ee[3];
     for (int k = 0; k < prm.iterations; ++k) {
@@ -1264,17 +1291,7 @@ chain_ik_solve_kernel(const float* __restrict__ model, const float* __restrict__
             big = fmaxf(big, fabsf(dq));
         }
         const float scale = big > prm.dq_max ? prm.dq_max / big : 1.f;
-        for (int m = 0; m < A; ++m) {
-            const float* j = model + CH_HDR + m * CH_JNT;
-            float v = q[m];
-            if (m < n_joints) v += scale * ax[m * 6 * 64];
-            if (j[16] != 0.f) {      // the position limits, as a step applies them
-                if (v > j[18]) v = j[18];
-                if (v < j[17]) v = j[17];
-            }
-            q[m] = v;
-            if constexpr (REC) iters_out[((int64_t)(k + 1) * total + cand) * A + m] = v;
-        }
+        ik_update<REC>(model, n_joints, A, scale, ax, q, REC ? iters_out + ((int64_t)(k + 1) * total + cand) * A : nullptr);
     }
     ik_walk<false>(model, n_joints, q, ax, ee);
     const float e0 = g0 - ee[0], e1 = g1 - ee[1], e2 = g2 - ee[2];
@@ -1490,16 +1507,9 @@ chain_ik_pose_kernel(const float* __restrict__ model, const float* __restrict__ 
     const int64_t cand = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (cand >= total) return;      // (one wave per workgroup and no barrier below)
     const int64_t n = cand / R;
-    const int r = (int)(cand - n * R);
     const int n_joints = (int)model[4];
     float* ax = ch_lds + threadIdx.x;
-    float* q = q_out + cand * A;
-    const float* src = r == 0 ? q_start + n * A : seeds + cand * A;
-    for (int m = 0; m < A; ++m) {
-        const float v = src[m];
-        q[m] = v;
-        if constexpr (REC) iters_out[cand * A + m] = v;
-    }
+    float* q = ik_seed<REC>(q_start, seeds, cand, n, R, A, q_out, iters_out);
     const float g0 = targets[n * 3], g1 = targets[n * 3 + 1], g2 = targets[n * 3 + 2];
     float goal[GOAL];
 #pragma unroll
@@ -1544,17 +1554,7 @@ chain_ik_pose_kernel(const float* __restrict__ model, const float* __restrict__ 
             big = fmaxf(big, fabsf(dq));
         }
         const float scale = big > prm.dq_max ? prm.dq_max / big : 1.f;
-        for (int m = 0; m < A; ++m) {
-            const float* j = model + CH_HDR + m * CH_JNT;
-            float v = q[m];
-            if (m < n_joints) v += scale * ax[m * 6 * 64];
-            if (j[16] != 0.f) {      // the position limits, as a step applies them
-                if (v > j[18]) v = j[18];
-                if (v < j[17]) v = j[17];
-            }
-            q[m] = v;
-            if constexpr (REC) iters_out[((int64_t)(k + 1) * total + cand) * A + m] = v;
-        }
+        ik_update<REC>(model, n_joints, A, scale, ax, q, REC ? iters_out + ((int64_t)(k + 1) * total + cand) * A : nullptr);
     }
     ik_walk<false, true>(model, n_joints, q, ax, ee, rot);
     const float e0 = g0 - ee[0], e1 = g1 - ee[1], e2 = g2 - ee[2];
@@ -1603,23 +1603,31 @@ extern "C" int naf_chain_ik_solve_pose(naf_chain_env_t* h, const float* targets_
                      : go([](auto... a) { return ch_ik_pose_launch<1, false>(a...); });
 }
 
-// ---- joint paths: the sampled collision check of start -> via -> goal polylines (include/naf_hip.h, "Joint paths") ---------------
-// One workgroup per candidate path (query n, via c); a lane is one sample of a pass, and the workgroup makes S / lanes passes — a
-// trip count the arguments fix. The sample's pose is never stored: the leg's two end poses are the same for the whole workgroup
-// (uniform loads), the lane's fraction f = (float)k / (float)n is its own, and the walk asks for joint m's value when it reaches
-// joint m: one fmaf. So there is no per-lane pose array, no LDS beside the pair phase's end points, and nothing in scratch.
-// SC is the probe's shape: wave 0 walks `lanes` samples and stages their capsules' end points as [segment][6][lane], every wave
-// joins the pair phase of every pass (its barriers), and only wave 0's lanes keep the running minima, the blocked count and the
-// first blocked index. Behind the last pass wave 0 reduces them by a butterfly of shuffles and lane 0 writes the record.
+// ---- line sweeps: the sampled collision check of a line in joint space (include/naf_hip.h, "Joint paths", "Roadmap edges") -------
+// chain_sweep below is the one algorithm; the line is a start -> via -> goal polyline (ViaLine, chain_path_check_kernel) or a
+// straight roadmap edge (EdgeLine, chain_edge_check_kernel). One workgroup per line; a lane is one sample of a pass, and the
+// workgroup makes S / lanes passes — a trip count the arguments fix. The sample's pose is never stored: the line's end poses are the
+// same for the whole workgroup (uniform loads), the lane's fraction is its own, and the walk asks for joint m's value when it
+// reaches joint m: one fmaf. So there is no per-lane pose array, no LDS beside the pair phase's end points, nothing in scratch,
+// nothing atomic. SC is the probe's shape: wave 0 walks `lanes` samples and stages their capsules' end points as
+// [segment][6][lane], every wave joins the pair phase of every pass (its barriers), and only wave 0's lanes keep the running
+// minima, the blocked count and the first blocked index; without pairs a workgroup is one wave with no barrier and no LDS. Behind
+// the last pass wave 0 reduces them by a butterfly of shuffles and lane 0 writes the record.
 //
-// A leading ChainCert in the pack (CERT below) is naf_chain_path_certify's kernel: the record has NAF_CHAIN_PATH_CERT_FLOATS floats.
-// Every interval of a leg has the same joint displacement, so how far a point of capsule s can travel over half an interval is one
-// number per leg: beta[s] = sum_m |b_m - a_m| reach[m][s] / (2 n), and for a pair (s, t) the same sum over the joints between the
-// two frames with reach[m][t]. Before the first pass the workgroup's threads fill three tables of n_seg + P such entries in LDS,
-// behind the pair phase's rows — leg 1, leg 2, and their entry-wise maximum for the via sample, which ends one leg's last interval
-// and begins the other's first — an entry per thread, the joint sum in joint order by fmaf. A lane picks its table by i < h,
-// i > h or i == h; the walk and the pair phase subtract the entry from every clearance they form and keep those minima beside
-// the plain ones. No per-lane array, nothing atomic; the kernels without ChainCert keep their arguments and their code.
+// A leading ChainCert in the pack (CERT below) is the certifying kernel of naf_chain_path_certify / naf_chain_edge_certify: the
+// record has four more floats. Every interval of a leg has the same joint displacement, so how far a point of capsule s can travel
+// over half an interval is one number per leg: beta[s] = sum_m |b_m - a_m| reach[m][s] / (2 n) for a leg of n intervals, and for a
+// pair (s, t) the same sum over the joints between the two frames with reach[m][t]. Before the first pass the workgroup's threads
+// fill the line's tables of n_seg + P such entries in LDS, behind the pair phase's rows — an entry per thread, the joint sum in
+// joint order by fmaf, one barrier. A lane picks its table by its sample; the walk and the pair phase subtract the entry from every
+// clearance they form and keep those minima beside the plain ones. The kernels without ChainCert keep their arguments.
+//
+// What the two lines differ in is the Line's, and nothing else is:
+//   ViaLine   h = S / 2; sample i is on leg 1 at i / h (i < h) or on leg 2 at (i - h) / (h - 1); three tables — leg 1, leg 2, and
+//             their entry-wise maximum for the via sample i == h, which ends one leg's last interval and begins the other's first;
+//             the record's floats 5 .. 7 are the two legs' summed length, the larger step, and whether the goal sample is blocked
+//   EdgeLine  ONE leg of S - 1 intervals, sample i at i / (S - 1), both ends included; one table, which every sample uses; floats
+//             5 .. 7 are the length, the step and 0
 struct ChainCert {
     const float* reach;      // [A][n_seg] (DEVICE)
     float guard;
@@ -1634,25 +1642,89 @@ __host__ __device__ static inline size_t ch_cert_lds_bytes(int n_seg, int n_pair
     return (ch_cert_table_floats(n_seg, n_pairs, lanes, waves) + 3 * (size_t)(n_seg + n_pairs)) * sizeof(float);
 }
 
-template <bool SC, class... Cell>
-__global__ void __launch_bounds__(SC ? 64 * CH_MAX_WAVES : 64)
-chain_path_check_kernel(const float* __restrict__ model, const float* __restrict__ q_start, const float* __restrict__ q_goal,
-                        const float* __restrict__ vias, const float* __restrict__ obstacles, float orad, int C, int S, int A, int n_seg,
-                        int n_pairs, int lanes, float margin, float* __restrict__ out, float* __restrict__ poses_out, const Cell... cell) {
+// The line a sweep samples: sample(i) is sample i's fraction (and, for the via line, its leg), pose(sample, m) joint m's value there
+// by one fmaf, table_of(i) the sample's table of half-steps, fill(...) entry e of the tables, finish(...) floats 5 .. 7 of the record.
+// ViaLine: start -> via over samples 0 .. h, via -> goal over h .. S - 1, h = S / 2; three tables (leg 1, leg 2, their maximum).
+struct ViaLine {
+    static constexpr bool GOAL = true;      // the record reports whether the last sample, the goal, is blocked
+    const float *start, *via, *goal;
+    int h;
+    struct Sample {
+        bool second;
+        float f;
+    };
+    __device__ Sample sample(int i) const {
+        const bool second = i >= h;
+        return {second, second ? (float)(i - h) / (float)(h - 1) : (float)i / (float)h};
+    }
+    __device__ float pose(const Sample& s, int m) const {
+        const float v = via[m];
+        const float a = s.second ? v : start[m], b = s.second ? goal[m] : v;
+        return fmaf(s.f, b - a, a);
+    }
+    __device__ int table_of(int i) const { return i < h ? 0 : (i == h ? 2 : 1); }
+    __device__ void fill(float* t, int n_tab, int e, int s, int m0, int m1, const float* reach, int n_seg) const {
+        float b1 = 0.f, b2 = 0.f;
+        for (int m = m0; m < m1; ++m) {
+            const float v = via[m], r = reach[m * n_seg + s];
+            b1 = fmaf(fabsf(v - start[m]), r, b1);
+            b2 = fmaf(fabsf(goal[m] - v), r, b2);
+        }
+        b1 = b1 / (float)(2 * h);
+        b2 = b2 / (float)(2 * (h - 1));
+        t[e] = b1;
+        t[n_tab + e] = b2;
+        t[2 * n_tab + e] = fmaxf(b1, b2);
+    }
+    __device__ void finish(float* o, int A, int goal_blocked) const {
+        float l1 = 0.f, l2 = 0.f;
+        for (int m = 0; m < A; ++m) {
+            l1 = fmaxf(l1, fabsf(via[m] - start[m]));
+            l2 = fmaxf(l2, fabsf(goal[m] - via[m]));
+        }
+        o[5] = l1 + l2;
+        o[6] = fmaxf(l1 / (float)h, l2 / (float)(h - 1));
+        o[7] = (float)goal_blocked;
+    }
+};
+// EdgeLine: a -> b over samples 0 .. S - 1, both ends included; ONE table, and fill writes nothing beyond t[e]: an edge launch
+// has LDS for one.
+struct EdgeLine {
+    static constexpr bool GOAL = false;
+    const float *a, *b;
+    int last;      // S - 1
+    __device__ float sample(int i) const { return (float)i / (float)last; }
+    __device__ float pose(float f, int m) const {
+        const float lo = a[m];
+        return fmaf(f, b[m] - lo, lo);
+    }
+    __device__ int table_of(int) const { return 0; }
+    __device__ void fill(float* t, int, int e, int s, int m0, int m1, const float* reach, int n_seg) const {
+        float acc = 0.f;
+        for (int m = m0; m < m1; ++m) acc = fmaf(fabsf(b[m] - a[m]), reach[m * n_seg + s], acc);
+        t[e] = acc / (float)(2 * last);
+    }
+    __device__ void finish(float* o, int A, int) const {
+        float len = 0.f;
+        for (int m = 0; m < A; ++m) len = fmaxf(len, fabsf(b[m] - a[m]));
+        o[5] = len;
+        o[6] = len / (float)last;
+        o[7] = 0.f;
+    }
+};
+
+// The sweep of workgroup `item` along `line`: `record` is the item's own, poses_out (or nullptr) the launch's [item][S][A].
+template <bool SC, class Line, class... Cell>
+__device__ __forceinline__ void chain_sweep(const float* __restrict__ model, const Line& line, float ox, float oy, float oz, float orad,
+                                            int S, int A, int n_seg, int n_pairs, int lanes, float margin, float* __restrict__ record,
+                                            float* __restrict__ poses_out, int64_t item, const Cell&... cell) {
     constexpr bool CELL = (std::is_same_v<Cell, ChainCell> || ... || false);
     constexpr bool BOX = (std::is_same_v<Cell, ChainBox> || ... || false);
     constexpr bool CERT = (std::is_same_v<Cell, ChainCert> || ... || false);
     extern __shared__ __attribute__((aligned(16))) float ch_lds[];
-    const int64_t cand = blockIdx.x;
-    const int64_t n = cand / C;
-    const float* start = q_start + n * A;
-    const float* via = vias + cand * A;
-    const float* goal = q_goal + n * A;
-    const float ox = obstacles[n * 3], oy = obstacles[n * 3 + 1], oz = obstacles[n * 3 + 2];
     const int lane = threadIdx.x & 63;
     const bool active = lane < lanes;
     const bool walker = active && threadIdx.x < 64;
-    const int h = S >> 1;
     float min_clear = INFINITY, min_self = INFINITY, min_cell = INFINITY;
     int first = INT_MAX, count = 0, goal_blocked = 0;
     float low_clear = INFINITY, low_self = INFINITY, low_cell = INFINITY, guard = 0.f;
@@ -1669,17 +1741,7 @@ chain_path_check_kernel(const float* __restrict__ model, const float* __restrict
             const int s = e < n_seg ? e : (int)pairs[2 * (e - n_seg) + 1];
             const int m0 = e < n_seg ? 0 : (int)segs[(int)pairs[2 * (e - n_seg)] * CH_SEG];
             const int m1 = (int)segs[s * CH_SEG];
-            float b1 = 0.f, b2 = 0.f;
-            for (int m = m0; m < m1; ++m) {
-                const float v = via[m], r = cert.reach[m * n_seg + s];
-                b1 = fmaf(fabsf(v - start[m]), r, b1);
-                b2 = fmaf(fabsf(goal[m] - v), r, b2);
-            }
-            b1 = b1 / (float)(2 * h);
-            b2 = b2 / (float)(2 * (h - 1));
-            t[e] = b1;
-            t[n_tab + e] = b2;
-            t[2 * n_tab + e] = fmaxf(b1, b2);
+            line.fill(t, n_tab, e, s, m0, m1, cert.reach, n_seg);
         }
         __syncthreads();
         tab = t;
@@ -1687,19 +1749,16 @@ chain_path_check_kernel(const float* __restrict__ model, const float* __restrict
     }
     for (int base = 0; base < S; base += lanes) {      // (uniform: every thread takes every pass)
         const int i = base + lane;
-        const bool second = i >= h;
-        const float f = second ? (float)(i - h) / (float)(h - 1) : (float)i / (float)h;
+        const auto at = line.sample(i);
         float ee[3];
-        WalkAux aux = {SC ? ch_lds + lane : nullptr, lanes, INFINITY, INFINITY,
-                       CERT ? tab + (i < h ? 0 : (i == h ? 2 : 1)) * n_tab : nullptr, INFINITY, INFINITY};
+        WalkAux aux = {SC ? ch_lds + lane : nullptr, lanes, INFINITY, INFINITY, CERT ? tab + line.table_of(i) * n_tab : nullptr,
+                       INFINITY, INFINITY};
         if (walker) {
-            float* rec = poses_out ? poses_out + (cand * S + i) * A : nullptr;
+            float* rec = poses_out ? poses_out + (item * S + i) * A : nullptr;
             chain_walk_at<SC, true, false, true, CELL, BOX, CERT>(
                 model, A, n_seg,
                 [=](int m) {
-                    const float v = via[m];
-                    const float a = second ? v : start[m], b = second ? goal[m] : v;
-                    const float q = fmaf(f, b - a, a);
+                    const float q = line.pose(at, m);
                     if (rec) rec[m] = q;
                     return q;
                 },
@@ -1717,7 +1776,7 @@ chain_path_check_kernel(const float* __restrict__ model, const float* __restrict
             if constexpr (CELL) min_cell = fminf(min_cell, aux.cell);
             first = blocked && i < first ? i : first;
             count += blocked ? 1 : 0;
-            goal_blocked |= blocked && i == S - 1 ? 1 : 0;
+            if constexpr (Line::GOAL) goal_blocked |= blocked && i == S - 1 ? 1 : 0;
             if constexpr (CERT) {
                 const float s0 = aux.slack - orad - guard, s1 = self_slack - guard, s2 = aux.cell_slack - guard;
                 low_clear = fminf(low_clear, s0);
@@ -1734,7 +1793,7 @@ chain_path_check_kernel(const float* __restrict__ model, const float* __restrict
         min_cell = fminf(min_cell, __shfl_xor(min_cell, off));
         first = min(first, __shfl_xor(first, off));
         count += __shfl_xor(count, off);
-        goal_blocked |= __shfl_xor(goal_blocked, off);
+        if constexpr (Line::GOAL) goal_blocked |= __shfl_xor(goal_blocked, off);
         if constexpr (CERT) {
             low_clear = fminf(low_clear, __shfl_xor(low_clear, off));
             low_self = fminf(low_self, __shfl_xor(low_self, off));
@@ -1743,26 +1802,33 @@ chain_path_check_kernel(const float* __restrict__ model, const float* __restrict
         }
     }
     if (threadIdx.x != 0) return;
-    float l1 = 0.f, l2 = 0.f;
-    for (int m = 0; m < A; ++m) {
-        l1 = fmaxf(l1, fabsf(via[m] - start[m]));
-        l2 = fmaxf(l2, fabsf(goal[m] - via[m]));
-    }
-    float* o = out + cand * (CERT ? NAF_CHAIN_PATH_CERT_FLOATS : NAF_CHAIN_PATH_FLOATS);
-    o[0] = min_clear;
-    o[1] = min_self;
-    o[2] = min_cell;
-    o[3] = first == INT_MAX ? -1.f : (float)first;
-    o[4] = (float)count;
-    o[5] = l1 + l2;
-    o[6] = fmaxf(l1 / (float)h, l2 / (float)(h - 1));
-    o[7] = (float)goal_blocked;
+    record[0] = min_clear;
+    record[1] = min_self;
+    record[2] = min_cell;
+    record[3] = first == INT_MAX ? -1.f : (float)first;
+    record[4] = (float)count;
+    line.finish(record, A, goal_blocked);
     if constexpr (CERT) {
-        o[8] = low_clear;
-        o[9] = low_self;
-        o[10] = low_cell;
-        o[11] = first_low == INT_MAX ? -1.f : (float)first_low;
+        record[8] = low_clear;
+        record[9] = low_self;
+        record[10] = low_cell;
+        record[11] = first_low == INT_MAX ? -1.f : (float)first_low;
     }
+}
+
+// one workgroup per candidate path (query n, via c)
+template <bool SC, class... Cell>
+__global__ void __launch_bounds__(SC ? 64 * CH_MAX_WAVES : 64)
+chain_path_check_kernel(const float* __restrict__ model, const float* __restrict__ q_start, const float* __restrict__ q_goal,
+                        const float* __restrict__ vias, const float* __restrict__ obstacles, float orad, int C, int S, int A, int n_seg,
+                        int n_pairs, int lanes, float margin, float* __restrict__ out, float* __restrict__ poses_out, const Cell... cell) {
+    constexpr bool CERT = (std::is_same_v<Cell, ChainCert> || ... || false);
+    const int64_t cand = blockIdx.x;
+    const int64_t n = cand / C;
+    const ViaLine line = {q_start + n * A, vias + cand * A, q_goal + n * A, S >> 1};
+    chain_sweep<SC>(model, line, obstacles[n * 3], obstacles[n * 3 + 1], obstacles[n * 3 + 2], orad, S, A, n_seg, n_pairs, lanes, margin,
+                    out + cand * (CERT ? NAF_CHAIN_PATH_CERT_FLOATS : NAF_CHAIN_PATH_FLOATS),
+                    poses_out, cand, cell...);
 }
 
 // what naf_chain_path_check and naf_chain_path_certify ask of the arguments they share
@@ -1805,133 +1871,24 @@ extern "C" int naf_chain_path_certify(naf_chain_env_t* h, const float* q_start_d
 }
 
 // ---- roadmap edges: the sampled collision check of straight joint-space edges (include/naf_hip.h, "Roadmap edges") ---------------
-// The path kernel with one leg and indexed end poses. One workgroup per (query n, edge e); the edge's two nodes are read from
-// edges[e] (the same list for every query of the launch) and their poses from nodes[n] — uniform loads. A lane is one sample of a
-// pass: f = (float)i / (float)(S - 1), both ends included, and the walk forms fmaf(f, b_m - a_m, a_m) when it reaches joint m.
-// No pose record, no per-lane array, nothing in scratch, no atomics. SC is the probe's shape, as in chain_path_check_kernel: wave
-// 0 walks, stages the end points as [segment][6][lane], and every wave joins the pair phase of every pass; without pairs a
-// workgroup is one wave with no barrier and no LDS. One butterfly of shuffles at the end; lane 0 writes the record.
-//
-// A leading ChainCert in the pack (CERT below) is naf_chain_edge_certify's kernel: the record has NAF_CHAIN_EDGE_CERT_FLOATS floats.
-// An edge is ONE leg of S - 1 intervals, all with the joint displacement (b - a) / (S - 1), so there is one table of n_seg + P
-// half-steps per edge and every sample uses it: beta[s] = sum_m |b_m - a_m| reach[m][s] / (2 (S - 1)), chain_path_check_kernel's
-// span for a pair. The workgroup's threads fill it in LDS behind the pair phase's rows before the first pass — an entry per
-// thread, the joint sum in joint order by fmaf, one division, one barrier — and the passes are what they were, with the entry
-// subtracted from every clearance beside the plain minima. The kernels without ChainCert keep their arguments and their code.
+// chain_sweep along an EdgeLine. One workgroup per (query n, edge e); the edge's two nodes are read from edges[e] (the same list
+// for every query of the launch) and their poses from nodes[n] — uniform loads. A leading ChainCert in the pack is
+// naf_chain_edge_certify's kernel: the record has NAF_CHAIN_EDGE_CERT_FLOATS floats.
 template <bool SC, class... Cell>
 __global__ void __launch_bounds__(SC ? 64 * CH_MAX_WAVES : 64)
 chain_edge_check_kernel(const float* __restrict__ model, const float* __restrict__ nodes, const int32_t* __restrict__ edges,
                         const float* __restrict__ obstacles, float orad, int V, int E, int S, int A, int n_seg, int n_pairs, int lanes,
                         float margin, float* __restrict__ out, float* __restrict__ poses_out, const Cell... cell) {
-    constexpr bool CELL = (std::is_same_v<Cell, ChainCell> || ... || false);
-    constexpr bool BOX = (std::is_same_v<Cell, ChainBox> || ... || false);
     constexpr bool CERT = (std::is_same_v<Cell, ChainCert> || ... || false);
-    extern __shared__ __attribute__((aligned(16))) float ch_lds[];
     const int64_t item = blockIdx.x;
     const int64_t n = item / E;
     const int e = (int)(item - n * E);
     // (the host validated 0 <= i < j < V for every edge before the upload; the clamp keeps a stray index inside the query's nodes)
     const int ni = min(max(edges[2 * e], 0), V - 1), nj = min(max(edges[2 * e + 1], 0), V - 1);
-    const float* a = nodes + (n * V + ni) * A;
-    const float* b = nodes + (n * V + nj) * A;
-    const float ox = obstacles[n * 3], oy = obstacles[n * 3 + 1], oz = obstacles[n * 3 + 2];
-    const int lane = threadIdx.x & 63;
-    const bool active = lane < lanes;
-    const bool walker = active && threadIdx.x < 64;
-    const float last = (float)(S - 1);
-    float min_clear = INFINITY, min_self = INFINITY, min_cell = INFINITY;
-    int first = INT_MAX, count = 0;
-    float low_clear = INFINITY, low_self = INFINITY, low_cell = INFINITY, guard = 0.f;
-    int first_low = INT_MAX;
-    const float* tab = nullptr;
-    if constexpr (CERT) {
-        const ChainCert& cert = path_cert(cell...);
-        const float* segs = model + ch_off_seg(A);
-        const float* pairs = model + ch_off_pair(A, n_seg);
-        float* t = ch_lds + ch_cert_table_floats(n_seg, n_pairs, lanes, blockDim.x >> 6);
-        for (int k = threadIdx.x; k < n_seg + n_pairs; k += blockDim.x) {
-            // entry k < n_seg: segment k against the world, joints 0 .. frame - 1; else pair (s, t): t against s, joints frame s ..
-            const int s = k < n_seg ? k : (int)pairs[2 * (k - n_seg) + 1];
-            const int m0 = k < n_seg ? 0 : (int)segs[(int)pairs[2 * (k - n_seg)] * CH_SEG];
-            const int m1 = (int)segs[s * CH_SEG];
-            float acc = 0.f;
-            for (int m = m0; m < m1; ++m) acc = fmaf(fabsf(b[m] - a[m]), cert.reach[m * n_seg + s], acc);
-            t[k] = acc / (float)(2 * (S - 1));
-        }
-        __syncthreads();
-        tab = t;
-        guard = cert.guard;
-    }
-    for (int base = 0; base < S; base += lanes) {      // (uniform: every thread takes every pass)
-        const int i = base + lane;
-        const float f = (float)i / last;
-        float ee[3];
-        WalkAux aux = {SC ? ch_lds + lane : nullptr, lanes, INFINITY, INFINITY, tab, INFINITY, INFINITY};
-        if (walker) {
-            float* rec = poses_out ? poses_out + (item * S + i) * A : nullptr;
-            chain_walk_at<SC, true, false, true, CELL, BOX, CERT>(
-                model, A, n_seg,
-                [=](int m) {
-                    const float lo = a[m];
-                    const float q = fmaf(f, b[m] - lo, lo);
-                    if (rec) rec[m] = q;
-                    return q;
-                },
-                ox, oy, oz, orad, nullptr, nullptr, ee, aux);
-        }
-        float self_clear = INFINITY, self_slack = INFINITY;
-        if constexpr (SC)
-            self_clear = self_clearance_phase<CERT>(model, A, n_seg, n_pairs, ch_lds, lanes, lane, active, CERT ? tab + n_seg : nullptr,
-                                                    CERT ? &self_slack : nullptr);
-        if (walker) {
-            const float clear = aux.clear - orad;
-            const bool blocked = clear < margin || self_clear < margin || (CELL && aux.cell < margin);
-            min_clear = fminf(min_clear, clear);
-            min_self = fminf(min_self, self_clear);
-            if constexpr (CELL) min_cell = fminf(min_cell, aux.cell);
-            first = blocked && i < first ? i : first;
-            count += blocked ? 1 : 0;
-            if constexpr (CERT) {
-                const float s0 = aux.slack - orad - guard, s1 = self_slack - guard, s2 = aux.cell_slack - guard;
-                low_clear = fminf(low_clear, s0);
-                low_self = fminf(low_self, s1);
-                if constexpr (CELL) low_cell = fminf(low_cell, s2);
-                first_low = (s0 < margin || s1 < margin || (CELL && s2 < margin)) && i < first_low ? i : first_low;
-            }
-        }
-    }
-    if (threadIdx.x >= 64) return;      // (behind the last barrier; wave 0 is whole: the lanes that walked nothing hold the identities)
-    for (int off = 32; off > 0; off >>= 1) {
-        min_clear = fminf(min_clear, __shfl_xor(min_clear, off));
-        min_self = fminf(min_self, __shfl_xor(min_self, off));
-        min_cell = fminf(min_cell, __shfl_xor(min_cell, off));
-        first = min(first, __shfl_xor(first, off));
-        count += __shfl_xor(count, off);
-        if constexpr (CERT) {
-            low_clear = fminf(low_clear, __shfl_xor(low_clear, off));
-            low_self = fminf(low_self, __shfl_xor(low_self, off));
-            low_cell = fminf(low_cell, __shfl_xor(low_cell, off));
-            first_low = min(first_low, __shfl_xor(first_low, off));
-        }
-    }
-    if (threadIdx.x != 0) return;
-    float len = 0.f;
-    for (int m = 0; m < A; ++m) len = fmaxf(len, fabsf(b[m] - a[m]));
-    float* o = out + item * (CERT ? NAF_CHAIN_EDGE_CERT_FLOATS : NAF_CHAIN_EDGE_FLOATS);
-    o[0] = min_clear;
-    o[1] = min_self;
-    o[2] = min_cell;
-    o[3] = first == INT_MAX ? -1.f : (float)first;
-    o[4] = (float)count;
-    o[5] = len;
-    o[6] = len / last;
-    o[7] = 0.f;
-    if constexpr (CERT) {
-        o[8] = low_clear;
-        o[9] = low_self;
-        o[10] = low_cell;
-        o[11] = first_low == INT_MAX ? -1.f : (float)first_low;
-    }
+    const EdgeLine line = {nodes + (n * V + ni) * A, nodes + (n * V + nj) * A, S - 1};
+    chain_sweep<SC>(model, line, obstacles[n * 3], obstacles[n * 3 + 1], obstacles[n * 3 + 2], orad, S, A, n_seg, n_pairs, lanes, margin,
+                    out + item * (CERT ? NAF_CHAIN_EDGE_CERT_FLOATS : NAF_CHAIN_EDGE_FLOATS),
+                    poses_out, item, cell...);
 }
 
 // what naf_chain_edge_check and naf_chain_edge_certify ask of the arguments they share

@@ -759,6 +759,27 @@ def test_engine_classes_stay_small():
     assert total < 3061, total
 
 
+def test_the_stale_check_sees_every_header_a_source_includes():
+    """_lib.HEADERS is what _stale() and build_library's compile_one compare the library and the objects with: every project header
+    a source of SOURCES includes — and every one such a header includes in turn — must be in it, or an edit of that header alone
+    rebuilds nothing. Reads the files, builds nothing."""
+    from robotic_manipulator_rloa_amd import _lib
+    watched = {os.path.normpath(os.path.join(_lib.CSRC, h)) for h in _lib.HEADERS}
+    assert all(os.path.isfile(p) for p in watched), [p for p in watched if not os.path.isfile(p)]
+    assert os.path.normpath(os.path.join(ROOT, "include", "naf_hip.h")) in watched and _lib.header_abi_version() >= 3
+    todo, seen = [os.path.join(_lib.CSRC, s) for s in _lib.SOURCES], set()
+    while todo:
+        path = os.path.normpath(todo.pop())
+        if path in seen:
+            continue
+        seen.add(path)
+        for name in re.findall(r'^\s*#\s*include\s+"([^"]+\.h)"', open(path).read(), re.M):
+            inc = os.path.normpath(os.path.join(os.path.dirname(path), name))
+            assert inc in watched, f"{os.path.relpath(path, ROOT)} includes {name}, which the stale check does not look at"
+            todo.append(inc)
+    assert len(seen) > len(_lib.SOURCES) + 5, "no include found: the pattern no longer matches the sources"
+
+
 def test_no_kernel_spills_to_scratch_and_the_switch_list_is_short():
     """nothing in libnaf_hip.so may keep values in scratch memory (private_segment_fixed_size, as hipcc's
     -Rpass-analysis=kernel-resource-usage reports it for every kernel at build time -> csrc/libnaf_hip.so.usage.json), and the
