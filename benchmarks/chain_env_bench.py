@@ -83,6 +83,15 @@ launches are the box instantiations, which test the floor and the spheres too.
       same process, on the same two-leg plans: the legs launch takes them split into K legs of the same actions, and the valid rows
       and records of the two are compared to the bit.
 
+  python benchmarks/chain_env_bench.py line [--envs 2048] [--launches 20] [--workcell [--boxes]]
+      straight-line end-effector moves, same arm (with self-collision; the cell only where asked for): N = --envs lines (default 2048 here) of W = 32 waypoints x U = 4 updates
+      from approach-from-above goal poses, 8 cm straight up. Microseconds per naf_chain_line_track launch between device events
+      in the modes full (orientation held) and position, each beside its yardstick — naf_chain_ik_solve_pose / naf_chain_ik_solve at
+      N x 1 candidates and W U = 128 iterations: the same number of the same updates in the same number of waves — the two
+      alternating launch by launch in the same process (median and minimum of `--launches`, at most 50, after two unmeasured
+      ones), with their ratios and the new kernels' registers. Then the whole ManipulatorFramework.plan_linear_moves call (upload,
+      tracking launch, download, verdict, the legs' edge launch, gather) in host milliseconds, and the outcomes it reports.
+
 `--hindsight R` (rate): the chain runs relabel a share R of every minibatch (NAFAgent.run_vectorized(hindsight=R)). Such a run
 wants an empty ring, so with the flag — also `--hindsight 0`, the figure to compare with — the warm-up steps run on an agent of
 their own and the timed run starts on a fresh one (its graph captures are inside the timed window, in both).
@@ -825,6 +834,84 @@ def edgecert(a):
                       "free_goal_poses": int(ok.sum()), "polylines": census, "kernel_registers": regs}))
 
 
+def line(a):
+    import time
+    import numpy as np
+    import torch
+    from robotic_manipulator_rloa_amd import ManipulatorFramework, _lib
+    from robotic_manipulator_rloa_amd.environment.line_moves import HOLD_FULL, HOLD_POSITION, line_constants
+    N, W, U, n = (2048 if a.envs == 64 else a.envs), 32, 4, a.joints
+    launches = min(a.launches, 50)
+    urdf = os.path.abspath(a.urdf) if os.path.isabs(a.urdf) else os.path.join(ROOT, a.urdf)
+    init = ([0.0, 0.6, 0.0, -1.2, 0.0, 0.8, 0.0] + [0.0] * n)[:n]
+    f = ManipulatorFramework()
+    old = os.getcwd()
+    os.chdir(tempfile.mkdtemp(prefix="naf_line_"))
+    try:
+        f.initialize_kinematic_environment(urdf, n - 1, [n], list(range(n)), [0.45, 0.3, 0.6], [0.35, 0.2, 0.45], init, [0.1] * n,
+                                           link_radius=0.03, obstacle_radius=0.06, consider_autocollision=True, **_workcell(a))
+    finally:
+        os.chdir(old)
+    model = f.env.model
+    rng = np.random.default_rng(5)
+    targets = np.array([0.45, 0.3, 0.6]) + rng.uniform(-0.15, 0.15, (N, 3))
+    goal = f.solve_goal_poses(targets, approach_directions=[0, 0, -1], iterations=64)
+    q = goal.joint_positions[goal.reachable]
+    q = q[np.arange(N) % len(q)]                              # N start poses: the reachable ones, in turn
+    disp = np.tile(np.float32([0.0, 0.0, 0.08]), (N, 1))
+    whole = []
+    for i in range(launches + 2):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        moves = f.plan_linear_moves(q, disp, waypoints=W, updates=U)
+        if i >= 2:
+            whole.append(1e3 * (time.perf_counter() - t))
+    tracker, solver = f.arm_planner.tools["line_moves"][1], f.arm_planner.tools["goal_poses"][1]
+    c = line_constants(model)
+    prm, pose = tracker.params(c, [0.0, 0.0, 1.0], [1.0, 0.0, 0.0])
+    tracker.load(q[:tracker.chunk], disp[:tracker.chunk])
+    per = min(N, tracker.chunk, solver.chunk)
+    # the yardsticks' queries: the same start poses, one candidate each, W U iterations, the goal the tracker holds
+    R_ee, ee = f.env.end_effector_frame(q[:per].astype(np.float64))
+    solver.load(q[:per], ee + disp[:per], np.tile([0.35, 0.2, 0.45], (per, 1)), np.zeros((per, 1, model.A), np.float32))
+    if solver.goals is None:
+        solver.goals, solver.angle, solver.merit = solver._zeros(solver.chunk, 9), solver._zeros(solver.chunk), solver._zeros(solver.chunk)
+    solver.goals.view(-1)[:per * 9].copy_(torch.from_numpy(np.ascontiguousarray(R_ee.reshape(-1), np.float32)))
+    ik_prm = _lib.IkParams(W * U, c["lam2"], c["e_max"], c["dq_max"])
+    out = {}
+    for name, mode in (("full", HOLD_FULL), ("position", HOLD_POSITION)):
+        times = {"track": [], "solve": []}
+        for i in range(2 * (launches + 2)):
+            which = "track" if i % 2 else "solve"
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            if which == "track":
+                tracker.launch(per, mode, W, U, prm, pose)
+            elif mode == HOLD_FULL:
+                solver.launch(per, 1, ik_prm, 1e-3, 0.0, solve_only=True, mode=0, pose=pose)
+            else:
+                solver.launch(per, 1, ik_prm, 1e-3, 0.0, solve_only=True)
+            t1.record()
+            t1.synchronize()
+            if i >= 4:
+                times[which].append(1e3 * t0.elapsed_time(t1))
+        stat = lambda v: {"median": round(float(np.median(v)), 1), "min": round(float(np.min(v)), 1)}      # noqa: E731
+        out[name] = {"us_per_line_track_launch": stat(times["track"]),
+                     "us_per_ik_solve_pose_launch" if mode == HOLD_FULL else "us_per_ik_solve_launch": stat(times["solve"]),
+                     "track_over_solve_median": round(float(np.median(times["track"]) / np.median(times["solve"])), 3)}
+    usage = json.load(open(_lib.USAGE_PATH)) if os.path.exists(_lib.USAGE_PATH) else {}
+    regs = {name: {k: v.get(k) for k in ("vgprs", "sgprs", "scratch_bytes_per_lane", "occupancy")} for name, v in usage.items()
+            if "chain_line_track" in name}
+    print(json.dumps({"arm": os.path.basename(urdf), "lines": N, "lines_per_launch": per, "waypoints": W, "updates": U,
+                      "yardstick_iterations": W * U, **out,
+                      "ms_per_plan_linear_moves_call_host_clock": {"median": round(float(np.median(whole)), 2),
+                                                                   "min": round(float(np.min(whole)), 2)},
+                      "outcomes": {k: int(v) for k, v in zip(*np.unique(moves.outcome, return_counts=True))},
+                      "samples_per_leg": int(moves.samples[0]), "worst_position_error": float(np.nanmax(moves.position_error)),
+                      "worst_angle_error": float(np.nanmax(moves.angle_error)), "worst_line_deviation": float(np.nanmax(moves.line_deviation)),
+                      "start_poses_reachable_of": [int(goal.reachable.sum()), N], "kernel_registers": regs}))
+
+
 def kernels(a):
     import numpy as np
     import torch
@@ -863,7 +950,7 @@ def kernels(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["rate", "kernels", "step", "rollout", "gather", "ik", "path", "demo", "edgecert"])
+    ap.add_argument("what", choices=["rate", "kernels", "step", "rollout", "gather", "ik", "path", "demo", "edgecert", "line"])
     ap.add_argument("--urdf", default=os.path.join("tests", "golden", "urdf", "iiwa_like7.urdf"))
     ap.add_argument("--joints", type=int, default=7)
     ap.add_argument("--envs", type=int, default=64)
@@ -899,7 +986,7 @@ def main():
     if a.legs and not 2 <= a.legs <= 63:
         ap.error("--legs K splits two-leg plans into K legs, 2 .. 63")
     {"rate": rate, "kernels": kernels, "step": step, "rollout": rollout, "gather": gather, "ik": ik, "path": paths, "demo": demo,
-     "edgecert": edgecert}[a.what](a)
+     "edgecert": edgecert, "line": line}[a.what](a)
 
 
 if __name__ == "__main__":

@@ -994,6 +994,40 @@ int naf_chain_ik_solve_pose(naf_chain_env_t* h, const float* targets_dev, const 
                             naf_chain_ik_pose_params_t pose_params, float* q_out, float* residual_out, float* angle_out,
                             float* merit_out, float* iters_out, void* stream);
 
+/* Line moves (an addition within ABI 40): the end effector tracks a straight line in the world, orientation held — the last
+ * centimetres onto a part and the first ones away from it. environment/line_moves.py (track_line, line_verdict, plan_line_moves) is
+ * the float64 statement; the updates are the ones of "Goal poses" and "Oriented goal poses", unchanged.
+ *   per query n : q_start_dev[n][A], a pose inside the limits, and disp_dev[n][3], a displacement in the world, not zero.
+ *   counts      : W waypoints, 1 .. 63 (W + 1 nodes <= 64: the K-leg demonstration launch and the edge launch's V take them);
+ *                 U updates per waypoint, >= 1, W U <= 4096.
+ *   mode        : what is held. 0 (full): R_goal = R_ee(q_start). 1 (axis): d = R_ee(q_start) tool_axis, the roll about it free.
+ *                 2: position only. The goal is formed ONCE, from the walk at q_start, together with p0 = ee(q_start).
+ *   tracking    : node 0 is q_start as given. For i = 1 .. W: g_i = p0 + ((float)i / (float)W) disp, q = node[i - 1], then U updates
+ *                 towards g_i — modes 0 / 1 the update of "Oriented goal poses" with the held goal (tool_axis, tool_normal as there),
+ *                 mode 2 the update of "Goal poses"; the limits as those updates apply them; node[i] = q. The trip counts are fixed:
+ *                 the updates go on behind a waypoint that was missed.
+ *   the record  : NAF_CHAIN_TRACK_FLOATS floats per waypoint i: [0] the residual |g_i - ee(node[i])| | [1] the angle |e_w| at
+ *                 node[i], uncut; 0 in mode 2 | [2] max_m |node[i]_m - node[i - 1]_m| | [3] |ee((node[i - 1] + node[i]) / 2) -
+ *                 (p0 + (((float)i - 0.5f) / (float)W) disp)|: how far the joint-linear leg between two waypoints is from the line's
+ *                 point at its middle, an upper bound of the perpendicular deviation there.
+ *   the verdict : the host's, shared by device and twin (line_verdict): waypoint i is tracked iff [0] <= tolerance and [1] <=
+ *                 orientation_tolerance; K = the number of leading tracked waypoints. Collision is not the tracker's: the W legs go
+ *                 through naf_chain_edge_check.
+ *   line_track  : nodes_out [N][W + 1][A], track_out [N][W][4] (DEVICE); iters_out NULL or [W U + 1][N][A], the pose before the
+ *                 first and after every update (for tests): iters_out[i U] is node i. One lane per query, one wave per workgroup, no
+ *                 barrier, grid ceil(N / 64); the LDS record is naf_chain_ik_solve's; the lane's working pose lives in its row of
+ *                 nodes_out. params.iterations and pose_params.angle_length are not read; pose_params is not read in mode 2.
+ *                 NAF_ERR_ARG, and no launch, for a null pointer other than iters_out, N < 1, W outside 1 .. 63, U < 1,
+ *                 W U > 4096, a mode other than 0 / 1 / 2, any of lam2 / e_max / dq_max not finite and positive, and in modes 0 / 1
+ *                 weight or w_max not finite and positive or a tool axis or normal that is not finite. NAF_CHAIN_ERR_LDS as
+ *                 naf_chain_ik_solve.
+ *   Out of scope: arcs and splines, time parameterisation, a collision-aware or null-space iteration, re-seeding a lost line from
+ *                 another IK branch, interpolation between two orientations. */
+#define NAF_CHAIN_TRACK_FLOATS 4
+int naf_chain_line_track(naf_chain_env_t* h, const float* q_start_dev, const float* disp_dev, int mode, int N, int W, int U,
+                         naf_chain_ik_params_t params, naf_chain_ik_pose_params_t pose_params, float* nodes_out, float* track_out,
+                         float* iters_out, void* stream);
+
 /* Joint paths (an addition within ABI 40): the sampled collision check of joint-space polylines start -> via -> goal, batched over
  * queries and candidate vias. environment/kinematic.py (path_pose, check_joint_path) is the float64 statement. The check is SAMPLED:
  * a verdict holds at the S poses and says nothing between them; out[6] reports how far apart they are.

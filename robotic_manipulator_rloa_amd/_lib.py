@@ -284,6 +284,7 @@ _PROTOS = {
     "naf_chain_env_step_tagged": [_vp, _vp, _vp, _vp, _vp, _i, _u64, _vp, _i, _vp, _i, _vp],
     "naf_chain_ik_solve": [_vp, _vp, _vp, _vp, _i, _i, IkParams, _vp, _vp, _vp, _vp],
     "naf_chain_ik_solve_pose": [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, IkParams, IkPoseParams, _vp, _vp, _vp, _vp, _vp, _vp],
+    "naf_chain_line_track": [_vp, _vp, _vp, _i, _i, _i, _i, IkParams, IkPoseParams, _vp, _vp, _vp, _vp],
     "naf_chain_ik_select": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp],
     "naf_chain_path_check": [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _f, _vp, _vp, _vp],
     "naf_chain_path_certify": [_vp, _vp, _vp, _vp, _vp, _f, _vp, _f, _i, _i, _i, _f, _vp, _vp, _vp],

@@ -18,6 +18,7 @@ import torch
 from .environment.kinematic import (DEMO_MAX_TICKS, PATH_CANDIDATES_MAX, ROADMAP_MAX, JointPaths, demonstration_plan,
                                     demonstration_rows_host, demonstration_speed_ok, goal_poses_host, ik_restarts_ok, joint_paths_host,
                                     orientation_goal, reach_queries, roadmap_milestones, roadmap_size_ok, shortcut_size_ok)
+from .environment.line_moves import LINE_WAYPOINTS_MAX, line_waypoints_ok
 from .environment.polyline import SHORTCUT_MAX, SHORTCUT_MIN, pad_shortcut, polyline_plan, roadmap_arguments, roadmap_queries
 from .utils.exceptions import InvalidEnvironmentParameter
 from .utils.logger import get_global_logger
@@ -64,6 +65,8 @@ _ARGUMENT_RULES = {
     'orientation_tolerance': (lambda v: not isinstance(v, bool) and _finite_number(v) and v > 0.0, 'a positive angle in radians'),
     'orientation_weight': (lambda v: v is None or (not isinstance(v, bool) and _finite_number(v) and v > 0.0),
                            'a positive length per radian, or None for a quarter of the reach'),
+    'waypoints': (line_waypoints_ok, f'a number of waypoints from 1 to {LINE_WAYPOINTS_MAX}'),
+    'reverse': (lambda v: isinstance(v, (bool, np.bool_)), 'a bool'),
 }
 
 ORIENTATION_ARGUMENTS = ('orientations', 'approach_directions', 'tool_axis', 'orientation_tolerance', 'orientation_weight')

@@ -1131,14 +1131,16 @@ extern "C" int naf_chain_env_rollout_step(naf_chain_env_t* h, float* env_state, 
 // reads back only what it wrote. Joints behind the end-effector frame are not walked: their columns are 0.
 
 // walks joints 0 .. ee_frame - 1 at the joint values q; STORE: a_m | p_m to ax[(m * 6 + k) * 64]; returns the end effector in ee
-// and, with ROT, the end frame's rotation R_ee in rot[9], row-major
-template <bool STORE, bool ROT = false>
+// and, with ROT, the end frame's rotation R_ee in rot[9], row-major. MID: the walk is at the middle (q + q2) / 2 of two poses,
+// formed joint by joint as the walk reaches it — no pose array of the lane's own
+template <bool STORE, bool ROT = false, bool MID = false>
 __device__ static inline void ik_walk(const float* __restrict__ model, int n_joints, const float* q, float* ax, float* ee,
-                                      float* rot = nullptr) {
+                                      float* rot = nullptr, const float* q2 = nullptr) {
     Frame F = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
     for (int m = 0; m < n_joints; ++m) {
         const float* j = model + CH_HDR + m * CH_JNT;
-        const float qm = q[m];
+        float qm = q[m];
+        if constexpr (MID) qm = (qm + q2[m]) * 0.5f;
         F.px += F.r00 * j[9] + F.r01 * j[10] + F.r02 * j[11];
         F.py += F.r10 * j[9] + F.r11 * j[10] + F.r12 * j[11];
         F.pz += F.r20 * j[9] + F.r21 * j[10] + F.r22 * j[11];
@@ -1242,6 +1244,43 @@ __device__ __forceinline__ void ik_update(const float* __restrict__ model, int n
         q[m] = v;
         if constexpr (REC) rec[m] = v;
     }
+}
+
+// chain_ik_solve_kernel's update between its walk and ik_update, restated for chain_line_track_kernel expression for expression
+// (calling it from the solve kernel changed that kernel's code beyond scheduling, so the solve kernel keeps its own text): from the
+// walk's LDS record and ee towards (g0, g1, g2) it leaves dq_m in the record's first float and returns the dq_max scale
+__device__ __forceinline__ float ik_delta(const float* __restrict__ model, int n_joints, float* ax, const float* ee, float g0, float g1,
+                                          float g2, const naf_chain_ik_params_t& prm) {
+    float e0 = g0 - ee[0], e1 = g1 - ee[1], e2 = g2 - ee[2];
+    const float len = sqrtf(e0 * e0 + e1 * e1 + e2 * e2);
+    if (len > prm.e_max) {
+        const float s = prm.e_max / len;
+        e0 *= s; e1 *= s; e2 *= s;
+    }
+    // pass 1 over LDS: M = sum c c^T + lam^2 I
+    float m00 = prm.lam2, m01 = 0.f, m02 = 0.f, m11 = prm.lam2, m12 = 0.f, m22 = prm.lam2;
+    for (int m = 0; m < n_joints; ++m) {
+        float c[3];
+        ik_column(model, m, ax, ee, c);
+        m00 += c[0] * c[0]; m01 += c[0] * c[1]; m02 += c[0] * c[2];
+        m11 += c[1] * c[1]; m12 += c[1] * c[2]; m22 += c[2] * c[2];
+    }
+    // M y = e in closed form: the adjugate over the determinant
+    const float c00 = m11 * m22 - m12 * m12, c01 = m02 * m12 - m01 * m22, c02 = m01 * m12 - m02 * m11;
+    const float c11 = m00 * m22 - m02 * m02, c12 = m01 * m02 - m00 * m12, c22 = m00 * m11 - m01 * m01;
+    const float det = m00 * c00 + m01 * c01 + m02 * c02;
+    const float y0 = (c00 * e0 + c01 * e1 + c02 * e2) / det, y1 = (c01 * e0 + c11 * e1 + c12 * e2) / det,
+                y2 = (c02 * e0 + c12 * e1 + c22 * e2) / det;
+    // pass 2: dq_m = c_m . y, kept in the record's first float, and max |dq_m|
+    float big = 0.f;
+    for (int m = 0; m < n_joints; ++m) {
+        float c[3];
+        ik_column(model, m, ax, ee, c);
+        const float dq = c[0] * y0 + c[1] * y1 + c[2] * y2;
+        ax[m * 6 * 64] = dq;
+        big = fmaxf(big, fabsf(dq));
+    }
+    return big > prm.dq_max ? prm.dq_max / big : 1.f;
 }
 
 template <bool REC>
@@ -1493,6 +1532,53 @@ __device__ __forceinline__ void ik_spd6_solve(const float* M, const float* e, fl
     }
 }
 
+// chain_ik_pose_kernel's update between its walk and ik_update, restated for chain_line_track_kernel below expression for
+// expression (calling it from the pose kernel changed that kernel's register allocation and its fused multiply-adds, so the pose
+// kernel keeps its own text): from the walk's LDS record, ee and R_ee towards (g0, g1, g2) and the orientation goal it leaves dq_m
+// in the record's first float and returns the dq_max scale; ew is the caller's
+template <int MODE>
+__device__ __forceinline__ float ik_pose_delta(const float* __restrict__ model, int n_joints, float* ax, const float* ee, const float* rot,
+                                               float g0, float g1, float g2, const float* goal, const naf_chain_ik_params_t& prm,
+                                               const naf_chain_ik_pose_params_t& pp, float* ew) {
+    float e[6];
+    e[0] = g0 - ee[0]; e[1] = g1 - ee[1]; e[2] = g2 - ee[2];
+    const float len = sqrtf(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+    if (len > prm.e_max) {
+        const float s = prm.e_max / len;
+        e[0] *= s; e[1] *= s; e[2] *= s;
+    }
+    ik_orientation_error<MODE>(rot, goal, pp, ew);
+    const float wlen = sqrtf(ew[0] * ew[0] + ew[1] * ew[1] + ew[2] * ew[2]);
+    const float ws = wlen > pp.w_max ? pp.w_max / wlen : 1.f;
+    e[3] = pp.weight * (ew[0] * ws); e[4] = pp.weight * (ew[1] * ws); e[5] = pp.weight * (ew[2] * ws);
+    // pass 1 over LDS: M = sum c c^T + lam2 I, the 21 entries of its upper triangle
+    float M[21];
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = i; j < 6; ++j) M[ik_tri(i, j)] = i == j ? prm.lam2 : 0.f;
+    for (int m = 0; m < n_joints; ++m) {
+        float c[6];
+        ik_column6(model, m, ax, ee, pp.weight, c);
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = i; j < 6; ++j) M[ik_tri(i, j)] += c[i] * c[j];
+    }
+    float y[6];
+    ik_spd6_solve(M, e, y);
+    // pass 2: dq_m = c_m . y, kept in the record's first float, and max |dq_m|
+    float big = 0.f;
+    for (int m = 0; m < n_joints; ++m) {
+        float c[6];
+        ik_column6(model, m, ax, ee, pp.weight, c);
+        const float dq = c[0] * y[0] + c[1] * y[1] + c[2] * y[2] + c[3] * y[3] + c[4] * y[4] + c[5] * y[5];
+        ax[m * 6 * 64] = dq;
+        big = fmaxf(big, fabsf(dq));
+    }
+    return big > prm.dq_max ? prm.dq_max / big : 1.f;
+}
+
 // MODE 0: goals [N][9] = R_goal, 1: goals [N][3] = d. REC: iters_out as chain_ik_solve_kernel's
 template <int MODE, bool REC>
 __global__ void __launch_bounds__(64)
@@ -1601,6 +1687,122 @@ extern "C" int naf_chain_ik_solve_pose(naf_chain_env_t* h, const float* targets_
                          : go([](auto... a) { return ch_ik_pose_launch<0, false>(a...); });
     return iters_out ? go([](auto... a) { return ch_ik_pose_launch<1, true>(a...); })
                      : go([](auto... a) { return ch_ik_pose_launch<1, false>(a...); });
+}
+
+// ---- line moves: the end effector tracks a straight line in the world (include/naf_hip.h, "Line moves") --------------------------
+// The two solve kernels' shape — one lane per query, one wave per workgroup, no barrier, the [m][6][lane] LDS record — and their
+// updates: ik_pose_delta (MODE 0 full, 1 axis) or ik_delta (MODE 2, position only), then ik_update. The lane's working pose lives
+// in its row of nodes_out: row i starts as a copy of row i - 1, takes U updates towards g_i = p0 + (i / W) disp and stays. The
+// orientation goal (R_ee, or R_ee tool_axis) and p0 are formed once, from the walk at q_start. Behind a waypoint's updates two more
+// walks form its record: one at the node (residual, angle) and one at the middle of the leg that ends there, whose joint values
+// ik_walk<.., MID> forms from the two rows as it goes. Trip counts are W and U for every lane. REC: iters_out [W U + 1][N][A].
+template <int MODE, bool REC>
+__global__ void __launch_bounds__(64)
+chain_line_track_kernel(const float* __restrict__ model, const float* __restrict__ q_start, const float* __restrict__ disp, int N, int A,
+                        int W, int U, const naf_chain_ik_params_t prm, const naf_chain_ik_pose_params_t pp, float* nodes_out,
+                        float* __restrict__ track_out, float* __restrict__ iters_out) {
+    extern __shared__ __attribute__((aligned(16))) float ch_lds[];
+    constexpr bool ORIENT = MODE != 2;
+    constexpr int GOAL = MODE == 0 ? 9 : 3;
+    const int64_t n = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (n >= N) return;      // (one wave per workgroup and no barrier below)
+    const int n_joints = (int)model[4];
+    float* ax = ch_lds + threadIdx.x;
+    float* q = nodes_out + n * (W + 1) * A;
+    for (int m = 0; m < A; ++m) {
+        const float v = q_start[n * A + m];
+        q[m] = v;
+        if constexpr (REC) iters_out[n * A + m] = v;
+    }
+    const float d0 = disp[n * 3], d1 = disp[n * 3 + 1], d2 = disp[n * 3 + 2];
+    float ee[3], rot[9], ew[3], goal[GOAL];
+    ik_walk<false, ORIENT>(model, n_joints, q, ax, ee, rot);
+    const float p0 = ee[0], p1 = ee[1], p2 = ee[2];
+    if constexpr (MODE == 0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) goal[k] = rot[k];
+    } else if constexpr (MODE == 1) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            goal[k] = rot[k * 3] * pp.tool_axis[0] + rot[k * 3 + 1] * pp.tool_axis[1] + rot[k * 3 + 2] * pp.tool_axis[2];
+    }
+    const float fw = (float)W;
+    for (int i = 1; i <= W; ++i) {
+        const float* prev = q;
+        q += A;
+        for (int m = 0; m < A; ++m) q[m] = prev[m];
+        const float f = (float)i / fw;
+        const float g0 = p0 + f * d0, g1 = p1 + f * d1, g2 = p2 + f * d2;
+        for (int u = 0; u < U; ++u) {
+            float scale;
+            if constexpr (ORIENT) {
+                ik_walk<true, true>(model, n_joints, q, ax, ee, rot);
+                scale = ik_pose_delta<MODE>(model, n_joints, ax, ee, rot, g0, g1, g2, goal, prm, pp, ew);
+            } else {
+                ik_walk<true>(model, n_joints, q, ax, ee);
+                scale = ik_delta(model, n_joints, ax, ee, g0, g1, g2, prm);
+            }
+            ik_update<REC>(model, n_joints, A, scale, ax, q, REC ? iters_out + (((int64_t)(i - 1) * U + u + 1) * N + n) * A : nullptr);
+        }
+        // the waypoint's record: residual and angle at the node, the largest joint step, the leg's middle against the line's
+        ik_walk<false, ORIENT>(model, n_joints, q, ax, ee, rot);
+        const float e0 = g0 - ee[0], e1 = g1 - ee[1], e2 = g2 - ee[2];
+        float angle = 0.f;
+        if constexpr (ORIENT) {
+            ik_orientation_error<MODE>(rot, goal, pp, ew);
+            angle = sqrtf(ew[0] * ew[0] + ew[1] * ew[1] + ew[2] * ew[2]);
+        }
+        float step = 0.f;
+        for (int m = 0; m < A; ++m) step = fmaxf(step, fabsf(q[m] - prev[m]));
+        ik_walk<false, false, true>(model, n_joints, q, ax, ee, nullptr, prev);
+        const float fm = ((float)i - 0.5f) / fw;
+        const float h0 = ee[0] - (p0 + fm * d0), h1 = ee[1] - (p1 + fm * d1), h2 = ee[2] - (p2 + fm * d2);
+        float* rec = track_out + (n * W + (i - 1)) * NAF_CHAIN_TRACK_FLOATS;
+        rec[0] = sqrtf(e0 * e0 + e1 * e1 + e2 * e2);
+        rec[1] = angle;
+        rec[2] = step;
+        rec[3] = sqrtf(h0 * h0 + h1 * h1 + h2 * h2);
+    }
+}
+
+template <int MODE, bool REC, typename... Args>
+static int ch_line_track_launch(unsigned grid, size_t lds, void* stream, Args... args) {
+    const int rc = ch_raise<chain_line_track_kernel<MODE, REC>>();
+    if (rc != NAF_OK) return rc;
+    chain_line_track_kernel<MODE, REC><<<grid, 64, lds, (hipStream_t)stream>>>(args...);
+    NAF_CHECK_LAUNCH();
+    return NAF_OK;
+}
+
+extern "C" int naf_chain_line_track(naf_chain_env_t* h, const float* q_start_dev, const float* disp_dev, int mode, int N, int W, int U,
+                                    naf_chain_ik_params_t params, naf_chain_ik_pose_params_t pose_params, float* nodes_out,
+                                    float* track_out, float* iters_out, void* stream) {
+    if (!h || !q_start_dev || !disp_dev || !nodes_out || !track_out || N < 1 || W < 1 || W > 63 || U < 1 || (int64_t)W * U > 4096 ||
+        mode < 0 || mode > 2)
+        return NAF_ERR_ARG;
+    const auto positive = [](float v) { return std::isfinite(v) && v > 0.f; };
+    if (!positive(params.lam2) || !positive(params.e_max) || !positive(params.dq_max)) return NAF_ERR_ARG;
+    if (mode != 2) {
+        if (!positive(pose_params.weight) || !positive(pose_params.w_max)) return NAF_ERR_ARG;
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(pose_params.tool_axis[k]) || !std::isfinite(pose_params.tool_normal[k])) return NAF_ERR_ARG;
+    }
+    const size_t lds = (size_t)std::max(h->ee_frame, 1) * 6 * 64 * sizeof(float);
+    if (lds > CH_MAX_DYN_LDS) return NAF_CHAIN_ERR_LDS;
+    const unsigned grid = (unsigned)(((int64_t)N + 63) / 64);
+    const auto go = [&](auto launch) {
+        return launch(grid, lds, stream, h->model_dev, q_start_dev, disp_dev, N, h->A, W, U, params, pose_params, nodes_out, track_out,
+                      iters_out);
+    };
+    // the dynamic LDS (1536 bytes per walked joint) may exceed the 64 KB a kernel gets unasked: the launched instantiation is raised
+    if (mode == 0)
+        return iters_out ? go([](auto... a) { return ch_line_track_launch<0, true>(a...); })
+                         : go([](auto... a) { return ch_line_track_launch<0, false>(a...); });
+    if (mode == 1)
+        return iters_out ? go([](auto... a) { return ch_line_track_launch<1, true>(a...); })
+                         : go([](auto... a) { return ch_line_track_launch<1, false>(a...); });
+    return iters_out ? go([](auto... a) { return ch_line_track_launch<2, true>(a...); })
+                     : go([](auto... a) { return ch_line_track_launch<2, false>(a...); });
 }
 
 // ---- line sweeps: the sampled collision check of a line in joint space (include/naf_hip.h, "Joint paths", "Roadmap edges") -------

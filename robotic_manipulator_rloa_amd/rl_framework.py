@@ -421,6 +421,41 @@ class ManipulatorFramework:
         planner = self._kinematic_planner('certify_joint_paths', 'chain model to certify on')
         return certify_joint_paths(planner, paths, obstacles, clearance_margin, resolution, on_device)
 
+    def plan_linear_moves(self, joint_positions, displacements, obstacles=None, hold: str = 'orientation',
+                          tool_axis=(0.0, 0.0, 1.0), waypoints: int = 32, updates: int = 4, tolerance: float = 1e-3,
+                          orientation_tolerance: float = 1e-3, resolution: float = 0.02, clearance_margin: float = 0.0,
+                          reverse: bool = False, on_device: Optional[bool] = None):
+        """Straight-line end-effector moves (kinematic environment only; needs no agent): from each given pose the end effector
+        travels along a displacement in the world, orientation held — the last centimetres onto a part, the first ones away from
+        it. The line is cut into `waypoints` equal parts; each waypoint is solved from the previous one's pose by `updates`
+        damped least-squares updates (the ones of solve_goal_poses; environment/line_moves.py states the rule), so the joints
+        follow one IK branch; then the joint-space legs between the waypoints are SAMPLED for collisions as plan_joint_paths
+        samples its legs.
+          joint_positions : [N][A], or [A] for one query: the poses the lines begin at (solve_goal_poses().joint_positions),
+                            inside the limits
+          displacements   : [N][3], or [3] for all queries: how far the end effector is to travel, metres in the world; not zero
+          obstacles       : as reach_targets() takes them
+          hold            : 'orientation': the end effector keeps the orientation it has at the given pose | 'axis': tool_axis (a
+                            direction in the end-effector frame) keeps pointing where it points, the roll about it free |
+                            'position': the orientation is free
+          waypoints       : 1 .. 63; updates: at least 1, waypoints x updates <= 4096
+          tolerance, orientation_tolerance : a waypoint is tracked iff it is within both of its line point and the held orientation
+          resolution, clearance_margin     : the legs' sample step and the margin, as plan_joint_paths takes them
+          reverse         : the nodes run from the far end to the given pose — the move is the approach; first_lost and
+                            first_blocked_leg keep counting from the given pose
+          on_device       : None: the device when there is one (one naf_chain_line_track launch and one naf_chain_edge_check
+                            launch per chunk); False: the float64 host twin under the same rule (slow)
+        Returns environment.line_moves.LinearMoves, arrays over the queries: outcome ('tracked' | 'lost': a waypoint missed a
+        tolerance — a joint limit, the reach, a singularity | 'blocked': a leg of the tracked part has a blocked sample | 'start':
+        the given pose is), fraction (the collision-free tracked share of the line), first_lost, first_blocked_leg, position_error,
+        angle_error, joint_step, line_deviation (how far a leg's middle is from the line), the three minima, sample_step, samples,
+        nodes [N][waypoints + 1][A], n_nodes, start, goal, end_effector_start, displacement. as_joint_paths() hands the 'tracked'
+        lines to certify_joint_paths() and demonstrate_joint_paths(polylines=True)."""
+        from .arm_line import plan_linear_moves
+        planner = self._kinematic_planner('plan_linear_moves', 'chain model to track a line on')
+        return plan_linear_moves(planner, joint_positions, displacements, obstacles, hold, tool_axis, waypoints, updates, tolerance,
+                                 orientation_tolerance, resolution, clearance_margin, reverse, on_device)
+
     def _check_demonstrations(self, demos, E) -> None:
         if not isinstance(demos, Demonstrations):
             raise InvalidNAFAgentParameter('demonstrations is the Demonstrations that demonstrate_joint_paths() returned')
