@@ -22,6 +22,7 @@ ARMS = {
     "standin8": (7, list(range(8)), [], [0.9, 0.45, 0, 0, 0, 0, 0, 0], [0.1] * 8),
     "long12": (11, list(range(12)), [], [0.1 * ((k % 5) - 2) for k in range(12)], [0.05] * 12),
     "long32": (31, list(range(32)), [], [0.1 * ((k % 5) - 2) for k in range(32)], [0.05] * 32),
+    "slider4": (3, [0, 1, 2, 3], [], [0.2, 0.1, 0.3, 0.1], [0.1] * 4),      # chain_ik_common.slider's: joints 1 and 3 prismatic
 }
 
 
@@ -93,7 +94,8 @@ def test_standin8_is_the_stand_ins_chain():
 
 # ---- 2. an independent forward kinematics ---------------------------------------------------------------------------------
 def independent_fk(name, q_by_joint_index):
-    """4 x 4 homogeneous matrices over the URDF tree, scipy rotations, read from the XML here: {link: T_world_link}."""
+    """4 x 4 homogeneous matrices over the URDF tree, scipy rotations, read from the XML here: {link: T_world_link}, and under
+    ("joint", k) the frame of joint k's origin."""
     import xml.etree.ElementTree as ET
     from scipy.spatial.transform import Rotation
     root = ET.parse(path(name)).getroot()
@@ -124,6 +126,7 @@ def independent_fk(name, q_by_joint_index):
         elif j.get("type") == "prismatic":
             ax = np.array([float(v) for v in j.find("axis").get("xyz").split()])
             Q[:3, 3] = ax / np.linalg.norm(ax) * q
+        T[("joint", k)] = T[parent] @ M                           # the joint's origin, before its own motion
         T[j.find("child").get("link")] = T[parent] @ M @ Q
     return T, joints, root
 
@@ -144,8 +147,10 @@ def test_twin_agrees_with_an_independent_fk(name):
             local = np.array([float(v) for v in el.find("inertial/origin").get("xyz").split()])
         want = (T[link] @ np.append(local, 1.0))[:3]
         assert np.abs(env.end_effector(q) - want).max() <= 1e-12 * env.model.reach
-    # every capsule's ends are joint origins (or the tip) of that independent tree
-    ends = [T[j.find("child").get("link")][:3, 3] for j in joints] + [want, np.zeros(3)]
+    # every capsule's ends are joint origins (or the tip) of that independent tree: a link's capsule ends where its child joint
+    # sits on it, which a prismatic joint's travel (slider4) carries the child link's own origin away from
+    ends = [T[("joint", k)][:3, 3] for k in range(len(joints))] + [T[j.find("child").get("link")][:3, 3] for j in joints] + \
+        [want, np.zeros(3)]
     for a, b, _ in env.world_segments(q):
         for p in (a, b):
             assert min(np.abs(p - e).max() for e in ends) <= 1e-12 * env.model.reach
@@ -343,7 +348,8 @@ def test_pack_round_trip_and_model_check(name):
     assert check(blob) == 0
     import hashlib
     assert m.digest() == hashlib.sha256(blob.tobytes()).hexdigest() and len(m.digest()) == 64
-    assert abs(m.reach - (sum(np.linalg.norm(j.pre_xyz) for j in m.joints) + np.linalg.norm(m.ee_point))) < 1e-12
+    travel = sum(max(abs(j.lower), abs(j.upper)) for j in m.joints if j.type == UC.PRISMATIC and j.limited)      # (slider4's 0.4 + 0.3)
+    assert abs(m.reach - (sum(np.linalg.norm(j.pre_xyz) for j in m.joints) + np.linalg.norm(m.ee_point) + travel)) < 1e-12
     bad = blob.copy()
     bad[0] = 2
     assert check(bad) == -11                                  # NAF_CHAIN_ERR_VERSION

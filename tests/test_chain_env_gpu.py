@@ -197,7 +197,7 @@ def run_case(name, E, rig_factory):
 
 
 @pytest.mark.parametrize("E", [1, 64, 100])
-@pytest.mark.parametrize("name", ["planar3", "iiwa_like7", "arm_with_gripper", "long12", "long32"])
+@pytest.mark.parametrize("name", ["planar3", "iiwa_like7", "arm_with_gripper", "long12", "long32", "slider4"])
 def test_kernel_against_twin(name, E):
     """Teacher-forced (the twin starts every step from the kernel's joint state): (a) 300 steps of N(0, 1) actions from reset,
     in episodes of up to 4 steps with the obstacle at contact distance from the initial pose's tip; (b) 300 scattered
