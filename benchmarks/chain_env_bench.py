@@ -40,6 +40,9 @@ launches are the box instantiations, which test the floor and the spheres too.
       solve -> reset_given -> probes -> select, downloads), each between device events, median and minimum of `--launches` after
       two unmeasured ones; the reachable and free shares; and the float64 host twin's seconds on the first 64 of the queries,
       with its time for all N EXTRAPOLATED from those 64 (it is linear in N) — that figure is not a measurement.
+      `--avoid-contact`: also the shares and the whole call's time with solve(avoid_contact=True), and naf_chain_ik_clear (16
+      updates on the solved candidates) timed alternating, launch by launch in this process, with naf_chain_ik_solve at the same
+      16 updates and with reset_given + probe + probe_cell over the same candidates.
 
   python benchmarks/chain_env_bench.py path [--envs 2048] [--launches 20] [--boxes] [--certify | --roadmap M]
       collision-checked joint paths on --urdf with self-collision inside the --workcell cell (always on for this subcommand): N =
@@ -356,6 +359,7 @@ def ik(a):
         if i >= 2:
             kernel.append(1e3 * t0.elapsed_time(t1))
     oriented = _ik_oriented(a, solver, q0, targets, obstacles, R, K, per, prm) if a.orientation else None
+    pushed = _ik_avoid_contact(a, solver, q0, targets, obstacles, R, K, per) if a.avoid_contact else None
     twin = KinematicEnvironment(model, (0.45, 0.3, 0.6), (0.35, 0.2, 0.45), 0.06)
     t = time.perf_counter()
     host = goal_poses_host(twin, q0[:64], targets[:64], obstacles[:64], restarts=R, iterations=K)
@@ -371,7 +375,61 @@ def ik(a):
                       "twin_seconds_for_64_queries": round(twin_s, 3),
                       "twin_seconds_for_all_queries_EXTRAPOLATED_from_64": round(twin_s * N / 64, 1),
                       "twin_and_device_agree_on_reachable_of_64": int(np.sum(host.reachable == out.reachable[:64])),
-                      "kernel_registers": regs, **({"orientation": oriented} if oriented else {})}))
+                      "kernel_registers": regs, **({"orientation": oriented} if oriented else {}),
+                      **({"avoid_contact": pushed} if pushed else {})}))
+
+
+def _ik_avoid_contact(a, solver, q0, targets, obstacles, R, K, per) -> dict:
+    """ik --avoid-contact: the same queries with the null-space push — the shares and the whole call's time, then three launches
+    timed alternating in this process on the last chunk's candidates: naf_chain_ik_clear, naf_chain_ik_solve at the same trip count,
+    and reset_given + probe + probe_cell."""
+    import numpy as np
+    import torch
+    from robotic_manipulator_rloa_amd._lib import check, ptr, stream_ptr
+    whole = []
+    for i in range(a.launches + 2):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        out = solver.solve(q0, targets, obstacles, restarts=R, iterations=K, avoid_contact=True)
+        t1.record()
+        t1.synchronize()
+        if i >= 2:
+            whole.append(t0.elapsed_time(t1))
+    clear = solver.clear_params(1e-3)
+    short, E = solver.params(clear[0].iterations), per * R
+    solver.launch(per, R, solver.params(K), 1e-3, 0.0, solve_only=True)      # the candidates the clear launch works on
+    solved = solver.q.clone()
+
+    def probes():
+        st = stream_ptr()
+        check(solver.lib.naf_chain_env_reset_given(solver._chain_env, ptr(solver.env_state), ptr(solver.obs), E, ptr(solver.q),
+                                                   ptr(solver.scene), solver.obstacle_radius, st), "reset_given")
+        check(solver.lib.naf_chain_env_probe(solver._chain_env, ptr(solver.env_state), ptr(solver.probe), E, st), "probe")
+        check(solver.lib.naf_chain_env_probe_cell(solver._chain_env, ptr(solver.env_state), ptr(solver.cell), E, st), "probe_cell")
+
+    def clear_launch():
+        solver.q.copy_(solved)                                               # (in place: every launch refines the solved poses)
+        return lambda: solver.launch_clear(per, R, clear)
+    kinds = {"clear": clear_launch, "solve_same_updates": lambda: (lambda: solver.launch(per, R, short, 1e-3, 0.0, solve_only=True)),
+             "reset_given_and_probes": lambda: probes}
+    times = {k: [] for k in kinds}
+    for i in range(3 * (a.launches + 2)):
+        which = list(kinds)[i % 3]
+        run = kinds[which]()
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        run()
+        t1.record()
+        t1.synchronize()
+        if i >= 6:
+            times[which].append(1e3 * t0.elapsed_time(t1))
+    stat = lambda v: {"median": round(float(np.median(v)), 1), "min": round(float(np.min(v)), 1)}      # noqa: E731
+    return {"updates": int(clear[0].iterations), "candidates": E, "us_per_ik_clear_launch": stat(times["clear"]),
+            "us_per_ik_solve_launch_same_updates": stat(times["solve_same_updates"]),
+            "us_per_reset_given_probe_probe_cell": stat(times["reset_given_and_probes"]),
+            "clear_over_solve_median": round(float(np.median(times["clear"]) / np.median(times["solve_same_updates"])), 3),
+            "ms_per_solve_goal_poses_call": stat(whole), "reachable_share": round(float(out.reachable.mean()), 4),
+            "free_share": round(float(out.free.mean()), 4), "pushed_share": round(float(out.pushed.mean()), 4)}
 
 
 def _ik_oriented(a, solver, q0, targets, obstacles, R, K, per, prm) -> dict:
@@ -972,6 +1030,8 @@ def main():
                     help="demo: time naf_chain_demo_rows_legs, the same plans split into K legs, beside naf_chain_demo_rows")
     ap.add_argument("--orientation", choices=["full", "axis"], default=None,
                     help="ik: also solve the section's queries with an orientation goal and time naf_chain_ik_solve_pose beside naf_chain_ik_solve")
+    ap.add_argument("--avoid-contact", action="store_true",
+                    help="ik: also solve with the null-space push and time naf_chain_ik_clear beside naf_chain_ik_solve and the probes")
     ap.add_argument("--trajectory", action="store_true", help="rollout: record the joint values of every frame")
     ap.add_argument("--arm", default="", help="rate: a fixture arm of tests/golden/urdf by name, --joints its joint count")
     ap.add_argument("--target-range", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))

@@ -949,6 +949,54 @@ int naf_chain_ik_select(naf_chain_env_t* h, const float* q_out, const float* q_s
                         const float* probe_dev, const float* cell_dev, int N, int R, float tolerance, float margin, int* choice_out,
                         int* class_out, float* joint_distance_out, void* stream);
 
+/* Goal poses out of contact (an addition within ABI 40: one entry point and one params struct, nothing above changes). One launch
+ * between naf_chain_ik_solve and the clearances: every candidate that is converged but closer than clearance_goal to the obstacle,
+ * the arm itself or the workcell is refined by updates that keep the end effector on the target and push the pose away from the
+ * one least clearance test, in the task's null space (Maciejewski & Klein's obstacle-avoidance point velocity). Positional goals
+ * only. environment/kinematic.py (least_test, clearance_gradient, ik_clear_step, refine_goal_poses) is the float64 statement.
+ *   A candidate is (query n, restart r), index n R + r, as under "Goal poses": target targets_dev[n], obstacle centre
+ *   obstacles_dev[n] ([N][3]), pose q_in_dev[n R + r] (naf_chain_ik_solve's q_out).
+ *   the rule    : iterate 0 is the input pose; then `params.iterations` = K updates, a fixed trip count. Each walk of ALL A driven
+ *                 joints gives ee, (a_m, p_m) for every m, the capsules' world end points, and the least test c(q): the minimum
+ *                 over (capsule, obstacle) of distance - capsule radius - obstacle radius, over every masked (capsule, workcell
+ *                 geometry) pair and over every self pair — min(probe [3], probe [4], probe_cell) — with its witness: the point x
+ *                 on the capsule's axis where the distance is attained, the unit direction n from the geometry's nearest point to
+ *                 x (a half-space: the end point with the smaller n.x and the plane's normal; a box: the parameter the box
+ *                 distance ends with and the clamp of that point; a pair: whichever of the five candidates is least, n from the
+ *                 second point x' to x), the capsule's frame f and a pair's second frame f'. A witness distance below 1e-6: n = 0.
+ *                 Tests are taken per capsule — obstacle, spheres, half-spaces, boxes — then the pairs; a later one replaces the
+ *                 least only when smaller.
+ *                   gamma_m = n . (a_m x (x - p_m)) revolute | n . a_m prismatic, for m < f, else 0; a pair subtracts the same at
+ *                   (x', f');  the task step is naf_chain_ik_solve's (e, M, y, dq scaled to dq_max);  z = M^-1 sum_m c_m gamma_m;
+ *                   h_m = gamma_m - c_m . z;  sigma = sum gamma_m h_m;  while c < clearance_goal, update index k < K - settle and
+ *                   sigma > 1e-6 the push is h (clearance_goal - c) / sigma, scaled so that max |.| <= push_max;
+ *                   q_m += dq_m + push_m, then the position limits as a step applies them.
+ *                 Every walk — the K before the updates and one after the last — yields (residual, c); the returned pose is the
+ *                 iterate with the largest min(c, clearance_goal) among those with residual <= tolerance, ties to the earliest. A
+ *                 candidate whose input has c >= clearance_goal or residual > tolerance returns after its first walk, its pose
+ *                 bit for bit.
+ *   ik_clear    : q_out [N R][A] the returned pose (may be q_in_dev itself: a lane reads and writes its own row only), q_work
+ *                 [N R][A] the running one (distinct from both), residual_out [N R] the residual at the returned pose, clear_out
+ *                 [N R][4] = c at the input | c at the returned pose | the returned iterate's index | the kind of the least test
+ *                 there, 0 obstacle, 1 self, 2 workcell (all DEVICE). iters_out and rec_out, both NULL or both DEVICE (for tests):
+ *                 iters_out [K + 1][N R][A] the pose before the first and after every update, rec_out [K][N R][A + 2] gamma | c |
+ *                 kind at each update's walk; a candidate that returned after its first walk repeats its pose, with gamma 0.
+ *                 One lane per candidate, one wave per workgroup, no barrier; LDS 1536 bytes per driven joint and per segment:
+ *                 NAF_CHAIN_ERR_LDS, and no launch, above the 144 KiB the handle's kernels may ask for. NAF_ERR_ARG, and no launch,
+ *                 for a null pointer (other than the two recording ones together), q_work aliasing q_out or q_in_dev, the counts
+ *                 as above, K < 1, settle outside [0, K], lam2 / e_max / dq_max / push_max not finite and positive, tolerance or
+ *                 obstacle_radius not finite or negative, clearance_goal not finite. */
+typedef struct {
+    int32_t settle;           /* the last `settle` updates apply no push, 0 .. iterations */
+    float tolerance;          /* a pose is converged iff residual <= tolerance */
+    float clearance_goal;     /* c*: the push lifts the least test to it and no further */
+    float push_max;           /* the largest joint update of one push, max-norm */
+    float obstacle_radius;
+} naf_chain_ik_clear_params_t;
+int naf_chain_ik_clear(naf_chain_env_t* h, const float* targets_dev, const float* obstacles_dev, const float* q_in_dev, int N, int R,
+                       naf_chain_ik_params_t params, naf_chain_ik_clear_params_t clear_params, float* q_out, float* q_work,
+                       float* residual_out, float* clear_out, float* iters_out, float* rec_out, void* stream);
+
 /* Oriented goal poses (an addition within ABI 40): naf_chain_ik_solve with an end-effector orientation in the goal. environment/kinematic.py
  * (end_effector_frame, orientation_error, spd6_solve, ik_pose_step, solve_ik_pose) is the float64 statement. Candidates, seeds, counts
  * and the clearances are as under "Goal poses"; naf_chain_ik_select is fed merit_out in the place of residual_out and is unchanged.

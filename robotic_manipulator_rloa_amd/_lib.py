@@ -176,6 +176,12 @@ class IkPoseParams(C.Structure):
                 ("tool_normal", C.c_float * 3)]
 
 
+class IkClearParams(C.Structure):
+    """naf_chain_ik_clear_params_t (include/naf_hip.h)"""
+    _fields_ = [("settle", C.c_int32), ("tolerance", C.c_float), ("clearance_goal", C.c_float), ("push_max", C.c_float),
+                ("obstacle_radius", C.c_float)]
+
+
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/naf_hip.h one to one
 _PROTOS = {
     "naf_hip_abi_version": [],
@@ -286,6 +292,7 @@ _PROTOS = {
     "naf_chain_ik_solve_pose": [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, IkParams, IkPoseParams, _vp, _vp, _vp, _vp, _vp, _vp],
     "naf_chain_line_track": [_vp, _vp, _vp, _i, _i, _i, _i, IkParams, IkPoseParams, _vp, _vp, _vp, _vp],
     "naf_chain_ik_select": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp],
+    "naf_chain_ik_clear": [_vp, _vp, _vp, _vp, _i, _i, IkParams, IkClearParams, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "naf_chain_path_check": [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _f, _vp, _vp, _vp],
     "naf_chain_path_certify": [_vp, _vp, _vp, _vp, _vp, _f, _vp, _f, _i, _i, _i, _f, _vp, _vp, _vp],
     "naf_chain_demo_rows": [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _i, _vp, _vp, _vp],

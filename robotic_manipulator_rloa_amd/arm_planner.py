@@ -15,7 +15,7 @@ import weakref
 import numpy as np
 import torch
 
-from .environment.kinematic import (DEMO_MAX_TICKS, PATH_CANDIDATES_MAX, ROADMAP_MAX, JointPaths, demonstration_plan,
+from .environment.kinematic import (DEMO_MAX_TICKS, PATH_CANDIDATES_MAX, PUSH_ORIENTATION_REFUSAL, ROADMAP_MAX, JointPaths, demonstration_plan,
                                     demonstration_rows_host, demonstration_speed_ok, goal_poses_host, ik_restarts_ok, joint_paths_host,
                                     orientation_goal, reach_queries, roadmap_milestones, roadmap_size_ok, shortcut_size_ok)
 from .environment.line_moves import LINE_WAYPOINTS_MAX, line_waypoints_ok
@@ -65,6 +65,9 @@ _ARGUMENT_RULES = {
     'orientation_tolerance': (lambda v: not isinstance(v, bool) and _finite_number(v) and v > 0.0, 'a positive angle in radians'),
     'orientation_weight': (lambda v: v is None or (not isinstance(v, bool) and _finite_number(v) and v > 0.0),
                            'a positive length per radian, or None for a quarter of the reach'),
+    'avoid_contact': (lambda v: isinstance(v, (bool, np.bool_)), 'a bool'),
+    'clearance_goal': (lambda v: v is None or (not isinstance(v, bool) and _finite_number(v)), 'a finite length, or None for clearance_margin + 0.02'),
+    'push_iterations': (lambda v: not isinstance(v, bool) and _positive_int(v) and v >= 4, 'a number of updates, at least 4 (the last four settle without a push)'),
     'waypoints': (line_waypoints_ok, f'a number of waypoints from 1 to {LINE_WAYPOINTS_MAX}'),
     'reverse': (lambda v: isinstance(v, (bool, np.bool_)), 'a bool'),
 }
@@ -88,6 +91,20 @@ def check_orientation(orientation, N: int, tolerance: float = 1e-3) -> dict:
         orientation_goal(N, kw.get('orientations'), kw.get('approach_directions'), kw.get('tool_axis', (0.0, 0.0, 1.0)), tolerance,
                          kw.get('orientation_tolerance', 1e-3))
     return kw
+
+
+def check_push(push, orientation) -> dict:
+    """The avoid_contact keyword arguments of a call through their refusals: {} where no push is asked for, otherwise the arguments
+    as the solvers take them. Positional goals only: refused together with an orientation goal."""
+    if not push:
+        return {}
+    check_arguments(avoid_contact=push.get('avoid_contact', False))
+    if not push.get('avoid_contact'):
+        return {}
+    check_arguments(clearance_goal=push.get('clearance_goal'), push_iterations=push.get('push_iterations', 16))
+    if orientation_given(orientation):
+        raise InvalidEnvironmentParameter(PUSH_ORIENTATION_REFUSAL)
+    return dict(avoid_contact=True, clearance_goal=push.get('clearance_goal'), push_iterations=int(push.get('push_iterations', 16)))
 
 
 def check_arguments(**given) -> None:
@@ -145,11 +162,12 @@ class ArmPlanner:
 
     # ---- goal poses ---------------------------------------------------------------------------------------------------------------
     def solve_goal_poses(self, targets, obstacles, initial_joint_positions, restarts, iterations, tolerance, clearance_margin, seed,
-                         on_device, orientation=None):
+                         on_device, orientation=None, push=None):
         check_arguments(restarts=restarts, iterations=iterations, tolerance=tolerance, clearance_margin=clearance_margin, seed=seed)
+        push = check_push(push, orientation)
         q0, targets, obstacles, _ = self.queries(targets, obstacles, initial_joint_positions)
         kw = dict(restarts=int(restarts), iterations=int(iterations), tolerance=float(tolerance), margin=float(clearance_margin),
-                  seed=int(seed), **check_orientation(orientation, len(q0), float(tolerance)))
+                  seed=int(seed), **check_orientation(orientation, len(q0), float(tolerance)), **push)
         if not _on_device(on_device):
             return goal_poses_host(self.env, q0, targets, obstacles, **kw)
         from .chain_tools import GoalPoseSolver
@@ -179,13 +197,17 @@ class ArmPlanner:
         return q0, q_goal, obstacles
 
     def plan_joint_paths(self, targets, obstacles, initial_joint_positions, goal_joint_positions, candidates, resolution,
-                         clearance_margin, seed, on_device, certify, roadmap, shortcut=0, orientation=None):
+                         clearance_margin, seed, on_device, certify, roadmap, shortcut=0, orientation=None, push=None):
         model = self.env.model
         if (targets is None) == (goal_joint_positions is None):
             raise InvalidEnvironmentParameter('plan_joint_paths() takes exactly one of targets and goal_joint_positions')
         if goal_joint_positions is not None and orientation_given(orientation):
             raise InvalidEnvironmentParameter('plan_joint_paths(goal_joint_positions=) is given the goal poses themselves: orientations '
                                               'and approach_directions are goals of the poses solved for targets')
+        if goal_joint_positions is not None and push and push.get('avoid_contact'):
+            raise InvalidEnvironmentParameter('plan_joint_paths(goal_joint_positions=) is given the goal poses themselves: avoid_contact '
+                                              'refines the poses solved for targets')
+        push = check_push(push, orientation)
         check_arguments(candidates=candidates, resolution=resolution, clearance_margin=clearance_margin, seed=seed, certify=certify)
         check_roadmap(roadmap, certify, 'plan_joint_paths', shortcut)
         if roadmap:
@@ -199,7 +221,7 @@ class ArmPlanner:
             return self.plan_checked(*self._goal_queries(goal_joint_positions, obstacles, initial_joint_positions), **kw)
         q0, targets, obstacles, _ = self.queries(targets, obstacles, initial_joint_positions)
         goal = self._framework().solve_goal_poses(targets, obstacles, q0, seed=seed, on_device=on_device,
-                                                  **check_orientation(orientation, len(q0)))
+                                                  **check_orientation(orientation, len(q0)), **push)
         return self.paths_to_goals(goal, q0, obstacles, kw)
 
     def plan_checked(self, q0, q_goal, obstacles, candidates=16, resolution=0.02, clearance_margin=0.0, seed=0, on_device=None,
@@ -276,7 +298,7 @@ class ArmPlanner:
 
     # ---- rollouts to given targets ------------------------------------------------------------------------------------------------
     def reach_targets(self, agent, targets, obstacles, initial_joint_positions, frames, noise_scale, n_envs, trajectories, goal_poses,
-                      joint_paths, certify, roadmap, shortcut=0, orientation=None):
+                      joint_paths, certify, roadmap, shortcut=0, orientation=None, push=None):
         """the queries and the refusals of reach_targets(), the agent's rollout, then the goal poses, the paths and their ratios"""
         env = self.env
         q0, targets, obstacles, frames = self.queries(targets, obstacles, initial_joint_positions, frames)
@@ -284,6 +306,10 @@ class ArmPlanner:
         if orientation_given(orientation) and not goal_poses:
             raise InvalidEnvironmentParameter('reach_targets(orientations= / approach_directions=) is a goal of the goal poses: it needs '
                                               'goal_poses=True or joint_paths=True (the policy and its outcome know no orientation)')
+        if push and push.get('avoid_contact') and not goal_poses:
+            raise InvalidEnvironmentParameter('reach_targets(avoid_contact=True) refines the goal poses: it needs goal_poses=True or '
+                                              'joint_paths=True')
+        push = check_push(push, orientation)
         orientation = check_orientation(orientation, len(q0))
         if not isinstance(certify, (bool, np.bool_)) or (certify and not joint_paths):
             raise InvalidEnvironmentParameter('reach_targets(certify=True) certifies the joint paths: it is a bool and needs joint_paths=True')
@@ -295,7 +321,7 @@ class ArmPlanner:
         result = agent.rollout_vectorized(env.model, targets, obstacles, q0, frames=frames, noise_scale=float(noise_scale),
                                           n_envs=n_envs, trajectories=bool(trajectories), scene={'obstacle_radius': env.obstacle_radius})
         if goal_poses:
-            result.goal = self._framework().solve_goal_poses(targets, obstacles, q0, **orientation)
+            result.goal = self._framework().solve_goal_poses(targets, obstacles, q0, **orientation, **push)
             path = np.asarray(result.joint_positions, np.float64)
             length = np.sum(np.max(np.abs(np.diff(path, axis=1)), axis=2), axis=1)
             with np.errstate(divide='ignore', invalid='ignore'):

@@ -23,10 +23,12 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
+from .chain_clear import ClearLaunch
 from .chain_legs import LegsLaunch
 from .environment.kinematic import (DEMO_CHUNK, DEMO_FLOATS, DEMO_MAX_TICKS, EDGE_FLOATS, PATH_CERT_FLOATS, PATH_CHUNK, PATH_FLOATS,
                                     GoalPoses, JointPaths, certificate_guard, concatenate_goal_poses, demo_row_layout,
-                                    gather_demonstrations, gather_goal_poses, ik_seeds, orientation_goal, plan_paths, reach_table)
+                                    gather_demonstrations, gather_goal_poses, ik_seeds, note_pushed, orientation_goal, plan_paths,
+                                    reach_table)
 
 
 class _ChainHandle:
@@ -77,14 +79,17 @@ class _ChainTool(_ChainHandle):
         return out.reshape(shape) if shape else out
 
 
-class GoalPoseSolver(_ChainTool):
+class GoalPoseSolver(ClearLaunch, _ChainTool):
     """Goal poses on a chain model (csrc/chain_env.hip, "goal poses"): per chunk of candidates naf_chain_ik_solve, then the
     clearances of the solved poses by naf_chain_env_reset_given + naf_chain_env_probe (+ naf_chain_env_probe_cell with a workcell),
     then naf_chain_ik_select. Owns the handle and the buffers; needs no agent. A chunk holds a fixed number of candidates,
     `chunk` rounded down to whole queries; a query's result does not depend on the chunk or the lane it lands in.
     With an orientation goal (solve(orientations=) or solve(approach_directions=)) the first launch is naf_chain_ik_solve_pose
     and the selection is fed its merit; the goal, angle and merit buffers are allocated on the first such call. Without one
-    the launches are the ones above and those buffers do not exist."""
+    the launches are the ones above and those buffers do not exist.
+    With solve(avoid_contact=True) one launch, naf_chain_ik_clear (chain_clear.ClearLaunch), sits between the solve and the
+    clearances: it refines the poses in self.q and their residuals in place, so the launches behind it are the ones above on better
+    poses. Its obstacle, working-pose and record buffers are allocated on the first such call; positional goals only."""
     CHUNK, CHUNK_MIN, CHUNK_REFUSAL = 32768, 64, "GoalPoseSolver: a chunk holds at least 64 candidates"
 
     def __init__(self, chain, obstacle_radius: float = 0.06, chunk: Optional[int] = None, device=None):
@@ -110,9 +115,11 @@ class GoalPoseSolver(_ChainTool):
         return _lib.IkPoseParams(float(0.25 * self.chain.reach if weight is None else weight), float(0.5 if w_max is None else w_max),
                                  og.angle_length, f3(*map(float, og.tool_axis)), f3(*map(float, og.tool_normal)))
 
-    def launch(self, n: int, R: int, prm, tolerance: float, margin: float, solve_only: bool = False, mode=None, pose=None) -> None:
+    def launch(self, n: int, R: int, prm, tolerance: float, margin: float, solve_only: bool = False, mode=None, pose=None,
+               clear=None) -> None:
         """the launches of one chunk of n queries x R restarts already in the buffers, on the current stream; mode / pose: the
-        chunk's orientation goals are in self.goals and the first launch is naf_chain_ik_solve_pose"""
+        chunk's orientation goals are in self.goals and the first launch is naf_chain_ik_solve_pose; clear (clear_setup): the
+        chunk's obstacles are in self.obstacles and naf_chain_ik_clear follows the solve"""
         st, E = stream_ptr(), n * R
         measure = self.residual
         if mode is None:
@@ -125,6 +132,8 @@ class GoalPoseSolver(_ChainTool):
             measure = self.merit
         if solve_only:
             return
+        if clear is not None:
+            self.launch_clear(n, R, clear)
         check(self.lib.naf_chain_env_reset_given(self._chain_env, ptr(self.env_state), ptr(self.obs), E, ptr(self.q), ptr(self.scene),
                                                  self.obstacle_radius, st), "chain_env_reset_given")
         check(self.lib.naf_chain_env_probe(self._chain_env, ptr(self.env_state), ptr(self.probe), E, st), "chain_env_probe")
@@ -149,13 +158,15 @@ class GoalPoseSolver(_ChainTool):
               **constants) -> GoalPoses:
         """q0[N][A] (action order), targets[N][3], obstacles[N][3] -> GoalPoses of numpy arrays (float32 where the device's).
         orientations[N][4] | [4] (quaternions x, y, z, w) or approach_directions[N][3] | [3] (for tool_axis, in the end-effector
-        frame): an orientation goal (environment.kinematic.orientation_goal); GoalPoses.angle_residual is then filled."""
+        frame): an orientation goal (environment.kinematic.orientation_goal); GoalPoses.angle_residual is then filled.
+        avoid_contact=True (with clearance_goal, push_iterations, push_settle, push_max): every chunk's candidates go through
+        naf_chain_ik_clear before their clearances are taken (positional goals only); GoalPoses.pushed and .input_clearance are
+        then filled."""
         A, R = self.A, int(restarts)
         q0 = np.ascontiguousarray(q0, np.float32).reshape(-1, A)
         N = len(q0)
         targets, obstacles = np.asarray(targets, np.float32).reshape(N, 3), np.asarray(obstacles, np.float32).reshape(N, 3)
         seeds = ik_seeds(self.chain, N, R, seed)
-        prm = self.params(iterations, **constants)
         og = orientation_goal(N, orientations, approach_directions, tool_axis, tolerance, orientation_tolerance)
         mode = pose = None
         if og is not None:
@@ -163,6 +174,8 @@ class GoalPoseSolver(_ChainTool):
             if self.goals is None:
                 self.goals, self.angle, self.merit = self._zeros(self.chunk, 9), self._zeros(self.chunk), self._zeros(self.chunk)
         tolerance, margin = float(np.float32(tolerance)), float(np.float32(margin))
+        clear = self.clear_setup(constants, tolerance, margin, orientations, approach_directions)
+        prm = self.params(iterations, **constants)
         per = self.chunk // R
         parts, get = [], self._download
         for first in range(0, N, per):
@@ -171,14 +184,14 @@ class GoalPoseSolver(_ChainTool):
             self.load(q0[sl], targets[sl], obstacles[sl], seeds[sl])
             if og is not None:      # the chunk's goals, [n][9] or [n][3] rows packed at the front of the buffer
                 self.goals.view(-1)[:og.goals[sl].size].copy_(torch.from_numpy(np.ascontiguousarray(og.goals[sl]).reshape(-1)))
-            self.launch(n, R, prm, tolerance, margin, mode=mode, pose=pose)
+            self.launch(n, R, prm, tolerance, margin, mode=mode, pose=pose, clear=self.load_clear(clear, obstacles[sl]))
             E = n * R
             cell = get(self.cell, E, n, R) if self.has_cell else np.full((n, R), np.inf, np.float32)
             probe = get(self.probe, E, n, R, 5)
             more = () if og is None else (get(self.angle, E, n, R), get(self.merit, E, n, R))
-            parts.append(gather_goal_poses(get(self.choice, n), get(self.cls, n), get(self.q, E, n, R, A), get(self.residual, E, n, R),
+            parts.append(note_pushed(gather_goal_poses(get(self.choice, n), get(self.cls, n), get(self.q, E, n, R, A), get(self.residual, E, n, R),
                                            probe[:, :, 3], probe[:, :, 4], cell, get(self.distance, E, n, R), np.float32(tolerance),
-                                           *more))
+                                           *more), clear and get(self.clear, E, n, R, 4)))
         return concatenate_goal_poses(parts)
 
 

@@ -2503,3 +2503,427 @@ extern "C" int naf_chain_demo_rows_legs(naf_chain_env_t* h, const float* q_start
             row_floats, rows_out, records_out, poses_out, cell...);
     });
 }
+
+// ---- goal poses pushed out of contact in the task's null space (include/naf_hip.h, "Goal poses out of contact") -------------------
+// chain_ik_solve_kernel's shape — one lane per candidate, one wave per workgroup, no barrier — with a walk of ALL A joints: the
+// [m][6][lane] record of (a_m, p_m) for every driven joint, and behind it the capsules' world end points as [segment][6][lane].
+// Beside the end effector the walk collects the LEAST of all the clearance tests the selection compares with the margin — per
+// capsule the obstacle, then the workcell geometries its mask names; after the walk the self pairs, a serial loop per lane over
+// LDS — and that test's witness: a handful of registers replaced by select when a smaller test appears. The distance bodies are
+// restated here with their witnesses; frame_geometry, chain_walk_at, seg_*_dist2 and the solve kernels are not touched. The counts
+// P, G, H, B are the blob's header floats, uniform: a loop runs zero times where its section is absent, and the mask and geometry
+// sections are not addressed in a blob without a workcell. environment/kinematic.py (least_test, clearance_gradient, ik_clear_step,
+// refine_goal_poses) is the float64 statement.
+#define IKC_SIGMA_FLOOR 1e-6f
+#define IKC_WITNESS_FLOOR 1e-6f      // (a micrometre: float32 leaves some 1e-8 of a zero distance between points half a metre out)
+
+struct ClearWitness {
+    float c;                     // the running least clearance
+    int kind, f, f2;             // 0 obstacle / 1 self / 2 workcell; the capsule's frame; a pair's second frame (0: no joint moves it)
+    float x0, x1, x2;            // the point on the capsule's axis where the distance is attained
+    float n0, n1, n2;            // the unit direction from the geometry's nearest point to x (0: no gradient)
+    float y0, y1, y2;            // a pair's second point
+};
+
+__device__ __forceinline__ void ikc_offer(ClearWitness& w, float c, int kind, int f, float x0, float x1, float x2, float d0, float d1,
+                                          float d2, float dist, int f2 = 0, float y0 = 0.f, float y1 = 0.f, float y2 = 0.f) {
+    const bool take = c < w.c;
+    const float inv = dist >= IKC_WITNESS_FLOOR ? 1.f / dist : 0.f;
+    w.c = take ? c : w.c;
+    w.kind = take ? kind : w.kind;
+    w.f = take ? f : w.f;
+    w.f2 = take ? f2 : w.f2;
+    w.x0 = take ? x0 : w.x0; w.x1 = take ? x1 : w.x1; w.x2 = take ? x2 : w.x2;
+    w.n0 = take ? d0 * inv : w.n0; w.n1 = take ? d1 * inv : w.n1; w.n2 = take ? d2 * inv : w.n2;
+    w.y0 = take ? y0 : w.y0; w.y1 = take ? y1 : w.y1; w.y2 = take ? y2 : w.y2;
+}
+
+// seg_point_dist2 with its witness: the clamped projection parameter
+__device__ __forceinline__ float ikc_seg_point(float ax, float ay, float az, float bx, float by, float bz, float cx, float cy, float cz,
+                                               float& t_out) {
+    const float ux = bx - ax, uy = by - ay, uz = bz - az;
+    const float wx = cx - ax, wy = cy - ay, wz = cz - az;
+    const float den = ux * ux + uy * uy + uz * uz;
+    float t = den > 0.f ? (wx * ux + wy * uy + wz * uz) / den : 0.f;
+    t = fminf(1.f, fmaxf(0.f, t));
+    const float dx = wx - t * ux, dy = wy - t * uy, dz = wz - t * uz;
+    t_out = t;
+    return dx * dx + dy * dy + dz * dz;
+}
+
+// a capsule's axis a-b against the sphere (centre c, radius rad): the test d - rad - rho and its witness
+__device__ __forceinline__ void ikc_sphere(ClearWitness& w, int kind, int f, float ax, float ay, float az, float bx, float by, float bz,
+                                           float cx, float cy, float cz, float rad, float rho) {
+    float t;
+    const float d = sqrtf(ikc_seg_point(ax, ay, az, bx, by, bz, cx, cy, cz, t));
+    const float x0 = ax + t * (bx - ax), x1 = ay + t * (by - ay), x2 = az + t * (bz - az);
+    ikc_offer(w, d - rad - rho, kind, f, x0, x1, x2, x0 - cx, x1 - cy, x2 - cz, d);
+}
+
+// seg_box_dist2 with its witness: the parameter t it ends with
+__device__ static inline float ikc_seg_box(float px, float py, float pz, float ux, float uy, float uz, float hx, float hy, float hz,
+                                           float& t_out) {
+    float t_lo = 0.f, t_hi = 1.f;
+    float g_lo = box_slope(0.f, px, py, pz, ux, uy, uz, hx, hy, hz), g_hi = box_slope(1.f, px, py, pz, ux, uy, uz, hx, hy, hz);
+    const float g0 = g_lo, g1 = g_hi;
+    const float p[3] = {px, py, pz}, u[3] = {ux, uy, uz}, h[3] = {hx, hy, hz};
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const int i = k >> 1;
+        const float inv = u[i] != 0.f ? 1.f / u[i] : 0.f;
+        const float t = fminf(1.f, fmaxf(0.f, ((k & 1 ? h[i] : -h[i]) - p[i]) * inv));
+        const float g = box_slope(t, px, py, pz, ux, uy, uz, hx, hy, hz);
+        const bool lo = g <= 0.f && t >= t_lo, hi = g >= 0.f && t <= t_hi;
+        t_lo = lo ? t : t_lo;
+        g_lo = lo ? g : g_lo;
+        t_hi = hi ? t : t_hi;
+        g_hi = hi ? g : g_hi;
+    }
+    const float den = g_hi - g_lo;
+    float t = den > 0.f ? t_lo - g_lo * (t_hi - t_lo) / den : t_lo;
+    t = fminf(t_hi, fmaxf(t_lo, t));
+    t = g0 > 0.f ? 0.f : (g1 < 0.f ? 1.f : t);
+    t_out = t;
+    const float x = fmaf(t, ux, px), y = fmaf(t, uy, py), z = fmaf(t, uz, pz);
+    const float ex = fmaxf(fabsf(x) - hx, 0.f), ey = fmaxf(fabsf(y) - hy, 0.f), ez = fmaxf(fabsf(z) - hz, 0.f);
+    return ex * ex + ey * ey + ez * ez;
+}
+
+// the tests of frame f's capsules — the obstacle, then the masked workcell geometries — and their end points into LDS
+__device__ static inline void ikc_frame(const float* __restrict__ model, int A, int n_seg, int f, const Frame& F, float ox, float oy,
+                                        float oz, float orad, float* ends, ClearWitness& w) {
+    const float* begin = model + ch_off_begin(A);
+    const float* segs = model + ch_off_seg(A);
+    const int s0 = (int)begin[f], s1 = (int)begin[f + 1];
+    const int n_sph = (int)model[10], n_geo = n_sph + (int)model[11], n_box = (int)model[12];
+    const float* geo = model + ch_off_cell(A, n_seg, (int)model[9]);      // (addressed only when n_geo + n_box > 0)
+    for (int s = s0; s < s1; ++s) {
+        const float* g = segs + s * CH_SEG;
+        const float ax = F.px + F.r00 * g[1] + F.r01 * g[2] + F.r02 * g[3];
+        const float ay = F.py + F.r10 * g[1] + F.r11 * g[2] + F.r12 * g[3];
+        const float az = F.pz + F.r20 * g[1] + F.r21 * g[2] + F.r22 * g[3];
+        const float bx = F.px + F.r00 * g[4] + F.r01 * g[5] + F.r02 * g[6];
+        const float by = F.py + F.r10 * g[4] + F.r11 * g[5] + F.r12 * g[6];
+        const float bz = F.pz + F.r20 * g[4] + F.r21 * g[5] + F.r22 * g[6];
+        float* e = ends + (size_t)s * 6 * 64;
+        e[0] = ax; e[64] = ay; e[128] = az;
+        e[192] = bx; e[256] = by; e[320] = bz;
+        ikc_sphere(w, 0, f, ax, ay, az, bx, by, bz, ox, oy, oz, orad, g[7]);
+        if (n_geo + n_box == 0) continue;
+        const int mask = (int)geo[4 * n_geo + CH_BOX * n_box + s];
+        for (int k = 0; k < n_geo; ++k) {      // (uniform: the counts, the mask and the geometry are the blob's)
+            if (!(mask >> k & 1)) continue;
+            const float* c = geo + 4 * k;
+            if (k < n_sph) {
+                ikc_sphere(w, 2, f, ax, ay, az, bx, by, bz, c[0], c[1], c[2], c[3], g[7]);
+            } else {      // the end point with the smaller n . x; the direction is the plane's normal
+                const float na = c[0] * ax + c[1] * ay + c[2] * az, nb = c[0] * bx + c[1] * by + c[2] * bz;
+                const bool first = na <= nb;
+                ikc_offer(w, fminf(na, nb) - c[3] - g[7], 2, f, first ? ax : bx, first ? ay : by, first ? az : bz, c[0], c[1], c[2], 1.f);
+            }
+        }
+        const int bmask = mask >> n_geo;
+        const float wx = bx - ax, wy = by - ay, wz = bz - az;
+        for (int k = 0; k < n_box; ++k) {      // (uniform, as above)
+            if (!(bmask >> k & 1)) continue;
+            const float* x = geo + 4 * n_geo + CH_BOX * k;      // c | R row-major | h | r
+            const float ex = ax - x[0], ey = ay - x[1], ez = az - x[2];
+            const float px = x[3] * ex + x[6] * ey + x[9] * ez, py = x[4] * ex + x[7] * ey + x[10] * ez,
+                        pz = x[5] * ex + x[8] * ey + x[11] * ez;
+            const float ux = x[3] * wx + x[6] * wy + x[9] * wz, uy = x[4] * wx + x[7] * wy + x[10] * wz,
+                        uz = x[5] * wx + x[8] * wy + x[11] * wz;
+            float t;
+            const float d = sqrtf(ikc_seg_box(px, py, pz, ux, uy, uz, x[12], x[13], x[14], t));
+            // the point at t in the box's frame minus its clamp into the box, rotated back to the world
+            const float lx = fmaf(t, ux, px), ly = fmaf(t, uy, py), lz = fmaf(t, uz, pz);
+            const float dx = lx - fminf(x[12], fmaxf(-x[12], lx)), dy = ly - fminf(x[13], fmaxf(-x[13], ly)),
+                        dz = lz - fminf(x[14], fmaxf(-x[14], lz));
+            ikc_offer(w, d - x[15] - g[7], 2, f, ax + t * wx, ay + t * wy, az + t * wz, x[3] * dx + x[4] * dy + x[5] * dz,
+                      x[6] * dx + x[7] * dy + x[8] * dz, x[9] * dx + x[10] * dy + x[11] * dz, d);
+        }
+    }
+}
+
+// walks all A joints at q: (a_m, p_m) of every joint to ax[(m * 6 + k) * 64], the capsules' end points to `ends`, the end effector
+// to ee, the least obstacle / workcell test and its witness to w
+__device__ static inline void ikc_walk(const float* __restrict__ model, int A, int n_seg, const float* q, float ox, float oy, float oz,
+                                       float orad, float* ax, float* ends, float* ee, ClearWitness& w) {
+    const int ee_frame = (int)model[4];
+    Frame F = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
+    w.c = INFINITY;
+    w.kind = w.f = w.f2 = 0;
+    w.x0 = w.x1 = w.x2 = w.n0 = w.n1 = w.n2 = w.y0 = w.y1 = w.y2 = 0.f;
+    ee[0] = ee[1] = ee[2] = 0.f;
+    for (int f = 0;; ++f) {
+        ikc_frame(model, A, n_seg, f, F, ox, oy, oz, orad, ends, w);
+        if (f == ee_frame) {
+            ee[0] = F.px + F.r00 * model[5] + F.r01 * model[6] + F.r02 * model[7];
+            ee[1] = F.py + F.r10 * model[5] + F.r11 * model[6] + F.r12 * model[7];
+            ee[2] = F.pz + F.r20 * model[5] + F.r21 * model[6] + F.r22 * model[7];
+        }
+        if (f == A) break;
+        const int m = f;
+        const float* j = model + CH_HDR + m * CH_JNT;
+        const float qm = q[m];
+        F.px += F.r00 * j[9] + F.r01 * j[10] + F.r02 * j[11];
+        F.py += F.r10 * j[9] + F.r11 * j[10] + F.r12 * j[11];
+        F.pz += F.r20 * j[9] + F.r21 * j[10] + F.r22 * j[11];
+        Frame G;
+        G.r00 = F.r00 * j[0] + F.r01 * j[3] + F.r02 * j[6];
+        G.r01 = F.r00 * j[1] + F.r01 * j[4] + F.r02 * j[7];
+        G.r02 = F.r00 * j[2] + F.r01 * j[5] + F.r02 * j[8];
+        G.r10 = F.r10 * j[0] + F.r11 * j[3] + F.r12 * j[6];
+        G.r11 = F.r10 * j[1] + F.r11 * j[4] + F.r12 * j[7];
+        G.r12 = F.r10 * j[2] + F.r11 * j[5] + F.r12 * j[8];
+        G.r20 = F.r20 * j[0] + F.r21 * j[3] + F.r22 * j[6];
+        G.r21 = F.r20 * j[1] + F.r21 * j[4] + F.r22 * j[7];
+        G.r22 = F.r20 * j[2] + F.r21 * j[5] + F.r22 * j[8];
+        const float x = j[12], y = j[13], z = j[14];
+        const float wx = G.r00 * x + G.r01 * y + G.r02 * z, wy = G.r10 * x + G.r11 * y + G.r12 * z,
+                    wz = G.r20 * x + G.r21 * y + G.r22 * z;
+        float* rec = ax + m * 6 * 64;
+        rec[0] = wx; rec[64] = wy; rec[128] = wz;
+        rec[192] = F.px; rec[256] = F.py; rec[320] = F.pz;
+        if (j[15] != 0.f) {      // prismatic
+            F.r00 = G.r00; F.r01 = G.r01; F.r02 = G.r02;
+            F.r10 = G.r10; F.r11 = G.r11; F.r12 = G.r12;
+            F.r20 = G.r20; F.r21 = G.r21; F.r22 = G.r22;
+            F.px += wx * qm;
+            F.py += wy * qm;
+            F.pz += wz * qm;
+        } else {                 // revolute: chain_walk's Rodrigues form
+            float s, c;
+            sincosf(qm, &s, &c);
+            const float v = 1.f - c;
+            const float m00 = 1.f - v * (y * y + z * z), m01 = v * x * y - s * z, m02 = v * x * z + s * y;
+            const float m10 = v * x * y + s * z, m11 = 1.f - v * (x * x + z * z), m12 = v * y * z - s * x;
+            const float m20 = v * x * z - s * y, m21 = v * y * z + s * x, m22 = 1.f - v * (x * x + y * y);
+            F.r00 = G.r00 * m00 + G.r01 * m10 + G.r02 * m20;
+            F.r01 = G.r00 * m01 + G.r01 * m11 + G.r02 * m21;
+            F.r02 = G.r00 * m02 + G.r01 * m12 + G.r02 * m22;
+            F.r10 = G.r10 * m00 + G.r11 * m10 + G.r12 * m20;
+            F.r11 = G.r10 * m01 + G.r11 * m11 + G.r12 * m21;
+            F.r12 = G.r10 * m02 + G.r11 * m12 + G.r12 * m22;
+            F.r20 = G.r20 * m00 + G.r21 * m10 + G.r22 * m20;
+            F.r21 = G.r20 * m01 + G.r21 * m11 + G.r22 * m21;
+            F.r22 = G.r20 * m02 + G.r21 * m12 + G.r22 * m22;
+        }
+    }
+}
+
+// the self pairs, a serial loop over the lane's end points in LDS: seg_seg_dist2's five candidates with their parameters, the
+// least of them (ties to the first) the pair's witness
+__device__ static inline void ikc_pairs(const float* __restrict__ model, int A, int n_seg, int n_pairs, const float* ends,
+                                        ClearWitness& w) {
+    const float* segs = model + ch_off_seg(A);
+    const float* pairs = model + ch_off_pair(A, n_seg);      // (addressed only when n_pairs > 0)
+    for (int p = 0; p < n_pairs; ++p) {
+        const int s = (int)pairs[2 * p], t_ = (int)pairs[2 * p + 1];
+        const float* e = ends + (size_t)s * 6 * 64;
+        const float* g = ends + (size_t)t_ * 6 * 64;
+        const float ax = e[0], ay = e[64], az = e[128], bx = e[192], by = e[256], bz = e[320];
+        const float cx = g[0], cy = g[64], cz = g[128], dx = g[192], dy = g[256], dz = g[320];
+        const float ux = bx - ax, uy = by - ay, uz = bz - az;
+        const float vx = dx - cx, vy = dy - cy, vz = dz - cz;
+        const float wx = ax - cx, wy = ay - cy, wz = az - cz;
+        const float a = ux * ux + uy * uy + uz * uz, b = ux * vx + uy * vy + uz * vz, c = vx * vx + vy * vy + vz * vz;
+        const float d = ux * wx + uy * wy + uz * wz, ee_ = vx * wx + vy * wy + vz * wz;
+        const float den = a * c - b * b;
+        float sp = den > 1e-7f * a * c ? (b * ee_ - c * d) / den : 0.f;
+        sp = fminf(1.f, fmaxf(0.f, sp));
+        float tp = c > 0.f ? (b * sp + ee_) / c : 0.f;
+        tp = fminf(1.f, fmaxf(0.f, tp));
+        sp = a > 0.f ? (b * tp - d) / a : 0.f;
+        sp = fminf(1.f, fmaxf(0.f, sp));
+        const float xx = wx + sp * ux - tp * vx, xy = wy + sp * uy - tp * vy, xz = wz + sp * uz - tp * vz;
+        float best = xx * xx + xy * xy + xz * xz, t;
+        float d2 = ikc_seg_point(cx, cy, cz, dx, dy, dz, ax, ay, az, t);
+        bool take = d2 < best;
+        sp = take ? 0.f : sp; tp = take ? t : tp; best = take ? d2 : best;
+        d2 = ikc_seg_point(cx, cy, cz, dx, dy, dz, bx, by, bz, t);
+        take = d2 < best;
+        sp = take ? 1.f : sp; tp = take ? t : tp; best = take ? d2 : best;
+        d2 = ikc_seg_point(ax, ay, az, bx, by, bz, cx, cy, cz, t);
+        take = d2 < best;
+        sp = take ? t : sp; tp = take ? 0.f : tp; best = take ? d2 : best;
+        d2 = ikc_seg_point(ax, ay, az, bx, by, bz, dx, dy, dz, t);
+        take = d2 < best;
+        sp = take ? t : sp; tp = take ? 1.f : tp; best = take ? d2 : best;
+        const float x0 = ax + sp * ux, x1 = ay + sp * uy, x2 = az + sp * uz;
+        const float y0 = cx + tp * vx, y1 = cy + tp * vy, y2 = cz + tp * vz;
+        const float e0 = x0 - y0, e1 = x1 - y1, e2 = x2 - y2;
+        const float dist = sqrtf(e0 * e0 + e1 * e1 + e2 * e2);
+        ikc_offer(w, dist - (segs[s * CH_SEG + 7] + segs[t_ * CH_SEG + 7]), 1, (int)segs[s * CH_SEG], x0, x1, x2, e0, e1, e2, dist,
+                  (int)segs[t_ * CH_SEG], y0, y1, y2);
+    }
+}
+
+// joint m's task column c and its entry gamma of the least test's gradient, from its LDS record
+__device__ __forceinline__ float ikc_column(const float* __restrict__ model, int m, int n_joints, const float* ax, const float* ee,
+                                            const ClearWitness& w, float* c) {
+    const float* r = ax + m * 6 * 64;
+    const float a0 = r[0], a1 = r[64], a2 = r[128], p0 = r[192], p1 = r[256], p2 = r[320];
+    const bool prismatic = model[CH_HDR + m * CH_JNT + 15] != 0.f;
+    float g1 = w.n0 * a0 + w.n1 * a1 + w.n2 * a2, g2 = g1;
+    if (prismatic) {
+        c[0] = a0; c[1] = a1; c[2] = a2;
+    } else {
+        float d0 = ee[0] - p0, d1 = ee[1] - p1, d2 = ee[2] - p2;
+        c[0] = a1 * d2 - a2 * d1;
+        c[1] = a2 * d0 - a0 * d2;
+        c[2] = a0 * d1 - a1 * d0;
+        d0 = w.x0 - p0; d1 = w.x1 - p1; d2 = w.x2 - p2;
+        g1 = w.n0 * (a1 * d2 - a2 * d1) + w.n1 * (a2 * d0 - a0 * d2) + w.n2 * (a0 * d1 - a1 * d0);
+        d0 = w.y0 - p0; d1 = w.y1 - p1; d2 = w.y2 - p2;
+        g2 = w.n0 * (a1 * d2 - a2 * d1) + w.n1 * (a2 * d0 - a0 * d2) + w.n2 * (a0 * d1 - a1 * d0);
+    }
+    if (m >= n_joints) c[0] = c[1] = c[2] = 0.f;
+    return (m < w.f ? g1 : 0.f) - (m < w.f2 ? g2 : 0.f);
+}
+
+template <bool REC>
+__global__ void __launch_bounds__(64)
+chain_ik_clear_kernel(const float* __restrict__ model, const float* __restrict__ targets, const float* __restrict__ obstacles,
+                      const float* q_in, int N, int R, int A, const naf_chain_ik_params_t prm, const naf_chain_ik_clear_params_t cp,
+                      float* q_out, float* q_work, float* __restrict__ residual_out, float* __restrict__ clear_out,
+                      float* __restrict__ iters_out, float* __restrict__ rec_out) {
+    extern __shared__ __attribute__((aligned(16))) float ch_lds[];
+    const int64_t total = (int64_t)N * R;
+    const int64_t cand = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (cand >= total) return;      // (one wave per workgroup and no barrier below)
+    const int64_t n = cand / R;
+    const int n_joints = (int)model[4], n_seg = (int)model[2], n_pairs = (int)model[9];
+    float* ax = ch_lds + threadIdx.x;
+    float* ends = ax + (size_t)A * 6 * 64;
+    float* q = q_work + cand * A;
+    float* keep = q_out + cand * A;
+    for (int m = 0; m < A; ++m) {
+        const float v = q_in[cand * A + m];
+        q[m] = v;
+        keep[m] = v;
+        if constexpr (REC) iters_out[cand * A + m] = v;
+    }
+    const float g0 = targets[n * 3], g1 = targets[n * 3 + 1], g2 = targets[n * 3 + 2];
+    const float o0 = obstacles[n * 3], o1 = obstacles[n * 3 + 1], o2 = obstacles[n * 3 + 2];
+    const int K = prm.iterations;
+    float* out4 = clear_out + cand * 4;
+    float best_key = -INFINITY;
+    for (int k = 0;; ++k) {
+        ClearWitness w;
+        float ee[3];
+        ikc_walk(model, A, n_seg, q, o0, o1, o2, cp.obstacle_radius, ax, ends, ee, w);
+        ikc_pairs(model, A, n_seg, n_pairs, ends, w);
+        float e0 = g0 - ee[0], e1 = g1 - ee[1], e2 = g2 - ee[2];
+        const float len = sqrtf(e0 * e0 + e1 * e1 + e2 * e2);
+        const float key = len <= cp.tolerance ? fminf(w.c, cp.clearance_goal) : -INFINITY;
+        if (k == 0) {      // iterate 0 is the input pose
+            best_key = key;
+            residual_out[cand] = len;
+            out4[0] = w.c; out4[1] = w.c; out4[2] = 0.f; out4[3] = (float)w.kind;
+            if (w.c >= cp.clearance_goal || len > cp.tolerance) {      // it keeps the goal, or is not converged: back bit for bit
+                if constexpr (REC) {
+                    for (int u = 0; u < K; ++u) {
+                        float* it = iters_out + ((int64_t)(u + 1) * total + cand) * A;
+                        float* rc = rec_out + ((int64_t)u * total + cand) * (A + 2);
+                        for (int m = 0; m < A; ++m) { it[m] = keep[m]; rc[m] = 0.f; }
+                        rc[A] = w.c; rc[A + 1] = (float)w.kind;
+                    }
+                }
+                return;
+            }
+        } else if (key > best_key) {      // (ties stay with the earliest)
+            best_key = key;
+            for (int m = 0; m < A; ++m) keep[m] = q[m];
+            residual_out[cand] = len;
+            out4[1] = w.c; out4[2] = (float)k; out4[3] = (float)w.kind;
+        }
+        if (k == K) break;
+        if (len > prm.e_max) {
+            const float s = prm.e_max / len;
+            e0 *= s; e1 *= s; e2 *= s;
+        }
+        // pass 1 over LDS: M = sum c c^T + lam^2 I and the second right-hand side b = sum c gamma
+        float m00 = prm.lam2, m01 = 0.f, m02 = 0.f, m11 = prm.lam2, m12 = 0.f, m22 = prm.lam2, b0 = 0.f, b1 = 0.f, b2 = 0.f;
+        for (int m = 0; m < A; ++m) {
+            float c[3];
+            const float gamma = ikc_column(model, m, n_joints, ax, ee, w, c);
+            m00 += c[0] * c[0]; m01 += c[0] * c[1]; m02 += c[0] * c[2];
+            m11 += c[1] * c[1]; m12 += c[1] * c[2]; m22 += c[2] * c[2];
+            b0 += c[0] * gamma; b1 += c[1] * gamma; b2 += c[2] * gamma;
+        }
+        const float c00 = m11 * m22 - m12 * m12, c01 = m02 * m12 - m01 * m22, c02 = m01 * m12 - m02 * m11;
+        const float c11 = m00 * m22 - m02 * m02, c12 = m01 * m02 - m00 * m12, c22 = m00 * m11 - m01 * m01;
+        const float det = m00 * c00 + m01 * c01 + m02 * c02;
+        const float y0 = (c00 * e0 + c01 * e1 + c02 * e2) / det, y1 = (c01 * e0 + c11 * e1 + c12 * e2) / det,
+                    y2 = (c02 * e0 + c12 * e1 + c22 * e2) / det;
+        const float z0 = (c00 * b0 + c01 * b1 + c02 * b2) / det, z1 = (c01 * b0 + c11 * b1 + c12 * b2) / det,
+                    z2 = (c02 * b0 + c12 * b1 + c22 * b2) / det;
+        // pass 2: dq_m = c_m . y and h_m = gamma_m - c_m . z into the record's first two floats; max |dq_m|, max |h_m|, sigma
+        float big = 0.f, top = 0.f, sigma = 0.f;
+        float* rc = REC ? rec_out + ((int64_t)k * total + cand) * (A + 2) : nullptr;
+        for (int m = 0; m < A; ++m) {
+            float c[3];
+            const float gamma = ikc_column(model, m, n_joints, ax, ee, w, c);
+            const float dq = c[0] * y0 + c[1] * y1 + c[2] * y2;
+            const float h = gamma - (c[0] * z0 + c[1] * z1 + c[2] * z2);
+            ax[m * 6 * 64] = dq;
+            ax[m * 6 * 64 + 64] = h;
+            big = fmaxf(big, fabsf(dq));
+            top = fmaxf(top, fabsf(h));
+            sigma += gamma * h;
+            if constexpr (REC) rc[m] = gamma;
+        }
+        if constexpr (REC) { rc[A] = w.c; rc[A + 1] = (float)w.kind; }
+        const float scale = big > prm.dq_max ? prm.dq_max / big : 1.f;
+        float coef = 0.f;
+        if (k < K - cp.settle && w.c < cp.clearance_goal && sigma > IKC_SIGMA_FLOOR) {
+            coef = (cp.clearance_goal - w.c) / sigma;      // the Gauss-Newton length that lifts the one active test to the goal
+            const float far = fabsf(coef) * top;
+            if (far > cp.push_max) coef *= cp.push_max / far;
+        }
+        float* it = REC ? iters_out + ((int64_t)(k + 1) * total + cand) * A : nullptr;
+        for (int m = 0; m < A; ++m) {
+            const float* j = model + CH_HDR + m * CH_JNT;
+            float v = q[m] + scale * ax[m * 6 * 64] + coef * ax[m * 6 * 64 + 64];
+            if (j[16] != 0.f) {
+                if (v > j[18]) v = j[18];
+                if (v < j[17]) v = j[17];
+            }
+            q[m] = v;
+            if constexpr (REC) it[m] = v;
+        }
+    }
+}
+
+extern "C" int naf_chain_ik_clear(naf_chain_env_t* h, const float* targets_dev, const float* obstacles_dev, const float* q_in_dev, int N,
+                                  int R, naf_chain_ik_params_t params, naf_chain_ik_clear_params_t clear_params, float* q_out,
+                                  float* q_work, float* residual_out, float* clear_out, float* iters_out, float* rec_out,
+                                  void* stream) {
+    if (!h || !targets_dev || !obstacles_dev || !q_in_dev || !q_out || !q_work || !residual_out || !clear_out ||
+        !ch_ik_counts_ok(N, R) || (iters_out == nullptr) != (rec_out == nullptr) || q_work == q_out || q_work == q_in_dev)
+        return NAF_ERR_ARG;
+    if (params.iterations < 1 || params.iterations > 1 << 20 || !std::isfinite(params.lam2) || !(params.lam2 > 0.f) ||
+        !std::isfinite(params.e_max) || !(params.e_max > 0.f) || !std::isfinite(params.dq_max) || !(params.dq_max > 0.f))
+        return NAF_ERR_ARG;
+    if (clear_params.settle < 0 || clear_params.settle > params.iterations || !std::isfinite(clear_params.tolerance) ||
+        !(clear_params.tolerance >= 0.f) || !std::isfinite(clear_params.clearance_goal) || !std::isfinite(clear_params.push_max) ||
+        !(clear_params.push_max > 0.f) || !std::isfinite(clear_params.obstacle_radius) || !(clear_params.obstacle_radius >= 0.f))
+        return NAF_ERR_ARG;
+    // 1536 bytes per driven joint and per segment: above what the handle's kernels may ask for there is no launch
+    const size_t lds = (size_t)(h->A + h->n_seg) * 6 * 64 * sizeof(float);
+    if (lds > CH_MAX_DYN_LDS) return NAF_CHAIN_ERR_LDS;
+    int rc = ch_raise<chain_ik_clear_kernel<false>>();
+    if (rc == NAF_OK) rc = ch_raise<chain_ik_clear_kernel<true>>();
+    if (rc != NAF_OK) return rc;
+    const unsigned grid = (unsigned)(((int64_t)N * R + 63) / 64);
+    if (iters_out)
+        chain_ik_clear_kernel<true><<<grid, 64, lds, (hipStream_t)stream>>>(h->model_dev, targets_dev, obstacles_dev, q_in_dev, N, R, h->A,
+                                                                           params, clear_params, q_out, q_work, residual_out, clear_out,
+                                                                           iters_out, rec_out);
+    else
+        chain_ik_clear_kernel<false><<<grid, 64, lds, (hipStream_t)stream>>>(h->model_dev, targets_dev, obstacles_dev, q_in_dev, N, R, h->A,
+                                                                            params, clear_params, q_out, q_work, residual_out, clear_out,
+                                                                            nullptr, nullptr);
+    NAF_CHECK_LAUNCH();
+    return NAF_OK;
+}

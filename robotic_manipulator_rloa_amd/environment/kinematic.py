@@ -21,77 +21,13 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .contact_push import (CLEAR_KINDS, CLEAR_TESTS, PUSH_ORIENTATION_REFUSAL, LeastTest, RefinedPoses, clear_defaults, clear_walk,  # noqa: F401
+                           clearance_gradient, ik_clear_step, least_test, note_pushed, pop_push, refine_goal_poses)
 from .orientation import (ORIENT_AXIS, ORIENT_FULL, OrientationGoal, PoseGoalRule, orientation_error,  # noqa: F401
                           orientation_goal, quaternion_matrix, spd6_solve, tool_normal_of)
+from .segment_distance import segment_box_distance, segment_point_distance2, segment_segment_distance2  # noqa: F401
 from .urdf_chain import (DT, OBSTACLE_RADIUS, PRISMATIC, SCENE_TRIES, TARGET_THRESHOLD, ChainModel, axis_rotation, compile_chain,
                          load_urdf)
-
-
-def segment_point_distance2(a: np.ndarray, b: np.ndarray, c: np.ndarray):
-    """Squared distance from point c to the segment a-b (projection clamped to [0, 1]); arrays of points [..., 3] broadcast."""
-    ab, ac = b - a, c - a
-    den = np.sum(ab * ab, axis=-1)
-    t = np.clip(np.sum(ac * ab, axis=-1) / np.where(den > 0.0, den, 1.0), 0.0, 1.0)
-    d = ac - t[..., None] * ab
-    return np.sum(d * d, axis=-1)
-
-
-def segment_segment_distance2(a1: np.ndarray, b1: np.ndarray, a2: np.ndarray, b2: np.ndarray):
-    """Squared distance between the segments a1-b1 and a2-b2; arrays of points [..., 3] broadcast.
-    The minimum over five candidates, each the squared distance between two points that DO lie on the two segments, so none is
-    below the answer: the four end-point-to-segment distances, and the closest points of the two carrying lines (closed form,
-    clamped into the segments, then each parameter projected once more given the other). One of them attains it: the minimum
-    over the square [0, 1]^2 of the two parameters is either interior — then it is the lines' closest pair — or has a parameter
-    at 0 or 1, an end point against the other segment. The closed form's denominator |u|^2 |v|^2 - (u.v)^2 vanishes for parallel
-    or zero-length segments; it is guarded and the candidate then starts from parameter 0, which loses nothing: between parallel
-    segments the minimum is also attained at an end point, and a zero-length segment is an end point."""
-    u, v, w = b1 - a1, b2 - a2, a1 - a2
-    a, b, c = np.sum(u * u, axis=-1), np.sum(u * v, axis=-1), np.sum(v * v, axis=-1)
-    d, e = np.sum(u * w, axis=-1), np.sum(v * w, axis=-1)
-    den = a * c - b * b
-    ok = den > 1e-14 * a * c
-    s = np.clip(np.where(ok, (b * e - c * d) / np.where(ok, den, 1.0), 0.0), 0.0, 1.0)
-    t = np.clip((b * s + e) / np.where(c > 0.0, c, 1.0), 0.0, 1.0) * (c > 0.0)
-    s = np.clip((b * t - d) / np.where(a > 0.0, a, 1.0), 0.0, 1.0) * (a > 0.0)
-    x = w + s[..., None] * u - t[..., None] * v
-    best = np.sum(x * x, axis=-1)
-    for cand in (segment_point_distance2(a2, b2, a1), segment_point_distance2(a2, b2, b1),
-                 segment_point_distance2(a1, b1, a2), segment_point_distance2(a1, b1, b2)):
-        best = np.minimum(best, cand)
-    return best
-
-
-def segment_box_distance(a: np.ndarray, b: np.ndarray, half: np.ndarray):
-    """Distance between the segment a-b and the box |x_i| <= half_i, the points given in the box's frame; arrays [..., 3]
-    broadcast. 0 for a segment that touches or enters the box: the rule reports no penetration depth.
-    With p(t) = a + t (b - a), f(t) = sum_i max(|p_i(t)| - half_i, 0)^2 is convex, C1 and piecewise quadratic: f' is non-decreasing
-    and linear between its knots — 0, 1 and the up to six t in (0, 1) at which a coordinate crosses a face plane, p_i(t) = +-half_i.
-    Sorted, the knots bracket the root of f': the last one with f' <= 0 and the first with f' >= 0, between which f' is linear. f' > 0
-    at 0 puts the minimum at t = 0, f' < 0 at 1 at t = 1; a zero-length segment has f' = 0 throughout and takes t = 0."""
-    a, b, half = np.broadcast_arrays(np.asarray(a, float), np.asarray(b, float), np.asarray(half, float))
-    u = b - a
-
-    def slope(t):                                         # f'(t) / 2
-        x = a + t[..., None] * u
-        return np.sum((x - np.clip(x, -half, half)) * u, axis=-1)
-
-    with np.errstate(divide="ignore", invalid="ignore"):
-        knots = np.concatenate([(half - a) / u, (-half - a) / u], axis=-1)
-    knots = np.where(np.isfinite(knots), np.clip(knots, 0.0, 1.0), 0.0)       # (an axis the segment does not move along: no knot)
-    lead = knots.shape[:-1]
-    knots = np.sort(np.concatenate([np.zeros(lead + (1,)), knots, np.ones(lead + (1,))], axis=-1), axis=-1)
-    g = np.stack([slope(knots[..., k]) for k in range(8)], axis=-1)
-    # f' is non-decreasing along the sorted knots up to rounding: the bracket is taken by position, not by value
-    n_neg = np.sum(np.cumsum(g > 0.0, axis=-1) == 0, axis=-1)                 # knots before the first with f' > 0
-    lo, hi = np.clip(n_neg - 1, 0, 7)[..., None], np.clip(n_neg, 0, 7)[..., None]
-    t_lo, t_hi = np.take_along_axis(knots, lo, -1)[..., 0], np.take_along_axis(knots, hi, -1)[..., 0]
-    g_lo, g_hi = np.take_along_axis(g, lo, -1)[..., 0], np.take_along_axis(g, hi, -1)[..., 0]
-    den = g_hi - g_lo
-    with np.errstate(divide="ignore", invalid="ignore"):
-        t = np.where(den > 0.0, t_lo - g_lo * (t_hi - t_lo) / np.where(den > 0.0, den, 1.0), t_lo)
-    t = np.where(n_neg == 0, 0.0, np.where(n_neg == 8, 1.0, np.clip(t, t_lo, t_hi)))
-    x = a + t[..., None] * u
-    return np.sqrt(np.sum(np.maximum(np.abs(x) - half, 0.0) ** 2, axis=-1))
 
 
 SCENE_CONDITIONS = ("the target is within reach of the start pose's end effector", "the obstacle touches the arm at the start pose",
@@ -501,6 +437,9 @@ class GoalPoses(_GoalPoseFields):
     orientation_tolerance) <= tolerance, and `reachable` / `converged_restarts` count that. It is an attribute behind the tuple, as
     JointPaths' later ones are: the tuple's ten fields are what they were and every loop over them runs as before. _replace keeps it."""
     angle_residual: Optional[np.ndarray] = None      # [N]: |e_w| at the chosen pose, radians; None without an orientation goal
+    # with avoid_contact (refine_goal_poses), None without it:
+    pushed: Optional[np.ndarray] = None              # [N] bool: the chosen pose is a later iterate of the refinement than its input
+    input_clearance: Optional[np.ndarray] = None     # [N]: the least clearance of the chosen candidate before the refinement
 
     def _replace(self, **kw):
         out = super()._replace(**kw)
@@ -543,8 +482,9 @@ def gather_goal_poses(choice, cls, q, residual, clearance, self_clearance, cell_
 def concatenate_goal_poses(parts: Sequence[GoalPoses]) -> GoalPoses:
     """the GoalPoses of the chunks of one call, in order"""
     out = GoalPoses(*[np.concatenate([getattr(p, f) for p in parts]) for f in GoalPoses._fields])
-    if parts[0].angle_residual is not None:
-        out.angle_residual = np.concatenate([p.angle_residual for p in parts])
+    for name in ("angle_residual", "pushed", "input_clearance"):
+        if getattr(parts[0], name) is not None:
+            setattr(out, name, np.concatenate([getattr(p, name) for p in parts]))
     return out
 
 
@@ -555,7 +495,11 @@ def goal_poses_host(twin: KinematicEnvironment, q0, targets, obstacles, restarts
     """solve_goal_poses through the twin alone, under the device's rule and on the values the device is given: start poses,
     targets, obstacles and seeds rounded to float32, the iteration and the clearances in float64, joint_distance in float32.
     With orientations or approach_directions (orientation_goal) the iteration is solve_ik_pose on the float32 goal the device is
-    given, and the selection is fed merit in the place of residual."""
+    given, and the selection is fed merit in the place of residual.
+    avoid_contact=True (with clearance_goal, push_iterations, push_settle, push_max: contact_push.PUSH_ARGUMENTS): between the solve and
+    the clearances every candidate goes through refine_goal_poses (positional goals only); GoalPoses.pushed and .input_clearance
+    are then filled."""
+    push = pop_push(constants, orientations, approach_directions)
     r32 = lambda a: np.asarray(a, np.float64).astype(np.float32).astype(np.float64)      # noqa: E731
     q0, targets, obstacles = r32(q0), r32(targets), r32(obstacles)
     N, R = len(q0), int(restarts)
@@ -570,11 +514,15 @@ def goal_poses_host(twin: KinematicEnvironment, q0, targets, obstacles, restarts
             targets[:, None, :], og.mode, og.goals.astype(np.float64)[:, None, :], seeds, og.angle_length, weight=orientation_weight,
             tool_axis=og.tool_axis.astype(np.float64), tool_normal=og.tool_normal.astype(np.float64), iterations=iterations, **constants)
     obstacle = np.broadcast_to(obstacles[:, None, :], q.shape[:-1] + (3,))
+    refined = None if push is None else refine_goal_poses(twin, q, targets[:, None, :], obstacle, tolerance, margin, **push, **constants)
+    if refined is not None:
+        q, residual = refined.q, refined.residual
     clear = twin.clearance(q, obstacle) - twin.obstacle_radius
     self_clear, cell_clear = twin.self_clearance(q) + np.zeros(clear.shape), twin.cell_clearance(q) + np.zeros(clear.shape)
     jd = joint_distance32(q, q0[:, None, :])
     choice, cls = select_goal_pose(residual if merit is None else merit, jd, clear, self_clear, cell_clear, tolerance, margin)
-    return gather_goal_poses(choice, cls, q, residual, clear, self_clear, cell_clear, jd, tolerance, angle, merit)
+    return note_pushed(gather_goal_poses(choice, cls, q, residual, clear, self_clear, cell_clear, jd, tolerance, angle, merit),
+                       None if refined is None else refined.clear, choice)
 
 
 # ---- joint paths: the sampled collision check of start -> via -> goal polylines (include/naf_hip.h, "Joint paths") ----------------

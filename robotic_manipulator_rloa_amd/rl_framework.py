@@ -256,7 +256,8 @@ class ManipulatorFramework:
     def reach_targets(self, targets, obstacles=None, initial_joint_positions=None, frames: int = 400, noise_scale: float = 0.0,
                       n_envs: Optional[int] = None, trajectories: bool = True, goal_poses: bool = False, joint_paths: bool = False,
                       certify: bool = False, roadmap: int = 0, shortcut: int = 0, orientations=None, approach_directions=None, tool_axis=(0.0, 0.0, 1.0),
-                      orientation_tolerance: float = 1e-3, orientation_weight: Optional[float] = None):
+                      orientation_tolerance: float = 1e-3, orientation_weight: Optional[float] = None,
+                      avoid_contact: bool = False, clearance_goal: Optional[float] = None, push_iterations: int = 16):
         """Roll the trained policy out to GIVEN targets (kinematic environment only; on the device, thousands at once): query i
         starts at initial_joint_positions[i], with target targets[i] and obstacle obstacles[i], and runs until it reaches the
         target, touches the obstacle, itself or the workcell, or has taken `frames` steps. A query whose start pose is already in contact or at
@@ -288,7 +289,8 @@ class ManipulatorFramework:
         orientations / approach_directions / tool_axis / orientation_tolerance / orientation_weight (with goal_poses or
         joint_paths): the goal poses are solve_goal_poses()'s with that orientation goal, and the paths lead to them. The
         rollout's own outcome stays positional — policy, observation and reward know no orientation: 'reached' says that the end
-        effector came within the target threshold, whichever way it pointed."""
+        effector came within the target threshold, whichever way it pointed.
+        avoid_contact / clearance_goal / push_iterations (with goal_poses or joint_paths): solve_goal_poses()'s."""
         self._require_env_and_agent()
         planner = self._kinematic_planner('reach_targets', 'given-scene reset')
         if getattr(self.naf_agent, 'world_size', 1) > 1:
@@ -298,7 +300,8 @@ class ManipulatorFramework:
         return planner.reach_targets(self.naf_agent, targets, obstacles, initial_joint_positions, frames, noise_scale, n_envs,
                                      trajectories, goal_poses, joint_paths, certify, roadmap, shortcut,
                                      dict(orientations=orientations, approach_directions=approach_directions, tool_axis=tool_axis,
-                                          orientation_tolerance=orientation_tolerance, orientation_weight=orientation_weight))
+                                          orientation_tolerance=orientation_tolerance, orientation_weight=orientation_weight),
+                                     dict(avoid_contact=avoid_contact, clearance_goal=clearance_goal, push_iterations=push_iterations))
 
     @functools.cached_property
     def arm_planner(self) -> ArmPlanner:
@@ -318,7 +321,8 @@ class ManipulatorFramework:
                          candidates: int = 16, resolution: float = 0.02, clearance_margin: float = 0.0, seed: int = 0,
                          on_device: Optional[bool] = None, certify: bool = False, roadmap: int = 0, shortcut: int = 0,
                          orientations=None, approach_directions=None, tool_axis=(0.0, 0.0, 1.0),
-                         orientation_tolerance: float = 1e-3, orientation_weight: Optional[float] = None):
+                         orientation_tolerance: float = 1e-3, orientation_weight: Optional[float] = None,
+                         avoid_contact: bool = False, clearance_goal: Optional[float] = None, push_iterations: int = 16):
         """Collision-checked joint paths from start poses to goal poses (kinematic environment only; needs no agent): per query
         `candidates` joint-space polylines start -> via -> goal — candidate 0 through the midpoint, the straight line, the others
         through vias drawn around it from `seed` (environment/kinematic.py: path_vias) — are SAMPLED at poses at most `resolution`
@@ -331,6 +335,8 @@ class ManipulatorFramework:
           goal_joint_positions : [N][A] or [A]: the goal poses themselves. Exactly one of the two is given.
           orientations, approach_directions, tool_axis, orientation_tolerance, orientation_weight : with targets, the orientation
                                  goal of solve_goal_poses(); refused with goal_joint_positions
+          avoid_contact, clearance_goal, push_iterations : with targets, solve_goal_poses()'s: goal poses that lean on something
+                                 are pushed out of contact first, so fewer queries end 'goal'; refused with an orientation goal
           obstacles, initial_joint_positions : as reach_targets() takes them
           candidates           : 1 .. 64
           on_device            : None: the device when there is one; False: the float64 host twin under the same rule (slow)
@@ -372,7 +378,8 @@ class ManipulatorFramework:
         return planner.plan_joint_paths(targets, obstacles, initial_joint_positions, goal_joint_positions, candidates, resolution,
                                         clearance_margin, seed, on_device, certify, roadmap, shortcut,
                                         dict(orientations=orientations, approach_directions=approach_directions, tool_axis=tool_axis,
-                                             orientation_tolerance=orientation_tolerance, orientation_weight=orientation_weight))
+                                             orientation_tolerance=orientation_tolerance, orientation_weight=orientation_weight),
+                                        dict(avoid_contact=avoid_contact, clearance_goal=clearance_goal, push_iterations=push_iterations))
 
     def demonstrate_joint_paths(self, paths, targets=None, obstacles=None, speed: float = 1.0, frames: int = 400,
                                 keep_contact: bool = False, on_device: Optional[bool] = None, polylines: bool = False):
@@ -476,7 +483,8 @@ class ManipulatorFramework:
     def solve_goal_poses(self, targets, obstacles=None, initial_joint_positions=None, restarts: int = 8, iterations: int = 32,
                          tolerance: float = 1e-3, clearance_margin: float = 0.0, seed: int = 0, on_device: Optional[bool] = None,
                          orientations=None, approach_directions=None, tool_axis=(0.0, 0.0, 1.0),
-                         orientation_tolerance: float = 1e-3, orientation_weight: Optional[float] = None):
+                         orientation_tolerance: float = 1e-3, orientation_weight: Optional[float] = None,
+                         avoid_contact: bool = False, clearance_goal: Optional[float] = None, push_iterations: int = 16):
         """Joint values that put the end effector on GIVEN targets (kinematic environment only; needs no agent): per query a
         damped least-squares iteration on the end effector's positional Jacobian from `restarts` seeds — the start pose and
         restarts - 1 poses drawn uniformly inside the limits from `seed` — for `iterations` updates each, then the choice among
@@ -495,6 +503,14 @@ class ManipulatorFramework:
           orientation_tolerance : radians; with an orientation goal a pose is converged iff |target - end effector| <= tolerance
                                 and the angle left to the goal <= orientation_tolerance
           orientation_weight  : metres per radian, how a radian of angular error weighs against a metre (None: 0.25 reach)
+          avoid_contact       : True: between the iteration and the choice every converged candidate that is closer than
+                                clearance_goal to the obstacle, the arm itself or the workcell is refined on the device (or by the
+                                twin) by push_iterations updates that hold the end effector on the target and push the pose away
+                                from its least clearance in the task's null space (environment/kinematic.py: refine_goal_poses);
+                                a candidate is never worse than it came in. Positional goals only: refused together with
+                                orientations or approach_directions. The result's pushed [N] and input_clearance [N] are then
+                                filled (None otherwise).
+          clearance_goal      : the clearance the push aims for (None: clearance_margin + 0.02)
         With an orientation goal the iteration runs on the 6-row Jacobian of position and orientation (environment/kinematic.py:
         orientation_error, ik_pose_step), and the result's angle_residual [N] holds the angle left at the chosen pose.
         Returns environment.kinematic.GoalPoses, arrays over the queries: reachable, free, joint_positions [N][A], residual,
@@ -504,7 +520,8 @@ class ManipulatorFramework:
         return planner.solve_goal_poses(targets, obstacles, initial_joint_positions, restarts, iterations, tolerance, clearance_margin,
                                         seed, on_device,
                                         dict(orientations=orientations, approach_directions=approach_directions, tool_axis=tool_axis,
-                                             orientation_tolerance=orientation_tolerance, orientation_weight=orientation_weight))
+                                             orientation_tolerance=orientation_tolerance, orientation_weight=orientation_weight),
+                                        dict(avoid_contact=avoid_contact, clearance_goal=clearance_goal, push_iterations=push_iterations))
 
     # ---- environment ------------------------------------------------------------------------------------------------
     def initialize_environment(self, manipulator_file: str, endeffector_index: int, fixed_joints: List[int],
