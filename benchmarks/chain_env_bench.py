@@ -95,6 +95,16 @@ launches are the box instantiations, which test the floor and the spheres too.
       ones), with their ratios and the new kernels' registers. Then the whole ManipulatorFramework.plan_linear_moves call (upload,
       tracking launch, download, verdict, the legs' edge launch, gather) in host milliseconds, and the outcomes it reports.
 
+  python benchmarks/chain_env_bench.py traj [--launches 20] [--certify] [--boxes] [--envs 2048]
+      time-parameterised trajectories, same arm (with self-collision, the floor and the two spheres): N = --envs targets (default
+      2048 here) around the nominal one, their paths planned with --roadmap 14 --shortcut 16, driven at vmax 1 rad/s, amax 4 rad/s^2
+      and the environment's tick. Microseconds per naf_chain_traj_check launch between device events beside naf_chain_edge_check
+      over the SAME number of walked poses — as many items, E = ticks / 256 edges of 256 samples each — alternating launch by
+      launch in the same process (median and minimum of `--launches`, at most 50, after two unmeasured ones), with the ratio;
+      --certify: the same for naf_chain_traj_certify beside naf_chain_edge_certify. Then what the trajectories of the free
+      polylines come to, what those of the certified polylines come to under certify at the same margin, the durations against a
+      stop at every corner, and the new kernels' registers.
+
 `--hindsight R` (rate): the chain runs relabel a share R of every minibatch (NAFAgent.run_vectorized(hindsight=R)). Such a run
 wants an empty ring, so with the flag — also `--hindsight 0`, the figure to compare with — the warm-up steps run on an agent of
 their own and the timed run starts on a fresh one (its graph captures are inside the timed window, in both).
@@ -970,6 +980,100 @@ def line(a):
                       "start_poses_reachable_of": [int(goal.reachable.sum()), N], "kernel_registers": regs}))
 
 
+def traj(a):
+    import numpy as np
+    import torch
+    from robotic_manipulator_rloa_amd import _lib
+    from robotic_manipulator_rloa_amd.chain_certify import PolylineCertifier
+    from robotic_manipulator_rloa_amd.chain_tools import GoalPoseSolver, JointPathChecker
+    from robotic_manipulator_rloa_amd.chain_traj import TrajectoryChecker
+    from robotic_manipulator_rloa_amd.environment.edge_certificate import polyline_nodes
+    from robotic_manipulator_rloa_amd.environment.kinematic import roadmap_edges
+    from robotic_manipulator_rloa_amd.environment.trajectory import DeviceSchedule, blend_schedule, device_schedule
+    from robotic_manipulator_rloa_amd.environment.urdf_chain import compile_chain, load_urdf
+    n_joints, M, W, N, dt = a.joints, a.roadmap or 14, a.shortcut or 16, (2048 if a.envs == 64 else a.envs), 1.0 / 240.0
+    launches = min(a.launches, 50)
+    a.workcell = True
+    urdf = os.path.abspath(a.urdf) if os.path.isabs(a.urdf) else os.path.join(ROOT, a.urdf)
+    init = ([0.0, 0.6, 0.0, -1.2, 0.0, 0.8, 0.0] + [0.0] * n_joints)[:n_joints]
+    model = compile_chain(load_urdf(urdf), n_joints - 1, list(range(n_joints)), [n_joints], init, [0.1] * n_joints, 0.03,
+                          consider_autocollision=True, **_workcell(a))
+    rng = np.random.default_rng(5)
+    targets = np.array([0.45, 0.3, 0.6]) + rng.uniform(-0.25, 0.25, (N, 3))
+    start, obstacle = np.tile(init, (N, 1)), np.tile([0.35, 0.2, 0.45], (N, 1))
+    goal = GoalPoseSolver(model, 0.06).solve(start, targets, obstacle)
+    ok = goal.free
+    checker, certifier, tool = JointPathChecker(model, 0.06), PolylineCertifier(model, 0.06), TrajectoryChecker(model, 0.06)
+    found = checker.check(start[ok], goal.joint_positions[ok], obstacle[ok], candidates=16, resolution=0.02, roadmap=M, shortcut=W)
+    ob = obstacle[ok]
+    vmax, amax = np.full(n_joints, 1.0), np.full(n_joints, 4.0)
+    # the launch, beside the edge launch over the same number of walked poses
+    nodes, count = polyline_nodes(found)
+    has = np.flatnonzero(count >= 2)
+    sched = [blend_schedule(nodes[q, :count[q]].astype(np.float32).astype(np.float64), vmax, amax) for q in has]
+    ds = device_schedule(sched, dt)
+    S = -(-int(ds.n_samples.max()) // 256) * 256              # a multiple of 256: E edges of 256 samples walk the same S poses
+    per = min(len(has), tool.chunk // S)
+    part = DeviceSchedule(*(x[:per] for x in ds[:5]), ds.dt)
+    E, V = S // 256, nodes.shape[1] if nodes.shape[1] * (nodes.shape[1] - 1) // 2 >= S // 256 else 16
+    edge_nodes = np.zeros((per, V, n_joints), np.float32)
+    edge_nodes[:, :part.nodes.shape[1]] = part.nodes
+    edge_nodes[:, part.nodes.shape[1]:] = part.nodes[:, -1:]
+    edges = roadmap_edges(V)[:E]
+    checker.load_edges(edge_nodes, edges, ob[has[:per]])
+    timing = {}
+    for certify in ((False, True) if a.certify else (False,)):
+        tool.records(part, ob[has[:per]], S, 0.0, certify, False)            # (uploads, and one unmeasured launch)
+        if certify:
+            certifier.edge_records(edge_nodes, edges, ob[has[:per]], 256, 0.0)
+        edge_launch = (lambda: certifier.launch(per, V, E, 256, 0.0)) if certify else (lambda: checker.launch_edges(per, V, E, 256, 0.0))
+        times = {"edge": [], "traj": []}
+        for i in range(launches + 2):                          # alternating, so that both see the same clocks
+            for name, launch in (("edge", edge_launch), ("traj", lambda: tool.launch(per, part.nodes.shape[1], S, ds.dt, 0.0, certify, False))):
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+                launch()
+                t1.record()
+                t1.synchronize()
+                if i >= 2:
+                    times[name].append(1e3 * t0.elapsed_time(t1))
+        stat = lambda v: {"median": round(float(np.median(v)), 1), "min": round(float(np.min(v)), 1)}      # noqa: E731
+        timing["certify" if certify else "check"] = {
+            "us_per_edge_launch": stat(times["edge"]), "us_per_traj_launch": stat(times["traj"]),
+            "traj_over_edge_median": round(float(np.median(times["traj"]) / np.median(times["edge"])), 3)}
+    # the shares: the trajectories of the free polylines, and of the certified ones
+    count_of = lambda x: {str(k): int(v) for k, v in zip(*np.unique(x, return_counts=True))}      # noqa: E731
+    import time
+    before, whole = tool.launches, []
+    for i in range(5):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        plain = tool.plan(found, ob, vmax, amax, dt, False, 0.0, positions=False)
+        whole.append(1e3 * (time.perf_counter() - t))
+    per_call = (tool.launches - before) // 5
+    margin = 2e-4 * model.A * model.reach
+    cert_poly = certifier.certify(found, ob, margin, 0.02)
+    cert_traj = tool.plan(found, ob, vmax, amax, dt, True, margin, positions=False)
+    ratio = (plain.duration / plain.rest_to_rest_duration)[plain.outcome != "none"]
+    usage = json.load(open(_lib.USAGE_PATH)) if os.path.exists(_lib.USAGE_PATH) else {}
+    regs = {name: {q: v.get(q) for q in ("vgprs", "sgprs", "scratch_bytes_per_lane", "lds_bytes", "occupancy")}
+            for name, v in usage.items() if "chain_traj_" in name}
+    print(json.dumps({"arm": os.path.basename(urdf), "self_pairs": len(model.self_pairs), "workcell_pairs": len(model.cell_pairs),
+                      "boxes": bool(a.boxes), "targets": N, "free_goal_poses": int(ok.sum()), "polylines": int(len(has)),
+                      "path_outcomes": count_of(found.outcome), "vmax": 1.0, "amax": 4.0, "dt": dt,
+                      "launch": {"trajectories": per, "ticks": S, "edges_of_256_samples": E, "walked_poses": per * S, **timing},
+                      "ms_per_plan_call_host_clock": {"median": round(float(np.median(whole[1:])), 1), "launches": per_call},
+                      "trajectories_of_free_polylines": count_of(plain.outcome[plain.outcome != "none"]),
+                      "margin": round(float(margin), 6), "polyline_certificates": count_of(cert_poly.outcome),
+                      "trajectories_of_certified_polylines": count_of(cert_traj.outcome[cert_poly.outcome == "certified"]),
+                      "duration_over_rest_to_rest": {"median": round(float(np.median(ratio)), 3), "min": round(float(ratio.min()), 3),
+                                                     "max": round(float(ratio.max()), 3)},
+                      "ticks_per_trajectory": {"median": int(np.median(plain.n_samples[plain.n_samples > 0])), "max": int(plain.n_samples.max())},
+                      "corner_deviation_rad": {"median": round(float(np.nanmedian(plain.corner_deviation)), 4),
+                                               "max": round(float(np.nanmax(plain.corner_deviation)), 4)},
+                      "kernel_registers": regs}))
+
+
 def kernels(a):
     import numpy as np
     import torch
@@ -1008,7 +1112,7 @@ def kernels(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["rate", "kernels", "step", "rollout", "gather", "ik", "path", "demo", "edgecert", "line"])
+    ap.add_argument("what", choices=["rate", "kernels", "step", "rollout", "gather", "ik", "path", "demo", "edgecert", "line", "traj"])
     ap.add_argument("--urdf", default=os.path.join("tests", "golden", "urdf", "iiwa_like7.urdf"))
     ap.add_argument("--joints", type=int, default=7)
     ap.add_argument("--envs", type=int, default=64)
@@ -1021,7 +1125,7 @@ def main():
     ap.add_argument("--autocollision", action="store_true")
     ap.add_argument("--workcell", action="store_true", help="step / rollout: a floor and two spheres in the chain model")
     ap.add_argument("--boxes", action="store_true", help="step / rollout / path, with --workcell: three boxes beside the floor and the spheres")
-    ap.add_argument("--certify", action="store_true", help="path: time naf_chain_path_certify beside naf_chain_path_check, and certify the README's paths")
+    ap.add_argument("--certify", action="store_true", help="path: time naf_chain_path_certify beside naf_chain_path_check, and certify the README's paths; traj: also time the certifying launches")
     ap.add_argument("--roadmap", type=int, default=0, metavar="M",
                     help="path: time naf_chain_edge_check beside naf_chain_path_check, and answer the README's paths with M milestones")
     ap.add_argument("--shortcut", type=int, default=0, metavar="W",
@@ -1039,14 +1143,14 @@ def main():
     ap.add_argument("--hindsight", type=float, default=None, help="rate, gather: the share of rows replayed under a hindsight goal")
     ap.add_argument("--horizon", type=int, default=None, help="rate, gather: hindsight_horizon (rate: max_frames; gather: 400)")
     a = ap.parse_args()
-    if a.roadmap and a.certify and a.what != "edgecert":
+    if a.roadmap and a.certify and a.what not in ("edgecert", "traj"):
         ap.error("--roadmap and --certify are two measurements: roadmap edges are checked at their samples only")
-    if a.shortcut and not a.roadmap and a.what != "edgecert":
+    if a.shortcut and not a.roadmap and a.what not in ("edgecert", "traj"):
         ap.error("--shortcut shortens roadmap paths: it needs --roadmap M")
     if a.legs and not 2 <= a.legs <= 63:
         ap.error("--legs K splits two-leg plans into K legs, 2 .. 63")
     {"rate": rate, "kernels": kernels, "step": step, "rollout": rollout, "gather": gather, "ik": ik, "path": paths, "demo": demo,
-     "edgecert": edgecert, "line": line}[a.what](a)
+     "edgecert": edgecert, "line": line, "traj": traj}[a.what](a)
 
 
 if __name__ == "__main__":

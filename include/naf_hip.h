@@ -1174,6 +1174,45 @@ int naf_chain_edge_certify(naf_chain_env_t* h, const float* nodes_dev, const int
                            float obstacle_radius, const float* reach_dev, float guard, int N, int V, int E, int S, float margin,
                            float* out, float* poses_out, void* stream);
 
+/* Trajectories (an addition within ABI 40): a law in TIME along a joint-space polyline — linear segments with parabolic blends, so
+ * that the arm need not stop at a corner — sampled at a controller's ticks and walked as naf_chain_edge_check walks an edge's
+ * samples. A blended corner LEAVES the polyline, so a verdict or a certificate of the polyline says nothing about it: this launch
+ * tests what the arm would drive. environment/trajectory.py (blend_schedule, trajectory_law, check_trajectory) is the float64
+ * statement; the schedule is formed there, on the host, and the launch evaluates it.
+ *   nodes_dev     : [N][V][A] (DEVICE): P_0 .. P_K of trajectory n, K + 1 = n_nodes_dev[n] in 1 .. V, V in 2 .. 64; consecutive nodes
+ *                   differ; the rows behind a trajectory's last node repeat it.
+ *   times_dev     : [N][V][3] (DEVICE): per node k (t_k, tau_k, 1 / T_k): its nominal time, the duration of the blend centred on it,
+ *                   and the reciprocal of leg k's duration (0 at k = 0). t_0 = tau_0 / 2; (tau_{k-1} + tau_k) / 2 <= T_k.
+ *   vpeak_dev     : [N][A] (DEVICE): max_k |v_km|, rounded up. n_samples_dev: [N] int32 (DEVICE): S_n = ceil(D_n / dt) + 1 in 1 .. S,
+ *                   D_n = t_K + tau_K / 2. The caller validates the counts before the upload; the kernel clamps a stray one.
+ *   the law       : leg k = 1 .. K runs P_{k-1} -> P_k at v_k = (P_k - P_{k-1}) (1 / T_k); v_0 = v_{K+1} = 0; legs 0 and K + 1 are
+ *                   virtual, P_0 -> P_0 over [0, t_0] and P_K -> P_K from t_K on. Sample i is at t = (float)i * dt; its leg j is how
+ *                   many t_k, k <= K, are <= t; s = t - (j ? t_{j-1} : 0); h0 = max(0, tau_{j-1} / 2 - s),
+ *                   h1 = max(0, (t - t_j) + tau_j / 2) (0 for j = K + 1; tau is 0 outside 0 .. K);
+ *                   q_m = fmaf(c1, v_{j+1} - v_j, fmaf(c0, v_j - v_{j-1}, fmaf(v_j, s, P_{j-1,m}))), c0 = h0^2 / (2 tau_{j-1}),
+ *                   c1 = h1^2 / (2 tau_j), 0 where the tau is 0. q(0) = P_0 and q(t) = P_K for t >= D, exactly. No limits are applied.
+ *   live samples  : i < S_n. A sample i >= S_n evaluates to P_K, is walked and written to poses_out, and COUNTS IN NOTHING: not in the
+ *                   minima, not in [3], not in [4], not in [8 .. 11].
+ *   out           : [N][NAF_CHAIN_EDGE_FLOATS] (DEVICE) = [0 .. 4] as naf_chain_edge_check, over the live samples | [5] D_n | [6]
+ *                   max_m vpeak_m dt, the bound on a joint's step between two ticks | [7] whether the last live sample is blocked.
+ *   poses_out     : NULL, or DEVICE [N][S][A]: every sample's pose.
+ * naf_chain_traj_certify adds the statement about the poses BETWEEN the ticks. Between two ticks joint m moves at most vpeak_m dt,
+ * so there is ONE table per trajectory: beta[s] = 1/2 dt sum_m vpeak_m reach[m][s], the pairs by naf_chain_edge_certify's span rule
+ * (float32: the joint sum by fmaf in joint order from 0, then times (0.5f * dt)). Slacks, guard and verdict are
+ * naf_chain_edge_certify's: out is [N][NAF_CHAIN_EDGE_CERT_FLOATS], [8] [9] [10] the minima over the live samples of
+ * (clearance - beta - guard), [11] the first live sample one of whose slacks is < margin, -1: none — then no pose of the trajectory
+ * is closer than margin. Its LDS rule and NAF_CHAIN_ERR_LDS are naf_chain_edge_certify's.
+ * One workgroup per trajectory, a lane per sample of a pass, S / lanes passes; S is a multiple of 64 in 64 .. 8192. NAF_ERR_ARG, and
+ * no launch, for a null pointer other than poses_out, N < 1, V outside 2 .. 64, S outside 64 .. 8192 or no multiple of 64, a dt that
+ * is not finite or not positive, a margin or radius that is not finite, a negative radius (and guard, as naf_chain_edge_certify). */
+int naf_chain_traj_check(naf_chain_env_t* h, const float* nodes_dev, const int32_t* n_nodes_dev, const float* times_dev,
+                         const float* vpeak_dev, const int32_t* n_samples_dev, const float* obstacles_dev, float obstacle_radius,
+                         float dt, int N, int V, int S, float margin, float* out, float* poses_out, void* stream);
+int naf_chain_traj_certify(naf_chain_env_t* h, const float* nodes_dev, const int32_t* n_nodes_dev, const float* times_dev,
+                           const float* vpeak_dev, const int32_t* n_samples_dev, const float* obstacles_dev, float obstacle_radius,
+                           const float* reach_dev, float guard, float dt, int N, int V, int S, float margin, float* out,
+                           float* poses_out, void* stream);
+
 /* Demonstrations (an addition within ABI 40): N planned joint paths turned into the replay rows of the episodes that follow them
  * open loop, one launch. environment/kinematic.py (demonstration_plan, demonstration_rows_host) is the float64 statement.
  *   Demonstration n starts at q_start_dev[n] clamped into the limits (p_0) in the scene targets_dev[n] / obstacles_dev[n] with

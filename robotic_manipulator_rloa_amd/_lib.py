@@ -299,6 +299,8 @@ _PROTOS = {
     "naf_chain_demo_rows_legs": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _i, _i, _vp, _i, _vp, _vp, _vp],
     "naf_chain_edge_check": [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _f, _vp, _vp, _vp],
     "naf_chain_edge_certify": [_vp, _vp, _vp, _vp, _f, _vp, _f, _i, _i, _i, _i, _f, _vp, _vp, _vp],
+    "naf_chain_traj_check": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _i, _f, _vp, _vp, _vp],
+    "naf_chain_traj_certify": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _f, _f, _i, _i, _i, _f, _vp, _vp, _vp],
     "naf_vec_act_env_append": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _f, _i, _vp, _i,
                                _vp, _u64, _vp, _vp, _f, _i, _i, _i, _vp, _vp],
     "naf_vec_draw_gather_moments": [_vp, _u64, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp],

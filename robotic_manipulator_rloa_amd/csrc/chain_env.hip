@@ -1830,6 +1830,10 @@ extern "C" int naf_chain_line_track(naf_chain_env_t* h, const float* q_start_dev
 //             the record's floats 5 .. 7 are the two legs' summed length, the larger step, and whether the goal sample is blocked
 //   EdgeLine  ONE leg of S - 1 intervals, sample i at i / (S - 1), both ends included; one table, which every sample uses; floats
 //             5 .. 7 are the length, the step and 0
+//   TrajLine  a law in TIME along a polyline of up to 63 legs (include/naf_hip.h, "Trajectories"): sample i is the tick (float)i dt;
+//             one table, of the joints' peak speeds over half a tick; only the samples below the trajectory's own count are LIVE —
+//             the others evaluate to the last node and count in nothing (Line::MASKED; absent at compile time for the other two);
+//             floats 5 .. 7 are the duration, the largest joint step between two ticks and whether the last live sample is blocked
 struct ChainCert {
     const float* reach;      // [A][n_seg] (DEVICE)
     float guard;
@@ -1849,6 +1853,7 @@ __host__ __device__ static inline size_t ch_cert_lds_bytes(int n_seg, int n_pair
 // ViaLine: start -> via over samples 0 .. h, via -> goal over h .. S - 1, h = S / 2; three tables (leg 1, leg 2, their maximum).
 struct ViaLine {
     static constexpr bool GOAL = true;      // the record reports whether the last sample, the goal, is blocked
+    static constexpr bool MASKED = false;   // every sample counts
     const float *start, *via, *goal;
     int h;
     struct Sample {
@@ -1893,6 +1898,7 @@ struct ViaLine {
 // has LDS for one.
 struct EdgeLine {
     static constexpr bool GOAL = false;
+    static constexpr bool MASKED = false;
     const float *a, *b;
     int last;      // S - 1
     __device__ float sample(int i) const { return (float)i / (float)last; }
@@ -1912,6 +1918,59 @@ struct EdgeLine {
         o[5] = len;
         o[6] = len / (float)last;
         o[7] = 0.f;
+    }
+};
+
+// TrajLine: linear segments with parabolic blends in time (environment/trajectory.py states the law). The schedule is the host's:
+// nodes P_k, and per node (t_k, tau_k, 1 / T_k). sample(i) finds the leg j of t = (float)i dt — how many node times are <= t, a
+// uniform scan of at most 64 — and what of the law does not depend on the joint; pose(sample, m) forms the three velocities it
+// needs from four node values. Legs 0 and K + 1 are the virtual ones: their 1 / T reads as 0 and their node indices are clamped,
+// so v_0 = v_{K+1} = 0 without a branch. Nothing but the node loads is indexed per lane.
+struct TrajLine {
+    static constexpr bool GOAL = true;      // float 7: whether the last LIVE sample is blocked
+    static constexpr bool MASKED = true;    // samples i >= live count in nothing
+    const float *nodes, *times, *vpeak;     // [V][A], [V][3], [A] of this trajectory
+    int A, n, live;                         // n = K + 1 nodes; live = S_n
+    float dt;
+    struct Sample {
+        int j;
+        float s, c0, c1, wm, w, wp;         // c0 = h0^2 / (2 tau_{j-1}), c1 = h1^2 / (2 tau_j); 1 / T of legs j - 1, j, j + 1 (0: virtual)
+    };
+    __device__ Sample sample(int i) const {
+        const float t = (float)i * dt;
+        int j = 0;
+        for (int k = 0; k < n; ++k) j += times[3 * k] <= t ? 1 : 0;
+        const int K = n - 1;
+        const int jp = max(j - 1, 0), jn = min(j, K), jq = min(j + 1, K);
+        const float s = t - (j >= 1 ? times[3 * jp] : 0.f);
+        const float tau_p = j >= 1 ? times[3 * jp + 1] : 0.f, tau_n = j <= K ? times[3 * jn + 1] : 0.f;
+        const float h0 = fmaxf(0.f, 0.5f * tau_p - s);
+        const float h1 = j <= K ? fmaxf(0.f, (t - times[3 * jn]) + 0.5f * tau_n) : 0.f;
+        const float c0 = tau_p > 0.f ? 0.5f * h0 * h0 * (1.f / tau_p) : 0.f, c1 = tau_n > 0.f ? 0.5f * h1 * h1 * (1.f / tau_n) : 0.f;
+        return {j, s, c0, c1, j >= 2 ? times[3 * jp + 2] : 0.f, j >= 1 && j <= K ? times[3 * jn + 2] : 0.f,
+                j + 1 <= K ? times[3 * jq + 2] : 0.f};
+    }
+    __device__ float pose(const Sample& at, int m) const {
+        const int K = n - 1;
+        const float pm2 = nodes[max(at.j - 2, 0) * A + m], pm1 = nodes[max(at.j - 1, 0) * A + m];
+        const float p0 = nodes[min(at.j, K) * A + m], p1 = nodes[min(at.j + 1, K) * A + m];
+        const float v_prev = (pm1 - pm2) * at.wm, v = (p0 - pm1) * at.w, v_next = (p1 - p0) * at.wp;
+        return fmaf(at.c1, v_next - v, fmaf(at.c0, v - v_prev, fmaf(v, at.s, pm1)));
+    }
+    __device__ bool counts(int i) const { return i < live; }
+    __device__ int last() const { return live - 1; }
+    __device__ int table_of(int) const { return 0; }
+    __device__ void fill(float* t, int, int e, int s, int m0, int m1, const float* reach, int n_seg) const {
+        float acc = 0.f;
+        for (int m = m0; m < m1; ++m) acc = fmaf(vpeak[m], reach[m * n_seg + s], acc);
+        t[e] = (0.5f * dt) * acc;
+    }
+    __device__ void finish(float* o, int, int last_blocked) const {
+        float step = 0.f;
+        for (int m = 0; m < A; ++m) step = fmaxf(step, vpeak[m] * dt);
+        o[5] = times[3 * (n - 1)] + 0.5f * times[3 * (n - 1) + 1];
+        o[6] = step;
+        o[7] = (float)last_blocked;
     }
 };
 
@@ -1971,6 +2030,8 @@ __device__ __forceinline__ void chain_sweep(const float* __restrict__ model, con
             self_clear = self_clearance_phase<CERT>(model, A, n_seg, n_pairs, ch_lds, lanes, lane, active,
                                                     CERT ? aux.beta + n_seg : nullptr, &self_slack);
         if (walker) {
+            if constexpr (Line::MASKED)      // (a dead sample walked, wrote its pose, and counts in nothing; this ends the pass's body)
+                if (!line.counts(i)) continue;
             const float clear = aux.clear - orad;
             const bool blocked = clear < margin || self_clear < margin || (CELL && aux.cell < margin);
             min_clear = fminf(min_clear, clear);
@@ -1978,7 +2039,8 @@ __device__ __forceinline__ void chain_sweep(const float* __restrict__ model, con
             if constexpr (CELL) min_cell = fminf(min_cell, aux.cell);
             first = blocked && i < first ? i : first;
             count += blocked ? 1 : 0;
-            if constexpr (Line::GOAL) goal_blocked |= blocked && i == S - 1 ? 1 : 0;
+            if constexpr (Line::MASKED) goal_blocked |= blocked && i == line.last() ? 1 : 0;
+            else if constexpr (Line::GOAL) goal_blocked |= blocked && i == S - 1 ? 1 : 0;
             if constexpr (CERT) {
                 const float s0 = aux.slack - orad - guard, s1 = self_slack - guard, s2 = aux.cell_slack - guard;
                 low_clear = fminf(low_clear, s0);
@@ -2131,6 +2193,66 @@ extern "C" int naf_chain_edge_certify(naf_chain_env_t* h, const float* nodes_dev
         return ch_launch_raising<chain_edge_check_kernel<sc(), ChainCert, decltype(cell)...>>(
             CH_MAX_DYN_LDS, (unsigned)((int64_t)N * E), w, stream, h->model_dev, nodes_dev, edges_dev, obstacles_dev, obstacle_radius,
             V, E, S, h->A, h->n_seg, w.n_pairs, w.lanes, margin, out, poses_out, cert, cell...);
+    });
+}
+
+// ---- trajectories: a time law along a polyline, checked at a controller's ticks (include/naf_hip.h, "Trajectories") --------------
+// chain_sweep along a TrajLine. One workgroup per trajectory n: its nodes, times, peak speeds and counts are uniform loads. A leading
+// ChainCert in the pack is naf_chain_traj_certify's kernel: the record has NAF_CHAIN_EDGE_CERT_FLOATS floats.
+template <bool SC, class... Cell>
+__global__ void __launch_bounds__(SC ? 64 * CH_MAX_WAVES : 64)
+chain_traj_check_kernel(const float* __restrict__ model, const float* __restrict__ nodes, const int32_t* __restrict__ n_nodes,
+                        const float* __restrict__ times, const float* __restrict__ vpeak, const int32_t* __restrict__ n_samples,
+                        const float* __restrict__ obstacles, float orad, float dt, int V, int S, int A, int n_seg, int n_pairs,
+                        int lanes, float margin, float* __restrict__ out, float* __restrict__ poses_out, const Cell... cell) {
+    constexpr bool CERT = (std::is_same_v<Cell, ChainCert> || ... || false);
+    const int64_t n = blockIdx.x;
+    // (the host validated 1 <= n_nodes <= V and 1 <= n_samples <= S before the upload; the clamps keep a stray count inside)
+    const TrajLine line = {nodes + n * V * A, times + n * V * 3, vpeak + n * A, A, min(max(n_nodes[n], 1), V),
+                           min(max(n_samples[n], 1), S), dt};
+    chain_sweep<SC>(model, line, obstacles[n * 3], obstacles[n * 3 + 1], obstacles[n * 3 + 2], orad, S, A, n_seg, n_pairs, lanes, margin,
+                    out + n * (CERT ? NAF_CHAIN_EDGE_CERT_FLOATS : NAF_CHAIN_EDGE_FLOATS), poses_out, n, cell...);
+}
+
+// what naf_chain_traj_check and naf_chain_traj_certify ask of the arguments they share
+static inline bool ch_traj_args_ok(int N, int V, int S, float dt, float margin, float obstacle_radius) {
+    if (N < 1 || N > 1 << 30 || V < 2 || V > 64 || S < 64 || S > 8192 || S % 64 != 0) return false;
+    return std::isfinite(dt) && dt > 0.f && std::isfinite(margin) && std::isfinite(obstacle_radius) && obstacle_radius >= 0.f;
+}
+
+// One workgroup per trajectory; the SC kernels' dynamic LDS is the probe's.
+extern "C" int naf_chain_traj_check(naf_chain_env_t* h, const float* nodes_dev, const int32_t* n_nodes_dev, const float* times_dev,
+                                    const float* vpeak_dev, const int32_t* n_samples_dev, const float* obstacles_dev,
+                                    float obstacle_radius, float dt, int N, int V, int S, float margin, float* out, float* poses_out,
+                                    void* stream) {
+    if (!h || !nodes_dev || !n_nodes_dev || !times_dev || !vpeak_dev || !n_samples_dev || !obstacles_dev || !out) return NAF_ERR_ARG;
+    if (!ch_traj_args_ok(N, V, S, dt, margin, obstacle_radius)) return NAF_ERR_ARG;
+    return ch_with_pack(h, [&](auto sc, auto... cell) {
+        const ChShape w = ch_shape<sc()>(h, h->waves);
+        return ch_launch_raising<chain_traj_check_kernel<sc(), decltype(cell)...>>(
+            CH_MAX_DYN_LDS, (unsigned)N, w, stream, h->model_dev, nodes_dev, n_nodes_dev, times_dev, vpeak_dev, n_samples_dev,
+            obstacles_dev, obstacle_radius, dt, V, S, h->A, h->n_seg, w.n_pairs, w.lanes, margin, out, poses_out, cell...);
+    });
+}
+
+// The certifying trajectory launch: naf_chain_edge_certify's LDS — the SC rows with the second reduction row per wave, then ONE table.
+extern "C" int naf_chain_traj_certify(naf_chain_env_t* h, const float* nodes_dev, const int32_t* n_nodes_dev, const float* times_dev,
+                                      const float* vpeak_dev, const int32_t* n_samples_dev, const float* obstacles_dev,
+                                      float obstacle_radius, const float* reach_dev, float guard, float dt, int N, int V, int S,
+                                      float margin, float* out, float* poses_out, void* stream) {
+    if (!h || !nodes_dev || !n_nodes_dev || !times_dev || !vpeak_dev || !n_samples_dev || !obstacles_dev || !reach_dev || !out)
+        return NAF_ERR_ARG;
+    if (!ch_traj_args_ok(N, V, S, dt, margin, obstacle_radius)) return NAF_ERR_ARG;
+    if (!std::isfinite(guard) || guard < 0.f) return NAF_ERR_ARG;
+    const size_t lds = (ch_cert_table_floats(h->n_seg, h->n_pairs, h->lanes, h->waves) + (size_t)(h->n_seg + h->n_pairs)) * sizeof(float);
+    if (lds > (h->n_pairs > 0 ? CH_MAX_DYN_LDS : 64 * 1024)) return NAF_CHAIN_ERR_LDS;
+    const ChainCert cert = {reach_dev, guard};
+    return ch_with_pack(h, [&](auto sc, auto... cell) {
+        ChShape w = ch_shape<sc()>(h, h->waves);
+        w.lds = lds;      // (the table: also without pairs)
+        return ch_launch_raising<chain_traj_check_kernel<sc(), ChainCert, decltype(cell)...>>(
+            CH_MAX_DYN_LDS, (unsigned)N, w, stream, h->model_dev, nodes_dev, n_nodes_dev, times_dev, vpeak_dev, n_samples_dev,
+            obstacles_dev, obstacle_radius, dt, V, S, h->A, h->n_seg, w.n_pairs, w.lanes, margin, out, poses_out, cert, cell...);
     });
 }
 
