@@ -1196,14 +1196,15 @@ def demonstration_rows_host(twin: KinematicEnvironment, plan: DemonstrationPlan,
     vel = np.where((pre < lo) | (pre > hi), 0.0, actions)
     qd = np.concatenate([np.zeros((N, 1, A)), vel], axis=1)
     obs = demo_observations(twin, path, qd, targets[:, None, :], obstacles[:, None, :])    # [N, T + 1, S]
-    dist = m[:, :, 0] + TARGET_THRESHOLD
-    reached = dist < TARGET_THRESHOLD
+    # trace's own margin d - 0.05: reached iff it is negative (x - y < 0 iff x < y in IEEE arithmetic), and the shaped reward is its
+    # negative, bit for bit step()'s -1 * (d - 0.05) — adding the threshold back and subtracting it again loses the last bit
+    reached = m[:, :, 0] < 0.0
     hit = (m[:, :, 1] < 0.0) | (m[:, :, 2] < 0.0) | (m[:, :, 3] < 0.0)
     rows = np.zeros((N, T, rf))
     rows[:, :, :S] = obs[:, :-1]
     rows[:, :, S:S + A] = actions
     with np.errstate(invalid="ignore"):
-        rows[:, :, S + A] = np.where(reached, 250.0, np.where(hit, -1000.0, -(dist - TARGET_THRESHOLD)))
+        rows[:, :, S + A] = np.where(reached, 250.0, np.where(hit, -1000.0, -1 * m[:, :, 0]))
     rows[:, :, off_s2:off_s2 + S] = obs[:, 1:]
     rows[:, :, off_d] = reached | hit
     rows[~live] = np.nan

@@ -3,7 +3,7 @@ Generates tests/golden/*.npz by importing and running the UNMODIFIED reference
 (/root/reference, JavierMtz5/robotic_manipulator_rloa) on CPU. Runs only in the build container — the
 GPU box has no /root/reference; the fixtures (numbers only) are what travels.
 
-Usage (from anywhere):  python tests/golden/make_golden.py [--g5-updates N]
+Usage (from anywhere):  python tests/golden/make_golden.py [--g5-updates N] [--only g1,g9,...]
 
 The reference imports pybullet at package import; pybullet is not installed, so two stub modules are put
 on sys.path first (a MagicMock-attribute `pybullet`, a one-function `pybullet_data`). Import side effects
@@ -468,8 +468,43 @@ def main():
             print(f"g8: {tag}: {n_upd} updates in {dt:.1f}s = {n_upd / dt:.1f} updates/s (reference learn(), CPU)", flush=True)
         np.savez_compressed(os.path.join(HERE, "g8_curves.npz"), data_seed=np.array(2024), idx_seed=np.array(99), **out)
 
-    with open(os.path.join(HERE, "VERSIONS.txt"), "w") as f:
+    # ---------------- G9: the reference's Environment under a scripted simulator (tests/scripted_pybullet.py; the scenarios are
+    # g9_scenarios.py's). The reference's modules bound `pybullet` at import; each scenario gets its own scripted module in their
+    # place. Numbers and call logs only; written with fixed zip timestamps, so a second run gives the same bytes.   --only g9
+    g9_line = None
+    if want("g9"):
+        import io
+        import zipfile
+        sys.path.insert(0, os.path.dirname(HERE))
+        import g9_scenarios
+        import scripted_pybullet
+        from robotic_manipulator_rloa.environment import environment as ref_env
+        from robotic_manipulator_rloa.utils import collision_detector as ref_cd
+        scs, records = g9_scenarios.scenarios(), []
+        for sc in scs:
+            pb, pbd = scripted_pybullet.make_modules(sc)
+            ref_env.p = ref_cd.p = pb
+            ref_env.pybullet_data = pbd
+            records.append(scripted_pybullet.drive(ref_env.Environment, ref_env.EnvironmentConfiguration, sc, pb))
+        arrays = g9_scenarios.pack(scs, records)
+        path = os.path.join(HERE, "g9_env.npz")
+        with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as zf:
+            for name in sorted(arrays):
+                buf = io.BytesIO()
+                np.lib.format.write_array(buf, np.asarray(arrays[name]), allow_pickle=False)
+                info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+                info.compress_type, info.external_attr = zipfile.ZIP_DEFLATED, 0o644 << 16
+                zf.writestr(info, buf.getvalue(), compresslevel=9)
+        g9_line = (f"g9_env.npz: make_golden.py --only g9, the reference's Environment under tests/scripted_pybullet.py, "
+                   f"numpy {meta['numpy']}, python {sys.version_info.major}.{sys.version_info.minor} (CPU)\n")
+        print("g9", len(scs), "scenarios,", os.path.getsize(path), "bytes")
+
+    versions = os.path.join(HERE, "VERSIONS.txt")
+    kept = [l for l in open(versions).read().splitlines(True)[1:] if g9_line is None or not l.startswith("g9_env.npz")] \
+        if os.path.exists(versions) else []
+    with open(versions, "w") as f:
         f.write(f"generated by make_golden.py with torch {meta['torch']}, numpy {meta['numpy']} (CPU)\n")
+        f.writelines(kept + ([g9_line] if g9_line else []))
 
 
 if __name__ == "__main__":

@@ -201,6 +201,13 @@ def test_index_rules_on_the_arm_with_a_gripper():
 
 
 # ---- 4. reward / terminal rule, limits, protocol ---------------------------------------------------------------------------
+def _oracle_says(env):
+    """(reward, done) by oracle/env_oracle.py — the rule as fixture G9 pins it on the reference — of what the last step exposed"""
+    from oracle import env_oracle
+    return env_oracle.rule(env.last_distance, [env.last_clearance - env.obstacle_radius, env.last_cell_clearance],
+                           [env.last_self_clearance], bool(env.model.self_pairs))
+
+
 def test_reward_and_terminal_rule_at_the_thresholds():
     env = env_of("iiwa_like7")
     q = np.array([0.2, 0.5, -0.3, -1.0, 0.4, 0.7, 0.1])
@@ -211,6 +218,7 @@ def test_reward_and_terminal_rule_at_the_thresholds():
         env.target_pos = ee + dist * d
         s, r, done = env.step(np.zeros(7))
         assert (r == 250 and done == 1) if reached else (done == 0 and abs(r + 1e-9) < 1e-12)
+        assert (r, done) == _oracle_says(env)
     env.target_pos = ee + 0.3 * d
     env.q = q.copy()
     s, r, done = env.step(np.zeros(7))
@@ -227,11 +235,12 @@ def test_reward_and_terminal_rule_at_the_thresholds():
         s, r, done = env.step(np.zeros(7))
         assert abs(env.last_clearance - (env.obstacle_radius + off)) < 1e-12
         assert (r == -1000 and done == 1) if hit else (done == 0 and r < 0)
+        assert (r, done) == _oracle_says(env)
     # reaching wins over contact (environment.py:345-371 tests the target first)
     env.q = q.copy()
     env.target_pos = ee.copy()
     env.obstacle_pos = ee.copy()
-    assert env.step(np.zeros(7))[1:] == (250, 1)
+    assert env.step(np.zeros(7))[1:] == (250, 1) == _oracle_says(env)
     assert segment_point_distance2(np.zeros(3), np.array([1.0, 0, 0]), np.array([2.0, 1.0, 0])) == 2.0     # clamped to the end
 
 

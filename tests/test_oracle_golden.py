@@ -343,3 +343,40 @@ def test_f64_checker_rejects_planted_defects(defect, cases, checks):
         assert reps[1].failed(*checks), (defect, name, reps[1].ratios)
         if defect == "norm":
             assert reps[1].meta["clip"] < 1.0 and reps[1].failed("norm_self")
+
+
+# ---- G9: the environment rule (oracle/env_oracle.py) against the reference's Environment under a scripted simulator -------------
+def test_g9_env_oracle_equals_the_reference_environment_record_for_record():
+    """Every record of tests/golden/g9_env.npz (make_golden.py --only g9: the unmodified reference's get_state, get_reward with and
+    without consider_autocollision, is_terminal_state likewise, get_endeffector_target_collision, step and the four reset forms,
+    with the log of its simulator calls) equals what env_oracle computes from the scripted numbers — exactly: states and distances
+    bit for bit, rewards as values and as int (250, -1000) or float, the call log row for row."""
+    import env_rule_common as E
+    from oracle import env_oracle as R
+    import scripted_pybullet as SP
+    recs = E.g9_records()
+    assert {sc["robot"] for sc, _ in recs} == {"kuka", "xarm6", "arm12"}
+    seen = set()
+    for sc, rec in recs:
+        got = E.oracle_records(sc)
+        assert E.records_differ(got, rec) == [], sc["name"]
+        seen.update(sc["cases"])
+        numbers = rec[1]
+        for k, op in enumerate(sc["ops"]):
+            cols = {SP.OP_PROBE: (0, 2), SP.OP_STEP: (0,)}.get(int(op[0]), ())
+            for c in cols:      # 250 and -1000 are ints, everything else a float, in the reference's own records
+                assert (numbers[k, c + 1] == SP.REWARD_INT) == (numbers[k, c] in (R.REACHED_REWARD, R.CONTACT_REWARD)), sc["name"]
+    assert len(seen) == 20 and {"reached_and_obstacle", "target_at_threshold", "obstacle_at_zero", "nothing_within_range"} <= seen
+    # the precedence, read off the reference's records: reached and in contact in one tick is worth +250 and ends the episode
+    sc, rec = next((s, r) for s, r in recs if "reached_and_obstacle" in s["cases"] and s["robot"] == "kuka")
+    op = 1 + 2 * (sc["cases"].index("reached_and_obstacle") - 1)
+    assert tuple(rec[1][op, :3]) == (250.0, SP.REWARD_INT, 1.0)
+
+
+@pytest.mark.parametrize("defect", __import__("oracle.env_oracle", fromlist=["DEFECTS"]).DEFECTS)
+def test_g9_rejects_every_mutant_of_the_rule(defect):
+    """Each way of getting the rule wrong (env_oracle.DEFECTS) contradicts at least one G9 record: the scenarios are enough to
+    tell the reference's rule from its ten nearest mistakes."""
+    import env_rule_common as E
+    caught = [sc["name"] for sc, rec in E.g9_records() if E.records_differ(E.oracle_records(sc, defect=defect), rec)]
+    assert caught, defect
