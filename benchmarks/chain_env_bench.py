@@ -724,6 +724,8 @@ def demo(a):
     plan = demonstration_plan(q_start, via, q_goal, 1.0, T)
     writer = DemonstrationWriter(model, 0.06, chunk=N * T)
     writer.load(plan, targets, obstacles, slice(0, N))
+    if a.ticks:
+        return _demo_ticks(a, writer, plan, targets, obstacles, N, T, launches, urdf, model)
     if a.legs:
         return _demo_legs(a, writer, plan, targets, obstacles, N, T, launches, urdf, model)
     fused = []
@@ -820,6 +822,73 @@ def _demo_legs(a, writer, plan, targets, obstacles, N, T, launches, urdf, model)
                       "us_per_demo_rows_launch": {"median": round(med["two_legs"], 1), "min": round(float(np.min(times["two_legs"])), 1)},
                       "us_per_demo_rows_legs_launch": {"median": round(med["legs"], 1), "min": round(float(np.min(times["legs"])), 1)},
                       "legs_over_two_legs": round(med["legs"] / med["two_legs"], 3), "mean_valid_rows": round(float(rec[:, 0].mean()), 1),
+                      "valid_rows_and_records_bit_equal": bool(same), "kernel_registers": regs}))
+
+
+def _demo_ticks(a, writer, plan, targets, obstacles, N, T, launches, urdf, model):
+    """--ticks: naf_chain_demo_rows_ticks beside naf_chain_demo_rows_legs, alternating in one process, on the same actions — the
+    two-leg plans split into K legs (--legs K, default 5) for the legs launch, and demo_actions of that plan as the tick table —
+    so that both write the same rows; and the whole writer call of either plan, upload and download included"""
+    import time
+    import numpy as np
+    import torch
+    from robotic_manipulator_rloa_amd import _lib
+    from robotic_manipulator_rloa_amd.environment.tick_demo import tick_plan_of
+    K = a.legs or 5
+    ticks, acts = np.zeros((N, K), np.int32), np.zeros((N, K) + plan.leg_actions.shape[2:], np.float32)
+    for n in range(N):
+        col = 0
+        for leg, parts in ((0, max(1, K // 2)), (1, K - max(1, K // 2))):
+            total = int(plan.n_ticks[n, leg])
+            parts = min(parts, total)
+            for k in range(parts):
+                ticks[n, col], acts[n, col] = total * (k + 1) // parts - total * k // parts, plan.leg_actions[n, leg]
+                col += 1
+    legs_plan = plan._replace(n_ticks=ticks, leg_actions=acts)
+    tick_plan = tick_plan_of(legs_plan, T)
+    legs_rows, legs_records = writer.rows, writer.records
+    tick_rows, tick_records = torch.zeros_like(legs_rows), torch.zeros_like(legs_records)
+    writer.load_legs(legs_plan, targets, obstacles, slice(0, N))
+    writer.load_ticks(tick_plan, targets, obstacles, slice(0, N))
+
+    def launch_ticks():
+        writer.rows, writer.records = tick_rows, tick_records
+        writer.launch_ticks(N, T)
+        writer.rows, writer.records = legs_rows, legs_records
+
+    times = {"legs": [], "ticks": []}
+    for i in range(launches + 2):                              # alternating, so that both see the same clocks
+        for name, launch in (("legs", lambda: writer.launch_legs(N, K, T)), ("ticks", launch_ticks)):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            launch()
+            t1.record()
+            t1.synchronize()
+            if i >= 2:
+                times[name].append(1e3 * t0.elapsed_time(t1))
+    rec = legs_records[:N].cpu().numpy()
+    live = (torch.arange(T, device=legs_rows.device)[None, :] < legs_records[:N, 0].long()[:, None]).reshape(-1)
+    same = torch.equal(legs_rows[:N * T][live], tick_rows[:N * T][live]) and torch.equal(legs_records[:N], tick_records[:N])
+    calls = {"legs": [], "ticks": []}
+    for i in range(5):
+        for name, p in (("legs", legs_plan), ("ticks", tick_plan)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            writer.write(p, targets, obstacles)
+            torch.cuda.synchronize()
+            if i >= 1:
+                calls[name].append(1e3 * (time.perf_counter() - t0))
+    usage = json.load(open(_lib.USAGE_PATH)) if os.path.exists(_lib.USAGE_PATH) else {}
+    regs = {name: {q: v.get(q) for q in ("vgprs", "sgprs", "scratch_bytes_per_lane", "lds_bytes", "occupancy")}
+            for name, v in usage.items() if "chain_demo_ticks" in name or "chain_demo_legs" in name}
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    print(json.dumps({"arm": os.path.basename(urdf), "demonstrations": N, "ticks": T, "legs": K, "self_pairs": len(model.self_pairs),
+                      "workcell_pairs": len(model.cell_pairs), "boxes": bool(a.boxes),
+                      "us_per_demo_rows_legs_launch": {"median": round(med["legs"], 1), "min": round(float(np.min(times["legs"])), 1)},
+                      "us_per_demo_rows_ticks_launch": {"median": round(med["ticks"], 1), "min": round(float(np.min(times["ticks"])), 1)},
+                      "ticks_over_legs": round(med["ticks"] / med["legs"], 3), "mean_valid_rows": round(float(rec[:, 0].mean()), 1),
+                      "table_upload_mb": round(N * T * model.A * 4 / 1e6, 1),
+                      "ms_per_writer_call": {k: round(float(np.median(v)), 2) for k, v in calls.items()},
                       "valid_rows_and_records_bit_equal": bool(same), "kernel_registers": regs}))
 
 
@@ -1132,6 +1201,8 @@ def main():
                     help="path, with --roadmap: answer the README's paths again with a shortcut round over W nodes, and demonstrate them")
     ap.add_argument("--legs", type=int, default=0, metavar="K",
                     help="demo: time naf_chain_demo_rows_legs, the same plans split into K legs, beside naf_chain_demo_rows")
+    ap.add_argument("--ticks", action="store_true",
+                    help="demo: time naf_chain_demo_rows_ticks beside naf_chain_demo_rows_legs on the same actions, and the whole writer call")
     ap.add_argument("--orientation", choices=["full", "axis"], default=None,
                     help="ik: also solve the section's queries with an orientation goal and time naf_chain_ik_solve_pose beside naf_chain_ik_solve")
     ap.add_argument("--avoid-contact", action="store_true",

@@ -1256,6 +1256,25 @@ int naf_chain_demo_rows_legs(naf_chain_env_t* h, const float* q_start_dev, const
                              float obstacle_radius, int N, int T_cap, float* rows_out, int row_floats, float* records_out,
                              float* poses_out, void* stream);
 
+/* Demonstrations under per-tick actions (an addition within ABI 40): naf_chain_demo_rows with the two legs replaced by a table of
+ * one action per tick — a time-parameterised trajectory driven at its own ticks. environment/tick_demo.py (trajectory_tick_plan)
+ * fills the table; environment/kinematic.py (demonstration_rows_host) is the float64 statement of the rows.
+ *   tick_actions_dev : [N][T_cap][A] (DEVICE), n_ticks_dev : [N] (DEVICE), the planned ticks of each demonstration, >= 1; a count
+ *                 may exceed T_cap (the caller validates the counts before the upload; the kernel clamps a wrong upload into the
+ *                 arrays). T_n = min(n_ticks_dev[n], T_cap) rows; tick k < T_n applies tick_actions_dev[n][k]. Entries at k >= T_n
+ *                 are never read. records_out[n][6] = n_ticks_dev[n]; end code 0 where T_cap cut it (T_n < n_ticks_dev[n]), 5
+ *                 where it ran to its last planned tick short of the target.
+ *   Everything else — the poses, rows_out, records_out, poses_out — is as documented for naf_chain_demo_rows; fed the actions a
+ *   two-leg or K-leg plan applies tick by tick and the sum of its counts, rows, records and poses are bit for bit that entry's.
+ * One workgroup per demonstration as there; before each pass wave 0 stages the pass's lanes x A actions in LDS behind the base pose
+ * (and keeps the one action before them). No atomics.
+ * NAF_ERR_ARG, and no launch, for naf_chain_demo_rows' refusals. NAF_CHAIN_ERR_LDS, and no launch, for an arm with pairs whose rows
+ * and table together exceed the 160 KiB of a workgroup. */
+int naf_chain_demo_rows_ticks(naf_chain_env_t* h, const float* q_start_dev, const float* tick_actions_dev /* [N][T_cap][A] */,
+                              const int32_t* n_ticks_dev /* [N] */, const float* targets_dev, const float* obstacles_dev,
+                              float obstacle_radius, int N, int T_cap, float* rows_out, int row_floats, float* records_out,
+                              float* poses_out, void* stream);
+
 /* ---- one-shot gradient all-reduce over peer-mapped memory (no reference counterpart) ----------
  * The data-parallel exchange that follows loss.backward() (naf_algorithm.py:207-210 on every rank): sum of the flat
  * gradient over the W <= 8 GPUs of one node, each rank pushing its gradient into a receive slot on every peer over

@@ -297,6 +297,7 @@ _PROTOS = {
     "naf_chain_path_certify": [_vp, _vp, _vp, _vp, _vp, _f, _vp, _f, _i, _i, _i, _f, _vp, _vp, _vp],
     "naf_chain_demo_rows": [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _i, _vp, _vp, _vp],
     "naf_chain_demo_rows_legs": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _i, _i, _vp, _i, _vp, _vp, _vp],
+    "naf_chain_demo_rows_ticks": [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _i, _vp, _vp, _vp],
     "naf_chain_edge_check": [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _f, _vp, _vp, _vp],
     "naf_chain_edge_certify": [_vp, _vp, _vp, _vp, _f, _vp, _f, _i, _i, _i, _i, _f, _vp, _vp, _vp],
     "naf_chain_traj_check": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _i, _f, _vp, _vp, _vp],

@@ -24,7 +24,7 @@ import torch
 from . import _lib
 from ._lib import check, ptr, stream_ptr
 from .chain_clear import ClearLaunch
-from .chain_legs import LegsLaunch
+from .chain_ticks import TicksLaunch
 from .environment.kinematic import (DEMO_CHUNK, DEMO_FLOATS, DEMO_MAX_TICKS, EDGE_FLOATS, PATH_CERT_FLOATS, PATH_CHUNK, PATH_FLOATS,
                                     GoalPoses, JointPaths, certificate_guard, concatenate_goal_poses, demo_row_layout,
                                     gather_demonstrations, gather_goal_poses, ik_seeds, note_pushed, orientation_goal, plan_paths,
@@ -341,14 +341,16 @@ def demonstration_chunks(rows_of, budget: int) -> List[Tuple[int, int, int]]:
     return out
 
 
-class DemonstrationWriter(LegsLaunch, _ChainTool):
+class DemonstrationWriter(TicksLaunch, _ChainTool):
     """Planned joint paths as replay rows on a chain model (csrc/chain_env.hip, "demonstrations"): per chunk of queries ONE
     naf_chain_demo_rows launch that writes every row of every demonstration, then torch plumbing — the mask `t < valid[n] and
     kept[n]` and a boolean index — to a contiguous device tensor of the kept rows in query order, then tick order. Owns the handle
     and staging buffers for `chunk` rows; needs no agent. A demonstration's rows do not depend on where in a launch it lies.
     A plan of two legs of at least one tick each takes that launch; any other plan of K <= 63 legs (demonstration_plan_legs: a
     polyline, 0 ticks for the padding behind a query's last leg) takes naf_chain_demo_rows_legs (chain_legs.LegsLaunch), whose staging
-    [chunk][K][A] / [chunk][K] is allocated on the first such call. Chunks, keep / drop and the gather are the same for both."""
+    [chunk][K][A] / [chunk][K] is allocated on the first such call; a tick_demo.TickPlan — one action per tick, a trajectory driven
+    at its own ticks — takes naf_chain_demo_rows_ticks (chain_ticks.TicksLaunch), whose staging [chunk rows][A] / [chunk] is
+    allocated on the first such call too. Chunks, keep / drop and the gather are the same for all three."""
     CHUNK, CHUNK_MIN, CHUNK_REFUSAL = DEMO_CHUNK, 1, "DemonstrationWriter: a chunk holds at least one row"
 
     def __init__(self, chain, obstacle_radius: float = 0.06, chunk: Optional[int] = None, device=None):
@@ -383,7 +385,7 @@ class DemonstrationWriter(LegsLaunch, _ChainTool):
         is a device tensor [rows_total][row_floats]. has_path[N] (default all): queries without one are launched with whatever
         plan holds for them and reported 'none'."""
         N = len(plan.q_start)
-        load, launch = self.entry_for(plan)                   # the two-leg entry or, for any other plan of K legs, the legs entry
+        load, launch = self.entry_for(plan)                   # the two-leg entry, the legs entry or, for a TickPlan, the tick entry
         T_of = np.asarray(plan.rows, np.int64)
         if N and (T_of.min() < 1 or T_of.max() > DEMO_MAX_TICKS):
             raise ValueError(f"DemonstrationWriter: a demonstration holds 1 .. {DEMO_MAX_TICKS} rows")

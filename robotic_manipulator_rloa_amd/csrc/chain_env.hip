@@ -77,6 +77,7 @@ struct naf_chain_env {
 #define CH_SCENE_WAVES (CH_MAX_WAVES < 8 ? CH_MAX_WAVES : 8)
 #define CH_PAIRS_PER_WAVE 16                 // waves = ceil(P / this), at most CH_MAX_WAVES
 #define CH_MAX_DYN_LDS (144 * 1024)          // of the CU's 160 KiB; the SC kernels have no static LDS beside it
+#define CH_WG_LDS (160 * 1024)               // all a gfx950 workgroup may take: the cap of an entry that adds tables behind the rows
 
 struct ChainScene {
     float v[NAF_CHAIN_SCENE_FLOATS];    // target | obstacle | jitter | obstacle radius
@@ -2623,6 +2624,177 @@ extern "C" int naf_chain_demo_rows_legs(naf_chain_env_t* h, const float* q_start
             CH_MAX_DYN_LDS + 1024 + NAF_CHAIN_DEMO_MAX_LEGS * (int)sizeof(int), (unsigned)N, w, stream, h->model_dev, q_start_dev,
             leg_actions_dev, n_ticks_dev, K, targets_dev, obstacles_dev, obstacle_radius, T_cap, h->A, h->n_seg, w.n_pairs, w.lanes,
             row_floats, rows_out, records_out, poses_out, cell...);
+    });
+}
+
+// ---- demonstrations under one action per tick (include/naf_hip.h, "Demonstrations under per-tick actions") ------------------------
+// chain_demo_legs_kernel with the schedule replaced by a table: tick k of demonstration n applies tick_actions[n][k], an action of
+// its own. A THIRD kernel beside the two, not a template argument of one body: the two existing symbols keep their instructions
+// (DESIGN §28). The base-pose recurrence is theirs. The action of tick k comes from a per-pass table in LDS behind the base —
+// table[lanes][A], the actions of ticks b .. b + lanes - 1 — staged by wave 0 before the pass with coalesced loads, bounded by
+// T_n x A so that nothing behind a demonstration's own ticks is read; in the accessor's tick loop every lane reads the same (k, m)
+// word, an LDS broadcast. Row t - 1's action is table row lane - 1; for lane 0 of a pass it is the last row of the PREVIOUS pass's
+// table, kept as row -1 (A floats in front of the table) before the table is staged again. Only wave 0 touches the table, in
+// program order, behind demo_wave_order as the base is.
+template <bool SC, class... Cell>
+__global__ void __launch_bounds__(SC ? 64 * CH_MAX_WAVES : 64)
+chain_demo_ticks_kernel(const float* __restrict__ model, const float* __restrict__ q_start, const float* __restrict__ tick_actions,
+                        const int* __restrict__ n_ticks, const float* __restrict__ targets, const float* __restrict__ obstacles,
+                        float orad, int T_cap, int A, int n_seg, int n_pairs, int lanes, int row_floats, float* __restrict__ rows_out,
+                        float* __restrict__ records_out, float* __restrict__ poses_out, const Cell... cell) {
+    constexpr bool CELL = (std::is_same_v<Cell, ChainCell> || ... || false);
+    constexpr bool BOX = (std::is_same_v<Cell, ChainBox> || ... || false);
+    extern __shared__ __attribute__((aligned(16))) float ch_lds[];
+    const int64_t n = blockIdx.x;
+    const int S = 2 * A + 9;
+    const int off_s2 = naf_row_off_s2(S, A), off_d = naf_row_off_done(S, A);
+    // (the host validated the count; the clamp only keeps a wrong upload inside the arrays)
+    const int planned = min(max(n_ticks[n], 1), 1 << 20);
+    const int T = min(planned, T_cap);                   // rows of this demonstration; poses 0 .. T
+    const float ox = obstacles[n * 3], oy = obstacles[n * 3 + 1], oz = obstacles[n * 3 + 2];
+    const float tx = targets[n * 3], ty = targets[n * 3 + 1], tz = targets[n * 3 + 2];
+    const int lane = threadIdx.x & 63;
+    const bool active = lane < lanes;
+    const bool wave0 = threadIdx.x < 64;
+    float* base = ch_lds + (SC ? ch_lds_bytes(n_seg, lanes, blockDim.x >> 6) / sizeof(float) : 0);
+    float* table = base + ch_demo_base_floats(A) + A;      // row -1, the A floats in front of it, is the carry
+    float* rows = rows_out + n * T_cap * row_floats;
+    if (wave0) {
+        for (int m = lane; m < A; m += 64) {
+            const float* j = model + CH_HDR + m * CH_JNT;
+            float q = q_start[n * A + m];
+            if (j[16] != 0.f) {      // p_0: the start pose clamped into the limits, as naf_chain_env_reset_given clamps it
+                if (q > j[18]) q = j[18];
+                if (q < j[17]) q = j[17];
+            }
+            base[m] = q;
+            base[A + 6 + m] = 0.f;
+        }
+        if (lane < 3) {
+            base[A + lane] = targets[n * 3 + lane];
+            base[A + 3 + lane] = obstacles[n * 3 + lane];
+        }
+        demo_wave_order();
+    }
+    float min_clear = INFINITY, min_self = INFINITY, min_cell = INFINITY, final_dist = -1.f;
+    int first_key = INT_MAX;      // 8 x (row of the first done) + its end code
+    bool stopped = false;         // (uniform in wave 0) a pass before this one held the first done
+    for (int b = 0; b <= T; b += lanes) {      // (uniform: every thread takes every pass)
+        const int t = b + lane;
+        if (wave0) {      // the pass's actions: the last one of the pass before into the carry, then ticks b .. b + lanes - 1 below T
+            if (b > 0) {
+                for (int m = lane; m < A; m += 64) table[m - A] = table[(lanes - 1) * A + m];
+                demo_wave_order();
+            }
+            const float* pass = tick_actions + (n * T_cap + b) * A;
+            for (int i = lane; i < min(lanes, T - b) * A; i += 64) table[i] = pass[i];
+            demo_wave_order();
+        }
+        const bool walks = active && wave0 && t <= T;
+        float* prev = rows + (int64_t)(t - 1) * row_floats;      // row t - 1: used only where t >= 1
+        float* o = t < T ? prev + row_floats : prev + off_s2;    // obs(p_t): row t's state, or the last row's next_state
+        float ee[3];
+        bool hit = false;
+        WalkAux aux = {SC ? ch_lds + lane : nullptr, lanes, INFINITY, INFINITY};
+        if (walks) {
+            hit = chain_walk_at<SC, false, false, true, CELL, BOX>(
+                model, A, n_seg,
+                [=](int m) {
+                    const float* j = model + CH_HDR + m * CH_JNT;
+                    float q = base[m], vel = base[A + 6 + m];
+                    for (int k = 0; k < lane; ++k) demo_tick(j, table[k * A + m], q, vel);      // ticks b .. t - 1
+                    const int slot = (int)j[21];
+                    if (slot >= 0) o[A + slot] = vel;      // what step t - 1 reported (0 at t = 0, 0 where a limit stopped the joint)
+                    if (poses_out) poses_out[((n * (T_cap + 1)) + t) * A + m] = q;
+                    return q;
+                },
+                ox, oy, oz, orad, base, o, ee, aux);
+        }
+        float self_clear = INFINITY;
+        if constexpr (SC) self_clear = self_clearance_phase(model, A, n_seg, n_pairs, ch_lds, lanes, lane, active && t <= T);
+        if (wave0) {
+            const bool outcome = walks && t >= 1;      // the walk of p_t is the outcome of row t - 1
+            float dist = 0.f, clear = INFINITY, cellc = INFINITY;
+            bool done = false;
+            int code = 0;
+            if (outcome) {
+                const float dx = ee[0] - tx, dy = ee[1] - ty, dz = ee[2] - tz;
+                dist = sqrtf(dx * dx + dy * dy + dz * dz);
+                clear = aux.clear - orad;
+                if constexpr (CELL) cellc = aux.cell;
+                const bool reached = dist < CH_REACHED, self_hit = self_clear < 0.f, cell_hit = CELL && aux.cell < 0.f;
+                const bool any = hit || self_hit || cell_hit;
+                done = reached || any;
+                code = reached ? 1 : (hit ? 2 : (self_hit ? 3 : (cell_hit ? 4 : 0)));
+                const float* act = table + (lane - 1) * A;      // the action of tick t - 1: for lane 0 the carry
+                for (int m = 0; m < A; ++m) prev[S + m] = act[m];
+                prev[S + A] = reached ? 250.f : (any ? -1000.f : -(dist - CH_REACHED));
+                for (int k = S + A + 1; k < off_s2; ++k) prev[k] = 0.f;
+                if (t < T)
+                    for (int k = 0; k < S; ++k) prev[off_s2 + k] = o[k];
+                prev[off_d] = done ? 1.f : 0.f;
+                for (int k = off_d + 1; k < row_floats; ++k) prev[k] = 0.f;      // the tag float included: an untagged row
+            }
+            const unsigned long long mask = __ballot(outcome && done);
+            const int first_lane = mask ? __ffsll(mask) - 1 : 64;
+            if (!stopped && outcome && lane <= first_lane) {      // rows up to the first done are the demonstration's
+                min_clear = fminf(min_clear, clear);
+                min_self = fminf(min_self, self_clear);
+                min_cell = fminf(min_cell, cellc);
+                if (lane == first_lane) { first_key = (t - 1) * 8 + code; final_dist = dist; }
+                else if (t == T && !mask) final_dist = dist;
+            }
+            stopped = stopped || mask != 0ull;
+            if (b + lanes <= T) {      // another pass: the base moves on by `lanes` ticks, a joint per lane
+                demo_wave_order();
+                for (int m = lane; m < A; m += 64) {
+                    const float* j = model + CH_HDR + m * CH_JNT;
+                    float q = base[m], vel = base[A + 6 + m];
+                    for (int k = 0; k < lanes; ++k) demo_tick(j, table[k * A + m], q, vel);      // ticks b .. b + lanes - 1, all below T
+                    base[m] = q;
+                    base[A + 6 + m] = vel;
+                }
+                demo_wave_order();
+            }
+        }
+    }
+    if (!wave0) return;      // (behind the last barrier; wave 0 is whole: the lanes that walked nothing hold the identities)
+    for (int off = 32; off > 0; off >>= 1) {
+        min_clear = fminf(min_clear, __shfl_xor(min_clear, off));
+        min_self = fminf(min_self, __shfl_xor(min_self, off));
+        min_cell = fminf(min_cell, __shfl_xor(min_cell, off));
+        first_key = min(first_key, __shfl_xor(first_key, off));
+        final_dist = fmaxf(final_dist, __shfl_xor(final_dist, off));
+    }
+    if (threadIdx.x != 0) return;
+    float* r = records_out + n * NAF_CHAIN_DEMO_FLOATS;
+    r[0] = first_key == INT_MAX ? (float)T : (float)(first_key / 8 + 1);
+    r[1] = first_key == INT_MAX ? (T < min(max(n_ticks[n], 1), 1 << 20) ? 0.f : 5.f) : (float)(first_key % 8);
+    r[2] = final_dist;
+    r[3] = min_clear;
+    r[4] = min_self;
+    r[5] = min_cell;
+    r[6] = (float)min(max(n_ticks[n], 1), 1 << 20);
+    r[7] = 0.f;
+}
+
+extern "C" int naf_chain_demo_rows_ticks(naf_chain_env_t* h, const float* q_start_dev, const float* tick_actions_dev,
+                                         const int32_t* n_ticks_dev, const float* targets_dev, const float* obstacles_dev,
+                                         float obstacle_radius, int N, int T_cap, float* rows_out, int row_floats, float* records_out,
+                                         float* poses_out, void* stream) {
+    if (!h || !q_start_dev || !tick_actions_dev || !n_ticks_dev || !targets_dev || !obstacles_dev || !rows_out || !records_out)
+        return NAF_ERR_ARG;
+    if (N < 1 || N > 1 << 30 || T_cap < 1 || T_cap > NAF_CHAIN_DEMO_MAX_TICKS) return NAF_ERR_ARG;
+    if (row_floats <= 0 || row_floats != naf_replay_row_floats(2 * h->A + 9, h->A)) return NAF_ERR_ARG;
+    if (!std::isfinite(obstacle_radius) || obstacle_radius < 0.f) return NAF_ERR_ARG;
+    return ch_with_pack(h, [&](auto sc, auto... cell) -> int {
+        ChShape w = ch_shape<sc()>(h, h->waves);
+        // the probe's rows, the base behind them, one action (the carry) and the pass's lanes x A actions behind the base
+        w.lds += ((size_t)ch_demo_base_floats(h->A) + (size_t)(w.lanes + 1) * h->A) * sizeof(float);
+        if (w.lds > CH_WG_LDS) return NAF_CHAIN_ERR_LDS;      // (rows that only just fit 144 KiB and a wide arm's table)
+        return ch_launch_raising<chain_demo_ticks_kernel<sc(), decltype(cell)...>>(
+            CH_WG_LDS, (unsigned)N, w, stream, h->model_dev, q_start_dev, tick_actions_dev, n_ticks_dev, targets_dev, obstacles_dev,
+            obstacle_radius, T_cap, h->A, h->n_seg, w.n_pairs, w.lanes, row_floats, rows_out, records_out, poses_out, cell...);
     });
 }
 

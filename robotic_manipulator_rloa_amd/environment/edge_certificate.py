@@ -92,7 +92,8 @@ def polyline_nodes(paths) -> Tuple[np.ndarray, np.ndarray]:
     has = np.asarray(paths.candidate) >= 0
     roadmap = np.asarray(paths.n_nodes) >= 2 if paths.n_nodes is not None else np.zeros(N, bool)
     count = np.where(has, 3, 0).astype(np.int64)
-    count[roadmap] = np.asarray(paths.n_nodes)[roadmap]
+    if roadmap.any():                                         # (paths planned without a roadmap hold no n_nodes at all)
+        count[roadmap] = np.asarray(paths.n_nodes)[roadmap]
     nodes = np.full((N, max(int(count.max()) if N else 2, 2), A), np.nan)
     if has.any():
         nodes[has, 0], nodes[has, 1] = start[has], np.asarray(paths.via, np.float64)[has]

@@ -1105,6 +1105,9 @@ class Demonstrations(NamedTuple):
                                       # through the twin
     rows_total: int
     action_size: int = 0              # A of the arm the rows belong to
+    tracking_error: Optional[np.ndarray] = None      # [N]: the last three from demonstrate_trajectories only: max |p_i - Q_i| of the host's
+    saturated_ticks: Optional[np.ndarray] = None     # float32 recurrence against the law | ticks with a component clamped to [-1, 1] |
+    peak_action: Optional[np.ndarray] = None         # the largest |a_i|
 
 
 def demonstration_speed_ok(speed) -> bool:
@@ -1166,16 +1169,17 @@ def demonstration_rows_host(twin: KinematicEnvironment, plan: DemonstrationPlan,
                             keep_contact: bool = False, has_path=None, full: bool = False):
     """naf_chain_demo_rows through the twin alone: KinematicEnvironment.trace — the float64 episode under given actions — from
     the plan's start poses under its actions, cut at T_n = min(n1 + n2, frames); the rows are get_state() before and after every
-    step, the velocity slots what the step before reported. Returns Demonstrations with `rows` a float32 numpy array; full=True
+    step, the velocity slots what the step before reported. `plan` is a DemonstrationPlan, whose actions are demo_actions', or a
+    tick_demo.TickPlan with a table of its own (naf_chain_demo_rows_ticks' twin): one body, and record [6] the planned ticks of
+    either. Returns Demonstrations with `rows` a float32 numpy array; full=True
     returns (demonstrations, records[N][8] float64, rows[N][T][row floats] float64 with NaN where there is no row, poses[N][T + 1][A])."""
     N, A = plan.q_start.shape
     S, off_s2, off_d, rf = demo_row_layout(A)
     has = np.ones(N, bool) if has_path is None else np.asarray(has_path, bool)
     targets = np.broadcast_to(np.asarray(targets, np.float32).astype(np.float64), (N, 3))
     obstacles = np.broadcast_to(np.asarray(obstacles, np.float32).astype(np.float64), (N, 3))
-    Tn = np.minimum(plan.n_ticks.astype(np.int64).sum(axis=1), int(frames))
-    T = int(Tn.max()) if N else 1
-    actions = demo_actions(plan, T)
+    from .tick_demo import plan_source
+    planned, Tn, T, actions = plan_source(plan, int(frames))
     tr = twin.trace(plan.q_start.astype(np.float64), actions, targets, obstacles, T)
     valid = np.minimum(tr.frames, Tn)
     done = (tr.code != 0) & (tr.frames <= Tn)
@@ -1184,11 +1188,11 @@ def demonstration_rows_host(twin: KinematicEnvironment, plan: DemonstrationPlan,
     last = np.take_along_axis(m, (valid - 1)[:, None, None], axis=1)[:, 0]
     records = np.zeros((N, DEMO_FLOATS))
     records[:, 0] = valid
-    records[:, 1] = np.where(done, tr.code, np.where(Tn < plan.n_ticks.astype(np.int64).sum(axis=1), 0, 5))
+    records[:, 1] = np.where(done, tr.code, np.where(Tn < planned, 0, 5))
     records[:, 2] = last[:, 0] + TARGET_THRESHOLD
     for k, col in ((3, 1), (4, 2), (5, 3)):
         records[:, k] = np.min(np.where(live, m[:, :, col], np.inf), axis=1)
-    records[:, 6] = plan.n_ticks.astype(np.int64).sum(axis=1)
+    records[:, 6] = planned
     # the rows: state t = obs(p_t) with step t - 1's reported velocities, next_state t = state t + 1
     lo, hi = twin.joint_limits()
     path = tr.joint_positions                                                              # [N, T + 1, A], held behind the end

@@ -30,6 +30,7 @@ from typing import List, Optional, Union
 import numpy as np
 
 from .arm_planner import ArmPlanner, _positive_int
+from .arm_trajectory import TrajectoryMethods
 from .environment.kinematic import (SCENE_CONDITIONS, Demonstrations, KinematicEnvironment, build_kinematic, cell_box_gaps,
                                     choose_scene)
 from .environment.synthetic import SyntheticEnvironment
@@ -100,7 +101,7 @@ SCENE_CHECK_SEED = 20241017
 _DEVICE_ENVS = (SyntheticEnvironment, KinematicEnvironment)
 
 
-class ManipulatorFramework:
+class ManipulatorFramework(TrajectoryMethods):
 
     def __init__(self) -> None:
         self.env = None
@@ -427,34 +428,6 @@ class ManipulatorFramework:
         from .arm_certify import certify_joint_paths
         planner = self._kinematic_planner('certify_joint_paths', 'chain model to certify on')
         return certify_joint_paths(planner, paths, obstacles, clearance_margin, resolution, on_device)
-
-    def plan_trajectories(self, paths, obstacles=None, max_velocity=1.0, max_acceleration=None, dt: float = 1.0 / 240.0, certify: bool = False,
-                          clearance_margin: float = 0.0, positions: bool = True, on_device: Optional[bool] = None):
-        """Time-parameterised trajectories along planned joint paths, collision-checked at the controller's ticks (kinematic
-        environment only; needs no agent). Every query of `paths` that has a path is driven as linear segments with parabolic
-        blends under the joints' velocity and acceleration limits (environment/trajectory.py states the schedule and the law): the
-        arm starts and ends at rest and does not stop at a corner, so it passes a corner NEAR it, not through it — a verdict or a
-        certificate of the polyline does not carry over. The trajectory is therefore sampled every `dt`, walked and tested again.
-          paths            : JointPaths of plan_joint_paths(), of any kind, or LinearMoves.as_joint_paths(); it is not changed
-          obstacles        : as reach_targets() takes them — the scenes the paths were planned in
-          max_velocity     : a scalar or [A], per joint (rad/s, m/s); the default 1.0 is the environment's own action bound
-          max_acceleration : a scalar or [A]; it has to be given (None is refused) — the model has no acceleration limits
-          dt               : the tick; the default is the environment's. With both defaults the sampled poses are a legal action
-                             sequence under the step rule. A trajectory holds at most 8192 ticks; a longer one is refused by name.
-          certify          : also decide the poses BETWEEN the ticks: every test at every tick has to keep clearance_margin plus
-                             how far the tested capsule can travel over half a tick at the joints' peak speeds
-          positions        : return the pose at every tick
-          on_device        : None: the device when there is one (one naf_chain_traj_check / naf_chain_traj_certify launch per
-                             chunk); False: the float64 host twin under the same rule (slow)
-        Returns environment.trajectory.Trajectories, arrays over the queries: outcome ('free' | 'certified' | 'sampled': free at
-        the ticks, not certified | 'blocked' | 'none': no path), duration, rest_to_rest_duration (with a stop at every corner: the
-        blended trajectory is usually, not always, the shorter), n_samples, first_blocked, first_blocked_time, the three minima,
-        corner_deviation, peak_velocity, peak_acceleration, slack and certified (with certify), leg_times, blend_times, positions
-        [N][Smax][A]; velocities() and at(times) evaluate the float64 law. A 'blocked' trajectory is not re-timed: a lower
-        max_velocity shrinks the corner deviation quadratically."""
-        from .arm_trajectory import plan_trajectories
-        planner = self._kinematic_planner('plan_trajectories', 'chain model to drive')
-        return plan_trajectories(planner, paths, obstacles, max_velocity, max_acceleration, dt, certify, clearance_margin, positions, on_device)
 
     def plan_linear_moves(self, joint_positions, displacements, obstacles=None, hold: str = 'orientation',
                           tool_axis=(0.0, 0.0, 1.0), waypoints: int = 32, updates: int = 4, tolerance: float = 1e-3,
