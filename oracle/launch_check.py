@@ -10,6 +10,10 @@ tests/test_rowsplit_launches_cpu.py feeds it f32_standin() — a float32 numpy c
 that fills the same dictionary — to show that every bound admits honest float32 arithmetic and rejects the planted DEFECTS. The
 two share this file and tests/rowsplit_cases.py so that they cannot drift apart.
 
+The other two chains — column-tile and unfused — are held the same way by check_tile_launches() and f32_standin_tiles() in the
+second half of this file (their dictionary, their n and c and their defects are stated there; tests/tilechain_cases.py,
+tests/test_tilechain_launches_{cpu,gpu}.py). The rules (1) - (3) below and the constants of (2) serve both.
+
 Everything is in the STORED layout (layout.NetLayout): H is the stored width (a layer of 128 | 320 is stored zero-padded to
 256 | 512), h the reference's; the three heads are one matrix Wh [NHP][HP] whose column H is the bias.
 
@@ -79,7 +83,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import naf_oracle as O
-from .learn_check import NORM_SELF_RTOL, Report
+from .learn_check import BIAS0_REL, NORM_SELF_RTOL, SUM_ABS_RTOL, Report
 
 U = 2.0 ** -24
 BN_MOMENTUM = O.BN_MOMENTUM
@@ -125,6 +129,9 @@ class Dims:
     keep_xhat1: bool
     p_mode: int
     gamma: float = 0.99
+    fuse: frozenset = frozenset()       # the column-tile / unfused chains (check_tile_launches): the plan's tags,
+    n_slabs: int | None = None          # the slab count of the split-K heads (s3)
+    fold_norm: bool = False             # and whether the gradient's producers leave the norm partials
 
     @property
     def T(self):
@@ -134,7 +141,8 @@ class Dims:
     def of(cls, plan, lay, B, p_mode, gamma=0.99):
         """From a chain_plan.ChainPlan and its layout.NetLayout."""
         return cls(lay.S, lay.A, lay.H, lay.H_ref, int(B), plan.Bp, lay.HP, lay.NHP, plan.kp, plan.nb, plan.nb1, plan.hk_rows,
-                   plan.ks_w2, plan.ks_wh, bool(plan.keep_xhat1), int(p_mode), float(gamma))
+                   plan.ks_w2, plan.ks_wh, bool(plan.keep_xhat1), int(p_mode), float(gamma), frozenset(plan.fuse), plan.n_slabs,
+                   bool(plan.fold_norm))
 
 
 def stored_state(main: dict, target: dict, d: Dims) -> dict:
@@ -181,6 +189,39 @@ def slab_sum_f32(slabs):
     return acc
 
 
+def _check_stats(rep, check, smean, sinv, bn1, layer, net, cache, rm, rv):
+    """(2): what one BatchNorm launch saved and left in ITS slots — layer `layer` (0 | 1) of network `net` — against float64."""
+    rep.add(f"{check}.mean", np.abs(smean[layer, net] - cache["mean"]), MEAN_RTOL * np.abs(cache["mean"]) + MEAN_ATOL,
+            f"save_mean layer {layer + 1} net {net}")
+    rep.add(f"{check}.invstd", np.abs(sinv[layer, net] - cache["invstd"]), INVSTD_RTOL * cache["invstd"],
+            f"save_invstd layer {layer + 1} net {net}")
+    rep.add(f"{check}.rm", np.abs(bn1[net, 2 * layer] - rm), RM_RTOL * np.abs(rm) + RM_ATOL, f"bn{layer + 1} running_mean net {net}")
+    rep.add(f"{check}.rv", np.abs(bn1[net, 2 * layer + 1] - rv), RV_RTOL * np.abs(rv) + RV_ATOL, f"bn{layer + 1} running_var net {net}")
+
+
+def _check_head(rep, pfx, d, mu_pre, l_pre, V, vn, vn_tol, ac, rw, q_dev, loss_dev, dH):
+    """(2): the NAF head of one launch — q, the loss and d_heads [Bp][NHP] — against float64 from the heads' pre-activations and the
+    target's V'(s') (float64 arrays); vn_tol: what V' carries of its own rounding. The d_V column is teacher-forced on the
+    launch's own q_out (the header says why)."""
+    A, T, B = d.A, d.T, d.B
+    u, r = _f64(ac), _f64(rw).reshape(-1)
+    Q = O.head_forward(mu_pre, l_pre, V, u, d.p_mode)["Q"]
+    y = r + d.gamma * vn
+    q = _f64(q_dev).reshape(-1)[:B]
+    rep.add(f"{pfx}.q", np.abs(q - Q), Q_RTOL * np.abs(Q) + Q_ATOL, "q_out")
+    loss64 = float(((Q - y) ** 2).mean())
+    rep.add(f"{pfx}.loss", abs(float(loss_dev) - loss64), LOSS_RTOL * abs(loss64), "summed loss partials")
+    dq_dev = dH[:B, A + T]
+    dq_ref = 2.0 * (q - y) / B
+    rep.add(f"{pfx}.dv", np.abs(dq_dev - dq_ref), DV_RTOL * np.abs(dq_ref) + DV_ATOL + (2.0 / B) * d.gamma * vn_tol, "d_heads, V column")
+    d_mu, d_l, _ = O.head_backward(mu_pre, l_pre, u, dq_dev, d.p_mode)
+    atol = DHEAD_ATOL_SCALE * np.abs(dq_dev).max() + DHEAD_ATOL
+    rep.add(f"{pfx}.dmu", np.abs(dH[:B, :A] - d_mu), DHEAD_RTOL * np.abs(d_mu) + atol, "d_heads, mu columns")
+    rep.add(f"{pfx}.dl", np.abs(dH[:B, A:A + T] - d_l), DHEAD_RTOL * np.abs(d_l) + atol, "d_heads, L columns")
+    rep.add(f"{pfx}.pad", 0.0 if (not dH[B:].any() and not dH[:, A + T + 1:].any()) else 1.0, 0.5,
+            "d_heads rows past the batch and pad columns")
+
+
 # ------------------------------------------------------------------------------------------------------------------------
 def check_launches(pre: dict, batch, dev: dict, d: Dims) -> Report:
     """Every launch of one update of the row-split chain against float64 from the values it read. Returns a learn_check.Report:
@@ -201,12 +242,7 @@ def check_launches(pre: dict, batch, dev: dict, d: Dims) -> Report:
         rep.add(check, 0.0 if bool(cond) else 1.0, 0.5, what)
 
     def stats(check, layer, net, cache, rm, rv):
-        rep.add(f"{check}.mean", np.abs(smean[layer, net] - cache["mean"]), MEAN_RTOL * np.abs(cache["mean"]) + MEAN_ATOL,
-                f"save_mean layer {layer + 1} net {net}")
-        rep.add(f"{check}.invstd", np.abs(sinv[layer, net] - cache["invstd"]), INVSTD_RTOL * cache["invstd"],
-                f"save_invstd layer {layer + 1} net {net}")
-        rep.add(f"{check}.rm", np.abs(bn1[net, 2 * layer] - rm), RM_RTOL * np.abs(rm) + RM_ATOL, f"bn{layer + 1} running_mean net {net}")
-        rep.add(f"{check}.rv", np.abs(bn1[net, 2 * layer + 1] - rv), RV_RTOL * np.abs(rv) + RV_ATOL, f"bn{layer + 1} running_var net {net}")
+        _check_stats(rep, check, smean, sinv, bn1, layer, net, cache, rm, rv)
 
     # ---- launch 1: naf_bb_layer1_adam ---------------------------------------------------------------------------------
     c1 = []
@@ -263,21 +299,7 @@ def check_launches(pre: dict, batch, dev: dict, d: Dims) -> Report:
     a2t = np.maximum(y2[1], 0)
     vn = a2t @ Wht[A + T, :H] + Wht[A + T, H]
     vn_tol = (H + 8) * U * (a2t @ np.abs(Wht[A + T, :H]) + abs(Wht[A + T, H]))
-    u, r = _f64(ac), _f64(rw).reshape(-1)
-    Q = O.head_forward(mu_pre, l_pre, V, u, d.p_mode)["Q"]
-    y = r + d.gamma * vn
-    q = _f64(dev["q"]).reshape(-1)[:B]
-    rep.add("l3.q", np.abs(q - Q), Q_RTOL * np.abs(Q) + Q_ATOL, "q_out")
-    loss64 = float(((Q - y) ** 2).mean())
-    rep.add("l3.loss", abs(float(dev["loss"]) - loss64), LOSS_RTOL * abs(loss64), "summed loss partials")
-    dq_dev = dH[:B, A + T]
-    dq_ref = 2.0 * (q - y) / B
-    rep.add("l3.dv", np.abs(dq_dev - dq_ref), DV_RTOL * np.abs(dq_ref) + DV_ATOL + (2.0 / B) * d.gamma * vn_tol, "d_heads, V column")
-    d_mu, d_l, _ = O.head_backward(mu_pre, l_pre, u, dq_dev, d.p_mode)
-    atol = DHEAD_ATOL_SCALE * np.abs(dq_dev).max() + DHEAD_ATOL
-    rep.add("l3.dmu", np.abs(dH[:B, :A] - d_mu), DHEAD_RTOL * np.abs(d_mu) + atol, "d_heads, mu columns")
-    rep.add("l3.dl", np.abs(dH[:B, A:A + T] - d_l), DHEAD_RTOL * np.abs(d_l) + atol, "d_heads, L columns")
-    exact("l3.pad", not dH[B:].any() and not dH[:, A + T + 1:].any(), "d_heads rows past the batch and pad columns")
+    _check_head(rep, "l3", d, mu_pre, l_pre, V, vn, vn_tol, ac, rw, dev["q"], dev["loss"], dH)
     on2 = A2[:B, :H] > 0
     rep.add("l3.dy2", np.abs(dY2[:B] - (dH[:B] @ Whm[:, :H]) * on2), (NHP + 2) * U * (np.abs(dH[:B]) @ np.abs(Whm[:, :H])) * on2, "dY2")
     exact("l3.pad", not dY2[B:].any(), "dY2 rows past the batch")
@@ -525,4 +547,346 @@ def f32_standin(pre: dict, batch, d: Dims, defect: str | None = None) -> dict:
                loss=float((err.astype(np.float64) ** 2).mean()), dH=dH, dY2=dY2, bw2=bw2, bw1=bw1, dw1=dw1, slab_w2=slab_w2,
                slab_wh=slab_wh, grad=grad, sumsq=float(f(sum(float((v.astype(np.float64) ** 2).sum()) for v in grad.values()))),
                step=int(pre["step"]) + 1, flag=int(pre["flag"]) + 1)
+    return out
+
+
+# ========================================================================================================================
+# The column-tile and the unfused chain: Learner._learn_rows_tiles and the non-row-split half of Learner.forward_train
+# (csrc/fused_layers.hip, bn_relu.hip, naf_head.hip, naf_head_wide.hip, the plain three-product form of gemm_bundle.hip, torch
+# GEMMs). The same convention: every launch against float64 from the device values it read. What differs from the row-split chain:
+# G1 / G2 are the bare products (the BatchNorm kernels add the bias themselves), A2 exists for both networks, every backward kernel
+# takes its ReLU mask from the stored activation (`out > 0`), so no mask has to be guessed, and Bp = B.
+#
+#     dev    A1 [2][B][H], G1 [2][B][H] | None (l1: layer 1's product never leaves the launch), G2 [2][B][H], A2 [2][B][HP],
+#            save_mean / save_invstd [layer][net][H], bn, heads_partial [n_slabs][B][NHP] + vnext_partial [n_slabs][B] (s3) | Gh
+#            [2][B][NHP], q [B], loss, dH [B][NHP], dA2 [B][HP] | None (b2), dZ2 [B][H], dA1 [B][H], dZ1 [B][H] | None (l1),
+#            grad {as pre["net"][0]}, sumsq (the summed norm partials), step
+#
+# THE BOUNDS, by the header's rules; n and c per output (U = 2^-24):
+# (1)   G1          n = S        c = 2    torch.bmm (rocBLAS): the product and the store
+#       G2          n = H        c = 2    torch.bmm
+#       heads       n = H + 1    c = 2    the slab-order float32 sum of heads_partial (H products and the bias, n_slabs adds of 8-term
+#                                         slabs: any order of H + 1 terms) against A2_dev[0] Wh_main^T; vnext the same with the target's row
+#       Gh          n = HP       c = 2    torch.bmm over the stored width (the ones column carries the bias)
+#       dA2         n = NHP      c = 2    torch.mm; inside naf_heads_bwd_bn_relu_bwd the same product stays in registers and its bound
+#                                         E_dy = (NHP + 2) U |dH| |Wh| (masked) is carried into everything below
+#       xhat        3 roundings (g + b, - mean, x invstd), each at most U (|g| + |b| + |mean|) invstd: xh_err. Where layer 1's z is
+#                   recomputed from the rows (naf_bn_relu_bwd_wgrad_push): (S + 4) U (|x| |W1|^T + |b1| + |mean|) invstd, as the
+#                   row-split epilogue's
+#       sum dy      n = B        c = 2    + sum E_dy                                   (d_beta; E_S1)
+#       sum dy xhat n = B        c = 4    + sum (E_dy |xhat| + |dy| xh_err)            (d_gamma; E_S2)
+#       dZ          |k1| (E_dy + E_S1 / B + |xhat| E_S2 / B + xh_err |S2| / B) + C_DZ U M_dz, M_dz = |k1| (|dy| + |S1| / B + |xhat| |S2| / B),
+#                   C_DZ = 8 roundings: k1 = gamma invstd, 1 / B, the two products with it, xhat x (.), two subtractions, k1 x (.)
+#       gWh         n = B        c = 2    dH_dev^T A2_dev[0], the ones column (the head biases) included
+#       gW2         n = B        c = 2    dZ2_dev^T A1_dev[0]
+#       dA1         n = H        c = 2    dZ2_dev W2_main
+#       gW1         n = B        c = 2    dZ1_dev^T X where dZ1 is in memory; else scale |dZ1|^T |X| plus the dZ bound above times |X|
+# (2)   activations, saved and running statistics, q, loss, d_heads: the constants above, unchanged — the streamed BatchNorm
+#       (B > 2048) at the same ones as the tiled. The heads' pre-activations and V' are the device's own (the slab-order sum is
+#       the head launch's own order, csrc/naf_head.hip: to the bit), so V' brings no tolerance of its own here.
+#       d_b1, d_b2 (identically 0 in exact arithmetic): max(BIAS0_REL ||grad||, SUM_ABS_RTOL sum|dZ|), learn_check's bound.
+#       The norm: NORM_SELF_RTOL on sum(partials) against ||grad||^2, folded or from naf_grad_norm_partials.
+# (3)   nothing is left to it: every output of these two chains is a dot product, sits behind (2), or is the BatchNorm backward
+#       whose bound is derived above. No constant of these checks is measured.
+C_DZ = 8
+TILE_DEFECTS = ("target_bn2_from_main", "target_w2_from_main", "target_vrow_from_main", "mask_no_beta1", "mask_no_beta2",
+                "k1_no_gamma", "vnext_from_state", "bn2_stats_in_layer1_slots", "target_stats_in_main_slots", "biased_running_var",
+                "momentum_on_old", "gwh_no_bias_column", "slab_twice", "last_phase_dropped")
+# move nothing where the target equals the main network, gamma = 1 and beta = 0. vnext_from_state is NOT among them: state and next_state
+# differ at any state of the networks, and the layer-1 check of the target rejects it at the init state too.
+TILE_ADMITTED_AT_INIT = TILE_DEFECTS[:6]
+
+
+def bn_row_phases(B: int) -> int:
+    """Row phases of the BatchNorm tile a batch takes (csrc/bn_relu.hip, BN_DISPATCH and BN_MAX_B): 64 up to B = 512, 128 beyond —
+    held in registers up to 2048 rows, streamed beyond."""
+    return 64 if B <= 512 else 128
+
+
+def _kink_tau(gamma, beta, cache, zabs):
+    """naf_oracle.relu_kink_tau's scale for one layer in the stored layout"""
+    g = np.abs(gamma)
+    return O.KINK_KAPPA * U * (g * cache["invstd"] * zabs + g * np.abs(cache["xhat"]) + np.abs(beta))
+
+
+def _bn_bwd_ref(dy, E_dy, xh, xh_err, k1, B):
+    """float64 BatchNorm backward of one layer from the launch's own inputs and the first-order bounds of the header:
+    (S1, S2, E_S1, E_S2, dz, tol_dz)"""
+    S1, S2 = dy.sum(0), (dy * xh).sum(0)
+    E1 = (B + 2) * U * np.abs(dy).sum(0) + E_dy.sum(0)
+    E2 = (B + 4) * U * np.abs(dy * xh).sum(0) + (E_dy * np.abs(xh) + np.abs(dy) * xh_err).sum(0)
+    dz = k1 * (dy - S1 / B - xh * (S2 / B))
+    Mdz = np.abs(k1) * (np.abs(dy) + np.abs(S1) / B + np.abs(xh) * (np.abs(S2) / B))
+    tol = np.abs(k1) * (E_dy + E1 / B + np.abs(xh) * (E2 / B) + xh_err * (np.abs(S2) / B)) + C_DZ * U * Mdz
+    return S1, S2, E1, E2, dz, tol
+
+
+def check_tile_launches(pre: dict, batch, dev: dict, d: Dims) -> Report:
+    """Every launch of one update of the column-tile | unfused chain (d.fuse says which launches ran) against float64 from the
+    values it read. Returns a learn_check.Report as check_launches does; .meta["ambiguous"]: ReLU elements of the main network
+    (both layers) within rounding of 0."""
+    rep = Report()
+    S, A, T, H, h, B, HP, NHP = d.S, d.A, d.T, d.H, d.h, d.B, d.HP, d.NHP
+    assert d.Bp == B and "bb" not in d.fuse
+    l1, b2, gb, s3 = ("l1" in d.fuse), ("b2" in d.fuse), ("gb" in d.fuse), ("s3" in d.fuse)
+    st, ac, rw, ns = batch
+    x = [_f64(st), _f64(ns)]
+    P = [{k: _f64(v) for k, v in pre["net"][n].items()} for n in (0, 1)]
+    bn0, bn1 = _f64(pre["bn"]), _f64(dev["bn"])
+    A1, G2, A2, dH, dZ2, dA1 = (_f64(dev[k]) for k in ("A1", "G2", "A2", "dH", "dZ2", "dA1"))
+    smean, sinv = _f64(dev["save_mean"]), _f64(dev["save_invstd"])
+    assert (dev.get("G1") is None) == l1 and (dev.get("dZ1") is None) == l1 and (dev.get("dA2") is None) == b2
+    assert (dev.get("heads_partial") is not None) == s3 and (dev.get("Gh") is None) == s3
+    assert A1.shape == (2, B, H) and G2.shape == (2, B, H) and A2.shape == (2, B, HP) and dH.shape == (B, NHP)
+
+    def exact(check, cond, what):
+        rep.add(check, 0.0 if bool(cond) else 1.0, 0.5, what)
+
+    # ---- layer 1, both nets: naf_linear_bn_relu_fwd_train | torch.bmm + naf_bn_relu_fwd_train(1) ------------------------------------
+    c1, amb = [], 0
+    for net in (0, 1):
+        p = P[net]
+        zabs = np.abs(x[net]) @ np.abs(p["W1"]).T
+        if l1:
+            z = x[net] @ p["W1"].T + p["b1"]
+        else:
+            G1 = _f64(dev["G1"])[net]
+            rep.add("f1.g1", np.abs(G1 - x[net] @ p["W1"].T), (S + 2) * U * zabs, f"G1 net {net}")
+            z, zabs = G1 + p["b1"], np.abs(G1)
+        y, cache, rm, rv = O.bn_train_forward(z, p["g1"], p["be1"], bn0[net, 0], bn0[net, 1])
+        ref = np.maximum(y, 0)
+        rep.add("f1.a1", np.abs(A1[net] - ref), ACT_TOL * ref + ACT_TOL, f"A1 net {net}")
+        _check_stats(rep, "f1", smean, sinv, bn1, 0, net, cache, rm, rv)
+        c1.append(cache)
+        if net == 0:
+            tau = _kink_tau(p["g1"], p["be1"], cache, zabs + np.abs(p["b1"]) + np.abs(cache["mean"]))
+            flips = (A1[0] > 0) != (y > 0)
+            rep.add("f1.mask", np.abs(y[flips]), tau[flips], "A1's mask unlike float64's beyond rounding")
+            amb += int((np.abs(y)[:, :h] <= tau[:, :h]).sum())
+
+    # ---- GEMM 2, both nets: torch.bmm, each from its own W2 and its own A1 -----------------------------------------------------------
+    for net in (0, 1):
+        a, w = A1[net], P[net]["W2"]
+        rep.add("g2.g2", np.abs(G2[net] - a @ w.T), (H + 2) * U * (np.abs(a) @ np.abs(w).T), f"G2 net {net}")
+
+    # ---- layer 2, both nets: naf_bn_relu_fwd_heads_partial | naf_bn_relu_fwd_train(2) + torch.bmm ---------------------------------------
+    c2 = []
+    for net in (0, 1):
+        p = P[net]
+        y, cache, rm, rv = O.bn_train_forward(G2[net] + p["b2"], p["g2"], p["be2"], bn0[net, 2], bn0[net, 3])
+        ref = np.maximum(y, 0)
+        rep.add("f2.a2", np.abs(A2[net, :, :H] - ref), ACT_TOL * ref + ACT_TOL, f"A2 net {net}")
+        _check_stats(rep, "f2", smean, sinv, bn1, 1, net, cache, rm, rv)
+        c2.append(cache)
+        if net == 0:
+            tau = _kink_tau(p["g2"], p["be2"], cache, np.abs(G2[0]) + np.abs(p["b2"]) + np.abs(cache["mean"]))
+            flips = (A2[0, :, :H] > 0) != (y > 0)
+            rep.add("f2.mask", np.abs(y[flips]), tau[flips], "A2's mask unlike float64's beyond rounding")
+            amb += int((np.abs(y)[:, :h] <= tau[:, :h]).sum())
+    rep.meta["ambiguous"] = amb
+    exact("f2.ones", (A2[:, :, H] == 1).all() and not A2[:, :, H + 1:].any(), "A2's constant-1 column and the zeros behind it")
+    Whm, Wht = P[0]["Wh"], P[1]["Wh"]
+    v = A + T
+    if s3:
+        hp, vp = np.asarray(dev["heads_partial"], np.float32), np.asarray(dev["vnext_partial"], np.float32)
+        assert hp.shape == (d.n_slabs, B, NHP) and vp.shape == (d.n_slabs, B) and d.n_slabs == H // 8
+        heads, vn = _f64(slab_sum_f32(hp)), _f64(slab_sum_f32(vp))
+        a2m, a2t = A2[0, :, :H], A2[1, :, :H]
+        rep.add("f2.heads", np.abs(heads - (a2m @ Whm[:, :H].T + Whm[:, H])), (H + 3) * U * (a2m @ np.abs(Whm[:, :H]).T + np.abs(Whm[:, H])),
+                "the slab-order sum of heads_partial")
+        rep.add("f2.vnext", np.abs(vn - (a2t @ Wht[v, :H] + Wht[v, H])), (H + 3) * U * (a2t @ np.abs(Wht[v, :H]) + abs(Wht[v, H])),
+                "the slab-order sum of vnext_partial against the TARGET's value row")
+    else:
+        Gh = _f64(dev["Gh"])
+        assert Gh.shape == (2, B, NHP)
+        for net in (0, 1):
+            w = P[net]["Wh"]
+            rep.add("f2.gh", np.abs(Gh[net] - A2[net] @ w.T), (HP + 2) * U * (np.abs(A2[net]) @ np.abs(w).T), f"Gh net {net}")
+        heads, vn = Gh[0], Gh[1][:, v]
+
+    # ---- head: naf_head_fwd_bwd_mse_splitk | naf_head_fwd_bwd_mse (naf_head_wide.hip beyond 8 joints) -----------------------------------
+    _check_head(rep, "hd", d, heads[:, :A], heads[:, A:v], heads[:, v], vn, 0.0, ac, rw, dev["q"], dev["loss"], dH)
+
+    # ---- layer 2 backward: naf_heads_bwd_bn_relu_bwd | torch.mm + naf_bn_relu_bwd(2) ------------------------------------------------------
+    grad = {k: _f64(dev["grad"][k]) for k in PARAMS}
+    gnorm2 = float(sum((g ** 2).sum() for g in grad.values()))
+    gnorm = gnorm2 ** 0.5
+    on2 = A2[0, :, :H] > 0
+    if b2:
+        dy2 = (dH @ Whm[:, :H]) * on2
+        E_dy = (NHP + 2) * U * (np.abs(dH) @ np.abs(Whm[:, :H])) * on2
+    else:
+        dA2 = _f64(dev["dA2"])
+        assert dA2.shape == (B, HP)
+        rep.add("b2.da2", np.abs(dA2 - dH @ Whm), (NHP + 2) * U * (np.abs(dH) @ np.abs(Whm)), "dA2")
+        dy2, E_dy = dA2[:, :H] * on2, np.zeros((B, H))
+    mean2, inv2, b2v = smean[1, 0], sinv[1, 0], P[0]["b2"]
+    xh2 = (G2[0] + b2v - mean2) * inv2
+    xe2 = 3 * U * (np.abs(G2[0]) + np.abs(b2v) + np.abs(mean2)) * inv2
+    S1, S2, E1, E2, dz2, tz2 = _bn_bwd_ref(dy2, E_dy, xh2, xe2, P[0]["g2"] * inv2, B)
+    rep.add("b2.dz2", np.abs(dZ2 - dz2), tz2, "dZ2")
+    rep.add("b2.g2", np.abs(grad["g2"] - S2), E2, "grad g2")
+    rep.add("b2.be2", np.abs(grad["be2"] - S1), E1, "grad be2")
+    rep.add("b2.bias0", np.abs(grad["b2"]), np.maximum(BIAS0_REL * gnorm, SUM_ABS_RTOL * np.abs(dZ2).sum(0)), "grad b2 = 0 to rounding")
+
+    # ---- the bundle (naf_gemm_bundle, three products) | three torch.mm ----------------------------------------------------------------------
+    rep.add("gb.gwh", np.abs(grad["Wh"] - dH.T @ A2[0]), (B + 2) * U * (np.abs(dH).T @ np.abs(A2[0])), "grad Wh, the bias column included")
+    rep.add("gb.gw2", np.abs(grad["W2"] - dZ2.T @ A1[0]), (B + 2) * U * (np.abs(dZ2).T @ np.abs(A1[0])), "grad W2")
+    rep.add("gb.da1", np.abs(dA1 - dZ2 @ P[0]["W2"]), (H + 2) * U * (np.abs(dZ2) @ np.abs(P[0]["W2"])), "dA1")
+
+    # ---- layer 1 backward: naf_bn_relu_bwd_wgrad_push (push = None) | naf_bn_relu_bwd(1) + torch.mm -----------------------------------------
+    p0 = P[0]
+    mean1, inv1 = smean[0, 0], sinv[0, 0]
+    dy1 = dA1 * (A1[0] > 0)
+    if l1:
+        z1 = x[0] @ p0["W1"].T + p0["b1"]
+        xe1 = (S + 4) * U * (np.abs(x[0]) @ np.abs(p0["W1"]).T + np.abs(p0["b1"]) + np.abs(mean1)) * inv1
+    else:
+        G1m = _f64(dev["G1"])[0]
+        z1 = G1m + p0["b1"]
+        xe1 = 3 * U * (np.abs(G1m) + np.abs(p0["b1"]) + np.abs(mean1)) * inv1
+    xh1 = (z1 - mean1) * inv1
+    S1, S2, E1, E2, dz1, tz1 = _bn_bwd_ref(dy1, np.zeros((B, H)), xh1, xe1, p0["g1"] * inv1, B)
+    rep.add("b1.g1", np.abs(grad["g1"] - S2), E2, "grad g1")
+    rep.add("b1.be1", np.abs(grad["be1"] - S1), E1, "grad be1")
+    ax = np.abs(x[0])
+    if l1:
+        rep.add("b1.gw1", np.abs(grad["W1"] - dz1.T @ x[0]), (B + 2) * U * (np.abs(dz1).T @ ax) + tz1.T @ ax, "grad W1")
+        dz1_abs = np.abs(dz1)
+    else:
+        dZ1 = _f64(dev["dZ1"])
+        rep.add("b1.dz1", np.abs(dZ1 - dz1), tz1, "dZ1")
+        rep.add("b1.gw1", np.abs(grad["W1"] - dZ1.T @ x[0]), (B + 2) * U * (np.abs(dZ1).T @ ax), "grad W1")
+        dz1_abs = np.abs(dZ1)
+    rep.add("b1.bias0", np.abs(grad["b1"]), np.maximum(BIAS0_REL * gnorm, SUM_ABS_RTOL * dz1_abs.sum(0)), "grad b1 = 0 to rounding")
+
+    # ---- the norm partials (folded into the producers | naf_grad_norm_partials) and the step count --------------------------------------------
+    rep.add("nm.sumsq", abs(float(dev["sumsq"]) - gnorm2), NORM_SELF_RTOL * gnorm2, "sum(partials) against ||grad||^2")
+    exact("nm.step", int(dev["step"]) == int(pre["step"]) + 1, "the step count advanced by exactly 1")
+
+    # ---- padding: the pad columns of a layer stored padded stay exactly 0 in every output -------------------------------------------------------
+    if h != H:
+        zero = [A1[:, :, h:], G2[:, :, h:], A2[:, :, h:H], dZ2[:, h:], dA1[:, h:], grad["W1"][h:], grad["g1"][h:], grad["be1"][h:],
+                grad["b1"][h:], grad["W2"][h:], grad["W2"][:, h:], grad["g2"][h:], grad["be2"][h:], grad["b2"][h:], grad["Wh"][:, h:H]]
+        zero += [_f64(dev[k])[..., h:H] for k in ("G1", "dZ1", "dA2") if dev.get(k) is not None]
+        exact("pad_cols", not any(z.any() for z in zero), "pad columns of a layer stored padded")
+    return rep
+
+
+def f32_standin_tiles(pre: dict, batch, d: Dims, defect: str | None = None) -> dict:
+    """What check_tile_launches() reads from a device, computed in float32 numpy from the same state, launch after launch, each
+    from the previous one's float32 output. defect: None or one of TILE_DEFECTS, a chain that is wrong in one way:
+      target_bn2_from_main        layer 2 normalises the target network with the main network's gamma2 / beta2
+      target_w2_from_main         GEMM 2 multiplies the target network's A1 with the main network's W2
+      target_vrow_from_main       V' from the main network's value row (and bias) on the target's A2
+      mask_no_beta1 | 2           the backward's ReLU mask of that layer is xhat gamma > 0 instead of the stored activation > 0
+      vnext_from_state            the target network reads `state` instead of `next_state`
+      k1_no_gamma                 layer 2's backward with k1 = invstd instead of gamma invstd
+      bn2_stats_in_layer1_slots   layer 2 writes its running statistics into layer 1's slots
+      target_stats_in_main_slots  both networks write their running statistics to the main network's slots
+      biased_running_var          running_var takes the biased variance
+      momentum_on_old             running statistics = momentum x old + (1 - momentum) x batch
+      gwh_no_bias_column          grad Wh without its column H (the head biases)
+      slab_twice                  the split-K head adds slab 1 twice (s3 only)
+      last_phase_dropped          the batch mean's sum leaves out the rows of the last, partial pass over the row phases"""
+    assert defect is None or defect in TILE_DEFECTS, defect
+    f = np.float32
+    S, A, T, H, B, HP, NHP = d.S, d.A, d.T, d.H, d.B, d.HP, d.NHP
+    l1, b2, s3 = ("l1" in d.fuse), ("b2" in d.fuse), ("s3" in d.fuse)
+    st, ac, rw, ns = batch
+    xs = [np.asarray(st, f), np.asarray(st if defect == "vnext_from_state" else ns, f)]
+    P = [{k: np.asarray(v, f) for k, v in pre["net"][n].items()} for n in (0, 1)]
+    bn0 = np.asarray(pre["bn"], f)
+    bn = bn0.copy()
+    mom_, one, eps = f(BN_MOMENTUM), f(1.0), f(O.BN_EPS)
+    out = {"save_mean": np.zeros((2, 2, H), f), "save_invstd": np.zeros((2, 2, H), f)}
+
+    def bn_fwd(z, gamma, beta, net, layer):
+        if defect == "last_phase_dropped":
+            mean = (z[:((B - 1) // bn_row_phases(B)) * bn_row_phases(B)].sum(0) / f(B)).astype(f)
+        else:
+            mean = z.mean(axis=0)
+        var = ((z - mean) ** 2).mean(axis=0)
+        invstd = (one / np.sqrt(var + eps)).astype(f)
+        xhat = (z - mean) * invstd
+        y = xhat * gamma + beta
+        unb = var if (defect == "biased_running_var" or B == 1) else var * f(B / (B - 1))
+        old_m, old_v = bn0[net, 2 * layer], bn0[net, 2 * layer + 1]
+        if defect == "momentum_on_old":
+            rm, rv = mom_ * old_m + (one - mom_) * mean, mom_ * old_v + (one - mom_) * unb
+        else:
+            rm, rv = (one - mom_) * old_m + mom_ * mean, (one - mom_) * old_v + mom_ * unb
+        slot = 0 if defect == "target_stats_in_main_slots" else net
+        ls = 0 if defect == "bn2_stats_in_layer1_slots" else layer
+        bn[slot, 2 * ls], bn[slot, 2 * ls + 1] = rm.astype(f), rv.astype(f)
+        out["save_mean"][layer, net], out["save_invstd"][layer, net] = mean, invstd
+        assert y.dtype == f
+        return y, {"mean": mean, "invstd": invstd, "xhat": xhat}
+
+    G1, A1, G2, A2 = np.zeros((2, B, H), f), np.zeros((2, B, H), f), np.zeros((2, B, H), f), np.zeros((2, B, HP), f)
+    A2[:, :, H] = 1.0
+    c1, c2 = [], []
+    for net in (0, 1):
+        p = P[net]
+        G1[net] = xs[net] @ p["W1"].T
+        y, cache = bn_fwd(G1[net] + p["b1"], p["g1"], p["be1"], net, 0)
+        A1[net] = np.maximum(y, 0)
+        c1.append(cache)
+    for net in (0, 1):
+        W2 = P[0]["W2"] if (net == 1 and defect == "target_w2_from_main") else P[net]["W2"]
+        G2[net] = A1[net] @ W2.T
+        src = P[0] if (net == 1 and defect == "target_bn2_from_main") else P[net]
+        y, cache = bn_fwd(G2[net] + P[net]["b2"], src["g2"], src["be2"], net, 1)
+        A2[net, :, :H] = np.maximum(y, 0)
+        c2.append(cache)
+    Whm = P[0]["Wh"]
+    Wv = (P[0] if defect == "target_vrow_from_main" else P[1])["Wh"][A + T]
+    if s3:
+        n = H // 8
+        hp, vp = np.zeros((n, B, NHP), f), np.zeros((n, B), f)
+        for w in range(n):
+            c = slice(8 * w, 8 * w + 8)
+            hp[w] = A2[0][:, c] @ Whm[:, c].T + (Whm[:, H] if w == 0 else f(0))
+            vp[w] = A2[1][:, c] @ Wv[c] + (Wv[H] if w == 0 else f(0))
+        out.update(heads_partial=hp, vnext_partial=vp, Gh=None)
+        heads = slab_sum_f32(np.concatenate([hp[:2], hp[1:]]) if defect == "slab_twice" else hp)
+        vn = slab_sum_f32(vp)
+    else:
+        Gh = np.stack([A2[net] @ P[net]["Wh"].T for net in (0, 1)]).astype(f)
+        Gh[1][:, A + T] = A2[1] @ Wv
+        out.update(heads_partial=None, vnext_partial=None, Gh=Gh)
+        heads, vn = Gh[0], Gh[1][:, A + T]
+    mu_pre, l_pre, V = heads[:, :A], heads[:, A:A + T], heads[:, A + T]
+    u, r = np.asarray(ac, f), np.asarray(rw, f).reshape(-1)
+    Q = O.head_forward(mu_pre, l_pre, V, u, d.p_mode)["Q"]
+    err = Q - (r + f(d.gamma) * vn)
+    dq = (f(2.0) * err / f(B)).astype(f)
+    d_mu, d_l, d_V = O.head_backward(mu_pre, l_pre, u, dq, d.p_mode)
+    dH = np.zeros((B, NHP), f)
+    dH[:, :A], dH[:, A:A + T], dH[:, A + T] = d_mu, d_l, d_V
+    grad = {k: np.zeros_like(P[0][k]) for k in PARAMS}
+    grad["Wh"] = dH.T @ A2[0]
+    if defect == "gwh_no_bias_column":
+        grad["Wh"][:, H] = 0
+    dA2 = dH @ Whm
+
+    def bn_bwd(d_out, act, cache, gamma, no_beta, no_gamma=False):
+        mask = (cache["xhat"] * gamma > 0) if no_beta else (act > 0)
+        dy = d_out * mask
+        s1, s2 = dy.sum(0), (dy * cache["xhat"]).sum(0)
+        k1 = cache["invstd"] if no_gamma else gamma * cache["invstd"]
+        dz = (k1 * (dy - s1 / f(B) - cache["xhat"] * (s2 / f(B)))).astype(f)
+        return dz, s2, s1, dz.sum(0)
+
+    dZ2, grad["g2"], grad["be2"], grad["b2"] = bn_bwd(dA2[:, :H], A2[0][:, :H], c2[0], P[0]["g2"], defect == "mask_no_beta2",
+                                                      defect == "k1_no_gamma")
+    grad["W2"] = dZ2.T @ A1[0]
+    dA1 = dZ2 @ P[0]["W2"]
+    dZ1, grad["g1"], grad["be1"], grad["b1"] = bn_bwd(dA1, A1[0], c1[0], P[0]["g1"], defect == "mask_no_beta1")
+    grad["W1"] = dZ1.T @ xs[0]
+    for k, v in grad.items():
+        assert v.dtype == f and v.shape == P[0][k].shape, k
+    out.update(A1=A1, G1=None if l1 else G1, G2=G2, A2=A2, bn=bn, q=Q, loss=float((err.astype(np.float64) ** 2).mean()), dH=dH,
+               dA2=None if b2 else dA2, dZ2=dZ2, dA1=dA1, dZ1=None if l1 else dZ1, grad=grad,
+               sumsq=float(f(sum(float((v.astype(np.float64) ** 2).sum()) for v in grad.values()))), step=int(pre["step"]) + 1)
     return out

@@ -69,10 +69,12 @@ def _linears(S, A, H, seed):
     return sd
 
 
-def launch_state(case: Case, seed: int | None = None):
+def launch_state(case: Case, seed: int | None = None, value_scale: float = 1.0):
     """(main, target): two state dicts in the reference's layout (width case.H, as learn_cases.init_state) from DIFFERENT seeds —
     every weight differs — whose four BatchNorm layers each have their own draws of weight ~ U(0.5, 1.5), bias ~ N(0, 0.3),
-    running_mean ~ N(0, 0.3), running_var ~ U(0.5, 2) (as test_policy_act_one_launch_matches_seven_launch_path draws them)."""
+    running_mean ~ N(0, 0.3), running_var ~ U(0.5, 2) (as test_policy_act_one_launch_matches_seven_launch_path draws them).
+    value_scale: both networks' value.weight and value.bias times this power of two (tests/tilechain_cases.py: with many joints
+    the quadratic term of Q dwarfs V at torch's init, and a check of the target's V' would pass because V' is negligible)."""
     seed = SEEDS.get(case.name, DEFAULT_SEED) if seed is None else seed
     out = []
     for net in (0, 1):
@@ -84,6 +86,9 @@ def launch_state(case: Case, seed: int | None = None):
             sd[f"{b}.running_mean"] = rng.normal(0, 0.3, case.H).astype(np.float32)
             sd[f"{b}.running_var"] = rng.uniform(0.5, 2.0, case.H).astype(np.float32)
             sd[f"{b}.num_batches_tracked"] = np.array(0)
+        if value_scale != 1.0:
+            sd["value.weight"] = (sd["value.weight"] * np.float32(value_scale)).astype(np.float32)
+            sd["value.bias"] = (sd["value.bias"] * np.float32(value_scale)).astype(np.float32)
         out.append(sd)
     return out[0], out[1]
 
